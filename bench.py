@@ -19,7 +19,16 @@ The one collective of the data path is a single RCCL all-reduce of the cost scal
 (SURVEY 8e), issued through the C ABI on the device-resident scalars (vch_comm_allreduce_cost;
 `--collective torch` uses torch.distributed on a host copy instead).
 
-One JSON line is printed by rank 0.  Extra objects:
+A plain run sets up, warms up, times the K steps, writes the last step's outputs when --dump-outputs DIR is given
+and prints one JSON line (rank 0); `ms_per_step` is the wall time of one timed step.  --dump-outputs writes what the
+timed path returned in its last step as DIR/<name>.npy (float64; with several ranks each rank writes rank<r>.<name>.npy):
+  cost, alpha, change, tracking_error, terminal_error, attempts   one entry per trajectory (pgd_iterate's result)
+  cost_allreduce                                                  the step's all-reduced {J1, J2, J3, J4, J} sums
+  u_sample, phi_sample                                            the control and state histories, every trajectory at
+                                                                  the same fixed, seeded sample of (time level, node)
+                                                                  positions (32 MiB in all over the two)
+The inputs (seeds 42+i, targets) are fixed, so two builds can be compared output for output.
+Everything else moves behind --full (off by default), which adds to the same line:
   roofline      the dominant kernel: algorithmic bytes per launch / mean duration of its LIVE launches, measured with
                 HIP event pairs on the engine's stream(s) during ONE extra PGD iteration in which every context
                 of the rank runs (the same contention as the timed region), the pair's own cost calibrated on an
@@ -123,6 +132,10 @@ def parse():
     ap.add_argument("--contexts", type=int, default=2,
                     help="engine contexts (HIP streams, one host thread each) the per-GPU batch is split over")
     ap.add_argument("--collective", choices=["cabi", "torch"], default="cabi")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the roofline iteration and the CPU baseline (each can be left out with --no-...)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--cpu-grid", type=int, default=None, help="grid of the CPU sample (default: --grid)")
@@ -130,7 +143,10 @@ def parse():
     ap.add_argument("--dry-run", action="store_true",
                     help="tests only: gloo + a stand-in engine, exercises the multi-rank skeleton without a GPU")
     ap.add_argument("--dry-run-fail-rank", type=int, default=-1, help="tests only: this rank's stand-in engine raises")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 def cpu_baseline(N, dt, M, n_steps):
@@ -155,6 +171,37 @@ def source_hash():
     return L.source_hash()
 
 
+DUMP_SAMPLE_ENTRIES = 1 << 21     # entries of each sampled history over all trajectories of all ranks (2 x 16 MiB in f64)
+DUMP_SAMPLE_SEED = 20240601
+
+
+def dump_outputs(dirname, last, engs, world, rank):
+    """--dump-outputs: the last timed step's results (module docstring).  `last` = (per-context pgd_iterate results,
+    all-reduced cost sums) of that step.  The histories are copied to the host one context at a time and sampled at
+    positions drawn once from a fixed seed, the same for every trajectory, so repeated runs sample the same nodes."""
+    os.makedirs(dirname, exist_ok=True)
+    prefix = f"rank{rank}." if world > 1 else ""
+    rs, Jsum = last
+    arrays = {"cost_allreduce": np.asarray(Jsum, dtype=np.float64).reshape(-1)}
+    for k in ("cost", "alpha", "change", "tracking_error", "terminal_error", "attempts"):
+        arrays[k] = np.concatenate([r[k][:, 0] for r in rs]).astype(np.float64)
+    B = sum(e.B for e in engs)
+    per_traj = max(1, DUMP_SAMPLE_ENTRIES // (B * max(world, 1)))
+    for what in ("u", "phi"):
+        parts, idx = [], None
+        for e in engs:
+            h = np.asarray(e.pgd_get(what)).reshape(e.B, -1)      # (trajectories, levels x nodes)
+            if idx is None:
+                n = h.shape[1]
+                idx = (np.arange(n) if n <= per_traj else
+                       np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, per_traj, replace=False)))
+            parts.append(h[:, idx].astype(np.float64))
+            del h
+        arrays[what + "_sample"] = np.concatenate(parts)
+    for name, arr in arrays.items():
+        np.save(os.path.join(dirname, prefix + name + ".npy"), np.ascontiguousarray(arr))
+
+
 class DryEngine:
     """Stand-in for Engine2D in --dry-run (tests of the multi-rank skeleton on CPU): same methods, no arithmetic."""
     uses_fft = True
@@ -174,6 +221,9 @@ class DryEngine:
         c = np.full((self.B, n), 1.0 / self.k)
         return dict(iters=n, cost=c, alpha=c, attempts=np.zeros((self.B, n), dtype=np.int32), change=c, tracking_error=c,
                     terminal_error=c, seconds=dict(backward=0.0, gradprox=0.0, optimistic_forward=0.02, cost=0.0, backtracking=0.0))
+
+    def pgd_get(self, what):
+        return np.full((self.B, 3, 2, 2), 1.0 / max(self.k, 1))
 
     def prof_begin(self, n):
         pass
@@ -373,7 +423,8 @@ def run(a, world, rank, local, dist):
             outs.append(dict(cost_sum=float(Jsum[4]), attempts=int(sum(int(x["attempts"].sum()) for x in rs)),
                              attempts_list=[int(v) for x in rs for v in x["attempts"][:, 0]],
                              iters=[int(x["iters"]) for x in rs],
-                             seconds={kk: max(x["seconds"][kk] for x in rs) for kk in rs[0]["seconds"]}))
+                             seconds={kk: max(x["seconds"][kk] for x in rs) for kk in rs[0]["seconds"]},
+                             results=(rs, Jsum)))
         for th in ths:
             th.join()
         return outs
@@ -387,8 +438,10 @@ def run(a, world, rank, local, dist):
     buckets = {}
     attempts = 0
     attempts_per_step = []
+    last = None
     for r in run_iterations(a.steps):               # synchronous: returns when the devices are done
         assert all(i == 1 for i in r["iters"]), "a context ran no iteration (all of its trajectories have stopped)"
+        last = r["results"]
         costs.append(r["cost_sum"])
         attempts += r["attempts"]
         attempts_per_step.append(r["attempts_list"])
@@ -399,10 +452,12 @@ def run(a, world, rank, local, dist):
     c1 = [e.counters() for e in engs]
     total_traj = B * max(world, 1)
     value = a.steps * total_traj / el
+    if a.dump_outputs:                              # before the roofline leg, whose extra iteration moves the iterate on
+        dump_outputs(a.dump_outputs, last, engs, world, rank)
 
     roof = None
     extra = {}
-    if rank == 0 and not a.no_roofline and not a.dry_run:
+    if rank == 0 and a.full and not a.no_roofline and not a.dry_run:
         # one extra iteration with an event pair around every profiled launch, ALL contexts of this rank running
         # (the contention of the timed region); the other ranks wait at the barrier below
         on_all(lambda k, e: e.prof_begin(400000))
@@ -497,7 +552,7 @@ def run(a, world, rank, local, dist):
     par.barrier(dist, dev)        # every rank leaves the measurement together (rank 0 has done its profiled iteration)
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and not a.dry_run:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline and not a.dry_run:
         cpu = cpu_baseline(a.cpu_grid or N, dt, M, a.cpu_steps)
 
     if rank == 0:

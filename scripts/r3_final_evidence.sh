@@ -17,8 +17,8 @@ cp profiles/live_stats_contexts2.txt profiles/live_stats_contexts1.txt profiles/
 bash scripts/pmc_traffic.sh > $OUT/pmc.log 2>&1
 cp gpurun_out/pmc/summary.json profiles/pmc_traffic.json
 cp gpurun_out/pmc/summary.json $OUT/pmc_traffic.json
-python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_steps20_warmup5.json 2> $OUT/bench_steps20_warmup5.err
+python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
+python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline > $OUT/bench_steps20_warmup5.json 2> $OUT/bench_steps20_warmup5.err
 python scripts/run_configs.py 2 3 5 > $OUT/configs_2_3_5.json 2> $OUT/configs.err
 python scripts/r3_config5_probe.py 100 > $OUT/config5_probe.txt 2>&1
 tail -c 600 $OUT/bench_steps20_warmup5.json

@@ -643,7 +643,7 @@ def test_bench_prints_exactly_one_json_line():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--grid", "64", "--time-steps", "20", "--batch-per-gpu", "2",
-                        "--contexts", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+                        "--contexts", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"],
                        cwd=root, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = r.stdout.splitlines()
