@@ -35,6 +35,27 @@ static inline int vch_fail(int code, const char *fmt, ...) {
         int r_ = (call);               \
         if (r_ < 0) return r_;         \
     } while (0)
+#define CTXCHK(c)                                                             \
+    do {                                                                      \
+        if (!(c)) return vch_fail(VCH_ERR_ARG, "%s: NULL context", __func__); \
+        HIPCHK(hipSetDevice((c)->device));                                    \
+    } while (0)
+#define ARGCHK(cond, msg)                                                   \
+    do {                                                                    \
+        if (!(cond)) return vch_fail(VCH_ERR_ARG, "%s: %s", __func__, msg); \
+    } while (0)
+// Launch on the stream of the context `c` in scope, `lds` bytes of dynamic LDS; a failed launch fails the calling function.
+// launch_begin / launch_end are the engine's bookkeeping around it (profiling class cls, -1 = none).
+#define LAUNCH_LDS(cls, kern, grid, block, lds, ...)                                         \
+    do {                                                                                    \
+        const bool rec_ = launch_begin(c, cls);                                             \
+        hipLaunchKernelGGL(kern, grid, block, lds, c->stream, __VA_ARGS__);                 \
+        launch_end(c, cls, rec_);                                                           \
+        hipError_t e_ = hipGetLastError();                                                  \
+        if (e_ != hipSuccess)                                                               \
+            return vch_fail(VCH_ERR_HIP, "launch %s: %s", #kern, hipGetErrorString(e_));    \
+    } while (0)
+#define LAUNCH(kern, grid, block, ...) LAUNCH_LDS(-1, kern, grid, block, 0, __VA_ARGS__)
 
 // ----------------------------------------------------------------------------------
 // geometry of one padded plane in HBM

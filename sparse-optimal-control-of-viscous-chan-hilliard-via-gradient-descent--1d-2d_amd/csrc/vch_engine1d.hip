@@ -37,22 +37,9 @@ struct vch1d_ctx {
     int pgd_err_n = 0;
 };
 
-#define LAUNCH1(kern, grid, block, lds, ...)                                       \
-    do {                                                                           \
-        hipLaunchKernelGGL(kern, grid, block, lds, c->stream, __VA_ARGS__);        \
-        hipError_t e_ = hipGetLastError();                                         \
-        if (e_ != hipSuccess)                                                      \
-            return vch_fail(VCH_ERR_HIP, "launch %s: %s", #kern, hipGetErrorString(e_)); \
-    } while (0)
-#define CTXCHK1(c)                                                        \
-    do {                                                                  \
-        if (!(c)) return vch_fail(VCH_ERR_ARG, "%s: NULL context", __func__); \
-        HIPCHK(hipSetDevice((c)->device));                                \
-    } while (0)
-#define ARGCHK1(cond, msg)                                            \
-    do {                                                              \
-        if (!(cond)) return vch_fail(VCH_ERR_ARG, "%s: %s", __func__, msg); \
-    } while (0)
+// no launch bookkeeping (LAUNCH_LDS, vch_common.h)
+static bool launch_begin(vch1d_ctx *, int) { return false; }
+static void launch_end(vch1d_ctx *, int, bool) {}
 
 static int dalloc1(double **p, size_t n, hipStream_t s) {
     *p = nullptr;
@@ -165,22 +152,22 @@ extern "C" void vch1d_destroy(vch1d_ctx *c) {
 }
 
 extern "C" int vch1d_apply_laplacian(vch1d_ctx *c, const double *v, double *out) {
-    CTXCHK1(c);
-    ARGCHK1(v && out, "NULL array");
+    CTXCHK(c);
+    ARGCHK(v && out, "NULL array");
     const size_t bn = (size_t)c->B * c->n;
     VCHCHK(up(c, c->tmp[0], v, bn));
-    LAUNCH1(k1d_lap, dim3((c->n + 255) / 256, c->B), dim3(256), 0, c->n, 1.0 / (c->h * c->h), (const double *)c->tmp[0], c->tmp[1]);
+    LAUNCH(k1d_lap, dim3((c->n + 255) / 256, c->B), dim3(256), c->n, 1.0 / (c->h * c->h), (const double *)c->tmp[0], c->tmp[1]);
     return down(c, out, c->tmp[1], bn);
 }
 
 extern "C" int vch1d_residuals(vch1d_ctx *c, const double *pn, const double *po, const double *mn, const double *mo,
                                const double *wn, const double *wo, double dt, double *Rp, double *Rm) {
-    CTXCHK1(c);
-    ARGCHK1(pn && po && mn && mo && wn && wo && Rp && Rm && dt > 0, "NULL array or dt <= 0");
+    CTXCHK(c);
+    ARGCHK(pn && po && mn && mo && wn && wo && Rp && Rm && dt > 0, "NULL array or dt <= 0");
     const size_t bn = (size_t)c->B * c->n;
     const double *src[6] = {pn, po, mn, mo, wn, wo};
     for (int k = 0; k < 6; ++k) VCHCHK(up(c, c->tmp[k], src[k], bn));
-    LAUNCH1(k1d_residuals, dim3((c->n + 255) / 256, c->B), dim3(256), 0, c->P, c->n, 1.0 / (c->h * c->h), dt,
+    LAUNCH(k1d_residuals, dim3((c->n + 255) / 256, c->B), dim3(256), c->P, c->n, 1.0 / (c->h * c->h), dt,
             (const double *)c->tmp[0], (const double *)c->tmp[1], (const double *)c->tmp[2], (const double *)c->tmp[3],
             (const double *)c->tmp[4], (const double *)c->tmp[5], c->tmp[6], c->tmp[7]);
     VCHCHK(down(c, Rp, c->tmp[6], bn));
@@ -189,28 +176,28 @@ extern "C" int vch1d_residuals(vch1d_ctx *c, const double *pn, const double *po,
 
 extern "C" int vch1d_jacobian_solve(vch1d_ctx *c, const double *phi_new, double dt, const double *rhs_phi,
                                     const double *rhs_mu, double *dphi, double *dmu) {
-    CTXCHK1(c);
-    ARGCHK1(phi_new && rhs_phi && rhs_mu && dphi && dmu && dt > 0, "NULL array or dt <= 0");
+    CTXCHK(c);
+    ARGCHK(phi_new && rhs_phi && rhs_mu && dphi && dmu && dt > 0, "NULL array or dt <= 0");
     const size_t bn = (size_t)c->B * c->n;
     VCHCHK(up(c, c->tmp[0], phi_new, bn));
     VCHCHK(up(c, c->tmp[1], rhs_phi, bn));
     VCHCHK(up(c, c->tmp[2], rhs_mu, bn));
     SysArgs A{nullptr, nullptr, nullptr, dt, 1.0 / (c->h * c->h), c->P.tau, c->P.c1, c->P.c2, c->P.kappa, c->n};
-    LAUNCH1((k1d_solve<0>), dim3(c->B), dim3(T1), c->lds_bytes, A, c->lvl, (const double *)c->tmp[0], (const double *)c->tmp[1],
+    LAUNCH_LDS(-1, (k1d_solve<0>), dim3(c->B), dim3(T1), c->lds_bytes, A, c->lvl, (const double *)c->tmp[0], (const double *)c->tmp[1],
             (const double *)c->tmp[2], c->tmp[3], c->tmp[4]);
     VCHCHK(down(c, dphi, c->tmp[3], bn));
     return down(c, dmu, c->tmp[4], bn);
 }
 
 extern "C" int vch1d_adjoint_solve(vch1d_ctx *c, const double *phi_n, double dt, const double *rhs, double *p_out) {
-    CTXCHK1(c);
-    ARGCHK1(rhs && p_out && dt >= 0 && (phi_n || dt == 0), "NULL array or dt < 0");
+    CTXCHK(c);
+    ARGCHK(rhs && p_out && dt >= 0 && (phi_n || dt == 0), "NULL array or dt < 0");
     const size_t bn = (size_t)c->B * c->n;
     if (phi_n) VCHCHK(up(c, c->tmp[0], phi_n, bn));
     else HIPCHK(hipMemsetAsync(c->tmp[0], 0, bn * sizeof(double), c->stream));
     VCHCHK(up(c, c->tmp[1], rhs, bn));
     SysArgs A{nullptr, nullptr, nullptr, dt, 1.0 / (c->h * c->h), c->F.tau, c->F.c1, c->F.c2, 0.0, c->n};
-    LAUNCH1((k1d_solve<1>), dim3(c->B), dim3(T1), c->lds_bytes, A, c->lvl, (const double *)c->tmp[0], (const double *)c->tmp[1],
+    LAUNCH_LDS(-1, (k1d_solve<1>), dim3(c->B), dim3(T1), c->lds_bytes, A, c->lvl, (const double *)c->tmp[0], (const double *)c->tmp[1],
             (const double *)nullptr, c->tmp[3], c->tmp[4]);
     return down(c, p_out, c->tmp[3], bn);
 }
@@ -218,8 +205,8 @@ extern "C" int vch1d_adjoint_solve(vch1d_ctx *c, const double *phi_n, double dt,
 extern "C" int vch1d_newton_raphson(vch1d_ctx *c, const double *phi_old, const double *mu_old, const double *w_old,
                                     const double *w_new, double dt, double *phi_new, double *mu_new, double *hist,
                                     int hist_cap, int32_t *n_hist) {
-    CTXCHK1(c);
-    ARGCHK1(phi_old && mu_old && w_old && w_new && phi_new && mu_new && dt > 0, "NULL array or dt <= 0");
+    CTXCHK(c);
+    ARGCHK(phi_old && mu_old && w_old && w_new && phi_new && mu_new && dt > 0, "NULL array or dt <= 0");
     const int n = c->n;
     for (int b = 0; b < c->B; ++b) {          // scratch layout: phi, mu, w, wnew are the first four arrays
         double *q = c->scratch + (size_t)b * NSCR1 * n;
@@ -228,7 +215,7 @@ extern "C" int vch1d_newton_raphson(vch1d_ctx *c, const double *phi_old, const d
         VCHCHK(up(c, q + 2 * n, w_old + (size_t)b * n, n));
         VCHCHK(up(c, q + 3 * n, w_new + (size_t)b * n, n));
     }
-    LAUNCH1(k1d_newton, dim3(c->B), dim3(T1), c->lds_bytes, c->P, n, c->h, c->lvl, dt, c->scratch, c->hist_dev, 64, c->stats_dev);
+    LAUNCH_LDS(-1, k1d_newton, dim3(c->B), dim3(T1), c->lds_bytes, c->P, n, c->h, c->lvl, dt, c->scratch, c->hist_dev, 64, c->stats_dev);
     HIPCHK(hipMemcpyAsync(c->stats_host, c->stats_dev, sizeof(int) * 8 * c->B, hipMemcpyDeviceToHost, c->stream));
     for (int b = 0; b < c->B; ++b) {
         double *q = c->scratch + (size_t)b * NSCR1 * n;
@@ -249,10 +236,10 @@ extern "C" int vch1d_newton_raphson(vch1d_ctx *c, const double *phi_old, const d
 
 extern "C" int vch1d_forward(vch1d_ctx *c, const double *phi0, const double *u, int u_rows, const double *dt, int M,
                              double *phi_hist_out, vch_stats *stats) {
-    CTXCHK1(c);
-    ARGCHK1(phi0 && dt && M >= 1 && M <= c->Mmax, "NULL array or M out of range (1..max_steps)");
+    CTXCHK(c);
+    ARGCHK(phi0 && dt && M >= 1 && M <= c->Mmax, "NULL array or M out of range (1..max_steps)");
     // F1:347-353 indexes control_input[step] for every step: fewer than M rows is an IndexError there
-    if (u) ARGCHK1(u_rows >= M && u_rows <= c->Mmax + 2, "control rows: need M <= rows <= max_steps+2 (IndexError in the reference)");
+    if (u) ARGCHK(u_rows >= M && u_rows <= c->Mmax + 2, "control rows: need M <= rows <= max_steps+2 (IndexError in the reference)");
     VCHCHK(ensure1(c, &c->phi_hist));
     if (u) {
         VCHCHK(ensure1(c, &c->u_hist));
@@ -261,7 +248,7 @@ extern "C" int vch1d_forward(vch1d_ctx *c, const double *phi0, const double *u, 
     VCHCHK(up(c, c->tmp[0], phi0, (size_t)c->B * c->n));
     VCHCHK(up(c, c->dts, dt, M));
     HIPCHK(hipEventRecord(c->ev0, c->stream));
-    LAUNCH1(k1d_forward, dim3(c->B), dim3(T1), c->lds_bytes, c->P, c->n, c->h, c->lvl, M, (const double *)c->dts,
+    LAUNCH_LDS(-1, k1d_forward, dim3(c->B), dim3(T1), c->lds_bytes, c->P, c->n, c->h, c->lvl, M, (const double *)c->dts,
             (const double *)c->tmp[0], (const double *)(u ? c->u_hist : nullptr), u_rows, hs1(c), c->phi_hist, hs1(c),
             c->scratch, c->stats_dev, (const int *)nullptr);
     HIPCHK(hipEventRecord(c->ev1, c->stream));
@@ -289,9 +276,9 @@ extern "C" int vch1d_forward(vch1d_ctx *c, const double *phi0, const double *u, 
 extern "C" int vch1d_backward(vch1d_ctx *c, const double *phi_hist, int rows, const double *t_hist, double h, double b1,
                               double b2, const double *phi_Q, const double *phi_T, double *p_out, double *q_out,
                               double *r_out) {
-    CTXCHK1(c);
-    ARGCHK1(t_hist && rows >= 2 && rows <= c->Mmax + 2, "NULL t_hist or rows out of range");
-    ARGCHK1(std::fabs(h - c->h) <= 1e-12 * c->h, "grid spacing differs from the context's Lx/N");
+    CTXCHK(c);
+    ARGCHK(t_hist && rows >= 2 && rows <= c->Mmax + 2, "NULL t_hist or rows out of range");
+    ARGCHK(std::fabs(h - c->h) <= 1e-12 * c->h, "grid spacing differs from the context's Lx/N");
     if (phi_hist) {
         VCHCHK(ensure1(c, &c->phi_hist));
         VCHCHK(up_hist(c, c->phi_hist, phi_hist, rows));
@@ -312,7 +299,7 @@ extern "C" int vch1d_backward(vch1d_ctx *c, const double *phi_hist, int rows, co
     HIPCHK(hipMemsetAsync(c->q_hist, 0, hb, c->stream));
     HIPCHK(hipMemsetAsync(c->r_hist, 0, hb, c->stream));
     VCHCHK(up(c, c->tgrid, t_hist, rows));
-    LAUNCH1(k1d_backward, dim3(c->B), dim3(T1), c->lds_bytes, c->F, c->n, c->h, c->lvl, rows, (const double *)c->tgrid,
+    LAUNCH_LDS(-1, k1d_backward, dim3(c->B), dim3(T1), c->lds_bytes, c->F, c->n, c->h, c->lvl, rows, (const double *)c->tgrid,
             (const double *)c->phi_hist, (const double *)(phi_Q ? c->phiQ : nullptr),
             (const double *)(phi_T ? c->phiT : nullptr), b1, b2, c->p_hist, c->q_hist, c->r_hist, hs1(c), c->scratch);
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -324,8 +311,8 @@ extern "C" int vch1d_backward(vch1d_ctx *c, const double *phi_hist, int rows, co
 
 extern "C" int vch1d_cost(vch1d_ctx *c, const double *phi_hist, const double *u, const double *phi_Q, const double *phi_T,
                           int rows, const double *x, const double *t_hist, const vch_opt_params *o, double *J_out) {
-    CTXCHK1(c);
-    ARGCHK1(phi_hist && x && t_hist && o && J_out && rows >= 2 && rows <= c->Mmax + 2, "NULL argument or rows out of range");
+    CTXCHK(c);
+    ARGCHK(phi_hist && x && t_hist && o && J_out && rows >= 2 && rows <= c->Mmax + 2, "NULL argument or rows out of range");
     VCHCHK(ensure1(c, &c->phi_hist));
     VCHCHK(up_hist(c, c->phi_hist, phi_hist, rows));
     c->rows_res = rows;
@@ -339,7 +326,7 @@ extern "C" int vch1d_cost(vch1d_ctx *c, const double *phi_hist, const double *u,
         wx[i + 1] += 0.5 * d;
     }
     VCHCHK(up(c, c->wx, wx.data(), c->n));
-    LAUNCH1(k1d_cost, dim3(rows, c->B), dim3(T1), 0, c->n, rows, (const double *)c->wx, (const double *)c->phi_hist,
+    LAUNCH(k1d_cost, dim3(rows, c->B), dim3(T1), c->n, rows, (const double *)c->wx, (const double *)c->phi_hist,
             (const double *)(u ? c->u_hist : nullptr), (const double *)(phi_Q ? c->phiQ : nullptr),
             (const double *)(phi_T ? c->phiT : nullptr), hs1(c), c->cost_lvl);
     VCHCHK(down(c, c->cost_host, c->cost_lvl, (size_t)c->B * rows * 4));
@@ -364,23 +351,23 @@ extern "C" int vch1d_cost(vch1d_ctx *c, const double *phi_hist, const double *u,
 
 extern "C" int vch1d_grad_prox(vch1d_ctx *c, const double *u, const double *r, int rows, const double *alpha,
                                const vch_opt_params *o, double *u_out) {
-    CTXCHK1(c);
-    ARGCHK1(u && r && alpha && o && u_out && rows >= 1 && rows <= c->Mmax + 2, "NULL argument or rows out of range");
+    CTXCHK(c);
+    ARGCHK(u && r && alpha && o && u_out && rows >= 1 && rows <= c->Mmax + 2, "NULL argument or rows out of range");
     VCHCHK(ensure1(c, &c->u_hist));
     VCHCHK(ensure1(c, &c->r_hist));
     VCHCHK(ensure1(c, &c->u_trial));
     VCHCHK(up_hist(c, c->u_hist, u, rows));
     VCHCHK(up_hist(c, c->r_hist, r, rows));
     VCHCHK(up(c, c->alpha_dev, alpha, c->B));
-    LAUNCH1(k1d_grad_prox, dim3(rows, c->B), dim3(T1), 0, c->n, (const double *)c->u_hist, (const double *)c->r_hist, hs1(c),
+    LAUNCH(k1d_grad_prox, dim3(rows, c->B), dim3(T1), c->n, (const double *)c->u_hist, (const double *)c->r_hist, hs1(c),
             (const double *)c->alpha_dev, o->b3, o->kappa_sparsity, o->u_min, o->u_max, c->u_trial, (double *)nullptr);
     return down_hist(c, u_out, c->u_trial, rows);
 }
 
 extern "C" int vch1d_free_energy(vch1d_ctx *c, const double *phi_hist, int rows, const double *w_hist, double h, double eps,
                                  double *E_out) {
-    CTXCHK1(c);
-    ARGCHK1(phi_hist && E_out && rows >= 1 && rows <= c->Mmax + 2 && h > 0, "NULL argument, rows out of range or h <= 0");
+    CTXCHK(c);
+    ARGCHK(phi_hist && E_out && rows >= 1 && rows <= c->Mmax + 2 && h > 0, "NULL argument, rows out of range or h <= 0");
     VCHCHK(ensure1(c, &c->phi_hist));
     VCHCHK(up_hist(c, c->phi_hist, phi_hist, rows));
     c->rows_res = rows;
@@ -388,7 +375,7 @@ extern "C" int vch1d_free_energy(vch1d_ctx *c, const double *phi_hist, int rows,
         VCHCHK(ensure1(c, &c->u_trial));
         VCHCHK(up_hist(c, c->u_trial, w_hist, rows));
     }
-    LAUNCH1(k1d_energy, dim3(rows, c->B), dim3(T1), 0, c->n, c->P.c1, c->P.c2, eps > 0 ? eps : 1e-8, (const double *)c->phi_hist,
+    LAUNCH(k1d_energy, dim3(rows, c->B), dim3(T1), c->n, c->P.c1, c->P.c2, eps > 0 ? eps : 1e-8, (const double *)c->phi_hist,
             (const double *)(w_hist ? c->u_trial : nullptr), hs1(c), c->cost_lvl);
     VCHCHK(down(c, c->cost_host, c->cost_lvl, (size_t)c->B * rows * 4));
     for (long k = 0; k < (long)c->B * rows; ++k) {
@@ -416,7 +403,7 @@ static void trapz_x(const vch1d_ctx *c, const double *x, std::vector<double> &wx
 static int cost1_core(vch1d_ctx *c, const double *phi_dev, const double *u_dev, int rows, double *J_out,
                       double *raw_out = nullptr /* [B][2] = {int int (phi - phi_Q)^2, int (phi_end - phi_T)^2} */) {
     const vch_opt_params *o = &c->opt;
-    LAUNCH1(k1d_cost, dim3(rows, c->B), dim3(T1), 0, c->n, rows, (const double *)c->wx, phi_dev, u_dev,
+    LAUNCH(k1d_cost, dim3(rows, c->B), dim3(T1), c->n, rows, (const double *)c->wx, phi_dev, u_dev,
             (const double *)c->phiQ, (const double *)c->phiT, hs1(c), c->cost_lvl);
     VCHCHK(down(c, c->cost_host, c->cost_lvl, (size_t)c->B * rows * 4));
     const double *t = c->t_host.data();
@@ -445,7 +432,7 @@ static int cost1_core(vch1d_ctx *c, const double *phi_dev, const double *u_dev, 
 
 // int_t int_x a^2 (rows > 1) or int_x a^2 (rows == 1) per trajectory with the cost's weights; arr [B][stride]
 static int l2sq1_core(vch1d_ctx *c, const double *arr, long stride, int rows, double *out) {
-    LAUNCH1(k1d_cost, dim3(rows, c->B), dim3(T1), 0, c->n, rows, (const double *)c->wx, arr, (const double *)nullptr,
+    LAUNCH(k1d_cost, dim3(rows, c->B), dim3(T1), c->n, rows, (const double *)c->wx, arr, (const double *)nullptr,
             (const double *)nullptr, (const double *)nullptr, stride, c->cost_lvl);
     VCHCHK(down(c, c->cost_host, c->cost_lvl, (size_t)c->B * rows * 4));
     const double *t = c->t_host.data();
@@ -461,7 +448,7 @@ static int l2sq1_core(vch1d_ctx *c, const double *arr, long stride, int rows, do
 
 static int fwd1_core(vch1d_ctx *c, const double *u_dev, int rows, double *hist_dev, const int *skip_dev) {
     const int M = rows - 2;
-    LAUNCH1(k1d_forward, dim3(c->B), dim3(T1), c->lds_bytes, c->P, c->n, c->h, c->lvl, M, (const double *)c->dts,
+    LAUNCH_LDS(-1, k1d_forward, dim3(c->B), dim3(T1), c->lds_bytes, c->P, c->n, c->h, c->lvl, M, (const double *)c->dts,
             (const double *)c->phi0_dev, u_dev, rows, hs1(c), hist_dev, hs1(c), c->scratch, c->stats_dev, skip_dev);
     HIPCHK(hipMemcpyAsync(c->stats_host, c->stats_dev, sizeof(int) * 8 * c->B, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -472,11 +459,11 @@ static int fwd1_core(vch1d_ctx *c, const double *u_dev, int rows, double *hist_d
 
 extern "C" int vch1d_pgd_init(vch1d_ctx *c, const double *phi0, const double *phi_T, const double *phi_Q, const double *x,
                               const double *t_hist, int rows, const double *dt, const vch_opt_params *opt, double *J0_out) {
-    CTXCHK1(c);
-    ARGCHK1(phi0 && phi_T && x && t_hist && dt && opt, "NULL argument");
-    ARGCHK1(rows >= 3 && rows <= c->Mmax + 2, "rows out of range (3..max_steps+2)");
+    CTXCHK(c);
+    ARGCHK(phi0 && phi_T && x && t_hist && dt && opt, "NULL argument");
+    ARGCHK(rows >= 3 && rows <= c->Mmax + 2, "rows out of range (3..max_steps+2)");
     const int B = c->B, M = rows - 2;
-    for (int k = 0; k < M; ++k) ARGCHK1(dt[k] > 0, "dt must be positive");
+    for (int k = 0; k < M; ++k) ARGCHK(dt[k] > 0, "dt must be positive");
     c->opt = *opt;
     c->pgd_rows = rows;
     c->t_host.assign(t_hist, t_hist + rows);
@@ -507,7 +494,7 @@ extern "C" int vch1d_pgd_init(vch1d_ctx *c, const double *phi0, const double *ph
         for (int k = 0; k < rows; ++k) tp[k] = t_hist[k] / Tend;
         VCHCHK(up(c, c->tp_dev, tp.data(), rows));
         HIPCHK(hipStreamSynchronize(c->stream));
-        LAUNCH1(k1d_ramp, dim3(rows, B), dim3(T1), 0, c->n, (const double *)c->tp_dev, (const double *)c->phi_hist,
+        LAUNCH(k1d_ramp, dim3(rows, B), dim3(T1), c->n, (const double *)c->tp_dev, (const double *)c->phi_hist,
                 (const double *)c->phiT, hs1(c), c->phiQ);
     }
     std::vector<double> J(5 * B);
@@ -538,9 +525,9 @@ static int copy_traj1(vch1d_ctx *c, double *dst, const double *src, int b, int r
 
 extern "C" int vch1d_pgd_iterate(vch1d_ctx *c, int n_iters, double *cost_out, double *alpha_out, int32_t *trials_out,
                                  double *change_out, double *seconds_out) {
-    CTXCHK1(c);
+    CTXCHK(c);
     if (!c->pgd_ready) return vch_fail(VCH_ERR_STATE, "vch1d_pgd_iterate: call vch1d_pgd_init first");
-    ARGCHK1(n_iters >= 1, "n_iters must be >= 1");
+    ARGCHK(n_iters >= 1, "n_iters must be >= 1");
     const int B = c->B, rows = c->pgd_rows;
     const vch_opt_params &O = c->opt;
     constexpr int MAX_LS = 5;                 // G1:74
@@ -569,7 +556,7 @@ extern "C" int vch1d_pgd_iterate(vch1d_ctx *c, int n_iters, double *cost_out, do
         HIPCHK(hipMemsetAsync(c->p_hist, 0, hb, c->stream));
         HIPCHK(hipMemsetAsync(c->q_hist, 0, hb, c->stream));
         HIPCHK(hipMemsetAsync(c->r_hist, 0, hb, c->stream));
-        LAUNCH1(k1d_backward, dim3(B), dim3(T1), c->lds_bytes, c->F, c->n, c->h, c->lvl, rows, (const double *)c->tgrid,
+        LAUNCH_LDS(-1, k1d_backward, dim3(B), dim3(T1), c->lds_bytes, c->F, c->n, c->h, c->lvl, rows, (const double *)c->tgrid,
                 (const double *)c->phi_hist, (const double *)c->phiQ, (const double *)c->phiT, O.b1, O.b2, c->p_hist, c->q_hist,
                 c->r_hist, hs1(c), c->scratch);
         HIPCHK(tick(c->ev1));
@@ -585,7 +572,7 @@ extern "C" int vch1d_pgd_iterate(vch1d_ctx *c, int n_iters, double *cost_out, do
             HIPCHK(tick(c->ev0));
             VCHCHK(up(c, c->alpha_dev, alpha.data(), B));
             HIPCHK(hipMemcpyAsync(c->skip_dev, accepted.data(), sizeof(int) * B, hipMemcpyHostToDevice, c->stream));
-            LAUNCH1(k1d_grad_prox, dim3(rows, B), dim3(T1), 0, c->n, (const double *)c->u_hist, (const double *)c->r_hist, hs1(c),
+            LAUNCH(k1d_grad_prox, dim3(rows, B), dim3(T1), c->n, (const double *)c->u_hist, (const double *)c->r_hist, hs1(c),
                     (const double *)c->alpha_dev, O.b3, O.kappa_sparsity, O.u_min, O.u_max, c->u_trial, c->chg_dev);
             VCHCHK(fwd1_core(c, c->u_trial, rows, c->phi_trial, c->skip_dev));
             VCHCHK(cost1_core(c, c->phi_trial, c->u_trial, rows, Jt.data(), raw.data()));
@@ -653,9 +640,9 @@ extern "C" int vch1d_pgd_iterate(vch1d_ctx *c, int n_iters, double *cost_out, do
 }
 
 extern "C" int vch1d_pgd_errors(vch1d_ctx *c, int n_iters, double *tracking_out, double *terminal_out) {
-    CTXCHK1(c);
+    CTXCHK(c);
     if (!c->pgd_ready) return vch_fail(VCH_ERR_STATE, "vch1d_pgd_errors: call vch1d_pgd_init first");
-    ARGCHK1(n_iters == c->pgd_err_n && n_iters >= 1, "n_iters differs from the last vch1d_pgd_iterate call");
+    ARGCHK(n_iters == c->pgd_err_n && n_iters >= 1, "n_iters differs from the last vch1d_pgd_iterate call");
     const size_t n = (size_t)c->B * n_iters;
     if (tracking_out) memcpy(tracking_out, c->pgd_trk.data(), n * sizeof(double));
     if (terminal_out) memcpy(terminal_out, c->pgd_trm.data(), n * sizeof(double));
@@ -663,8 +650,8 @@ extern "C" int vch1d_pgd_errors(vch1d_ctx *c, int n_iters, double *tracking_out,
 }
 
 extern "C" int vch1d_pgd_get(vch1d_ctx *c, int what, double *out) {
-    CTXCHK1(c);
-    ARGCHK1(out && what >= 0 && what <= 3, "NULL out or what not in 0..3");
+    CTXCHK(c);
+    ARGCHK(out && what >= 0 && what <= 3, "NULL out or what not in 0..3");
     if (!c->pgd_ready) return vch_fail(VCH_ERR_STATE, "vch1d_pgd_get: call vch1d_pgd_init first");
     const double *src = what == 0 ? c->u_hist : what == 1 ? c->phi_hist : what == 2 ? c->r_hist : c->phiQ;
     return down_hist(c, out, src, c->pgd_rows);

@@ -207,15 +207,6 @@ struct vch2d_ctx {
     long n_launch, n_sync;
 };
 
-#define LAUNCH(kern, grid, block, ...)                                             \
-    do {                                                                           \
-        hipLaunchKernelGGL(kern, grid, block, 0, c->stream, __VA_ARGS__);          \
-        c->n_launch++;                                                             \
-        hipError_t e_ = hipGetLastError();                                         \
-        if (e_ != hipSuccess)                                                      \
-            return vch_fail(VCH_ERR_HIP, "launch %s: %s", #kern, hipGetErrorString(e_)); \
-    } while (0)
-
 // Kernel classes for the in-situ timing of vch2d_prof_begin/_end.
 enum { PC_SCHUR_P = 0, PC_GEMM = 1, PC_RESIDUAL = 2, PC_ADJ_Q = 3, PC_CG_UPDATE = 4, PC_ADJ_RHS = 5, PC_COST = 6,
        PC_PROX = 7, PC_DCT_R0 = 8, PC_DCT_C = 9, PC_DCT_R3 = 10, PC_SCHUR_P1 = 11, PC_CG_ROWS = 12, PC_CG_ROWS1 = 13,
@@ -225,23 +216,22 @@ enum { PC_SCHUR_P = 0, PC_GEMM = 1, PC_RESIDUAL = 2, PC_ADJ_Q = 3, PC_CG_UPDATE 
 // an empty kernel: what an event pair measures around it is the cost of the pair itself (vch2d_prof_begin)
 __global__ void k_noop() {}
 
-// launch with an event pair around it when profiling is on (events are recorded on the
-// engine's own stream, the one the kernel is launched on)
-#define LAUNCHC(cls, kern, grid, block, ...)                                                    \
-    do {                                                                                        \
-        const bool rec_ = c->prof_on && c->prof_used + 2 <= c->prof_ev.size();                  \
-        if (rec_) hipEventRecord(c->prof_ev[c->prof_used], c->stream);                          \
-        hipLaunchKernelGGL(kern, grid, block, 0, c->stream, __VA_ARGS__);                       \
-        c->n_launch++;                                                                          \
-        if (rec_) {                                                                             \
-            hipEventRecord(c->prof_ev[c->prof_used + 1], c->stream);                            \
-            c->prof_cls.push_back(cls);                                                         \
-            c->prof_used += 2;                                                                  \
-        }                                                                                       \
-        hipError_t e_ = hipGetLastError();                                                      \
-        if (e_ != hipSuccess)                                                                   \
-            return vch_fail(VCH_ERR_HIP, "launch %s: %s", #kern, hipGetErrorString(e_));        \
-    } while (0)
+// Bookkeeping of LAUNCH_LDS (vch_common.h): every launch is counted; a launch of class cls >= 0 gets an event pair around
+// it when profiling is on (events are recorded on the engine's own stream, the one the kernel is launched on).
+static bool launch_begin(vch2d_ctx *c, int cls) {
+    const bool rec = cls >= 0 && c->prof_on && c->prof_used + 2 <= c->prof_ev.size();
+    if (rec) hipEventRecord(c->prof_ev[c->prof_used], c->stream);
+    return rec;
+}
+static void launch_end(vch2d_ctx *c, int cls, bool rec) {
+    c->n_launch++;
+    if (rec) {
+        hipEventRecord(c->prof_ev[c->prof_used + 1], c->stream);
+        c->prof_cls.push_back(cls);
+        c->prof_used += 2;
+    }
+}
+#define LAUNCHC(cls, kern, grid, block, ...) LAUNCH_LDS(cls, kern, grid, block, 0, __VA_ARGS__)
 
 static int dalloc(double **p, size_t n, hipStream_t s) {
     *p = nullptr;
@@ -607,15 +597,81 @@ extern "C" void vch2d_destroy(vch2d_ctx *c) {
 
 extern "C" int vch2d_batch(const vch2d_ctx *c) { return c ? c->B : VCH_ERR_ARG; }
 
-#define CTXCHK(c)                                                         \
-    do {                                                                  \
-        if (!(c)) return vch_fail(VCH_ERR_ARG, "%s: NULL context", __func__); \
-        HIPCHK(hipSetDevice((c)->device));                                \
-    } while (0)
-#define ARGCHK(cond, msg)                                             \
-    do {                                                              \
-        if (!(cond)) return vch_fail(VCH_ERR_ARG, "%s: %s", __func__, msg); \
-    } while (0)
+// ------------------------------------------------------------------------------------
+// FFT pass launches.  A compile-time plan is C complex doubles per workgroup (1024 unless the FFT is longer) and LOGL =
+// log2 of the FFT length, 0 for a run-time length; lengths 512 / 1024 / 2048 (grids 256^2, 512^2, 1024^2) are compiled
+// with a constant length.  with_plan calls f with the plan of `ax` as two std::integral_constant and returns its status.
+// ------------------------------------------------------------------------------------
+template <class F>
+static int with_plan(const FftAxis &ax, F &&f) {
+    using std::integral_constant;
+    if (ax.logL == 10) return f(integral_constant<int, 1024>(), integral_constant<int, 10>());
+    if (ax.logL == 9) return f(integral_constant<int, 1024>(), integral_constant<int, 9>());
+    if (ax.logL < 10) return f(integral_constant<int, 1024>(), integral_constant<int, 0>());
+    if (ax.logL == 11) return f(integral_constant<int, 2048>(), integral_constant<int, 11>());
+    return f(integral_constant<int, 4096>(), integral_constant<int, 0>());
+}
+
+// k_dct_rows<EPI> (E along the fast axis): in -> out
+template <int EPI>
+static int dct_rows(vch2d_ctx *c, const double *in, long in_slot_stride, double *out, const SpecArgs &sp, int gate) {
+    return with_plan(c->fax, [&](auto C, auto LG) {
+        const int rpw = 2 * (C >> c->fax.logL);
+        LAUNCHC(EPI >= 3 ? PC_DCT_R3 : PC_DCT_R0, (k_dct_rows<EPI, C, LG>), dim3((c->G.ns + rpw - 1) / rpw, 1, c->B),
+                dim3(FftThreads<C, LG>::T), c->G, c->fax, in, in_slot_stride, out, 1.0, sp, c->st, gate);
+        return 0;
+    });
+}
+
+// k_dct_cols (E along the slow axis, spectral multiplier, E again): c->t1 -> c->t2
+template <int C, int LOGL>
+static int dct_cols_plan(vch2d_ctx *c, const SpecArgs &sp, double scale, int gate) {
+    const int cpw = 2 * (C >> c->sax.logL);
+    LAUNCHC(PC_DCT_C, (k_dct_cols<C, LOGL>), dim3((c->G.nf + cpw - 1) / cpw, 1, c->B), dim3(FftThreads<C, LOGL>::T), c->G,
+            c->sax, (const double *)c->t1, c->t2, scale, sp, c->st, gate);
+    return 0;
+}
+static int dct_cols(vch2d_ctx *c, const SpecArgs &sp, double scale, int gate) {
+    // the column pass reads 16 bytes per row and column pair: at length 1024 a workgroup that owns 2 C / 1024 adjacent
+    // columns uses that share of every 128-byte line it pulls through L2 (profiles/r02_cols_width.txt)
+    const int wide = c->sax.logL == 10 ? c->cols_c : 0;
+    if (wide == 4096) return dct_cols_plan<4096, 10>(c, sp, scale, gate);
+    if (wide == 2048) return dct_cols_plan<2048, 10>(c, sp, scale, gate);
+    return with_plan(c->sax, [&](auto C, auto LG) { return dct_cols_plan<C, LG>(c, sp, scale, gate); });
+}
+
+// first pass of a stencil-free forward CG sweep (k_cg_rows_fwd): E_rows(Delta p) -> c->t1
+static int cg_rows(vch2d_ctx *c, const CgSweepArgs &a, bool first) {
+    return with_plan(c->fax, [&](auto C, auto LG) {
+        const int rpw = 2 * (C >> c->fax.logL);
+        auto k_rows = first ? k_cg_rows_fwd<1, C, LG> : k_cg_rows_fwd<0, C, LG>;
+        LAUNCHC(first ? PC_CG_ROWS1 : PC_CG_ROWS, k_rows, dim3((c->G.ns + rpw - 1) / rpw, 1, c->B), dim3(FftThreads<C, LG>::T),
+                c->G, c->fax, a, c->t1, c->st);
+        return 0;
+    });
+}
+
+// row kernel of a reduction-free sweep (k_cheb_rows): c->t2 -> c->t1
+static int cheb_rows(vch2d_ctx *c, const ChebSweepArgs &a, bool first) {
+    return with_plan(c->fax, [&](auto C, auto LG) {
+        const int rpw = 2 * (C >> c->fax.logL);
+        auto k_rows = first ? k_cheb_rows<C, LG, 1> : k_cheb_rows<C, LG, 0>;
+        LAUNCHC(first ? PC_CHEB_ROWS0 : PC_CHEB_ROWS, k_rows, dim3((c->G.ns + rpw - 1) / rpw, 1, c->B), dim3(FftThreads<C, LG>::T),
+                c->G, c->fax, a, (const double *)c->t2, c->t1, (const TrajState *)c->st);
+        return 0;
+    });
+}
+
+// first pass of an adjoint CG sweep (k_adj_rows_fwd): -> c->t1
+static int adj_rows(vch2d_ctx *c, const AdjSweepArgs &a, bool first) {
+    return with_plan(c->fax, [&](auto C, auto LG) {
+        const int rpw = 2 * (C >> c->fax.logL);
+        auto k_rows = first ? k_adj_rows_fwd<1, C, LG> : k_adj_rows_fwd<0, C, LG>;
+        LAUNCHC(PC_ADJ_Q, k_rows, dim3((c->G.ns + rpw - 1) / rpw, 1, c->B), dim3(FftThreads<C, LG>::T), c->G, c->fax, a, c->t1,
+                c->st);
+        return 0;
+    });
+}
 
 // ------------------------------------------------------------------------------------
 // fast-diagonalisation preconditioner:  out = (c0 + m (c1a + c1b dbar + c2 m))^-1 in
@@ -630,55 +686,21 @@ static int precond(vch2d_ctx *c, const double *in, long in_slot_stride, double *
     SpecArgs sp{c0, c1a, c1b, c2, c->ms, c->mf, other, c->D_s, c->slot_stride, c->gpart, c->gpart2, 0};
     if (c->use_fft) {
         const double scale = 1.0 / (4.0 * (double)c->fax.N * (double)c->sax.N);
-        // C = complex doubles per workgroup: 1024 (one wavefront) unless the FFT is longer
-#define DCT_ROWS(EPI_, C_, LG_, in_, iss_, out_)                                                                \
-    do {                                                                                                        \
-        const int rpw = 2 * (C_ >> c->fax.logL);                                                                \
-        LAUNCHC(((EPI_) >= 3 ? PC_DCT_R3 : PC_DCT_R0), (k_dct_rows<EPI_, C_, LG_>), dim3((ns + rpw - 1) / rpw, 1, c->B), dim3(FftThreads<C_, LG_>::T), G, \
-                c->fax, in_, iss_, out_, 1.0, sp, c->st, gate);                                                 \
-    } while (0)
-#define DCT_COLS(C_, LG_)                                                                                       \
-    do {                                                                                                        \
-        const int cpw = 2 * (C_ >> c->sax.logL);                                                                \
-        LAUNCHC(PC_DCT_C, (k_dct_cols<C_, LG_>), dim3((nf + cpw - 1) / cpw, 1, c->B), dim3(FftThreads<C_, LG_>::T), G, \
-                c->sax, (const double *)c->t1, c->t2, scale, sp, c->st, gate);                                  \
-    } while (0)
-        // the column pass reads 16 bytes per row and column pair: a workgroup that owns 2 C / 1024 adjacent columns uses
-        // that share of every 128-byte line it pulls through L2 (profiles/r02_cols_width.txt)
-#define DCT_COLS_10()                                        \
-    do {                                                     \
-        if (c->cols_c == 4096) DCT_COLS(4096, 10);           \
-        else if (c->cols_c == 2048) DCT_COLS(2048, 10);      \
-        else DCT_COLS(1024, 10);                             \
-    } while (0)
-        // FFT lengths 512 / 1024 / 2048 (grids 256^2, 512^2, 1024^2) are compiled with a constant length
-#define DCT_ROWS_ANY(EPI_, in_, iss_, out_)                                       \
-    do {                                                                          \
-        if (c->fax.logL == 10) DCT_ROWS(EPI_, 1024, 10, in_, iss_, out_);         \
-        else if (c->fax.logL == 9) DCT_ROWS(EPI_, 1024, 9, in_, iss_, out_);      \
-        else if (c->fax.logL < 10) DCT_ROWS(EPI_, 1024, 0, in_, iss_, out_);      \
-        else if (c->fax.logL == 11) DCT_ROWS(EPI_, 2048, 11, in_, iss_, out_);    \
-        else DCT_ROWS(EPI_, 4096, 0, in_, iss_, out_);                            \
-    } while (0)
 #define DCTH_ROWS(EPI_, in_, iss_, out_)                                                                        \
     LAUNCHC(((EPI_) == 3 ? PC_DCT_R3 : PC_DCT_R0), (k_dcth_rows<EPI_>), dim3((ns + 3) / 4, 1, c->B), dim3(HT), G, c->fax, c->fax_h, in_, iss_, out_, 1.0, sp, \
             c->st, gate)
         if (c->half_f) DCTH_ROWS(0, in, in_slot_stride, c->t1);
-        else DCT_ROWS_ANY(0, in, in_slot_stride, c->t1);
+        else VCHCHK(dct_rows<0>(c, in, in_slot_stride, c->t1, sp, gate));
         if (c->half_s)
             LAUNCHC(PC_DCT_C, k_dcth_cols, dim3((nf + 3) / 4, 1, c->B), dim3(HT), G, c->sax, c->sax_h, (const double *)c->t1, c->t2,
                     scale, sp, c->st, gate);
-        else if (c->sax.logL == 10) DCT_COLS_10();
-        else if (c->sax.logL == 9) DCT_COLS(1024, 9);
-        else if (c->sax.logL < 10) DCT_COLS(1024, 0);
-        else if (c->sax.logL == 11) DCT_COLS(2048, 11);
-        else DCT_COLS(4096, 0);
+        else VCHCHK(dct_cols(c, sp, scale, gate));
         if (c->half_f) {
             if (last == 3) DCTH_ROWS(3, (const double *)c->t2, 0L, out);
             else DCTH_ROWS(0, (const double *)c->t2, 0L, out);
-        } else if (last == 3) DCT_ROWS_ANY(3, (const double *)c->t2, 0L, out);
-        else if (last == 4) DCT_ROWS_ANY(4, (const double *)c->t2, 0L, out);
-        else DCT_ROWS_ANY(0, (const double *)c->t2, 0L, out);
+        } else if (last == 3) VCHCHK(dct_rows<3>(c, c->t2, 0L, out, sp, gate));
+        else if (last == 4) VCHCHK(dct_rows<4>(c, c->t2, 0L, out, sp, gate));
+        else VCHCHK(dct_rows<0>(c, c->t2, 0L, out, sp, gate));
         return 0;
     }
     // T1 = g Q1f
@@ -703,17 +725,9 @@ static int precond(vch2d_ctx *c, const double *in, long in_slot_stride, double *
 // Passes 2 and 3 of a stencil-free forward CG sweep (after k_cg_rows_fwd has left E_rows(Delta p) in c->t1):
 // column transforms with the multiplier m / P(m), then q = p + E_rows(.) with the partials of <p,q>_Z, <q,q>_Z.
 static int sweep_tail(vch2d_ctx *c, const double *p, double *q, double c0, double c2, int gate) {
-    const Geom &G = c->G;
-    const int ns = G.ns, nf = G.nf;
-    SpecArgs sp{c0, 0.0, 1.0, c2, c->ms, c->mf, p, c->D_s, c->slot_stride, c->gpart, c->gpart2, 1};
-    const double scale = 1.0 / (4.0 * (double)c->fax.N * (double)c->sax.N);
-    if (c->sax.logL == 10) DCT_COLS_10();
-    else if (c->sax.logL == 9) DCT_COLS(1024, 9);
-    else if (c->sax.logL < 10) DCT_COLS(1024, 0);
-    else if (c->sax.logL == 11) DCT_COLS(2048, 11);
-    else DCT_COLS(4096, 0);
-    DCT_ROWS_ANY(4, (const double *)c->t2, 0L, q);
-    return 0;
+    const SpecArgs sp{c0, 0.0, 1.0, c2, c->ms, c->mf, p, c->D_s, c->slot_stride, c->gpart, c->gpart2, 1};
+    VCHCHK(dct_cols(c, sp, 1.0 / (4.0 * (double)c->fax.N * (double)c->sax.N), gate));
+    return dct_rows<4>(c, c->t2, 0L, q, sp, gate);
 }
 
 // CG iterations to enqueue: the largest rigorous bound among the trajectories still solving
@@ -757,22 +771,7 @@ static int schur_solve(vch2d_ctx *c, double dt, int budget, bool look) {
                 // into x and z on the way into the row transform; 3 launches per sweep, no stencil
                 CgSweepArgs a{done == 0 ? zb[0] : zb[(done + 1) & 1], c->cg_q, po, c->x, zb[done & 1], pn, c->D_s, c->slot_stride,
                               c->gpart, c->gpart2, c->gpart3, done, c->lin_maxit, c->B, c->x0g};
-#define CG_ROWS(FIRST_, C_, LG_)                                                                                          \
-    do {                                                                                                                  \
-        const int rpw = 2 * (C_ >> c->fax.logL);                                                                          \
-        LAUNCHC((FIRST_ ? PC_CG_ROWS1 : PC_CG_ROWS), (k_cg_rows_fwd<FIRST_, C_, LG_>), dim3((c->G.ns + rpw - 1) / rpw, 1, c->B), \
-                dim3(FftThreads<C_, LG_>::T), c->G, c->fax, a, c->t1, c->st);                                             \
-    } while (0)
-#define CG_ROWS_ANY(FIRST_)                                       \
-    do {                                                          \
-        if (c->fax.logL == 10) CG_ROWS(FIRST_, 1024, 10);         \
-        else if (c->fax.logL == 9) CG_ROWS(FIRST_, 1024, 9);      \
-        else if (c->fax.logL < 10) CG_ROWS(FIRST_, 1024, 0);      \
-        else if (c->fax.logL == 11) CG_ROWS(FIRST_, 2048, 11);    \
-        else CG_ROWS(FIRST_, 4096, 0);                            \
-    } while (0)
-                if (done == 0) CG_ROWS_ANY(1);
-                else CG_ROWS_ANY(0);
+                VCHCHK(cg_rows(c, a, done == 0));
                 VCHCHK(sweep_tail(c, pn, c->cg_q, c0, c2, 2 + (done & 1)));      // q = P^-1 A p, <p,q>_Z, <q,q>_Z
                 continue;
             }
@@ -810,20 +809,12 @@ static int schur_solve(vch2d_ctx *c, double dt, int budget, bool look) {
 // finished increment x0 + y in c->x; one whose plan is longer than n_enq is left unfinished (k_fin_ceiling).
 static int cheb_solve(vch2d_ctx *c, double dt, int n_enq) {
     c->cheb_enq = n_enq;
-    const Geom &G = c->G;
-    const int ns = G.ns, nf = G.nf;
     const double c0 = 1.0 / dt, c2 = 0.5 * c->P.kappa;
     const double scale = 1.0 / (4.0 * (double)c->fax.N * (double)c->sax.N);
     {   // E_rows(rhs), then E_cols, 1 / P(m), E_cols (the transform pair's scale is applied by k_cheb_rows)
-        SpecArgs sp{c0, 0.0, 1.0, c2, c->ms, c->mf, nullptr, c->D_s, c->slot_stride, c->gpart, c->gpart2, 0};
-        const int gate = 8;
-        DCT_ROWS_ANY(0, (const double *)c->rhs_s, c->slot_stride, c->t1);
-        const double scale = 1.0;
-        if (c->sax.logL == 10) DCT_COLS_10();
-        else if (c->sax.logL == 9) DCT_COLS(1024, 9);
-        else if (c->sax.logL < 10) DCT_COLS(1024, 0);
-        else if (c->sax.logL == 11) DCT_COLS(2048, 11);
-        else DCT_COLS(4096, 0);
+        const SpecArgs sp{c0, 0.0, 1.0, c2, c->ms, c->mf, nullptr, c->D_s, c->slot_stride, c->gpart, c->gpart2, 0};
+        VCHCHK(dct_rows<0>(c, c->rhs_s, c->slot_stride, c->t1, sp, 8));
+        VCHCHK(dct_cols(c, sp, 1.0, 8));
     }
     for (int j = 0; j <= n_enq; ++j) {
         // y_j lives in cg_p[j & 1] (y_{j+1} overwrites y_{j-1}), b~ in c->r
@@ -831,30 +822,10 @@ static int cheb_solve(vch2d_ctx *c, double dt, int n_enq) {
                         j == 0 ? c->gpart : c->gpart2, j, scale, c->phi_s, c->gpart3,
                         c->guess_wr >= 0 ? c->dprev[c->guess_wr] : (double *)nullptr,
                         (c->guess_wr >= 0 && c->guess2_on) ? c->dprev2[c->guess_wr] : (double *)nullptr};
-#define CHEB_ROWS(C_, LG_)                                                                                             \
-    do {                                                                                                               \
-        const int rpw = 2 * (C_ >> c->fax.logL);                                                                       \
-        if (j == 0)                                                                                                    \
-            LAUNCHC(PC_CHEB_ROWS0, (k_cheb_rows<C_, LG_, 1>), dim3((ns + rpw - 1) / rpw, 1, c->B),                     \
-                    dim3(FftThreads<C_, LG_>::T), G, c->fax, a, (const double *)c->t2, c->t1, (const TrajState *)c->st); \
-        else                                                                                                           \
-            LAUNCHC(PC_CHEB_ROWS, (k_cheb_rows<C_, LG_, 0>), dim3((ns + rpw - 1) / rpw, 1, c->B),                      \
-                    dim3(FftThreads<C_, LG_>::T), G, c->fax, a, (const double *)c->t2, c->t1, (const TrajState *)c->st); \
-    } while (0)
-        if (c->fax.logL == 10) CHEB_ROWS(1024, 10);
-        else if (c->fax.logL == 9) CHEB_ROWS(1024, 9);
-        else if (c->fax.logL < 10) CHEB_ROWS(1024, 0);
-        else if (c->fax.logL == 11) CHEB_ROWS(2048, 11);
-        else CHEB_ROWS(4096, 0);
+        VCHCHK(cheb_rows(c, a, j == 0));
         if (j < n_enq) {   // E_cols, m / P(m), E_cols of E_rows(Delta y_{j+1}) for the trajectories that go on to sweep j + 1
-            SpecArgs sp{c0, 0.0, 1.0, c2, c->ms, c->mf, nullptr, c->D_s, c->slot_stride, c->gpart, c->gpart2, 1};
-            const int gate = 16 + j + 1;
-            const double scale = 1.0;
-            if (c->sax.logL == 10) DCT_COLS_10();
-            else if (c->sax.logL == 9) DCT_COLS(1024, 9);
-            else if (c->sax.logL < 10) DCT_COLS(1024, 0);
-            else if (c->sax.logL == 11) DCT_COLS(2048, 11);
-            else DCT_COLS(4096, 0);
+            const SpecArgs sp{c0, 0.0, 1.0, c2, c->ms, c->mf, nullptr, c->D_s, c->slot_stride, c->gpart, c->gpart2, 1};
+            VCHCHK(dct_cols(c, sp, 1.0, 16 + j + 1));
         }
     }
     return 0;
@@ -891,39 +862,33 @@ static int dmu_ceiling(vch2d_ctx *c, int strict) {
 
 // One residual evaluation of the pending Armijo trials.  inline_dmu (marches on the stencil-free path): the back
 // substitution happens inside the trial kernel, whichever form the solve took (k_eval<2>, or k_residual2 with VCH_FUSED=0).
-#define RESIDUAL_TRIAL()                                                                                                    \
-    do {                                                                                                                    \
-        const bool tg_ = guess2 && trial_guess_;                                                                            \
-        if (inline_dmu && fused) {                                                                                          \
-            GuessArgs gt_ = c->gtab2;                                                                                       \
-            if (!tg_) memset(gt_.c, 0, sizeof(gt_.c));                                                                      \
-            if (fin_inside)                                                                                                 \
-                LAUNCHC(PC_RESIDUAL, (k_eval<2, true>), c->grid, dim3(NTH), c->G, c->P, c->st, c->slot_stride, c->phi_s,    \
-                        c->mu_s, c->Rphi_s, c->rhs_s, c->D_s, (const double *)c->xf, c->cphi, c->cmu, dt, c->part,          \
-                        (const double *)nullptr, (const double *)nullptr, (const double *)nullptr, 0L, (double *)nullptr,   \
-                        gt_, c->x0g, efin_, PostArgs{nullptr, nullptr, 0});                                                 \
-            else                                                                                                            \
-                LAUNCHC(PC_RESIDUAL, (k_eval<2, false>), c->grid, dim3(NTH), c->G, c->P, c->st, c->slot_stride, c->phi_s,   \
-                        c->mu_s, c->Rphi_s, c->rhs_s, c->D_s, (const double *)c->xf, c->cphi, c->cmu, dt, c->part,          \
-                        (const double *)nullptr, (const double *)nullptr, (const double *)nullptr, 0L, (double *)nullptr,   \
-                        gt_, c->x0g, efin_, PostArgs{nullptr, nullptr, 0});                                                 \
-            if (!fin_inside)                                                                                                \
-                LAUNCH((k_fin_residual<1>), dim3(c->B), dim3(64), c->st, c->part, c->nblk, c->hist_dev, c->P.kappa, dt,     \
-                       c->lin_tol, eta_, tg_ ? (int)c->gmask2 : 0, so_);                                              \
-            break;                                                                                                          \
-        }                                                                                                                   \
-        if (inline_dmu)                                                                                                     \
-            LAUNCHC(PC_RESIDUAL, k_residual2, c->grid, dim3(NTH), c->G, c->P, c->st, c->slot_stride, c->phi_s, c->mu_s,     \
-                    c->Rphi_s, c->rhs_s, c->D_s, (const double *)c->xf, c->cphi, c->cmu, dt, c->part);                      \
-        else                                                                                                                \
-            LAUNCHC(PC_RESIDUAL, (k_residual<1>), c->grid, dim3(NTH), c->G, c->P, c->st, c->slot_stride, c->phi_s, c->mu_s, \
-                    c->Rphi_s, c->rhs_s, c->D_s, c->mu0, c->xf, c->dmu, c->cphi, c->cmu, dt, c->part);                      \
-        if (tg_)                                                                                                            \
-            LAUNCHC(PC_GUESS, k_guess, c->grid, dim3(NTH), c->G, c->P, c->st, c->slot_stride, c->gtab2,                     \
-                    (const double *)c->D_s, dt, c->rhs_s, c->x0g, c->part, 1);                                              \
-        LAUNCH((k_fin_residual<1>), dim3(c->B), dim3(64), c->st, c->part, c->nblk, c->hist_dev, c->P.kappa, dt, c->lin_tol, \
-               eta_, tg_ ? (int)c->gmask2 : 0, so_);                                                                  \
-    } while (0)
+static int residual_trial(vch2d_ctx *c, double dt, bool inline_dmu, bool fused, bool fin_inside, bool guess, double eta,
+                          const SolveOpts &so, const EvalFin &efin) {
+    if (inline_dmu && fused) {
+        GuessArgs gt = c->gtab2;
+        if (!guess) memset(gt.c, 0, sizeof(gt.c));
+        auto k_trial = fin_inside ? k_eval<2, true> : k_eval<2, false>;
+        LAUNCHC(PC_RESIDUAL, k_trial, c->grid, dim3(NTH), c->G, c->P, c->st, c->slot_stride, c->phi_s, c->mu_s, c->Rphi_s, c->rhs_s,
+                c->D_s, (const double *)c->xf, c->cphi, c->cmu, dt, c->part, (const double *)nullptr, (const double *)nullptr,
+                (const double *)nullptr, 0L, (double *)nullptr, gt, c->x0g, efin, PostArgs{nullptr, nullptr, 0});
+        if (!fin_inside)
+            LAUNCH((k_fin_residual<1>), dim3(c->B), dim3(64), c->st, c->part, c->nblk, c->hist_dev, c->P.kappa, dt, c->lin_tol, eta,
+                   guess ? (int)c->gmask2 : 0, so);
+        return 0;
+    }
+    if (inline_dmu)
+        LAUNCHC(PC_RESIDUAL, k_residual2, c->grid, dim3(NTH), c->G, c->P, c->st, c->slot_stride, c->phi_s, c->mu_s, c->Rphi_s,
+                c->rhs_s, c->D_s, (const double *)c->xf, c->cphi, c->cmu, dt, c->part);
+    else
+        LAUNCHC(PC_RESIDUAL, (k_residual<1>), c->grid, dim3(NTH), c->G, c->P, c->st, c->slot_stride, c->phi_s, c->mu_s, c->Rphi_s,
+                c->rhs_s, c->D_s, c->mu0, c->xf, c->dmu, c->cphi, c->cmu, dt, c->part);
+    if (guess)
+        LAUNCHC(PC_GUESS, k_guess, c->grid, dim3(NTH), c->G, c->P, c->st, c->slot_stride, c->gtab2, (const double *)c->D_s, dt,
+                c->rhs_s, c->x0g, c->part, 1);
+    LAUNCH((k_fin_residual<1>), dim3(c->B), dim3(64), c->st, c->part, c->nblk, c->hist_dev, c->P.kappa, dt, c->lin_tol, eta,
+           guess ? (int)c->gmask2 : 0, so);
+    return 0;
+}
 
 // One implicit time level for the whole batch (F2:323-427).  On entry the old level is
 // (phi_s, mu_s)[slot], w; on exit the new iterate is in (phi_s, mu_s)[slot] and w_new in c->wnew.
@@ -961,14 +926,10 @@ static int newton_level(vch2d_ctx *c, double dt, const double *un, const double 
         // the previous step's clip / mass fix / history store, if forward_core left it to this kernel
         const PostArgs post_{c->post_pending ? (const double *)c->part_mass : (const double *)nullptr, c->post_hist, hist_stride(c)};
         c->post_pending = false;
-        if (fin_inside)
-            LAUNCHC(PC_RESIDUAL0, (k_eval<0, true>), c->grid, dim3(NTH), c->G, c->P, c->st, c->slot_stride, c->phi_s, c->mu_s, c->Rphi_s,
-                    c->rhs_s, c->D_s, (const double *)nullptr, c->cphi, c->cmu, dt, c->part, (const double *)c->w, un, unp1, u_stride,
-                    c->wnew, g1_, c->x0g, efin_, post_);
-        else
-            LAUNCHC(PC_RESIDUAL0, (k_eval<0, false>), c->grid, dim3(NTH), c->G, c->P, c->st, c->slot_stride, c->phi_s, c->mu_s, c->Rphi_s,
-                    c->rhs_s, c->D_s, (const double *)nullptr, c->cphi, c->cmu, dt, c->part, (const double *)c->w, un, unp1, u_stride,
-                    c->wnew, g1_, c->x0g, efin_, post_);
+        auto k_start = fin_inside ? k_eval<0, true> : k_eval<0, false>;
+        LAUNCHC(PC_RESIDUAL0, k_start, c->grid, dim3(NTH), c->G, c->P, c->st, c->slot_stride, c->phi_s, c->mu_s, c->Rphi_s, c->rhs_s,
+                c->D_s, (const double *)nullptr, c->cphi, c->cmu, dt, c->part, (const double *)c->w, un, unp1, u_stride, c->wnew, g1_,
+                c->x0g, efin_, post_);
         if (!fin_inside)
             LAUNCH((k_fin_residual<2>), dim3(c->B), dim3(64), c->st, c->part, c->nblk, c->hist_dev, c->P.kappa, dt, c->lin_tol, eta_,
                    guess ? (int)c->gmask1 : 0, so_);
@@ -992,8 +953,7 @@ static int newton_level(vch2d_ctx *c, double dt, const double *un, const double 
             VCHCHK(dmu_ceiling(c, 1));
             // the second solve's guess goes with the trial that follows a trajectory's FIRST solve (the kernels check
             // iters == 1), in whichever slot that solve finished: the result must not depend on the launch schedule
-            const bool trial_guess_ = true;
-            RESIDUAL_TRIAL();
+            VCHCHK(residual_trial(c, dt, inline_dmu, fused, fin_inside, guess2, eta_, so_, efin_));
         }
     }
     VCHCHK(sync_state(c, false));
@@ -1031,9 +991,8 @@ static int newton_level(vch2d_ctx *c, double dt, const double *un, const double 
         if (budget > 0) VCHCHK(schur_solve(c, dt, std::min(budget, c->lin_maxit), true));
         VCHCHK(dmu_ceiling(c, 0));
         int tguard = 0;
-        const bool trial_guess_ = true;
         do {
-            RESIDUAL_TRIAL();
+            VCHCHK(residual_trial(c, dt, inline_dmu, fused, fin_inside, guess2, eta_, so_, efin_));
             VCHCHK(sync_state(c, false));
             if (++tguard > ARMIJO_TRIALS + 2) return vch_fail(VCH_ERR_STATE, "newton_level: Armijo loop did not terminate");
         } while (any_trial());
@@ -1254,8 +1213,6 @@ static int adjoint_solve_cg(vch2d_ctx *c, double dt, int budget, bool look) {
     if (spectral) {
         if (budget <= 0) return 0;
         const double cadj = 0.5 * dt;
-        const Geom &G = c->G;
-        const int ns = G.ns, nf = G.nf;
         double *rb[2] = {c->r, c->cg_z2}, *y = c->cg_v;
         int done = 0;
         while (done < budget) {
@@ -1264,32 +1221,12 @@ static int adjoint_solve_cg(vch2d_ctx *c, double dt, int budget, bool look) {
                 double *pn = c->cg_p[done & 1], *po = c->cg_p[(done + 1) & 1];
                 AdjSweepArgs a{done == 0 ? rb[0] : rb[(done + 1) & 1], c->cg_q, po, y, rb[done & 1], pn, c->cmu,
                                c->gpart, c->gpart2, c->gpart3, done, c->lin_maxit, c->B, c->part, c->nblk, c->lin_tol};
-#define ADJ_ROWS(FIRST_, C_, LG_)                                                                                       \
-    do {                                                                                                                \
-        const int rpw = 2 * (C_ >> c->fax.logL);                                                                        \
-        LAUNCHC(PC_ADJ_Q, (k_adj_rows_fwd<FIRST_, C_, LG_>), dim3((ns + rpw - 1) / rpw, 1, c->B), dim3(FftThreads<C_, LG_>::T), G, \
-                c->fax, a, c->t1, c->st);                                                                               \
-    } while (0)
-#define ADJ_ROWS_ANY(FIRST_)                                       \
-    do {                                                           \
-        if (c->fax.logL == 10) ADJ_ROWS(FIRST_, 1024, 10);         \
-        else if (c->fax.logL == 9) ADJ_ROWS(FIRST_, 1024, 9);      \
-        else if (c->fax.logL < 10) ADJ_ROWS(FIRST_, 1024, 0);      \
-        else if (c->fax.logL == 11) ADJ_ROWS(FIRST_, 2048, 11);    \
-        else ADJ_ROWS(FIRST_, 4096, 0);                            \
-    } while (0)
-                if (done == 0) ADJ_ROWS_ANY(1);
-                else ADJ_ROWS_ANY(0);
+                VCHCHK(adj_rows(c, a, done == 0));
                 // q = ph + c Delta (M P^-1 ph), <ph,q>_Z', <q,q>_Z'
-                SpecArgs sp{1.0, c->P.tau, cadj, cadj, c->ms, c->mf, pn, c->cmu, 0L, c->gpart, c->gpart2, 1, cadj};
-                const double scale = 1.0 / (4.0 * (double)c->fax.N * (double)c->sax.N);
+                const SpecArgs sp{1.0, c->P.tau, cadj, cadj, c->ms, c->mf, pn, c->cmu, 0L, c->gpart, c->gpart2, 1, cadj};
                 const int gate = 2 + (done & 1);
-                if (c->sax.logL == 10) DCT_COLS_10();
-                else if (c->sax.logL == 9) DCT_COLS(1024, 9);
-                else if (c->sax.logL < 10) DCT_COLS(1024, 0);
-                else if (c->sax.logL == 11) DCT_COLS(2048, 11);
-                else DCT_COLS(4096, 0);
-                DCT_ROWS_ANY(5, (const double *)c->t2, 0L, c->cg_q);
+                VCHCHK(dct_cols(c, sp, 1.0 / (4.0 * (double)c->fax.N * (double)c->sax.N), gate));
+                VCHCHK(dct_rows<5>(c, c->t2, 0L, c->cg_q, sp, gate));
             }
             if (done < budget) {
                 LAUNCH(k_cg_publish, dim3((c->B + 63) / 64), dim3(64), c->st, (done - 1) & 1, c->B);
@@ -2302,27 +2239,4 @@ extern "C" int vch2d_counters(vch2d_ctx *c, int64_t *out) {
 
 extern "C" int vch2d_uses_fft(const vch2d_ctx *c) { return c ? (c->use_fft ? 1 : 0) : VCH_ERR_ARG; }
 
-#ifdef VCH_FFT_TIMING
-// tuning builds only: run ONE forward row pass on tmp[0] with phase stamps; out [B * blocks][4] ticks
-extern "C" int vch2d_debug_fft_phases(vch2d_ctx *c, long long *out, int cap) {
-    CTXCHK(c);
-    if (!c->use_fft || c->fax.logL != 10) return vch_fail(VCH_ERR_STATE, "debug: needs the 512-interval FFT path");
-    const int nblk = (c->G.ns + 1) / 2, n = c->B * nblk;
-    if (cap < n * 4) return vch_fail(VCH_ERR_ARG, "debug: buffer too small");
-    long long *dev = nullptr;
-    HIPCHK(hipMalloc((void **)&dev, sizeof(long long) * n * 4));
-    HIPCHK(hipMemset(dev, 0, sizeof(long long) * n * 4));
-    HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_fft_dbg), &dev, sizeof(dev)));
-    SpecArgs sp{1.0, 0.0, 0.0, 0.0, c->ms, c->mf, nullptr, c->D_s, c->slot_stride, c->gpart, c->gpart2};
-    for (int rep = 0; rep < 3; ++rep)
-        LAUNCH((k_dct_rows<0, 1024, 10>), dim3(nblk, 1, c->B), dim3(FftThreads<1024, 10>::T), c->G, c->fax, (const double *)c->tmp[0], 0L,
-               c->t1, 1.0, sp, c->st, 0);
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpy(out, dev, sizeof(long long) * n * 4, hipMemcpyDeviceToHost));
-    long long *nul = nullptr;
-    HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_fft_dbg), &nul, sizeof(nul)));
-    hipFree(dev);
-    return n;
-}
-#endif
 

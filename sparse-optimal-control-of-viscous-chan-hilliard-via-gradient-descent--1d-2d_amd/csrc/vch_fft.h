@@ -28,15 +28,6 @@
 #include "vch_kernels2d.h"
 #include "vch_gemm.h"        // SpecArgs
 
-#ifdef VCH_FFT_TIMING
-// phase timing of the DCT kernels (tuning builds only, scripts/fft_phases.py): per workgroup
-// {start, after load, after FFT(s), end} in s_memrealtime ticks (100 MHz)
-__device__ long long *g_fft_dbg = nullptr;
-#define FFT_STAMP(i) do { if (g_fft_dbg && threadIdx.x == 0) g_fft_dbg[(((long)blockIdx.z * gridDim.x + blockIdx.x) * 4 + (i))] = wall_clock64(); } while (0)
-#else
-#define FFT_STAMP(i) do { } while (0)
-#endif
-
 struct FftAxis {
     int N, L, logL;          // intervals, FFT length 2N, log2 L
     const double2 *tw;       // exp(-2 pi i m / L), m = 0..L-1
@@ -47,10 +38,6 @@ __device__ __forceinline__ double2 cmul(double2 a, double2 b) {
     return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
 }
 
-#ifndef FFT_RCP
-#define FFT_RCP 1             // spectral multiplier of a column pair from ONE v_rcp_f64 of the product of the two
-                              // denominators + two Newton steps instead of two IEEE divisions
-#endif
 // scale * (mult_m ? m : 1) / (c0 + m (c1 + c2 m)) for the two columns of a pair.  The denominators are positive and of
 // moderate magnitude (1/dt ... c2 m^2), so the operand scaling and fix-up of an IEEE division buy nothing: one hardware
 // reciprocal of pa*pb refined by two Newton steps, then 1/pa = r pb, 1/pb = r pa (within 2 ulp of the divisions).
@@ -62,93 +49,36 @@ __device__ __forceinline__ void spec_mult2(const SP &sp, double c1, double scale
     // numerator: 1 (inverse of P), m (M P^-1), or mode 2 = -(c0 + c2 m^2) (the multiplier -E of the right-scaled CG form)
     const double na = scale * (mode == 2 ? -(sp.c0 + sp.c2 * ma * ma) : (mode ? ma : 1.0));
     const double nb = scale * (mode == 2 ? -(sp.c0 + sp.c2 * mb * mb) : (mode ? mb : 1.0));
-#if FFT_RCP
     const double d = pa * pb;
     double r = __builtin_amdgcn_rcp(d);
     r = fma(fma(-d, r, 1.0), r, r);
     r = fma(fma(-d, r, 1.0), r, r);
     fa = na * (r * pb);
     fb = nb * (r * pa);
-#else
-    fa = na / pa;
-    fb = nb / pb;
-#endif
 }
 
 // LDS image addressing.  A wavefront's ds_*_b128 is served 8 lanes (one 128-byte row of banks) per clock.
 // Reads of every pass take consecutive complex numbers (conflict-free); the Stockham writes of the first two
 // radix-4 passes do not: lane j writes index 4j + r (pass 0: 8 lanes fall on 2 of the 8 slots of a row) and
 // 16 (j >> 2) + (j & 3) + 4r (pass 1: 4 of 8).  XOR-ing the slot (index bits 0..2) with (i3, i4, i4) makes
-// both patterns -- and still every aligned run of 8 consecutive indices -- hit 8 distinct slots.
-// FFT_SWZ=0 restores the plain image, FFT_PAD=1 the padded one (profiles/r01_c_fft_variants.txt).
-#ifndef FFT_PAD
-#define FFT_PAD 0
-#endif
-#ifndef FFT_SWZ
-#define FFT_SWZ 1
-#endif
-#if FFT_PAD
-#define PADC(c) ((c) + ((c) >> 2))
-#elif FFT_SWZ
-#define PADC(c) ((c) ^ ((((c) >> 3) & 1) | ((((c) >> 4) & 1) * 6)))
-#else
-#define PADC(c) (c)
-#endif
-// Lengths 512 / 1024 / 2048 (grids 256^2, 512^2, 1024^2) start with radix-8 passes (FFT_R8): plans 8x8x8, 8x8x4x4 and
+// both patterns -- and still every aligned run of 8 consecutive indices -- hit 8 distinct slots
+// (plain and padded images measured slower, profiles/r01_c_fft_variants.txt).
+// Lengths 512 / 1024 / 2048 (grids 256^2, 512^2, 1024^2) start with radix-8 passes: plans 8x8x8, 8x8x4x4 and
 // 8x8x8x4, i.e. 3 / 4 / 4 LDS exchanges instead of 5 / 5 / 6.  Those passes write index 8j + r, 64 (j >> 3) + (j & 7) + 8r,
 // 512 (j >> 6) + (j & 63) + 64r, for which the slot is XOR-ed with (i3, i4, i5).
-#ifndef FFT_R8
-#define FFT_R8 1
-#endif
-#ifndef FFT_ROWS_INGEST
-#define FFT_ROWS_INGEST 1
-#endif
-#ifndef FFT_COLS_PAIR
-#define FFT_COLS_PAIR 1       // column pass: 16-byte accesses of a column pair (-1.3 % on the march, r02_fft_variants.txt)
-#endif
-#ifndef FFT_COLS_FUSE
-#define FFT_COLS_FUSE 1       // column pass: the last pass of the first transform hands its outputs to the first pass of the
-                              // second in registers (same eight indices per thread), multiplier applied on the way
-#endif
-#ifndef CG_ROWS_STAGED
-#define CG_ROWS_STAGED 1      // first pass of a CG sweep: visit every node once and stage the even extension in LDS (0: feed the
-                              // first FFT pass from global memory, which reads each operand twice; -5 % on the march, r02_fft_variants.txt)
-#endif
-#ifndef FFT_COLS_INGEST
-#define FFT_COLS_INGEST 0
-#endif
-#ifndef FFT_COLS_EMIT
-#define FFT_COLS_EMIT 1
-#endif
-// FFT_W64 (off): the 1024-point FFT (512^2 grid) done by ONE wavefront with the plan 16 x 8 x 8: a radix-16 butterfly per
-// lane fed from global memory, then two radix-8 passes with two butterflies per lane -- two LDS exchanges instead of
-// three, no workgroup barrier that ever waits for another wave, the last pass emitted from registers.  Its radix-16
-// pass writes index 16 j + r, for which the 16-byte slot within a 256-byte row of banks is XOR-ed with index bits 4..7.
-#ifndef FFT_W64
-#define FFT_W64 0      // measured slower than the two-wave 8x8x4x4 plan (profiles/r02_fft_variants.txt): opt-in A/B knob
-#endif
+// A one-wavefront 16 x 8 x 8 plan of the 1024-point FFT measured slower than the two-wave 8x8x4x4 plan
+// (profiles/r02_fft_variants.txt).
 template <int LOGL>
 __device__ __forceinline__ int swz(int c) {
-#if FFT_R8 && FFT_SWZ && !FFT_PAD
-    if (LOGL == 10 && FFT_W64) return c ^ ((c >> 4) & 15);
     if (LOGL >= 9 && LOGL <= 11) return c ^ ((c >> 3) & 7);
-#endif
-    return PADC(c);
+    return c ^ (((c >> 3) & 1) | (((c >> 4) & 1) * 6));
 }
-template <int C>
-struct FftLds {
-    static constexpr int SIZE = FFT_PAD ? C + C / 4 + 4 : C;
-};
 
-// In-place FFT of the NFFT = C/L sequences stored back to back in buf (C/16 threads).
-// threads per workgroup for an image of C complex doubles (tuning knob: C/16 = one butterfly
-// quartet per thread per pass; fewer butterflies per thread = more wavefronts per CU at equal LDS)
-#ifndef FFT_BPT
-#define FFT_BPT 2
-#endif
+// In-place FFT of the NFFT = C/L sequences stored back to back in buf: C/8 threads, i.e. one radix-8 butterfly or
+// two radix-4 butterfly quartets per thread per pass.
 template <int C, int LOGL = 0>
 struct FftThreads {
-    static constexpr int T = (LOGL == 10 && C == 1024 && FFT_W64 && FFT_R8) ? 64 : C / (4 * FFT_BPT);
+    static constexpr int T = C / 8;
 };
 
 // LOGL > 0: log2 of the FFT length is a compile-time constant (all index arithmetic folds and the
@@ -171,112 +101,6 @@ struct FftNoIngest {
     __device__ __forceinline__ double2 operator()(int) const { return make_double2(0.0, 0.0); }
 };
 
-// ---- one-wavefront 1024-point FFT (plan 16 x 8 x 8) ----
-__device__ __forceinline__ double2 cadd(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ double2 csub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
-
-// 8-point DFT, natural order in and out (o_m = sum_n a_n exp(-2 pi i n m / 8))
-__device__ __forceinline__ void dft8(const double2 (&a)[8], double2 (&o)[8]) {
-    constexpr double RH = 0.70710678118654752440;
-    double2 bb[4], cc[4];
-#pragma unroll
-    for (int n = 0; n < 4; ++n) {
-        bb[n] = cadd(a[n], a[n + 4]);
-        cc[n] = csub(a[n], a[n + 4]);
-    }
-    cc[1] = make_double2(RH * (cc[1].x + cc[1].y), RH * (cc[1].y - cc[1].x));      // * (1 - i)/sqrt 2
-    cc[2] = make_double2(cc[2].y, -cc[2].x);                                       // * (-i)
-    cc[3] = make_double2(RH * (cc[3].y - cc[3].x), -RH * (cc[3].x + cc[3].y));     // * (-1 - i)/sqrt 2
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const double2 *v = h ? cc : bb;
-        const double2 t0 = cadd(v[0], v[2]), t1 = csub(v[0], v[2]), t2 = cadd(v[1], v[3]);
-        const double2 t3 = make_double2(v[1].y - v[3].y, -(v[1].x - v[3].x));      // -i (v1 - v3)
-        o[h + 0] = cadd(t0, t2);
-        o[h + 2] = cadd(t1, t3);
-        o[h + 4] = csub(t0, t2);
-        o[h + 6] = csub(t1, t3);
-    }
-}
-
-// 16-point DFT, natural order in and out: b_n = a_n + a_{n+8}, c_n = (a_n - a_{n+8}) W16^n, then DFT8(b) gives the even
-// and DFT8(c) the odd outputs
-__device__ __forceinline__ void dft16(const double2 (&a)[16], double2 (&o)[16]) {
-    constexpr double C1 = 0.92387953251128675613, S1 = 0.38268343236508977173, RH = 0.70710678118654752440;
-    constexpr double WR[8] = {1.0, C1, RH, S1, 0.0, -S1, -RH, -C1};
-    constexpr double WI[8] = {0.0, -S1, -RH, -C1, -1.0, -C1, -RH, -S1};
-    double2 b[8], c[8], e[8], f[8];
-#pragma unroll
-    for (int n = 0; n < 8; ++n) {
-        b[n] = cadd(a[n], a[n + 8]);
-        const double2 d = csub(a[n], a[n + 8]);
-        c[n] = make_double2(d.x * WR[n] - d.y * WI[n], d.x * WI[n] + d.y * WR[n]);
-    }
-    dft8(b, e);
-    dft8(c, f);
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {
-        o[2 * m] = e[m];
-        o[2 * m + 1] = f[m];
-    }
-}
-
-// One wavefront (threadIdx.x & 63 = lane; the workgroup IS that wavefront) transforms the 1024 complex entries of buf.
-// Stockham autosort: pass A radix 16 (Ns = 1), passes B, C radix 8 (Ns = 16, 128), two butterflies per lane.
-template <bool EMIT, bool EMIT_TO_LDS, bool INGEST, class Emit, class Ingest>
-__device__ __forceinline__ void fft1024_wave(double2 *buf, const FftAxis ax, Emit emit, Ingest ingest) {
-    constexpr int LG = 10;
-    const int lane = threadIdx.x & 63;
-    {   // pass A: inputs x[lane + 64 r], outputs y[16 lane + r]
-        double2 a[16], o[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) a[r] = INGEST ? ingest(lane + 64 * r) : buf[swz<LG>(lane + 64 * r)];
-        dft16(a, o);
-        if (!INGEST) __syncthreads();             // every lane has read the image
-#pragma unroll
-        for (int r = 0; r < 16; ++r) buf[swz<LG>(16 * lane + r)] = o[r];
-        __syncthreads();
-    }
-#pragma unroll
-    for (int ps = 0; ps < 2; ++ps) {             // passes B (Ns = 16) and C (Ns = 128)
-        const int lNs = ps ? 7 : 4, Ns = 1 << lNs;
-        double2 o[2][8];
-        int wb[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int j = lane + 64 * i, k = j & (Ns - 1);
-            double2 a[8];
-#pragma unroll
-            for (int r = 0; r < 8; ++r) a[r] = buf[swz<LG>(j + 128 * r)];
-            const double2 w1 = ax.tw[k << (LG - 3 - lNs)];      // exp(-2 pi i k / (8 Ns))
-            double2 w = w1;
-            a[1] = cmul(a[1], w);
-#pragma unroll
-            for (int r = 2; r < 8; ++r) {
-                w = cmul(w, w1);
-                a[r] = cmul(a[r], w);
-            }
-            dft8(a, o[i]);
-            wb[i] = ((j >> lNs) << (lNs + 3)) + k;
-        }
-        if (EMIT && ps == 1) {
-            if (EMIT_TO_LDS) __syncthreads();
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int r = 0; r < 8; ++r) emit(wb[i] + r * Ns, o[i][r]);
-            if (EMIT_TO_LDS) __syncthreads();
-        } else {
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int r = 0; r < 8; ++r) buf[swz<LG>(wb[i] + r * Ns)] = o[i][r];
-            __syncthreads();
-        }
-    }
-}
-
 // REGMODE (two transforms back to back, k_dct_cols): 1 = the last pass leaves its outputs in xr[0..8) instead of the image,
 // 2 = the first pass takes its inputs from xr.  With one butterfly octet per thread the first radix-8 pass reads the
 // indices j + s L/8 (s = 0..7) of its transform, and the last pass of the plan produces exactly those: a radix-8 pass
@@ -284,29 +108,22 @@ __device__ __forceinline__ void fft1024_wave(double2 *buf, const FftAxis ax, Emi
 // j + (i + 2 r) L/8.  FftRegOk says for which images that holds.
 template <int C, int LOGL>
 struct FftRegOk {
-    static constexpr bool V = FFT_R8 && !FFT_W64 && (LOGL == 9 || ((LOGL == 10 || LOGL == 11) && C == (1 << LOGL)));
+    static constexpr bool V = (LOGL == 9 || ((LOGL == 10 || LOGL == 11) && C == (1 << LOGL)));
 };
 template <int C, int LOGL, class Emit = FftNoEmit, class Ingest = FftNoIngest, int REGMODE = 0>
 __device__ __forceinline__ void fft_lds(double2 *buf, const FftAxis ax, Emit emit = Emit(), Ingest ingest = Ingest(),
                                         double2 *xr = nullptr) {
     static_assert(REGMODE == 0 || FftRegOk<C, LOGL>::V, "register hand-over needs a compile-time radix-8 plan");
-    constexpr bool EMIT = Emit::ACTIVE && LOGL >= 9 && LOGL <= 11 && FFT_R8;
-    constexpr bool INGEST = Ingest::ACTIVE && LOGL >= 9 && LOGL <= 11 && FFT_R8;
+    constexpr bool EMIT = Emit::ACTIVE && LOGL >= 9 && LOGL <= 11;
+    constexpr bool INGEST = Ingest::ACTIVE && LOGL >= 9 && LOGL <= 11;
     constexpr int T = FftThreads<C, LOGL>::T;
     constexpr int NB4 = C / (4 * T), NB2 = C / (2 * T);
     const int tid = threadIdx.x;
     const int logL = LOGL ? LOGL : ax.logL, L = 1 << logL;
     int logNs = 0;
-#if FFT_R8 && FFT_W64
-    if constexpr (LOGL == 10 && T == 64 && C == 1024) {
-        fft1024_wave<Emit::ACTIVE != 0, Emit::TO_LDS != 0, Ingest::ACTIVE != 0>(buf, ax, emit, ingest);
-        return;
-    }
-#endif
-#if FFT_R8
     if (LOGL >= 9 && LOGL <= 11) {
         // leading radix-8 passes (Ns = 1, 8[, 64]): C/8 butterflies = one per thread (T = C/8)
-        static_assert(LOGL < 9 || LOGL > 11 || C == 8 * T || (LOGL == 10 && T == 64), "radix-8 plan: one butterfly per thread");
+        static_assert(LOGL < 9 || LOGL > 11 || C == 8 * T, "radix-8 plan: one butterfly per thread");
         constexpr int NR8 = LOGL == 10 ? 2 : 3;
         constexpr double RH = 0.70710678118654752440;
         const int f = tid >> (logL - 3), j = tid & ((L >> 3) - 1), fb = f * L;
@@ -369,7 +186,6 @@ __device__ __forceinline__ void fft_lds(double2 *buf, const FftAxis ax, Emit emi
         }
         logNs = 3 * NR8;
     }
-#endif
     // radix-4 passes: C/4 butterflies = 4 per thread
     const int logQ = logL - 2, Q = L >> 2;
 #pragma unroll
@@ -472,7 +288,7 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_dct_rows(Geom G, F
                                                   SpecArgs sp, const TrajState *__restrict__ st, int gate) {
     const int b = blockIdx.z;
     if (gate && !gate_open(st[b], gate)) return;
-    __shared__ double2 buf[FftLds<C>::SIZE];
+    __shared__ double2 buf[C];
     constexpr int T = FftThreads<C, LOGL>::T;
     const int tid = threadIdx.x;
     const int logL = LOGL ? LOGL : ax.logL, L = 1 << logL, N = L >> 1, nfft = C >> logL;
@@ -480,9 +296,8 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_dct_rows(Geom G, F
     const double *ib = in + b * G.plane + (in_slot_stride ? st[b].slot * in_slot_stride : 0);
     const int n1 = N + 1;
     const float inv_n1 = 1.0f / (float)n1;       // idx < 2^14: the float quotient is exact enough
-    FFT_STAMP(0);
-    constexpr bool DIRECT = FFT_R8 && LOGL >= 9 && LOGL <= 11;
-    if (!(DIRECT && FFT_ROWS_INGEST)) {
+    constexpr bool DIRECT = LOGL >= 9 && LOGL <= 11;
+    if (!DIRECT) {
         for (int idx = tid; idx < nfft * n1; idx += T) {
             const int f = nfft == 1 ? 0 : (int)(((float)idx + 0.5f) * inv_n1), j = idx - f * n1;
             const int ra = row0 + 2 * f, rb = ra + 1;
@@ -493,7 +308,6 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_dct_rows(Geom G, F
         }
         __syncthreads();
     }
-    FFT_STAMP(1);
     double dot = 0.0, dot2 = 0.0, dbar = 0.0;
     const double *Dp = nullptr, *Ob = nullptr;
     int scaled = 0;
@@ -555,12 +369,9 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_dct_rows(Geom G, F
                 return make_double2(ra < ns_ ? p[0] : 0.0, ra + 1 < ns_ ? p[pitch_] : 0.0);
             }
         };
-        if (FFT_ROWS_INGEST) fft_lds<C, LOGL>(buf, ax, RowEmit{put, row0, G.ns}, RowIngest{ib, (long)G.pitch, row0, G.ns});
-        else fft_lds<C, LOGL>(buf, ax, RowEmit{put, row0, G.ns});
-        FFT_STAMP(2);
+        fft_lds<C, LOGL>(buf, ax, RowEmit{put, row0, G.ns}, RowIngest{ib, (long)G.pitch, row0, G.ns});
     } else {
         fft_lds<C, LOGL>(buf, ax);
-        FFT_STAMP(2);
         for (int idx = tid; idx < 2 * nfft * n1; idx += T) {
             const int rr = nfft == 1 ? (idx >= n1 ? 1 : 0) : (int)(((float)idx + 0.5f) * inv_n1), k = idx - rr * n1;
             const int row = row0 + rr;
@@ -570,7 +381,6 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_dct_rows(Geom G, F
             }
         }
     }
-    FFT_STAMP(3);
     if (EPI >= 3) {
         dot = wave_sum(dot);
         dot2 = wave_sum(dot2);
@@ -713,7 +523,7 @@ template <int FIRST, int C, int LOGL>
 __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_cg_rows_fwd(Geom G, FftAxis ax, CgSweepArgs a, double *__restrict__ out,
                                                                          TrajState *__restrict__ st) {
     const int b = blockIdx.z;
-    __shared__ double2 buf[FftLds<C>::SIZE];
+    __shared__ double2 buf[C];
     __shared__ double s3[4];
     constexpr int T = FftThreads<C, LOGL>::T;
     const int tid = threadIdx.x;
@@ -809,7 +619,7 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_cg_rows_fwd(Geom G
     };
     double *ob = out + pb;
     auto put = [&](int row, int k, double e) { ob[(long)row * G.pitch + k] = e; };
-    constexpr bool DIRECT = FFT_R8 && LOGL >= 9 && LOGL <= 11;
+    constexpr bool DIRECT = LOGL >= 9 && LOGL <= 11;
     if (DIRECT) {
         struct Emit {
             enum { ACTIVE = 1, TO_LDS = 0 };
@@ -825,20 +635,9 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_cg_rows_fwd(Geom G
                 }
             }
         };
-        struct Ingest {
-            enum { ACTIVE = 1 };
-            decltype(node) &node_;
-            int row0_;
-            __device__ __forceinline__ double2 operator()(int idx) const {
-                constexpr int LL = 1 << (LOGL ? LOGL : 1);
-                const int f = idx >> (LOGL ? LOGL : 1), i = idx & (LL - 1);
-                const bool owner = i <= LL / 2;
-                const int m = owner ? i : LL - i, ra = row0_ + 2 * f;
-                return make_double2(node_(ra, m, owner), node_(ra + 1, m, owner));
-            }
-        };
-#if CG_ROWS_STAGED
         // every node once (no second visit for the mirror half of the even extension): stage the image, then transform
+        // (feeding the first FFT pass from global memory reads each operand twice; staging: -5 % on the march,
+        // profiles/r02_fft_variants.txt)
         for (int idx = tid; idx < nfft * n1; idx += T) {
             const int f = nfft == 1 ? 0 : idx / n1, j = idx - f * n1;
             const int ra = row0 + 2 * f;
@@ -848,9 +647,6 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_cg_rows_fwd(Geom G
         }
         __syncthreads();
         fft_lds<C, LOGL>(buf, ax, Emit{put, row0, G.ns});
-#else
-        fft_lds<C, LOGL>(buf, ax, Emit{put, row0, G.ns}, Ingest{node, row0});
-#endif
     } else {
         const float inv_n1 = 1.0f / (float)n1;
         for (int idx = tid; idx < nfft * n1; idx += T) {
@@ -931,7 +727,7 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T), CHEB_MINW) void k_cheb_ro
     if (FIRST) a.j = 0;
     if (!st[b].lin_active || !st[b].use_cheb || a.j > st[b].cheb_n) return;
     const bool last = a.j == st[b].cheb_n;
-    __shared__ double2 buf[FftLds<C>::SIZE];
+    __shared__ double2 buf[C];
     constexpr int T = FftThreads<C, LOGL>::T;
     const int tid = threadIdx.x;
     const int logL = LOGL ? LOGL : ax.logL, L = 1 << logL, N = L >> 1, nfft = C >> logL;
@@ -986,7 +782,7 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T), CHEB_MINW) void k_cheb_ro
     const double *ib = in + pb;
     double *ob = out + pb;
     auto put = [&](int row, int k, double e) { ob[(long)row * G.pitch + k] = e; };
-    constexpr bool DIRECT = FFT_R8 && LOGL >= 9 && LOGL <= 11;
+    constexpr bool DIRECT = LOGL >= 9 && LOGL <= 11;
     if (DIRECT) {
         constexpr int LL = 1 << (LOGL ? LOGL : 1), LG = LOGL ? LOGL : 1;
         struct RowIngest {
@@ -1213,7 +1009,7 @@ template <int FIRST, int C, int LOGL>
 __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_adj_rows_fwd(Geom G, FftAxis ax, AdjSweepArgs a, double *__restrict__ out,
                                                                           TrajState *__restrict__ st) {
     const int b = blockIdx.z;
-    __shared__ double2 buf[FftLds<C>::SIZE];
+    __shared__ double2 buf[C];
     __shared__ double s4[4];
     constexpr int T = FftThreads<C, LOGL>::T;
     const int tid = threadIdx.x;
@@ -1330,7 +1126,7 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_adj_rows_fwd(Geom 
     };
     double *ob = out + pb;
     auto put = [&](int row, int k, double e) { ob[(long)row * G.pitch + k] = e; };
-    constexpr bool DIRECT = FFT_R8 && LOGL >= 9 && LOGL <= 11;
+    constexpr bool DIRECT = LOGL >= 9 && LOGL <= 11;
     if (DIRECT) {
         struct Emit {
             enum { ACTIVE = 1, TO_LDS = 0 };
@@ -1346,20 +1142,9 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_adj_rows_fwd(Geom 
                 }
             }
         };
-        struct Ingest {
-            enum { ACTIVE = 1 };
-            decltype(node) &node_;
-            int row0_;
-            __device__ __forceinline__ double2 operator()(int idx) const {
-                constexpr int LL = 1 << (LOGL ? LOGL : 1);
-                const int f = idx >> (LOGL ? LOGL : 1), i = idx & (LL - 1);
-                const bool owner = i <= LL / 2;
-                const int m = owner ? i : LL - i, ra = row0_ + 2 * f;
-                return make_double2(node_(ra, m, owner), node_(ra + 1, m, owner));
-            }
-        };
-#if CG_ROWS_STAGED
         // every node once (no second visit for the mirror half of the even extension): stage the image, then transform
+        // (feeding the first FFT pass from global memory reads each operand twice; staging: -5 % on the march,
+        // profiles/r02_fft_variants.txt)
         for (int idx = tid; idx < nfft * n1; idx += T) {
             const int f = nfft == 1 ? 0 : idx / n1, j = idx - f * n1;
             const int ra = row0 + 2 * f;
@@ -1369,9 +1154,6 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_adj_rows_fwd(Geom 
         }
         __syncthreads();
         fft_lds<C, LOGL>(buf, ax, Emit{put, row0, G.ns});
-#else
-        fft_lds<C, LOGL>(buf, ax, Emit{put, row0, G.ns}, Ingest{node, row0});
-#endif
     } else {
         const float inv_n1 = 1.0f / (float)n1;
         for (int idx = tid; idx < nfft * n1; idx += T) {
@@ -1422,62 +1204,34 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_dct_cols(Geom G, F
                                                   const TrajState *__restrict__ st, int gate) {
     const int b = blockIdx.z;
     if (gate && !gate_open(st[b], gate)) return;
-    __shared__ double2 buf[FftLds<C>::SIZE];
+    __shared__ double2 buf[C];
     constexpr int T = FftThreads<C, LOGL>::T;
     const int tid = threadIdx.x;
     const int logL = LOGL ? LOGL : ax.logL, L = 1 << logL, N = L >> 1, nfft = C >> logL, ncol = 2 * nfft;
     const int col0 = xcd_remap(blockIdx.x, gridDim.x) * ncol;
     const double *ib = in + b * G.plane;
-    double *sb = reinterpret_cast<double *>(buf);
     const int n1 = N + 1;
-    int lc = 0;                                   // log2(ncol)
-    while ((1 << lc) < ncol) ++lc;
-    constexpr bool DIRECT = FFT_R8 && LOGL >= 9 && LOGL <= 11;
+    constexpr bool DIRECT = LOGL >= 9 && LOGL <= 11;
     constexpr int LL = 1 << (LOGL ? LOGL : 1), LG = LOGL ? LOGL : 1;
-    if (!(DIRECT && FFT_COLS_INGEST && (FFT_COLS_EMIT & 1))) {
-#if FFT_COLS_PAIR
-        // a column pair is 16 contiguous, 16-byte aligned bytes of a row (col0 even, pitch a multiple of 8): one b128 load
-        // and one b128 LDS store per row instead of two 8-byte ones from two lanes
-        for (int idx = tid; idx < n1 * nfft; idx += T) {
-            const int r = nfft == 1 ? idx : idx / nfft, f = nfft == 1 ? 0 : idx - r * nfft;
-            const int ca = col0 + 2 * f;
-            const double *p = ib + (long)r * G.pitch + ca;
-            double2 v = make_double2(0.0, 0.0);
-            if (ca + 1 < G.nf) v = *reinterpret_cast<const double2 *>(p);
-            else if (ca < G.nf) v.x = p[0];
-            buf[swz<LOGL>(f * L + r)] = v;
-            if (r > 0 && r < N) buf[swz<LOGL>(f * L + L - r)] = v;
-        }
-        if (false)
-#endif
-        for (int idx = tid; idx < n1 * ncol; idx += T) {
-            const int r = idx >> lc, cc = idx & (ncol - 1);
-            const int col = col0 + cc;
-            const double v = col < G.nf ? ib[(long)r * G.pitch + col] : 0.0;
-            const int f = cc >> 1, comp = cc & 1;
-            sb[2 * swz<LOGL>(f * L + r) + comp] = v;
-            if (r > 0 && r < N) sb[2 * swz<LOGL>(f * L + L - r) + comp] = v;
-        }
-        __syncthreads();
+    // a column pair is 16 contiguous, 16-byte aligned bytes of a row (col0 even, pitch a multiple of 8): one b128 load
+    // and one b128 LDS store per row instead of two 8-byte ones from two lanes (-1.3 % on the march,
+    // profiles/r02_fft_variants.txt)
+    for (int idx = tid; idx < n1 * nfft; idx += T) {
+        const int r = nfft == 1 ? idx : idx / nfft, f = nfft == 1 ? 0 : idx - r * nfft;
+        const int ca = col0 + 2 * f;
+        const double *p = ib + (long)r * G.pitch + ca;
+        double2 v = make_double2(0.0, 0.0);
+        if (ca + 1 < G.nf) v = *reinterpret_cast<const double2 *>(p);
+        else if (ca < G.nf) v.x = p[0];
+        buf[swz<LOGL>(f * L + r)] = v;
+        if (r > 0 && r < N) buf[swz<LOGL>(f * L + L - r)] = v;
     }
-    // first pass of the forward transform fed from global memory: entry i of the even extension of columns col0 + 2f, + 1
-    struct ColIngest {
-        enum { ACTIVE = 1 };
-        const double *ib_;
-        long pitch_;
-        int col0_, nf_;
-        __device__ __forceinline__ double2 operator()(int idx) const {
-            const int f = idx >> LG, i = idx & (LL - 1), m = i <= LL / 2 ? i : LL - i;
-            const int ca = col0_ + 2 * f;
-            const double *p = ib_ + (long)m * pitch_ + ca;
-            return make_double2(ca < nf_ ? p[0] : 0.0, ca + 1 < nf_ ? p[1] : 0.0);
-        }
-    };
+    __syncthreads();
     const double c1 = sp.c1a + sp.c1b * st[b].dbar;
     const int mmode = (sp.mult_m && st[b].scaled) ? 2 : sp.mult_m;      // right-scaled CG form of this trajectory's solve
     double *ob = out + b * G.plane;
     // forward transform; with a compile-time plan its last pass writes the outputs back already multiplied by the
-    // spectral multiplier (FFT_COLS_EMIT & 1), otherwise a separate pass over the image does
+    // spectral multiplier, otherwise a separate pass over the image does
     struct ScaleEmit {
         enum { ACTIVE = 1, TO_LDS = 1 };
         double2 *buf_;
@@ -1496,7 +1250,7 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_dct_cols(Geom G, F
             buf_[swz<LOGL>(idx)] = v;
         }
     };
-    constexpr bool FUSE = FFT_COLS_FUSE && DIRECT && FftRegOk<C, LOGL>::V && !FFT_COLS_INGEST && !(FFT_COLS_EMIT & 2);
+    constexpr bool FUSE = DIRECT && FftRegOk<C, LOGL>::V;
     if constexpr (FUSE) {
         // first transform, its last pass kept in registers; multiplier; second transform fed from those registers: one
         // LDS round trip and one barrier pair less than ScaleEmit, same arithmetic
@@ -1515,11 +1269,8 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_dct_cols(Geom G, F
             xr[s].y *= fb;
         }
         fft_lds<C, LOGL, FftNoEmit, FftNoIngest, 2>(buf, ax, FftNoEmit(), FftNoIngest(), xr);
-    } else if (DIRECT && (FFT_COLS_EMIT & 1)) {
-        if (FFT_COLS_INGEST)
-            fft_lds<C, LOGL>(buf, ax, ScaleEmit{buf, sp, c1, scale, col0, G.nf, mmode}, ColIngest{ib, (long)G.pitch, col0, G.nf});
-        else
-            fft_lds<C, LOGL>(buf, ax, ScaleEmit{buf, sp, c1, scale, col0, G.nf, mmode});
+    } else if (DIRECT) {
+        fft_lds<C, LOGL>(buf, ax, ScaleEmit{buf, sp, c1, scale, col0, G.nf, mmode});
     } else {
         fft_lds<C, LOGL>(buf, ax);
         for (int idx = tid; idx < nfft * L; idx += T) {
@@ -1537,28 +1288,8 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_dct_cols(Geom G, F
         }
         __syncthreads();
     }
-    // second transform; the wanted half of its last pass's outputs can go straight to global memory (FFT_COLS_EMIT & 2)
-    struct ColEmit {
-        enum { ACTIVE = 1, TO_LDS = 0 };
-        double *ob_;
-        long pitch_;
-        int col0_, nf_;
-        __device__ __forceinline__ void operator()(int idx, double2 v) const {
-            const int f = idx >> LG, k = idx & (LL - 1);
-            if (k <= LL / 2) {
-                const int ca = col0_ + 2 * f;
-                double *po = ob_ + (long)k * pitch_ + ca;
-                if (ca < nf_) po[0] = v.x;
-                if (ca + 1 < nf_) po[1] = v.y;
-            }
-        }
-    };
-    if (DIRECT && (FFT_COLS_EMIT & 2)) {
-        fft_lds<C, LOGL>(buf, ax, ColEmit{ob, (long)G.pitch, col0, G.nf});
-        return;
-    }
+    // second transform
     if constexpr (!FUSE) fft_lds<C, LOGL>(buf, ax);
-#if FFT_COLS_PAIR
     for (int idx = tid; idx < n1 * nfft; idx += T) {
         const int r = nfft == 1 ? idx : idx / nfft, f = nfft == 1 ? 0 : idx - r * nfft;
         const int ca = col0 + 2 * f;
@@ -1566,13 +1297,6 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_dct_cols(Geom G, F
         double *p = ob + (long)r * G.pitch + ca;
         if (ca + 1 < G.nf) *reinterpret_cast<double2 *>(p) = v;
         else if (ca < G.nf) p[0] = v.x;
-    }
-    return;
-#endif
-    for (int idx = tid; idx < n1 * ncol; idx += T) {
-        const int r = idx >> lc, cc = idx & (ncol - 1);
-        const int col = col0 + cc;
-        if (col < G.nf) ob[(long)r * G.pitch + col] = sb[2 * swz<LOGL>((cc >> 1) * L + r) + (cc & 1)];
     }
 }
 

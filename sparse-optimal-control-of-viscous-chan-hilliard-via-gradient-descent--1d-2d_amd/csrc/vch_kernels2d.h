@@ -146,11 +146,7 @@ __device__ __forceinline__ double lap_at(const double *s, int p, double ax, doub
 __device__ __forceinline__ double reglog(double phi) {   // F2:86-102 with delta_sep = 1e-2
     const double eps = 0.5 * DELTA_SEP;                  // max(1e-8, delta_sep/2)
     double p = fmin(fmax(phi, -1.0 + eps), 1.0 - eps);
-#ifdef VCH_FAKE_LOG                                      // timing experiment only (wrong numbers): how much of the evaluation
-    return 2.0 * p * (1.0 + 0.33 * p * p);               // kernels' time is the logarithm and the quotient?
-#else
     return log((1.0 + p) / (1.0 - p));
-#endif
 }
 
 __device__ __forceinline__ double jac_diag(double phi, double tau_dt, double c1) {   // F2:243-244
@@ -1128,9 +1124,6 @@ __device__ __forceinline__ void fin_reduce(const double *part, int nblk, int b, 
 // (A per-thread copy `TrajState S = st[b]` lives in private memory -- the record has arrays indexed at run time -- and
 // costs ~120 scratch instructions and 70 one-lane global loads / stores per launch; through a reference to global memory
 // every field access is a round trip.)
-#ifndef FIN_LDS
-#define FIN_LDS 1
-#endif
 __device__ __forceinline__ void traj_copy_in(TrajState &dst, const TrajState *src) {
     const unsigned *s = reinterpret_cast<const unsigned *>(src);
     unsigned *d = reinterpret_cast<unsigned *>(&dst);
@@ -1261,7 +1254,6 @@ __global__ void k_fin_residual(TrajState *st, const double *__restrict__ part, i
                                double *__restrict__ hist, double kappa, double dt, double lin_tol, double eta, int guess,
                                SolveOpts so) {
     const int b = blockIdx.x;
-#if FIN_LDS
     __shared__ TrajState S;
     traj_copy_in(S, st + b);
     if (MODE == 2) {               // after k_eval<0> without the fin step inside: the record has not been armed yet
@@ -1282,22 +1274,6 @@ __global__ void k_fin_residual(TrajState *st, const double *__restrict__ part, i
     if (threadIdx.x == 0)
         fin_residual_update<(MODE == 1 ? 1 : 0)>(S, v, primed, hist + (long)b * HIST_CAP, kappa, dt, lin_tol, eta, so);
     traj_copy_out(st + b, S);
-#else
-    TrajState S = st[b];
-    if (MODE == 2) {
-        if (S.frozen) return;
-        newton_begin(S);
-        S.slot = 1 - S.slot;
-    }
-    if (!S.newton_active || !S.need_trial) return;
-    double v[NPART];
-    const int op[NPART] = {0, 0, 1, 2, 0, 0};
-    const bool primed = guess_bit((unsigned)guess, b) && (MODE != 1 || S.iters == 1);
-    fin_reduce(part, nblk, b, v, op, primed ? 5 : 4);
-    if (threadIdx.x != 0) return;
-    fin_residual_update<(MODE == 1 ? 1 : 0)>(S, v, primed, hist + (long)b * HIST_CAP, kappa, dt, lin_tol, eta, so);
-    st[b] = S;
-#endif
 }
 
 template <int MODE>
@@ -1440,12 +1416,9 @@ __device__ __forceinline__ void fin_reduce_agent(const double *part, int nblk, i
 #ifndef EVAL_MINBLK
 #define EVAL_MINBLK 5          // workgroups per CU the register allocation must allow (LDS allows 5)
 #endif
-#ifndef EVAL_PREFETCH
-#define EVAL_PREFETCH 1        // 1: every global operand of the later phases is loaded into registers BEFORE the first barrier,
-                               // so a workgroup pays the global-memory latency once instead of once per phase (march at 8
-                               // trajectories 0.533 -> 0.517 s, bench 5.17 -> 5.31; with the register cap lifted to fit them
-                               // all, 122 VGPRs = 4 workgroups per CU: 0.551 s; profiles/r03_fused_ab.txt)
-#endif
+// Every global operand of the later phases is loaded into registers BEFORE the first barrier, so a workgroup pays the
+// global-memory latency once instead of once per phase (march at 8 trajectories 0.533 -> 0.517 s, bench 5.17 -> 5.31; with
+// the register cap lifted to fit them all, 122 VGPRs = 4 workgroups per CU: 0.551 s; profiles/r03_fused_ab.txt).
 // FIN_INSIDE: the hand-off variant (VCH_FUSED=1).  The default variant ends with the partials and carries neither the record
 // copy of the fin step (584 B of private memory per thread) nor the counter traffic.
 template <int MODE, bool FIN_INSIDE>
@@ -1514,7 +1487,6 @@ __global__ __launch_bounds__(NTH, EVAL_MINBLK) void k_eval(Geom G, Phys P, TrajS
             load_tile<2>(sp, phi_s + src * slot_stride + pb, G, c0, r0);
         }
         load_tile<1>(sm, mu_s + src * slot_stride + pb, G, c0, r0);          // mu of the old level
-#if EVAL_PREFETCH
         double vW[I1], vU0[I1], vU1[I1];
 #pragma unroll
         for (int i = 0; i < I1; ++i) {
@@ -1529,7 +1501,6 @@ __global__ __launch_bounds__(NTH, EVAL_MINBLK) void k_eval(Geom G, Phys P, TrajS
                 vU1[i] = unp1 ? unp1[b * u_stride + o] : 0.0;
             }
         }
-#endif
         __syncthreads();
         for (int k = 0; k < TY / 4; ++k) {                                   // c_mu needs the Laplacian of the old mu
             int ly = ly0 + 4 * k, r = r0 + ly, c = c0 + lx;
@@ -1552,12 +1523,7 @@ __global__ __launch_bounds__(NTH, EVAL_MINBLK) void k_eval(Geom G, Phys P, TrajS
             int gr = refl(rr, G.ns), gc = refl(cc, G.nf);
             int p2 = (ly + 1) * W2 + lxx + 1;
             long o = (long)gr * G.pitch + gc, ob = pb + o;
-#if EVAL_PREFETCH
             const double u0 = vU0[i], u1 = vU1[i], wo = vW[i];
-#else
-            const double u0 = un ? un[b * u_stride + o] : 0.0, u1 = unp1 ? unp1[b * u_stride + o] : 0.0;
-            const double wo = w[ob];
-#endif
             const double wn = ((gdt - 0.5) * wo + 0.5 * (u1 + u0)) / (gdt + 0.5);
             const double ph = sp[p2], lp = lap_at<W2>(sp, p2, G.ax, G.ay);
             const double m0 = -P.kappa * lp + (P.c1 * reglog(ph) - 2.0 * P.c2 * ph) - wn;
@@ -1596,7 +1562,6 @@ __global__ __launch_bounds__(NTH, EVAL_MINBLK) void k_eval(Geom G, Phys P, TrajS
         const double *phi_o = phi_s + src * slot_stride + pb, *mu_o = mu_s + src * slot_stride + pb;
         const double *D_o = D_s + src * slot_stride + pb, *R_o = Rphi_s + src * slot_stride + pb;
         constexpr int N1 = (TY + 2) * W1, I1 = (N1 + NTH - 1) / NTH;      // halo-1 elements, per thread
-#if EVAL_PREFETCH
         // phase-1 loads first (the compiler's vmcnt then waits for them only), the later phases' operands right behind
         double pd[(W2 * (TY + 4) + NTH - 1) / NTH], pp[(W2 * (TY + 4) + NTH - 1) / NTH];
         {
@@ -1638,16 +1603,6 @@ __global__ __launch_bounds__(NTH, EVAL_MINBLK) void k_eval(Geom G, Phys P, TrajS
                 sp[e] = pp[i] + S_alpha * pd[i];
             }
         }
-#else
-        for (int e = threadIdx.x; e < W2 * (TY + 4); e += NTH) {
-            int ly = e / W2, lxx = e - ly * W2;
-            int gr = refl(r0 - 2 + ly, G.ns), gc = refl(c0 - 2 + lxx, G.nf);
-            long o = (long)gr * G.pitch + gc;
-            const double d = dphi[pb + o];
-            sd[e] = d;
-            sp[e] = phi_o[o] + S_alpha * d;
-        }
-#endif
         __syncthreads();
 #pragma unroll
         for (int i = 0; i < I1; ++i) {
@@ -1655,13 +1610,7 @@ __global__ __launch_bounds__(NTH, EVAL_MINBLK) void k_eval(Geom G, Phys P, TrajS
             if (e < N1) {
                 int ly = e / W1, lxx = e - ly * W1;
                 int p2 = (ly + 1) * W2 + lxx + 1;
-#if EVAL_PREFETCH
                 const double Dv = vD[i], Rv = vR[i], Mv = vM[i];
-#else
-                int gr = refl(r0 - 1 + ly, G.ns), gc = refl(c0 - 1 + lxx, G.nf);
-                long o = (long)gr * G.pitch + gc;
-                const double Dv = D_o[o], Rv = R_o[o], Mv = mu_o[o];
-#endif
                 const double dm = 2.0 * ((-0.5 * P.kappa * lap_at<W2>(sd, p2, G.ax, G.ay) + Dv * sd[p2]) + Rv);
                 sm[e] = Mv + S_alpha * dm;
             }
@@ -1673,11 +1622,7 @@ __global__ __launch_bounds__(NTH, EVAL_MINBLK) void k_eval(Geom G, Phys P, TrajS
             rm[k] = mt[k] = 0.0;
             if (r < G.ns && c < G.nf) {
                 int p1 = (ly + 1) * W1 + lx + 1, p2 = (ly + 2) * W2 + lx + 2;
-#if EVAL_PREFETCH
                 const double cm = vcm[k];
-#else
-                const double cm = cmu[pb + (long)r * G.pitch + c];
-#endif
                 rm[k] = sp[p2] / dt - 0.5 * lap_at<W1>(sm, p1, G.ax, G.ay) + cm;
                 mt[k] = sm[p1];
             }
@@ -1689,12 +1634,7 @@ __global__ __launch_bounds__(NTH, EVAL_MINBLK) void k_eval(Geom G, Phys P, TrajS
             if (e < N1) {
                 int ly = e / W1, lxx = e - ly * W1;
                 int p2 = (ly + 1) * W2 + lxx + 1;
-#if EVAL_PREFETCH
                 const double cp = vC[i];
-#else
-                int gr = refl(r0 - 1 + ly, G.ns), gc = refl(c0 - 1 + lxx, G.nf);
-                const double cp = cphi[pb + (long)gr * G.pitch + gc];
-#endif
                 double ph = sp[p2];
                 sm[e] = tdt * ph - 0.5 * P.kappa * lap_at<W2>(sp, p2, G.ax, G.ay) + P.c1 * reglog(ph) - 0.5 * sm[e] + cp;
             }
@@ -2003,12 +1943,8 @@ struct ChebFin {
 };
 __global__ void k_fin_ceiling(TrajState *st, const double *__restrict__ part, int nblk, int strict, int fin_copy, ChebFin cheb) {
     const int b = blockIdx.x;
-#if FIN_LDS
     __shared__ TrajState S;                 // the record in LDS, copied in and out by the whole wavefront (see k_fin_residual)
     traj_copy_in(S, st + b);
-#else
-    TrajState S = st[b];
-#endif
     if (!S.newton_active || S.need_trial) return;
     if ((cheb.enq >= 0) != (S.use_cheb != 0)) return;      // the other form's launch sequence looks after this trajectory
     int lin_active = S.lin_active;          // (a value every lane keeps: the record itself is advanced by lane 0 only)
@@ -2061,11 +1997,7 @@ __global__ void k_fin_ceiling(TrajState *st, const double *__restrict__ part, in
         S.best_norm = 1e300;
         S.best_alpha = S.alpha;
     }
-#if FIN_LDS
     traj_copy_out(st + b, S);
-#else
-    if (threadIdx.x == 0) st[b] = S;
-#endif
 }
 
 __global__ void k_fin_mass(TrajState *st, const double *__restrict__ part, int nblk, int init) {
