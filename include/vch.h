@@ -81,7 +81,11 @@ typedef struct vch_stats {
 typedef struct vch2d_ctx vch2d_ctx;
 
 /* Create a context for `batch` trajectories and marches of at most `max_steps` steps on
- * HIP device `device`.  History buffers are allocated lazily by the calls that need them. */
+ * HIP device `device`.  History buffers are allocated lazily by the calls that need them.
+ * Up to 32 trajectories, each one chooses the starting guesses of its march and adjoint solves
+ * from its own history, so a trajectory's results are bit for bit those of a single-trajectory
+ * context.  Above 32, the batch shares one guess policy, fed by its worst trajectory: results
+ * are still correct to the solvers' tolerance, but no longer bitwise equal to single runs. */
 vch2d_ctx *vch2d_create(const vch2d_params *p, int batch, int max_steps, int device);
 void vch2d_destroy(vch2d_ctx *ctx);
 int vch2d_batch(const vch2d_ctx *ctx);

@@ -257,7 +257,11 @@ def newton_step(phi_old, mu_old, w_old, w_new, dt, P: Params2D, hx, hy, L=None,
     guess (phi_old, mu_init(phi_old, w_new)) (F2:350-351), absolute stop
     ||R||_2 < 1e-6, step ceiling alpha_max = min(2, 0.9*min ratio) with
     alpha = min(1, alpha_max) (F2:377-391), Armijo (eta=1e-4, <=12 halvings) with
-    best-trial fallback (F2:394-423)."""
+    best-trial fallback (F2:394-423).
+
+    `stats` (optional dict) accumulates "solves" (linear solves), "newton_its" (residual norms
+    recorded, the initial one included) and "armijo_trials" (trial residuals evaluated inside
+    the Armijo loop, the accepted one included)."""
     Nx, Ny = phi_old.shape[0] - 1, phi_old.shape[1] - 1
     if L is None:
         L = lap_matrix(Nx, Ny, hx, hy)
@@ -266,6 +270,7 @@ def newton_step(phi_old, mu_old, w_old, w_new, dt, P: Params2D, hx, hy, L=None,
     n = phi_old.size
     hist = []
     nsolve = 0
+    ntrial = 0
 
     def resid(ph, mu):
         return np.concatenate([
@@ -299,6 +304,7 @@ def newton_step(phi_old, mu_old, w_old, w_new, dt, P: Params2D, hx, hy, L=None,
         best = (np.inf, phi_new, mu_new)
         accepted = False
         for _t in range(ARMIJO_TRIALS):
+            ntrial += 1
             ph_t = phi_new + alpha * dphi.reshape(phi_new.shape)
             mu_t = mu_new + alpha * dmu.reshape(mu_new.shape)
             nRt = np.linalg.norm(resid(ph_t, mu_t))
@@ -314,6 +320,7 @@ def newton_step(phi_old, mu_old, w_old, w_new, dt, P: Params2D, hx, hy, L=None,
     if stats is not None:
         stats["solves"] = stats.get("solves", 0) + nsolve
         stats["newton_its"] = stats.get("newton_its", 0) + len(hist)
+        stats["armijo_trials"] = stats.get("armijo_trials", 0) + ntrial
     return (phi_new, mu_new, hist) if return_history else (phi_new, mu_new)
 
 
@@ -330,6 +337,9 @@ def time_grid(T, dt, time_tol=1e-10):
         t += d
         ts.append(min(t, T))
     return np.array(ts), np.array(dts)
+
+
+_COUNTS = ("newton_its", "solves", "armijo_trials")
 
 
 def forward(P: Params2D, control=None, phi0=None, seed=42, amp=0.1, max_steps=None, stats=None):
@@ -364,7 +374,10 @@ def forward(P: Params2D, control=None, phi0=None, seed=42, amp=0.1, max_steps=No
             u_n = u_np1 = np.zeros_like(phi)
         _t_step = _time.perf_counter()
         w_new = w_filter(w, dts, P.gamma, u_n, u_np1)
+        before = {k: stats.get(k, 0) for k in _COUNTS} if stats is not None else None
         phi_new, mu_new = newton_step(phi, mu, w, w_new, dts, P, hx, hy, L=L, stats=stats)
+        if stats is not None:           # per-step (newton_its, solves, armijo_trials)
+            stats.setdefault("step_counts", []).append(tuple(stats.get(k, 0) - before[k] for k in _COUNTS))
         phi = np.clip(phi_new, lo, hi)
         err = np.sum(wts_h * phi) - mass0
         if abs(err) > 1e-16:                                   # F2:567-577
