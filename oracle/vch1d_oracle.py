@@ -142,28 +142,26 @@ def jac_dense(pn, dt, P, L):
     return J
 
 
-def _solve_newton_banded(pn, dt, P, h, R):
-    """Same matrix as jac_dense with unknowns interleaved (phi_i, mu_i): bandwidth 3."""
+def newton_rows(pn, dt, P, h):
+    """Row-wise coefficients (offsets -3..3, the convention of _rows_to_banded) of jac_dense's matrix with the
+    unknowns interleaved (dphi_0, dmu_0, dphi_1, dmu_1, ...): row 2i is the phi equation of node i, row 2i+1 its
+    mu equation.  Offsets +-3 are structurally zero (the bandwidth is 2); they keep LAPACK's band (3, 3)."""
     n = pn.size
-    a = 1.0 / (h * h)
-    lo = np.full(n, a); lo[-1] = 2 * a; lo[0] = 0.0       # coefficient of v[i-1] in (Lv)[i]
-    up = np.full(n, a); up[0] = 2 * a; up[-1] = 0.0       # coefficient of v[i+1]
-    dg = -2.0 * a
-    ab = np.zeros((7, 2 * n))                              # l = u = 3
-    D = jac_diag(pn, dt, P)
-    ev, od = np.arange(0, 2 * n, 2), np.arange(1, 2 * n, 2)
+    lo, dg, up = _lap_rows(n, h)
+    rows = tuple(np.zeros(2 * n) for _ in range(7))
+    m2, m1, d0, p1, p2 = rows[1:6]
+    m2[0::2], d0[0::2], p1[0::2], p2[0::2] = (-0.5 * P.kappa * lo, -0.5 * P.kappa * dg + jac_diag(pn, dt, P), -0.5,
+                                              -0.5 * P.kappa * up)
+    m2[1::2], m1[1::2], d0[1::2], p2[1::2] = -0.5 * lo, 1.0 / dt, -0.5 * dg, -0.5 * up
+    return rows
 
-    def put(r, c, val):
-        ab[3 + r - c, c] = val
-    put(ev, ev, -0.5 * P.kappa * dg + D)
-    put(ev, od, -0.5)
-    put(od, ev, 1.0 / dt)
-    put(od, od, -0.5 * dg)
-    put(ev[1:], ev[:-1], -0.5 * P.kappa * lo[1:]); put(ev[:-1], ev[1:], -0.5 * P.kappa * up[:-1])
-    put(od[1:], od[:-1], -0.5 * lo[1:]); put(od[:-1], od[1:], -0.5 * up[:-1])
+
+def _solve_newton_banded(pn, dt, P, h, R):
+    """Same matrix as jac_dense with unknowns interleaved (phi_i, mu_i), newton_rows."""
+    n = pn.size
     rhs = np.empty(2 * n)
     rhs[0::2], rhs[1::2] = -R[:n], -R[n:]
-    sol = solve_banded((3, 3), ab, rhs)
+    sol = solve_banded((3, 3), _rows_to_banded(newton_rows(pn, dt, P, h)), rhs)
     return np.concatenate([sol[0::2], sol[1::2]])
 
 
@@ -195,13 +193,19 @@ def newton_step(phi_old, mu_old, w_old, w_new, dt, P, h, solver="dense", return_
     """F1:139-235.  Initial guess (phi_old, mu_old) (F1:141-142); step
     alpha = min(1, 0.9*alpha_max) (F1:198-212); Armijo eta=1e-3 with the extra admissibility
     test all|phi_t| < 1-delta (F1:219); 12 failed halvings END the whole Newton loop with
-    the current iterate (F1:227-229)."""
+    the current iterate (F1:227-229).
+
+    `stats` (optional dict) accumulates the engine's counts under vch2d_oracle's names: "solves", "newton_its"
+    (residual norms recorded, the initial one included), "armijo_trials" (trial points that pass the admissibility
+    test, whose residual is evaluated), "failed_ls" (loops left through the line-search-failure return); and
+    appends the loop's last residual norm to "last_norms"."""
     pn, mn = phi_old.copy(), mu_old.copy()
     n = pn.size
     wts_h = h * trapz_weights(n)
     L = lap_dense(n - 1, h) if solver == "dense" else None
     hist = []
-    nsolve = 0
+    nsolve = ntrial = 0
+    failed = False
     for k in range(NEWTON_MAXIT):
         R = np.concatenate([residual_phi(pn, phi_old, mn, mu_old, w_new, w_old, dt, P, h),
                             residual_mu(pn, phi_old, mn, mu_old, dt, h)])
@@ -233,6 +237,7 @@ def newton_step(phi_old, mu_old, w_old, w_new, dt, P, h, solver="dense", return_
         for _ in range(12):
             pt, mt = pn + alpha * dphi, mn + alpha * dmu
             if np.all(np.abs(pt) < 1 - DELTA_SEP):
+                ntrial += 1
                 Rt = np.concatenate([residual_phi(pt, phi_old, mt, mu_old, w_new, w_old, dt, P, h),
                                      residual_mu(pt, phi_old, mt, mu_old, dt, h)])
                 if np.linalg.norm(Rt) <= (1 - ARMIJO_ETA * alpha) * nR:
@@ -240,9 +245,14 @@ def newton_step(phi_old, mu_old, w_old, w_new, dt, P, h, solver="dense", return_
                     break
             alpha *= 0.5
         if not ok:
+            failed = True
             break
     if stats is not None:
         stats["solves"] = stats.get("solves", 0) + nsolve
+        stats["newton_its"] = stats.get("newton_its", 0) + len(hist)
+        stats["armijo_trials"] = stats.get("armijo_trials", 0) + ntrial
+        stats["failed_ls"] = stats.get("failed_ls", 0) + int(failed)
+        stats.setdefault("last_norms", []).append(hist[-1])
     return (pn, mn, hist) if return_history else (pn, mn)
 
 
@@ -332,6 +342,97 @@ def _rows_matvec(rows, x):
     return y
 
 
+def _adjoint_comb(n, h, cL2, D):
+    """Row-wise coefficients (offsets -2..2) of I - tau L + cL2 L@L + diag(D) L with the frozen tau (B1:29-33);
+    D = None: no diagonal term."""
+    lo, dg, up = _lap_rows(n, h)
+    z, one = np.zeros(n), np.ones(n)
+    cL = -_FROZEN.tau + (0.0 if D is None else D)
+    return tuple(e + cL * l + cL2 * l2 for e, l, l2 in zip((z, z, one, z, z), (z, lo, dg, up, z), _penta_rows(n, h)))
+
+
+def adjoint_rows(phi_n, dt, h, n=None):
+    """Rows of the adjoint step matrix A(phi_n) = I - tau L + dt/2 L@L - dt/2 diag(fpp(phi_n)) L (B1:99-101, 116);
+    dt = 0 gives the terminal matrix I - tau L (B1:94), for which phi_n may be None if n is given."""
+    n = phi_n.size if n is None else n
+    return _adjoint_comb(n, h, 0.5 * dt, None if dt == 0 else -0.5 * dt * fpp(phi_n))
+
+
+def adjoint_rhs_rows(phi_np1, dt, h):
+    """Rows of B(phi_np1) = I - tau L - dt/2 L@L + dt/2 diag(fpp(phi_np1)) L, the step's right-hand side operator
+    (B1:103-113)."""
+    return _adjoint_comb(phi_np1.size, h, -0.5 * dt, 0.5 * dt * fpp(phi_np1))
+
+
+# ---------------------------------------------------------------------------------------
+# checkers for the engine's banded solves (test infrastructure)
+# ---------------------------------------------------------------------------------------
+def _residual_ld(rows, x, b):
+    """(b - A x, |A||x| + |b|) accumulated in np.longdouble."""
+    k = (len(rows) - 1) // 2
+    x, b = np.asarray(x, np.longdouble), np.asarray(b, np.longdouble)
+    n = x.size
+    r, s = b.copy(), np.abs(b)
+    for off, v in zip(range(-k, k + 1), rows):
+        i = np.arange(max(0, -off), min(n, n - off))
+        t = np.asarray(v[i], np.longdouble) * x[i + off]
+        r[i] -= t
+        s[i] += np.abs(t)
+    return r, s
+
+
+def backward_error(rows, x, b, f=None):
+    """Componentwise (Oettli-Prager) backward error of x as a solution of A x = b, A given by its rows
+    (_rows_to_banded convention):  omega = max_i |b - A x|_i / (|A||x| + f)_i, the smallest omega such that
+    (A + E) x = b + e with |E| <= omega |A|, |e| <= omega f.  f defaults to |b|; a right-hand side formed as
+    b = B y + s passes f = |B||y| + |s|, the size of the data it is made of.  A backward-stable solve gives a few eps.
+
+    The residual and the denominator are accumulated in np.longdouble, which is 80-bit extended on x86-64
+    (eps 1.1e-19): omega is then exact to ~1e-3 eps.  Where longdouble is only double, omega is still accurate to a
+    few eps.  b may be a longdouble array (a right-hand side formed in extended precision)."""
+    r, s = _residual_ld(rows, x, b)
+    if f is not None:
+        s = s - np.abs(np.asarray(b, np.longdouble)) + np.asarray(f, np.longdouble)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        w = np.where(s > 0, np.abs(r) / s, np.where(r == 0, 0.0, np.inf))
+    return float(np.max(w))
+
+
+def hp_solve(rows, b, steps=2):
+    """High-precision reference solution of A x = b: LAPACK banded LU (solve_banded) followed by `steps` steps of
+    iterative refinement with the residual computed in np.longdouble."""
+    k = (len(rows) - 1) // 2
+    ab = _rows_to_banded(rows)
+    x = solve_banded((k, k), ab, np.asarray(b, np.float64))
+    for _ in range(steps):
+        x = x + solve_banded((k, k), ab, _residual_ld(rows, x, b)[0].astype(np.float64))
+    return x
+
+
+def _rows_to_csc(rows):
+    from scipy import sparse
+    k = (len(rows) - 1) // 2
+    n = rows[0].size
+    offs = list(range(-k, k + 1))
+    return sparse.diags([v[max(0, -o):min(n, n - o)] for o, v in zip(offs, rows)], offs, shape=(n, n), format="csc")
+
+
+def cond_estimate(rows, x, b):
+    """Condition number of A x = b for componentwise perturbations (Skeel):
+    cond = || |A^-1| (|A||x| + |b|) ||_inf / ||x||_inf, so that a solution with backward error omega has the
+    normwise relative forward error  ||x_hat - x||_inf / ||x||_inf <= omega * cond  (to first order).  Invariant
+    under row scaling, unlike ||A|| ||A^-1||.  || |A^-1| g ||_inf = || A^-1 diag(g) ||_inf is estimated with the
+    Hager-Higham 1-norm estimator (scipy onenormest, t = 1: deterministic) applied to its transpose, with A^-1 from
+    a sparse LU."""
+    from scipy.sparse.linalg import LinearOperator, onenormest, splu
+    lu = splu(_rows_to_csc(rows))
+    g = _residual_ld(rows, x, b)[1].astype(np.float64)
+    n = g.size
+    op = LinearOperator((n, n), dtype=np.float64, matvec=lambda v: g * lu.solve(np.ravel(v), trans="T"),
+                        rmatvec=lambda v: lu.solve(g * np.ravel(v)))
+    return float(onenormest(op, t=1)) / float(np.max(np.abs(x)))
+
+
 def backward(phi_hist, x, t_hist, b1, b2, phi_Q=None, phi_T=None, solver="dense", max_steps=None):
     """B1:48-126.  Physical parameters are the frozen defaults (B1:29-33); dt_n <= 0
     rows are skipped and stay zero (B1:110), so row 0 of p, q, r is zero because of the
@@ -352,15 +453,7 @@ def backward(phi_hist, x, t_hist, b1, b2, phi_Q=None, phi_T=None, solver="dense"
         p[-1] = np.linalg.solve(I - tau * L, b2 * (phi_hist[-1] - phi_T))
         q[-1] = -(L @ p[-1])
     else:
-        lo, dg, up = _lap_rows(n, h)
-        z = np.zeros(n)
-        one = np.ones(n)
-        Lr = (z, lo, dg, up, z)
-        L2r = _penta_rows(n, h)
-        comb = lambda cI, cL, cL2, D: tuple(cI * e + (cL + (0.0 if D is None else D)) * l + cL2 * l2
-                                            for e, l, l2 in zip((z, z, one, z, z), Lr, L2r))
-        p[-1] = solve_banded((2, 2), _rows_to_banded(comb(1.0, -tau, 0.0, None)),
-                             b2 * (phi_hist[-1] - phi_T))
+        p[-1] = solve_banded((2, 2), _rows_to_banded(adjoint_rows(None, 0.0, h, n=n)), b2 * (phi_hist[-1] - phi_T))
         q[-1] = -lap(p[-1], h)
     for k in range(M1 - 2, last - 1, -1):
         dt = t_hist[k + 1] - t_hist[k]
@@ -377,10 +470,8 @@ def backward(phi_hist, x, t_hist, b1, b2, phi_Q=None, phi_T=None, solver="dense"
                 p[k] = np.linalg.solve(A + 1e-10 * I, rhs)
             q[k] = -(L @ p[k])
         else:
-            Ar = comb(1.0, -tau, 0.5 * dt, -0.5 * dt * fpp(phi_hist[k]))
-            Br = comb(1.0, -tau, -0.5 * dt, 0.5 * dt * fpp(phi_hist[k + 1]))
-            rhs = _rows_matvec(Br, p[k + 1]) + src
-            p[k] = solve_banded((2, 2), _rows_to_banded(Ar), rhs)
+            rhs = _rows_matvec(adjoint_rhs_rows(phi_hist[k + 1], dt, h), p[k + 1]) + src
+            p[k] = solve_banded((2, 2), _rows_to_banded(adjoint_rows(phi_hist[k], dt, h)), rhs)
             q[k] = -lap(p[k], h)
         r[k] = ((gamma - 0.5 * dt) / (gamma + 0.5 * dt)) * r[k + 1] \
             + ((dt * 0.5) / (gamma + 0.5 * dt)) * (q[k] + q[k + 1])
@@ -476,11 +567,14 @@ class PGDResult:
     converged: bool = False
 
 
-def pgd(P: Params1D, O: OptParams1D, n_iter=None, choice_t=1, choice_q=1, solver="dense"):
+def pgd(P: Params1D, O: OptParams1D, n_iter=None, choice_t=1, choice_q=1, solver="dense", initial_phi=None,
+        stats=None):
     """G1:333-477: optimistic step with alpha_prev; on failure backtracking from
     alpha_prev (beta 0.8, <=5 trials, G1:73-113); alpha growth 1.2, plateau (10 its,
-    |dJ|<1e-7) -> 2.0; stop when the relative control change < 1e-5 and k > 10."""
-    fwd = lambda u: forward(P, control=u, solver=solver)
+    |dJ|<1e-7) -> 2.0; stop when the relative control change < 1e-5 and k > 10.
+    `initial_phi` replaces the seeded initial state of every march (as in forward); `stats` accumulates the
+    counts of every march (forward's stats)."""
+    fwd = lambda u: forward(P, control=u, initial_phi=initial_phi, solver=solver, stats=stats)
     phi_k, x, t_hist = fwd(None)
     u_k = np.zeros_like(phi_k)
     phi_T, phi_Q = build_targets(x, t_hist, phi_k[0].copy(), P.Lx, P.T, choice_t, choice_q)
