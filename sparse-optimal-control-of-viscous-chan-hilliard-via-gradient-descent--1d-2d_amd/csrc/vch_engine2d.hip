@@ -1650,16 +1650,43 @@ static int backward_core(vch2d_ctx *c, const double *phi_hist_dev, int M, const 
     bool redo = false;
     long iters = 0;
     const double accept = 10.0 * c->lin_tol;
+    std::vector<int> keep;                     // trajectories whose first pass stands
     for (int b = 0; b < c->B; ++b) {
         const TrajState &S = c->st_host[b];
         iters += S.lin_total;
         // a solve that ran out of sweeps above the solve tolerance's class: the schedule was too short somewhere
         if ((S.lin_unconv > 0 && S.lin_maxrel > accept) || (S.lin_active && S.lin_rel > accept)) redo = true;
+        else keep.push_back(b);
     }
     if (!redo) return 0;
+    // The second pass (rigorous budgets, no starting guesses) is for the trajectories whose schedule fell short.  It runs for
+    // the whole batch, so the sweeps of the others are set aside and put back afterwards: what a trajectory gets must not
+    // depend on its batch mates (vch.h, vch2d_create).  A rare path: the copies cost nothing where it matters.
+    double *outs[3] = {r_out, p_out, q_out};
+    const size_t blk = (size_t)(M + 1) * c->G.plane;
+    const long hs = hist_stride(c);
+    size_t nsave = 0;
+    for (double *o : outs)
+        if (o) nsave += keep.size();
+    double *save = nullptr;
+    if (nsave) {
+        HIPCHK(hipMalloc((void **)&save, nsave * blk * sizeof(double)));
+        size_t k = 0;
+        for (double *o : outs)
+            for (size_t i = 0; o && i < keep.size(); ++i, ++k)
+                HIPCHK(hipMemcpyAsync(save + k * blk, o + keep[i] * hs, blk * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    }
     const long syncs = c->n_sync, launches = c->n_launch;
     VCHCHK(reset_counters(c));
     VCHCHK(backward_pass(c, phi_hist_dev, M, t_hist, b1, b2, phiQ_dev, phiT_dev, r_out, p_out, q_out, true));
+    if (save) {
+        size_t k = 0;
+        for (double *o : outs)
+            for (size_t i = 0; o && i < keep.size(); ++i, ++k)
+                HIPCHK(hipMemcpyAsync(o + keep[i] * hs, save + k * blk, blk * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipFree(save));
+    }
     c->redo_iters = iters;                     // the first pass stays in the books (fill_stats, counters)
     c->n_sync += syncs;
     c->n_launch += launches;
