@@ -185,6 +185,27 @@ int vch2d_grad_prox(vch2d_ctx *ctx, const double *u, const double *r, int rows, 
 int vch2d_pgd_init(vch2d_ctx *ctx, const double *phi0, const double *phi_T, const double *phi_Q,
                    int ramp, double T, const double *t_hist, int M, const double *x, const double *y,
                    const vch_opt_params *opt, double *J0_out /* [B][5] */);
+/* The same with one parameter set PER TRAJECTORY, a warm start and a first step size (ABI version stays 3: detect this
+ * entry point and vch2d_pgd_kkt by symbol).  vch2d_pgd_init is this call with n_opts = 1 and u0 = alpha0 = NULL.
+ *   opts    n_opts parameter sets, n_opts = 1 (one set for the whole batch) or B (trajectory b takes opts[b]); anything
+ *           else is VCH_ERR_ARG.  Trajectory b's own values are used everywhere in the loop: b1 in the adjoint source, b2
+ *           in the terminal condition, b3 / kappa_sparsity / u_min / u_max in the gradient + prox step, the four weights
+ *           in the cost, alpha_max in the growth and plateau rules.  They live in a [B] table on the device that the
+ *           kernels index by trajectory; a kernel's arithmetic is that of the scalar form, so a trajectory computes the
+ *           same bits as in a single-trajectory context with its parameters (batches up to 32, see vch2d_create).
+ *           VCH_ERR_ARG, with a message that names the trajectory, before anything is launched: non-finite b1, b2, b3 or
+ *           kappa_sparsity, kappa_sparsity < 0, alpha_max <= 0, u_min > u_max (infinite bounds are legal).
+ *   u0      [B][M+1][Nx+1][Ny+1] start control or NULL (zeros).  Taken as given, NOT clipped to the box: the initial
+ *           march runs under it and J0_out is its cost under each trajectory's own weights.
+ *   alpha0  [B] or NULL.  NULL: the first alpha_prev is each trajectory's alpha_max (G2:293); otherwise alpha0[b] (finite,
+ *           > 0), capped at that trajectory's alpha_max.
+ * The iteration counter (the k of the stop rule `change < 1e-5 and k > 20`) and the plateau counter start at 0 as after
+ * vch2d_pgd_init, also under a warm start: a resumed run is a new run from u0, it does not inherit the saved run's k.
+ * max_iter is not read: the loop length is the n_iters of vch2d_pgd_iterate. */
+int vch2d_pgd_init_v(vch2d_ctx *ctx, const double *phi0, const double *phi_T, const double *phi_Q,
+                     int ramp, double T, const double *t_hist, int M, const double *x, const double *y,
+                     const vch_opt_params *opts, int n_opts, const double *u0 /* or NULL */,
+                     const double *alpha0 /* [B] or NULL */, double *J0_out /* [B][5] */);
 /* Run n_iters PGD iterations for every trajectory of the batch (optimistic step,
  * backtracking from 0.8 alpha_prev with beta 0.8 and <= 10 trials, alpha growth / plateau
  * rule, stop rule; G2:295-382).  Outputs [B][n_iters] unless noted; any may be NULL.
@@ -205,6 +226,23 @@ int vch2d_pgd_errors(vch2d_ctx *ctx, int n_iters, double *tracking_out, double *
 /* Copy resident PGD arrays to the host: what = 0 control u, 1 state history, 2 adjoint r,
  * 3 phi_Q.  out [B][M+1][Nx+1][Ny+1]. */
 int vch2d_pgd_get(vch2d_ctx *ctx, int what, double *out);
+/* KKT sparsity statistic `u* = 0 <=> |r*| <= kappa_sparsity` of the resident iterate, counted on the device (replaces
+ * pulling u and r through vch2d_pgd_get for sparsity_statistics / verify_sparsity_condition, S2:238-297; only 3 B integers
+ * cross to the host).
+ *   counts_out[b] = { #nodes |u| < tol, #nodes |r| <= kappa_sparsity of trajectory b, #nodes where the two predicates
+ *                     agree, #nodes } over all (M+1)(Nx+1)(Ny+1) nodes of trajectory b; tol <= 0 means 1e-6.
+ *   refresh != 0  first runs the adjoint sweep on the resident state (each trajectory's own b1, b2; the accuracy of
+ *                 vch2d_backward), as the reference's main() does with run_backward after the loop (G2:424).  The result
+ *                 stays in the resident r; the next vch2d_pgd_iterate recomputes it anyway.
+ *   refresh == 0  uses the resident r as it is: the adjoint the last iteration started from, i.e. that of the iterate
+ *                 BEFORE the last accepted step.  VCH_ERR_STATE if no sweep has run since vch2d_pgd_init.
+ *   stationarity_out[b] (or NULL) = ||prox_1(u) - u||_2 / (||u||_2 + 1e-9): prox_1 is the gradient + prox step with
+ *                 alpha = 1 and trajectory b's parameters, written to the trial-control scratch.
+ * The control, the state history and the loop's bookkeeping are not touched: with refresh == 0 the following iterations
+ * are bit for bit those of an uninterrupted run.  VCH_ERR_STATE before vch2d_pgd_init.  Launches and looks are counted
+ * by vch2d_counters like those of any other call. */
+int vch2d_pgd_kkt(vch2d_ctx *ctx, int refresh, double tol, int64_t *counts_out /* [B][4] */,
+                  double *stationarity_out /* [B] or NULL */);
 /* Per-trajectory cost scalars {J1,J2,J3,J4,J} of the current iterate on the DEVICE
  * (5*B doubles), for the caller's RCCL all-reduce; returns a device pointer via *ptr_dev. */
 int vch2d_pgd_cost_dev(vch2d_ctx *ctx, double **ptr_dev);
@@ -223,7 +261,9 @@ int vch2d_counters(vch2d_ctx *ctx, int64_t *out /* [2] */);
  *   vch_comm_allreduce_cost  sum over the trajectories of the nctx contexts of this rank (all on the
  *                        communicator's device) and over all ranks of the cost scalars of PGD iteration
  *                        `iteration` (0-based count since vch2d_pgd_init; < 0: the current iterate);
- *                        J_sum_out [5] on the host.  Every rank must call it, in the same order. */
+ *                        J_sum_out [5] on the host.  Every rank must call it, in the same order.  The sum is over
+ *                        whatever each trajectory's J is: with per-trajectory weights (vch2d_pgd_init_v) it adds costs of
+ *                        different functionals. */
 #define VCH_COMM_ID_BYTES 128
 typedef struct vch_comm vch_comm;
 int vch_comm_unique_id(unsigned char *id_out /* [VCH_COMM_ID_BYTES] */);

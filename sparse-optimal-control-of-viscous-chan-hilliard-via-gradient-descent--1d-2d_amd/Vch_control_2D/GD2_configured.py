@@ -81,6 +81,43 @@ def run_optimization(fwd_config: ForwardSolverConfig, opt_config: OptimizationCo
                 r=eng.pgd_get("r"), phi_T=phi_T, t_hist=t_hist, x=eng.x.copy(), y=eng.y.copy())
 
 
+def run_sweep(fwd_config: ForwardSolverConfig, opt_configs, n_iter=None, seed=42, amp=0.1, choice_t=DEFAULT_TARGET_CHOICE,
+              choice_q=DEFAULT_TRACKING_CHOICE, u0=None, return_controls=False, device=0):
+    """A parameter sweep as ONE batch: member b runs the PGD loop with opt_configs[b] (weights, sparsity parameter, box,
+    alpha_max), all members from the same initial state (`seed`, `amp`) and targets, so that they differ by their
+    parameters only.  `u0`: start control, one (M+1, Nx+1, Ny+1) array for every member or one per member (continuation
+    in kappa_sparsity, resuming from a saved optimal_control.npy); default zeros.  `n_iter` None: the largest max_iter of
+    the members (the loop length is one for the batch).  Returns dict(costs [B][it+1], alphas, attempts, changes,
+    tracking_error, terminal_error, iters, seconds, kkt = Engine2D.pgd_kkt(refresh=True) -- the sparsity statistic and
+    the stationarity measure of every member, counted on the device -- t_hist, x, y, and u only with return_controls);
+    the state history never leaves the device."""
+    opt_configs = list(opt_configs)
+    B = len(opt_configs)
+    if B < 1:
+        raise ValueError("run_sweep needs at least one OptimizationConfig")
+    Nx, Ny = int(fwd_config.Nx), int(fwd_config.Ny)
+    t_hist, dts = time_grid(float(fwd_config.T), float(fwd_config.dt_initial))
+    eng = engine_for_config(fwd_config, batch=B, max_steps=len(dts), device=device)
+    phi0 = np.repeat(init_phi_random(Nx, Ny, DELTA_SEP, amp=amp, seed=int(seed))[None], B, axis=0)
+    phi_T, _ = build_targets(eng.x, eng.y, t_hist, phi0[0], fwd_config.Lx, fwd_config.Ly, fwd_config.T,
+                             choice_t=choice_t, choice_q=2)
+    if u0 is not None:
+        u0 = np.asarray(u0, dtype=np.float64)
+        if u0.ndim == 3:
+            u0 = np.repeat(u0[None], B, axis=0)
+    J0 = eng.pgd_init(phi0, np.repeat(phi_T[None], B, axis=0), t_hist, [make_opt(o) for o in opt_configs],
+                      ramp=(choice_q == 1), T=float(fwd_config.T), u0=u0)
+    n = int(max(int(o.max_iter) for o in opt_configs) if n_iter is None else n_iter)
+    res = eng.pgd_iterate(n)
+    out = dict(costs=np.concatenate([J0[:, 4:5], res["cost"]], axis=1), alphas=res["alpha"], attempts=res["attempts"],
+               changes=res["change"], tracking_error=res["tracking_error"], terminal_error=res["terminal_error"],
+               iters=res["iters"], seconds=res["seconds"], kkt=eng.pgd_kkt(refresh=True), phi_T=phi_T, t_hist=t_hist,
+               x=eng.x.copy(), y=eng.y.copy())
+    if return_controls:
+        out["u"] = eng.pgd_get("u").reshape((B, len(t_hist)) + eng.shape)
+    return out
+
+
 def main(n_iter=None, params_file="last_run_config_2d.json", num_directions=5, verbose=True):
     """Non-interactive equivalent of the reference's `__main__` block (G2:230-441) without previews and
     plots: parameters from the last-run JSON (defaults if absent, K2:181-190), uncontrolled march, targets

@@ -174,7 +174,15 @@ struct vch2d_ctx {
     double rampT;
     std::vector<double> t_hist, dt, xg, yg, tfrac;
     double *tfrac_dev;
-    vch_opt_params opt;
+    // optimisation parameters, one set per trajectory (vch2d_pgd_init_v; vch2d_pgd_init repeats one set): the host copy,
+    // its device table [B][OPT_STRIDE] read by k_adj_rhs / k_scaled_diff / k_grad_prox / k_kkt_count, and a second table
+    // (with its host staging) that the stateless seams vch2d_backward / vch2d_grad_prox fill with their scalar arguments,
+    // so that they leave the resident problem's table alone
+    std::vector<vch_opt_params> opts;
+    double *opt_tab, *seam_tab;
+    std::vector<double> tab_host;
+    bool pgd_r_valid;                     // r_hist holds an adjoint of the resident problem (a sweep has run since the init)
+    unsigned long long *kkt_dev;          // vch2d_pgd_kkt: [B][3] counts, then [B][Mmax+1][3] per-level partials
     std::vector<double> pgd_cost, pgd_alpha_prev, pgd_J;    // per trajectory
     std::vector<int> pgd_plateau, pgd_done, pgd_k;
     std::vector<std::vector<double>> pgd_cost_hist;
@@ -444,6 +452,11 @@ extern "C" vch2d_ctx *vch2d_create(const vch2d_params *p, int batch, int max_ste
     if (dalloc(&c->gpart3, 4 * (size_t)batch * (c->gnblk + G.ns), c->stream)) return fail("hipMalloc");
     if (dalloc(&c->hist_dev, (size_t)batch * HIST_CAP, c->stream)) return fail("hipMalloc");
     if (dalloc(&c->alpha_dev, batch, c->stream) || dalloc(&c->J_dev, 5 * (size_t)batch, c->stream)) return fail("hipMalloc");
+    if (dalloc(&c->opt_tab, (size_t)OPT_STRIDE * batch, c->stream) || dalloc(&c->seam_tab, (size_t)OPT_STRIDE * batch, c->stream))
+        return fail("hipMalloc");
+    if (hipMalloc((void **)&c->kkt_dev, sizeof(unsigned long long) * 3 * batch * (max_steps + 2)) != hipSuccess)
+        return fail("hipMalloc");
+    c->pgd_r_valid = false;
     if (dalloc(&c->J_ring_dev, (size_t)J_RING * 5 * batch, c->stream)) return fail("hipMalloc");
     if (hipHostMalloc((void **)&c->J_ring_host, sizeof(double) * J_RING * 5 * batch) != hipSuccess) return fail("hipHostMalloc");
     c->pgd_iter_total = 0;
@@ -569,13 +582,14 @@ extern "C" void vch2d_destroy(vch2d_ctx *c) {
     hipStreamSynchronize(c->stream);
     double *all[] = {c->phi_s, c->mu_s, c->Rphi_s, c->rhs_s, c->D_s, c->w, c->wnew, c->mu0, c->cphi, c->cmu, c->x,
                      c->r, c->dmu, c->t1, c->t2, c->cg_p[0], c->cg_p[1], c->cg_v, c->cg_q, c->cg_z2, c->xf, c->dprev[0], c->dprev[1], c->dprev[2], c->dprev[3], c->dprev[4], c->dprev[5], c->dprev[6], c->dprev[7], c->dprev2[0], c->dprev2[1], c->dprev2[2], c->dprev2[3], c->dprev2[4], c->dprev2[5], c->dprev2[6], c->dprev2[7], c->x0g, c->gpart, c->gpart3, c->tmp[0], c->tmp[1], c->tmp[2], c->tmp[3], c->tmp[4], c->tmp[5],
-                     c->phiT, c->phi0, c->wts_mass, c->W_cost, c->part, c->part_mass, c->hist_dev, c->alpha_dev, c->J_dev, c->Q1f,
+                     c->phiT, c->phi0, c->wts_mass, c->W_cost, c->part, c->part_mass, c->hist_dev, c->alpha_dev, c->opt_tab, c->seam_tab, c->J_dev, c->Q1f,
                      c->Q2f, c->Q1s, c->Q2s, c->mf, c->ms, c->phi_hist, c->u_hist, c->u_trial, c->phi_trial, c->phiQ,
                      c->r_hist, c->p_hist, c->q_hist, c->cost_part, c->cost_lvl, c->tfrac_dev};
     for (double *q : all)
         if (q) hipFree(q);
     hipFree(c->st);
     hipFree(c->frozen_dev);
+    if (c->kkt_dev) hipFree(c->kkt_dev);
     if (c->fin_counter) hipFree(c->fin_counter);
     if (c->tw_fh) hipFree(c->tw_fh);
     if (c->tw_sh) hipFree(c->tw_sh);
@@ -1512,6 +1526,19 @@ extern "C" int vch2d_forward(vch2d_ctx *c, const double *phi0, const double *u, 
     return 0;
 }
 
+// Fill a device parameter table from n_o (1 or B) host parameter sets: an ordinary host-to-device copy on the engine's stream.
+static int write_opt_tab(vch2d_ctx *c, double *tab_dev, const vch_opt_params *o, int n_o) {
+    c->tab_host.assign((size_t)OPT_STRIDE * c->B, 0.0);
+    for (int b = 0; b < c->B; ++b) {
+        const vch_opt_params &s = o[n_o == 1 ? 0 : b];
+        double *t = c->tab_host.data() + (size_t)OPT_STRIDE * b;
+        t[OPT_B1] = s.b1; t[OPT_B2] = s.b2; t[OPT_B3] = s.b3;
+        t[OPT_KS] = s.kappa_sparsity; t[OPT_UMIN] = s.u_min; t[OPT_UMAX] = s.u_max;
+    }
+    HIPCHK(hipMemcpyAsync(tab_dev, c->tab_host.data(), sizeof(double) * OPT_STRIDE * c->B, hipMemcpyHostToDevice, c->stream));
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------
 // adjoint sweep (B2:75-246)
 // ------------------------------------------------------------------------------------
@@ -1521,14 +1548,16 @@ extern "C" int vch2d_forward(vch2d_ctx *c, const double *phi0, const double *u, 
 // the rigorous bound; solves are gated per trajectory, and one that its sweeps did not finish is counted on the device
 // (lin_unconv).  safe = true: a look and the rigorous budget at every step (the fallback of backward_core).
 constexpr int ADJ_LOOK = 8, ADJ_SETTLE = 16;
-static int backward_pass(vch2d_ctx *c, const double *phi_hist_dev, int M, const double *t_hist, double b1, double b2,
+// opt_tab: the device table whose rows give every trajectory its b1 (adjoint source) and b2 (terminal condition).
+static int backward_pass(vch2d_ctx *c, const double *phi_hist_dev, int M, const double *t_hist, const double *opt_tab,
                          const double *phiQ_dev, const double *phiT_dev, double *r_out, double *p_out, double *q_out, bool safe) {
     const long hs = hist_stride(c);
     const Geom &G = c->G;
     double *rhs = c->cphi, *Dn = c->cmu, *rcur = c->wnew;
     double *qa = c->mu0, *qb = c->dmu;
     // terminal condition (B2:183-187): (I - tau L) p_M = b2 (phi_M - phi_T), q_M = -L p_M, r_M = 0
-    LAUNCH(k_scaled_diff, c->grid, dim3(NTH), G, phi_hist_dev + (long)M * G.plane, hs, phiT_dev, G.plane, b2, rhs, c->part);
+    LAUNCH(k_scaled_diff, c->grid, dim3(NTH), G, phi_hist_dev + (long)M * G.plane, hs, phiT_dev, G.plane, opt_tab + OPT_B2, OPT_STRIDE, rhs,
+           c->part);
     LAUNCH(k_adj_setup, c->grid, dim3(NTH), G, c->P, (const double *)nullptr, (const double *)rhs, Dn, c->part);
     LAUNCH(k_fin_lin_begin, dim3(c->B), dim3(64), c->st, c->part, c->nblk, 0, c->P.tau, c->P.kappa, 0.0, c->lin_tol);
     LAUNCH(k_fill, c->grid, dim3(NTH), G, c->x, 0.0);
@@ -1560,7 +1589,7 @@ static int backward_pass(vch2d_ctx *c, const double *phi_hist_dev, int M, const 
         }
         LAUNCHC(PC_ADJ_RHS, k_adj_rhs, c->grid, dim3(NTH), G, c->P, c->x, qa, phi_hist_dev + (long)n * G.plane,
                phi_hist_dev + (long)(n + 1) * G.plane, phiQ_dev ? phiQ_dev + (long)n * G.plane : (const double *)nullptr,
-               phiQ_dev ? phiQ_dev + (long)(n + 1) * G.plane : (const double *)nullptr, hs, dtn, b1, rhs, Dn, c->part);
+               phiQ_dev ? phiQ_dev + (long)(n + 1) * G.plane : (const double *)nullptr, hs, dtn, opt_tab, rhs, Dn, c->part);
         LAUNCH(k_fin_lin_begin, dim3(c->B), dim3(64), c->st, c->part, c->nblk, 0, c->P.tau, c->P.kappa, dtn, c->lin_tol);
         // looks at levels fixed in advance (every level for the first ADJ_SETTLE ones, where the orders of the guesses are
         // being raised, then every ADJ_LOOK-th): when a trajectory's order changes depends on its own ratios only
@@ -1638,14 +1667,14 @@ static int backward_pass(vch2d_ctx *c, const double *phi_hist_dev, int M, const 
     return 0;
 }
 
-static int backward_core(vch2d_ctx *c, const double *phi_hist_dev, int M, const double *t_hist, double b1, double b2,
+static int backward_core(vch2d_ctx *c, const double *phi_hist_dev, int M, const double *t_hist, const double *opt_tab,
                          const double *phiQ_dev, const double *phiT_dev, double *r_out, double *p_out, double *q_out) {
     c->adj_guess_off = getenv("VCH_ADJ_GUESS_OFF") != nullptr;
     c->adj_safe = getenv("VCH_ADJ_SAFE") != nullptr;
     if (c->adj_safe)                  // diagnostics: the fallback schedule (a look and the rigorous budget at every step)
-        return backward_pass(c, phi_hist_dev, M, t_hist, b1, b2, phiQ_dev, phiT_dev, r_out, p_out, q_out, true);
+        return backward_pass(c, phi_hist_dev, M, t_hist, opt_tab, phiQ_dev, phiT_dev, r_out, p_out, q_out, true);
     c->redo_iters = 0;
-    VCHCHK(backward_pass(c, phi_hist_dev, M, t_hist, b1, b2, phiQ_dev, phiT_dev, r_out, p_out, q_out, false));
+    VCHCHK(backward_pass(c, phi_hist_dev, M, t_hist, opt_tab, phiQ_dev, phiT_dev, r_out, p_out, q_out, false));
     VCHCHK(sync_state(c));
     bool redo = false;
     long iters = 0;
@@ -1678,7 +1707,7 @@ static int backward_core(vch2d_ctx *c, const double *phi_hist_dev, int M, const 
     }
     const long syncs = c->n_sync, launches = c->n_launch;
     VCHCHK(reset_counters(c));
-    VCHCHK(backward_pass(c, phi_hist_dev, M, t_hist, b1, b2, phiQ_dev, phiT_dev, r_out, p_out, q_out, true));
+    VCHCHK(backward_pass(c, phi_hist_dev, M, t_hist, opt_tab, phiQ_dev, phiT_dev, r_out, p_out, q_out, true));
     if (save) {
         size_t k = 0;
         for (double *o : outs)
@@ -1728,8 +1757,14 @@ extern "C" int vch2d_backward(vch2d_ctx *c, const double *phi_hist, int M, const
     if (p_out) VCHCHK(ensure_hist(c, &c->p_hist));
     if (q_out) VCHCHK(ensure_hist(c, &c->q_hist));
     VCHCHK(reset_counters(c));
+    {
+        vch_opt_params o{};
+        o.b1 = b1;
+        o.b2 = b2;
+        VCHCHK(write_opt_tab(c, c->seam_tab, &o, 1));
+    }
     HIPCHK(hipEventRecord(c->ev0, c->stream));
-    VCHCHK(backward_core(c, c->phi_hist, M, t_hist, b1, b2, pq, pt, c->r_hist, p_out ? c->p_hist : nullptr,
+    VCHCHK(backward_core(c, c->phi_hist, M, t_hist, c->seam_tab, pq, pt, c->r_hist, p_out ? c->p_hist : nullptr,
                          q_out ? c->q_hist : nullptr));
     HIPCHK(hipEventRecord(c->ev1, c->stream));
     VCHCHK(sync_state(c));
@@ -1772,8 +1807,9 @@ static int set_cost_weights(vch2d_ctx *c, const double *x, const double *y) {
 
 // J_out [B][5]; arrays on the device in history layout; phiQ_dev NULL + ramp => on-the-fly ramp target
 static int cost_core(vch2d_ctx *c, const double *phi_dev, const double *u_dev, const double *pq_dev, const double *pt_dev,
-                     bool ramp, int M, const double *t_hist, const vch_opt_params *o, double *J_out,
-                     double *raw_out = nullptr /* [B][2] = {int int (phi - phi_Q)^2, int (phi_M - phi_T)^2} */) {
+                     bool ramp, int M, const double *t_hist, const vch_opt_params *opts, double *J_out,
+                     double *raw_out = nullptr /* [B][2] = {int int (phi - phi_Q)^2, int (phi_M - phi_T)^2} */,
+                     int n_opts = 1 /* 1: opts[0] weighs every trajectory; B: trajectory b takes opts[b] */) {
     const Geom &G = c->G;
     const int levels = M + 1, ntiles = c->nblk;
     if (!c->cost_part) {
@@ -1799,6 +1835,7 @@ static int cost_core(vch2d_ctx *c, const double *phi_dev, const double *u_dev, c
             i4 += d * (s[(n + 1) * 4 + 3] + s[n * 4 + 3]) / 2.0;
         }
         double *J = J_out + 5 * b;
+        const vch_opt_params *o = opts + (n_opts == 1 ? 0 : b);
         J[0] = (o->b1 / 2.0) * i1;
         J[1] = (o->b2 / 2.0) * s[M * 4 + 1];
         J[2] = (o->b3 / 2.0) * i3;
@@ -1918,9 +1955,10 @@ extern "C" int vch2d_free_energy(vch2d_ctx *c, const double *phi_hist, int rows,
     return 0;
 }
 
-// u_out = prox(u - alpha (r + b3 u)); change_out [B][2] = {sum (u+ - u)^2, sum u^2} or NULL
+// u_out = prox(u - alpha (r + b3 u)), trajectory b with row b of the device table opt_tab; change_out [B][2] =
+// {sum (u+ - u)^2, sum u^2} or NULL
 static int grad_prox_core(vch2d_ctx *c, const double *u_dev, const double *r_dev, int rows, const double *alpha_host,
-                          const vch_opt_params *o, double *uout_dev, double *change_out) {
+                          const double *opt_tab, double *uout_dev, double *change_out) {
     HIPCHK(hipMemcpyAsync(c->alpha_dev, alpha_host, sizeof(double) * c->B, hipMemcpyHostToDevice, c->stream));
     if (!c->cost_part) {
         const size_t n = (size_t)c->B * (c->Mmax + 1) * c->nblk * 4;
@@ -1930,8 +1968,8 @@ static int grad_prox_core(vch2d_ctx *c, const double *u_dev, const double *r_dev
     }
     dim3 g(c->nblk, rows, c->B);
     HIPCHK(hipMemsetAsync(c->cost_part, 0, (size_t)c->B * rows * c->nblk * 4 * 8, c->stream));
-    LAUNCHC(PC_PROX, k_grad_prox, g, dim3(NTH), c->G, c->G.tiles_f, u_dev, r_dev, hist_stride(c), (const double *)c->alpha_dev, o->b3,
-           o->kappa_sparsity, o->u_min, o->u_max, uout_dev, c->cost_part);
+    LAUNCHC(PC_PROX, k_grad_prox, g, dim3(NTH), c->G, c->G.tiles_f, u_dev, r_dev, hist_stride(c), (const double *)c->alpha_dev, opt_tab,
+           uout_dev, c->cost_part);
     if (change_out) {
         LAUNCH(k_cost_fin, dim3(c->B * rows), dim3(64), c->nblk, (const double *)c->cost_part, c->cost_lvl);
         HIPCHK(hipMemcpyAsync(c->cost_lvl_host, c->cost_lvl, (size_t)c->B * rows * 4 * 8, hipMemcpyDeviceToHost, c->stream));
@@ -1958,7 +1996,8 @@ extern "C" int vch2d_grad_prox(vch2d_ctx *c, const double *u, const double *r, i
     VCHCHK(ensure_hist(c, &c->u_trial));
     VCHCHK(h2d_hist(c, c->u_hist, u, rows));
     VCHCHK(h2d_hist(c, c->r_hist, r, rows));
-    VCHCHK(grad_prox_core(c, c->u_hist, c->r_hist, rows, alpha, opt, c->u_trial, nullptr));
+    VCHCHK(write_opt_tab(c, c->seam_tab, opt, 1));
+    VCHCHK(grad_prox_core(c, c->u_hist, c->r_hist, rows, alpha, c->seam_tab, c->u_trial, nullptr));
     return d2h_hist(c, u_out, c->u_trial, rows);
 }
 
@@ -1971,12 +2010,27 @@ static int copy_traj(vch2d_ctx *c, double *dst, const double *src, int b, int ro
     return 0;
 }
 
-extern "C" int vch2d_pgd_init(vch2d_ctx *c, const double *phi0, const double *phi_T, const double *phi_Q, int ramp, double T,
-                              const double *t_hist, int M, const double *x, const double *y, const vch_opt_params *opt,
-                              double *J0_out) {
+extern "C" int vch2d_pgd_init_v(vch2d_ctx *c, const double *phi0, const double *phi_T, const double *phi_Q, int ramp, double T,
+                                const double *t_hist, int M, const double *x, const double *y, const vch_opt_params *opts,
+                                int n_opts, const double *u0, const double *alpha0, double *J0_out) {
     CTXCHK(c);
-    ARGCHK(phi0 && phi_T && t_hist && x && y && opt && M >= 1 && M <= c->Mmax, "NULL argument or M out of range");
-    c->opt = *opt;
+    ARGCHK(phi0 && phi_T && t_hist && x && y && opts && M >= 1 && M <= c->Mmax, "NULL argument or M out of range");
+    ARGCHK(n_opts == 1 || n_opts == c->B, "n_opts must be 1 or the context's batch");
+    // all of this before anything is enqueued or any resident state changes
+    for (int b = 0; b < c->B; ++b) {
+        const vch_opt_params &o = opts[n_opts == 1 ? 0 : b];
+        const char *bad = nullptr;
+        if (!std::isfinite(o.b1) || !std::isfinite(o.b2) || !std::isfinite(o.b3)) bad = "b1, b2, b3 must be finite";
+        else if (!std::isfinite(o.kappa_sparsity) || o.kappa_sparsity < 0) bad = "kappa_sparsity must be finite and >= 0";
+        else if (!(o.alpha_max > 0)) bad = "alpha_max must be > 0";
+        else if (std::isnan(o.u_min) || std::isnan(o.u_max) || o.u_min > o.u_max) bad = "u_min must be <= u_max";
+        else if (alpha0 && !(std::isfinite(alpha0[b]) && alpha0[b] > 0)) bad = "alpha0 must be finite and > 0";
+        if (bad) return vch_fail(VCH_ERR_ARG, "vch2d_pgd_init_v: trajectory %d: %s", b, bad);
+    }
+    c->opts.resize(c->B);
+    for (int b = 0; b < c->B; ++b) c->opts[b] = opts[n_opts == 1 ? 0 : b];
+    VCHCHK(write_opt_tab(c, c->opt_tab, c->opts.data(), c->B));
+    c->pgd_r_valid = false;
     c->t_hist.assign(t_hist, t_hist + M + 1);
     c->dt.resize(M);
     for (int n = 0; n < M; ++n) {
@@ -2011,16 +2065,19 @@ extern "C" int vch2d_pgd_init(vch2d_ctx *c, const double *phi0, const double *ph
     } else {
         if (c->phiQ) HIPCHK(hipMemsetAsync(c->phiQ, 0, sizeof(double) * c->B * hist_stride(c), c->stream));
     }
-    // u^0 = 0, uncontrolled march, J(u^0)   (G2:255-258, G2:291)
+    // u^0 = 0 and the uncontrolled march (G2:255-258), or the caller's u^0 as given (not clipped) and the march under it;
+    // then J(u^0) under every trajectory's own weights (G2:291)
     HIPCHK(hipMemsetAsync(c->u_hist, 0, sizeof(double) * c->B * hist_stride(c), c->stream));
+    if (u0) VCHCHK(h2d_hist(c, c->u_hist, u0, M + 1));
     c->u_rows_res = M + 1;
     VCHCHK(reset_counters(c));
     HIPCHK(hipMemcpyAsync(c->phi_s, c->phi0, sizeof(double) * c->B * c->G.plane, hipMemcpyDeviceToDevice, c->stream));
-    VCHCHK(forward_core(c, nullptr, 0, c->dt.data(), M, c->phi_hist));
+    if (u0) VCHCHK(forward_core(c, c->u_hist, M + 1, c->dt.data(), M, c->phi_hist));
+    else VCHCHK(forward_core(c, nullptr, 0, c->dt.data(), M, c->phi_hist));
     c->M_res = M;
     c->pgd_J.assign(5 * c->B, 0.0);
     VCHCHK(cost_core(c, c->phi_hist, c->u_hist, (phi_Q || ramp) ? c->phiQ : nullptr, c->phiT, false, M, c->t_hist.data(),
-                     &c->opt, c->pgd_J.data()));
+                     c->opts.data(), c->pgd_J.data(), nullptr, c->B));
     // target norms of the error metrics (G2:348-361)
     c->pgd_denQ2.assign(c->B, 0.0);
     c->pgd_denT2.assign(c->B, 0.0);
@@ -2032,7 +2089,9 @@ extern "C" int vch2d_pgd_init(vch2d_ctx *c, const double *phi0, const double *ph
     }
     c->pgd_err_n = 0;
     c->pgd_cost.resize(c->B);
-    c->pgd_alpha_prev.assign(c->B, opt->alpha_max);
+    c->pgd_alpha_prev.resize(c->B);
+    for (int b = 0; b < c->B; ++b)          // the first alpha_prev: alpha_max (G2:293), or the caller's, capped at alpha_max
+        c->pgd_alpha_prev[b] = alpha0 ? std::min(alpha0[b], c->opts[b].alpha_max) : c->opts[b].alpha_max;
     c->pgd_plateau.assign(c->B, 0);
     c->pgd_done.assign(c->B, 0);
     c->pgd_k.assign(c->B, 0);
@@ -2047,6 +2106,12 @@ extern "C" int vch2d_pgd_init(vch2d_ctx *c, const double *phi0, const double *ph
     c->pgd_iter_total = 0;
     c->pgd_ready = true;
     return 0;
+}
+
+extern "C" int vch2d_pgd_init(vch2d_ctx *c, const double *phi0, const double *phi_T, const double *phi_Q, int ramp, double T,
+                              const double *t_hist, int M, const double *x, const double *y, const vch_opt_params *opt,
+                              double *J0_out) {
+    return vch2d_pgd_init_v(c, phi0, phi_T, phi_Q, ramp, T, t_hist, M, x, y, opt, 1, nullptr, nullptr, J0_out);
 }
 
 static double elapsed_s(vch2d_ctx *c, hipEvent_t a, hipEvent_t b) {
@@ -2085,10 +2150,10 @@ extern "C" int vch2d_pgd_iterate(vch2d_ctx *c, int n_iters, double *cost_out, do
             // three orders below the tolerance of the PGD parity statement; 1.92 -> 1.38 sweeps per solve.
             const double keep = c->lin_tol;
             c->lin_tol = std::max(c->lin_tol, c->pgd_adj_tol);
-            const int rc_ = backward_core(c, c->phi_hist, M, c->t_hist.data(), c->opt.b1, c->opt.b2, pq, c->phiT, c->r_hist, nullptr,
-                                          nullptr);
+            const int rc_ = backward_core(c, c->phi_hist, M, c->t_hist.data(), c->opt_tab, pq, c->phiT, c->r_hist, nullptr, nullptr);
             c->lin_tol = keep;
             VCHCHK(rc_);
+            c->pgd_r_valid = true;
         }
         HIPCHK(hipEventRecord(e1, c->stream));
         sec[0] += elapsed_s(c, e0, e1);
@@ -2101,7 +2166,7 @@ extern "C" int vch2d_pgd_iterate(vch2d_ctx *c, int n_iters, double *cost_out, do
         for (int round = 0; round <= 10; ++round) {
             // round 0 = optimistic step; rounds 1..10 = backtracking trials (G2:128-146)
             HIPCHK(hipEventRecord(e0, c->stream));
-            VCHCHK(grad_prox_core(c, c->u_hist, c->r_hist, rows, alpha.data(), &c->opt, c->u_trial, chg.data()));
+            VCHCHK(grad_prox_core(c, c->u_hist, c->r_hist, rows, alpha.data(), c->opt_tab, c->u_trial, chg.data()));
             HIPCHK(hipEventRecord(e1, c->stream));
             sec[1] += elapsed_s(c, e0, e1);
             HIPCHK(hipEventRecord(e0, c->stream));
@@ -2113,7 +2178,7 @@ extern "C" int vch2d_pgd_iterate(vch2d_ctx *c, int n_iters, double *cost_out, do
             HIPCHK(hipEventRecord(e1, c->stream));
             sec[round == 0 ? 2 : 4] += elapsed_s(c, e0, e1);
             HIPCHK(hipEventRecord(e0, c->stream));
-            VCHCHK(cost_core(c, c->phi_trial, c->u_trial, pq, c->phiT, false, M, c->t_hist.data(), &c->opt, Jt.data(), raw.data()));
+            VCHCHK(cost_core(c, c->phi_trial, c->u_trial, pq, c->phiT, false, M, c->t_hist.data(), c->opts.data(), Jt.data(), raw.data(), B));
             HIPCHK(hipEventRecord(e1, c->stream));
             sec[round == 0 ? 3 : 4] += elapsed_s(c, e0, e1);
             bool pending = false;
@@ -2148,10 +2213,10 @@ extern "C" int vch2d_pgd_iterate(vch2d_ctx *c, int n_iters, double *cost_out, do
                     if (k > 0 && std::fabs(ch[ch.size() - 1] - ch[ch.size() - 2]) < 1e-5) c->pgd_plateau[b]++;
                     else c->pgd_plateau[b] = 0;
                     if (c->pgd_plateau[b] >= 5) {
-                        c->pgd_alpha_prev[b] = std::min(c->opt.alpha_max, alpha_k[b] * 1.5);
+                        c->pgd_alpha_prev[b] = std::min(c->opts[b].alpha_max, alpha_k[b] * 1.5);
                         c->pgd_plateau[b] = 0;
                     } else {
-                        c->pgd_alpha_prev[b] = std::min(c->opt.alpha_max, alpha_k[b] * 1.2);
+                        c->pgd_alpha_prev[b] = std::min(c->opts[b].alpha_max, alpha_k[b] * 1.2);
                     }
                     if (change < 1e-5 && k > 20) c->pgd_done[b] = 1;
                     c->pgd_cost[b] = cost_new[b];
@@ -2198,6 +2263,43 @@ extern "C" int vch2d_pgd_get(vch2d_ctx *c, int what, double *out) {
     const double *src = what == 0 ? c->u_hist : what == 1 ? c->phi_hist : what == 2 ? c->r_hist : c->phiQ;
     if (!src) return vch_fail(VCH_ERR_STATE, "vch2d_pgd_get: array %d is not resident", what);
     return d2h_hist(c, out, src, c->M_res + 1);
+}
+
+extern "C" int vch2d_pgd_kkt(vch2d_ctx *c, int refresh, double tol, int64_t *counts_out, double *stationarity_out) {
+    CTXCHK(c);
+    if (!c->pgd_ready) return vch_fail(VCH_ERR_STATE, "vch2d_pgd_kkt: call vch2d_pgd_init first");
+    ARGCHK(counts_out, "NULL counts_out");
+    if (!refresh && !c->pgd_r_valid)
+        return vch_fail(VCH_ERR_STATE, "vch2d_pgd_kkt: no adjoint sweep has run since vch2d_pgd_init (pass refresh != 0)");
+    const int B = c->B, M = c->M_res, rows = M + 1;
+    if (!(tol > 0)) tol = 1e-6;
+    if (refresh) {
+        // the adjoint of the resident iterate, every trajectory with its own b1, b2, at the accuracy of vch2d_backward
+        VCHCHK(backward_core(c, c->phi_hist, M, c->t_hist.data(), c->opt_tab, c->phiQ ? c->phiQ : nullptr, c->phiT, c->r_hist,
+                             nullptr, nullptr));
+        VCHCHK(reset_counters(c));      // the records as the end of a PGD iteration leaves them
+        c->pgd_r_valid = true;
+    }
+    unsigned long long *kpart = c->kkt_dev + 3 * (size_t)B;
+    HIPCHK(hipMemsetAsync(kpart, 0, sizeof(unsigned long long) * 3 * B * rows, c->stream));
+    LAUNCH(k_kkt_count, dim3(c->nblk, rows, B), dim3(NTH), c->G, c->G.tiles_f, (const double *)c->u_hist,
+           (const double *)c->r_hist, hist_stride(c), (const double *)c->opt_tab, tol, kpart);
+    LAUNCH(k_kkt_fin, dim3(B), dim3(64), rows, (const unsigned long long *)kpart, c->kkt_dev);
+    std::vector<unsigned long long> cnt(3 * (size_t)B);
+    HIPCHK(hipMemcpyAsync(cnt.data(), c->kkt_dev, sizeof(unsigned long long) * 3 * B, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const int64_t total = (int64_t)rows * c->G.ns * c->G.nf;
+    for (int b = 0; b < B; ++b) {
+        for (int k = 0; k < 3; ++k) counts_out[4 * b + k] = (int64_t)cnt[3 * b + k];
+        counts_out[4 * b + 3] = total;
+    }
+    if (stationarity_out) {
+        // prox_1(u): the grad-prox step with alpha = 1 into the trial-control scratch, and that kernel's change sums
+        std::vector<double> one(B, 1.0), chg(2 * (size_t)B);
+        VCHCHK(grad_prox_core(c, c->u_hist, c->r_hist, rows, one.data(), c->opt_tab, c->u_trial, chg.data()));
+        for (int b = 0; b < B; ++b) stationarity_out[b] = std::sqrt(chg[2 * b]) / (std::sqrt(chg[2 * b + 1]) + 1e-9);
+    }
+    return 0;
 }
 
 extern "C" int vch2d_pgd_cost_dev(vch2d_ctx *c, double **ptr_dev) {

@@ -817,6 +817,12 @@ __global__ __launch_bounds__(NTH) void k_post(Geom G, Phys P, const TrajState *_
     }
 }
 
+// Per-trajectory optimisation parameters on the device: OPT_STRIDE doubles per trajectory, written by the host with a plain
+// copy (vch2d_pgd_init_v; the stateless seams fill a table of their own with one row repeated).  A kernel indexes it by
+// blockIdx.z, which is uniform over the workgroup, so the values arrive as scalar loads and sit in SGPRs.
+constexpr int OPT_STRIDE = 8;
+enum { OPT_B1 = 0, OPT_B2 = 1, OPT_B3 = 2, OPT_KS = 3, OPT_UMIN = 4, OPT_UMAX = 5 };
+
 // ---------------------------------------------------------------------------------
 // Adjoint sweep (B2:212-242).  With q = -L p carried from the previous step,
 //   rhs = B(phi_{n+1}) p_{n+1} + src = p + (tau - dt/2 D+) q + dt/2 L q + src,
@@ -827,9 +833,10 @@ __global__ __launch_bounds__(NTH) void k_adj_rhs(Geom G, Phys P, const double *_
                                                  const double *__restrict__ q, const double *__restrict__ phin,
                                                  const double *__restrict__ phin1, const double *__restrict__ qn,
                                                  const double *__restrict__ qn1, long hist_stride, double dt,
-                                                 double b1, double *__restrict__ rhs, double *__restrict__ Dn,
-                                                 double *__restrict__ part) {
+                                                 const double *__restrict__ opt_tab, double *__restrict__ rhs,
+                                                 double *__restrict__ Dn, double *__restrict__ part) {
     TILE_COORDS;
+    const double b1 = opt_tab[b * OPT_STRIDE + OPT_B1];
     __shared__ double sq[(TY + 2) * (TX + 2)];
     __shared__ double sred[NPART * 4];
     constexpr int W = TX + 2;
@@ -933,11 +940,13 @@ __global__ __launch_bounds__(NTH) void k_adj_finish(Geom G, const double *__rest
     }
 }
 
-// out = a*(x - y) (terminal right-hand side b2 (phi_M - phi_T), B2:183); y may be NULL
+// out = a_b*(x - y), a_b = a_tab[b * a_stride] (terminal right-hand side b2 (phi_M - phi_T), B2:183); y may be NULL
 __global__ __launch_bounds__(NTH) void k_scaled_diff(Geom G, const double *__restrict__ x, long xs,
-                                                     const double *__restrict__ y, long ys, double a,
+                                                     const double *__restrict__ y, long ys,
+                                                     const double *__restrict__ a_tab, int a_stride,
                                                      double *__restrict__ out, double *__restrict__ part) {
     TILE_COORDS;
+    const double a = a_tab[b * a_stride];
     __shared__ double sred[NPART * 4];
     double acc[1] = {0.0};
     for (int k = 0; k < TY / 4; ++k) {
@@ -1064,10 +1073,12 @@ __global__ void k_cost_fin(int ntiles, const double *__restrict__ part, double *
 // ---------------------------------------------------------------------------------
 __global__ __launch_bounds__(NTH) void k_grad_prox(Geom G, int tiles_f, const double *__restrict__ u,
                                                    const double *__restrict__ r, long hist_stride,
-                                                   const double *__restrict__ alpha, double b3, double ks,
-                                                   double umin, double umax, double *__restrict__ uout,
+                                                   const double *__restrict__ alpha,
+                                                   const double *__restrict__ opt_tab, double *__restrict__ uout,
                                                    double *__restrict__ part) {
     const int b = blockIdx.z, lvl = blockIdx.y;
+    const double *ot = opt_tab + b * OPT_STRIDE;
+    const double b3 = ot[OPT_B3], ks = ot[OPT_KS], umin = ot[OPT_UMIN], umax = ot[OPT_UMAX];
     const int tf = blockIdx.x % tiles_f, ts = blockIdx.x / tiles_f;
     const int c0 = tf * TX, r0 = ts * TY;
     const int lx = threadIdx.x & 63, ly0 = threadIdx.x >> 6;
@@ -1093,6 +1104,69 @@ __global__ __launch_bounds__(NTH) void k_grad_prox(Geom G, int tiles_f, const do
         const int op[2] = {0, 0};
         block_reduce_store<2>(acc, op, sred, part + (((long)b * gridDim.y + lvl) * gridDim.x + blockIdx.x) * 4);
     }
+}
+
+// ---------------------------------------------------------------------------------
+// KKT sparsity statistic u* = 0 <=> |r*| <= kappa_s (sparsity_statistics of second_order_conditions_2d): per trajectory
+// the number of nodes with |u| < tol, with |r| <= kappa_s (trajectory b's own), and where the two predicates agree.
+// Pad columns of the pitched rows and rows beyond ns take no part: their lanes vote false in all three ballots.  Every
+// wavefront counts by ballot + popcount, the workgroup's four wavefronts meet in LDS, and three lanes add the workgroup's
+// three integers to part[b][level][3] with vector integer atomics (integer sums do not depend on the order; one address
+// per trajectory and statistic instead of one per level made the atomics the kernel's cost: 20.6 ms against 6.1 ms
+// at 512^2 x 1000 x 8).  The caller zeroes part; k_kkt_fin adds the levels up.
+// grid = (tiles, levels, B)
+// ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(NTH) void k_kkt_count(Geom G, int tiles_f, const double *__restrict__ u,
+                                                   const double *__restrict__ r, long hist_stride,
+                                                   const double *__restrict__ opt_tab, double tol,
+                                                   unsigned long long *__restrict__ part) {
+    const int b = blockIdx.z, lvl = blockIdx.y;
+    const int tf = blockIdx.x % tiles_f, ts = blockIdx.x / tiles_f;
+    const int c0 = tf * TX, r0 = ts * TY;
+    const int lx = threadIdx.x & 63, ly0 = threadIdx.x >> 6;
+    const double ks = opt_tab[b * OPT_STRIDE + OPT_KS];
+    const long lb = b * hist_stride + (long)lvl * G.plane;
+    unsigned nz = 0, nsm = 0, nm = 0;
+    for (int k = 0; k < TY / 4; ++k) {
+        const int rr = r0 + ly0 + 4 * k, c = c0 + lx;
+        const bool in = rr < G.ns && c < G.nf;
+        bool zero = false, small = false;
+        if (in) {
+            const long o = lb + (long)rr * G.pitch + c;
+            zero = fabs(u[o]) < tol;
+            small = fabs(r[o]) <= ks;
+        }
+        nz += __popcll(__ballot(zero));
+        nsm += __popcll(__ballot(small));
+        nm += __popcll(__ballot(in && zero == small));
+    }
+    __shared__ unsigned sc[NTH / 64][3];
+    if (lx == 0) {
+        sc[ly0][0] = nz;
+        sc[ly0][1] = nsm;
+        sc[ly0][2] = nm;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        unsigned v = 0;
+        for (int w = 0; w < NTH / 64; ++w) v += sc[w][threadIdx.x];
+        if (v) atomicAdd(part + ((long)b * gridDim.y + lvl) * 3 + threadIdx.x, (unsigned long long)v);
+    }
+}
+
+// counts[b][3] = sum over the levels of part[b][level][3]; one workgroup of 64 threads per trajectory
+__global__ void k_kkt_fin(int levels, const unsigned long long *__restrict__ part, unsigned long long *__restrict__ counts) {
+    const int b = blockIdx.x;
+    __shared__ unsigned long long tot[3];
+    if (threadIdx.x < 3) tot[threadIdx.x] = 0;
+    __syncthreads();
+    unsigned long long a[3] = {0, 0, 0};
+    for (int l = threadIdx.x; l < levels; l += 64)
+        for (int k = 0; k < 3; ++k) a[k] += part[((long)b * levels + l) * 3 + k];
+    for (int k = 0; k < 3; ++k)
+        if (a[k]) atomicAdd(&tot[k], a[k]);
+    __syncthreads();
+    if (threadIdx.x < 3) counts[3 * b + threadIdx.x] = tot[threadIdx.x];
 }
 
 // =================================================================================
