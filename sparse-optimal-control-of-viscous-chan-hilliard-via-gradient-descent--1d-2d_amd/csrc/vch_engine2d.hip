@@ -147,8 +147,19 @@ struct vch2d_ctx {
     // look at the device state without a copy command and a stream wait: a one-workgroup kernel writes the records into
     // mapped host memory (st_pub) and then a sequence number (seq_pub) the host spins on (sync_state)
     TrajState *st_pub;
-    unsigned long long *seq_pub, seq_next;
+    unsigned long long *seq_pub, seq_next;          // one sequence slot per trajectory
     bool look_spin;
+    // The forward step's chain on the default path (fused evaluation kernels with the fin step as its own launch, looks through
+    // mapped memory); each switch defaults to on and =0 restores the launches it replaces:
+    //   VCH_MASS_EARLY   the step's k_mass is enqueued in front of the look (newton_level), not behind it
+    //   VCH_FIN_PUBLISH  the k_fin_residual<1> in front of a look publishes the state itself (no k_publish_state launch)
+    //   VCH_CEIL_CELL    the ceiling of a reduction-free solve goes through one cell per trajectory (no k_fin_ceiling launch)
+    bool mass_early, fin_publish, ceil_cell_on;
+    unsigned long long *ceil_cell;        // [B][CeilCell::STRIDE] (vch_kernels2d.h)
+    bool cell_now;                        // the level being enqueued uses the cells
+    int trial_enq;                        // sweeps of the reduction-free solve the NEXT trial launch arms the trial for (-1: none)
+    unsigned long long pub_pending;       // sequence number a fin launch already enqueued will publish (0: none)
+    bool mass_done;                       // newton_level has enqueued the step's k_mass
     int *frozen_dev;                      // [B] line-search flags for k_set_frozen
     double *hist_dev, *hist_host;         // [B][HIST_CAP]
     // DCT-I matrices and eigenvalues
@@ -292,11 +303,11 @@ static inline long hist_stride(const vch2d_ctx *c) { return (long)(c->Mmax + 1) 
 
 // records -> mapped host memory, then the sequence number (system-scope release after a system fence)
 __global__ void k_publish_state(const unsigned *__restrict__ st, int nwords, unsigned *__restrict__ dst,
-                                unsigned long long *seq, unsigned long long val) {
+                                unsigned long long *seq, int nseq, unsigned long long val) {
     for (int i = threadIdx.x; i < nwords; i += blockDim.x) dst[i] = st[i];
     __threadfence_system();
     __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(seq, val, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    for (int i = threadIdx.x; i < nseq; i += blockDim.x) __hip_atomic_store(seq + i, val, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // One look of the host at the per-trajectory state machine.  full = false (the per-step looks of a march): the stream is
@@ -306,22 +317,34 @@ __global__ void k_publish_state(const unsigned *__restrict__ st, int nwords, uns
 static int sync_state(vch2d_ctx *c, bool full = true) {
     c->n_sync++;
     if (full || !c->look_spin) {
+        c->pub_pending = 0;
         HIPCHK(hipMemcpyAsync(c->st_host, c->st, sizeof(TrajState) * c->B, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         return 0;
     }
-    const unsigned long long want = ++c->seq_next;
     static_assert(sizeof(TrajState) % 4 == 0, "TrajState is copied in 32-bit words");
-    hipLaunchKernelGGL(k_publish_state, dim3(1), dim3(256), 0, c->stream, (const unsigned *)c->st,
-                       (int)(sizeof(TrajState) / 4 * c->B), (unsigned *)c->st_pub, c->seq_pub, want);
-    HIPCHK(hipGetLastError());
+    // every trajectory's slot carries the look's number: stored by the one-workgroup kernel, or each by the workgroup of its
+    // trajectory in a k_fin_residual launch that is already enqueued (pub_pending, see publish_tail)
+    unsigned long long want = c->pub_pending;
+    c->pub_pending = 0;
+    if (!want) {
+        want = ++c->seq_next;
+        hipLaunchKernelGGL(k_publish_state, dim3(1), dim3(256), 0, c->stream, (const unsigned *)c->st,
+                           (int)(sizeof(TrajState) / 4 * c->B), (unsigned *)c->st_pub, c->seq_pub, c->B, want);
+        HIPCHK(hipGetLastError());
+    }
+    auto arrived = [&]() {
+        for (int b = 0; b < c->B; ++b)
+            if (__atomic_load_n(c->seq_pub + b, __ATOMIC_ACQUIRE) != want) return false;
+        return true;
+    };
     const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned spins = 1; __atomic_load_n(c->seq_pub, __ATOMIC_ACQUIRE) != want; ++spins) {
+    for (unsigned spins = 1; !arrived(); ++spins) {
         __builtin_ia32_pause();
         if ((spins & 0x3fff) == 0) {
             const hipError_t q = hipStreamQuery(c->stream);
             if (q != hipSuccess && q != hipErrorNotReady) return vch_fail(VCH_ERR_HIP, "sync_state: %s", hipGetErrorString(q));
-            if (q == hipSuccess && __atomic_load_n(c->seq_pub, __ATOMIC_ACQUIRE) != want)
+            if (q == hipSuccess && !arrived())
                 return vch_fail(VCH_ERR_STATE, "sync_state: stream drained but the state was not published");
             if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(120))
                 return vch_fail(VCH_ERR_STATE, "sync_state: no state from the device after 120 s");
@@ -416,6 +439,14 @@ extern "C" vch2d_ctx *vch2d_create(const vch2d_params *p, int batch, int max_ste
     c->post_pending = false;
     c->post_hist = nullptr;
     c->fin_counter = nullptr;
+    auto env_on = [](const char *name) { const char *e = getenv(name); return !(e && atoi(e) == 0); };
+    c->mass_early = env_on("VCH_MASS_EARLY");
+    c->fin_publish = env_on("VCH_FIN_PUBLISH");
+    c->ceil_cell_on = env_on("VCH_CEIL_CELL");
+    c->ceil_cell = nullptr;
+    c->cell_now = c->mass_done = false;
+    c->trial_enq = -1;
+    c->pub_pending = 0;
     for (int &n : c->spec_chn) n = 2;
     c->cheb_margin = 1;
     if (const char *e = getenv("VCH_CHEB_MARGIN")) c->cheb_margin = std::max(0, atoi(e));
@@ -466,6 +497,8 @@ extern "C" vch2d_ctx *vch2d_create(const vch2d_params *p, int batch, int max_ste
     if (hipMalloc((void **)&c->frozen_dev, sizeof(int) * batch) != hipSuccess) return fail("hipMalloc");
     if (hipMalloc((void **)&c->fin_counter, sizeof(unsigned) * batch) != hipSuccess) return fail("hipMalloc");
     hipMemsetAsync(c->fin_counter, 0, sizeof(unsigned) * batch, c->stream);
+    if (hipMalloc((void **)&c->ceil_cell, sizeof(unsigned long long) * CeilCell::STRIDE * batch) != hipSuccess) return fail("hipMalloc");
+    hipMemsetAsync(c->ceil_cell, 0, sizeof(unsigned long long) * CeilCell::STRIDE * batch, c->stream);
     if (hipHostMalloc((void **)&c->st_host, sizeof(TrajState) * batch) != hipSuccess) return fail("hipHostMalloc");
     // looks through mapped host memory (sync_state); where the platform refuses mapped coherent memory the looks fall back
     // to a copy command and a stream synchronisation
@@ -475,14 +508,15 @@ extern "C" vch2d_ctx *vch2d_create(const vch2d_params *p, int batch, int max_ste
     c->look_spin = !(getenv("VCH_LOOK_SPIN") && atoi(getenv("VCH_LOOK_SPIN")) == 0);
     if (c->look_spin) {
         if (hipHostMalloc((void **)&c->st_pub, sizeof(TrajState) * batch, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-            hipHostMalloc((void **)&c->seq_pub, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
+            hipHostMalloc((void **)&c->seq_pub, std::max<size_t>(64, sizeof(unsigned long long) * batch),
+                          hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
             (void)hipGetLastError();
             if (c->st_pub) hipHostFree(c->st_pub);
             c->st_pub = nullptr;
             c->seq_pub = nullptr;
             c->look_spin = false;
         } else {
-            *c->seq_pub = 0;
+            for (int b = 0; b < batch; ++b) c->seq_pub[b] = 0;
         }
     }
     if (hipHostMalloc((void **)&c->hist_host, sizeof(double) * batch * HIST_CAP) != hipSuccess) return fail("hipHostMalloc");
@@ -591,6 +625,7 @@ extern "C" void vch2d_destroy(vch2d_ctx *c) {
     hipFree(c->frozen_dev);
     if (c->kkt_dev) hipFree(c->kkt_dev);
     if (c->fin_counter) hipFree(c->fin_counter);
+    if (c->ceil_cell) hipFree(c->ceil_cell);
     if (c->tw_fh) hipFree(c->tw_fh);
     if (c->tw_sh) hipFree(c->tw_sh);
     if (c->tw_f) hipFree(c->tw_f);
@@ -835,7 +870,8 @@ static int cheb_solve(vch2d_ctx *c, double dt, int n_enq) {
         ChebSweepArgs a{c->r, c->r, c->cg_p[j & 1], c->cg_p[(j + 1) & 1], c->cg_p[(j + 1) & 1], c->xf, c->x0g, c->D_s, c->slot_stride,
                         j == 0 ? c->gpart : c->gpart2, j, scale, c->phi_s, c->gpart3,
                         c->guess_wr >= 0 ? c->dprev[c->guess_wr] : (double *)nullptr,
-                        (c->guess_wr >= 0 && c->guess2_on) ? c->dprev2[c->guess_wr] : (double *)nullptr};
+                        (c->guess_wr >= 0 && c->guess2_on) ? c->dprev2[c->guess_wr] : (double *)nullptr,
+                        c->cell_now ? c->ceil_cell : (unsigned long long *)nullptr};
         VCHCHK(cheb_rows(c, a, j == 0));
         if (j < n_enq) {   // E_cols, m / P(m), E_cols of E_rows(Delta y_{j+1}) for the trajectories that go on to sweep j + 1
             const SpecArgs sp{c0, 0.0, 1.0, c2, c->ms, c->mf, nullptr, c->D_s, c->slot_stride, c->gpart, c->gpart2, 1};
@@ -851,9 +887,12 @@ static int dmu_ceiling(vch2d_ctx *c, int strict) {
     const ChebFin nocheb{-1, 0, nullptr, nullptr, nullptr};
     if (spectral && c->cheb_enq >= 0) {
         // reduction-free solves: the last row kernel has stored dphi (c->xf), kept it for the guesses and taken the ceiling
-        // ratios; the trial kernel does the back substitution itself
-        LAUNCH(k_fin_ceiling, dim3(c->B), dim3(64), c->st, c->part, c->nblk, strict, -1,
-               ChebFin{c->cheb_enq, c->gnblk, c->gpart, c->gpart2, c->gpart3});
+        // ratios; the trial kernel does the back substitution itself.  With the ceiling cells the trial launches that follow
+        // (k_eval<2>, k_fin_residual<1>) also do what k_fin_ceiling does here
+        if (c->cell_now) c->trial_enq = c->cheb_enq;
+        else
+            LAUNCH(k_fin_ceiling, dim3(c->B), dim3(64), c->st, c->part, c->nblk, strict, -1,
+                   ChebFin{c->cheb_enq, c->gnblk, c->gpart, c->gpart2, c->gpart3});
     }
     if (spectral && c->cg_last >= 0) {
         const int last = c->cg_last, rd = last & 1;
@@ -874,20 +913,38 @@ static int dmu_ceiling(vch2d_ctx *c, int strict) {
     return 0;
 }
 
+static const FinTail NO_FIN_TAIL{ChebFin{-1, 0, nullptr, nullptr, nullptr}, nullptr, nullptr, 0};
+// The tail that makes a k_fin_residual launch publish the state for the look that follows it (sync_state(c, false)).
+static FinTail publish_tail(vch2d_ctx *c, FinTail t) {
+    c->pub_pending = ++c->seq_next;
+    t.pub = c->st_pub;
+    t.seq = c->seq_pub;
+    t.val = c->pub_pending;
+    return t;
+}
+
 // One residual evaluation of the pending Armijo trials.  inline_dmu (marches on the stencil-free path): the back
 // substitution happens inside the trial kernel, whichever form the solve took (k_eval<2>, or k_residual2 with VCH_FUSED=0).
+// publish (the default path only): the host's look follows this launch, and its k_fin_residual<1> publishes the state.
 static int residual_trial(vch2d_ctx *c, double dt, bool inline_dmu, bool fused, bool fin_inside, bool guess, double eta,
-                          const SolveOpts &so, const EvalFin &efin) {
+                          const SolveOpts &so, const EvalFin &efin, bool publish) {
     if (inline_dmu && fused) {
         GuessArgs gt = c->gtab2;
         if (!guess) memset(gt.c, 0, sizeof(gt.c));
+        // the trial of a reduction-free solve that no k_fin_ceiling launch has closed (dmu_ceiling): this launch pair only
+        EvalFin ef = efin;
+        ef.cheb_enq = c->trial_enq;
+        c->trial_enq = -1;
         auto k_trial = fin_inside ? k_eval<2, true> : k_eval<2, false>;
         LAUNCHC(PC_RESIDUAL, k_trial, c->grid, dim3(NTH), c->G, c->P, c->st, c->slot_stride, c->phi_s, c->mu_s, c->Rphi_s, c->rhs_s,
                 c->D_s, (const double *)c->xf, c->cphi, c->cmu, dt, c->part, (const double *)nullptr, (const double *)nullptr,
-                (const double *)nullptr, 0L, (double *)nullptr, gt, c->x0g, efin, PostArgs{nullptr, nullptr, 0});
-        if (!fin_inside)
+                (const double *)nullptr, 0L, (double *)nullptr, gt, c->x0g, ef, PostArgs{nullptr, nullptr, 0});
+        if (!fin_inside) {
+            FinTail tail{ChebFin{ef.cheb_enq, c->gnblk, c->gpart, c->gpart2, nullptr}, nullptr, nullptr, 0};
+            if (publish) tail = publish_tail(c, tail);
             LAUNCH((k_fin_residual<1>), dim3(c->B), dim3(64), c->st, c->part, c->nblk, c->hist_dev, c->P.kappa, dt, c->lin_tol, eta,
-                   guess ? (int)c->gmask2 : 0, so);
+                   guess ? (int)c->gmask2 : 0, so, tail);
+        }
         return 0;
     }
     if (inline_dmu)
@@ -900,7 +957,7 @@ static int residual_trial(vch2d_ctx *c, double dt, bool inline_dmu, bool fused, 
         LAUNCHC(PC_GUESS, k_guess, c->grid, dim3(NTH), c->G, c->P, c->st, c->slot_stride, c->gtab2, (const double *)c->D_s, dt,
                 c->rhs_s, c->x0g, c->part, 1);
     LAUNCH((k_fin_residual<1>), dim3(c->B), dim3(64), c->st, c->part, c->nblk, c->hist_dev, c->P.kappa, dt, c->lin_tol, eta,
-           guess ? (int)c->gmask2 : 0, so);
+           guess ? (int)c->gmask2 : 0, so, NO_FIN_TAIL);
     return 0;
 }
 
@@ -927,8 +984,14 @@ static int newton_level(vch2d_ctx *c, double dt, const double *un, const double 
     // VCH_FUSED=2: fused evaluation kernels, but the `fin` step as its own launch (no hand-off inside the launch)
     const bool fin_inside = c->fused_mode == 1;
     // CG-form solves whose diagonal spans more than cg_scale_ratio run on the right-scaled system (cg_weight, vch_kernels2d.h)
-    const SolveOpts so_{cheb_max_, spectral ? c->cg_scale_ratio : 0.0, in_march ? c->eta1_factor : 0.0};
-    const EvalFin efin_{fin_inside ? c->fin_counter : (unsigned *)nullptr, c->hist_dev, c->P.kappa, c->lin_tol, eta_, so_};
+    // the shortened chain (vch2d_ctx::mass_early ...): the default path only
+    const bool chain = fused && !fin_inside && c->look_spin;
+    c->cell_now = chain && c->ceil_cell_on && cheb_max_ >= 0;
+    c->trial_enq = -1;
+    const bool fin_pub = chain && c->fin_publish;
+    const SolveOpts so_{cheb_max_, spectral ? c->cg_scale_ratio : 0.0, in_march ? c->eta1_factor : 0.0,
+                        c->cell_now ? c->ceil_cell : (unsigned long long *)nullptr};
+    const EvalFin efin_{fin_inside ? c->fin_counter : (unsigned *)nullptr, c->hist_dev, c->P.kappa, c->lin_tol, eta_, so_, -1};
     // starting guesses (marches on the stencil-free path only; forward_core fills the coefficient tables): of the first
     // solve here, of the second solve inside the residual trial of slot 0
     const bool guess = in_march && c->guess_on && c->gmask1 != 0;
@@ -946,7 +1009,7 @@ static int newton_level(vch2d_ctx *c, double dt, const double *un, const double 
                 c->x0g, efin_, post_);
         if (!fin_inside)
             LAUNCH((k_fin_residual<2>), dim3(c->B), dim3(64), c->st, c->part, c->nblk, c->hist_dev, c->P.kappa, dt, c->lin_tol, eta_,
-                   guess ? (int)c->gmask1 : 0, so_);
+                   guess ? (int)c->gmask1 : 0, so_, NO_FIN_TAIL);
     } else {
         LAUNCH(k_prepare, c->grid, dim3(NTH), c->G, c->P, c->st, c->slot_stride, c->phi_s, c->mu_s, c->w, un, unp1, u_stride,
                wnew_in, dt, c->wnew, c->mu0, c->cphi, c->cmu);
@@ -956,7 +1019,7 @@ static int newton_level(vch2d_ctx *c, double dt, const double *un, const double 
             LAUNCHC(PC_GUESS, k_guess, c->grid, dim3(NTH), c->G, c->P, c->st, c->slot_stride, c->gtab1, (const double *)c->D_s, dt, c->rhs_s,
                    c->x0g, c->part, 0);
         LAUNCH((k_fin_residual<0>), dim3(c->B), dim3(64), c->st, c->part, c->nblk, c->hist_dev, c->P.kappa, dt, c->lin_tol, eta_,
-               guess ? (int)c->gmask1 : 0, so_);
+               guess ? (int)c->gmask1 : 0, so_, NO_FIN_TAIL);
     }
     if (c->spec) {
         for (int s = 0; s < c->spec_slots; ++s) {
@@ -967,9 +1030,15 @@ static int newton_level(vch2d_ctx *c, double dt, const double *un, const double 
             VCHCHK(dmu_ceiling(c, 1));
             // the second solve's guess goes with the trial that follows a trajectory's FIRST solve (the kernels check
             // iters == 1), in whichever slot that solve finished: the result must not depend on the launch schedule
-            VCHCHK(residual_trial(c, dt, inline_dmu, fused, fin_inside, guess2, eta_, so_, efin_));
+            VCHCHK(residual_trial(c, dt, inline_dmu, fused, fin_inside, guess2, eta_, so_, efin_,
+                                  fin_pub && s == c->spec_slots - 1));
         }
     }
+    // the step's weighted mass (F2:565) in front of the look: it reads the final iterate only, so the host's look, its guess
+    // tables and the enqueue of the next step's first kernel overlap it.  A trajectory the schedule did not finish is summed
+    // behind the continuation loop, by a second launch over all of them (a pure function of the final iterate)
+    c->mass_done = chain && c->mass_early;
+    if (c->mass_done) LAUNCH(k_mass, c->grid, dim3(NTH), c->G, c->st, c->slot_stride, c->phi_s, c->wts_mass, 1, c->part_mass, 1);
     VCHCHK(sync_state(c, false));
     auto any_active = [&]() {
         for (int b = 0; b < c->B; ++b)
@@ -991,6 +1060,7 @@ static int newton_level(vch2d_ctx *c, double dt, const double *un, const double 
                 S.newton_total, S.ntrials, S.use_cheb, S.cheb_n, S.step_R[0], S.step_R[1], S.step_R[2], S.lin_r0);
     }
     int guard = 0;
+    const bool unfit = any_active();
     while (any_active()) {
         if (++guard > NEWTON_MAXIT + 2) return vch_fail(VCH_ERR_STATE, "newton_level: state machine did not terminate");
         // the pending solves' forms and plans are in the state the host has just read
@@ -1006,11 +1076,12 @@ static int newton_level(vch2d_ctx *c, double dt, const double *un, const double 
         VCHCHK(dmu_ceiling(c, 0));
         int tguard = 0;
         do {
-            VCHCHK(residual_trial(c, dt, inline_dmu, fused, fin_inside, guess2, eta_, so_, efin_));
+            VCHCHK(residual_trial(c, dt, inline_dmu, fused, fin_inside, guess2, eta_, so_, efin_, fin_pub));
             VCHCHK(sync_state(c, false));
             if (++tguard > ARMIJO_TRIALS + 2) return vch_fail(VCH_ERR_STATE, "newton_level: Armijo loop did not terminate");
         } while (any_trial());
     }
+    if (unfit && c->mass_done) LAUNCH(k_mass, c->grid, dim3(NTH), c->G, c->st, c->slot_stride, c->phi_s, c->wts_mass, 1, c->part_mass, 0);
     {
         // next step's schedule: as many slots as the busiest trajectory had linear solves (failed trials do not count: they
         // are rare and the loop above absorbs them); per slot the launch sequences of the forms seen there, CG sweeps for the
@@ -1358,7 +1429,7 @@ static int forward_core(vch2d_ctx *c, const double *u_dev, int u_rows, const dou
     // slot 0 holds phi0; w = 0; mu = initialize_mu(phi0, 0) (F2:518-520); mass0 (F2:532)
     HIPCHK(hipMemsetAsync(c->w, 0, sizeof(double) * c->B * c->G.plane, c->stream));
     LAUNCH(k_init_mu, c->grid, dim3(NTH), c->G, c->P, c->phi_s, c->w, c->mu_s);
-    LAUNCH(k_mass, c->grid, dim3(NTH), c->G, c->st, c->slot_stride, c->phi_s, c->wts_mass, 0, c->part);
+    LAUNCH(k_mass, c->grid, dim3(NTH), c->G, c->st, c->slot_stride, c->phi_s, c->wts_mass, 0, c->part, 0);
     LAUNCH(k_fin_mass, dim3(c->B), dim3(64), c->st, c->part, c->nblk, 1);
     c->post_pending = false;
     // marches whose steps start with k_eval<0> (newton_level: the fused path) leave the end of every step but the last to it
@@ -1435,8 +1506,9 @@ static int forward_core(vch2d_ctx *c, const double *u_dev, int u_rows, const dou
             }
         }
         VCHCHK(newton_level(c, dt[step], un, unp1, hs, nullptr, true));
-        // clip, mass fix, store (F2:562-585)
-        LAUNCH(k_mass, c->grid, dim3(NTH), c->G, c->st, c->slot_stride, c->phi_s, c->wts_mass, 1, c->part_mass);
+        // clip, mass fix, store (F2:562-585); the mass sums may be on their way already (newton_level)
+        if (!c->mass_done) LAUNCH(k_mass, c->grid, dim3(NTH), c->G, c->st, c->slot_stride, c->phi_s, c->wts_mass, 1, c->part_mass, 0);
+        c->mass_done = false;
         double *const lvl = hist_out ? hist_out + (long)(step + 1) * c->G.plane : (double *)nullptr;
         if (fold_post && step + 1 < M) {
             c->post_pending = true;

@@ -713,6 +713,7 @@ struct ChebSweepArgs {
     const double *phi_s;                  // slot-indexed iterate
     double *cmin;                         // [B][gridDim.x]
     double *keep1, *keep2;                // ring planes of this step (or NULL)
+    unsigned long long *cell;             // [B][CeilCell::STRIDE] or NULL: the minima are folded into the trajectory's ceiling cell instead (CeilCell)
 };
 
 // FIRST = 1: the kernel with j = 0 (a separate instantiation: its branches fold, and profiles tell the two apart)
@@ -889,7 +890,10 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T), CHEB_MINW) void k_cheb_ro
                 mn = fmin(mn, sred[T / 64 + w]);
             }
             if (need_norm) a.gpart[(long)b * gridDim.x + blockIdx.x] = tot;
-            if (last) a.cmin[(long)b * gridDim.x + blockIdx.x] = mn;
+            if (last) {
+                if (a.cell) CeilCell::fold(a.cell + b * CeilCell::STRIDE, mn);
+                else a.cmin[(long)b * gridDim.x + blockIdx.x] = mn;
+            }
         }
     }
 }

@@ -726,10 +726,13 @@ __global__ __launch_bounds__(NTH) void k_residual_plain(Geom G, Phys P, const do
 // ---------------------------------------------------------------------------------
 __global__ __launch_bounds__(NTH) void k_mass(Geom G, const TrajState *__restrict__ st, long slot_stride,
                                               const double *__restrict__ phi_s, const double *__restrict__ wts,
-                                              int do_clip, double *__restrict__ part) {
+                                              int do_clip, double *__restrict__ part, int ended_only) {
     TILE_COORDS;
     __shared__ double sred[NPART * 4];
     if (st[b].frozen) return;
+    // ended_only: the launch sits in front of the host's look at the step (newton_level); a trajectory whose Newton loop is
+    // still running has no final iterate yet and is summed by a second launch behind the continuation loop
+    if (ended_only && st[b].newton_active) return;
     const int slot = st[b].slot;
     const double hi = 1.0 - DELTA_SEP;
     double acc[2] = {0.0, 0.0};
@@ -1266,7 +1269,43 @@ struct SolveOpts {
     double scale_ratio;        // CG form: Dmax > scale_ratio * Dmin switches to the right-scaled system (0: never)
     double eta1_factor;        // first solve of a step: Schur-residual target max(eta, eta1_factor * min ||R_1|| of the last
                                // three steps) (0: eta always)
+    unsigned long long *cell;  // [B][CeilCell::STRIDE] step-ceiling cells (below), reset where a solve is armed; NULL: not in use
 };
+
+// Step ceiling of a reduction-free solve in ONE 64-bit cell per trajectory: the workgroups of the solve's last row kernel
+// fold their minima into it with an atomic minimum on an order-preserving integer key of the double (sign-flip map: the
+// ratios are negative where phi has left the band).  A minimum is exact in any order, so the cell holds the same double as
+// a fixed-order reduction over the workgroups' values; 1e300 = no constraint, as there.  Only the step alpha = min(1, 0.9 v)
+// is ever taken from the cell (ceiling_alpha), and a ratio v >= FREE gives alpha = 1 whatever the other ratios are, like an
+// empty cell: such a minimum is not folded, so a solve whose step no node constrains -- nearly every one -- makes no atomic
+// at all.  The cells of a batch lie 128 B apart (atomics on one line are executed one after the other).
+struct CeilCell {
+    static constexpr int STRIDE = 16;
+    static constexpr double FREE = 2.0;
+    static __device__ __forceinline__ unsigned long long key(double v) {
+        const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+        return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+    }
+    static __device__ __forceinline__ double value(unsigned long long k) {
+        return __longlong_as_double((long long)((k >> 63) ? (k ^ 0x8000000000000000ull) : ~k));
+    }
+    static __device__ __forceinline__ void reset(unsigned long long *c) {
+        __hip_atomic_store(c, key(1e300), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    static __device__ __forceinline__ void fold(unsigned long long *c, double v) {
+        if (v < FREE) __hip_atomic_fetch_min(c, key(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);    // (false for a NaN: skipped, as fmin skips it)
+    }
+    static __device__ __forceinline__ double load(const unsigned long long *c) {
+        return value(__hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    }
+};
+// F2:381-387: the first Armijo step from the smallest ceiling ratio (>= 1e299: no node constrains the step)
+__device__ __forceinline__ double ceiling_alpha(double vmin) {
+    double amax = 2.0;
+    if (vmin < 1e299) amax = fmin(amax, 0.9 * vmin);
+    if (!isfinite(amax) || amax <= 0.0) amax = 1.0;
+    return fmin(1.0, amax);
+}
 
 // Right-scaled CG form.  With S = dbar / D (a diagonal in (0, 1]) the Schur operator is
 //     A S = (I/dt + kappa/2 M^2)(I - F) + dbar M (I - F) + M D S ... = P - (I/dt + kappa/2 M^2) F,     F = I - S = (D - dbar) / D,
@@ -1319,6 +1358,63 @@ __device__ __forceinline__ double cheb_last_factor(double theta, double delta, i
     return tkm1 / tk;
 }
 
+// gpart: partials written by the GEMM epilogue (gnblk per trajectory, 1 value each)
+__device__ __forceinline__ double fin_sum1(const double *part, int n, int b, int stride, int k) {
+    double a = 0.0;
+    for (int t = threadIdx.x; t < n; t += 64) a += part[((long)b * n + t) * stride + k];
+    return wave_sum(a);
+}
+
+// What k_fin_ceiling gets after a Chebyshev solve with `enq` sweeps enqueued (enq < 0: no such solve).
+struct ChebFin {
+    int enq, gnblk;
+    const double *g0, *gn;                  // [B][gnblk] partials of <z_0,z_0>_Z and of <z_n,z_n>_Z
+    const double *cmin;                     // [B][gnblk] step-ceiling ratios taken by the solve's last row kernel
+};
+// The books of a finished reduction-free solve: the relative residual it left, estimated as the last directly summed
+// ||z_n||_Z / ||z_0||_Z (partials of k_cheb_rows; all 64 lanes) times the factor T_n / T_{n+1} the bound promises for the last
+// step, and the sweep counts (one lane).
+__device__ __forceinline__ double cheb_solve_rel(int cheb_n, const ChebFin &cheb, int b) {
+    if (cheb_n < 1) return 1.0;
+    const double g0 = fin_sum1(cheb.g0, cheb.gnblk, b, 1, 0), gn = fin_sum1(cheb.gn, cheb.gnblk, b, 1, 0);
+    return g0 > 0.0 ? sqrt(fmax(gn, 0.0) / g0) : 0.0;
+}
+__device__ __forceinline__ void cheb_close_books(TrajState &S, double rel) {
+    rel *= cheb_last_factor(S.cheb_theta, S.cheb_delta, S.cheb_n);
+    S.lin_rel = rel;
+    S.lin_it = S.cheb_n;
+    S.lin_total += S.cheb_n;
+    if (rel * S.lin_rscale > S.lin_maxrel) S.lin_maxrel = rel * S.lin_rscale;
+    S.lin_maxabs = fmax(S.lin_maxabs, rel * S.lin_r0);
+    if (S.cheb_n > S.step_lin_max) S.step_lin_max = S.cheb_n;
+    if (S.step_solves >= 1 && S.step_solves <= 4) S.step_lin[S.step_solves - 1] = S.cheb_n;
+}
+// Start of the Armijo loop (F2:388-396) from the smallest ceiling ratio; lin_active: the solve was cut short by the host's budget
+__device__ __forceinline__ void ceiling_arm(TrajState &S, double vmin, int lin_active) {
+    S.alpha = ceiling_alpha(vmin);
+    if (lin_active && S.lin_rel > S.lin_maxrel) S.lin_maxrel = S.lin_rel;     // the host's sweep budget ran out: go on
+    S.lin_active = 0;                                                         // with an inexact step
+    S.need_trial = 1;
+    S.trial_no = 0;
+    S.force_accept = 0;
+    S.best_norm = 1e300;
+    S.best_alpha = S.alpha;
+}
+
+// Optional tails of k_fin_residual.
+//   cheb.enq >= 0 (MODE 1, the trial that follows a reduction-free solve with cheb.enq sweeps enqueued; so.cell set): no
+//   k_fin_ceiling launch has run.  A trajectory whose solve has just finished (Newton running, no trial pending, use_cheb,
+//   and not a plan longer than cheb.enq that is still lin_active) had its trial armed by k_eval<2> itself from the ceiling
+//   cell; the same is done to the record here -- the solve's books, alpha from the cell, trial 0 -- before the Armijo /
+//   Newton step.
+//   pub != NULL (the launch the host's look follows): the workgroup of trajectory b copies its record to the mapped host
+//   memory pub[b] and then stores val to seq[b] (system-scope release behind a system fence), on every path through the kernel.
+struct FinTail {
+    ChebFin cheb;
+    TrajState *pub;
+    unsigned long long *seq, val;
+};
+
 template <int MODE>
 __device__ __forceinline__ void fin_residual_update(TrajState &S, const double (&v)[NPART], bool primed, double *__restrict__ hist,
                                                     double kappa, double dt, double lin_tol, double eta, SolveOpts so);
@@ -1326,28 +1422,52 @@ __device__ __forceinline__ void fin_residual_update(TrajState &S, const double (
 template <int MODE>
 __global__ void k_fin_residual(TrajState *st, const double *__restrict__ part, int nblk,
                                double *__restrict__ hist, double kappa, double dt, double lin_tol, double eta, int guess,
-                               SolveOpts so) {
+                               SolveOpts so, FinTail tail) {
     const int b = blockIdx.x;
     __shared__ TrajState S;
     traj_copy_in(S, st + b);
+    bool go = true;                // (the same for all 64 lanes)
     if (MODE == 2) {               // after k_eval<0> without the fin step inside: the record has not been armed yet
-        if (S.frozen) return;
-        if (threadIdx.x == 0) {
+        go = !S.frozen;
+        if (go && threadIdx.x == 0) {
             newton_begin(S);
             S.slot = 1 - S.slot;
         }
         __syncthreads();
     }
-    if (!S.newton_active || !S.need_trial) return;
-    double v[NPART];
-    const int op[NPART] = {0, 0, 1, 2, 0, 0};
-    // guess: k_guess has deflated the right-hand side (MODE 0: of the step's first solve; MODE 1: of its second solve, for
-    // a trajectory whose first solve is done); slot 1 holds sum (rhs - A x0)^2, slot 4 sum rhs^2
-    const bool primed = guess_bit((unsigned)guess, b) && (MODE != 1 || S.iters == 1);
-    fin_reduce(part, nblk, b, v, op, primed ? 5 : 4);
-    if (threadIdx.x == 0)
-        fin_residual_update<(MODE == 1 ? 1 : 0)>(S, v, primed, hist + (long)b * HIST_CAP, kappa, dt, lin_tol, eta, so);
-    traj_copy_out(st + b, S);
+    go = go && S.newton_active && S.need_trial;
+    if (MODE == 1 && !go && tail.cheb.enq >= 0 && S.newton_active && S.use_cheb && !(S.lin_active && S.cheb_n > tail.cheb.enq)) {
+        const int books = S.lin_active;             // as in k_fin_ceiling: not after k_cg_publish has taken the flag back
+        const double rel = books ? cheb_solve_rel(S.cheb_n, tail.cheb, b) : 1.0;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            if (books) cheb_close_books(S, rel);
+            ceiling_arm(S, CeilCell::load(so.cell + b * CeilCell::STRIDE), 0);
+        }
+        __syncthreads();
+        go = true;
+    }
+    if (go) {
+        double v[NPART];
+        const int op[NPART] = {0, 0, 1, 2, 0, 0};
+        // guess: k_guess has deflated the right-hand side (MODE 0: of the step's first solve; MODE 1: of its second solve, for
+        // a trajectory whose first solve is done); slot 1 holds sum (rhs - A x0)^2, slot 4 sum rhs^2
+        const bool primed = guess_bit((unsigned)guess, b) && (MODE != 1 || S.iters == 1);
+        fin_reduce(part, nblk, b, v, op, primed ? 5 : 4);
+        if (so.cell) so.cell += b * CeilCell::STRIDE;
+        if (threadIdx.x == 0)
+            fin_residual_update<(MODE == 1 ? 1 : 0)>(S, v, primed, hist + (long)b * HIST_CAP, kappa, dt, lin_tol, eta, so);
+        traj_copy_out(st + b, S);
+    }
+    if (tail.pub) {
+        __syncthreads();
+        const unsigned *s = reinterpret_cast<const unsigned *>(&S);
+        unsigned *d = reinterpret_cast<unsigned *>(tail.pub + b);
+        for (int i = threadIdx.x; i < (int)(sizeof(TrajState) / 4); i += 64) d[i] = s[i];
+        __threadfence_system();
+        __syncthreads();
+        if (threadIdx.x == 0) __hip_atomic_store(tail.seq + b, tail.val, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
 }
 
 template <int MODE>
@@ -1409,6 +1529,7 @@ __device__ __forceinline__ void fin_residual_update(TrajState &S, const double (
         S.use_cheb = (so.cheb_max >= 0 && S.cheb_n <= so.cheb_max) ? 1 : 0;
         S.scaled = (!S.use_cheb && so.scale_ratio > 0.0 && S.Dmax > so.scale_ratio * S.Dmin) ? 1 : 0;
         S.lin_active = 1;
+        if (so.cell) CeilCell::reset(so.cell);          // (the caller's pointer is this trajectory's cell)
         S.lin_it = 0;
         S.lin_prev = 1e300;
         S.lin_rel = 1.0;
@@ -1461,6 +1582,8 @@ struct EvalFin {
     double *hist;              // [B][HIST_CAP] residual-norm histories
     double kappa, lin_tol, eta;
     SolveOpts so;
+    int cheb_enq;              // MODE 2 without the fin step inside: sweeps enqueued for the reduction-free solve this trial follows,
+                               // with no k_fin_ceiling launch in between (FinTail); -1: off
 };
 
 __device__ __forceinline__ void store_agent(double *p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -1505,14 +1628,25 @@ __global__ __launch_bounds__(NTH, EVAL_MINBLK) void k_eval(Geom G, Phys P, TrajS
     // only the few fields the evaluation needs are read here; the record as a whole is read, advanced and written back by
     // one thread of the workgroup that finishes last (a per-thread copy of the record would live in private memory)
     const int S_slot = st[b].slot, S_iters = MODE == 0 ? 0 : st[b].iters;
-    const double S_alpha = MODE == 0 ? 0.0 : st[b].alpha;
+    double S_alpha = MODE == 0 ? 0.0 : st[b].alpha;
+    // (read beside the record, not behind it: the cell's address does not depend on the record)
+    const bool use_cell = MODE == 2 && !FIN_INSIDE && fin.cheb_enq >= 0;
+    const double cell_min = use_cell ? CeilCell::load(fin.so.cell + b * CeilCell::STRIDE) : 1e300;
     if (MODE == 0) {
         if (st[b].frozen) {    // what newton_begin does for a trajectory that sits this march out
             if (blk == 0 && threadIdx.x == 0) st[b].newton_active = st[b].need_trial = st[b].lin_active = 0;
             return;
         }
     } else {
-        if (!st[b].newton_active || !st[b].need_trial) return;
+        if (!st[b].newton_active) return;
+        if (!st[b].need_trial) {
+            // a reduction-free solve that has just finished (no k_fin_ceiling launch: the record is armed by the k_fin_residual
+            // behind this kernel): trial 0 with the step the ceiling cell allows, the same number in every workgroup
+            // (k_fin_ceiling's conditions: an unfinished plan is left alone; lin_active may already have been taken back by
+            // k_cg_publish when a long CG solve of a batch mate ran behind this trajectory's solve)
+            if (!use_cell || !st[b].use_cheb || (st[b].lin_active && st[b].cheb_n > fin.cheb_enq)) return;
+            S_alpha = ceiling_alpha(cell_min);
+        }
     }
     __shared__ double sp[(TY + 4) * (TX + 4)];
     __shared__ double sd[MODE == 2 ? (TY + 4) * (TX + 4) : 1];
@@ -1831,14 +1965,7 @@ __global__ __launch_bounds__(NTH, EVAL_MINBLK) void k_eval(Geom G, Phys P, TrajS
     }
 }
 
-// ---- CG scalar updates (one thread per trajectory does the arithmetic) ----
-// gpart: partials written by the GEMM epilogue (gnblk per trajectory, 1 value each)
-__device__ __forceinline__ double fin_sum1(const double *part, int n, int b, int stride, int k) {
-    double a = 0.0;
-    for (int t = threadIdx.x; t < n; t += 64) a += part[((long)b * n + t) * stride + k];
-    return wave_sum(a);
-}
-
+// ---- CG scalar updates (one thread per trajectory does the arithmetic; fin_sum1 is above k_fin_residual) ----
 // forward set-up: gamma0 = <z, z>_Z with z = P^-1 rhs (from the GEMM epilogue)
 __global__ void k_fin_cg_init(TrajState *st, const double *__restrict__ gpart, int gnblk) {
     const int b = blockIdx.x;
@@ -2010,11 +2137,6 @@ __global__ void k_fin_cg_beta(TrajState *st, const double *__restrict__ part, in
 // not finished (it is left as it is, like an unfinished CG solve under `strict`); for the others the solve's books are
 // closed here: sweeps done, and the relative residual the solve left, estimated as the last directly summed
 // ||z_n||_Z / ||z_0||_Z (partials of k_cheb_rows) times the factor T_n / T_{n+1} the bound promises for the last step.
-struct ChebFin {
-    int enq, gnblk;
-    const double *g0, *gn;                  // [B][gnblk] partials of <z_0,z_0>_Z and of <z_n,z_n>_Z
-    const double *cmin;                     // [B][gnblk] step-ceiling ratios taken by the solve's last row kernel
-};
 __global__ void k_fin_ceiling(TrajState *st, const double *__restrict__ part, int nblk, int strict, int fin_copy, ChebFin cheb) {
     const int b = blockIdx.x;
     __shared__ TrajState S;                 // the record in LDS, copied in and out by the whole wavefront (see k_fin_residual)
@@ -2024,21 +2146,8 @@ __global__ void k_fin_ceiling(TrajState *st, const double *__restrict__ part, in
     int lin_active = S.lin_active;          // (a value every lane keeps: the record itself is advanced by lane 0 only)
     if (cheb.enq >= 0 && lin_active) {
         if (S.cheb_n > cheb.enq) return;    // unfinished: taken up again by the next solve slot / the host's loop
-        double rel = 1.0;
-        if (S.cheb_n >= 1) {
-            const double g0 = fin_sum1(cheb.g0, cheb.gnblk, b, 1, 0), gn = fin_sum1(cheb.gn, cheb.gnblk, b, 1, 0);
-            rel = g0 > 0.0 ? sqrt(fmax(gn, 0.0) / g0) : 0.0;
-        }
-        if (threadIdx.x == 0) {
-            rel *= cheb_last_factor(S.cheb_theta, S.cheb_delta, S.cheb_n);
-            S.lin_rel = rel;
-            S.lin_it = S.cheb_n;
-            S.lin_total += S.cheb_n;
-            if (rel * S.lin_rscale > S.lin_maxrel) S.lin_maxrel = rel * S.lin_rscale;
-            S.lin_maxabs = fmax(S.lin_maxabs, rel * S.lin_r0);
-            if (S.cheb_n > S.step_lin_max) S.step_lin_max = S.cheb_n;
-            if (S.step_solves >= 1 && S.step_solves <= 4) S.step_lin[S.step_solves - 1] = S.cheb_n;
-        }
+        const double rel = cheb_solve_rel(S.cheb_n, cheb, b);
+        if (threadIdx.x == 0) cheb_close_books(S, rel);
         lin_active = 0;
     }
     if (fin_copy >= 0 && lin_active) {
@@ -2058,19 +2167,7 @@ __global__ void k_fin_ceiling(TrajState *st, const double *__restrict__ part, in
     } else {
         fin_reduce(part, nblk, b, v, op, 1);
     }
-    if (threadIdx.x == 0) {
-        double amax = 2.0;
-        if (v[0] < 1e299) amax = fmin(amax, 0.9 * v[0]);
-        if (!isfinite(amax) || amax <= 0.0) amax = 1.0;
-        S.alpha = fmin(1.0, amax);
-        if (lin_active && S.lin_rel > S.lin_maxrel) S.lin_maxrel = S.lin_rel;     // the host's sweep budget ran out: go on
-        S.lin_active = 0;                                                         // with an inexact step
-        S.need_trial = 1;
-        S.trial_no = 0;
-        S.force_accept = 0;
-        S.best_norm = 1e300;
-        S.best_alpha = S.alpha;
-    }
+    if (threadIdx.x == 0) ceiling_arm(S, v[0], lin_active);
     traj_copy_out(st + b, S);
 }
 
