@@ -243,6 +243,48 @@ int vch2d_pgd_get(vch2d_ctx *ctx, int what, double *out);
  * by vch2d_counters like those of any other call. */
 int vch2d_pgd_kkt(vch2d_ctx *ctx, int refresh, double tol, int64_t *counts_out /* [B][4] */,
                   double *stationarity_out /* [B] or NULL */);
+/* Exact first and second directional derivatives of the smooth part J1 + J2 + J3 of the cost along h, about the resident
+ * control and state history (ABI version stays 3: detect this entry point by symbol).  No adjoint and no nonlinear march:
+ * the derivative of one Crank-Nicolson / Newton time level with respect to its inputs is one linear solve with the Newton
+ * matrix J(phi_{n+1}) of vch2d_jacobian_apply at the converged new level, its second derivative one more solve with the
+ * same matrix.  With dphi_0 = dmu_0 = dw_0 = 0 and d2phi_0 = d2mu_0 = 0, per step n:
+ *   dw'  = ((gamma/dt - 1/2) dw + 1/2 (h_{n+1} + h_n)) / (gamma/dt + 1/2)
+ *   J [dphi'; dmu']   = [ tau dphi/dt + kappa/2 L dphi + 2 c2 dphi + 1/2 dmu + 1/2 (dw' + dw) ;  dphi/dt + 1/2 L dmu ]
+ *   J [d2phi'; d2mu'] = [ tau d2phi/dt + kappa/2 L d2phi + 2 c2 d2phi + 1/2 d2mu - c1 rho(phi_{n+1}) (dphi')^2 ;
+ *                         d2phi/dt + 1/2 L d2mu ],      rho(p) = 4 p / (1 - p^2)^2
+ * The end-of-step clip and the interior mass fix of the march are taken as the identity: the linearised scheme conserves the
+ * weighted mass of dphi exactly, and the clip is inactive wherever |phi| < 1 - delta_sep; the call does NOT detect an active
+ * clip.  The L1 term J4 has no curvature away from its kink and is left out.
+ *   h       [B][h_rows][Nx+1][Ny+1] direction, row rule of a control: rows (n, n+1) drive step n while n < h_rows-1, zeros
+ *           afterwards (F2:545-548); in the integrals h counts as zero from row h_rows on
+ *   out[b] = { s_state = b1 int int (phi - phi_Q) dphi + b2 int (phi_M - phi_T) dphi_M,   s_ctrl = b3 int int u h,
+ *              c_gn    = b1 int int dphi^2 + b2 int dphi_M^2,
+ *              c_state = b1 int int (phi - phi_Q) d2phi + b2 int (phi_M - phi_T) d2phi_M,
+ *              c_ctrl  = b3 int int h^2,   n_h = int int h^2 }
+ *           with the cost's nested trapezoid rule in y, x, t and trajectory b's own b1, b2, b3 (n_opts = 1: one set for
+ *           the batch; B: opts[b]; nothing else of opts is read):  J'(u) h = s_state + s_ctrl,
+ *           J''(u)[h,h] = c_gn + c_state + c_ctrl.  order = 1 skips the second march; c_state is then NaN.
+ *   rtol    relative residual at which the linear solves stop (<= 0: 1e-12); every trajectory is gated by its own solve, and
+ *           one whose right-hand side is exactly zero (h == 0) gets exact zeros
+ *   dphi_hist_out, d2phi_hist_out  [B][M+1][Nx+1][Ny+1] or NULL: the tangent fields, copied level by level (they are not
+ *           kept on the device); d2phi_hist_out is written at level 0 only when order = 1
+ * After vch2d_forward: dt, t_hist, x, y are required; phi_Q / phi_T NULL are zeros (as in vch2d_cost); the control is the one
+ * that march ran under.  After vch2d_pgd_init / _iterate the call works about the current iterate (what vch2d_pgd_get(0 / 1)
+ * return): dt, t_hist, x, y may be NULL (the problem's; x, y if given must equal them) and phi_Q, phi_T must be NULL (the
+ * problem's targets).  VCH_ERR_STATE without a resident state history; VCH_ERR_ARG for M != the history's steps, n_opts not
+ * 1 or B, order not 1 or 2, h_rows outside 1..max_steps+1, non-finite b1, b2, b3 -- all before anything is launched.
+ * The control, the state history, the adjoint and the PGD bookkeeping are not touched (the direction goes through the
+ * trial-control scratch): a following vch2d_pgd_iterate is bit for bit that of an uninterrupted run.  Up to 32 trajectories,
+ * a trajectory's six scalars are bitwise those of a single-trajectory context.  stats (or NULL): launches, looks, linear
+ * solves and iterations, device seconds of the call. */
+int vch2d_second_order(vch2d_ctx *ctx, const double *h, int h_rows, const double *dt, int M,
+                       const double *t_hist, const double *x, const double *y,
+                       const double *phi_Q, const double *phi_T,          /* NULL: resident targets (PGD) */
+                       const vch_opt_params *opts, int n_opts,            /* 1 or B; only b1,b2,b3 are read */
+                       int order /* 1 or 2 */, double rtol,
+                       double *out /* [B][6] */,
+                       double *dphi_hist_out, double *d2phi_hist_out      /* [B][M+1][..] or NULL */,
+                       vch_stats *stats);
 /* Per-trajectory cost scalars {J1,J2,J3,J4,J} of the current iterate on the DEVICE
  * (5*B doubles), for the caller's RCCL all-reduce; returns a device pointer via *ptr_dev. */
 int vch2d_pgd_cost_dev(vch2d_ctx *ctx, double **ptr_dev);

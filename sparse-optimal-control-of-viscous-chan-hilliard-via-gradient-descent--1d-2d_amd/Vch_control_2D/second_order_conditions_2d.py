@@ -1,6 +1,7 @@
 """Host-side mirror of src/2D/Vch_control_2D/second_order_conditions_2d.py: finite-difference
 coercivity test (N extra forward marches + costs, all on the GPU through the mirrored
-`run_main_simulation` / `calculate_cost`) and the sparsity (KKT) match statistic."""
+`run_main_simulation` / `calculate_cost`) and the sparsity (KKT) match statistic; beside the reference's
+formula, `exact_second_order_condition_2d` gives the exact second derivative by tangent marches."""
 from __future__ import annotations
 
 import contextlib
@@ -100,6 +101,53 @@ def _perturbed_costs(controls, fwd_config, phi_Q_target, phi_T_target, x, y, t_h
         J = eng.cost(phi_p, U, tile(phi_Q_target), tile(phi_T_target), t_hist, opt, x, y)
         costs.extend(float(v) for v in np.atleast_2d(J)[:, 4])
     return costs
+
+
+def exact_second_order_condition_2d(u_star, r_star, phi_star, x, y, t_hist,
+                                    opt_config: Optional[OptimizationConfig] = None, b1=None, b2=None, b3=None,
+                                    kappa=None, phi_Q_target=None, phi_T_target=None, u_min: float = -np.inf,
+                                    u_max: float = np.inf, num_directions: int = 10, epsilon: float = 1e-4,
+                                    seed: Optional[int] = None,
+                                    fwd_config: Optional[ForwardSolverConfig] = None) -> List[float]:
+    """J''(u*)[h,h] of the smooth part J1 + J2 + J3 of the discrete cost, exactly (to the tolerance of a linear solve), for
+    the same seeded directions as `approximate_second_order_condition_2d` draws: no difference quotient, so `epsilon` is
+    not used.  One forward march of u* tiled over up to MAX_BATCH directions, then one tangent call per chunk
+    (Engine2D.second_order: two linear solves per step and direction).  Per direction the curvature, the exact slope
+    J'(u*)h and the adjoint's unweighted `sum(g h)`, g = r* + b3 u*, that the finite-difference formula subtracts, are
+    printed side by side.  The L1 term J4 has no curvature away from its kink and is left out; the clip at the end of a time
+    step is taken as inactive (|phi| < 1 - delta_sep)."""
+    from ..engine import time_grid
+    from ._ctx import engine_for_config
+    from .Forward2_solver import init_phi_random, DELTA_SEP
+    rng = np.random.default_rng(seed)
+    opt = _ensure_opt_config(b1, b2, b3, kappa, opt_config)
+    if phi_Q_target is None:
+        phi_Q_target = np.zeros_like(phi_star)
+    if phi_T_target is None:
+        phi_T_target = np.zeros_like(phi_star[-1])
+    grad_star = r_star + opt.b3 * u_star
+    print(f"Testing {num_directions} random directions in the critical cone (exact tangent marches)...")
+    dirs = [_generate_direction(u_star, r_star, u_min, u_max, rng) for _ in range(num_directions)]
+    cfg = fwd_config
+    t_grid, dts = time_grid(float(cfg.T), float(cfg.dt_initial))
+    M = len(dts)
+    phi0 = init_phi_random(int(cfg.Nx), int(cfg.Ny), DELTA_SEP, amp=0.1, seed=42)
+    cut = lambda a: np.asarray(a)[:M + 1]                                   # rows beyond the march are never read (F2:545-548)
+    out: List[float] = []
+    for k0 in range(0, len(dirs), MAX_BATCH):
+        chunk = dirs[k0:k0 + MAX_BATCH]
+        nb = len(chunk)
+        eng = engine_for_config(cfg, batch=nb, max_steps=max(M, 1))
+        tile = lambda a: np.ascontiguousarray(np.broadcast_to(a, (nb,) + np.shape(a)))
+        eng.forward(tile(phi0), dts, u=tile(cut(u_star)), store=False)
+        res = eng.second_order(np.stack([cut(h) for h in chunk]), dts, t_grid, opt, phi_Q=tile(cut(phi_Q_target)),
+                               phi_T=tile(phi_T_target), x=x, y=y)
+        for i, h in enumerate(chunk):
+            d2, slope = float(res["curvature"][i]), float(res["slope"][i])
+            out.append(d2)
+            print(f"  Direction {k0 + i + 1}/{num_directions}: exact d²J/dh² = {d2:.6e}   exact slope J'h = {slope:.6e}   "
+                  f"adjoint sum(g·h) = {np.sum(grad_star * h):.6e}")
+    return out
 
 
 def sparsity_statistics(u_optimal, r_optimal, kappa: float, tol: float = 1e-6):

@@ -194,6 +194,12 @@ struct vch2d_ctx {
     std::vector<double> tab_host;
     bool pgd_r_valid;                     // r_hist holds an adjoint of the resident problem (a sweep has run since the init)
     unsigned long long *kkt_dev;          // vch2d_pgd_kkt: [B][3] counts, then [B][Mmax+1][3] per-level partials
+    // vch2d_second_order (lazy): workgroup partials [B][Mmax+1][nblk][TAN_NSUM], level sums [B][Mmax+1][TAN_NSUM], the time
+    // levels [Mmax+1] and the six scalars [B][6] on the device; rows of the control the resident state history was marched
+    // under (0: none)
+    double *tan_part = nullptr, *tan_lvl = nullptr, *tan_t = nullptr, *tan_out = nullptr;
+    int fwd_u_rows = 0;
+    bool res_pgd = false;                 // the resident state history is the resident PGD problem's iterate
     std::vector<double> pgd_cost, pgd_alpha_prev, pgd_J;    // per trajectory
     std::vector<int> pgd_plateau, pgd_done, pgd_k;
     std::vector<std::vector<double>> pgd_cost_hist;
@@ -618,7 +624,8 @@ extern "C" void vch2d_destroy(vch2d_ctx *c) {
                      c->r, c->dmu, c->t1, c->t2, c->cg_p[0], c->cg_p[1], c->cg_v, c->cg_q, c->cg_z2, c->xf, c->dprev[0], c->dprev[1], c->dprev[2], c->dprev[3], c->dprev[4], c->dprev[5], c->dprev[6], c->dprev[7], c->dprev2[0], c->dprev2[1], c->dprev2[2], c->dprev2[3], c->dprev2[4], c->dprev2[5], c->dprev2[6], c->dprev2[7], c->x0g, c->gpart, c->gpart3, c->tmp[0], c->tmp[1], c->tmp[2], c->tmp[3], c->tmp[4], c->tmp[5],
                      c->phiT, c->phi0, c->wts_mass, c->W_cost, c->part, c->part_mass, c->hist_dev, c->alpha_dev, c->opt_tab, c->seam_tab, c->J_dev, c->Q1f,
                      c->Q2f, c->Q1s, c->Q2s, c->mf, c->ms, c->phi_hist, c->u_hist, c->u_trial, c->phi_trial, c->phiQ,
-                     c->r_hist, c->p_hist, c->q_hist, c->cost_part, c->cost_lvl, c->tfrac_dev};
+                     c->r_hist, c->p_hist, c->q_hist, c->cost_part, c->cost_lvl, c->tfrac_dev, c->tan_part, c->tan_lvl, c->tan_t,
+                     c->tan_out};
     for (double *q : all)
         if (q) hipFree(q);
     hipFree(c->st);
@@ -1591,6 +1598,8 @@ extern "C" int vch2d_forward(vch2d_ctx *c, const double *phi0, const double *u, 
     HIPCHK(hipEventRecord(c->ev1, c->stream));
     VCHCHK(sync_state(c));
     c->M_res = M;
+    c->res_pgd = false;
+    c->fwd_u_rows = u_dev ? u_rows : 0;
     if (phi_hist_out) VCHCHK(d2h_hist(c, phi_hist_out, c->phi_hist, M + 1));
     float ms = 0;
     hipEventElapsedTime(&ms, c->ev0, c->ev1);
@@ -1808,6 +1817,7 @@ extern "C" int vch2d_backward(vch2d_ctx *c, const double *phi_hist, int M, const
         VCHCHK(ensure_hist(c, &c->phi_hist));
         VCHCHK(h2d_hist(c, c->phi_hist, phi_hist, M + 1));
         c->M_res = M;
+        c->res_pgd = false;
     } else {
         if (c->M_res != M) return vch_fail(VCH_ERR_STATE, "vch2d_backward: no resident history with %d steps", M);
     }
@@ -1957,6 +1967,7 @@ extern "C" int vch2d_cost(vch2d_ctx *c, const double *phi_hist, const double *u,
         VCHCHK(ensure_hist(c, &c->phi_hist));
         VCHCHK(h2d_hist(c, c->phi_hist, phi_hist, M + 1));
         c->M_res = M;
+        c->res_pgd = false;
     } else if (c->M_res != M) {
         return vch_fail(VCH_ERR_STATE, "vch2d_cost: no resident history with %d steps", M);
     }
@@ -1997,6 +2008,7 @@ extern "C" int vch2d_free_energy(vch2d_ctx *c, const double *phi_hist, int rows,
         VCHCHK(ensure_hist(c, &c->phi_hist));
         VCHCHK(h2d_hist(c, c->phi_hist, phi_hist, rows));
         c->M_res = rows - 1;
+        c->res_pgd = false;
         pd = c->phi_hist;
     }
     if (w_hist) {                      // the coupling field travels through the trial-state buffer
@@ -2147,6 +2159,7 @@ extern "C" int vch2d_pgd_init_v(vch2d_ctx *c, const double *phi0, const double *
     if (u0) VCHCHK(forward_core(c, c->u_hist, M + 1, c->dt.data(), M, c->phi_hist));
     else VCHCHK(forward_core(c, nullptr, 0, c->dt.data(), M, c->phi_hist));
     c->M_res = M;
+    c->res_pgd = false;
     c->pgd_J.assign(5 * c->B, 0.0);
     VCHCHK(cost_core(c, c->phi_hist, c->u_hist, (phi_Q || ramp) ? c->phiQ : nullptr, c->phiT, false, M, c->t_hist.data(),
                      c->opts.data(), c->pgd_J.data(), nullptr, c->B));
@@ -2177,6 +2190,7 @@ extern "C" int vch2d_pgd_init_v(vch2d_ctx *c, const double *phi0, const double *
     if (J0_out) memcpy(J0_out, c->pgd_J.data(), sizeof(double) * 5 * c->B);
     c->pgd_iter_total = 0;
     c->pgd_ready = true;
+    c->res_pgd = true;
     return 0;
 }
 
@@ -2372,6 +2386,150 @@ extern "C" int vch2d_pgd_kkt(vch2d_ctx *c, int refresh, double tol, int64_t *cou
         for (int b = 0; b < B; ++b) stationarity_out[b] = std::sqrt(chg[2 * b]) / (std::sqrt(chg[2 * b + 1]) + 1e-9);
     }
     return 0;
+}
+
+// ------------------------------------------------------------------------------------
+// exact second-order check: tangent marches about the resident control and state history (kernels: "Tangent march" in
+// vch_kernels2d.h)
+// ------------------------------------------------------------------------------------
+// One tangent solve: the right-hand side is in slot 0 (k_tan_rhs); x = 0 start, the context's lin_tol, every trajectory
+// gated by its own lin_active; on return dphi' is in c->xf and dmu' in c->dmu.
+static int tangent_solve(vch2d_ctx *c, double dt) {
+    LAUNCH(k_fin_lin_begin, dim3(c->B), dim3(64), c->st, c->part, c->nblk, 2, c->P.tau, c->P.kappa, dt, c->lin_tol);
+    LAUNCH(k_tan_arm, dim3((c->B + 63) / 64), dim3(64), c->st, c->B);
+    VCHCHK(sync_state(c, false));
+    VCHCHK(schur_solve(c, dt, cg_budget(c, false), true));
+    return dmu_ceiling(c, 0);
+}
+
+// one level of a [B][plane] work plane -> host history [B][M+1][ns][nf] (asynchronous; the caller synchronises)
+static int tangent_level_out(vch2d_ctx *c, double *host, const double *dev, int M, int lvl) {
+    const size_t lev = (size_t)c->G.nf * c->G.ns;
+    for (int b = 0; b < c->B; ++b)
+        HIPCHK(hipMemcpy2DAsync(host + ((size_t)b * (M + 1) + lvl) * lev, (size_t)c->G.nf * 8, dev + b * c->G.plane,
+                                (size_t)c->G.pitch * 8, (size_t)c->G.nf * 8, (size_t)c->G.ns, hipMemcpyDeviceToHost, c->stream));
+    return 0;
+}
+
+static int second_order_core(vch2d_ctx *c, const double *h, int h_rows, const double *dt, int M, const double *t_hist,
+                             const double *pq, const double *pt, const vch_opt_params *opts, int n_opts, int order, double *out,
+                             double *dphi_hist_out, double *d2phi_hist_out, vch_stats *stats) {
+    const Geom &G = c->G;
+    const int B = c->B, levels = M + 1;
+    const long hs = hist_stride(c);
+    if (!c->tan_part) HIPCHK(hipMalloc((void **)&c->tan_part, (size_t)B * (c->Mmax + 1) * c->nblk * TAN_NSUM * 8));
+    if (!c->tan_lvl) HIPCHK(hipMalloc((void **)&c->tan_lvl, (size_t)B * (c->Mmax + 1) * TAN_NSUM * 8));
+    if (!c->tan_t) HIPCHK(hipMalloc((void **)&c->tan_t, (size_t)(c->Mmax + 1) * 8));
+    if (!c->tan_out) HIPCHK(hipMalloc((void **)&c->tan_out, (size_t)B * 6 * 8));
+    VCHCHK(ensure_hist(c, &c->u_trial));            // the direction lives in the trial-control scratch
+    VCHCHK(h2d_hist(c, c->u_trial, h, h_rows));
+    VCHCHK(write_opt_tab(c, c->seam_tab, opts, n_opts));
+    HIPCHK(hipMemcpyAsync(c->tan_t, t_hist, sizeof(double) * levels, hipMemcpyHostToDevice, c->stream));
+    VCHCHK(reset_counters(c));
+    HIPCHK(hipEventRecord(c->ev0, c->stream));
+    // planes: dphi, dmu, d2phi, d2mu, and dw in two copies
+    double *dphi = c->tmp[0], *dmu = c->tmp[1], *d2phi = c->tmp[2], *d2mu = c->tmp[3], *dw[2] = {c->tmp[4], c->tmp[5]};
+    for (int k = 0; k < 6; ++k) HIPCHK(hipMemsetAsync(c->tmp[k], 0, sizeof(double) * B * G.plane, c->stream));
+    c->guess_wr = -1;          // the back substitution keeps no increment for a march's starting guesses
+    c->cheb_enq = -1;
+    const int u_rows = c->res_pgd ? levels : std::min(c->fwd_u_rows, levels);
+    const long part_stride = (long)levels * c->nblk * TAN_NSUM;
+    auto level = [&](int lvl, const double *d1, const double *d2, double *dst_phi, double *dst_mu) -> int {
+        TanLevelArgs a{c->phi_hist + (long)lvl * G.plane,
+                       pq ? pq + (long)lvl * G.plane : (const double *)nullptr,
+                       lvl < u_rows ? c->u_hist + (long)lvl * G.plane : (const double *)nullptr,
+                       lvl < h_rows ? c->u_trial + (long)lvl * G.plane : (const double *)nullptr,
+                       hs, pt, lvl == M ? 1 : 0, d1, d2, c->xf, c->dmu, dst_phi, dst_mu, c->W_cost};
+        LAUNCH(k_tan_level, c->grid, dim3(NTH), G, a, c->tan_part + (long)lvl * c->nblk * TAN_NSUM, part_stride);
+        return 0;
+    };
+    VCHCHK(level(0, nullptr, nullptr, nullptr, nullptr));
+    if (dphi_hist_out) VCHCHK(tangent_level_out(c, dphi_hist_out, dphi, M, 0));
+    if (d2phi_hist_out) VCHCHK(tangent_level_out(c, d2phi_hist_out, d2phi, M, 0));
+    for (int n = 0; n < M; ++n) {
+        const double *phi1 = c->phi_hist + (long)(n + 1) * G.plane;
+        const bool live = n < h_rows - 1;           // F2:545-548
+        TanRhsArgs a1{dphi, dmu, dw[n & 1], dw[(n + 1) & 1], live ? c->u_trial + (long)n * G.plane : (const double *)nullptr,
+                      live ? c->u_trial + (long)(n + 1) * G.plane : (const double *)nullptr, phi1, hs, nullptr, nullptr, nullptr,
+                      nullptr};
+        LAUNCH((k_tan_rhs<0>), c->grid, dim3(NTH), G, c->P, a1, dt[n], c->Rphi_s, c->rhs_s, c->D_s, c->part);
+        VCHCHK(tangent_solve(c, dt[n]));
+        if (order == 2) {
+            TanRhsArgs a2{d2phi, d2mu, nullptr, nullptr, nullptr, nullptr, phi1, hs, c->xf, c->dmu, dphi, dmu};
+            LAUNCH((k_tan_rhs<1>), c->grid, dim3(NTH), G, c->P, a2, dt[n], c->Rphi_s, c->rhs_s, c->D_s, c->part);
+            VCHCHK(tangent_solve(c, dt[n]));
+            if (dphi_hist_out) VCHCHK(tangent_level_out(c, dphi_hist_out, dphi, M, n + 1));
+            if (d2phi_hist_out) VCHCHK(tangent_level_out(c, d2phi_hist_out, c->xf, M, n + 1));
+            VCHCHK(level(n + 1, dphi, c->xf, d2phi, d2mu));
+        } else {
+            if (dphi_hist_out) VCHCHK(tangent_level_out(c, dphi_hist_out, c->xf, M, n + 1));
+            VCHCHK(level(n + 1, c->xf, nullptr, dphi, dmu));
+        }
+    }
+    LAUNCH(k_tan_fin, dim3(B * levels), dim3(64), c->nblk, (const double *)c->tan_part, c->tan_lvl);
+    LAUNCH(k_tan_scalars, dim3(B), dim3(64), M, (const double *)c->tan_lvl, (const double *)c->tan_t, (const double *)c->seam_tab,
+           order, c->tan_out);
+    HIPCHK(hipEventRecord(c->ev1, c->stream));
+    HIPCHK(hipMemcpyAsync(out, c->tan_out, sizeof(double) * 6 * B, hipMemcpyDeviceToHost, c->stream));
+    VCHCHK(sync_state(c));
+    float ms = 0;
+    hipEventElapsedTime(&ms, c->ev0, c->ev1);
+    fill_stats(c, stats, ms);
+    return reset_counters(c);       // the records as the end of a PGD iteration leaves them
+}
+
+extern "C" int vch2d_second_order(vch2d_ctx *c, const double *h, int h_rows, const double *dt, int M, const double *t_hist,
+                                  const double *x, const double *y, const double *phi_Q, const double *phi_T,
+                                  const vch_opt_params *opts, int n_opts, int order, double rtol, double *out,
+                                  double *dphi_hist_out, double *d2phi_hist_out, vch_stats *stats) {
+    CTXCHK(c);
+    // everything below is checked before anything is enqueued or any resident state changes
+    if (c->M_res < 1 || !c->phi_hist)
+        return vch_fail(VCH_ERR_STATE, "vch2d_second_order: no resident state history (call vch2d_forward or vch2d_pgd_init first)");
+    ARGCHK(h && opts && out, "NULL h, opts or out");
+    ARGCHK(M == c->M_res, "M differs from the steps of the resident state history");
+    ARGCHK(n_opts == 1 || n_opts == c->B, "n_opts must be 1 or the context's batch");
+    ARGCHK(order == 1 || order == 2, "order must be 1 or 2");
+    ARGCHK(h_rows >= 1 && h_rows <= c->Mmax + 1, "direction rows out of range (1..max_steps+1)");
+    for (int b = 0; b < c->B; ++b) {
+        const vch_opt_params &o = opts[n_opts == 1 ? 0 : b];
+        if (!std::isfinite(o.b1) || !std::isfinite(o.b2) || !std::isfinite(o.b3))
+            return vch_fail(VCH_ERR_ARG, "vch2d_second_order: trajectory %d: b1, b2, b3 must be finite", b);
+    }
+    const bool pgd = c->pgd_ready && c->res_pgd;
+    if (pgd) {
+        ARGCHK(!phi_Q && !phi_T, "the resident problem's targets are used: pass phi_Q = phi_T = NULL");
+        if (x) for (int i = 0; i <= c->prm.Nx; ++i) ARGCHK(x[i] == c->xg[i], "x differs from the resident problem's grid");
+        if (y) for (int j = 0; j <= c->prm.Ny; ++j) ARGCHK(y[j] == c->yg[j], "y differs from the resident problem's grid");
+        if (!dt) dt = c->dt.data();
+        if (!t_hist) t_hist = c->t_hist.data();
+    } else {
+        ARGCHK(dt && t_hist && x && y, "NULL dt, t_hist, x or y without a resident problem");
+    }
+    for (int k = 0; k < M; ++k) ARGCHK(dt[k] > 0, "dt must be positive");
+    const double *pq = nullptr, *pt = nullptr;
+    if (pgd) {
+        pq = c->phiQ;
+        pt = c->phiT;
+    } else {
+        VCHCHK(set_cost_weights(c, x, y));
+        if (phi_Q) {
+            VCHCHK(ensure_hist(c, &c->phiQ));
+            VCHCHK(h2d_hist(c, c->phiQ, phi_Q, M + 1));
+            pq = c->phiQ;
+        }
+        if (phi_T) {
+            VCHCHK(h2d(c, c->phiT, phi_T, c->B));
+            pt = c->phiT;
+        }
+    }
+    // the solves stop at rtol (relative residual); the context's own tolerance comes back on every path out
+    const double keep_tol = c->lin_tol;
+    c->lin_tol = rtol > 0 ? rtol : 1e-12;
+    const int rc = second_order_core(c, h, h_rows, dt, M, t_hist, pq, pt, opts, n_opts, order, out, dphi_hist_out, d2phi_hist_out,
+                                     stats);
+    c->lin_tol = keep_tol;
+    return rc;
 }
 
 extern "C" int vch2d_pgd_cost_dev(vch2d_ctx *c, double **ptr_dev) {

@@ -2569,3 +2569,195 @@ __global__ __launch_bounds__(NTH) void k_cg_update_adj(Geom G, const TrajState *
     const int op[2] = {0, 0};
     block_reduce_store<2>(acc, op, sred, part + ((long)b * nblk + blk) * NPART);
 }
+
+// ---------------------------------------------------------------------------------
+// Tangent (linearised) march of vch2d_second_order: J'(u)h and J''(u)[h,h] about the resident control and state history.
+//
+// With delta-phi_0 = delta-mu_0 = delta-w_0 = 0 and the second-order fields delta2-phi_0 = delta2-mu_0 = 0, step n is
+//   dw'  = ((gamma/dt - 1/2) dw + 1/2 (h_{n+1} + h_n)) / (gamma/dt + 1/2)                              (the solve_w rule)
+//   J(phi_{n+1}) [dphi'; dmu']   = [ tau dphi/dt + kappa/2 L dphi + 2 c2 dphi + 1/2 dmu + 1/2 (dw' + dw) ;  dphi/dt + 1/2 L dmu ]
+//   J(phi_{n+1}) [d2phi'; d2mu'] = [ tau d2phi/dt + kappa/2 L d2phi + 2 c2 d2phi + 1/2 d2mu - c1 rho(phi_{n+1}) (dphi')^2 ;
+//                                    d2phi/dt + 1/2 L d2mu ],        rho(p) = 4 p / (1 - p^2)^2 = reglog''(p)
+// J = the Newton matrix of k_jac_apply at the converged level n+1 of the history: one linear solve per field and step, by the
+// Schur reduction + preconditioned CG of the Newton solves (k_fin_lin_begin -> schur_solve -> dmu_ceiling).
+// The end-of-step clip and the interior mass fix of the march are taken as the identity: the linearised scheme conserves
+// the weighted mass of dphi exactly, and the clip is inactive wherever |phi| < 1 - delta_sep.  An active clip is NOT detected.
+// ---------------------------------------------------------------------------------
+__device__ __forceinline__ double tan_rho(double phi) {      // reglog''(p), p clipped to the band of jac_diag
+    const double lim = sqrt(1.0 - DELTA_SEP * DELTA_SEP);
+    const double p = fmin(fmax(phi, -lim), lim), q = 1.0 - p * p;
+    return 4.0 * p / (q * q);
+}
+
+struct TanRhsArgs {
+    const double *a, *m;            // [B][plane] dphi, dmu of level n (SECOND: d2phi, d2mu)
+    const double *w_in;             // first order: dw of level n ...
+    double *w_out;                  // ... and where dw' goes (another plane: neighbours read w_in on their halo)
+    const double *hn, *hp;          // first order: rows n, n+1 of the direction (history layout), NULL = zeros (F2:545-548)
+    const double *phi1;             // level n+1 of the state history
+    long hist_stride;               // trajectory stride of hn, hp, phi1
+    const double *d1, *m1;          // SECOND: this step's finished dphi', dmu' (the solver's output planes) ...
+    double *keep_phi, *keep_mu;     // ... and the planes that keep them while the second solve reuses the solver's
+};
+
+// Right-hand side of a tangent solve in the form k_solve_setup leaves: with [A; Bv] the right-hand side above,
+// R_phi := -A, rhs := Bv - L A (Schur), D from phi_{n+1}, partials {-, sum rhs^2, min D, max D} for k_fin_lin_begin (mode 2).
+// A is evaluated on the tile and its one-node halo (from dphi with a two-node halo), so that L A needs no second launch.
+template <int SECOND>
+__global__ __launch_bounds__(NTH) void k_tan_rhs(Geom G, Phys P, TanRhsArgs a, double dt, double *__restrict__ Rphi,
+                                                 double *__restrict__ rhs, double *__restrict__ D, double *__restrict__ part) {
+    TILE_COORDS;
+    __shared__ double sa[(TY + 4) * (TX + 4)];
+    __shared__ double sm[(TY + 2) * (TX + 2)];
+    __shared__ double sr[(TY + 2) * (TX + 2)];
+    __shared__ double sred[NPART * 4];
+    constexpr int W2 = TX + 4, W = TX + 2;
+    const long pb = b * G.plane, hb = b * a.hist_stride;
+    load_tile<2>(sa, a.a + pb, G, c0, r0);
+    load_tile<1>(sm, a.m + pb, G, c0, r0);
+    __syncthreads();
+    const double gdt = P.gamma / dt;
+    auto w_new = [&](long o, double w0) {
+        const double h0 = a.hn ? a.hn[hb + o] : 0.0, h1 = a.hp ? a.hp[hb + o] : 0.0;
+        return ((gdt - 0.5) * w0 + 0.5 * (h1 + h0)) / (gdt + 0.5);
+    };
+    for (int e = threadIdx.x; e < W * (TY + 2); e += NTH) {
+        const int ly = e / W, lxx = e - ly * W;
+        const int gr = refl(r0 - 1 + ly, G.ns), gc = refl(c0 - 1 + lxx, G.nf);
+        const long o = (long)gr * G.pitch + gc;
+        const int p2 = (ly + 1) * W2 + lxx + 1;
+        const double av = sa[p2];
+        double v = P.tau * av / dt + 0.5 * P.kappa * lap_at<W2>(sa, p2, G.ax, G.ay) + 2.0 * P.c2 * av + 0.5 * sm[e];
+        if (SECOND) {
+            const double d = a.d1[pb + o];
+            v -= P.c1 * tan_rho(a.phi1[hb + o]) * (d * d);
+        } else {
+            const double w0 = a.w_in[pb + o];
+            v += 0.5 * (w_new(o, w0) + w0);
+        }
+        sr[e] = v;
+    }
+    __syncthreads();
+    double acc[4] = {0.0, 0.0, 1e300, -1e300};
+    for (int k = 0; k < TY / 4; ++k) {
+        int ly = ly0 + 4 * k, r = r0 + ly, c = c0 + lx;
+        if (r < G.ns && c < G.nf) {
+            const int p = (ly + 1) * W + lx + 1;
+            const long o = (long)r * G.pitch + c;
+            const double rm = sa[(ly + 2) * W2 + lx + 2] / dt + 0.5 * lap_at<W>(sm, p, G.ax, G.ay);
+            const double rh = rm - lap_at<W>(sr, p, G.ax, G.ay);
+            const double d = jac_diag(a.phi1[hb + o], P.tau / dt, P.c1);
+            Rphi[pb + o] = -sr[p];
+            rhs[pb + o] = rh;
+            D[pb + o] = d;
+            if (SECOND) {
+                a.keep_phi[pb + o] = a.d1[pb + o];
+                a.keep_mu[pb + o] = a.m1[pb + o];
+            } else {
+                a.w_out[pb + o] = w_new(o, a.w_in[pb + o]);
+            }
+            acc[1] += rh * rh;
+            acc[2] = fmin(acc[2], d);
+            acc[3] = fmax(acc[3], d);
+        }
+    }
+    const int op[4] = {0, 0, 1, 2};
+    block_reduce_store<4>(acc, op, sred, part + ((long)b * nblk + blk) * NPART);
+}
+
+// The stand-alone solve sequence outside a Newton loop: after k_fin_lin_begin, the record is put into the phase the back
+// substitution (k_dmu_ceiling / k_dmu_ceiling_fin, k_fin_ceiling) expects -- Newton running, no trial pending.  The trial
+// those kernels arm and the step ceiling they take are never consumed: the next solve's k_tan_arm clears them.
+__global__ void k_tan_arm(TrajState *st, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    st[b].newton_active = 1;
+    st[b].need_trial = 0;
+    st[b].x_primed = 0;
+    st[b].lin_rscale = 1.0;
+}
+
+// Integrands of one level, weighted with W_cost (nested trapezoid rule in y, x), per workgroup:
+//   {W e dphi, W dphi^2, W e d2phi, W u h, W h^2, W eT dphi, W eT d2phi, 0},  e = phi - phi_Q, eT = phi_M - phi_T (last level only)
+// and the hand-over of the level's fields from the solver's output planes to the planes the next step reads.
+constexpr int TAN_NSUM = 8;
+struct TanLevelArgs {
+    const double *phi, *pq, *u, *h;     // this level of the histories (trajectory stride hist_stride); pq, u, h may be NULL (zeros)
+    long hist_stride;
+    const double *pt;                   // [B][plane] terminal target or NULL (zeros); read on the last level
+    int last;
+    const double *d1, *d2;              // [B][plane] dphi, d2phi of this level, NULL = zeros
+    const double *src_phi, *src_mu;     // copy src -> dst at every node (NULL dst: no copy)
+    double *dst_phi, *dst_mu;
+    const double *W;
+};
+__global__ __launch_bounds__(NTH) void k_tan_level(Geom G, TanLevelArgs a, double *__restrict__ part /* this level's [B][nblk][8] */,
+                                                   long part_stride) {
+    TILE_COORDS;
+    __shared__ double sred[TAN_NSUM * 4];
+    const long pb = b * G.plane, hb = b * a.hist_stride;
+    double acc[TAN_NSUM] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int k = 0; k < TY / 4; ++k) {
+        int r = r0 + ly0 + 4 * k, c = c0 + lx;
+        if (r < G.ns && c < G.nf) {
+            const long o = (long)r * G.pitch + c;
+            const double w = a.W[o], ph = a.phi[hb + o];
+            const double e = ph - (a.pq ? a.pq[hb + o] : 0.0);
+            const double uu = a.u ? a.u[hb + o] : 0.0, hh = a.h ? a.h[hb + o] : 0.0;
+            const double d1 = a.d1 ? a.d1[pb + o] : 0.0, d2 = a.d2 ? a.d2[pb + o] : 0.0;
+            acc[0] += w * (e * d1);
+            acc[1] += w * (d1 * d1);
+            acc[2] += w * (e * d2);
+            acc[3] += w * (uu * hh);
+            acc[4] += w * (hh * hh);
+            if (a.last) {
+                const double eT = ph - (a.pt ? a.pt[pb + o] : 0.0);
+                acc[5] += w * (eT * d1);
+                acc[6] += w * (eT * d2);
+            }
+            if (a.dst_phi) {
+                a.dst_phi[pb + o] = a.src_phi[pb + o];
+                a.dst_mu[pb + o] = a.src_mu[pb + o];
+            }
+        }
+    }
+    const int op[TAN_NSUM] = {0, 0, 0, 0, 0, 0, 0, 0};
+    block_reduce_store<TAN_NSUM>(acc, op, sred, part + b * part_stride + (long)blk * TAN_NSUM);
+}
+
+// level sums out[b][lvl][8] from the workgroup partials [b][lvl][ntiles][8], in a fixed order; grid = B * levels
+__global__ void k_tan_fin(int ntiles, const double *__restrict__ part, double *__restrict__ out) {
+    const long idx = (long)blockIdx.x;
+    double a[TAN_NSUM] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int t = threadIdx.x; t < ntiles; t += 64)
+        for (int k = 0; k < TAN_NSUM; ++k) a[k] += part[(idx * ntiles + t) * TAN_NSUM + k];
+    for (int k = 0; k < TAN_NSUM; ++k) {
+        double v = wave_sum(a[k]);
+        if (threadIdx.x == 0) out[idx * TAN_NSUM + k] = v;
+    }
+}
+
+// np.trapz over t of the level sums and the six scalars of a trajectory, with its own b1, b2, b3; grid = B, 64 threads
+//   out[b] = {s_state, s_ctrl, c_gn, c_state, c_ctrl, n_h}   (c_state = NaN when order == 1)
+__global__ void k_tan_scalars(int M, const double *__restrict__ lvl, const double *__restrict__ t,
+                              const double *__restrict__ opt_tab, int order, double *__restrict__ out) {
+    const int b = blockIdx.x, k = threadIdx.x;
+    __shared__ double I[TAN_NSUM];
+    const double *s = lvl + (long)b * (M + 1) * TAN_NSUM;
+    if (k < TAN_NSUM) {
+        double acc = 0.0;
+        for (int n = 0; n < M; ++n) acc += (t[n + 1] - t[n]) * (s[(n + 1) * TAN_NSUM + k] + s[n * TAN_NSUM + k]) / 2.0;
+        I[k] = acc;
+    }
+    __syncthreads();
+    if (k != 0) return;
+    const double b1 = opt_tab[b * OPT_STRIDE + OPT_B1], b2 = opt_tab[b * OPT_STRIDE + OPT_B2], b3 = opt_tab[b * OPT_STRIDE + OPT_B3];
+    const double *sM = s + (long)M * TAN_NSUM;
+    double *o = out + 6 * b;
+    o[0] = b1 * I[0] + b2 * sM[5];
+    o[1] = b3 * I[3];
+    o[2] = b1 * I[1] + b2 * sM[1];
+    o[3] = order == 2 ? b1 * I[2] + b2 * sM[6] : __longlong_as_double(0x7ff8000000000000LL);
+    o[4] = b3 * I[4];
+    o[5] = I[4];
+}

@@ -317,6 +317,58 @@ class Engine2D:
         check(self.lib.vch2d_pgd_get(self.ctx, {"u": 0, "phi": 1, "r": 2, "phi_Q": 3}[what], _dp(out)))
         return self._sq(out)
 
+    SECOND_ORDER_KEYS = ("s_state", "s_ctrl", "c_gn", "c_state", "c_ctrl", "n_h")
+
+    def second_order(self, h, dt=None, t_hist=None, opt=None, phi_Q=None, phi_T=None, x=None, y=None, order=2, rtol=0.0,
+                     histories=False):
+        """Exact J'(u)h and J''(u)[h,h] of the smooth part J1 + J2 + J3 about the resident control and state history
+        (vch2d_second_order): tangent marches, two linear solves per step and direction, no finite differences.
+        After forward(): dt, t_hist are required, x / y default to the engine's grid, phi_Q / phi_T None are zeros.  After
+        pgd_init() / pgd_iterate(): the current iterate with the problem's grid, time levels and targets (leave dt, t_hist,
+        x, y, phi_Q, phi_T None).
+        h: (B, rows, Nx+1, Ny+1), the row rule of a control.  opt: one parameter object or a sequence of B (only b1, b2, b3
+        are read).  Returns a dict of [B] arrays: the six scalars of SECOND_ORDER_KEYS, slope = s_state + s_ctrl,
+        curvature = c_gn + c_state + c_ctrl (NaN with order=1), `stats`, and with histories=True dphi, d2phi [B][M+1][..]."""
+        h = self._hist(h, 0, "h")
+        if dt is None or t_hist is None:
+            if not hasattr(self, "_pgd_M"):
+                raise ValueError("dt and t_hist are required without a resident PGD problem")
+            dt = t_hist = None
+            M = self._pgd_M
+        else:
+            dt = np.ascontiguousarray(dt, dtype=np.float64)
+            t_hist = np.ascontiguousarray(t_hist, dtype=np.float64)
+            M = int(dt.size)
+            if t_hist.size != M + 1:
+                raise ValueError("t_hist must have len(dt) + 1 entries")
+            x = self.x if x is None else x
+            y = self.y if y is None else y
+        if x is not None or y is not None:
+            x = np.ascontiguousarray(self.x if x is None else x, dtype=np.float64)
+            y = np.ascontiguousarray(self.y if y is None else y, dtype=np.float64)
+            if x.shape != (self.Nx + 1,) or y.shape != (self.Ny + 1,):
+                raise ValueError("x, y must have Nx+1, Ny+1 entries")
+        pq = None if phi_Q is None else self._hist(phi_Q, M + 1, "phi_Q_target")
+        pt = None if phi_T is None else self._fld(phi_T, "phi_T_target")
+        seq = list(opt) if isinstance(opt, (list, tuple)) else [opt]
+        arr = (OptParams * len(seq))(*[o if isinstance(o, OptParams) else make_opt(o) for o in seq])
+        out = np.empty((self.B, 6))
+        d1 = self._out(rows=M + 1) if histories else None
+        d2 = self._out(rows=M + 1) if histories else None
+        if d2 is not None:
+            d2[...] = 0.0
+        st = Stats()
+        check(self.lib.vch2d_second_order(self.ctx, _dp(h), int(h.shape[1]), _dp(dt), M, _dp(t_hist), _dp(x), _dp(y), _dp(pq),
+                                          _dp(pt), arr, len(seq), int(order), float(rtol), _dp(out), _dp(d1), _dp(d2),
+                                          C.byref(st)))
+        res = {k: out[:, i].copy() for i, k in enumerate(self.SECOND_ORDER_KEYS)}
+        res["slope"] = out[:, 0] + out[:, 1]
+        res["curvature"] = (out[:, 2] + out[:, 3]) + out[:, 4]
+        res["stats"] = st.as_dict()
+        if histories:
+            res["dphi"], res["d2phi"] = d1, d2
+        return res
+
     def pgd_cost_device_ptr(self):
         p = C.c_void_p()
         check(self.lib.vch2d_pgd_cost_dev(self.ctx, C.byref(p)))

@@ -1,0 +1,78 @@
+"""CPU reference of the tangent (linearised) march behind the exact second-order check, built from the oracle's assembled
+Newton matrix and a sparse direct solve.  Shared by test_tangent_cpu.py (which pins it against central differences of the
+oracle's nonlinear march) and test_gpu_second_order.py (which compares the engine with it).
+
+With dphi_0 = dmu_0 = dw_0 = 0 and d2phi_0 = d2mu_0 = 0, per step n (dt = t_{n+1} - t_n, J = jac_matrix(phi_{n+1})):
+    dw'  = w_filter(dw, dt, gamma, h_n, h_{n+1})                       rows (n, n+1) while n < len(h) - 1, zeros afterwards
+    J [dphi'; dmu']   = [tau dphi/dt + kappa/2 L dphi + 2 c2 dphi + dmu/2 + (dw' + dw)/2 ;  dphi/dt + L dmu / 2]
+    J [d2phi'; d2mu'] = [tau d2phi/dt + kappa/2 L d2phi + 2 c2 d2phi + d2mu/2 - c1 rho(phi_{n+1}) dphi'^2 ;  d2phi/dt + L d2mu / 2]
+    rho(p) = 4 p / (1 - p^2)^2
+The clip and the mass fix at the end of a step are taken as the identity (callers assert max|phi| < 1 - delta_sep)."""
+import numpy as np
+from scipy.sparse.linalg import spsolve
+
+from oracle import vch2d_oracle as o
+
+KEYS = ("s_state", "s_ctrl", "c_gn", "c_state", "c_ctrl", "n_h")
+
+
+def tangent_reference(P, phi_hist, t_hist, h):
+    """(dphi_hist, d2phi_hist), both shaped like phi_hist, for the direction h (rows, Nx+1, Ny+1)."""
+    Nx, Ny = int(P.Nx), int(P.Ny)
+    hx, hy = P.Lx / Nx, P.Ly / Ny
+    L = o.lap_matrix(Nx, Ny, hx, hy)
+    n = (Nx + 1) * (Ny + 1)
+    M = len(t_hist) - 1
+    d1 = np.zeros_like(phi_hist)
+    d2 = np.zeros_like(phi_hist)
+    z = np.zeros(phi_hist.shape[1:])
+    dphi, dmu, dw, ephi, emu = z, z, z, z, z
+
+    def rhs(a, m, dt):
+        return (P.tau * a / dt + 0.5 * P.kappa * o.lap(a, hx, hy) + 2.0 * P.c2 * a + 0.5 * m,
+                a / dt + 0.5 * o.lap(m, hx, hy))
+
+    def solve(J, rp, rm):
+        s = spsolve(J, np.concatenate([rp.ravel(), rm.ravel()]))
+        return s[:n].reshape(z.shape), s[n:].reshape(z.shape)
+
+    for k in range(M):
+        dt = float(t_hist[k + 1] - t_hist[k])
+        hn, hp = (h[k], h[k + 1]) if k < h.shape[0] - 1 else (z, z)
+        dw_new = o.w_filter(dw, dt, P.gamma, hn, hp)
+        p = phi_hist[k + 1]
+        J = o.jac_matrix(p, dt, P, L).tocsc()
+        rp, rm = rhs(dphi, dmu, dt)
+        nphi, nmu = solve(J, rp + 0.5 * (dw_new + dw), rm)
+        rp, rm = rhs(ephi, emu, dt)
+        ephi, emu = solve(J, rp - P.c1 * (4.0 * p / (1.0 - p * p) ** 2) * nphi ** 2, rm)
+        dphi, dmu, dw = nphi, nmu, dw_new
+        d1[k + 1], d2[k + 1] = dphi, ephi
+    return d1, d2
+
+
+def pad_rows(a, rows):
+    """a cut or zero-padded to `rows` leading rows (a direction or control counts as zero beyond its last row)."""
+    out = np.zeros((rows,) + a.shape[1:])
+    k = min(rows, a.shape[0])
+    out[:k] = a[:k]
+    return out
+
+
+def tangent_scalars(phi_hist, d1, d2, u, h, phi_Q, phi_T, x, y, t_hist, b1, b2, b3):
+    """The six scalars of the second-order call plus slope and curvature, with the cost's nested trapezoid rule."""
+    rows = phi_hist.shape[0]
+    u, h = pad_rows(u, rows), pad_rows(h, rows)
+    sp_int = lambda f: o._trapz(o._trapz(f, y, -1), x, -1)
+    tt = lambda f: o._trapz(sp_int(f), t_hist)
+    e, eT = phi_hist - phi_Q, phi_hist[-1] - phi_T
+    r = dict(s_state=b1 * tt(e * d1) + b2 * sp_int(eT * d1[-1]),
+             s_ctrl=b3 * tt(u * h),
+             c_gn=b1 * tt(d1 * d1) + b2 * sp_int(d1[-1] ** 2),
+             c_state=b1 * tt(e * d2) + b2 * sp_int(eT * d2[-1]),
+             c_ctrl=b3 * tt(h * h),
+             n_h=tt(h * h))
+    r = {k: float(v) for k, v in r.items()}
+    r["slope"] = r["s_state"] + r["s_ctrl"]
+    r["curvature"] = r["c_gn"] + r["c_state"] + r["c_ctrl"]
+    return r
