@@ -246,15 +246,21 @@ int vch2d_pgd_kkt(vch2d_ctx *ctx, int refresh, double tol, int64_t *counts_out /
 /* Exact first and second directional derivatives of the smooth part J1 + J2 + J3 of the cost along h, about the resident
  * control and state history (ABI version stays 3: detect this entry point by symbol).  No adjoint and no nonlinear march:
  * the derivative of one Crank-Nicolson / Newton time level with respect to its inputs is one linear solve with the Newton
- * matrix J(phi_{n+1}) of vch2d_jacobian_apply at the converged new level, its second derivative one more solve with the
- * same matrix.  With dphi_0 = dmu_0 = dw_0 = 0 and d2phi_0 = d2mu_0 = 0, per step n:
+ * matrix J(phi*) of vch2d_jacobian_apply at the converged new level, its second derivative one more solve with the
+ * same matrix.  phi* = phi_{n+1} + s_n is the Newton solution of step n before the march's interior mass fix
+ * subtracted the shift s_n (vch2d_mass_shifts).  With dphi_0 = dmu_0 = dw_0 = 0 and d2phi_0 = d2mu_0 = 0, per step n:
  *   dw'  = ((gamma/dt - 1/2) dw + 1/2 (h_{n+1} + h_n)) / (gamma/dt + 1/2)
- *   J [dphi'; dmu']   = [ tau dphi/dt + kappa/2 L dphi + 2 c2 dphi + 1/2 dmu + 1/2 (dw' + dw) ;  dphi/dt + 1/2 L dmu ]
- *   J [d2phi'; d2mu'] = [ tau d2phi/dt + kappa/2 L d2phi + 2 c2 d2phi + 1/2 d2mu - c1 rho(phi_{n+1}) (dphi')^2 ;
+ *   J [dphi*; dmu']   = [ tau dphi/dt + kappa/2 L dphi + 2 c2 dphi + 1/2 dmu + 1/2 (dw' + dw) ;  dphi/dt + 1/2 L dmu ]
+ *   J [d2phi*; d2mu'] = [ tau d2phi/dt + kappa/2 L d2phi + 2 c2 d2phi + 1/2 d2mu - c1 rho(phi*) (dphi*)^2 ;
  *                         d2phi/dt + 1/2 L d2mu ],      rho(p) = 4 p / (1 - p^2)^2
- * The end-of-step clip and the interior mass fix of the march are taken as the identity: the linearised scheme conserves the
- * weighted mass of dphi exactly, and the clip is inactive wherever |phi| < 1 - delta_sep; the call does NOT detect an active
- * clip.  The L1 term J4 has no curvature away from its kink and is left out.
+ *   dphi' = dphi* - sum(wts dphi*) / W_int,   d2phi' = d2phi* - sum(wts d2phi*) / W_int      (where s_n != 0)
+ * The mass fix is linearised: the linearised step conserves the mass of dphi only in the weights of the Laplacian (its
+ * Kronecker-order quirk), which are the fix's weights wts = hx hy outer(trapz_x, trapz_y) only for Nx == Ny.  The weighted
+ * mean leaves the interior nodes (|phi*| < 1 - delta_sep - 5e-3, W_int their weight); dmu' and dw' are carried as they are.
+ * The end-of-step clip is taken as the identity (inactive wherever |phi| < 1 - delta_sep); the call does NOT detect an active
+ * clip or nodes outside the interior band.  Behind a state history the caller uploaded (vch2d_backward, vch2d_cost,
+ * vch2d_free_energy) there is no march of this context and the shifts count as zero.  The L1 term J4 has no curvature away
+ * from its kink and is left out.
  *   h       [B][h_rows][Nx+1][Ny+1] direction, row rule of a control: rows (n, n+1) drive step n while n < h_rows-1, zeros
  *           afterwards (F2:545-548); in the integrals h counts as zero from row h_rows on
  *   out[b] = { s_state = b1 int int (phi - phi_Q) dphi + b2 int (phi_M - phi_T) dphi_M,   s_ctrl = b3 int int u h,
@@ -285,6 +291,12 @@ int vch2d_second_order(vch2d_ctx *ctx, const double *h, int h_rows, const double
                        double *out /* [B][6] */,
                        double *dphi_hist_out, double *d2phi_hist_out      /* [B][M+1][..] or NULL */,
                        vch_stats *stats);
+/* What the interior mass fix subtracted at the end of every step of the march behind the resident state history (F2:567-577;
+ * 0 where the fix was not applied), read-only: out[b][n] = s_n of trajectory b.  The march records it beside the history it
+ * writes (a PGD line-search trial's record follows its history on acceptance); vch2d_second_order linearises the fix about
+ * it.  Returns M, the steps of that history.  ABI version stays 3: detect this entry point by symbol.  VCH_ERR_STATE without a resident state history that
+ * vch2d_forward or vch2d_pgd_init / _iterate of this context wrote. */
+int vch2d_mass_shifts(vch2d_ctx *ctx, double *out /* [B][M] */);
 /* Per-trajectory cost scalars {J1,J2,J3,J4,J} of the current iterate on the DEVICE
  * (5*B doubles), for the caller's RCCL all-reduce; returns a device pointer via *ptr_dev. */
 int vch2d_pgd_cost_dev(vch2d_ctx *ctx, double **ptr_dev);

@@ -348,7 +348,10 @@ def forward(P: Params2D, control=None, phi0=None, seed=42, amp=0.1, max_steps=No
     `phi0`/`seed`/`amp` generalise the hard-coded init_phi_random(amp=0.1, seed=42)
     of F2:517 (the reference's tests monkey-patch it instead).  `control` rows are
     used as (u[step], u[step+1]) while step < len(u)-1, else zeros (F2:545-548).
-    mu and w are carried un-recomputed after the clip/mass fix (F2:579)."""
+    mu and w are carried un-recomputed after the clip/mass fix (F2:579).
+
+    `stats` (optional dict) also collects, per step, "mass_shifts" (the value the mass fix subtracted, 0.0 where it was not
+    applied) and "mass_shift_interior" (True where it was subtracted on the interior nodes only, F2:567-574)."""
     Nx, Ny = int(P.Nx), int(P.Ny)
     hx, hy = P.Lx / Nx, P.Ly / Ny
     x = np.linspace(0.0, P.Lx, Nx + 1)
@@ -380,14 +383,20 @@ def forward(P: Params2D, control=None, phi0=None, seed=42, amp=0.1, max_steps=No
             stats.setdefault("step_counts", []).append(tuple(stats.get(k, 0) - before[k] for k in _COUNTS))
         phi = np.clip(phi_new, lo, hi)
         err = np.sum(wts_h * phi) - mass0
+        shift, shift_interior = 0.0, False
         if abs(err) > 1e-16:                                   # F2:567-577
             interior = np.abs(phi) < (1.0 - DELTA_SEP - 5e-3)
             Wint = float(np.sum(wts_h[interior]))
             if Wint > 0.0:
+                shift, shift_interior = err / Wint, True
                 phi[interior] -= err / Wint
             else:
+                shift = err / (P.Lx * P.Ly)
                 phi -= err / (P.Lx * P.Ly)
                 phi = np.clip(phi, lo, hi)
+        if stats is not None:
+            stats.setdefault("mass_shifts", []).append(float(shift))
+            stats.setdefault("mass_shift_interior", []).append(shift_interior)
         mu, w = mu_new, w_new
         t += dts
         step += 1

@@ -143,6 +143,12 @@ struct vch2d_ctx {
     bool post_fold;                       // VCH_POST_FOLD (default 1): the end of a step is applied by the next step's k_eval<0>
     bool post_pending;                    // a step's clip / mass fix / history store waits for the next k_eval<0>
     double *post_hist;                    // ... its history level (or NULL)
+    double *post_rec;                     // ... and its cell of the shift record (or NULL)
+    // what the mass fix subtracted at the end of every step of a march, beside the history the march wrote:
+    // [B][Mmax][SHIFT_REC] = {shift, 1.0 where it went to the interior nodes only}; shift_hist belongs to phi_hist,
+    // shift_trial to phi_trial (a line-search trial's record moves with its history, copy_traj_shifts)
+    double *shift_hist, *shift_trial;
+    bool shift_res = false;               // shift_hist is the record of the resident state history
     TrajState *st, *st_host;
     // look at the device state without a copy command and a stream wait: a one-workgroup kernel writes the records into
     // mapped host memory (st_pub) and then a sequence number (seq_pub) the host spins on (sync_state)
@@ -444,6 +450,7 @@ extern "C" vch2d_ctx *vch2d_create(const vch2d_params *p, int batch, int max_ste
     if (const char *e = getenv("VCH_POST_FOLD")) c->post_fold = atoi(e) != 0;
     c->post_pending = false;
     c->post_hist = nullptr;
+    c->post_rec = nullptr;
     c->fin_counter = nullptr;
     auto env_on = [](const char *name) { const char *e = getenv(name); return !(e && atoi(e) == 0); };
     c->mass_early = env_on("VCH_MASS_EARLY");
@@ -488,6 +495,9 @@ extern "C" vch2d_ctx *vch2d_create(const vch2d_params *p, int batch, int max_ste
     c->gpart2 = c->gpart + (size_t)batch * (c->gnblk + G.ns);
     if (dalloc(&c->gpart3, 4 * (size_t)batch * (c->gnblk + G.ns), c->stream)) return fail("hipMalloc");
     if (dalloc(&c->hist_dev, (size_t)batch * HIST_CAP, c->stream)) return fail("hipMalloc");
+    if (dalloc(&c->shift_hist, (size_t)batch * max_steps * SHIFT_REC, c->stream) ||
+        dalloc(&c->shift_trial, (size_t)batch * max_steps * SHIFT_REC, c->stream))
+        return fail("hipMalloc");
     if (dalloc(&c->alpha_dev, batch, c->stream) || dalloc(&c->J_dev, 5 * (size_t)batch, c->stream)) return fail("hipMalloc");
     if (dalloc(&c->opt_tab, (size_t)OPT_STRIDE * batch, c->stream) || dalloc(&c->seam_tab, (size_t)OPT_STRIDE * batch, c->stream))
         return fail("hipMalloc");
@@ -622,7 +632,7 @@ extern "C" void vch2d_destroy(vch2d_ctx *c) {
     hipStreamSynchronize(c->stream);
     double *all[] = {c->phi_s, c->mu_s, c->Rphi_s, c->rhs_s, c->D_s, c->w, c->wnew, c->mu0, c->cphi, c->cmu, c->x,
                      c->r, c->dmu, c->t1, c->t2, c->cg_p[0], c->cg_p[1], c->cg_v, c->cg_q, c->cg_z2, c->xf, c->dprev[0], c->dprev[1], c->dprev[2], c->dprev[3], c->dprev[4], c->dprev[5], c->dprev[6], c->dprev[7], c->dprev2[0], c->dprev2[1], c->dprev2[2], c->dprev2[3], c->dprev2[4], c->dprev2[5], c->dprev2[6], c->dprev2[7], c->x0g, c->gpart, c->gpart3, c->tmp[0], c->tmp[1], c->tmp[2], c->tmp[3], c->tmp[4], c->tmp[5],
-                     c->phiT, c->phi0, c->wts_mass, c->W_cost, c->part, c->part_mass, c->hist_dev, c->alpha_dev, c->opt_tab, c->seam_tab, c->J_dev, c->Q1f,
+                     c->phiT, c->phi0, c->wts_mass, c->W_cost, c->part, c->part_mass, c->hist_dev, c->shift_hist, c->shift_trial, c->alpha_dev, c->opt_tab, c->seam_tab, c->J_dev, c->Q1f,
                      c->Q2f, c->Q1s, c->Q2s, c->mf, c->ms, c->phi_hist, c->u_hist, c->u_trial, c->phi_trial, c->phiQ,
                      c->r_hist, c->p_hist, c->q_hist, c->cost_part, c->cost_lvl, c->tfrac_dev, c->tan_part, c->tan_lvl, c->tan_t,
                      c->tan_out};
@@ -1008,7 +1018,8 @@ static int newton_level(vch2d_ctx *c, double dt, const double *un, const double 
         GuessArgs g1_ = c->gtab1;
         if (!guess) memset(g1_.c, 0, sizeof(g1_.c));
         // the previous step's clip / mass fix / history store, if forward_core left it to this kernel
-        const PostArgs post_{c->post_pending ? (const double *)c->part_mass : (const double *)nullptr, c->post_hist, hist_stride(c)};
+        const PostArgs post_{c->post_pending ? (const double *)c->part_mass : (const double *)nullptr, c->post_hist, hist_stride(c), c->post_rec,
+                             (long)c->Mmax * SHIFT_REC};
         c->post_pending = false;
         auto k_start = fin_inside ? k_eval<0, true> : k_eval<0, false>;
         LAUNCHC(PC_RESIDUAL0, k_start, c->grid, dim3(NTH), c->G, c->P, c->st, c->slot_stride, c->phi_s, c->mu_s, c->Rphi_s, c->rhs_s,
@@ -1267,7 +1278,7 @@ extern "C" int vch2d_jacobian_solve(vch2d_ctx *c, const double *phi_new, double 
     HIPCHK(hipMemcpyAsync(c->phi_s, c->tmp[0], sizeof(double) * c->B * c->G.plane, hipMemcpyDeviceToDevice, c->stream));
     LAUNCH(k_solve_setup, c->grid, dim3(NTH), c->G, c->P, c->tmp[1], c->tmp[2], c->tmp[0], dt, c->Rphi_s, c->rhs_s, c->D_s,
            c->part);
-    LAUNCH(k_fin_lin_begin, dim3(c->B), dim3(64), c->st, c->part, c->nblk, 2, c->P.tau, c->P.kappa, dt, c->lin_tol);
+    LAUNCH(k_fin_lin_begin, dim3(c->B), dim3(64), c->st, c->part, c->nblk, 2, c->P.tau, c->P.kappa, dt, c->lin_tol, 0.0);
     VCHCHK(sync_state(c));
     VCHCHK(schur_solve(c, dt, cg_budget(c, false), true));
     // back substitution needs newton_active && !need_trial
@@ -1379,7 +1390,7 @@ extern "C" int vch2d_adjoint_solve(vch2d_ctx *c, const double *phi_n, double dt,
     VCHCHK(h2d(c, c->cphi, rhs, c->B));
     LAUNCH(k_adj_setup, c->grid, dim3(NTH), c->G, c->P, (dt > 0 ? c->tmp[0] : (const double *)nullptr), c->cphi, c->cmu,
            c->part);
-    LAUNCH(k_fin_lin_begin, dim3(c->B), dim3(64), c->st, c->part, c->nblk, 0, c->P.tau, c->P.kappa, dt, c->lin_tol);
+    LAUNCH(k_fin_lin_begin, dim3(c->B), dim3(64), c->st, c->part, c->nblk, 0, c->P.tau, c->P.kappa, dt, c->lin_tol, 0.0);
     LAUNCH(k_fill, c->grid, dim3(NTH), c->G, c->x, 0.0);
     VCHCHK(sync_state(c));
     VCHCHK(adjoint_solve_cg(c, dt, cg_budget(c, false), true));
@@ -1439,6 +1450,10 @@ static int forward_core(vch2d_ctx *c, const double *u_dev, int u_rows, const dou
     LAUNCH(k_mass, c->grid, dim3(NTH), c->G, c->st, c->slot_stride, c->phi_s, c->wts_mass, 0, c->part, 0);
     LAUNCH(k_fin_mass, dim3(c->B), dim3(64), c->st, c->part, c->nblk, 1);
     c->post_pending = false;
+    // the shift record goes beside the history the march writes
+    double *const rec_out = hist_out && hist_out == c->phi_hist ? c->shift_hist
+                          : hist_out && hist_out == c->phi_trial ? c->shift_trial : (double *)nullptr;
+    const long rec_stride = (long)c->Mmax * SHIFT_REC;
     // marches whose steps start with k_eval<0> (newton_level: the fused path) leave the end of every step but the last to it
     const bool fold_post = c->post_fold && c->fused_on && c->use_fft && !c->half_f && !c->half_s;
     if (hist_out) LAUNCH(k_copy_plane, c->grid, dim3(NTH), c->G, c->phi_s, c->G.plane, hist_out, hs);
@@ -1517,11 +1532,14 @@ static int forward_core(vch2d_ctx *c, const double *u_dev, int u_rows, const dou
         if (!c->mass_done) LAUNCH(k_mass, c->grid, dim3(NTH), c->G, c->st, c->slot_stride, c->phi_s, c->wts_mass, 1, c->part_mass, 0);
         c->mass_done = false;
         double *const lvl = hist_out ? hist_out + (long)(step + 1) * c->G.plane : (double *)nullptr;
+        double *const rec = rec_out ? rec_out + (long)step * SHIFT_REC : (double *)nullptr;
         if (fold_post && step + 1 < M) {
             c->post_pending = true;
             c->post_hist = lvl;
+            c->post_rec = rec;
         } else {
-            LAUNCH(k_post, c->grid, dim3(NTH), c->G, c->P, c->st, c->slot_stride, c->phi_s, lvl, hs, (const double *)c->part_mass);
+            LAUNCH(k_post, c->grid, dim3(NTH), c->G, c->P, c->st, c->slot_stride, c->phi_s, lvl, hs, (const double *)c->part_mass,
+                   rec, rec_stride);
         }
         std::swap(c->w, c->wnew);
         if (c->guess_on) {
@@ -1599,6 +1617,7 @@ extern "C" int vch2d_forward(vch2d_ctx *c, const double *phi0, const double *u, 
     VCHCHK(sync_state(c));
     c->M_res = M;
     c->res_pgd = false;
+    c->shift_res = true;
     c->fwd_u_rows = u_dev ? u_rows : 0;
     if (phi_hist_out) VCHCHK(d2h_hist(c, phi_hist_out, c->phi_hist, M + 1));
     float ms = 0;
@@ -1640,7 +1659,7 @@ static int backward_pass(vch2d_ctx *c, const double *phi_hist_dev, int M, const 
     LAUNCH(k_scaled_diff, c->grid, dim3(NTH), G, phi_hist_dev + (long)M * G.plane, hs, phiT_dev, G.plane, opt_tab + OPT_B2, OPT_STRIDE, rhs,
            c->part);
     LAUNCH(k_adj_setup, c->grid, dim3(NTH), G, c->P, (const double *)nullptr, (const double *)rhs, Dn, c->part);
-    LAUNCH(k_fin_lin_begin, dim3(c->B), dim3(64), c->st, c->part, c->nblk, 0, c->P.tau, c->P.kappa, 0.0, c->lin_tol);
+    LAUNCH(k_fin_lin_begin, dim3(c->B), dim3(64), c->st, c->part, c->nblk, 0, c->P.tau, c->P.kappa, 0.0, c->lin_tol, 0.0);
     LAUNCH(k_fill, c->grid, dim3(NTH), G, c->x, 0.0);
     VCHCHK(adjoint_solve_cg(c, 0.0, 3, false));
     int sweeps = -1, steps_since_look = 0;
@@ -1671,7 +1690,7 @@ static int backward_pass(vch2d_ctx *c, const double *phi_hist_dev, int M, const 
         LAUNCHC(PC_ADJ_RHS, k_adj_rhs, c->grid, dim3(NTH), G, c->P, c->x, qa, phi_hist_dev + (long)n * G.plane,
                phi_hist_dev + (long)(n + 1) * G.plane, phiQ_dev ? phiQ_dev + (long)n * G.plane : (const double *)nullptr,
                phiQ_dev ? phiQ_dev + (long)(n + 1) * G.plane : (const double *)nullptr, hs, dtn, opt_tab, rhs, Dn, c->part);
-        LAUNCH(k_fin_lin_begin, dim3(c->B), dim3(64), c->st, c->part, c->nblk, 0, c->P.tau, c->P.kappa, dtn, c->lin_tol);
+        LAUNCH(k_fin_lin_begin, dim3(c->B), dim3(64), c->st, c->part, c->nblk, 0, c->P.tau, c->P.kappa, dtn, c->lin_tol, 0.0);
         // looks at levels fixed in advance (every level for the first ADJ_SETTLE ones, where the orders of the guesses are
         // being raised, then every ADJ_LOOK-th): when a trajectory's order changes depends on its own ratios only
         if (safe || steps_since_look >= ((guess && M - 1 - n < ADJ_SETTLE) ? 1 : ADJ_LOOK) || sweeps < 0) {
@@ -1818,6 +1837,7 @@ extern "C" int vch2d_backward(vch2d_ctx *c, const double *phi_hist, int M, const
         VCHCHK(h2d_hist(c, c->phi_hist, phi_hist, M + 1));
         c->M_res = M;
         c->res_pgd = false;
+        c->shift_res = false;         // a history of the caller's: no march of this context stands behind it
     } else {
         if (c->M_res != M) return vch_fail(VCH_ERR_STATE, "vch2d_backward: no resident history with %d steps", M);
     }
@@ -1968,6 +1988,7 @@ extern "C" int vch2d_cost(vch2d_ctx *c, const double *phi_hist, const double *u,
         VCHCHK(h2d_hist(c, c->phi_hist, phi_hist, M + 1));
         c->M_res = M;
         c->res_pgd = false;
+        c->shift_res = false;         // a history of the caller's: no march of this context stands behind it
     } else if (c->M_res != M) {
         return vch_fail(VCH_ERR_STATE, "vch2d_cost: no resident history with %d steps", M);
     }
@@ -2009,6 +2030,7 @@ extern "C" int vch2d_free_energy(vch2d_ctx *c, const double *phi_hist, int rows,
         VCHCHK(h2d_hist(c, c->phi_hist, phi_hist, rows));
         c->M_res = rows - 1;
         c->res_pgd = false;
+        c->shift_res = false;
         pd = c->phi_hist;
     }
     if (w_hist) {                      // the coupling field travels through the trial-state buffer
@@ -2088,6 +2110,12 @@ extern "C" int vch2d_grad_prox(vch2d_ctx *c, const double *u, const double *r, i
 // ------------------------------------------------------------------------------------
 // device-resident PGD loop (G2:291-382)
 // ------------------------------------------------------------------------------------
+// the shift record of an accepted trial follows its history (copy_traj(phi_hist, phi_trial))
+static int copy_traj_shifts(vch2d_ctx *c, int b) {
+    const size_t n = (size_t)c->Mmax * SHIFT_REC;
+    HIPCHK(hipMemcpyAsync(c->shift_hist + b * n, c->shift_trial + b * n, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
+    return 0;
+}
 static int copy_traj(vch2d_ctx *c, double *dst, const double *src, int b, int rows) {
     const long hs = hist_stride(c);
     HIPCHK(hipMemcpyAsync(dst + b * hs, src + b * hs, sizeof(double) * rows * c->G.plane, hipMemcpyDeviceToDevice, c->stream));
@@ -2160,6 +2188,7 @@ extern "C" int vch2d_pgd_init_v(vch2d_ctx *c, const double *phi0, const double *
     else VCHCHK(forward_core(c, nullptr, 0, c->dt.data(), M, c->phi_hist));
     c->M_res = M;
     c->res_pgd = false;
+    c->shift_res = true;
     c->pgd_J.assign(5 * c->B, 0.0);
     VCHCHK(cost_core(c, c->phi_hist, c->u_hist, (phi_Q || ramp) ? c->phiQ : nullptr, c->phiT, false, M, c->t_hist.data(),
                      c->opts.data(), c->pgd_J.data(), nullptr, c->B));
@@ -2293,6 +2322,7 @@ extern "C" int vch2d_pgd_iterate(vch2d_ctx *c, int n_iters, double *cost_out, do
                     const double change = std::sqrt(chg[2 * b]) / (std::sqrt(chg[2 * b + 1]) + 1e-9);
                     VCHCHK(copy_traj(c, c->u_hist, c->u_trial, b, rows));
                     VCHCHK(copy_traj(c, c->phi_hist, c->phi_trial, b, rows));
+                    VCHCHK(copy_traj_shifts(c, b));
                     c->pgd_cost_hist[b].push_back(cost_new[b]);
                     auto &ch = c->pgd_cost_hist[b];
                     const int k = c->pgd_k[b];
@@ -2393,13 +2423,21 @@ extern "C" int vch2d_pgd_kkt(vch2d_ctx *c, int refresh, double tol, int64_t *cou
 // vch_kernels2d.h)
 // ------------------------------------------------------------------------------------
 // One tangent solve: the right-hand side is in slot 0 (k_tan_rhs); x = 0 start, the context's lin_tol, every trajectory
-// gated by its own lin_active; on return dphi' is in c->xf and dmu' in c->dmu.
-static int tangent_solve(vch2d_ctx *c, double dt) {
-    LAUNCH(k_fin_lin_begin, dim3(c->B), dim3(64), c->st, c->part, c->nblk, 2, c->P.tau, c->P.kappa, dt, c->lin_tol);
+// gated by its own lin_active; on return dphi* is in c->xf and dmu' in c->dmu.  With a shift record (rec: the step's cell)
+// the partials of the fix's weighted mean of dphi* follow in c->part_mass, for the kernel that reads c->xf next.
+static int tangent_solve(vch2d_ctx *c, double dt, const double *phi1, const double *rec) {
+    // a wide diagonal takes the right-scaled CG form by the march's rule (newton_level: the stencil-free path only)
+    const bool spectral = c->use_fft && !c->half_f && !c->half_s;
+    LAUNCH(k_fin_lin_begin, dim3(c->B), dim3(64), c->st, c->part, c->nblk, 2, c->P.tau, c->P.kappa, dt, c->lin_tol,
+           spectral ? c->cg_scale_ratio : 0.0);
     LAUNCH(k_tan_arm, dim3((c->B + 63) / 64), dim3(64), c->st, c->B);
     VCHCHK(sync_state(c, false));
     VCHCHK(schur_solve(c, dt, cg_budget(c, false), true));
-    return dmu_ceiling(c, 0);
+    VCHCHK(dmu_ceiling(c, 0));
+    if (rec)
+        LAUNCH(k_tan_mass, c->grid, dim3(NTH), c->G, (const double *)c->xf, phi1, hist_stride(c), rec, (long)c->Mmax * SHIFT_REC,
+               (const double *)c->wts_mass, c->part_mass);
+    return 0;
 }
 
 // one level of a [B][plane] work plane -> host history [B][M+1][ns][nf] (asynchronous; the caller synchronises)
@@ -2434,12 +2472,17 @@ static int second_order_core(vch2d_ctx *c, const double *h, int h_rows, const do
     c->cheb_enq = -1;
     const int u_rows = c->res_pgd ? levels : std::min(c->fwd_u_rows, levels);
     const long part_stride = (long)levels * c->nblk * TAN_NSUM;
+    const long rec_stride = (long)c->Mmax * SHIFT_REC;
+    // the cell of step n in the shift record of the resident history (none behind a history the caller uploaded)
+    auto rec_of = [&](int n) { return c->shift_res ? (const double *)c->shift_hist + (long)n * SHIFT_REC : (const double *)nullptr; };
     auto level = [&](int lvl, const double *d1, const double *d2, double *dst_phi, double *dst_mu) -> int {
         TanLevelArgs a{c->phi_hist + (long)lvl * G.plane,
                        pq ? pq + (long)lvl * G.plane : (const double *)nullptr,
                        lvl < u_rows ? c->u_hist + (long)lvl * G.plane : (const double *)nullptr,
                        lvl < h_rows ? c->u_trial + (long)lvl * G.plane : (const double *)nullptr,
-                       hs, pt, lvl == M ? 1 : 0, d1, d2, c->xf, c->dmu, dst_phi, dst_mu, c->W_cost};
+                       hs, pt, lvl == M ? 1 : 0, d1, d2, c->xf, c->dmu, dst_phi, dst_mu, c->W_cost,
+                       lvl == 0 ? 0 : (d2 ? 2 : 1), lvl == 0 ? (const double *)nullptr : rec_of(lvl - 1), rec_stride,
+                       (const double *)c->part_mass, c->P.LxLy};
         LAUNCH(k_tan_level, c->grid, dim3(NTH), G, a, c->tan_part + (long)lvl * c->nblk * TAN_NSUM, part_stride);
         return 0;
     };
@@ -2451,19 +2494,22 @@ static int second_order_core(vch2d_ctx *c, const double *h, int h_rows, const do
         const bool live = n < h_rows - 1;           // F2:545-548
         TanRhsArgs a1{dphi, dmu, dw[n & 1], dw[(n + 1) & 1], live ? c->u_trial + (long)n * G.plane : (const double *)nullptr,
                       live ? c->u_trial + (long)(n + 1) * G.plane : (const double *)nullptr, phi1, hs, nullptr, nullptr, nullptr,
-                      nullptr};
+                      nullptr, rec_of(n), rec_stride, nullptr};
         LAUNCH((k_tan_rhs<0>), c->grid, dim3(NTH), G, c->P, a1, dt[n], c->Rphi_s, c->rhs_s, c->D_s, c->part);
-        VCHCHK(tangent_solve(c, dt[n]));
+        VCHCHK(tangent_solve(c, dt[n], phi1, rec_of(n)));
+        // the level's kernel takes the fix's mean out of the last solve's output on its way to the plane the next step reads
+        // (k_tan_rhs<1> does that for dphi'), so the host copies come from those planes
         if (order == 2) {
-            TanRhsArgs a2{d2phi, d2mu, nullptr, nullptr, nullptr, nullptr, phi1, hs, c->xf, c->dmu, dphi, dmu};
+            TanRhsArgs a2{d2phi, d2mu, nullptr, nullptr, nullptr, nullptr, phi1, hs, c->xf, c->dmu, dphi, dmu, rec_of(n), rec_stride,
+                          (const double *)c->part_mass};
             LAUNCH((k_tan_rhs<1>), c->grid, dim3(NTH), G, c->P, a2, dt[n], c->Rphi_s, c->rhs_s, c->D_s, c->part);
-            VCHCHK(tangent_solve(c, dt[n]));
-            if (dphi_hist_out) VCHCHK(tangent_level_out(c, dphi_hist_out, dphi, M, n + 1));
-            if (d2phi_hist_out) VCHCHK(tangent_level_out(c, d2phi_hist_out, c->xf, M, n + 1));
+            VCHCHK(tangent_solve(c, dt[n], phi1, rec_of(n)));
             VCHCHK(level(n + 1, dphi, c->xf, d2phi, d2mu));
+            if (dphi_hist_out) VCHCHK(tangent_level_out(c, dphi_hist_out, dphi, M, n + 1));
+            if (d2phi_hist_out) VCHCHK(tangent_level_out(c, d2phi_hist_out, d2phi, M, n + 1));
         } else {
-            if (dphi_hist_out) VCHCHK(tangent_level_out(c, dphi_hist_out, c->xf, M, n + 1));
             VCHCHK(level(n + 1, c->xf, nullptr, dphi, dmu));
+            if (dphi_hist_out) VCHCHK(tangent_level_out(c, dphi_hist_out, dphi, M, n + 1));
         }
     }
     LAUNCH(k_tan_fin, dim3(B * levels), dim3(64), c->nblk, (const double *)c->tan_part, c->tan_lvl);
@@ -2530,6 +2576,20 @@ extern "C" int vch2d_second_order(vch2d_ctx *c, const double *h, int h_rows, con
                                      stats);
     c->lin_tol = keep_tol;
     return rc;
+}
+
+extern "C" int vch2d_mass_shifts(vch2d_ctx *c, double *out) {
+    CTXCHK(c);
+    ARGCHK(out, "NULL out");
+    if (c->M_res < 1 || !c->phi_hist || !c->shift_res)
+        return vch_fail(VCH_ERR_STATE, "vch2d_mass_shifts: no resident state history that a march of this context wrote");
+    const int B = c->B, M = c->M_res;
+    std::vector<double> rec((size_t)B * c->Mmax * SHIFT_REC);
+    HIPCHK(hipMemcpyAsync(rec.data(), c->shift_hist, sizeof(double) * rec.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int b = 0; b < B; ++b)
+        for (int n = 0; n < M; ++n) out[(size_t)b * M + n] = rec[((size_t)b * c->Mmax + n) * SHIFT_REC];
+    return M;
 }
 
 extern "C" int vch2d_pgd_cost_dev(vch2d_ctx *c, double **ptr_dev) {

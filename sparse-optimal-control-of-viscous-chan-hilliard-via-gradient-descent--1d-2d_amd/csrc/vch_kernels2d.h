@@ -791,16 +791,26 @@ struct PostFix {
         }
         return ph;
     }
+    // the step's cell of the shift record (vch2d_second_order linearises the fix about it): what was subtracted, and whether
+    // on the interior nodes only; written by one lane of one workgroup per trajectory
+    __device__ __forceinline__ void record(double *rec) const {
+        rec[0] = shift;
+        rec[1] = (fix && !interior_ok) ? 0.0 : 1.0;
+    }
 };
+constexpr int SHIFT_REC = 2;
 struct PostArgs {
     const double *part;        // k_mass partials of the step that has just ended (own buffer), or NULL: nothing pending
     double *hist;              // history level of that step, or NULL
     long hist_stride;
+    double *rec;               // that step's cell of the shift record ([B] cells rec_stride apart), or NULL
+    long rec_stride;
 };
 
 __global__ __launch_bounds__(NTH) void k_post(Geom G, Phys P, const TrajState *__restrict__ st, long slot_stride,
                                               double *__restrict__ phi_s, double *__restrict__ hist_level,
-                                              long hist_stride, const double *__restrict__ part) {
+                                              long hist_stride, const double *__restrict__ part, double *__restrict__ rec,
+                                              long rec_stride) {
     TILE_COORDS;
     const TrajState S = st[b];
     if (S.frozen) return;
@@ -808,6 +818,7 @@ __global__ __launch_bounds__(NTH) void k_post(Geom G, Phys P, const TrajState *_
     post_sums(part, nblk, b, sm);
     __syncthreads();
     const PostFix pf(sm, S.mass0, P.LxLy);
+    if (rec && blk == 0 && threadIdx.x == 0) pf.record(rec + b * rec_stride);
     for (int k = 0; k < TY / 4; ++k) {
         int r = r0 + ly0 + 4 * k, c = c0 + lx;
         if (r < G.ns && c < G.nf) {
@@ -1686,6 +1697,7 @@ __global__ __launch_bounds__(NTH, EVAL_MINBLK) void k_eval(Geom G, Phys P, TrajS
             post_sums(post.part, nblk, (int)b, s_post);
             __syncthreads();
             const PostFix pf(s_post, st[b].mass0, P.LxLy);
+            if (post.rec && blk == 0 && threadIdx.x == 0) pf.record(post.rec + b * post.rec_stride);
 #pragma unroll
             for (int i = 0; i < I2; ++i) {
                 const int e = threadIdx.x + i * NTH;
@@ -2192,8 +2204,9 @@ __global__ void k_fin_mass(TrajState *st, const double *__restrict__ part, int n
 //   mode 0: partial slots {min D, max D, sum rhs^2}, adjoint operator A(phi_n)  (B2:198)
 //   mode 1: partial slot  {sum rhs^2}, constant-coefficient operator (D = 0)     (B2:184)
 //   mode 2: partial slots {sum(.), sum rhs^2, min D, max D}, forward Schur operator
+//           scale_ratio > 0: Dmax > scale_ratio * Dmin takes the right-scaled CG form (cg_weight), as in the march
 __global__ void k_fin_lin_begin(TrajState *st, const double *__restrict__ part, int nblk, int mode,
-                                double tau, double kappa, double dt, double lin_tol) {
+                                double tau, double kappa, double dt, double lin_tol, double scale_ratio) {
     const int b = blockIdx.x;
     TrajState &S = st[b];
     if (threadIdx.x == 0 && S.lin_active) {      // the previous solve of this trajectory ended on its sweep budget
@@ -2223,7 +2236,8 @@ __global__ void k_fin_lin_begin(TrajState *st, const double *__restrict__ part, 
     S.lin_rel = 1.0;
     S.lin_reltol = lin_tol;
     S.use_cheb = 0;
-    S.scaled = 0;
+    // mode 2, on request: the rule of the march's CG-form solves (fin_residual_update)
+    S.scaled = (mode == 2 && scale_ratio > 0.0 && dmax > scale_ratio * dmin) ? 1 : 0;
     S.nsolves++;
 }
 
@@ -2575,18 +2589,63 @@ __global__ __launch_bounds__(NTH) void k_cg_update_adj(Geom G, const TrajState *
 //
 // With delta-phi_0 = delta-mu_0 = delta-w_0 = 0 and the second-order fields delta2-phi_0 = delta2-mu_0 = 0, step n is
 //   dw'  = ((gamma/dt - 1/2) dw + 1/2 (h_{n+1} + h_n)) / (gamma/dt + 1/2)                              (the solve_w rule)
-//   J(phi_{n+1}) [dphi'; dmu']   = [ tau dphi/dt + kappa/2 L dphi + 2 c2 dphi + 1/2 dmu + 1/2 (dw' + dw) ;  dphi/dt + 1/2 L dmu ]
-//   J(phi_{n+1}) [d2phi'; d2mu'] = [ tau d2phi/dt + kappa/2 L d2phi + 2 c2 d2phi + 1/2 d2mu - c1 rho(phi_{n+1}) (dphi')^2 ;
-//                                    d2phi/dt + 1/2 L d2mu ],        rho(p) = 4 p / (1 - p^2)^2 = reglog''(p)
-// J = the Newton matrix of k_jac_apply at the converged level n+1 of the history: one linear solve per field and step, by the
-// Schur reduction + preconditioned CG of the Newton solves (k_fin_lin_begin -> schur_solve -> dmu_ceiling).
-// The end-of-step clip and the interior mass fix of the march are taken as the identity: the linearised scheme conserves
-// the weighted mass of dphi exactly, and the clip is inactive wherever |phi| < 1 - delta_sep.  An active clip is NOT detected.
+//   J(phi*) [dphi*; dmu']   = [ tau dphi/dt + kappa/2 L dphi + 2 c2 dphi + 1/2 dmu + 1/2 (dw' + dw) ;  dphi/dt + 1/2 L dmu ]
+//   J(phi*) [d2phi*; d2mu'] = [ tau d2phi/dt + kappa/2 L d2phi + 2 c2 d2phi + 1/2 d2mu - c1 rho(phi*) (dphi*)^2 ;
+//                               d2phi/dt + 1/2 L d2mu ],             rho(p) = 4 p / (1 - p^2)^2 = reglog''(p)
+//   dphi' = dphi* - sum(wts dphi*) / W_int,   d2phi' = d2phi* - sum(wts d2phi*) / W_int
+// phi* = phi_{n+1} + s_n is the Newton solution of the step before the march's mass fix subtracted s_n (the shift record the
+// march keeps beside its history, PostFix::record), J = the Newton matrix of k_jac_apply there: one linear solve per field
+// and step, by the Schur reduction + preconditioned CG of the Newton solves (k_fin_lin_begin -> schur_solve -> dmu_ceiling).
+// The mass fix is linearised, not taken as the identity: the linearised step conserves the mass of dphi in the weights of
+// the Laplacian (its Kronecker-order quirk), which are the fix's weights wts = hx hy outer(trapz_x, trapz_y) only for
+// Nx == Ny.  The weighted mean leaves the interior nodes (|phi*| < 1 - delta_sep - 5e-3, W_int their weight), as the shift
+// did; where the march did not apply the fix (s_n == 0) nothing is subtracted; dmu' and dw' are carried as they are.  The clip
+// is inactive wherever |phi| < 1 - delta_sep.  An active clip, or nodes outside the interior band, are NOT detected.
 // ---------------------------------------------------------------------------------
 __device__ __forceinline__ double tan_rho(double phi) {      // reglog''(p), p clipped to the band of jac_diag
     const double lim = sqrt(1.0 - DELTA_SEP * DELTA_SEP);
     const double p = fmin(fmax(phi, -lim), lim), q = 1.0 - p * p;
     return 4.0 * p / (q * q);
+}
+
+// The linearised mass fix of one solve's output x: sums = {sum wts x, W_int} (k_tan_mass's partials through post_sums, read
+// only where the step has a shift), rec = the step's cell of the shift record.
+struct TanFix {
+    double mean, thr;
+    bool all;
+    __device__ __forceinline__ TanFix(const double *sums, const double *rec, double LxLy) {
+        thr = (1.0 - DELTA_SEP) - 5e-3;
+        all = rec && rec[1] == 0.0;              // the march fell back to the all-node form (no interior node)
+        mean = (rec && rec[0] != 0.0) ? sums[0] / (all ? LxLy : sums[1]) : 0.0;
+    }
+    __device__ __forceinline__ double apply(double v, double phi_star) const {
+        return (all || fabs(phi_star) < thr) ? v - mean : v;
+    }
+};
+
+// Workgroup partials {sum wts x, sum of wts over the interior nodes of phi* = phi1 + s} of a solve's output x, in the slots
+// post_sums reads; a trajectory whose step has no shift is left out (its consumers do not read the sums).
+__global__ __launch_bounds__(NTH) void k_tan_mass(Geom G, const double *__restrict__ x, const double *__restrict__ phi1,
+                                                  long hist_stride, const double *__restrict__ rec, long rec_stride,
+                                                  const double *__restrict__ wts, double *__restrict__ part) {
+    TILE_COORDS;
+    __shared__ double sred[NPART * 4];
+    const double s = rec[b * rec_stride];
+    if (s == 0.0) return;
+    const double thr = (1.0 - DELTA_SEP) - 5e-3;
+    const long pb = b * G.plane, hb = b * hist_stride;
+    double acc[2] = {0.0, 0.0};
+    for (int k = 0; k < TY / 4; ++k) {
+        int r = r0 + ly0 + 4 * k, c = c0 + lx;
+        if (r < G.ns && c < G.nf) {
+            const long o = (long)r * G.pitch + c;
+            const double w = wts[o];
+            acc[0] += w * x[pb + o];
+            if (fabs(phi1[hb + o] + s) < thr) acc[1] += w;
+        }
+    }
+    const int op[2] = {0, 0};
+    block_reduce_store<2>(acc, op, sred, part + ((long)b * nblk + blk) * NPART);
 }
 
 struct TanRhsArgs {
@@ -2598,11 +2657,15 @@ struct TanRhsArgs {
     long hist_stride;               // trajectory stride of hn, hp, phi1
     const double *d1, *m1;          // SECOND: this step's finished dphi', dmu' (the solver's output planes) ...
     double *keep_phi, *keep_mu;     // ... and the planes that keep them while the second solve reuses the solver's
+    const double *rec;              // this step's cell of the shift record ([B] cells rec_stride apart), NULL = no shifts
+    long rec_stride;
+    const double *mpart;            // SECOND: k_tan_mass's partials of d1 (keep_phi gets d1 with the fix's mean taken out)
 };
 
 // Right-hand side of a tangent solve in the form k_solve_setup leaves: with [A; Bv] the right-hand side above,
 // R_phi := -A, rhs := Bv - L A (Schur), D from phi_{n+1}, partials {-, sum rhs^2, min D, max D} for k_fin_lin_begin (mode 2).
 // A is evaluated on the tile and its one-node halo (from dphi with a two-node halo), so that L A needs no second launch.
+// D and rho are taken at phi* = phi_{n+1} + s_n.
 template <int SECOND>
 __global__ __launch_bounds__(NTH) void k_tan_rhs(Geom G, Phys P, TanRhsArgs a, double dt, double *__restrict__ Rphi,
                                                  double *__restrict__ rhs, double *__restrict__ D, double *__restrict__ part) {
@@ -2611,11 +2674,16 @@ __global__ __launch_bounds__(NTH) void k_tan_rhs(Geom G, Phys P, TanRhsArgs a, d
     __shared__ double sm[(TY + 2) * (TX + 2)];
     __shared__ double sr[(TY + 2) * (TX + 2)];
     __shared__ double sred[NPART * 4];
+    __shared__ double s_fix[2];
     constexpr int W2 = TX + 4, W = TX + 2;
     const long pb = b * G.plane, hb = b * a.hist_stride;
+    const double *rec = a.rec ? a.rec + b * a.rec_stride : (const double *)nullptr;
+    const double shift = rec ? rec[0] : 0.0;
     load_tile<2>(sa, a.a + pb, G, c0, r0);
     load_tile<1>(sm, a.m + pb, G, c0, r0);
+    if (SECOND && shift != 0.0) post_sums(a.mpart, nblk, (int)b, s_fix);
     __syncthreads();
+    const TanFix tf(s_fix, SECOND ? rec : (const double *)nullptr, P.LxLy);
     const double gdt = P.gamma / dt;
     auto w_new = [&](long o, double w0) {
         const double h0 = a.hn ? a.hn[hb + o] : 0.0, h1 = a.hp ? a.hp[hb + o] : 0.0;
@@ -2630,7 +2698,7 @@ __global__ __launch_bounds__(NTH) void k_tan_rhs(Geom G, Phys P, TanRhsArgs a, d
         double v = P.tau * av / dt + 0.5 * P.kappa * lap_at<W2>(sa, p2, G.ax, G.ay) + 2.0 * P.c2 * av + 0.5 * sm[e];
         if (SECOND) {
             const double d = a.d1[pb + o];
-            v -= P.c1 * tan_rho(a.phi1[hb + o]) * (d * d);
+            v -= P.c1 * tan_rho(a.phi1[hb + o] + shift) * (d * d);
         } else {
             const double w0 = a.w_in[pb + o];
             v += 0.5 * (w_new(o, w0) + w0);
@@ -2646,12 +2714,13 @@ __global__ __launch_bounds__(NTH) void k_tan_rhs(Geom G, Phys P, TanRhsArgs a, d
             const long o = (long)r * G.pitch + c;
             const double rm = sa[(ly + 2) * W2 + lx + 2] / dt + 0.5 * lap_at<W>(sm, p, G.ax, G.ay);
             const double rh = rm - lap_at<W>(sr, p, G.ax, G.ay);
-            const double d = jac_diag(a.phi1[hb + o], P.tau / dt, P.c1);
+            const double ps = a.phi1[hb + o] + shift;
+            const double d = jac_diag(ps, P.tau / dt, P.c1);
             Rphi[pb + o] = -sr[p];
             rhs[pb + o] = rh;
             D[pb + o] = d;
             if (SECOND) {
-                a.keep_phi[pb + o] = a.d1[pb + o];
+                a.keep_phi[pb + o] = tf.apply(a.d1[pb + o], ps);
                 a.keep_mu[pb + o] = a.m1[pb + o];
             } else {
                 a.w_out[pb + o] = w_new(o, a.w_in[pb + o]);
@@ -2679,7 +2748,9 @@ __global__ void k_tan_arm(TrajState *st, int B) {
 
 // Integrands of one level, weighted with W_cost (nested trapezoid rule in y, x), per workgroup:
 //   {W e dphi, W dphi^2, W e d2phi, W u h, W h^2, W eT dphi, W eT d2phi, 0},  e = phi - phi_Q, eT = phi_M - phi_T (last level only)
-// and the hand-over of the level's fields from the solver's output planes to the planes the next step reads.
+// and the hand-over of the level's fields from the solver's output planes to the planes the next step reads.  fix = 1 / 2:
+// d1 / d2 is the raw output of this step's last solve (and src_phi): the linearised mass fix (TanFix, sums from mpart) is
+// applied to it before the integrands, and dst_phi receives the fixed field.
 constexpr int TAN_NSUM = 8;
 struct TanLevelArgs {
     const double *phi, *pq, *u, *h;     // this level of the histories (trajectory stride hist_stride); pq, u, h may be NULL (zeros)
@@ -2690,12 +2761,25 @@ struct TanLevelArgs {
     const double *src_phi, *src_mu;     // copy src -> dst at every node (NULL dst: no copy)
     double *dst_phi, *dst_mu;
     const double *W;
+    int fix;                            // 0: none, 1: d1, 2: d2
+    const double *rec;                  // the cell of the step that led to this level in the shift record, or NULL
+    long rec_stride;
+    const double *mpart;                // k_tan_mass's partials of the field to fix
+    double LxLy;
 };
 __global__ __launch_bounds__(NTH) void k_tan_level(Geom G, TanLevelArgs a, double *__restrict__ part /* this level's [B][nblk][8] */,
                                                    long part_stride) {
     TILE_COORDS;
     __shared__ double sred[TAN_NSUM * 4];
+    __shared__ double s_fix[2];
     const long pb = b * G.plane, hb = b * a.hist_stride;
+    const double *rec = (a.fix && a.rec) ? a.rec + b * a.rec_stride : (const double *)nullptr;
+    const double shift = rec ? rec[0] : 0.0;
+    if (shift != 0.0) {                 // uniform over the workgroup
+        post_sums(a.mpart, nblk, (int)b, s_fix);
+        __syncthreads();
+    }
+    const TanFix tf(s_fix, rec, a.LxLy);
     double acc[TAN_NSUM] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int k = 0; k < TY / 4; ++k) {
         int r = r0 + ly0 + 4 * k, c = c0 + lx;
@@ -2704,7 +2788,9 @@ __global__ __launch_bounds__(NTH) void k_tan_level(Geom G, TanLevelArgs a, doubl
             const double w = a.W[o], ph = a.phi[hb + o];
             const double e = ph - (a.pq ? a.pq[hb + o] : 0.0);
             const double uu = a.u ? a.u[hb + o] : 0.0, hh = a.h ? a.h[hb + o] : 0.0;
-            const double d1 = a.d1 ? a.d1[pb + o] : 0.0, d2 = a.d2 ? a.d2[pb + o] : 0.0;
+            double d1 = a.d1 ? a.d1[pb + o] : 0.0, d2 = a.d2 ? a.d2[pb + o] : 0.0;
+            if (a.fix == 1) d1 = tf.apply(d1, ph + shift);
+            else if (a.fix == 2) d2 = tf.apply(d2, ph + shift);
             acc[0] += w * (e * d1);
             acc[1] += w * (d1 * d1);
             acc[2] += w * (e * d2);
@@ -2716,7 +2802,7 @@ __global__ __launch_bounds__(NTH) void k_tan_level(Geom G, TanLevelArgs a, doubl
                 acc[6] += w * (eT * d2);
             }
             if (a.dst_phi) {
-                a.dst_phi[pb + o] = a.src_phi[pb + o];
+                a.dst_phi[pb + o] = a.fix == 1 ? d1 : a.fix == 2 ? d2 : a.src_phi[pb + o];
                 a.dst_mu[pb + o] = a.src_mu[pb + o];
             }
         }

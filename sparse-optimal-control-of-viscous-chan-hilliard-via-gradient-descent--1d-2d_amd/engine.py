@@ -369,6 +369,13 @@ class Engine2D:
             res["dphi"], res["d2phi"] = d1, d2
         return res
 
+    def mass_shifts(self):
+        """(B, M): what the march's interior mass fix subtracted at the end of every step of the resident state history
+        (vch2d_mass_shifts; zeros where the fix was not applied); M = the steps of that history."""
+        buf = np.empty(self.B * self.max_steps)
+        M = check(self.lib.vch2d_mass_shifts(self.ctx, _dp(buf)))
+        return buf[:self.B * M].reshape(self.B, M).copy()
+
     def pgd_cost_device_ptr(self):
         p = C.c_void_p()
         check(self.lib.vch2d_pgd_cost_dev(self.ctx, C.byref(p)))

@@ -2,27 +2,44 @@
 Newton matrix and a sparse direct solve.  Shared by test_tangent_cpu.py (which pins it against central differences of the
 oracle's nonlinear march) and test_gpu_second_order.py (which compares the engine with it).
 
-With dphi_0 = dmu_0 = dw_0 = 0 and d2phi_0 = d2mu_0 = 0, per step n (dt = t_{n+1} - t_n, J = jac_matrix(phi_{n+1})):
+With dphi_0 = dmu_0 = dw_0 = 0 and d2phi_0 = d2mu_0 = 0, per step n (dt = t_{n+1} - t_n), with s_n the shift the march's
+mass fix subtracted at the end of step n and phi* = phi_{n+1} + s_n the Newton solution before it, J = jac_matrix(phi*):
     dw'  = w_filter(dw, dt, gamma, h_n, h_{n+1})                       rows (n, n+1) while n < len(h) - 1, zeros afterwards
-    J [dphi'; dmu']   = [tau dphi/dt + kappa/2 L dphi + 2 c2 dphi + dmu/2 + (dw' + dw)/2 ;  dphi/dt + L dmu / 2]
-    J [d2phi'; d2mu'] = [tau d2phi/dt + kappa/2 L d2phi + 2 c2 d2phi + d2mu/2 - c1 rho(phi_{n+1}) dphi'^2 ;  d2phi/dt + L d2mu / 2]
+    J [dphi*; dmu']   = [tau dphi/dt + kappa/2 L dphi + 2 c2 dphi + dmu/2 + (dw' + dw)/2 ;  dphi/dt + L dmu / 2]
+    J [d2phi*; d2mu'] = [tau d2phi/dt + kappa/2 L d2phi + 2 c2 d2phi + d2mu/2 - c1 rho(phi*) dphi*^2 ;  d2phi/dt + L d2mu / 2]
     rho(p) = 4 p / (1 - p^2)^2
-The clip and the mass fix at the end of a step are taken as the identity (callers assert max|phi| < 1 - delta_sep)."""
+    dphi' = dphi* - sum(wts dphi*) / W_int,   d2phi' = d2phi* - sum(wts d2phi*) / W_int       (where s_n != 0)
+wts = hx hy outer(trapz_x, trapz_y) are the mass fix's own weights and W_int their sum over the interior nodes
+(|phi*| < 1 - delta_sep - 5e-3), on which alone the mean is subtracted; dmu' and dw' are carried as they are, like the march
+carries mu (F2:579).  The mass fix is NOT the identity: the linearised step conserves the mass of dphi only in the weights
+of the Laplacian (its Kronecker-order quirk, oracle.lap), which are the fix's weights only for Nx == Ny.  The clip is taken
+as the identity and so is the interior set (callers assert max|phi| < 1 - delta_sep - 5e-3 - |s|)."""
 import numpy as np
-from scipy.sparse.linalg import spsolve
+from scipy.sparse.linalg import splu
 
 from oracle import vch2d_oracle as o
 
 KEYS = ("s_state", "s_ctrl", "c_gn", "c_state", "c_ctrl", "n_h")
 
 
-def tangent_reference(P, phi_hist, t_hist, h):
-    """(dphi_hist, d2phi_hist), both shaped like phi_hist, for the direction h (rows, Nx+1, Ny+1)."""
+def march_with_shifts(P, **kw):
+    """o.forward plus the per-step shifts of its mass fix: (phi_hist, (x, y), t_hist, shifts)."""
+    st = {}
+    phi, xy, t = o.forward(P, stats=st, **kw)
+    return phi, xy, t, np.array(st.get("mass_shifts", []), dtype=float)
+
+
+def tangent_reference(P, phi_hist, t_hist, h, shifts=None):
+    """(dphi_hist, d2phi_hist), both shaped like phi_hist, for the direction h (rows, Nx+1, Ny+1).  `shifts` (M,): what the
+    march's mass fix subtracted at the end of each step (None or zeros: the fix taken as the identity)."""
     Nx, Ny = int(P.Nx), int(P.Ny)
     hx, hy = P.Lx / Nx, P.Ly / Ny
     L = o.lap_matrix(Nx, Ny, hx, hy)
     n = (Nx + 1) * (Ny + 1)
     M = len(t_hist) - 1
+    shifts = np.zeros(M) if shifts is None else np.asarray(shifts, dtype=float)
+    assert shifts.shape == (M,)
+    wts = hx * hy * np.outer(o.trapz_weights(Nx + 1), o.trapz_weights(Ny + 1))
     d1 = np.zeros_like(phi_hist)
     d2 = np.zeros_like(phi_hist)
     z = np.zeros(phi_hist.shape[1:])
@@ -33,19 +50,27 @@ def tangent_reference(P, phi_hist, t_hist, h):
                 a / dt + 0.5 * o.lap(m, hx, hy))
 
     def solve(J, rp, rm):
-        s = spsolve(J, np.concatenate([rp.ravel(), rm.ravel()]))
+        s = J.solve(np.concatenate([rp.ravel(), rm.ravel()]))
         return s[:n].reshape(z.shape), s[n:].reshape(z.shape)
+
+    def unmean(a, interior):
+        a = a.copy()
+        a[interior] -= np.sum(wts * a) / float(np.sum(wts[interior]))
+        return a
 
     for k in range(M):
         dt = float(t_hist[k + 1] - t_hist[k])
         hn, hp = (h[k], h[k + 1]) if k < h.shape[0] - 1 else (z, z)
         dw_new = o.w_filter(dw, dt, P.gamma, hn, hp)
-        p = phi_hist[k + 1]
-        J = o.jac_matrix(p, dt, P, L).tocsc()
+        p = phi_hist[k + 1] + shifts[k]
+        J = splu(o.jac_matrix(p, dt, P, L).tocsc())         # one factorisation serves both solves of the step
         rp, rm = rhs(dphi, dmu, dt)
         nphi, nmu = solve(J, rp + 0.5 * (dw_new + dw), rm)
         rp, rm = rhs(ephi, emu, dt)
         ephi, emu = solve(J, rp - P.c1 * (4.0 * p / (1.0 - p * p) ** 2) * nphi ** 2, rm)
+        if shifts[k] != 0.0:
+            interior = np.abs(p) < 1.0 - o.DELTA_SEP - 5e-3
+            nphi, ephi = unmean(nphi, interior), unmean(ephi, interior)
         dphi, dmu, dw = nphi, nmu, dw_new
         d1[k + 1], d2[k + 1] = dphi, ephi
     return d1, d2

@@ -1,7 +1,8 @@
 """vch2d_second_order on the GPU: the tangent marches and the six scalars of J'(u)h and J''(u)[h,h] against CPU linear
 algebra (tests/_tangent_ref.py: the oracle's assembled Newton matrix and a sparse direct solve, pinned against central
-differences of the nonlinear march by test_tangent_cpu.py).  The engine marches, its state history is pulled and fed to
-the CPU reference, so the engine's linear solves are compared with direct ones on the same history, not with themselves.
+differences of the nonlinear march by test_tangent_cpu.py).  The engine marches, its state history and the shifts of its
+mass fix (mass_shifts()) are pulled and fed to the CPU reference, so the engine's linear solves are compared with direct
+ones on the same history, not with themselves.
 
 Cases: 16 x 16 with 5 steps and a ragged last one (T = 0.045, dt = 0.01; stencil-free FFT path), 14 x 11 (GEMM-DCT path;
 the rectangular grid exercises the Laplacian's Kronecker-order quirk), 32 x 16 (rectangular FFT, a direction of 3 rows
@@ -82,15 +83,16 @@ def runs(V):
         eng = _engine(V, P, 3)
         assert eng.uses_fft == pr["fft"]
         phi, _ = eng.forward(pr["phi0"], pr["dts"], u=pr["U"])
+        shifts = eng.mass_shifts()              # what the march's mass fix subtracted: the reference linearises it
         tg = [o.build_targets(pr["x"], pr["y"], pr["t"], phi[b][0], P.Lx, P.Ly, P.T) for b in range(3)]
         phi_T, phi_Q = np.stack([a for a, _ in tg]), np.stack([q for _, q in tg])
         opt = V.make_opt()
         res = eng.second_order(pr["H"], pr["dts"], pr["t"], opt, phi_Q=phi_Q, phi_T=phi_T, histories=True)
         ref = []
         for b in range(3):
-            d1, d2 = tangent_reference(P, phi[b], pr["t"], pr["H"][b])
+            d1, d2 = tangent_reference(P, phi[b], pr["t"], pr["H"][b], shifts[b])
             ref.append((d1, d2))
-        pr.update(eng=eng, phi=phi, phi_T=phi_T, phi_Q=phi_Q, res=res, ref=ref, opt=opt)
+        pr.update(eng=eng, phi=phi, shifts=shifts, phi_T=phi_T, phi_Q=phi_Q, res=res, ref=ref, opt=opt)
         cache[name] = pr
         return pr
 
@@ -114,6 +116,8 @@ def test_fields_and_scalars_against_cpu_linear_algebra(runs, name):
     pr = runs(name)
     res = pr["res"]
     assert np.abs(pr["phi"]).max() < 1.0 - o.DELTA_SEP - 0.1          # the clip the tangent scheme ignores is inactive
+    if pr["P"].Nx != pr["P"].Ny:
+        assert np.abs(pr["shifts"][:2]).min() > 1e-7                  # rectangular grid: the mass fix shifts every step
     worst = dict(d1=0.0, d2=0.0, s=0.0)
     for b in (0, 1):
         d1, d2 = pr["ref"][b]
@@ -212,10 +216,11 @@ def test_pgd_iterate_is_not_disturbed_and_the_iterate_is_the_base_point(V):
     eng = start()
     u, phi, phi_Q = eng.pgd_get("u"), eng.pgd_get("phi"), eng.pgd_get("phi_Q")
     res = eng.second_order(H, opt=opts, histories=True)
+    shifts = eng.mass_shifts()
     assert np.array_equal(eng.pgd_get("u"), u) and np.array_equal(eng.pgd_get("phi"), phi)
     assert np.abs(u).max() > 0
     for b in range(2):
-        d1, d2 = tangent_reference(P, phi[b], t, H[b])
+        d1, d2 = tangent_reference(P, phi[b], t, H[b], shifts[b])
         e1, e2 = _rel(res["dphi"][b], d1), _rel(res["d2phi"][b], d2)
         S = tangent_scalars(phi[b], d1, d2, u[b], H[b], phi_Q[b], phi_T[b], x, x, t, opts[b].b1, opts[b].b2, opts[b].b3)
         devs = {k: abs(float(res[k][b]) / S[k] - 1.0) for k in KEYS + ("slope", "curvature")}
