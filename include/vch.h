@@ -434,6 +434,68 @@ int vch1d_pgd_get(vch1d_ctx *ctx, int what, double *out);
  * same conventions as vch2d_pgd_errors. */
 int vch1d_pgd_errors(vch1d_ctx *ctx, int n_iters, double *tracking_out, double *terminal_out);
 
+/* Exact first and second directional derivatives of the smooth part J1 + J2 + J3 of the 1D cost along h, by a tangent
+ * (linearised) march on the device: the 1D counterpart of vch2d_second_order (ABI version stays 3: detect this entry point
+ * by symbol).  One persistent workgroup per direction runs the whole march and the quadrature; no adjoint, no nonlinear
+ * march, no finite differences, no host round trip between the launch and the six scalars.
+ * The history has rows = M + 2 rows (t = 0 twice, F1:329-336); step n = 0..M-1 takes row n+1 to row n+2 with dt_n and is
+ * driven by the direction rows (h_n, h_{n+1}), the control's own indexing by step (F1:347-353).  J(phi*) is the Newton
+ * matrix of vch1d_jacobian_solve (unclipped diagonal tau/dt + 2 c1 / (1 - phi*^2), F1:122) at phi* = phi_hist[n+2].  All
+ * tangent fields start at zero; per step:
+ *   dw'  = ((gamma/dt - 1/2) dw + 1/2 (h_{n+1} + h_n)) / (gamma/dt + 1/2)
+ *   J [dphi*; dmu']   = [ tau dphi/dt + kappa/2 L dphi + 2 c2 dphi + 1/2 dmu + 1/2 (dw' + dw) ;  dphi/dt + 1/2 L dmu ]
+ *   J [d2phi*; d2mu'] = [ tau d2phi/dt + kappa/2 L d2phi + 2 c2 d2phi + 1/2 d2mu - c1 rho(phi*) (dphi*)^2 ;
+ *                         d2phi/dt + 1/2 L d2mu ],      rho(p) = 4 p / (1 - p^2)^2
+ *   dphi' = dphi* - sum(wts dphi*) / Lx,   d2phi' = d2phi* - sum(wts d2phi*) / Lx,     wts = (Lx / N) trapz
+ * Two things differ from 2D.  The concave term is explicit: -2 c2 phi_old sits in the residual (F1:99-109), so +2 c2 dphi
+ * is on the right-hand side, not in the matrix.  The mass shift is uniform and always applied (F1:366); its linearisation
+ * is the weighted-mean removal over all nodes.  No record of the shifts is needed: the 1D Laplacian conserves mass in
+ * exactly these weights, the shift the march subtracted is bounded by the Newton tolerance, and J, rho are taken at the
+ * stored row.  The end-of-step clip (F1:361) is taken as the identity.  The call does NOT detect an active clip
+ * (|phi| >= 1 - delta_sep somewhere) nor a step the march left through the line-search-failure return (F1:227-229): behind
+ * either, the result is not the derivative of the march.
+ *   phi_hist [n_base][rows][N+1] base-point state history, or NULL: the resident one (last vch1d_forward / _backward /
+ *           _cost upload, or the PGD iterate)
+ *   u       [n_base][rows][N+1] base-point control; NULL: zeros; VCH_RESIDENT: the PGD's resident control.  It enters
+ *           s_ctrl alone: the tangent depends on the state history and h only.
+ *   n_base  1: one base point shared by all B directions (read with stride 0 on the device; of resident arrays, trajectory
+ *           0's); B: one per trajectory.  It holds for phi_hist, u, phi_Q and phi_T alike.
+ *   h       [B][rows][N+1] direction
+ *   dt      [M] step sizes or NULL: t_hist[n+2] - t_hist[n+1];  t_hist [rows], x [N+1]: the cost's quadrature grids
+ *   phi_Q   [n_base][rows][N+1], phi_T [n_base][N+1]; NULL: zeros; VCH_RESIDENT: the PGD's targets
+ *   opts    n_opts = 1 (one set for the batch) or B (trajectory b takes opts[b]); only b1, b2, b3 are read
+ *   order   1 or 2; order 1 skips the second solve of every step, c_state is then NaN
+ *   out[b] = { s_state = b1 int int (phi - phi_Q) dphi + b2 int (phi_M - phi_T) dphi_M,   s_ctrl = b3 int int u h,
+ *              c_gn    = b1 int int dphi^2 + b2 int dphi_M^2,
+ *              c_state = b1 int int (phi - phi_Q) d2phi + b2 int (phi_M - phi_T) d2phi_M,
+ *              c_ctrl  = b3 int int h^2,   n_h = int int h^2 }
+ *           with the cost's own quadrature (C1:55-73): trapezoid in x, then in t_hist over all rows, so the duplicated
+ *           t = 0 row has zero weight.  J'(u) h = s_state + s_ctrl,  J''(u)[h,h] = c_gn + c_state + c_ctrl.  The L1 term J4
+ *           has no curvature away from its kink and is left out.  A trajectory with h == 0 gets exact zeros.
+ *   dphi_hist_out, d2phi_hist_out  [B][rows][N+1] or NULL: the tangent fields (rows 0 and 1 are zero; with order 1
+ *           d2phi_hist_out is all zeros)
+ *   stats (or NULL): linear_solves = order M B, launches = 1, device seconds of the march.
+ * VCH_ERR_ARG, each with a message naming what failed, before anything is copied or launched: rows outside
+ * 3..max_steps+2; n_base or n_opts not 1 or B; order not 1 or 2; NULL h, t_hist, x, out or opts; a dt_n <= 0 or
+ * non-finite; non-finite b1, b2, b3.  VCH_ERR_STATE: phi_hist == NULL without a resident history of `rows` rows;
+ * VCH_RESIDENT before vch1d_pgd_init (or for a problem with another number of rows).
+ * The call is stateless like vch1d_backward and vch1d_cost, and more so: the direction, an uploaded base point, the grids
+ * and the tangent fields live in buffers of its own (the work planes in the per-trajectory march scratch, whose contents
+ * no call relies on), so the control, the state history, the adjoint, the trial buffers and the PGD bookkeeping are not
+ * touched and a following vch1d_pgd_iterate is bit for bit that of an uninterrupted run.  One trajectory is one workgroup
+ * with fixed reduction orders: its outputs are bitwise independent of the batch.
+ * Stop quirk: after a trajectory's stop rule fired (G1:462-465) the resident control is the NEW iterate while the resident
+ * state history is the PREVIOUS one's.  The tangent then belongs to the previous control (it depends on the state history
+ * and h only), and only s_ctrl sees the new one. */
+int vch1d_second_order(vch1d_ctx *ctx, const double *phi_hist, const double *u, int n_base,
+                       const double *h, int rows, const double *dt, const double *t_hist, const double *x,
+                       const double *phi_Q, const double *phi_T,
+                       const vch_opt_params *opts, int n_opts,            /* 1 or B; only b1,b2,b3 are read */
+                       int order /* 1 or 2 */,
+                       double *out /* [B][6] */,
+                       double *dphi_hist_out, double *d2phi_hist_out      /* [B][rows][N+1] or NULL */,
+                       vch_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,7 @@
 """Host-side mirror of src/1D/Vch_control_1D/second_order_conditions.py: finite-difference
-coercivity test with the kink-aware critical cone; forward marches and costs run on the GPU."""
+coercivity test with the kink-aware critical cone; forward marches and costs run on the GPU.
+`approximate_second_order_condition` is the reference's formula, `exact_second_order_condition` gives the exact
+second derivative by tangent marches on the device."""
 from __future__ import annotations
 
 import contextlib
@@ -109,3 +111,46 @@ def _perturbed_costs(controls, fwd_config, phi_Q_target, phi_T_target, x, t_hist
         J = eng.cost(phi_p, U, tile(phi_Q_target), tile(phi_T_target), x, t_hist, opt)
         costs.extend(float(v) for v in np.atleast_2d(J)[:, 4])
     return costs
+
+
+def exact_second_order_condition(fwd_config: ForwardSolverConfig, u_star, r_star, phi_star, x, t_hist, b1, b2, b3, kappa,
+                                 phi_Q_target, phi_T_target, u_min, u_max, num_directions: int = 10, seed=None,
+                                 rng=None) -> List[float]:
+    """J''(u*)[h,h] of the smooth part J1 + J2 + J3 of the discrete cost, exactly (to the round-off of a direct solve), for
+    the same seeded directions as `approximate_second_order_condition` draws (`_generate_direction`, one draw each, in the
+    same order).  No difference quotient and no nonlinear march, so there is no `epsilon`: the directions run as one
+    shared-base batch about `phi_star` as given, in chunks of MAX_BATCH (Engine1D.second_order: one persistent workgroup
+    per direction, two linear solves per step).  Per direction the curvature, the exact slope J'(u*)h and the adjoint's
+    unweighted `sum(g h)`, g = r* + b3 u*, that the finite-difference formula subtracts, are printed side by side.
+
+    What differs from the reference's number:
+      * the smooth part only: the L1 term J4 has no curvature away from its kink and is left out (the one-sided
+        difference of J picks up kappa (|u + eps h| - |u|) wherever u* = 0);
+      * the exact slope: the derivative of the discrete cost, not the node sum of the hand-derived adjoint, which in 1D
+        also runs on parameters frozen at the defaults (B1:29-33);
+      * J'' is the quadrature-weighted second derivative for the unit-Euclidean h: with the cost's trapezoid weights in x
+        and t, as J itself is, and not rescaled by `n_h = int int h^2`.
+    The clip at the end of a time step is taken as inactive (|phi| < 1 - delta_sep), and a step of the march behind
+    `phi_star` that left Newton's loop through the line-search-failure return is not detected."""
+    from ..engine import make_opt
+    from ._ctx import engine_for_config
+    rng = _as_generator(rng if rng is not None else seed)
+    cfg = fwd_config if fwd_config is not None else ForwardSolverConfig()
+    grad_star = r_star + b3 * u_star
+    print(f"Testing {num_directions} random directions in the critical cone (exact tangent marches)...")
+    dirs = [_generate_direction(u_star, r_star, u_min, u_max, kappa, b3, rng) for _ in range(num_directions)]
+    opt = make_opt(b1=b1, b2=b2, b3=b3, kappa_sparsity=kappa)
+    t_hist = np.asarray(t_hist, dtype=np.float64)
+    rows = int(t_hist.size)
+    out: List[float] = []
+    for k0 in range(0, len(dirs), MAX_BATCH):
+        chunk = dirs[k0:k0 + MAX_BATCH]
+        eng = engine_for_config(cfg, batch=len(chunk), max_steps=max(rows - 2, 1))
+        res = eng.second_order(np.stack(chunk), t_hist, opt, phi_hist=phi_star, u=u_star, phi_Q=phi_Q_target,
+                               phi_T=phi_T_target, x=x, shared_base=True)
+        for i, h in enumerate(chunk):
+            d2, slope = float(res["curvature"][i]), float(res["slope"][i])
+            out.append(d2)
+            print(f"  Direction {k0 + i + 1}/{num_directions}: exact d²J/dh² = {d2:.6e}   exact slope J'h = {slope:.6e}   "
+                  f"adjoint sum(g·h) = {np.sum(grad_star * h):.6e}")
+    return out

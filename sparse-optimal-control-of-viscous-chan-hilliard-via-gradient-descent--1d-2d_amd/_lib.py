@@ -159,6 +159,8 @@ SIGNATURES = {
     "vch1d_pgd_init": (C.c_int, [_P, _D, _D, _D, _D, _D, C.c_int, _D, C.POINTER(OptParams), _D]),
     "vch1d_pgd_iterate": (C.c_int, [_P, C.c_int, _D, _D, _I32, _D, _D]),
     "vch1d_pgd_get": (C.c_int, [_P, C.c_int, _D]),
+    "vch1d_second_order": (C.c_int, [_P, _D, _D, C.c_int, _D, C.c_int, _D, _D, _D, _D, _D, C.POINTER(OptParams), C.c_int,
+                                     C.c_int, _D, _D, _D, C.POINTER(Stats)]),
     "vch2d_counters": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "vch_comm_unique_id": (C.c_int, [C.POINTER(C.c_ubyte)]),
     "vch_comm_create": (_P, [C.POINTER(C.c_ubyte), C.c_int, C.c_int, C.c_int]),

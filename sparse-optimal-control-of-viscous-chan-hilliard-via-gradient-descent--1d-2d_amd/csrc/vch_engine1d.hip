@@ -35,6 +35,10 @@ struct vch1d_ctx {
     std::vector<double> pgd_denQ2, pgd_denT2, pgd_trk, pgd_trm;
     double pgd_rms = 1.0;
     int pgd_err_n = 0;
+    // vch1d_second_order (lazy): its own copies of the base point, the direction and the grids, so that the call leaves
+    // every resident buffer as it found it
+    double *so_base = nullptr, *so_u = nullptr, *so_pq = nullptr, *so_h = nullptr, *so_d1 = nullptr, *so_d2 = nullptr;   // [B][Mmax+2][n]
+    double *so_pt = nullptr, *so_dts = nullptr, *so_t = nullptr, *so_wx = nullptr, *so_wts = nullptr, *so_out = nullptr;
 };
 
 // no launch bookkeeping (LAUNCH_LDS, vch_common.h)
@@ -128,6 +132,8 @@ extern "C" vch1d_ctx *vch1d_create(const vch1d_params *p, int batch, int max_ste
     hipFuncSetAttribute((const void *)k1d_backward, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes);
     hipFuncSetAttribute((const void *)k1d_solve<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes);
     hipFuncSetAttribute((const void *)k1d_solve<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes);
+    hipFuncSetAttribute((const void *)k1d_tangent<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes);
+    hipFuncSetAttribute((const void *)k1d_tangent<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes);
     if (hipStreamSynchronize(c->stream) != hipSuccess) return fail("hipStreamSynchronize");
     return c;
 }
@@ -138,7 +144,9 @@ extern "C" void vch1d_destroy(vch1d_ctx *c) {
     hipStreamSynchronize(c->stream);
     double *all[] = {c->scratch, c->tmp[0], c->tmp[1], c->tmp[2], c->tmp[3], c->tmp[4], c->tmp[5], c->tmp[6], c->tmp[7],
                      c->phiT, c->dts, c->tgrid, c->wx, c->alpha_dev, c->cost_lvl, c->hist_dev, c->phi_hist, c->u_hist,
-                     c->u_trial, c->phiQ, c->p_hist, c->q_hist, c->r_hist, c->phi0_dev, c->phi_trial, c->chg_dev, c->tp_dev};
+                     c->u_trial, c->phiQ, c->p_hist, c->q_hist, c->r_hist, c->phi0_dev, c->phi_trial, c->chg_dev, c->tp_dev,
+                     c->so_base, c->so_u, c->so_pq, c->so_h, c->so_d1, c->so_d2, c->so_pt, c->so_dts, c->so_t, c->so_wx,
+                     c->so_wts, c->so_out};
     for (double *q : all)
         if (q) hipFree(q);
     hipFree(c->stats_dev);
@@ -657,3 +665,127 @@ extern "C" int vch1d_pgd_get(vch1d_ctx *c, int what, double *out) {
     return down_hist(c, out, src, c->pgd_rows);
 }
 
+
+// ------------------------------------------------------------------------------------
+// exact J'(u)h and J''(u)[h,h] by a tangent march on the device (k1d_tangent)
+// ------------------------------------------------------------------------------------
+// host [nb][rows][n] -> device [nb][Mmax+2][n]
+static int up_hist_n(vch1d_ctx *c, double *dev, const double *host, int rows, int nb) {
+    for (int b = 0; b < nb; ++b) VCHCHK(up(c, dev + b * hs1(c), host + (size_t)b * rows * c->n, (size_t)rows * c->n));
+    return 0;
+}
+
+extern "C" int vch1d_second_order(vch1d_ctx *c, const double *phi_hist, const double *u, int n_base, const double *h,
+                                  int rows, const double *dt, const double *t_hist, const double *x, const double *phi_Q,
+                                  const double *phi_T, const vch_opt_params *opts, int n_opts, int order, double *out,
+                                  double *dphi_hist_out, double *d2phi_hist_out, vch_stats *stats) {
+    CTXCHK(c);
+    const int B = c->B, n = c->n;
+    const char *fn = "vch1d_second_order";
+    if (rows < 3 || rows > c->Mmax + 2)
+        return vch_fail(VCH_ERR_ARG, "%s: rows = %d outside 3..%d (max_steps + 2)", fn, rows, c->Mmax + 2);
+    if (n_base != 1 && n_base != B) return vch_fail(VCH_ERR_ARG, "%s: n_base = %d is neither 1 nor the batch %d", fn, n_base, B);
+    if (n_opts != 1 && n_opts != B) return vch_fail(VCH_ERR_ARG, "%s: n_opts = %d is neither 1 nor the batch %d", fn, n_opts, B);
+    if (order != 1 && order != 2) return vch_fail(VCH_ERR_ARG, "%s: order = %d is neither 1 nor 2", fn, order);
+    if (!h) return vch_fail(VCH_ERR_ARG, "%s: NULL direction h", fn);
+    if (!t_hist) return vch_fail(VCH_ERR_ARG, "%s: NULL t_hist", fn);
+    if (!x) return vch_fail(VCH_ERR_ARG, "%s: NULL x", fn);
+    if (!out) return vch_fail(VCH_ERR_ARG, "%s: NULL out", fn);
+    if (!opts) return vch_fail(VCH_ERR_ARG, "%s: NULL opts", fn);
+    const int M = rows - 2;
+    std::vector<double> dts(M);
+    for (int k = 0; k < M; ++k) {
+        dts[k] = dt ? dt[k] : t_hist[k + 2] - t_hist[k + 1];
+        if (!(dts[k] > 0.0) || !std::isfinite(dts[k]))
+            return vch_fail(VCH_ERR_ARG, "%s: step %d: dt = %g must be positive and finite", fn, k, dts[k]);
+    }
+    std::vector<double> wts(3 * (size_t)B);
+    for (int b = 0; b < B; ++b) {
+        const vch_opt_params &o = opts[n_opts == 1 ? 0 : b];
+        if (!std::isfinite(o.b1) || !std::isfinite(o.b2) || !std::isfinite(o.b3))
+            return vch_fail(VCH_ERR_ARG, "%s: trajectory %d: b1, b2, b3 must be finite", fn, b);
+        wts[3 * b] = o.b1; wts[3 * b + 1] = o.b2; wts[3 * b + 2] = o.b3;
+    }
+    if (!phi_hist && (!c->phi_hist || c->rows_res != rows))
+        return vch_fail(VCH_ERR_STATE, "%s: no resident state history with %d rows", fn, rows);
+    if ((u == VCH_RESIDENT || phi_Q == VCH_RESIDENT || phi_T == VCH_RESIDENT) && !c->pgd_ready)
+        return vch_fail(VCH_ERR_STATE, "%s: VCH_RESIDENT control or targets before vch1d_pgd_init", fn);
+    if ((u == VCH_RESIDENT || phi_Q == VCH_RESIDENT) && c->pgd_rows != rows)
+        return vch_fail(VCH_ERR_STATE, "%s: the resident PGD problem has %d rows, not %d", fn, c->pgd_rows, rows);
+    // ---- nothing was launched or copied up to here
+    const long hs = hs1(c), bs = n_base == 1 ? 0 : hs;
+    Tan1Args G{};
+    G.hs = hs;
+    if (phi_hist) {
+        VCHCHK(ensure1(c, &c->so_base));
+        VCHCHK(up_hist_n(c, c->so_base, phi_hist, rows, n_base));
+        G.phi = c->so_base;
+    } else {
+        G.phi = c->phi_hist;
+    }
+    G.phi_s = bs;
+    if (u == VCH_RESIDENT) {
+        G.u = c->u_hist;
+    } else if (u) {
+        VCHCHK(ensure1(c, &c->so_u));
+        VCHCHK(up_hist_n(c, c->so_u, u, rows, n_base));
+        G.u = c->so_u;
+    }
+    G.u_s = bs;
+    if (phi_Q == VCH_RESIDENT) {
+        G.pq = c->phiQ;
+    } else if (phi_Q) {
+        VCHCHK(ensure1(c, &c->so_pq));
+        VCHCHK(up_hist_n(c, c->so_pq, phi_Q, rows, n_base));
+        G.pq = c->so_pq;
+    }
+    G.pq_s = bs;
+    if (phi_T == VCH_RESIDENT) {
+        G.pt = c->phiT;
+    } else if (phi_T) {
+        if (!c->so_pt) VCHCHK(dalloc1(&c->so_pt, (size_t)B * n, c->stream));
+        VCHCHK(up(c, c->so_pt, phi_T, (size_t)n_base * n));
+        G.pt = c->so_pt;
+    }
+    G.pt_s = n_base == 1 ? 0 : n;
+    VCHCHK(ensure1(c, &c->so_h));
+    VCHCHK(up_hist(c, c->so_h, h, rows));
+    G.hd = c->so_h;
+    if (!c->so_dts) {
+        VCHCHK(dalloc1(&c->so_dts, c->Mmax + 2, c->stream));
+        VCHCHK(dalloc1(&c->so_t, c->Mmax + 2, c->stream));
+        VCHCHK(dalloc1(&c->so_wx, n, c->stream));
+        VCHCHK(dalloc1(&c->so_wts, 3 * (size_t)B, c->stream));
+        VCHCHK(dalloc1(&c->so_out, 6 * (size_t)B, c->stream));
+    }
+    std::vector<double> wx;
+    trapz_x(c, x, wx);
+    VCHCHK(up(c, c->so_dts, dts.data(), M));
+    VCHCHK(up(c, c->so_t, t_hist, rows));
+    VCHCHK(up(c, c->so_wx, wx.data(), n));
+    VCHCHK(up(c, c->so_wts, wts.data(), wts.size()));
+    G.dts = c->so_dts; G.t = c->so_t; G.wx = c->so_wx; G.wts = c->so_wts; G.out = c->so_out;
+    if (dphi_hist_out) { VCHCHK(ensure1(c, &c->so_d1)); G.d1 = c->so_d1; }
+    if (d2phi_hist_out && order == 2) { VCHCHK(ensure1(c, &c->so_d2)); G.d2 = c->so_d2; }
+    HIPCHK(hipEventRecord(c->ev0, c->stream));
+    if (order == 2)
+        LAUNCH_LDS(-1, (k1d_tangent<2>), dim3(B), dim3(T1), c->lds_bytes, c->P, n, c->h, c->lvl, rows, G, c->scratch);
+    else
+        LAUNCH_LDS(-1, (k1d_tangent<1>), dim3(B), dim3(T1), c->lds_bytes, c->P, n, c->h, c->lvl, rows, G, c->scratch);
+    HIPCHK(hipEventRecord(c->ev1, c->stream));
+    VCHCHK(down(c, out, c->so_out, 6 * (size_t)B));          // synchronises: the host vectors above are done with
+    if (dphi_hist_out) VCHCHK(down_hist(c, dphi_hist_out, c->so_d1, rows));
+    if (d2phi_hist_out) {
+        if (order == 2) VCHCHK(down_hist(c, d2phi_hist_out, c->so_d2, rows));
+        else memset(d2phi_hist_out, 0, sizeof(double) * B * rows * n);
+    }
+    if (stats) {
+        float ms = 0;
+        hipEventElapsedTime(&ms, c->ev0, c->ev1);
+        memset(stats, 0, sizeof(*stats));
+        stats->linear_solves = (int64_t)order * M * B;
+        stats->launches = 1;
+        stats->seconds = ms * 1e-3;
+    }
+    return 0;
+}

@@ -520,6 +520,162 @@ __global__ __launch_bounds__(T1) void k1d_backward(Phys1 F, int n, double h, int
 }
 
 // ---------------------------------------------------------------------------------
+// persistent tangent march (vch1d_second_order): J'(u)h and J''(u)[h,h] of J1 + J2 + J3 about a state
+// history.  grid = B workgroups, one direction each.  All tangent fields start at zero; step s takes history row s+1 to
+// row s+2 with phi* = row s+2 and the direction rows (s, s+1):
+//   dw'  = ((gamma/dt - 1/2) dw + 1/2 (h_{s+1} + h_s)) / (gamma/dt + 1/2)
+//   J(phi*) [dphi*; dmu']   = [tau dphi/dt + kappa/2 L dphi + 2 c2 dphi + dmu/2 + (dw' + dw)/2 ;  dphi/dt + L dmu / 2]
+//   J(phi*) [d2phi*; d2mu'] = [tau d2phi/dt + kappa/2 L d2phi + 2 c2 d2phi + d2mu/2 - c1 rho(phi*) dphi*^2 ;
+//                              d2phi/dt + L d2mu / 2],      rho(p) = 4 p / (1 - p^2)^2
+//   dphi' = dphi* - sum(wts dphi*) / Lx,  d2phi' = d2phi* - sum(wts d2phi*) / Lx,   wts = h trapz
+// J is the Newton matrix of row0<0> (unclipped diagonal); the concave term -2 c2 phi_old is explicit in 1D (F1:99-109),
+// hence on the right-hand side; the mean removal is the linearisation of the uniform mass shift (F1:366).  The clip of
+// F1:361 is taken as the identity.  No Newton loop, no line search: two solves per step (one with ORDER 1).
+// The level sums are folded into trapezoid sums over t in row order, every reduction in block_red's order: a
+// trajectory's results do not depend on the batch.
+// ---------------------------------------------------------------------------------
+struct Tan1Args {
+    const double *phi; long phi_s;      // base point: state history, stride per trajectory (0 = one base for the batch)
+    const double *u; long u_s;          // control (or NULL = zeros)
+    const double *pq; long pq_s;        // phi_Q (or NULL)
+    const double *pt; long pt_s;        // phi_T (or NULL)
+    const double *hd; long hs;          // direction [B][hs]
+    const double *dts, *t, *wx, *wts;   // [rows-2], [rows], [n] trapezoid weights of the cost, [B][3] = {b1, b2, b3}
+    double *d1, *d2;                    // tangent histories [B][hs] or NULL
+    double *out;                        // [B][6]
+};
+
+template <int K>       // K sums at once, each in block_red<0>'s order; sk: K * (T1 / 64) doubles
+__device__ __forceinline__ void block_sums(double (&v)[K], double *sk) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = wsum1(v[k]);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0)
+#pragma unroll
+        for (int k = 0; k < K; ++k) sk[k * (T1 / 64) + (threadIdx.x >> 6)] = v[k];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        double r = sk[k * (T1 / 64)];
+        for (int w = 1; w < T1 / 64; ++w) r += sk[k * (T1 / 64) + w];
+        v[k] = r;
+    }
+}
+
+template <int ORDER>
+__global__ __launch_bounds__(T1) void k1d_tangent(Phys1 P, int n, double h, int lvl, int rows, Tan1Args G, double *scratch) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    __shared__ double sk[5 * (T1 / 64)];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const double a = 1.0 / (h * h);
+    double *q = scratch + (long)b * NSCR1 * n;
+    double *dphi = q, *dmu = q + n, *dw = q + 2 * n, *ephi = q + 3 * n, *emu = q + 4 * n, *rp = q + 5 * n, *rm = q + 6 * n,
+           *nphi = q + 7 * n, *nmu = q + 8 * n, *rp2 = q + 9 * n, *rm2 = q + 10 * n, *nephi = q + 11 * n, *nemu = q + 12 * n;
+    const double *ph = G.phi + b * G.phi_s;
+    const double *uu = G.u ? G.u + b * G.u_s : nullptr;
+    const double *pq = G.pq ? G.pq + b * G.pq_s : nullptr;
+    const double *pt = G.pt ? G.pt + b * G.pt_s : nullptr;
+    const double *hd = G.hd + b * G.hs;
+    double *d1 = G.d1 ? G.d1 + b * G.hs : nullptr, *d2 = G.d2 ? G.d2 + b * G.hs : nullptr;
+    for (int i = tid; i < n; i += T1) {
+        dphi[i] = dmu[i] = dw[i] = ephi[i] = emu[i] = 0.0;
+        if (d1) d1[i] = d1[n + i] = 0.0;
+        if (d2) d2[i] = d2[n + i] = 0.0;
+    }
+    // S = {sum wx (phi - phi_Q) dphi, sum wx dphi^2, sum wx (phi - phi_Q) d2phi, sum wx u h, sum wx h^2} of one history row
+    auto level = [&](int row, double (&S)[5]) {
+        const long o = (long)row * n;
+        S[0] = S[1] = S[2] = S[3] = S[4] = 0.0;
+        for (int i = tid; i < n; i += T1) {
+            const double w = G.wx[i], e = ph[o + i] - (pq ? pq[o + i] : 0.0), d = dphi[i], hh = hd[o + i];
+            S[0] += w * (e * d);
+            S[1] += w * (d * d);
+            if (ORDER == 2) S[2] += w * (e * ephi[i]);
+            S[3] += w * ((uu ? uu[o + i] : 0.0) * hh);
+            S[4] += w * (hh * hh);
+        }
+        block_sums<5>(S, sk);
+    };
+    double I[5] = {0, 0, 0, 0, 0}, S0[5], S1[5];
+    auto fold = [&](int row) {           // interval (row - 1, row) of the trapezoid rule in t (C1:55-73)
+        const double d = G.t[row] - G.t[row - 1];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) { I[k] += d * (S1[k] + S0[k]) / 2.0; S0[k] = S1[k]; }
+    };
+    level(0, S0);
+    level(1, S1);
+    fold(1);
+    for (int s = 0; s < rows - 2; ++s) {
+        const double dt = G.dts[s], gdt = P.gamma / dt;
+        const double *ps = ph + (long)(s + 2) * n;
+        const double *h0 = hd + (long)s * n, *h1 = h0 + n;
+        for (int i = tid; i < n; i += T1) {
+            const double wo = dw[i], wn = ((gdt - 0.5) * wo + 0.5 * (h1[i] + h0[i])) / (gdt + 0.5);
+            const double d = dphi[i];
+            rp[i] = (P.tau / dt) * d + 0.5 * P.kappa * lap1(dphi, i, n, a) + 2.0 * P.c2 * d + 0.5 * dmu[i] + 0.5 * (wn + wo);
+            rm[i] = d / dt + 0.5 * lap1(dmu, i, n, a);
+            dw[i] = wn;
+            if (ORDER == 2) {
+                const double e = ephi[i];
+                rp2[i] = (P.tau / dt) * e + 0.5 * P.kappa * lap1(ephi, i, n, a) + 2.0 * P.c2 * e + 0.5 * emu[i];
+                rm2[i] = e / dt + 0.5 * lap1(emu, i, n, a);
+            }
+        }
+        __syncthreads();
+        SysArgs A{ps, rp, rm, dt, a, P.tau, P.c1, P.c2, P.kappa, n};
+        cr_solve<0>(A, lvl, lds, nphi, nmu);
+        double ms = 0.0;
+        for (int i = tid; i < n; i += T1) ms += ((i == 0 || i == n - 1) ? 0.5 : 1.0) * h * nphi[i];
+        const double m1 = block_red<0>(ms, sk) / P.Lx;
+        for (int i = tid; i < n; i += T1) {
+            const double v = nphi[i];
+            dphi[i] = v - m1;
+            dmu[i] = nmu[i];
+            if (d1) d1[(long)(s + 2) * n + i] = v - m1;
+            if (ORDER == 2) {
+                const double p = ps[i], om = 1.0 - p * p;
+                rp2[i] -= P.c1 * (4.0 * p / (om * om)) * (v * v);
+            }
+        }
+        __syncthreads();
+        if (ORDER == 2) {
+            SysArgs A2{ps, rp2, rm2, dt, a, P.tau, P.c1, P.c2, P.kappa, n};
+            cr_solve<0>(A2, lvl, lds, nephi, nemu);
+            double es = 0.0;
+            for (int i = tid; i < n; i += T1) es += ((i == 0 || i == n - 1) ? 0.5 : 1.0) * h * nephi[i];
+            const double m2 = block_red<0>(es, sk) / P.Lx;
+            for (int i = tid; i < n; i += T1) {
+                ephi[i] = nephi[i] - m2;
+                emu[i] = nemu[i];
+                if (d2) d2[(long)(s + 2) * n + i] = nephi[i] - m2;
+            }
+            __syncthreads();
+        }
+        level(s + 2, S1);
+        fold(s + 2);
+    }
+    // terminal terms (C1:63): sum wx (phi_M - phi_T) dphi_M and the same with d2phi_M; sum wx dphi_M^2 is S0[1]
+    double T[2] = {0.0, 0.0};
+    const long ol = (long)(rows - 1) * n;
+    for (int i = tid; i < n; i += T1) {
+        const double w = G.wx[i], e = ph[ol + i] - (pt ? pt[i] : 0.0);
+        T[0] += w * (e * dphi[i]);
+        if (ORDER == 2) T[1] += w * (e * ephi[i]);
+    }
+    block_sums<2>(T, sk);
+    if (tid == 0) {
+        const double b1 = G.wts[3 * b], b2 = G.wts[3 * b + 1], b3 = G.wts[3 * b + 2];
+        double *o = G.out + 6 * (long)b;
+        o[0] = b1 * I[0] + b2 * T[0];
+        o[1] = b3 * I[3];
+        o[2] = b1 * I[1] + b2 * S0[1];
+        o[3] = ORDER == 2 ? b1 * I[2] + b2 * T[1] : (double)NAN;
+        o[4] = b3 * I[4];
+        o[5] = I[4];
+    }
+}
+
+// ---------------------------------------------------------------------------------
 // element-wise / reduction kernels: Laplacian, residuals, cost (C1:55-73), gradient+prox
 // (C1:99,111, G1:68-70); grid = (rows or 1, B)
 // ---------------------------------------------------------------------------------

@@ -624,3 +624,65 @@ class Engine1D:
         out = np.empty((self.B, self._pgd_rows, self.n))
         check(self.lib.vch1d_pgd_get(self.ctx, {"u": 0, "phi": 1, "r": 2, "phi_Q": 3}[what], _dp(out)))
         return self._sq(out)
+
+    SECOND_ORDER_KEYS = Engine2D.SECOND_ORDER_KEYS
+    RESIDENT = "resident"
+
+    def second_order(self, h, t_hist, opt, phi_hist=None, u=None, phi_Q=None, phi_T=None, dt=None, x=None, order=2,
+                     histories=False, shared_base=False):
+        """Exact J'(u)h and J''(u)[h,h] of the smooth part J1 + J2 + J3 (vch1d_second_order): one tangent march per
+        direction on the device, two linear solves per step, no finite differences and no nonlinear march.
+        h: (B, rows, N+1) directions, rows = M + 2 = len(t_hist).  phi_hist None: the resident history (last forward() or
+        the PGD iterate).  u / phi_Q / phi_T: arrays, None (zeros) or Engine1D.RESIDENT (the PGD's control / targets).
+        shared_base=True: phi_hist, u, phi_Q are (rows, N+1) and phi_T (N+1,), one base point for all B directions (of
+        resident arrays, trajectory 0's).  dt None: t_hist[n+2] - t_hist[n+1]; x None: the engine's grid.  opt: one
+        parameter object or a sequence of B (only b1, b2, b3 are read).
+        Returns a dict of [B] arrays: the six scalars of SECOND_ORDER_KEYS, slope = s_state + s_ctrl, curvature = c_gn +
+        c_state + c_ctrl (NaN with order=1), `stats`, and with histories=True dphi, d2phi (B, rows, N+1)."""
+        t_hist = np.ascontiguousarray(t_hist, dtype=np.float64)
+        rows = int(t_hist.size)
+        h = self._hist(h, rows, "h")
+        nb = 1 if shared_base else self.B
+        resident = C.cast(C.c_void_p(1), _lib._D)
+
+        def base(a, name, field=False):
+            if a is None:
+                return None, None
+            if isinstance(a, str):
+                if a != self.RESIDENT:
+                    raise ValueError(f"{name}: expected an array, None or Engine1D.RESIDENT")
+                return None, resident
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            want = (self.n,) if field else (rows, self.n)
+            if a.shape == want and nb == 1:
+                a = a.reshape((1,) + want)
+            if a.shape != (nb,) + want:
+                raise ValueError(f"{name} must have shape {(nb,) + want}, got {a.shape}")
+            return a, _dp(a)
+
+        if isinstance(phi_hist, str):
+            raise ValueError("phi_hist: pass None for the resident history")
+        keep = [base(phi_hist, "phi_hist"), base(u, "u"), base(phi_Q, "phi_Q_target"), base(phi_T, "phi_T_target", True)]
+        if dt is not None:
+            dt = np.ascontiguousarray(dt, dtype=np.float64)
+            if dt.shape != (rows - 2,):
+                raise ValueError(f"dt must have len(t_hist) - 2 = {rows - 2} entries, got {dt.shape}")
+        x = np.ascontiguousarray(self.x if x is None else x, dtype=np.float64)
+        if x.shape != (self.n,):
+            raise ValueError(f"x must have {self.n} entries")
+        seq = list(opt) if isinstance(opt, (list, tuple)) else [opt]
+        arr = (OptParams * len(seq))(*[o if isinstance(o, OptParams) else make_opt(o) for o in seq])
+        out = np.empty((self.B, 6))
+        d1 = np.empty((self.B, rows, self.n)) if histories else None
+        d2 = np.empty((self.B, rows, self.n)) if histories else None
+        st = Stats()
+        check(self.lib.vch1d_second_order(self.ctx, keep[0][1], keep[1][1], nb, _dp(h), rows, _dp(dt), _dp(t_hist), _dp(x),
+                                          keep[2][1], keep[3][1], arr, len(seq), int(order), _dp(out), _dp(d1), _dp(d2),
+                                          C.byref(st)))
+        res = {k: out[:, i].copy() for i, k in enumerate(self.SECOND_ORDER_KEYS)}
+        res["slope"] = out[:, 0] + out[:, 1]
+        res["curvature"] = (out[:, 2] + out[:, 3]) + out[:, 4]
+        res["stats"] = st.as_dict()
+        if histories:
+            res["dphi"], res["d2phi"] = d1, d2
+        return res
