@@ -427,9 +427,59 @@ int vch1d_free_energy(vch1d_ctx *ctx, const double *phi_hist, int rows, const do
 int vch1d_pgd_init(vch1d_ctx *ctx, const double *phi0, const double *phi_T, const double *phi_Q,
                    const double *x, const double *t_hist, int rows, const double *dt,
                    const vch_opt_params *opt, double *J0_out);
+/* vch1d_pgd_init with one parameter set PER TRAJECTORY, a warm start and a first step size: the 1D counterpart of
+ * vch2d_pgd_init_v (ABI version stays 3: detect this entry point and vch1d_pgd_kkt by symbol).  vch1d_pgd_init is this
+ * call with n_opts = 1 and u0 = alpha0 = NULL.
+ *   opts    n_opts parameter sets, n_opts = 1 (one set for the whole batch) or B (trajectory b takes opts[b]); anything
+ *           else is VCH_ERR_ARG.  Trajectory b's own values are used everywhere in the loop: b1 in the adjoint source, b2
+ *           in the terminal condition, b3 / kappa_sparsity / u_min / u_max in the gradient + prox step, the four weights
+ *           in the cost, alpha_max in the growth (x 1.2) and plateau (x 2.0) rules and as the default first step.  The
+ *           six numbers the kernels need live in a [B] table on the device, indexed by the trajectory's workgroup; the
+ *           arithmetic is that of the scalar form.  One trajectory is one workgroup with fixed reduction orders and the
+ *           Newton and adjoint solves are direct, so a member of a mixed batch computes the bits of a batch-1 run with
+ *           its parameters.
+ *           VCH_ERR_ARG, with a message that names the trajectory, before anything is copied or launched: non-finite b1,
+ *           b2, b3 or kappa_sparsity, kappa_sparsity < 0, alpha_max <= 0, u_min > u_max (infinite bounds are legal),
+ *           alpha0[b] not finite or <= 0.
+ *   u0      [B][rows][N+1] start control or NULL (zeros).  Taken as given, NOT clipped to the box: the initial march
+ *           runs under it and J0_out is its cost under each trajectory's own weights.  The ramp target phi_Q (phi_Q ==
+ *           NULL) is built from history row 0, the initial state, as without a start control.
+ *   alpha0  [B] or NULL.  NULL: the first alpha_prev is each trajectory's alpha_max (the reference's start); otherwise
+ *           min(alpha0[b], alpha_max of b).
+ * The iteration counter (the k of the stop rule `change < 1e-5 and k > 10`), the plateau counter, the cost history and
+ * the done flags start as after vch1d_pgd_init, also under a warm start: a resumed run is a new run from u0.  max_iter is
+ * not read: the loop length is the n_iters of vch1d_pgd_iterate. */
+int vch1d_pgd_init_v(vch1d_ctx *ctx, const double *phi0, const double *phi_T, const double *phi_Q,
+                     const double *x, const double *t_hist, int rows, const double *dt,
+                     const vch_opt_params *opts, int n_opts,
+                     const double *u0 /* [B][rows][N+1] or NULL */, const double *alpha0 /* [B] or NULL */,
+                     double *J0_out /* [B][5] */);
 int vch1d_pgd_iterate(vch1d_ctx *ctx, int n_iters, double *cost_out, double *alpha_out,
                       int32_t *trials_out, double *change_out, double *seconds_out);
 int vch1d_pgd_get(vch1d_ctx *ctx, int what, double *out);
+/* KKT sparsity statistic `u* = 0 <=> |r*| <= kappa_sparsity` of the resident iterate (verify_sparsity_condition,
+ * G1:115-147), counted on the device in one launch, one workgroup per trajectory: 4 B integers and 2 B doubles cross to
+ * the host instead of the control and the adjoint through vch1d_pgd_get.
+ *   counts_out[b] = { #nodes |u| < tol, #nodes |r| <= kappa_sparsity of trajectory b, #nodes where the two predicates
+ *                     agree, #nodes } over all rows (N+1) nodes of trajectory b, the duplicated t = 0 row included, as
+ *                     u_optimal.size counts them in the reference; tol <= 0 means 1e-6.
+ *   refresh != 0  first runs the adjoint sweep on the resident state with each trajectory's own b1, b2, as
+ *                 GD_1D.main() does with run_backward after the loop.  The result stays in the resident p, q, r.
+ *   refresh == 0  uses the resident r as it is: the adjoint the last iteration started from, i.e. that of the iterate
+ *                 BEFORE the last accepted step.  VCH_ERR_STATE if no sweep has run since the init, or if a stateless
+ *                 call that writes the same buffer (vch1d_backward, vch1d_grad_prox) ran on this context after it.  Those
+ *                 calls, vch1d_forward and vch1d_cost upload into the buffers of a loaded PGD problem: keep them on a
+ *                 context of their own while a loop is in progress.
+ *   stationarity_out[b] (or NULL) = ||prox_1(u) - u||_2 / (||u||_2 + 1e-9): prox_1 is the gradient + prox step of
+ *                 vch1d_grad_prox with alpha = 1 and trajectory b's parameters.  Its image is not stored.
+ * The control, the state history, the trial buffers and the loop's bookkeeping are not touched, and the adjoint is a
+ * direct solve that the next iteration repeats from the same state: a following vch1d_pgd_iterate is bit for bit that of
+ * an uninterrupted run with either value of refresh.  VCH_ERR_STATE before vch1d_pgd_init.
+ * Stop quirk: after a trajectory's stop rule fired (G1:462-465) the resident control is the NEW iterate while the resident
+ * state history is the PREVIOUS one's.  The refreshed adjoint then belongs to the previous control, and the statistic
+ * pairs it with the new one. */
+int vch1d_pgd_kkt(vch1d_ctx *ctx, int refresh, double tol, int64_t *counts_out /* [B][4] */,
+                  double *stationarity_out /* [B] or NULL */);
 /* Relative tracking / terminal errors of the iterations of the last vch1d_pgd_iterate call (G1:425-450);
  * same conventions as vch2d_pgd_errors. */
 int vch1d_pgd_errors(vch1d_ctx *ctx, int n_iters, double *tracking_out, double *terminal_out);

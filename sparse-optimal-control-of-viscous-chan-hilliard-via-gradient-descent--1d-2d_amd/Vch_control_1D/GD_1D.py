@@ -182,6 +182,55 @@ def run_optimization_resident(fwd_config: ForwardSolverConfig, opt_config: Optim
     return out
 
 
+def run_sweep(fwd_config: ForwardSolverConfig, opt_configs, n_iter=None, seed=42, amp=0.01, initial_phi=None, choice_t=1,
+              choice_q=1, u0=None, return_controls=False):
+    """A parameter sweep as ONE batch: member b runs the PGD loop with opt_configs[b] (weights, sparsity parameter, box,
+    alpha_max), all members from the same initial state (`initial_phi` (N+1,), else `seed`, `amp`) and targets, so that
+    they differ by their parameters only.  `u0`: start control, one (rows, N+1) array for every member or one per member
+    (continuation in kappa_sparsity, resuming from a saved optimal_control.npy); default zeros.  `n_iter` None: the
+    largest max_iter of the members (the loop length is one for the batch).  Returns dict(costs [B][it+1], alphas, trials,
+    changes, tracking_error, terminal_error, iters, seconds, kkt = Engine1D.pgd_kkt(refresh=True) -- the sparsity
+    statistic and the stationarity measure of every member, counted on the device -- phi_T, t_hist, x, and u only with
+    return_controls); the state history never leaves the device."""
+    from ..engine import Engine1D, time_grid
+    from .Forward_solver import init_phi_random, delta_sep
+    opt_configs = list(opt_configs)
+    B = len(opt_configs)
+    if B < 1:
+        raise ValueError("run_sweep needs at least one OptimizationConfig")
+    N = int(fwd_config.N)
+    tg, dts = time_grid(float(fwd_config.T), float(fwd_config.dt_initial))
+    t_hist = np.concatenate([[0.0], tg])
+    if initial_phi is None:
+        initial_phi = init_phi_random(N, delta_sep, amp=amp, seed=int(seed), enforce_zero_mean=True)
+    phi0 = np.repeat(np.asarray(initial_phi, dtype=np.float64).reshape(1, N + 1), B, axis=0)
+    if u0 is not None:
+        u0 = np.asarray(u0, dtype=np.float64)
+        if u0.ndim == 2:
+            u0 = np.repeat(u0[None], B, axis=0)
+    eng = Engine1D(N=N, Lx=float(fwd_config.Lx), tau=float(fwd_config.tau), gamma=float(fwd_config.gamma),
+                   c1=float(fwd_config.c1), c2=float(fwd_config.c2), kappa=float(fwd_config.kappa), batch=B,
+                   max_steps=max(len(dts), 1))
+    try:
+        x = eng.x.copy()
+        phi_T = build_targets_1d(x, t_hist, phi0[0], float(fwd_config.Lx), float(fwd_config.T), choice_t=choice_t,
+                                 choice_q=2)[0]
+        phi_Q = None if choice_q == 1 else np.zeros((B, len(t_hist), N + 1))
+        J0 = eng.pgd_init(phi0, np.repeat(phi_T[None], B, axis=0), t_hist, dts, [make_opt(o) for o in opt_configs],
+                          phi_Q=phi_Q, x=x, u0=u0)
+        n = int(max(int(o.max_iter) for o in opt_configs) if n_iter is None else n_iter)
+        res = eng.pgd_iterate(n)
+        out = dict(costs=np.concatenate([J0[:, 4:5], res["cost"]], axis=1), alphas=res["alpha"], trials=res["trials"],
+                   changes=res["change"], tracking_error=res["tracking_error"], terminal_error=res["terminal_error"],
+                   iters=res["iters"], seconds=res["seconds"], kkt=eng.pgd_kkt(refresh=True), phi_T=phi_T, t_hist=t_hist,
+                   x=x)
+        if return_controls:
+            out["u"] = eng.pgd_get("u").reshape(B, len(t_hist), N + 1)
+    finally:
+        eng.close()
+    return out
+
+
 def main(n_iter=None, params_file="last_run_config.json", control_file="optimal_control.npy", num_directions=3,
          verbose=True):
     """Non-interactive equivalent of the reference's `__main__` block (G1:256-609) without prompts and

@@ -157,6 +157,8 @@ SIGNATURES = {
     "vch2d_free_energy": (C.c_int, [_P, _D, C.c_int, _D, C.c_double, C.c_double, C.c_double, _D]),
     "vch1d_free_energy": (C.c_int, [_P, _D, C.c_int, _D, C.c_double, C.c_double, _D]),
     "vch1d_pgd_init": (C.c_int, [_P, _D, _D, _D, _D, _D, C.c_int, _D, C.POINTER(OptParams), _D]),
+    "vch1d_pgd_init_v": (C.c_int, [_P, _D, _D, _D, _D, _D, C.c_int, _D, C.POINTER(OptParams), C.c_int, _D, _D, _D]),
+    "vch1d_pgd_kkt": (C.c_int, [_P, C.c_int, C.c_double, C.POINTER(C.c_int64), _D]),
     "vch1d_pgd_iterate": (C.c_int, [_P, C.c_int, _D, _D, _I32, _D, _D]),
     "vch1d_pgd_get": (C.c_int, [_P, C.c_int, _D]),
     "vch1d_second_order": (C.c_int, [_P, _D, _D, C.c_int, _D, C.c_int, _D, _D, _D, _D, _D, C.POINTER(OptParams), C.c_int,

@@ -25,7 +25,14 @@ struct vch1d_ctx {
     // device-resident PGD (vch1d_pgd_*)
     bool pgd_ready = false;
     int pgd_rows = 0;
-    vch_opt_params opt;
+    std::vector<vch_opt_params> opts;      // one set per trajectory (vch1d_pgd_init repeats one set)
+    std::vector<double> opt_tab_host;      // the table's host copy: the source of an asynchronous upload outlives the call
+    double *seam_tab = nullptr;            // [OPT1_STRIDE]: the one row vch1d_backward / vch1d_grad_prox fill from their scalars
+    double seam_tab_host[6] = {0, 0, 0, 0, 0, 0};
+    double *opt_tab = nullptr;             // [B][OPT1_STRIDE]: the device copy the kernels index by trajectory
+    bool pgd_r_valid = false;              // an adjoint sweep has run since the last init
+    long long *kkt_cnt = nullptr;          // vch1d_pgd_kkt: [B][4] counts
+    double *kkt_nrm = nullptr;             //                [B][2] squared norms
     double *phi0_dev = nullptr, *phi_trial = nullptr, *chg_dev = nullptr, *tp_dev = nullptr;
     int *skip_dev = nullptr;
     std::vector<double> t_host, chg_host, pgd_cost, pgd_alpha_prev;
@@ -59,6 +66,13 @@ static int ensure1(vch1d_ctx *c, double **p) {
 static int up(vch1d_ctx *c, double *dev, const double *host, size_t n) {
     HIPCHK(hipMemcpyAsync(dev, host, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     return 0;
+}
+// the function seams' scalar parameters as one table row on the device (read by every trajectory: stride 0)
+static int seam_row(vch1d_ctx *c, double b1, double b2, double b3, double ks, double umin, double umax) {
+    if (!c->seam_tab) VCHCHK(dalloc1(&c->seam_tab, OPT1_STRIDE, c->stream));
+    double *row = c->seam_tab_host;
+    row[OPT1_B1] = b1; row[OPT1_B2] = b2; row[OPT1_B3] = b3; row[OPT1_KS] = ks; row[OPT1_UMIN] = umin; row[OPT1_UMAX] = umax;
+    return up(c, c->seam_tab, row, OPT1_STRIDE);
 }
 static int down(vch1d_ctx *c, double *host, const double *dev, size_t n) {
     HIPCHK(hipMemcpyAsync(host, dev, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -145,12 +159,13 @@ extern "C" void vch1d_destroy(vch1d_ctx *c) {
     double *all[] = {c->scratch, c->tmp[0], c->tmp[1], c->tmp[2], c->tmp[3], c->tmp[4], c->tmp[5], c->tmp[6], c->tmp[7],
                      c->phiT, c->dts, c->tgrid, c->wx, c->alpha_dev, c->cost_lvl, c->hist_dev, c->phi_hist, c->u_hist,
                      c->u_trial, c->phiQ, c->p_hist, c->q_hist, c->r_hist, c->phi0_dev, c->phi_trial, c->chg_dev, c->tp_dev,
-                     c->so_base, c->so_u, c->so_pq, c->so_h, c->so_d1, c->so_d2, c->so_pt, c->so_dts, c->so_t, c->so_wx,
-                     c->so_wts, c->so_out};
+                     c->opt_tab, c->seam_tab, c->kkt_nrm, c->so_base, c->so_u, c->so_pq, c->so_h, c->so_d1, c->so_d2, c->so_pt, c->so_dts,
+                     c->so_t, c->so_wx, c->so_wts, c->so_out};
     for (double *q : all)
         if (q) hipFree(q);
     hipFree(c->stats_dev);
     if (c->skip_dev) hipFree(c->skip_dev);
+    if (c->kkt_cnt) hipFree(c->kkt_cnt);
     hipHostFree(c->stats_host);
     hipHostFree(c->cost_host);
     hipEventDestroy(c->ev0);
@@ -302,14 +317,17 @@ extern "C" int vch1d_backward(vch1d_ctx *c, const double *phi_hist, int rows, co
     VCHCHK(ensure1(c, &c->p_hist));
     VCHCHK(ensure1(c, &c->q_hist));
     VCHCHK(ensure1(c, &c->r_hist));
+    c->pgd_r_valid = false;               // the resident r is no longer the loop's (vch1d_pgd_kkt with refresh == 0)
     const size_t hb = (size_t)c->B * hs1(c) * sizeof(double);
     HIPCHK(hipMemsetAsync(c->p_hist, 0, hb, c->stream));
     HIPCHK(hipMemsetAsync(c->q_hist, 0, hb, c->stream));
     HIPCHK(hipMemsetAsync(c->r_hist, 0, hb, c->stream));
     VCHCHK(up(c, c->tgrid, t_hist, rows));
+    VCHCHK(seam_row(c, b1, b2, 0.0, 0.0, 0.0, 0.0));
     LAUNCH_LDS(-1, k1d_backward, dim3(c->B), dim3(T1), c->lds_bytes, c->F, c->n, c->h, c->lvl, rows, (const double *)c->tgrid,
             (const double *)c->phi_hist, (const double *)(phi_Q ? c->phiQ : nullptr),
-            (const double *)(phi_T ? c->phiT : nullptr), b1, b2, c->p_hist, c->q_hist, c->r_hist, hs1(c), c->scratch);
+            (const double *)(phi_T ? c->phiT : nullptr), (const double *)c->seam_tab, 0, c->p_hist, c->q_hist, c->r_hist, hs1(c),
+            c->scratch);
     HIPCHK(hipStreamSynchronize(c->stream));
     if (p_out) VCHCHK(down_hist(c, p_out, c->p_hist, rows));
     if (q_out) VCHCHK(down_hist(c, q_out, c->q_hist, rows));
@@ -364,11 +382,13 @@ extern "C" int vch1d_grad_prox(vch1d_ctx *c, const double *u, const double *r, i
     VCHCHK(ensure1(c, &c->u_hist));
     VCHCHK(ensure1(c, &c->r_hist));
     VCHCHK(ensure1(c, &c->u_trial));
+    c->pgd_r_valid = false;               // as in vch1d_backward
     VCHCHK(up_hist(c, c->u_hist, u, rows));
     VCHCHK(up_hist(c, c->r_hist, r, rows));
     VCHCHK(up(c, c->alpha_dev, alpha, c->B));
+    VCHCHK(seam_row(c, 0.0, 0.0, o->b3, o->kappa_sparsity, o->u_min, o->u_max));
     LAUNCH(k1d_grad_prox, dim3(rows, c->B), dim3(T1), c->n, (const double *)c->u_hist, (const double *)c->r_hist, hs1(c),
-            (const double *)c->alpha_dev, o->b3, o->kappa_sparsity, o->u_min, o->u_max, c->u_trial, (double *)nullptr);
+            (const double *)c->alpha_dev, (const double *)c->seam_tab, 0, c->u_trial, (double *)nullptr);
     return down_hist(c, u_out, c->u_trial, rows);
 }
 
@@ -410,7 +430,6 @@ static void trapz_x(const vch1d_ctx *c, const double *x, std::vector<double> &wx
 // J[b][5] of (phi, u) on the device; wx already uploaded
 static int cost1_core(vch1d_ctx *c, const double *phi_dev, const double *u_dev, int rows, double *J_out,
                       double *raw_out = nullptr /* [B][2] = {int int (phi - phi_Q)^2, int (phi_end - phi_T)^2} */) {
-    const vch_opt_params *o = &c->opt;
     LAUNCH(k1d_cost, dim3(rows, c->B), dim3(T1), c->n, rows, (const double *)c->wx, phi_dev, u_dev,
             (const double *)c->phiQ, (const double *)c->phiT, hs1(c), c->cost_lvl);
     VCHCHK(down(c, c->cost_host, c->cost_lvl, (size_t)c->B * rows * 4));
@@ -424,6 +443,7 @@ static int cost1_core(vch1d_ctx *c, const double *phi_dev, const double *u_dev, 
             i3 += d * (s[(k + 1) * 4 + 2] + s[k * 4 + 2]) / 2.0;
             i4 += d * (s[(k + 1) * 4 + 3] + s[k * 4 + 3]) / 2.0;
         }
+        const vch_opt_params *o = &c->opts[b];
         double *J = J_out + 5 * b;
         J[0] = (o->b1 / 2.0) * i1;
         J[1] = (o->b2 / 2.0) * s[(rows - 1) * 4 + 1];
@@ -465,14 +485,49 @@ static int fwd1_core(vch1d_ctx *c, const double *u_dev, int rows, double *hist_d
     return 0;
 }
 
-extern "C" int vch1d_pgd_init(vch1d_ctx *c, const double *phi0, const double *phi_T, const double *phi_Q, const double *x,
-                              const double *t_hist, int rows, const double *dt, const vch_opt_params *opt, double *J0_out) {
+// adjoint sweep of the resident state history into the resident p, q, r; trajectory b with b1, b2 of row b of the table
+static int backward1_core(vch1d_ctx *c, int rows) {
+    const size_t hb = (size_t)c->B * hs1(c) * sizeof(double);
+    HIPCHK(hipMemsetAsync(c->p_hist, 0, hb, c->stream));
+    HIPCHK(hipMemsetAsync(c->q_hist, 0, hb, c->stream));
+    HIPCHK(hipMemsetAsync(c->r_hist, 0, hb, c->stream));
+    LAUNCH_LDS(-1, k1d_backward, dim3(c->B), dim3(T1), c->lds_bytes, c->F, c->n, c->h, c->lvl, rows, (const double *)c->tgrid,
+            (const double *)c->phi_hist, (const double *)c->phiQ, (const double *)c->phiT, (const double *)c->opt_tab, OPT1_STRIDE,
+            c->p_hist, c->q_hist, c->r_hist, hs1(c), c->scratch);
+    return 0;
+}
+
+extern "C" int vch1d_pgd_init_v(vch1d_ctx *c, const double *phi0, const double *phi_T, const double *phi_Q, const double *x,
+                                const double *t_hist, int rows, const double *dt, const vch_opt_params *opts, int n_opts,
+                                const double *u0, const double *alpha0, double *J0_out) {
     CTXCHK(c);
-    ARGCHK(phi0 && phi_T && x && t_hist && dt && opt, "NULL argument");
+    ARGCHK(phi0 && phi_T && x && t_hist && dt && opts, "NULL argument");
     ARGCHK(rows >= 3 && rows <= c->Mmax + 2, "rows out of range (3..max_steps+2)");
+    ARGCHK(n_opts == 1 || n_opts == c->B, "n_opts must be 1 or the context's batch");
     const int B = c->B, M = rows - 2;
     for (int k = 0; k < M; ++k) ARGCHK(dt[k] > 0, "dt must be positive");
-    c->opt = *opt;
+    // all of this before anything is copied or launched, or any resident state changes
+    for (int b = 0; b < B; ++b) {
+        const vch_opt_params &o = opts[n_opts == 1 ? 0 : b];
+        const char *bad = nullptr;
+        if (!std::isfinite(o.b1) || !std::isfinite(o.b2) || !std::isfinite(o.b3)) bad = "b1, b2, b3 must be finite";
+        else if (!std::isfinite(o.kappa_sparsity) || o.kappa_sparsity < 0) bad = "kappa_sparsity must be finite and >= 0";
+        else if (!(o.alpha_max > 0)) bad = "alpha_max must be > 0";
+        else if (std::isnan(o.u_min) || std::isnan(o.u_max) || o.u_min > o.u_max) bad = "u_min must be <= u_max";
+        else if (alpha0 && !(std::isfinite(alpha0[b]) && alpha0[b] > 0)) bad = "alpha0 must be finite and > 0";
+        if (bad) return vch_fail(VCH_ERR_ARG, "vch1d_pgd_init_v: trajectory %d: %s", b, bad);
+    }
+    c->opts.resize(B);
+    std::vector<double> &tab = c->opt_tab_host;
+    tab.assign((size_t)B * OPT1_STRIDE, 0.0);
+    for (int b = 0; b < B; ++b) {
+        const vch_opt_params &o = c->opts[b] = opts[n_opts == 1 ? 0 : b];
+        double *row = tab.data() + (size_t)b * OPT1_STRIDE;
+        row[OPT1_B1] = o.b1; row[OPT1_B2] = o.b2; row[OPT1_B3] = o.b3;
+        row[OPT1_KS] = o.kappa_sparsity; row[OPT1_UMIN] = o.u_min; row[OPT1_UMAX] = o.u_max;
+    }
+    c->pgd_ready = false;                 // until this init has gone through
+    c->pgd_r_valid = false;
     c->pgd_rows = rows;
     c->t_host.assign(t_hist, t_hist + rows);
     double **hs[] = {&c->phi_hist, &c->u_hist, &c->u_trial, &c->phiQ, &c->p_hist, &c->q_hist, &c->r_hist, &c->phi_trial};
@@ -481,6 +536,10 @@ extern "C" int vch1d_pgd_init(vch1d_ctx *c, const double *phi0, const double *ph
     if (!c->chg_dev) VCHCHK(dalloc1(&c->chg_dev, (size_t)B * (c->Mmax + 2) * 2, c->stream));
     if (!c->tp_dev) VCHCHK(dalloc1(&c->tp_dev, c->Mmax + 2, c->stream));
     if (!c->skip_dev) HIPCHK(hipMalloc((void **)&c->skip_dev, sizeof(int) * B));
+    if (!c->opt_tab) VCHCHK(dalloc1(&c->opt_tab, tab.size(), c->stream));
+    if (!c->kkt_cnt) HIPCHK(hipMalloc((void **)&c->kkt_cnt, sizeof(long long) * 4 * B));
+    if (!c->kkt_nrm) VCHCHK(dalloc1(&c->kkt_nrm, 2 * (size_t)B, c->stream));
+    VCHCHK(up(c, c->opt_tab, tab.data(), tab.size()));
     c->chg_host.assign((size_t)B * rows * 2, 0.0);
     VCHCHK(up(c, c->phi0_dev, phi0, (size_t)B * c->n));
     VCHCHK(up(c, c->phiT, phi_T, (size_t)B * c->n));
@@ -490,10 +549,11 @@ extern "C" int vch1d_pgd_init(vch1d_ctx *c, const double *phi0, const double *ph
     trapz_x(c, x, wx);
     VCHCHK(up(c, c->wx, wx.data(), c->n));
     HIPCHK(hipStreamSynchronize(c->stream));          // wx is a local
-    // uncontrolled march (G1:341), u = 0
-    VCHCHK(fwd1_core(c, nullptr, rows, c->phi_hist, nullptr));
-    c->rows_res = rows;
+    // u = 0 and the uncontrolled march (G1:341), or the caller's u0 as given (not clipped) and the march under it
     HIPCHK(hipMemsetAsync(c->u_hist, 0, sizeof(double) * B * hs1(c), c->stream));
+    if (u0) VCHCHK(up_hist(c, c->u_hist, u0, rows));
+    VCHCHK(fwd1_core(c, u0 ? c->u_hist : nullptr, rows, c->phi_hist, nullptr));
+    c->rows_res = rows;
     if (phi_Q) {
         VCHCHK(up_hist(c, c->phiQ, phi_Q, rows));
     } else {
@@ -516,7 +576,9 @@ extern "C" int vch1d_pgd_init(vch1d_ctx *c, const double *phi0, const double *ph
     c->pgd_cost.assign(B, 0.0);
     for (int b = 0; b < B; ++b) c->pgd_cost[b] = J[5 * b + 4];
     if (J0_out) memcpy(J0_out, J.data(), sizeof(double) * 5 * B);
-    c->pgd_alpha_prev.assign(B, opt->alpha_max);
+    c->pgd_alpha_prev.resize(B);
+    for (int b = 0; b < B; ++b)           // the first alpha_prev: alpha_max (G1 start), or the caller's, capped at alpha_max
+        c->pgd_alpha_prev[b] = alpha0 ? std::min(alpha0[b], c->opts[b].alpha_max) : c->opts[b].alpha_max;
     c->pgd_plateau.assign(B, 0);
     c->pgd_k.assign(B, 0);
     c->pgd_done.assign(B, 0);
@@ -524,6 +586,11 @@ extern "C" int vch1d_pgd_init(vch1d_ctx *c, const double *phi0, const double *ph
     for (int b = 0; b < B; ++b) c->pgd_cost_hist[b].push_back(c->pgd_cost[b]);
     c->pgd_ready = true;
     return 0;
+}
+
+extern "C" int vch1d_pgd_init(vch1d_ctx *c, const double *phi0, const double *phi_T, const double *phi_Q, const double *x,
+                              const double *t_hist, int rows, const double *dt, const vch_opt_params *opt, double *J0_out) {
+    return vch1d_pgd_init_v(c, phi0, phi_T, phi_Q, x, t_hist, rows, dt, opt, 1, nullptr, nullptr, J0_out);
 }
 
 static int copy_traj1(vch1d_ctx *c, double *dst, const double *src, int b, int rows) {
@@ -537,7 +604,6 @@ extern "C" int vch1d_pgd_iterate(vch1d_ctx *c, int n_iters, double *cost_out, do
     if (!c->pgd_ready) return vch_fail(VCH_ERR_STATE, "vch1d_pgd_iterate: call vch1d_pgd_init first");
     ARGCHK(n_iters >= 1, "n_iters must be >= 1");
     const int B = c->B, rows = c->pgd_rows;
-    const vch_opt_params &O = c->opt;
     constexpr int MAX_LS = 5;                 // G1:74
     constexpr double LS_BETA = 0.8;
     double sec[3] = {0, 0, 0};                // backward, optimistic round, backtracking rounds
@@ -550,7 +616,6 @@ extern "C" int vch1d_pgd_iterate(vch1d_ctx *c, int n_iters, double *cost_out, do
     };
     std::vector<double> alpha(B), Jt(5 * B), raw(2 * B);
     std::vector<int> accepted(B), trials(B);
-    const size_t hb = (size_t)B * hs1(c) * sizeof(double);
     c->pgd_err_n = n_iters;
     c->pgd_trk.assign((size_t)B * n_iters, std::nan(""));
     c->pgd_trm.assign((size_t)B * n_iters, std::nan(""));
@@ -561,12 +626,8 @@ extern "C" int vch1d_pgd_iterate(vch1d_ctx *c, int n_iters, double *cost_out, do
         if (all_done) break;
         // --- adjoint sweep (G1:356); only r is consumed
         HIPCHK(tick(c->ev0));
-        HIPCHK(hipMemsetAsync(c->p_hist, 0, hb, c->stream));
-        HIPCHK(hipMemsetAsync(c->q_hist, 0, hb, c->stream));
-        HIPCHK(hipMemsetAsync(c->r_hist, 0, hb, c->stream));
-        LAUNCH_LDS(-1, k1d_backward, dim3(B), dim3(T1), c->lds_bytes, c->F, c->n, c->h, c->lvl, rows, (const double *)c->tgrid,
-                (const double *)c->phi_hist, (const double *)c->phiQ, (const double *)c->phiT, O.b1, O.b2, c->p_hist, c->q_hist,
-                c->r_hist, hs1(c), c->scratch);
+        VCHCHK(backward1_core(c, rows));
+        c->pgd_r_valid = true;
         HIPCHK(tick(c->ev1));
         sec[0] += lap();
         for (int b = 0; b < B; ++b) {
@@ -581,7 +642,7 @@ extern "C" int vch1d_pgd_iterate(vch1d_ctx *c, int n_iters, double *cost_out, do
             VCHCHK(up(c, c->alpha_dev, alpha.data(), B));
             HIPCHK(hipMemcpyAsync(c->skip_dev, accepted.data(), sizeof(int) * B, hipMemcpyHostToDevice, c->stream));
             LAUNCH(k1d_grad_prox, dim3(rows, B), dim3(T1), c->n, (const double *)c->u_hist, (const double *)c->r_hist, hs1(c),
-                    (const double *)c->alpha_dev, O.b3, O.kappa_sparsity, O.u_min, O.u_max, c->u_trial, c->chg_dev);
+                    (const double *)c->alpha_dev, (const double *)c->opt_tab, OPT1_STRIDE, c->u_trial, c->chg_dev);
             VCHCHK(fwd1_core(c, c->u_trial, rows, c->phi_trial, c->skip_dev));
             VCHCHK(cost1_core(c, c->phi_trial, c->u_trial, rows, Jt.data(), raw.data()));
             VCHCHK(down(c, c->chg_host.data(), c->chg_dev, (size_t)B * rows * 2));
@@ -619,11 +680,12 @@ extern "C" int vch1d_pgd_iterate(vch1d_ctx *c, int n_iters, double *cost_out, do
                 ch.push_back(c_n);
                 if (k > 0 && std::fabs(ch[ch.size() - 1] - ch[ch.size() - 2]) < 1e-7) c->pgd_plateau[b]++;
                 else c->pgd_plateau[b] = 0;
+                const double alpha_max = c->opts[b].alpha_max;
                 if (c->pgd_plateau[b] >= 10) {
-                    c->pgd_alpha_prev[b] = std::min(O.alpha_max, a_k * 2.0);
+                    c->pgd_alpha_prev[b] = std::min(alpha_max, a_k * 2.0);
                     c->pgd_plateau[b] = 0;
                 } else {
-                    c->pgd_alpha_prev[b] = std::min(O.alpha_max, a_k * 1.2);
+                    c->pgd_alpha_prev[b] = std::min(alpha_max, a_k * 1.2);
                 }
                 VCHCHK(copy_traj1(c, c->u_hist, c->u_trial, b, rows));
                 if (change < 1e-5 && k > 10) {
@@ -663,6 +725,32 @@ extern "C" int vch1d_pgd_get(vch1d_ctx *c, int what, double *out) {
     if (!c->pgd_ready) return vch_fail(VCH_ERR_STATE, "vch1d_pgd_get: call vch1d_pgd_init first");
     const double *src = what == 0 ? c->u_hist : what == 1 ? c->phi_hist : what == 2 ? c->r_hist : c->phiQ;
     return down_hist(c, out, src, c->pgd_rows);
+}
+
+extern "C" int vch1d_pgd_kkt(vch1d_ctx *c, int refresh, double tol, int64_t *counts_out, double *stationarity_out) {
+    CTXCHK(c);
+    if (!c->pgd_ready) return vch_fail(VCH_ERR_STATE, "vch1d_pgd_kkt: call vch1d_pgd_init first");
+    ARGCHK(counts_out, "NULL counts_out");
+    if (!refresh && !c->pgd_r_valid)
+        return vch_fail(VCH_ERR_STATE, "vch1d_pgd_kkt: no adjoint sweep has run since vch1d_pgd_init (pass refresh != 0)");
+    const int B = c->B, rows = c->pgd_rows;
+    if (!(tol > 0)) tol = 1e-6;
+    if (refresh) {      // the adjoint of the resident state, as GD_1D.main() takes it after the loop; it stays in r
+        VCHCHK(backward1_core(c, rows));
+        c->pgd_r_valid = true;
+    }
+    LAUNCH(k1d_kkt, dim3(B), dim3(T1), c->n, rows, (const double *)c->u_hist, (const double *)c->r_hist, hs1(c),
+            (const double *)c->opt_tab, tol, c->kkt_cnt, c->kkt_nrm);
+    std::vector<long long> cnt(4 * (size_t)B);
+    std::vector<double> nh(2 * (size_t)B);
+    HIPCHK(hipMemcpyAsync(cnt.data(), c->kkt_cnt, sizeof(long long) * 4 * B, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(nh.data(), c->kkt_nrm, sizeof(double) * 2 * B, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int b = 0; b < B; ++b) {
+        for (int k = 0; k < 4; ++k) counts_out[4 * b + k] = (int64_t)cnt[4 * b + k];
+        if (stationarity_out) stationarity_out[b] = std::sqrt(nh[2 * b]) / (std::sqrt(nh[2 * b + 1]) + 1e-9);
+    }
+    return 0;
 }
 
 

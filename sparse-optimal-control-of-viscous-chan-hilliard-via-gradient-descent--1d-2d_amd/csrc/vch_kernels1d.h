@@ -472,14 +472,22 @@ __global__ __launch_bounds__(T1) void k1d_solve(SysArgs A0, int lvl, const doubl
 // ---------------------------------------------------------------------------------
 // persistent adjoint sweep (B1:48-126): rows = M+2 history rows; parameters are the frozen
 // defaults of B1:29-33 (passed in F).  p, q, r histories [B][rows][n] must be zero-initialised.
+// b1, b2 come from row blockIdx.x * opt_stride of a parameter table: the [B] table of vch1d_pgd_init_v (opt_stride =
+// OPT1_STRIDE) or the one row the function seam fills from its scalar arguments (opt_stride = 0).  The index is
+// wave-uniform, hence scalar loads, issued beside the kernel's other first loads; the arithmetic below is that of the
+// scalar form.
 // ---------------------------------------------------------------------------------
+constexpr int OPT1_STRIDE = 6;          // one row of the table: {b1, b2, b3, kappa_sparsity, u_min, u_max}
+enum { OPT1_B1 = 0, OPT1_B2, OPT1_B3, OPT1_KS, OPT1_UMIN, OPT1_UMAX };
+
 __global__ __launch_bounds__(T1) void k1d_backward(Phys1 F, int n, double h, int lvl, int rows,
                                                    const double *__restrict__ t, const double *__restrict__ phi,
                                                    const double *__restrict__ phiQ, const double *__restrict__ phiT,
-                                                   double b1, double b2, double *p, double *q, double *r,
-                                                   long hs, double *scratch) {
+                                                   const double *__restrict__ opt_tab, int opt_stride, double *p,
+                                                   double *q, double *r, long hs, double *scratch) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int b = blockIdx.x, tid = threadIdx.x;
+    const double b1 = opt_tab[b * opt_stride + OPT1_B1], b2 = opt_tab[b * opt_stride + OPT1_B2];
     const double a = 1.0 / (h * h);
     double *rhs = scratch + (long)b * NSCR1 * n, *x1 = rhs + n;
     const double *ph = phi + b * hs;
@@ -721,25 +729,66 @@ __global__ __launch_bounds__(T1) void k1d_cost(int n, int rows, const double *__
     }
 }
 
+// prox(u - alpha (r + b3 u)): gradient step (C1:99, C1:111), soft threshold alpha ks, box (G1:68-70)
+__device__ __forceinline__ double grad_prox1(double uu, double rr, double al, double b3, double ks, double umin, double umax) {
+    const double v = uu - al * (rr + b3 * uu);
+    const double sg = v > 0.0 ? 1.0 : (v < 0.0 ? -1.0 : 0.0);
+    return fmin(fmax(sg * fmax(fabs(v) - al * ks, 0.0), umin), umax);
+}
+
+// b3, ks, umin, umax: row blockIdx.y * opt_stride of the parameter table (see k1d_backward)
 __global__ __launch_bounds__(T1) void k1d_grad_prox(int n, const double *__restrict__ u, const double *__restrict__ r, long hs,
-                                                    const double *__restrict__ alpha, double b3, double ks, double umin,
-                                                    double umax, double *__restrict__ uout, double *__restrict__ chg) {
+                                                    const double *__restrict__ alpha, const double *__restrict__ opt_tab,
+                                                    int opt_stride, double *__restrict__ uout, double *__restrict__ chg) {
     __shared__ double s4[T1 / 64];
     const int row = blockIdx.x, b = blockIdx.y, rows = gridDim.x;
+    const double *ot = opt_tab + b * opt_stride;
+    const double b3 = ot[OPT1_B3], ks = ot[OPT1_KS], umin = ot[OPT1_UMIN], umax = ot[OPT1_UMAX];
     const long o = b * hs + (long)row * n;
     const double al = alpha[b];
     double d2 = 0, n2 = 0;
     for (int i = threadIdx.x; i < n; i += T1) {
         const double uu = u[o + i];
-        const double v = uu - al * (r[o + i] + b3 * uu);                 // C1:99, C1:111
-        const double sg = v > 0.0 ? 1.0 : (v < 0.0 ? -1.0 : 0.0);
-        const double un = fmin(fmax(sg * fmax(fabs(v) - al * ks, 0.0), umin), umax);    // G1:68-70
+        const double un = grad_prox1(uu, r[o + i], al, b3, ks, umin, umax);
         uout[o + i] = un;
         d2 += (un - uu) * (un - uu);
         n2 += uu * uu;
     }
     d2 = block_red<0>(d2, s4); n2 = block_red<0>(n2, s4);
     if (chg && threadIdx.x == 0) { chg[((long)b * rows + row) * 2] = d2; chg[((long)b * rows + row) * 2 + 1] = n2; }
+}
+
+// KKT sparsity statistic of one trajectory (verify_sparsity_condition, G1:115-147) and the two squared norms of the
+// stationarity measure ||prox_1(u) - u|| / (||u|| + 1e-9), prox_1 = grad_prox1 with alpha = 1.  grid = B workgroups of T1
+// threads, each striding over the rows * n nodes of its trajectory (the duplicated t = 0 row included).  A thread's counts
+// are integers below 2^31, their sums go through block_red as doubles, where integers up to 2^53 add exactly in any
+// order; the norms take block_red's fixed order.  Writes cnt [B][4] = {#|u| < tol, #|r| <= ks, #agree, #nodes} and
+// nrm [B][2] = {||prox_1(u) - u||^2, ||u||^2} and nothing else: the prox image is not stored.
+__global__ __launch_bounds__(T1) void k1d_kkt(int n, int rows, const double *__restrict__ u, const double *__restrict__ r,
+                                              long hs, const double *__restrict__ opt_tab, double tol,
+                                              long long *__restrict__ cnt, double *__restrict__ nrm) {
+    __shared__ double s4[T1 / 64];
+    const int b = blockIdx.x;
+    const double *ot = opt_tab + b * OPT1_STRIDE;
+    const double b3 = ot[OPT1_B3], ks = ot[OPT1_KS], umin = ot[OPT1_UMIN], umax = ot[OPT1_UMAX];
+    const long o = b * hs, tot = (long)rows * n;
+    int c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+    double d2 = 0, n2 = 0;
+    for (long i = threadIdx.x; i < tot; i += T1) {
+        const double uu = u[o + i], rr = r[o + i];
+        const bool zero = fabs(uu) < tol, small = fabs(rr) <= ks;
+        c0 += zero; c1 += small; c2 += (zero == small); c3 += 1;
+        const double un = grad_prox1(uu, rr, 1.0, b3, ks, umin, umax);
+        d2 += (un - uu) * (un - uu);
+        n2 += uu * uu;
+    }
+    const double s0 = block_red<0>((double)c0, s4), s1 = block_red<0>((double)c1, s4), s2 = block_red<0>((double)c2, s4),
+                 s3 = block_red<0>((double)c3, s4);
+    d2 = block_red<0>(d2, s4); n2 = block_red<0>(n2, s4);
+    if (threadIdx.x == 0) {
+        cnt[4 * b] = (long long)s0; cnt[4 * b + 1] = (long long)s1; cnt[4 * b + 2] = (long long)s2; cnt[4 * b + 3] = (long long)s3;
+        nrm[2 * b] = d2; nrm[2 * b + 1] = n2;
+    }
 }
 
 // phi_Q = (1 - t/T) phi_initial + (t/T) phi_T, phi_initial = history row 0 (build_targets_1d, G1:238-241)

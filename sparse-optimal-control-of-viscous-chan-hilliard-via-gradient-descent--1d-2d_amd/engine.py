@@ -589,8 +589,12 @@ class Engine1D:
         return self._sq(E)
 
     # -- device-resident PGD (G1:333-477) ----------------------------------------------------
-    def pgd_init(self, phi0, phi_T, t_hist, dt, opt, phi_Q=None, x=None):
-        """Uncontrolled march + targets + J0; t_hist has M+2 entries, dt M.  Returns J0 (B, 5)."""
+    def pgd_init(self, phi0, phi_T, t_hist, dt, opt, phi_Q=None, x=None, u0=None, alpha0=None):
+        """Initial march + targets + J0; t_hist has M+2 entries, dt M.  Returns J0 (B, 5).  `opt`: one parameter object
+        for the whole batch or a list / tuple of B (trajectory b runs with opt[b]: weights, sparsity parameter, box and
+        alpha_max).  `u0` (B, rows, N+1): start control (taken as given, not clipped; default zeros).  `alpha0` [B] or a
+        scalar: first step size, capped at each trajectory's alpha_max (default: alpha_max).  A single `opt` without
+        u0 / alpha0 goes through vch1d_pgd_init."""
         phi0, phi_T = self._fld(phi0, "phi0"), self._fld(phi_T, "phi_T_target")
         t_hist = np.ascontiguousarray(t_hist, dtype=np.float64)
         dt = np.ascontiguousarray(dt, dtype=np.float64)
@@ -599,12 +603,34 @@ class Engine1D:
             raise ValueError(f"dt must have len(t_hist) - 2 = {rows - 2} entries, got {dt.size}")
         pq = None if phi_Q is None else self._hist(phi_Q, rows, "phi_Q_target")
         x = np.ascontiguousarray(self.x if x is None else x, dtype=np.float64)
-        o = opt if isinstance(opt, OptParams) else make_opt(opt)
         J0 = np.empty((self.B, 5))
-        check(self.lib.vch1d_pgd_init(self.ctx, _dp(phi0), _dp(phi_T), _dp(pq), _dp(x), _dp(t_hist), rows, _dp(dt),
-                                      C.byref(o), _dp(J0)))
+        many = isinstance(opt, (list, tuple))
+        if not many and u0 is None and alpha0 is None:
+            o = opt if isinstance(opt, OptParams) else make_opt(opt)
+            check(self.lib.vch1d_pgd_init(self.ctx, _dp(phi0), _dp(phi_T), _dp(pq), _dp(x), _dp(t_hist), rows, _dp(dt),
+                                          C.byref(o), _dp(J0)))
+        else:
+            seq = list(opt) if many else [opt]
+            arr = (OptParams * len(seq))(*[o if isinstance(o, OptParams) else make_opt(o) for o in seq])
+            uu = None if u0 is None else self._hist(u0, rows, "u0")
+            al = None if alpha0 is None else np.ascontiguousarray(
+                np.broadcast_to(np.asarray(alpha0, dtype=np.float64), (self.B,)))
+            check(self.lib.vch1d_pgd_init_v(self.ctx, _dp(phi0), _dp(phi_T), _dp(pq), _dp(x), _dp(t_hist), rows, _dp(dt),
+                                            arr, len(seq), _dp(uu), _dp(al), _dp(J0)))
         self._pgd_rows = rows
         return J0
+
+    def pgd_kkt(self, refresh=True, tol=1e-6):
+        """KKT sparsity statistic `u* = 0 <=> |r*| <= kappa_sparsity` of the resident iterate, counted on the device.
+        refresh=True recomputes the adjoint of the resident state first; refresh=False takes the resident r (the adjoint of
+        the iterate before the last accepted step).  Returns dict(n_zero, n_small, n_match, total: int64 [B]; pct [B][3],
+        the three percentages of verify_sparsity_condition; stationarity [B] = ||prox_1(u) - u|| / (||u|| + 1e-9))."""
+        cnt = np.zeros((self.B, 4), dtype=np.int64)
+        stat = np.empty(self.B)
+        check(self.lib.vch1d_pgd_kkt(self.ctx, int(bool(refresh)), float(tol), cnt.ctypes.data_as(C.POINTER(C.c_int64)),
+                                     _dp(stat)))
+        return dict(n_zero=cnt[:, 0].copy(), n_small=cnt[:, 1].copy(), n_match=cnt[:, 2].copy(), total=cnt[:, 3].copy(),
+                    pct=100.0 * cnt[:, :3] / cnt[:, 3:4], stationarity=stat)
 
     def pgd_iterate(self, n_iters):
         n = int(n_iters)
