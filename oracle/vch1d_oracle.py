@@ -198,8 +198,20 @@ def newton_step(phi_old, mu_old, w_old, w_new, dt, P, h, solver="dense", return_
     `stats` (optional dict) accumulates the engine's counts under vch2d_oracle's names: "solves", "newton_its"
     (residual norms recorded, the initial one included), "armijo_trials" (trial points that pass the admissibility
     test, whose residual is evaluated), "failed_ls" (loops left through the line-search-failure return); and
-    appends the loop's last residual norm to "last_norms"."""
+    appends the loop's last residual norm to "last_norms".
+
+    Decision margins: "min_margin" is the smallest relative distance to its threshold over every comparison the loops
+    took -- |nR / NEWTON_TOL - 1| at each stop test, |max|phi_t| / (1 - DELTA_SEP) - 1| at each admissibility test,
+    |nt / ((1 - eta alpha) nR) - 1| at each Armijo test, and |amax| (relative to 1) where a finite amax is tested
+    against 0.  (min(1, 0.9 amax) is continuous in amax: no decision.)  Two correct implementations whose iterates
+    differ by much less than min_margin take the same path.  "exits" gets one tuple per loop: (kind, iterations,
+    halvings, capped) with kind "conv" | "maxit" | "failed_ls", iterations the residual norms recorded (this loop's
+    share of "newton_its": one more than its solves after "conv", equal to them otherwise), halvings the step
+    halvings of all its line searches, capped the iterations whose first step was cut by the ceiling 0.9 amax < 1."""
     pn, mn = phi_old.copy(), mu_old.copy()
+    margin = np.inf
+    halvings = capped = 0
+    kind = "maxit"
     n = pn.size
     wts_h = h * trapz_weights(n)
     L = lap_dense(n - 1, h) if solver == "dense" else None
@@ -213,7 +225,9 @@ def newton_step(phi_old, mu_old, w_old, w_new, dt, P, h, solver="dense", return_
         hist.append(nR)
         if k % 10 == 0 and not np.isfinite(np.dot(wts_h, R[n:])):
             raise RuntimeError("Non-finite mass_defect; check phi bounds/log regularization.")
+        margin = min(margin, abs(nR / NEWTON_TOL - 1.0))
         if nR < NEWTON_TOL:
+            kind = "conv"
             break
         if solver == "dense":
             J = jac_dense(pn, dt, P, L)
@@ -230,22 +244,31 @@ def newton_step(phi_old, mu_old, w_old, w_new, dt, P, h, solver="dense", return_
             a_pos = np.min((1 - DELTA_SEP - pn[pos]) / dphi[pos]) if np.any(pos) else np.inf
             a_neg = np.min((-1 + DELTA_SEP - pn[neg]) / dphi[neg]) if np.any(neg) else np.inf
             amax = min(a_pos, a_neg)
-        if not np.isfinite(amax) or amax <= 0:
+        if np.isfinite(amax):
+            margin = min(margin, abs(amax))
+        reset = not np.isfinite(amax) or amax <= 0
+        if reset:
             amax = 1.0
         alpha = min(1.0, 0.9 * amax)
+        capped += int(not reset and 0.9 * amax < 1.0)       # after a reset alpha = 0.9 comes from no ceiling
         ok = False
         for _ in range(12):
             pt, mt = pn + alpha * dphi, mn + alpha * dmu
+            margin = min(margin, abs(np.max(np.abs(pt)) / (1 - DELTA_SEP) - 1.0))
             if np.all(np.abs(pt) < 1 - DELTA_SEP):
                 ntrial += 1
                 Rt = np.concatenate([residual_phi(pt, phi_old, mt, mu_old, w_new, w_old, dt, P, h),
                                      residual_mu(pt, phi_old, mt, mu_old, dt, h)])
-                if np.linalg.norm(Rt) <= (1 - ARMIJO_ETA * alpha) * nR:
+                nt = np.linalg.norm(Rt)
+                margin = min(margin, abs(nt / ((1 - ARMIJO_ETA * alpha) * nR) - 1.0))
+                if nt <= (1 - ARMIJO_ETA * alpha) * nR:
                     pn, mn, ok = pt, mt, True
                     break
             alpha *= 0.5
+            halvings += 1
         if not ok:
             failed = True
+            kind = "failed_ls"
             break
     if stats is not None:
         stats["solves"] = stats.get("solves", 0) + nsolve
@@ -253,6 +276,8 @@ def newton_step(phi_old, mu_old, w_old, w_new, dt, P, h, solver="dense", return_
         stats["armijo_trials"] = stats.get("armijo_trials", 0) + ntrial
         stats["failed_ls"] = stats.get("failed_ls", 0) + int(failed)
         stats.setdefault("last_norms", []).append(hist[-1])
+        stats["min_margin"] = min(stats.get("min_margin", np.inf), float(margin))
+        stats.setdefault("exits", []).append((kind, len(hist), halvings, capped))
     return (pn, mn, hist) if return_history else (pn, mn)
 
 
@@ -558,6 +583,7 @@ def error_metrics(phi_hist, phi_Q, phi_T, x, t_hist):
 class PGDResult:
     costs: list = field(default_factory=list)
     alphas: list = field(default_factory=list)
+    alphas_used: list = field(default_factory=list)   # the step the accepted control was made with, see pgd
     trials: list = field(default_factory=list)
     tracking: list = field(default_factory=list)
     terminal: list = field(default_factory=list)
@@ -573,7 +599,10 @@ def pgd(P: Params1D, O: OptParams1D, n_iter=None, choice_t=1, choice_q=1, solver
     alpha_prev (beta 0.8, <=5 trials, G1:73-113); alpha growth 1.2, plateau (10 its,
     |dJ|<1e-7) -> 2.0; stop when the relative control change < 1e-5 and k > 10.
     `initial_phi` replaces the seeded initial state of every march (as in forward); `stats` accumulates the
-    counts of every march (forward's stats)."""
+    counts of every march (forward's stats) and "min_cost_gap", the smallest relative gap |c_trial - cost_k| / cost_k
+    over the acceptance tests c_trial < cost_k.  A search that runs out returns its fifth try, made with
+    alpha_prev 0.8^4, but reports a_k after one more `alpha *= 0.8` (G1:107-113); `alphas` keeps the reported values,
+    `alphas_used` the step each accepted control was really made with."""
     fwd = lambda u: forward(P, control=u, initial_phi=initial_phi, solver=solver, stats=stats)
     phi_k, x, t_hist = fwd(None)
     u_k = np.zeros_like(phi_k)
@@ -583,6 +612,11 @@ def pgd(P: Params1D, O: OptParams1D, n_iter=None, choice_t=1, choice_q=1, solver
     res = PGDResult(costs=[cost_k])
     alpha_prev, plateau = O.alpha_max, 0
     r_k = None
+
+    def gap(c):
+        if stats is not None:
+            stats["min_cost_gap"] = min(stats.get("min_cost_gap", np.inf), abs(c - cost_k) / cost_k)
+
     for k in range(O.max_iter if n_iter is None else n_iter):
         _, _, r_k = backward(phi_k, x, t_hist, O.b1, O.b2, phi_Q, phi_T, solver=solver)
         g = gradient(r_k, u_k, O.b3)
@@ -590,21 +624,25 @@ def pgd(P: Params1D, O: OptParams1D, n_iter=None, choice_t=1, choice_q=1, solver
                            O.u_min, O.u_max)
         phi_o, _, _ = fwd(u_o)
         c_o = cost(phi_o, u_o, phi_Q, phi_T, x, t_hist, *cargs)
+        gap(c_o)
         if c_o < cost_k:
             a_k, u_n, c_n, phi_n, nt = alpha_prev, u_o, c_o, phi_o, 1
+            a_used = alpha_prev
         else:
             alpha, nt = alpha_prev, 0
             for _ in range(5):
                 nt += 1
+                a_used = alpha
                 u_n = prox_project(gradient_step(u_k, g, alpha), alpha, O.kappa_sparsity,
                                    O.u_min, O.u_max)
                 phi_n, _, _ = fwd(u_n)
                 c_n = cost(phi_n, u_n, phi_Q, phi_T, x, t_hist, *cargs)
+                gap(c_n)
                 if c_n < cost_k:
                     break
                 alpha *= 0.8
             a_k = alpha
-        res.costs.append(c_n); res.alphas.append(a_k); res.trials.append(nt)
+        res.costs.append(c_n); res.alphas.append(a_k); res.trials.append(nt); res.alphas_used.append(a_used)
         e1, e2 = error_metrics(phi_n, phi_Q, phi_T, x, t_hist)
         res.tracking.append(e1); res.terminal.append(e2)
         if k > 0 and abs(res.costs[-1] - res.costs[-2]) < 1e-7:
