@@ -3,6 +3,7 @@
 // F1:329-336), contiguous on host and device alike.
 #include "vch_common.h"
 #include "vch_kernels1d.h"
+#include "vch_pgd.h"
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -35,13 +36,8 @@ struct vch1d_ctx {
     double *kkt_nrm = nullptr;             //                [B][2] squared norms
     double *phi0_dev = nullptr, *phi_trial = nullptr, *chg_dev = nullptr, *tp_dev = nullptr;
     int *skip_dev = nullptr;
-    std::vector<double> t_host, chg_host, pgd_cost, pgd_alpha_prev;
-    std::vector<std::vector<double>> pgd_cost_hist;
-    std::vector<int> pgd_plateau, pgd_k, pgd_done;
-    // error metrics of the driver loop (G1:425-450): squared target norms, RMS fallback scale, histories of the last iterate call
-    std::vector<double> pgd_denQ2, pgd_denT2, pgd_trk, pgd_trm;
-    double pgd_rms = 1.0;
-    int pgd_err_n = 0;
+    std::vector<double> t_host, chg_host;
+    vch_pgd_state pgd;                     // the line search's books and the error metrics of the driver loop (vch_pgd.h)
     // vch1d_second_order (lazy): its own copies of the base point, the direction and the grids, so that the call leaves
     // every resident buffer as it found it
     double *so_base = nullptr, *so_u = nullptr, *so_pq = nullptr, *so_h = nullptr, *so_d1 = nullptr, *so_d2 = nullptr;   // [B][Mmax+2][n]
@@ -507,21 +503,14 @@ extern "C" int vch1d_pgd_init_v(vch1d_ctx *c, const double *phi0, const double *
     const int B = c->B, M = rows - 2;
     for (int k = 0; k < M; ++k) ARGCHK(dt[k] > 0, "dt must be positive");
     // all of this before anything is copied or launched, or any resident state changes
-    for (int b = 0; b < B; ++b) {
-        const vch_opt_params &o = opts[n_opts == 1 ? 0 : b];
-        const char *bad = nullptr;
-        if (!std::isfinite(o.b1) || !std::isfinite(o.b2) || !std::isfinite(o.b3)) bad = "b1, b2, b3 must be finite";
-        else if (!std::isfinite(o.kappa_sparsity) || o.kappa_sparsity < 0) bad = "kappa_sparsity must be finite and >= 0";
-        else if (!(o.alpha_max > 0)) bad = "alpha_max must be > 0";
-        else if (std::isnan(o.u_min) || std::isnan(o.u_max) || o.u_min > o.u_max) bad = "u_min must be <= u_max";
-        else if (alpha0 && !(std::isfinite(alpha0[b]) && alpha0[b] > 0)) bad = "alpha0 must be finite and > 0";
-        if (bad) return vch_fail(VCH_ERR_ARG, "vch1d_pgd_init_v: trajectory %d: %s", b, bad);
-    }
+    for (int b = 0; b < B; ++b)
+        if (const char *bad = vch_pgd_check(opts, n_opts, alpha0, b))
+            return vch_fail(VCH_ERR_ARG, "vch1d_pgd_init_v: trajectory %d: %s", b, bad);
     c->opts.resize(B);
     std::vector<double> &tab = c->opt_tab_host;
     tab.assign((size_t)B * OPT1_STRIDE, 0.0);
     for (int b = 0; b < B; ++b) {
-        const vch_opt_params &o = c->opts[b] = opts[n_opts == 1 ? 0 : b];
+        const vch_opt_params &o = c->opts[b] = vch_pgd_opt(opts, n_opts, b);
         double *row = tab.data() + (size_t)b * OPT1_STRIDE;
         row[OPT1_B1] = o.b1; row[OPT1_B2] = o.b2; row[OPT1_B3] = o.b3;
         row[OPT1_KS] = o.kappa_sparsity; row[OPT1_UMIN] = o.u_min; row[OPT1_UMAX] = o.u_max;
@@ -567,23 +556,13 @@ extern "C" int vch1d_pgd_init_v(vch1d_ctx *c, const double *phi0, const double *
     }
     std::vector<double> J(5 * B);
     VCHCHK(cost1_core(c, c->phi_hist, c->u_hist, rows, J.data()));
-    c->pgd_denQ2.assign(B, 0.0);
-    c->pgd_denT2.assign(B, 0.0);
-    VCHCHK(l2sq1_core(c, c->phiQ, hs1(c), rows, c->pgd_denQ2.data()));
-    VCHCHK(l2sq1_core(c, c->phiT, c->n, 1, c->pgd_denT2.data()));
-    c->pgd_rms = std::sqrt(std::max(x[c->n - 1] - x[0], 1e-30) * std::max(t_hist[rows - 1] - t_hist[0], 1e-30));
-    c->pgd_err_n = 0;
-    c->pgd_cost.assign(B, 0.0);
-    for (int b = 0; b < B; ++b) c->pgd_cost[b] = J[5 * b + 4];
+    c->pgd.denQ2.assign(B, 0.0);
+    c->pgd.denT2.assign(B, 0.0);
+    VCHCHK(l2sq1_core(c, c->phiQ, hs1(c), rows, c->pgd.denQ2.data()));
+    VCHCHK(l2sq1_core(c, c->phiT, c->n, 1, c->pgd.denT2.data()));
+    c->pgd.rms = std::sqrt(std::max(x[c->n - 1] - x[0], 1e-30) * std::max(t_hist[rows - 1] - t_hist[0], 1e-30));
+    c->pgd.reset(B, J.data(), c->opts.data(), alpha0);
     if (J0_out) memcpy(J0_out, J.data(), sizeof(double) * 5 * B);
-    c->pgd_alpha_prev.resize(B);
-    for (int b = 0; b < B; ++b)           // the first alpha_prev: alpha_max (G1 start), or the caller's, capped at alpha_max
-        c->pgd_alpha_prev[b] = alpha0 ? std::min(alpha0[b], c->opts[b].alpha_max) : c->opts[b].alpha_max;
-    c->pgd_plateau.assign(B, 0);
-    c->pgd_k.assign(B, 0);
-    c->pgd_done.assign(B, 0);
-    c->pgd_cost_hist.assign(B, std::vector<double>());
-    for (int b = 0; b < B; ++b) c->pgd_cost_hist[b].push_back(c->pgd_cost[b]);
     c->pgd_ready = true;
     return 0;
 }
@@ -604,8 +583,8 @@ extern "C" int vch1d_pgd_iterate(vch1d_ctx *c, int n_iters, double *cost_out, do
     if (!c->pgd_ready) return vch_fail(VCH_ERR_STATE, "vch1d_pgd_iterate: call vch1d_pgd_init first");
     ARGCHK(n_iters >= 1, "n_iters must be >= 1");
     const int B = c->B, rows = c->pgd_rows;
-    constexpr int MAX_LS = 5;                 // G1:74
-    constexpr double LS_BETA = 0.8;
+    constexpr vch_pgd_rule R = VCH_PGD_1D;
+    vch_pgd_state &st = c->pgd;
     double sec[3] = {0, 0, 0};                // backward, optimistic round, backtracking rounds
     auto tick = [&](hipEvent_t e) { return hipEventRecord(e, c->stream); };
     auto lap = [&]() {
@@ -614,33 +593,23 @@ extern "C" int vch1d_pgd_iterate(vch1d_ctx *c, int n_iters, double *cost_out, do
         hipEventElapsedTime(&ms, c->ev0, c->ev1);
         return (double)ms * 1e-3;
     };
-    std::vector<double> alpha(B), Jt(5 * B), raw(2 * B);
-    std::vector<int> accepted(B), trials(B);
-    c->pgd_err_n = n_iters;
-    c->pgd_trk.assign((size_t)B * n_iters, std::nan(""));
-    c->pgd_trm.assign((size_t)B * n_iters, std::nan(""));
+    std::vector<double> Jt(5 * B), raw(2 * B);
+    st.begin_call(n_iters);
     int done_iters = 0;
     for (int it = 0; it < n_iters; ++it) {
-        bool all_done = true;
-        for (int b = 0; b < B; ++b) all_done &= (c->pgd_done[b] != 0);
-        if (all_done) break;
+        if (!st.begin_iteration()) break;
         // --- adjoint sweep (G1:356); only r is consumed
         HIPCHK(tick(c->ev0));
         VCHCHK(backward1_core(c, rows));
         c->pgd_r_valid = true;
         HIPCHK(tick(c->ev1));
         sec[0] += lap();
-        for (int b = 0; b < B; ++b) {
-            alpha[b] = c->pgd_alpha_prev[b];
-            accepted[b] = c->pgd_done[b] ? 1 : 0;
-            trials[b] = 0;
-        }
         // round 0: optimistic step with alpha_prev (G1:365-372), which is also the first trial of the line
-        // search (alpha_init = alpha_prev, G1:383) -- that repetition is not recomputed; rounds 1..4: alpha *= 0.8
-        for (int round = 0; round < MAX_LS; ++round) {
+        // search (alpha_init = alpha_prev, G1:383) -- that repetition is not recomputed; later rounds: alpha *= beta
+        for (int round = 0; round < R.rounds; ++round) {
             HIPCHK(tick(c->ev0));
-            VCHCHK(up(c, c->alpha_dev, alpha.data(), B));
-            HIPCHK(hipMemcpyAsync(c->skip_dev, accepted.data(), sizeof(int) * B, hipMemcpyHostToDevice, c->stream));
+            VCHCHK(up(c, c->alpha_dev, st.alpha.data(), B));
+            HIPCHK(hipMemcpyAsync(c->skip_dev, st.accepted.data(), sizeof(int) * B, hipMemcpyHostToDevice, c->stream));
             LAUNCH(k1d_grad_prox, dim3(rows, B), dim3(T1), c->n, (const double *)c->u_hist, (const double *)c->r_hist, hs1(c),
                     (const double *)c->alpha_dev, (const double *)c->opt_tab, OPT1_STRIDE, c->u_trial, c->chg_dev);
             VCHCHK(fwd1_core(c, c->u_trial, rows, c->phi_trial, c->skip_dev));
@@ -650,55 +619,26 @@ extern "C" int vch1d_pgd_iterate(vch1d_ctx *c, int n_iters, double *cost_out, do
             sec[round == 0 ? 1 : 2] += lap();
             bool pending = false;
             for (int b = 0; b < B; ++b) {
-                if (accepted[b]) continue;
-                trials[b] = round + 1;
-                const bool ok = Jt[5 * b + 4] < c->pgd_cost[b];
-                const bool last = (round == MAX_LS - 1);
-                if (!ok && !last) {
-                    alpha[b] *= LS_BETA;
-                    pending = true;
-                    continue;
-                }
-                accepted[b] = 1;
-                const double a_k = ok ? alpha[b] : alpha[b] * LS_BETA;     // G1:112-113 returns the once-more reduced step
-                const double c_n = Jt[5 * b + 4];
+                if (st.accepted[b]) continue;
                 double d2 = 0, n2 = 0;
                 for (int r = 0; r < rows; ++r) {
                     d2 += c->chg_host[((size_t)b * rows + r) * 2];
                     n2 += c->chg_host[((size_t)b * rows + r) * 2 + 1];
                 }
-                const double change = std::sqrt(d2) / (std::sqrt(n2) + 1e-9);
-                {   // relative tracking / terminal errors of the accepted state (G1:438-450)
-                    double denQ = std::sqrt(std::max(c->pgd_denQ2[b], 0.0));
-                    if (denQ < 1e-9 * c->pgd_rms) denQ = c->pgd_rms;
-                    c->pgd_trk[(size_t)b * n_iters + it] = std::sqrt(std::max(raw[2 * b], 0.0)) / (denQ + 1e-12);
-                    c->pgd_trm[(size_t)b * n_iters + it] =
-                        std::sqrt(std::max(raw[2 * b + 1], 0.0)) / (std::sqrt(std::max(c->pgd_denT2[b], 0.0)) + 1e-12);
-                }
-                const int k = c->pgd_k[b];
-                auto &ch = c->pgd_cost_hist[b];
-                ch.push_back(c_n);
-                if (k > 0 && std::fabs(ch[ch.size() - 1] - ch[ch.size() - 2]) < 1e-7) c->pgd_plateau[b]++;
-                else c->pgd_plateau[b] = 0;
-                const double alpha_max = c->opts[b].alpha_max;
-                if (c->pgd_plateau[b] >= 10) {
-                    c->pgd_alpha_prev[b] = std::min(alpha_max, a_k * 2.0);
-                    c->pgd_plateau[b] = 0;
-                } else {
-                    c->pgd_alpha_prev[b] = std::min(alpha_max, a_k * 1.2);
+                vch_pgd_step s;
+                const vch_pgd_verdict v =
+                    st.judge(R, b, it, round, c->opts[b].alpha_max, Jt[5 * b + 4], d2, n2, raw[2 * b], raw[2 * b + 1], s);
+                if (v == VCH_PGD_PENDING) {
+                    pending = true;
+                    continue;
                 }
                 VCHCHK(copy_traj1(c, c->u_hist, c->u_trial, b, rows));
-                if (change < 1e-5 && k > 10) {
-                    c->pgd_done[b] = 1;                 // G1:462-465: u_k taken, state and cost keep the previous iterate
-                } else {
-                    VCHCHK(copy_traj1(c, c->phi_hist, c->phi_trial, b, rows));
-                    c->pgd_cost[b] = c_n;
-                }
-                c->pgd_k[b] = k + 1;
-                if (cost_out) cost_out[(long)b * n_iters + it] = c_n;
-                if (alpha_out) alpha_out[(long)b * n_iters + it] = a_k;
-                if (trials_out) trials_out[(long)b * n_iters + it] = trials[b];
-                if (change_out) change_out[(long)b * n_iters + it] = change;
+                // G1:462-465: on a stop u_k is taken, the state (like the stored cost) keeps the previous iterate
+                if (!(v == VCH_PGD_STOP && R.stop_keeps_state)) VCHCHK(copy_traj1(c, c->phi_hist, c->phi_trial, b, rows));
+                if (cost_out) cost_out[(long)b * n_iters + it] = Jt[5 * b + 4];
+                if (alpha_out) alpha_out[(long)b * n_iters + it] = s.alpha_k;
+                if (trials_out) trials_out[(long)b * n_iters + it] = s.count;
+                if (change_out) change_out[(long)b * n_iters + it] = s.change;
             }
             HIPCHK(hipStreamSynchronize(c->stream));
             if (!pending) break;
@@ -712,10 +652,7 @@ extern "C" int vch1d_pgd_iterate(vch1d_ctx *c, int n_iters, double *cost_out, do
 extern "C" int vch1d_pgd_errors(vch1d_ctx *c, int n_iters, double *tracking_out, double *terminal_out) {
     CTXCHK(c);
     if (!c->pgd_ready) return vch_fail(VCH_ERR_STATE, "vch1d_pgd_errors: call vch1d_pgd_init first");
-    ARGCHK(n_iters == c->pgd_err_n && n_iters >= 1, "n_iters differs from the last vch1d_pgd_iterate call");
-    const size_t n = (size_t)c->B * n_iters;
-    if (tracking_out) memcpy(tracking_out, c->pgd_trk.data(), n * sizeof(double));
-    if (terminal_out) memcpy(terminal_out, c->pgd_trm.data(), n * sizeof(double));
+    ARGCHK(c->pgd.errors(n_iters, tracking_out, terminal_out), "n_iters differs from the last vch1d_pgd_iterate call");
     return 0;
 }
 
@@ -789,9 +726,8 @@ extern "C" int vch1d_second_order(vch1d_ctx *c, const double *phi_hist, const do
     }
     std::vector<double> wts(3 * (size_t)B);
     for (int b = 0; b < B; ++b) {
-        const vch_opt_params &o = opts[n_opts == 1 ? 0 : b];
-        if (!std::isfinite(o.b1) || !std::isfinite(o.b2) || !std::isfinite(o.b3))
-            return vch_fail(VCH_ERR_ARG, "%s: trajectory %d: b1, b2, b3 must be finite", fn, b);
+        const vch_opt_params &o = vch_pgd_opt(opts, n_opts, b);
+        if (const char *bad = vch_pgd_check_weights(opts, n_opts, b)) return vch_fail(VCH_ERR_ARG, "%s: trajectory %d: %s", fn, b, bad);
         wts[3 * b] = o.b1; wts[3 * b + 1] = o.b2; wts[3 * b + 2] = o.b3;
     }
     if (!phi_hist && (!c->phi_hist || c->rows_res != rows))

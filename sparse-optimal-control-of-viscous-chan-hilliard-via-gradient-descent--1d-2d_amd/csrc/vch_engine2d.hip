@@ -7,6 +7,7 @@
 #include "vch_kernels2d.h"
 #include "vch_gemm.h"
 #include "vch_fft.h"
+#include "vch_pgd.h"
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -206,14 +207,8 @@ struct vch2d_ctx {
     double *tan_part = nullptr, *tan_lvl = nullptr, *tan_t = nullptr, *tan_out = nullptr;
     int fwd_u_rows = 0;
     bool res_pgd = false;                 // the resident state history is the resident PGD problem's iterate
-    std::vector<double> pgd_cost, pgd_alpha_prev, pgd_J;    // per trajectory
-    std::vector<int> pgd_plateau, pgd_done, pgd_k;
-    std::vector<std::vector<double>> pgd_cost_hist;
-    // error metrics of the driver loop (G2:336-363): squared norms of the targets (once per problem), the RMS fallback
-    // scale, and the per-iteration histories of the last vch2d_pgd_iterate call ([B][pgd_err_n])
-    std::vector<double> pgd_denQ2, pgd_denT2, pgd_trk, pgd_trm;
-    double pgd_rms;
-    int pgd_err_n;
+    vch_pgd_state pgd;                    // the line search's books and the error metrics of the driver loop (vch_pgd.h)
+    std::vector<double> J_host;           // [B][5] cost terms of the accepted iterate, the source of J_dev and the ring
     double *J_dev;
     // cost scalars of the last J_RING iterations, [J_RING][B][5] on the device (slot = iteration index mod J_RING), so
     // that the collective of iteration k (vch_comm_allreduce_cost) reads iteration k's values even when the context
@@ -2129,18 +2124,11 @@ extern "C" int vch2d_pgd_init_v(vch2d_ctx *c, const double *phi0, const double *
     ARGCHK(phi0 && phi_T && t_hist && x && y && opts && M >= 1 && M <= c->Mmax, "NULL argument or M out of range");
     ARGCHK(n_opts == 1 || n_opts == c->B, "n_opts must be 1 or the context's batch");
     // all of this before anything is enqueued or any resident state changes
-    for (int b = 0; b < c->B; ++b) {
-        const vch_opt_params &o = opts[n_opts == 1 ? 0 : b];
-        const char *bad = nullptr;
-        if (!std::isfinite(o.b1) || !std::isfinite(o.b2) || !std::isfinite(o.b3)) bad = "b1, b2, b3 must be finite";
-        else if (!std::isfinite(o.kappa_sparsity) || o.kappa_sparsity < 0) bad = "kappa_sparsity must be finite and >= 0";
-        else if (!(o.alpha_max > 0)) bad = "alpha_max must be > 0";
-        else if (std::isnan(o.u_min) || std::isnan(o.u_max) || o.u_min > o.u_max) bad = "u_min must be <= u_max";
-        else if (alpha0 && !(std::isfinite(alpha0[b]) && alpha0[b] > 0)) bad = "alpha0 must be finite and > 0";
-        if (bad) return vch_fail(VCH_ERR_ARG, "vch2d_pgd_init_v: trajectory %d: %s", b, bad);
-    }
+    for (int b = 0; b < c->B; ++b)
+        if (const char *bad = vch_pgd_check(opts, n_opts, alpha0, b))
+            return vch_fail(VCH_ERR_ARG, "vch2d_pgd_init_v: trajectory %d: %s", b, bad);
     c->opts.resize(c->B);
-    for (int b = 0; b < c->B; ++b) c->opts[b] = opts[n_opts == 1 ? 0 : b];
+    for (int b = 0; b < c->B; ++b) c->opts[b] = vch_pgd_opt(opts, n_opts, b);
     VCHCHK(write_opt_tab(c, c->opt_tab, c->opts.data(), c->B));
     c->pgd_r_valid = false;
     c->t_hist.assign(t_hist, t_hist + M + 1);
@@ -2189,34 +2177,22 @@ extern "C" int vch2d_pgd_init_v(vch2d_ctx *c, const double *phi0, const double *
     c->M_res = M;
     c->res_pgd = false;
     c->shift_res = true;
-    c->pgd_J.assign(5 * c->B, 0.0);
+    c->J_host.assign(5 * c->B, 0.0);
     VCHCHK(cost_core(c, c->phi_hist, c->u_hist, (phi_Q || ramp) ? c->phiQ : nullptr, c->phiT, false, M, c->t_hist.data(),
-                     c->opts.data(), c->pgd_J.data(), nullptr, c->B));
+                     c->opts.data(), c->J_host.data(), nullptr, c->B));
     // target norms of the error metrics (G2:348-361)
-    c->pgd_denQ2.assign(c->B, 0.0);
-    c->pgd_denT2.assign(c->B, 0.0);
-    if (phi_Q || ramp) VCHCHK(l2sq_core(c, c->phiQ, hist_stride(c), M + 1, c->t_hist.data(), c->pgd_denQ2.data()));
-    VCHCHK(l2sq_core(c, c->phiT, c->G.plane, 1, nullptr, c->pgd_denT2.data()));
+    c->pgd.denQ2.assign(c->B, 0.0);
+    c->pgd.denT2.assign(c->B, 0.0);
+    if (phi_Q || ramp) VCHCHK(l2sq_core(c, c->phiQ, hist_stride(c), M + 1, c->t_hist.data(), c->pgd.denQ2.data()));
+    VCHCHK(l2sq_core(c, c->phiT, c->G.plane, 1, nullptr, c->pgd.denT2.data()));
     {
         const double area = (x[c->prm.Nx] - x[0]) * (y[c->prm.Ny] - y[0]), tl = t_hist[M] - t_hist[0];
-        c->pgd_rms = std::sqrt(std::max(area, 1e-30) * std::max(tl, 1e-30));
+        c->pgd.rms = std::sqrt(std::max(area, 1e-30) * std::max(tl, 1e-30));
     }
-    c->pgd_err_n = 0;
-    c->pgd_cost.resize(c->B);
-    c->pgd_alpha_prev.resize(c->B);
-    for (int b = 0; b < c->B; ++b)          // the first alpha_prev: alpha_max (G2:293), or the caller's, capped at alpha_max
-        c->pgd_alpha_prev[b] = alpha0 ? std::min(alpha0[b], c->opts[b].alpha_max) : c->opts[b].alpha_max;
-    c->pgd_plateau.assign(c->B, 0);
-    c->pgd_done.assign(c->B, 0);
-    c->pgd_k.assign(c->B, 0);
-    c->pgd_cost_hist.assign(c->B, {});
-    for (int b = 0; b < c->B; ++b) {
-        c->pgd_cost[b] = c->pgd_J[5 * b + 4];
-        c->pgd_cost_hist[b].push_back(c->pgd_cost[b]);
-    }
-    HIPCHK(hipMemcpyAsync(c->J_dev, c->pgd_J.data(), sizeof(double) * 5 * c->B, hipMemcpyHostToDevice, c->stream));
+    c->pgd.reset(c->B, c->J_host.data(), c->opts.data(), alpha0);
+    HIPCHK(hipMemcpyAsync(c->J_dev, c->J_host.data(), sizeof(double) * 5 * c->B, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (J0_out) memcpy(J0_out, c->pgd_J.data(), sizeof(double) * 5 * c->B);
+    if (J0_out) memcpy(J0_out, c->J_host.data(), sizeof(double) * 5 * c->B);
     c->pgd_iter_total = 0;
     c->pgd_ready = true;
     c->res_pgd = true;
@@ -2245,17 +2221,14 @@ extern "C" int vch2d_pgd_iterate(vch2d_ctx *c, int n_iters, double *cost_out, do
     const double *pq = (c->phiQ) ? c->phiQ : nullptr;
     double sec[5] = {0, 0, 0, 0, 0};
     hipEvent_t e0 = c->ev0, e1 = c->ev1;
-    std::vector<double> alpha(B), Jt(5 * B), chg(2 * B), alpha_k(B), cost_new(B), raw(2 * B);
-    std::vector<int> attempts(B), accepted(B);
+    constexpr vch_pgd_rule R = VCH_PGD_2D;
+    static_assert(!R.stop_keeps_state, "an accepted trial is taken whole, also on a stop");
+    vch_pgd_state &st = c->pgd;
+    std::vector<double> Jt(5 * B), chg(2 * B), raw(2 * B);
     int done_iters = 0;
-    const double nan_ = std::nan("");
-    c->pgd_err_n = n_iters;
-    c->pgd_trk.assign((size_t)B * n_iters, nan_);
-    c->pgd_trm.assign((size_t)B * n_iters, nan_);
+    st.begin_call(n_iters);
     for (int it = 0; it < n_iters; ++it) {
-        bool all_done = true;
-        for (int b = 0; b < B; ++b) all_done &= (c->pgd_done[b] != 0);
-        if (all_done) break;
+        if (!st.begin_iteration()) break;
         // --- adjoint sweep on the current state (G2:299)
         HIPCHK(hipEventRecord(e0, c->stream));
         {
@@ -2272,23 +2245,17 @@ extern "C" int vch2d_pgd_iterate(vch2d_ctx *c, int n_iters, double *cost_out, do
         }
         HIPCHK(hipEventRecord(e1, c->stream));
         sec[0] += elapsed_s(c, e0, e1);
-        // --- optimistic step with alpha_prev (G2:304-313)
-        for (int b = 0; b < B; ++b) {
-            alpha[b] = c->pgd_alpha_prev[b];
-            attempts[b] = 0;
-            accepted[b] = c->pgd_done[b] ? 1 : 0;
-        }
-        for (int round = 0; round <= 10; ++round) {
-            // round 0 = optimistic step; rounds 1..10 = backtracking trials (G2:128-146)
+        for (int round = 0; round < R.rounds; ++round) {
+            // round 0 = optimistic step with alpha_prev (G2:304-313); later rounds = backtracking trials (G2:128-146)
             HIPCHK(hipEventRecord(e0, c->stream));
-            VCHCHK(grad_prox_core(c, c->u_hist, c->r_hist, rows, alpha.data(), c->opt_tab, c->u_trial, chg.data()));
+            VCHCHK(grad_prox_core(c, c->u_hist, c->r_hist, rows, st.alpha.data(), c->opt_tab, c->u_trial, chg.data()));
             HIPCHK(hipEventRecord(e1, c->stream));
             sec[1] += elapsed_s(c, e0, e1);
             HIPCHK(hipEventRecord(e0, c->stream));
             HIPCHK(hipMemcpyAsync(c->phi_s, c->phi0, sizeof(double) * B * c->G.plane, hipMemcpyDeviceToDevice, c->stream));
             VCHCHK(reset_counters(c));
             // a trajectory whose step is already accepted (or that has stopped) sits the trial out
-            if (std::any_of(accepted.begin(), accepted.end(), [](int a) { return a != 0; })) VCHCHK(freeze(c, accepted));
+            if (std::any_of(st.accepted.begin(), st.accepted.end(), [](int a) { return a != 0; })) VCHCHK(freeze(c, st.accepted));
             VCHCHK(forward_core(c, c->u_trial, rows, c->dt.data(), M, c->phi_trial));
             HIPCHK(hipEventRecord(e1, c->stream));
             sec[round == 0 ? 2 : 4] += elapsed_s(c, e0, e1);
@@ -2298,52 +2265,22 @@ extern "C" int vch2d_pgd_iterate(vch2d_ctx *c, int n_iters, double *cost_out, do
             sec[round == 0 ? 3 : 4] += elapsed_s(c, e0, e1);
             bool pending = false;
             for (int b = 0; b < B; ++b) {
-                if (accepted[b]) continue;
-                if (round > 0) attempts[b]++;
-                const bool ok = Jt[5 * b + 4] < c->pgd_cost[b];
-                const bool last = (round == 10);
-                if (ok || last) {
-                    // accept (or "return last try", G2:144-146, where alpha has been multiplied once more)
-                    accepted[b] = 1;
-                    alpha_k[b] = (ok ? alpha[b] : alpha[b] * 0.8);
-                    cost_new[b] = Jt[5 * b + 4];
-                    if (change_out) change_out[(long)b * n_iters + it] = std::sqrt(chg[2 * b]) / (std::sqrt(chg[2 * b + 1]) + 1e-9);
-                    c->pgd_J[5 * b + 0] = Jt[5 * b + 0]; c->pgd_J[5 * b + 1] = Jt[5 * b + 1];
-                    c->pgd_J[5 * b + 2] = Jt[5 * b + 2]; c->pgd_J[5 * b + 3] = Jt[5 * b + 3];
-                    c->pgd_J[5 * b + 4] = Jt[5 * b + 4];
-                    {   // relative tracking / terminal errors of the accepted state (G2:348-361)
-                        double denQ = std::sqrt(std::max(c->pgd_denQ2[b], 0.0));
-                        if (denQ < 1e-9 * c->pgd_rms) denQ = c->pgd_rms;
-                        c->pgd_trk[(size_t)b * n_iters + it] = std::sqrt(std::max(raw[2 * b], 0.0)) / (denQ + 1e-12);
-                        c->pgd_trm[(size_t)b * n_iters + it] =
-                            std::sqrt(std::max(raw[2 * b + 1], 0.0)) / (std::sqrt(std::max(c->pgd_denT2[b], 0.0)) + 1e-12);
-                    }
-                    // the stop rule uses the relative control change (G2:375-381)
-                    const double change = std::sqrt(chg[2 * b]) / (std::sqrt(chg[2 * b + 1]) + 1e-9);
-                    VCHCHK(copy_traj(c, c->u_hist, c->u_trial, b, rows));
-                    VCHCHK(copy_traj(c, c->phi_hist, c->phi_trial, b, rows));
-                    VCHCHK(copy_traj_shifts(c, b));
-                    c->pgd_cost_hist[b].push_back(cost_new[b]);
-                    auto &ch = c->pgd_cost_hist[b];
-                    const int k = c->pgd_k[b];
-                    if (k > 0 && std::fabs(ch[ch.size() - 1] - ch[ch.size() - 2]) < 1e-5) c->pgd_plateau[b]++;
-                    else c->pgd_plateau[b] = 0;
-                    if (c->pgd_plateau[b] >= 5) {
-                        c->pgd_alpha_prev[b] = std::min(c->opts[b].alpha_max, alpha_k[b] * 1.5);
-                        c->pgd_plateau[b] = 0;
-                    } else {
-                        c->pgd_alpha_prev[b] = std::min(c->opts[b].alpha_max, alpha_k[b] * 1.2);
-                    }
-                    if (change < 1e-5 && k > 20) c->pgd_done[b] = 1;
-                    c->pgd_cost[b] = cost_new[b];
-                    c->pgd_k[b] = k + 1;
-                    if (cost_out) cost_out[(long)b * n_iters + it] = cost_new[b];
-                    if (alpha_out) alpha_out[(long)b * n_iters + it] = alpha_k[b];
-                    if (attempts_out) attempts_out[(long)b * n_iters + it] = attempts[b];
-                } else {
+                if (st.accepted[b]) continue;
+                vch_pgd_step s;     // the stop rule uses the relative control change (G2:375-381)
+                if (st.judge(R, b, it, round, c->opts[b].alpha_max, Jt[5 * b + 4], chg[2 * b], chg[2 * b + 1], raw[2 * b],
+                             raw[2 * b + 1], s) == VCH_PGD_PENDING) {
                     pending = true;
-                    alpha[b] = (round == 0) ? c->pgd_alpha_prev[b] * 0.8 : alpha[b] * 0.8;
+                    continue;
                 }
+                // accepted (or "return last try", G2:144-146)
+                std::copy_n(&Jt[5 * b], 5, &c->J_host[5 * b]);
+                VCHCHK(copy_traj(c, c->u_hist, c->u_trial, b, rows));
+                VCHCHK(copy_traj(c, c->phi_hist, c->phi_trial, b, rows));
+                VCHCHK(copy_traj_shifts(c, b));
+                if (cost_out) cost_out[(long)b * n_iters + it] = Jt[5 * b + 4];
+                if (alpha_out) alpha_out[(long)b * n_iters + it] = s.alpha_k;
+                if (attempts_out) attempts_out[(long)b * n_iters + it] = s.count;
+                if (change_out) change_out[(long)b * n_iters + it] = s.change;
             }
             if (!pending) break;
         }
@@ -2351,12 +2288,12 @@ extern "C" int vch2d_pgd_iterate(vch2d_ctx *c, int n_iters, double *cost_out, do
         done_iters = it + 1;
         {   // this iteration's cost scalars into the ring (read by the collective of this iteration)
             const size_t slot = (size_t)(c->pgd_iter_total.load(std::memory_order_relaxed) % J_RING) * 5 * B;
-            memcpy(c->J_ring_host + slot, c->pgd_J.data(), sizeof(double) * 5 * B);
+            memcpy(c->J_ring_host + slot, c->J_host.data(), sizeof(double) * 5 * B);
             HIPCHK(hipMemcpyAsync(c->J_ring_dev + slot, c->J_ring_host + slot, sizeof(double) * 5 * B, hipMemcpyHostToDevice, c->stream));
             c->pgd_iter_total.fetch_add(1, std::memory_order_release);
         }
     }
-    HIPCHK(hipMemcpyAsync(c->J_dev, c->pgd_J.data(), sizeof(double) * 5 * B, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->J_dev, c->J_host.data(), sizeof(double) * 5 * B, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (seconds_out) memcpy(seconds_out, sec, sizeof(sec));
     return done_iters;
@@ -2365,10 +2302,7 @@ extern "C" int vch2d_pgd_iterate(vch2d_ctx *c, int n_iters, double *cost_out, do
 extern "C" int vch2d_pgd_errors(vch2d_ctx *c, int n_iters, double *tracking_out, double *terminal_out) {
     CTXCHK(c);
     if (!c->pgd_ready) return vch_fail(VCH_ERR_STATE, "vch2d_pgd_errors: call vch2d_pgd_init first");
-    ARGCHK(n_iters == c->pgd_err_n && n_iters >= 1, "n_iters differs from the last vch2d_pgd_iterate call");
-    const size_t n = (size_t)c->B * n_iters;
-    if (tracking_out) memcpy(tracking_out, c->pgd_trk.data(), n * sizeof(double));
-    if (terminal_out) memcpy(terminal_out, c->pgd_trm.data(), n * sizeof(double));
+    ARGCHK(c->pgd.errors(n_iters, tracking_out, terminal_out), "n_iters differs from the last vch2d_pgd_iterate call");
     return 0;
 }
 
@@ -2537,11 +2471,9 @@ extern "C" int vch2d_second_order(vch2d_ctx *c, const double *h, int h_rows, con
     ARGCHK(n_opts == 1 || n_opts == c->B, "n_opts must be 1 or the context's batch");
     ARGCHK(order == 1 || order == 2, "order must be 1 or 2");
     ARGCHK(h_rows >= 1 && h_rows <= c->Mmax + 1, "direction rows out of range (1..max_steps+1)");
-    for (int b = 0; b < c->B; ++b) {
-        const vch_opt_params &o = opts[n_opts == 1 ? 0 : b];
-        if (!std::isfinite(o.b1) || !std::isfinite(o.b2) || !std::isfinite(o.b3))
-            return vch_fail(VCH_ERR_ARG, "vch2d_second_order: trajectory %d: b1, b2, b3 must be finite", b);
-    }
+    for (int b = 0; b < c->B; ++b)
+        if (const char *bad = vch_pgd_check_weights(opts, n_opts, b))
+            return vch_fail(VCH_ERR_ARG, "vch2d_second_order: trajectory %d: %s", b, bad);
     const bool pgd = c->pgd_ready && c->res_pgd;
     if (pgd) {
         ARGCHK(!phi_Q && !phi_T, "the resident problem's targets are used: pass phi_Q = phi_T = NULL");
