@@ -673,15 +673,30 @@ static int with_plan(const FftAxis &ax, F &&f) {
     return f(integral_constant<int, 4096>(), integral_constant<int, 0>());
 }
 
+// grid and block of the row kernels (vch_fft.h) for the plan (C, LG) of c->fax: a workgroup owns 2 C / L rows
+struct RowsDims { dim3 grid, block; };
+template <int C, int LG>
+static RowsDims rows_dims(const vch2d_ctx *c) {
+    const int rpw = 2 * (C >> c->fax.logL);
+    return {dim3((c->G.ns + rpw - 1) / rpw, 1, c->B), dim3(FftThreads<C, LG>::T)};
+}
+
 // k_dct_rows<EPI> (E along the fast axis): in -> out
 template <int EPI>
 static int dct_rows(vch2d_ctx *c, const double *in, long in_slot_stride, double *out, const SpecArgs &sp, int gate) {
     return with_plan(c->fax, [&](auto C, auto LG) {
-        const int rpw = 2 * (C >> c->fax.logL);
-        LAUNCHC(EPI >= 3 ? PC_DCT_R3 : PC_DCT_R0, (k_dct_rows<EPI, C, LG>), dim3((c->G.ns + rpw - 1) / rpw, 1, c->B),
-                dim3(FftThreads<C, LG>::T), c->G, c->fax, in, in_slot_stride, out, 1.0, sp, c->st, gate);
+        const RowsDims d = rows_dims<C, LG>(c);
+        LAUNCHC(EPI >= 3 ? PC_DCT_R3 : PC_DCT_R0, (k_dct_rows<EPI, C, LG>), d.grid, d.block, c->G, c->fax, in, in_slot_stride,
+                out, 1.0, sp, c->st, gate);
         return 0;
     });
+}
+// the same by the half-size DCT (k_dcth_rows, opt-in)
+template <int EPI>
+static int dcth_rows(vch2d_ctx *c, const double *in, long in_slot_stride, double *out, const SpecArgs &sp, int gate) {
+    LAUNCHC(EPI == 3 ? PC_DCT_R3 : PC_DCT_R0, (k_dcth_rows<EPI>), dim3((c->G.ns + 3) / 4, 1, c->B), dim3(HT), c->G, c->fax,
+            c->fax_h, in, in_slot_stride, out, 1.0, sp, c->st, gate);
+    return 0;
 }
 
 // k_dct_cols (E along the slow axis, spectral multiplier, E again): c->t1 -> c->t2
@@ -704,10 +719,9 @@ static int dct_cols(vch2d_ctx *c, const SpecArgs &sp, double scale, int gate) {
 // first pass of a stencil-free forward CG sweep (k_cg_rows_fwd): E_rows(Delta p) -> c->t1
 static int cg_rows(vch2d_ctx *c, const CgSweepArgs &a, bool first) {
     return with_plan(c->fax, [&](auto C, auto LG) {
-        const int rpw = 2 * (C >> c->fax.logL);
+        const RowsDims d = rows_dims<C, LG>(c);
         auto k_rows = first ? k_cg_rows_fwd<1, C, LG> : k_cg_rows_fwd<0, C, LG>;
-        LAUNCHC(first ? PC_CG_ROWS1 : PC_CG_ROWS, k_rows, dim3((c->G.ns + rpw - 1) / rpw, 1, c->B), dim3(FftThreads<C, LG>::T),
-                c->G, c->fax, a, c->t1, c->st);
+        LAUNCHC(first ? PC_CG_ROWS1 : PC_CG_ROWS, k_rows, d.grid, d.block, c->G, c->fax, a, c->t1, c->st);
         return 0;
     });
 }
@@ -715,10 +729,10 @@ static int cg_rows(vch2d_ctx *c, const CgSweepArgs &a, bool first) {
 // row kernel of a reduction-free sweep (k_cheb_rows): c->t2 -> c->t1
 static int cheb_rows(vch2d_ctx *c, const ChebSweepArgs &a, bool first) {
     return with_plan(c->fax, [&](auto C, auto LG) {
-        const int rpw = 2 * (C >> c->fax.logL);
+        const RowsDims d = rows_dims<C, LG>(c);
         auto k_rows = first ? k_cheb_rows<C, LG, 1> : k_cheb_rows<C, LG, 0>;
-        LAUNCHC(first ? PC_CHEB_ROWS0 : PC_CHEB_ROWS, k_rows, dim3((c->G.ns + rpw - 1) / rpw, 1, c->B), dim3(FftThreads<C, LG>::T),
-                c->G, c->fax, a, (const double *)c->t2, c->t1, (const TrajState *)c->st);
+        LAUNCHC(first ? PC_CHEB_ROWS0 : PC_CHEB_ROWS, k_rows, d.grid, d.block, c->G, c->fax, a, (const double *)c->t2, c->t1,
+                (const TrajState *)c->st);
         return 0;
     });
 }
@@ -726,10 +740,9 @@ static int cheb_rows(vch2d_ctx *c, const ChebSweepArgs &a, bool first) {
 // first pass of an adjoint CG sweep (k_adj_rows_fwd): -> c->t1
 static int adj_rows(vch2d_ctx *c, const AdjSweepArgs &a, bool first) {
     return with_plan(c->fax, [&](auto C, auto LG) {
-        const int rpw = 2 * (C >> c->fax.logL);
+        const RowsDims d = rows_dims<C, LG>(c);
         auto k_rows = first ? k_adj_rows_fwd<1, C, LG> : k_adj_rows_fwd<0, C, LG>;
-        LAUNCHC(PC_ADJ_Q, k_rows, dim3((c->G.ns + rpw - 1) / rpw, 1, c->B), dim3(FftThreads<C, LG>::T), c->G, c->fax, a, c->t1,
-                c->st);
+        LAUNCHC(PC_ADJ_Q, k_rows, d.grid, d.block, c->G, c->fax, a, c->t1, c->st);
         return 0;
     });
 }
@@ -747,18 +760,15 @@ static int precond(vch2d_ctx *c, const double *in, long in_slot_stride, double *
     SpecArgs sp{c0, c1a, c1b, c2, c->ms, c->mf, other, c->D_s, c->slot_stride, c->gpart, c->gpart2, 0};
     if (c->use_fft) {
         const double scale = 1.0 / (4.0 * (double)c->fax.N * (double)c->sax.N);
-#define DCTH_ROWS(EPI_, in_, iss_, out_)                                                                        \
-    LAUNCHC(((EPI_) == 3 ? PC_DCT_R3 : PC_DCT_R0), (k_dcth_rows<EPI_>), dim3((ns + 3) / 4, 1, c->B), dim3(HT), G, c->fax, c->fax_h, in_, iss_, out_, 1.0, sp, \
-            c->st, gate)
-        if (c->half_f) DCTH_ROWS(0, in, in_slot_stride, c->t1);
+        if (c->half_f) VCHCHK(dcth_rows<0>(c, in, in_slot_stride, c->t1, sp, gate));
         else VCHCHK(dct_rows<0>(c, in, in_slot_stride, c->t1, sp, gate));
         if (c->half_s)
             LAUNCHC(PC_DCT_C, k_dcth_cols, dim3((nf + 3) / 4, 1, c->B), dim3(HT), G, c->sax, c->sax_h, (const double *)c->t1, c->t2,
                     scale, sp, c->st, gate);
         else VCHCHK(dct_cols(c, sp, scale, gate));
         if (c->half_f) {
-            if (last == 3) DCTH_ROWS(3, (const double *)c->t2, 0L, out);
-            else DCTH_ROWS(0, (const double *)c->t2, 0L, out);
+            if (last == 3) VCHCHK(dcth_rows<3>(c, c->t2, 0L, out, sp, gate));
+            else VCHCHK(dcth_rows<0>(c, c->t2, 0L, out, sp, gate));
         } else if (last == 3) VCHCHK(dct_rows<3>(c, c->t2, 0L, out, sp, gate));
         else if (last == 4) VCHCHK(dct_rows<4>(c, c->t2, 0L, out, sp, gate));
         else VCHCHK(dct_rows<0>(c, c->t2, 0L, out, sp, gate));

@@ -19,10 +19,24 @@
 //     in registers (Emit) instead of going through the image.
 // Twiddles come from a table of exp(-2 pi i m / L) computed in long double on the host.
 //
-//   k_dct_rows : E along the fast (contiguous) axis for 2 NFFT rows; optional epilogue
-//                (weighted dot partial for the CG scalars)
-//   k_dct_cols : E along the slow axis for 2 NFFT columns, spectral multiplier, E again (the
-//                forward and the backward slow-axis transforms fused: one load, one store)
+//   k_dct_rows        : E along the fast (contiguous) axis for 2 NFFT rows; optional epilogue
+//                       (weighted dot partials for the CG scalars)
+//   k_cg_rows_fwd     : first pass of a forward CG sweep: reduction point, CG update, E_rows(Delta p')
+//   k_cheb_rows       : row kernel of a reduction-free (Chebyshev) sweep: E_rows, update, E_rows
+//   k_adj_rows_fwd    : first pass of an adjoint CG sweep: reduction point, CG update, E_rows(ph')
+//   k_dmu_ceiling_fin : end of a stencil-free forward solve fused with the back substitution (a stencil-tile kernel)
+//   k_fin_adj_step    : reduction point of the last enqueued adjoint sweep
+//   k_dct_cols        : E along the slow axis for 2 NFFT columns, spectral multiplier, E again (the
+//                       forward and the backward slow-axis transforms fused: one load, one store)
+//   k_dcth_rows / k_dcth_cols : the same two passes for N = 512 by a half-size real FFT (opt-in, no part of the scaffold)
+//
+// The four row kernels share ONE scaffold (the rows_* helpers below fft_lds).  Workgroup blockIdx.x owns the rows from
+// row0 = 2 NFFT blockIdx.x of trajectory blockIdx.z; transform f takes rows row0 + 2f and row0 + 2f + 1 as real and
+// imaginary part, rows >= ns read as zero and are never written.  A pass stages entry j <= N of each row pair and its
+// mirror L - j into the image (rows_stage_plain / rows_stage_node; or the first FFT pass reads global memory, RowIngest),
+// runs fft_lds, hands entry k <= N of each transform to a per-node put(row, k, value) (from the last pass's registers,
+// RowEmit, or by a loop over the image, rows_unstage) and reduces its per-thread accumulators through the image
+// (rows_partials).  Only the per-node arithmetic (node / upd / put) and where the totals go differ between the kernels.
 #pragma once
 #include "vch_common.h"
 #include "vch_kernels2d.h"
@@ -276,6 +290,145 @@ __device__ __forceinline__ void fft_lds(double2 *buf, const FftAxis ax, Emit emi
     }
 }
 
+// ---- Row-pass scaffold (see the header).  Functors are taken by reference: the kernels' lambdas capture their
+// accumulators by reference.
+// Emit of a compile-time plan: entry k <= N of transform f is (E(a)_k, E(b)_k) of rows row0 + 2f, row0 + 2f + 1 (the
+// upper half of the spectrum is its mirror image and is dropped)
+template <int LOGL, class Put>
+struct RowEmit {
+    enum { ACTIVE = 1, TO_LDS = 0 };
+    Put &put_;
+    int row0_, ns_;
+    __device__ __forceinline__ void operator()(int idx, double2 v) const {
+        constexpr int LL = 1 << (LOGL ? LOGL : 1);
+        const int f = idx >> (LOGL ? LOGL : 1), k = idx & (LL - 1);
+        if (k <= LL / 2) {
+            const int ra = row0_ + 2 * f;
+            if (ra < ns_) put_(ra, k, v.x);
+            if (ra + 1 < ns_) put_(ra + 1, k, v.y);
+        }
+    }
+};
+// Ingest of a compile-time plan: entry i of the even extension of rows row0 + 2f, + 1 from global memory
+template <int LOGL>
+struct RowIngest {
+    enum { ACTIVE = 1 };
+    const double *ib_;
+    long pitch_;
+    int row0_, ns_;
+    __device__ __forceinline__ double2 operator()(int idx) const {
+        constexpr int LL = 1 << (LOGL ? LOGL : 1);
+        const int f = idx >> (LOGL ? LOGL : 1), i = idx & (LL - 1), m = i <= LL / 2 ? i : LL - i;
+        const int ra = row0_ + 2 * f;
+        const double *p = ib_ + (long)ra * pitch_ + m;
+        return make_double2(ra < ns_ ? p[0] : 0.0, ra + 1 < ns_ ? p[pitch_] : 0.0);
+    }
+};
+
+// Stage the image through node(row, m, owner), every node once (no second visit for the mirror half of the even extension).
+// A compile-time plan divides by the constant n1, a run-time length takes the float quotient.  The caller's barrier follows.
+template <int C, int LOGL, class Node>
+__device__ __forceinline__ void rows_stage_node(double2 *buf, int logL, int row0, Node &node) {
+    constexpr int T = FftThreads<C, LOGL>::T;
+    constexpr bool DIRECT = LOGL >= 9 && LOGL <= 11;
+    const int L = 1 << logL, N = L >> 1, nfft = C >> logL, n1 = N + 1;
+    const float inv_n1 = 1.0f / (float)n1;       // idx < 2^14: the float quotient is exact enough
+    for (int idx = threadIdx.x; idx < nfft * n1; idx += T) {
+        const int f = nfft == 1 ? 0 : (DIRECT ? idx / n1 : (int)(((float)idx + 0.5f) * inv_n1)), j = idx - f * n1;
+        const int ra = row0 + 2 * f;
+        const double2 v = make_double2(node(ra, j, true), node(ra + 1, j, true));
+        buf[swz<LOGL>(f * L + j)] = v;
+        if (j > 0 && j < N) buf[swz<LOGL>(f * L + L - j)] = v;
+    }
+}
+
+// the same from a plane in global memory (run-time lengths)
+template <int C, int LOGL>
+__device__ __forceinline__ void rows_stage_plain(double2 *buf, int logL, int row0, const double *ib, const Geom &G) {
+    auto node = [&](int row, int j, bool) { return row < G.ns ? ib[(long)row * G.pitch + j] : 0.0; };
+    rows_stage_node<C, LOGL>(buf, logL, row0, node);
+}
+
+// image -> put (run-time lengths): entry k <= N of transform rr / 2, real or imaginary part by the parity of rr
+template <int C, int LOGL, class Put>
+__device__ __forceinline__ void rows_unstage(const double2 *buf, int logL, int row0, int ns, Put &put) {
+    constexpr int T = FftThreads<C, LOGL>::T;
+    const int L = 1 << logL, N = L >> 1, nfft = C >> logL, n1 = N + 1;
+    const float inv_n1 = 1.0f / (float)n1;
+    for (int idx = threadIdx.x; idx < 2 * nfft * n1; idx += T) {
+        const int rr = nfft == 1 ? (idx >= n1 ? 1 : 0) : (int)(((float)idx + 0.5f) * inv_n1), k = idx - rr * n1;
+        const int row = row0 + rr;
+        if (row < ns) {
+            const double2 c = buf[swz<LOGL>((rr >> 1) * L + k)];
+            put(row, k, (rr & 1) ? c.y : c.x);
+        }
+    }
+}
+
+// The whole row pass of a CG sweep's first kernel: stage the image through node, then transform, outputs to put.
+// (Feeding the first FFT pass from global memory instead reads each operand twice; staging: -5 % on the march,
+// profiles/r02_fft_variants.txt.)
+template <int C, int LOGL, class Node, class Put>
+__device__ __forceinline__ void rows_node_transform(double2 *buf, const FftAxis &ax, int logL, int row0, int ns,
+                                                    Node &node, Put &put) {
+    rows_stage_node<C, LOGL>(buf, logL, row0, node);
+    __syncthreads();
+    if (LOGL >= 9 && LOGL <= 11) {
+        fft_lds<C, LOGL>(buf, ax, RowEmit<LOGL, Put>{put, row0, ns});
+    } else {
+        fft_lds<C, LOGL>(buf, ax);
+        rows_unstage<C, LOGL>(buf, logL, row0, ns, put);
+    }
+}
+
+// The two early exits of a CG sweep's reduction point (k_cg_rows_fwd, k_adj_rows_fwd).  The trajectory finished in an
+// earlier sweep: hand its state on to the other copy (one thread)
+__device__ __forceinline__ void ci_hand_on(TrajState &S, int rd, int wr) {
+    S.ci_active[wr] = 0;
+    S.ci_it[wr] = S.ci_it[rd];
+    S.ci_gamma[wr] = S.ci_gamma[rd];
+}
+// Converged at this point: only the step dst += alpha src over the workgroup's rows is left (dst, src: the trajectory's planes)
+template <int C, int LOGL>
+__device__ __forceinline__ void rows_axpy(double *dst, const double *src, double alpha, int logL, int row0, const Geom &G) {
+    constexpr int T = FftThreads<C, LOGL>::T;
+    const int nfft = C >> logL, n1 = ((1 << logL) >> 1) + 1;
+    for (int idx = threadIdx.x; idx < 2 * nfft * n1; idx += T) {
+        const int rr = idx / n1, k = idx - rr * n1, row = row0 + rr;
+        if (row < G.ns) {
+            const long o = (long)row * G.pitch + k;
+            dst[o] += alpha * src[o];
+        }
+    }
+}
+
+// End of a row kernel: the workgroup's totals of a sum and of a second value (OP2: none, a sum, or a minimum), through
+// the image (all threads call it; the image is dead afterwards).  Returns true on thread 0, where v1 / v2 then hold the
+// totals, combined in wave order w = 0 .. T/64 - 1.  RED_NONE reduces, stores and reads nothing for v2.
+enum { RED_NONE, RED_SUM, RED_MIN };
+template <int T, int OP2>
+__device__ __forceinline__ bool rows_partials(double2 *buf, double &v1, double &v2) {
+    const int tid = threadIdx.x;
+    v1 = wave_sum(v1);
+    if (OP2 != RED_NONE) v2 = OP2 == RED_MIN ? wave_min(v2) : wave_sum(v2);
+    __syncthreads();
+    double *sred = reinterpret_cast<double *>(buf);
+    if ((tid & 63) == 0) {
+        sred[tid >> 6] = v1;
+        if (OP2 != RED_NONE) sred[T / 64 + (tid >> 6)] = v2;
+    }
+    __syncthreads();
+    if (tid != 0) return false;
+    double t1 = 0.0, t2 = OP2 == RED_MIN ? 1e300 : 0.0;
+    for (int w = 0; w < T / 64; ++w) {
+        t1 += sred[w];
+        if (OP2 != RED_NONE) t2 = OP2 == RED_MIN ? fmin(t2, sred[T / 64 + w]) : t2 + sred[T / 64 + w];
+    }
+    v1 = t1;
+    v2 = t2;
+    return true;
+}
+
 // E along the fast axis.  EPI 0: out = scale * E(in);  EPI 3: same + per-workgroup partials of
 // sum W (D[slot] - dbar) (other ? other : out) * out  into sp.gpart[b * gridDim.x + blockIdx.x] and of
 // sum W (D[slot] - dbar) out * out into sp.gpart2[same];  EPI 4 (last pass of a CG sweep, see k_cg_rows_fwd):
@@ -290,22 +443,12 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_dct_rows(Geom G, F
     if (gate && !gate_open(st[b], gate)) return;
     __shared__ double2 buf[C];
     constexpr int T = FftThreads<C, LOGL>::T;
-    const int tid = threadIdx.x;
-    const int logL = LOGL ? LOGL : ax.logL, L = 1 << logL, N = L >> 1, nfft = C >> logL;
+    const int logL = LOGL ? LOGL : ax.logL, nfft = C >> logL;
     const int row0 = blockIdx.x * 2 * nfft;
     const double *ib = in + b * G.plane + (in_slot_stride ? st[b].slot * in_slot_stride : 0);
-    const int n1 = N + 1;
-    const float inv_n1 = 1.0f / (float)n1;       // idx < 2^14: the float quotient is exact enough
     constexpr bool DIRECT = LOGL >= 9 && LOGL <= 11;
     if (!DIRECT) {
-        for (int idx = tid; idx < nfft * n1; idx += T) {
-            const int f = nfft == 1 ? 0 : (int)(((float)idx + 0.5f) * inv_n1), j = idx - f * n1;
-            const int ra = row0 + 2 * f, rb = ra + 1;
-            double2 v = make_double2(ra < G.ns ? ib[(long)ra * G.pitch + j] : 0.0,
-                                     rb < G.ns ? ib[(long)rb * G.pitch + j] : 0.0);
-            buf[swz<LOGL>(f * L + j)] = v;
-            if (j > 0 && j < N) buf[swz<LOGL>(f * L + L - j)] = v;
-        }
+        rows_stage_plain<C, LOGL>(buf, logL, row0, ib, G);
         __syncthreads();
     }
     double dot = 0.0, dot2 = 0.0, dbar = 0.0;
@@ -339,67 +482,16 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_dct_rows(Geom G, F
         }
     };
     if (DIRECT) {
-        // the last pass hands its outputs over in registers: entry k <= N of transform f is (E(a)_k, E(b)_k) of rows
-        // row0 + 2f, row0 + 2f + 1 (the upper half of the spectrum is its mirror image and is dropped)
-        struct RowEmit {
-            enum { ACTIVE = 1, TO_LDS = 0 };
-            decltype(put) &put_;
-            int row0_, ns_;
-            __device__ __forceinline__ void operator()(int idx, double2 v) const {
-                constexpr int LL = 1 << (LOGL ? LOGL : 1);
-                const int f = idx >> (LOGL ? LOGL : 1), k = idx & (LL - 1);
-                if (k <= LL / 2) {
-                    const int ra = row0_ + 2 * f;
-                    if (ra < ns_) put_(ra, k, v.x);
-                    if (ra + 1 < ns_) put_(ra + 1, k, v.y);
-                }
-            }
-        };
-        // ... and the first pass takes its inputs (entry i of the even extension of rows row0 + 2f, + 1) from global memory
-        struct RowIngest {
-            enum { ACTIVE = 1 };
-            const double *ib_;
-            long pitch_;
-            int row0_, ns_;
-            __device__ __forceinline__ double2 operator()(int idx) const {
-                constexpr int LL = 1 << (LOGL ? LOGL : 1);
-                const int f = idx >> (LOGL ? LOGL : 1), i = idx & (LL - 1), m = i <= LL / 2 ? i : LL - i;
-                const int ra = row0_ + 2 * f;
-                const double *p = ib_ + (long)ra * pitch_ + m;
-                return make_double2(ra < ns_ ? p[0] : 0.0, ra + 1 < ns_ ? p[pitch_] : 0.0);
-            }
-        };
-        fft_lds<C, LOGL>(buf, ax, RowEmit{put, row0, G.ns}, RowIngest{ib, (long)G.pitch, row0, G.ns});
+        // the first pass reads global memory, the last pass hands its outputs over in registers
+        fft_lds<C, LOGL>(buf, ax, RowEmit<LOGL, decltype(put)>{put, row0, G.ns},
+                         RowIngest<LOGL>{ib, (long)G.pitch, row0, G.ns});
     } else {
         fft_lds<C, LOGL>(buf, ax);
-        for (int idx = tid; idx < 2 * nfft * n1; idx += T) {
-            const int rr = nfft == 1 ? (idx >= n1 ? 1 : 0) : (int)(((float)idx + 0.5f) * inv_n1), k = idx - rr * n1;
-            const int row = row0 + rr;
-            if (row < G.ns) {
-                const double2 c = buf[swz<LOGL>((rr >> 1) * L + k)];
-                put(row, k, (rr & 1) ? c.y : c.x);
-            }
-        }
+        rows_unstage<C, LOGL>(buf, logL, row0, G.ns, put);
     }
-    if (EPI >= 3) {
-        dot = wave_sum(dot);
-        dot2 = wave_sum(dot2);
-        __syncthreads();
-        double *sred = reinterpret_cast<double *>(buf);
-        if ((tid & 63) == 0) {
-            sred[tid >> 6] = dot;
-            sred[T / 64 + (tid >> 6)] = dot2;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            double tot = 0.0, tot2 = 0.0;
-            for (int w = 0; w < T / 64; ++w) {
-                tot += sred[w];
-                tot2 += sred[T / 64 + w];
-            }
-            sp.gpart[(long)b * gridDim.x + blockIdx.x] = tot;
-            sp.gpart2[(long)b * gridDim.x + blockIdx.x] = tot2;
-        }
+    if (EPI >= 3 && rows_partials<T, RED_SUM>(buf, dot, dot2)) {
+        sp.gpart[(long)b * gridDim.x + blockIdx.x] = dot;
+        sp.gpart2[(long)b * gridDim.x + blockIdx.x] = dot2;
     }
 }
 
@@ -527,8 +619,7 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_cg_rows_fwd(Geom G
     __shared__ double s3[4];
     constexpr int T = FftThreads<C, LOGL>::T;
     const int tid = threadIdx.x;
-    const int logL = LOGL ? LOGL : ax.logL, L = 1 << logL, N = L >> 1, nfft = C >> logL;
-    const int row0 = blockIdx.x * 2 * nfft, n1 = N + 1;
+    const int logL = LOGL ? LOGL : ax.logL, row0 = blockIdx.x * 2 * (C >> logL);
     const int rd = (a.it + 1) & 1, wr = a.it & 1;
     const long pb = b * G.plane;
     double alpha = 0.0, beta = 0.0;
@@ -560,11 +651,7 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_cg_rows_fwd(Geom G
         if (!active) return;
     } else {
         if (!st[b].ci_active[rd]) {
-            if (blockIdx.x == 0 && tid == 0) {             // hand the (finished) state on to the other copy
-                st[b].ci_active[wr] = 0;
-                st[b].ci_it[wr] = st[b].ci_it[rd];
-                st[b].ci_gamma[wr] = st[b].ci_gamma[rd];
-            }
+            if (blockIdx.x == 0 && tid == 0) ci_hand_on(st[b], rd, wr);
             return;
         }
         const double gamma0 = st[b].cg_gamma0, gamma_old = st[b].ci_gamma[rd], tol = st[b].lin_reltol;
@@ -575,14 +662,7 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_cg_rows_fwd(Geom G
         alpha = nx.alpha;
         beta = nx.beta;
         if (!nx.active) {                                  // converged (or broke down, alpha = 0): take the step only
-            if (!nx.breakdown)
-                for (int idx = tid; idx < 2 * nfft * n1; idx += T) {
-                    const int rr = idx / n1, k = idx - rr * n1, row = row0 + rr;
-                    if (row < G.ns) {
-                        const long o = pb + (long)row * G.pitch + k;
-                        a.x[o] += alpha * a.p_old[o];
-                    }
-                }
+            if (!nx.breakdown) rows_axpy<C, LOGL>(a.x + pb, a.p_old + pb, alpha, logL, row0, G);
             return;
         }
     }
@@ -619,66 +699,10 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_cg_rows_fwd(Geom G
     };
     double *ob = out + pb;
     auto put = [&](int row, int k, double e) { ob[(long)row * G.pitch + k] = e; };
-    constexpr bool DIRECT = LOGL >= 9 && LOGL <= 11;
-    if (DIRECT) {
-        struct Emit {
-            enum { ACTIVE = 1, TO_LDS = 0 };
-            decltype(put) &put_;
-            int row0_, ns_;
-            __device__ __forceinline__ void operator()(int idx, double2 v) const {
-                constexpr int LL = 1 << (LOGL ? LOGL : 1);
-                const int f = idx >> (LOGL ? LOGL : 1), k = idx & (LL - 1);
-                if (k <= LL / 2) {
-                    const int ra = row0_ + 2 * f;
-                    if (ra < ns_) put_(ra, k, v.x);
-                    if (ra + 1 < ns_) put_(ra + 1, k, v.y);
-                }
-            }
-        };
-        // every node once (no second visit for the mirror half of the even extension): stage the image, then transform
-        // (feeding the first FFT pass from global memory reads each operand twice; staging: -5 % on the march,
-        // profiles/r02_fft_variants.txt)
-        for (int idx = tid; idx < nfft * n1; idx += T) {
-            const int f = nfft == 1 ? 0 : idx / n1, j = idx - f * n1;
-            const int ra = row0 + 2 * f;
-            const double2 v = make_double2(node(ra, j, true), node(ra + 1, j, true));
-            buf[swz<LOGL>(f * L + j)] = v;
-            if (j > 0 && j < N) buf[swz<LOGL>(f * L + L - j)] = v;
-        }
-        __syncthreads();
-        fft_lds<C, LOGL>(buf, ax, Emit{put, row0, G.ns});
-    } else {
-        const float inv_n1 = 1.0f / (float)n1;
-        for (int idx = tid; idx < nfft * n1; idx += T) {
-            const int f = nfft == 1 ? 0 : (int)(((float)idx + 0.5f) * inv_n1), j = idx - f * n1;
-            const int ra = row0 + 2 * f;
-            const double2 v = make_double2(node(ra, j, true), node(ra + 1, j, true));
-            buf[swz<LOGL>(f * L + j)] = v;
-            if (j > 0 && j < N) buf[swz<LOGL>(f * L + L - j)] = v;
-        }
-        __syncthreads();
-        fft_lds<C, LOGL>(buf, ax);
-        for (int idx = tid; idx < 2 * nfft * n1; idx += T) {
-            const int rr = nfft == 1 ? (idx >= n1 ? 1 : 0) : (int)(((float)idx + 0.5f) * inv_n1), k = idx - rr * n1;
-            const int row = row0 + rr;
-            if (row < G.ns) {
-                const double2 c = buf[swz<LOGL>((rr >> 1) * L + k)];
-                put(row, k, (rr & 1) ? c.y : c.x);
-            }
-        }
-    }
-    if (!FIRST) {
-        acc = wave_sum(acc);
-        __syncthreads();
-        double *sred = reinterpret_cast<double *>(buf);
-        if ((tid & 63) == 0) sred[tid >> 6] = acc;
-        __syncthreads();
-        if (tid == 0) {
-            double tot = 0.0;
-            for (int w = 0; w < T / 64; ++w) tot += sred[w];
-            a.gpart3[((long)wr * a.nbatch + b) * gridDim.x + blockIdx.x] = tot;
-        }
-    }
+    rows_node_transform<C, LOGL>(buf, ax, logL, row0, G.ns, node, put);
+    double none = 0.0;
+    if (!FIRST && rows_partials<T, RED_NONE>(buf, acc, none))
+        a.gpart3[((long)wr * a.nbatch + b) * gridDim.x + blockIdx.x] = acc;
 }
 
 // =====================================================================================================
@@ -786,18 +810,6 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T), CHEB_MINW) void k_cheb_ro
     constexpr bool DIRECT = LOGL >= 9 && LOGL <= 11;
     if (DIRECT) {
         constexpr int LL = 1 << (LOGL ? LOGL : 1), LG = LOGL ? LOGL : 1;
-        struct RowIngest {
-            enum { ACTIVE = 1 };
-            const double *ib_;
-            long pitch_;
-            int row0_, ns_;
-            __device__ __forceinline__ double2 operator()(int idx) const {
-                const int f = idx >> LG, i = idx & (LL - 1), m = i <= LL / 2 ? i : LL - i;
-                const int ra = row0_ + 2 * f;
-                const double *p = ib_ + (long)ra * pitch_ + m;
-                return make_double2(ra < ns_ ? p[0] : 0.0, ra + 1 < ns_ ? p[pitch_] : 0.0);
-            }
-        };
         // the first transform's last pass hands its outputs to the update; what the update returns goes back into the
         // image as the even extension of the next transform's input (entry k and its mirror L - k from the same thread)
         struct UpdEmit {
@@ -819,31 +831,11 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T), CHEB_MINW) void k_cheb_ro
                 }
             }
         };
-        struct RowEmit {
-            enum { ACTIVE = 1, TO_LDS = 0 };
-            decltype(put) &put_;
-            int row0_, ns_;
-            __device__ __forceinline__ void operator()(int idx, double2 v) const {
-                const int f = idx >> LG, k = idx & (LL - 1);
-                if (k <= LL / 2) {
-                    const int ra = row0_ + 2 * f;
-                    if (ra < ns_) put_(ra, k, v.x);
-                    if (ra + 1 < ns_) put_(ra + 1, k, v.y);
-                }
-            }
-        };
-        fft_lds<C, LOGL>(buf, ax, UpdEmit{upd, buf, row0, G.ns, last}, RowIngest{ib, (long)G.pitch, row0, G.ns});
-        if (!last) fft_lds<C, LOGL>(buf, ax, RowEmit{put, row0, G.ns});
+        fft_lds<C, LOGL>(buf, ax, UpdEmit{upd, buf, row0, G.ns, last}, RowIngest<LOGL>{ib, (long)G.pitch, row0, G.ns});
+        if (!last) fft_lds<C, LOGL>(buf, ax, RowEmit<LOGL, decltype(put)>{put, row0, G.ns});
     } else {
         const float inv_n1 = 1.0f / (float)n1;
-        for (int idx = tid; idx < nfft * n1; idx += T) {
-            const int f = nfft == 1 ? 0 : (int)(((float)idx + 0.5f) * inv_n1), j = idx - f * n1;
-            const int ra = row0 + 2 * f;
-            const double2 v = make_double2(ra < G.ns ? ib[(long)ra * G.pitch + j] : 0.0,
-                                           ra + 1 < G.ns ? ib[(long)(ra + 1) * G.pitch + j] : 0.0);
-            buf[swz<LOGL>(f * L + j)] = v;
-            if (j > 0 && j < N) buf[swz<LOGL>(f * L + L - j)] = v;
-        }
+        rows_stage_plain<C, LOGL>(buf, logL, row0, ib, G);
         __syncthreads();
         fft_lds<C, LOGL>(buf, ax);
         // entry k <= N of a transform is read and rewritten by ONE thread, the entries above N are only written: no barrier
@@ -863,37 +855,14 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T), CHEB_MINW) void k_cheb_ro
         if (!last) {
             __syncthreads();
             fft_lds<C, LOGL>(buf, ax);
-            for (int idx = tid; idx < 2 * nfft * n1; idx += T) {
-                const int rr = nfft == 1 ? (idx >= n1 ? 1 : 0) : (int)(((float)idx + 0.5f) * inv_n1), k = idx - rr * n1;
-                const int row = row0 + rr;
-                if (row < G.ns) {
-                    const double2 c = buf[swz<LOGL>((rr >> 1) * L + k)];
-                    put(row, k, (rr & 1) ? c.y : c.x);
-                }
-            }
+            rows_unstage<C, LOGL>(buf, logL, row0, G.ns, put);
         }
     }
-    if (need_norm || last) {
-        acc = wave_sum(acc);
-        cmin = wave_min(cmin);
-        __syncthreads();
-        double *sred = reinterpret_cast<double *>(buf);
-        if ((tid & 63) == 0) {
-            sred[tid >> 6] = acc;
-            sred[T / 64 + (tid >> 6)] = cmin;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            double tot = 0.0, mn = 1e300;
-            for (int w = 0; w < T / 64; ++w) {
-                tot += sred[w];
-                mn = fmin(mn, sred[T / 64 + w]);
-            }
-            if (need_norm) a.gpart[(long)b * gridDim.x + blockIdx.x] = tot;
-            if (last) {
-                if (a.cell) CeilCell::fold(a.cell + b * CeilCell::STRIDE, mn);
-                else a.cmin[(long)b * gridDim.x + blockIdx.x] = mn;
-            }
+    if ((need_norm || last) && rows_partials<T, RED_MIN>(buf, acc, cmin)) {
+        if (need_norm) a.gpart[(long)b * gridDim.x + blockIdx.x] = acc;
+        if (last) {
+            if (a.cell) CeilCell::fold(a.cell + b * CeilCell::STRIDE, cmin);
+            else a.cmin[(long)b * gridDim.x + blockIdx.x] = cmin;
         }
     }
 }
@@ -925,35 +894,14 @@ struct AdjSweepArgs {
     double tol;
 };
 
-struct CgNextAdj {
-    int active, breakdown, it;
-    double alpha, beta, gamma, rel;
-};
-__device__ __forceinline__ CgNextAdj cg_next_adj(double pq, double qq, double gamma, double r2, double rhs_norm, int it_old,
+// the adjoint's form of cg_next: the same step, the stop test on ||r||_2 / ||rhs||_2 (see above)
+__device__ __forceinline__ CgNext cg_next_adj(double pq, double qq, double gamma, double r2, double rhs_norm, int it_old,
                                                  double tol, int maxit) {
-    CgNextAdj n;
-    n.it = it_old;
     const double rel_now = rhs_norm > 0.0 ? sqrt(fmax(r2, 0.0)) / rhs_norm : 0.0;
-    if (!(pq > 0.0) || !(gamma > 0.0)) {     // round-off level residual: stop here, no step
-        n.active = 0; n.breakdown = 1; n.alpha = 0.0; n.beta = 0.0; n.gamma = fmax(gamma, 0.0); n.rel = rel_now;
-        return n;
-    }
-    n.breakdown = 0;
-    n.alpha = gamma / pq;
-    double gn = n.alpha * n.alpha * qq - gamma;
-    if (gn > 1e-13 * gamma) {
-        n.beta = gn / gamma;
-    } else {                                  // prediction lost in cancellation: restart the direction
-        gn = 1e-13 * gamma;
-        n.beta = 0.0;
-    }
-    n.gamma = gn;
-    n.it = it_old + 1;
-    n.rel = sqrt(gn / gamma) * rel_now;
-    n.active = (n.rel > tol && n.it < maxit) ? 1 : 0;
-    return n;
+    return cg_step(pq, qq, gamma, it_old, tol, maxit, [&] { return rel_now; },
+                   [&](double gn) { return sqrt(gn / gamma) * rel_now; });
 }
-__device__ __forceinline__ void adj_record(TrajState &S, const CgNextAdj &n, int wr) {
+__device__ __forceinline__ void adj_record(TrajState &S, const CgNext &n, int wr) {
     S.cg_alpha = n.alpha;
     S.cg_beta = n.beta;
     S.cg_gamma = n.gamma;
@@ -1000,8 +948,8 @@ __global__ void k_fin_adj_step(TrajState *st, const double *__restrict__ gpart, 
     }
     adj_sums4<192>(gpart, gpart2, direct ? gpart3_rd : nullptr, gnblk, b, s4);
     if (threadIdx.x != 0) return;
-    const CgNextAdj n = cg_next_adj(s4[0], s4[1], direct ? s4[2] : S.ci_gamma[rd], direct ? s4[3] : S.aux[0], S.lin_r0,
-                                    S.ci_it[rd], S.lin_reltol, maxit);
+    const CgNext n = cg_next_adj(s4[0], s4[1], direct ? s4[2] : S.ci_gamma[rd], direct ? s4[3] : S.aux[0], S.lin_r0,
+                                 S.ci_it[rd], S.lin_reltol, maxit);
     adj_record(S, n, rd ^ 1);
     if (n.it > S.step_lin_max) S.step_lin_max = n.it;
     S.cg_pending = n.breakdown ? 0 : 1;
@@ -1017,8 +965,7 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_adj_rows_fwd(Geom 
     __shared__ double s4[4];
     constexpr int T = FftThreads<C, LOGL>::T;
     const int tid = threadIdx.x;
-    const int logL = LOGL ? LOGL : ax.logL, L = 1 << logL, N = L >> 1, nfft = C >> logL;
-    const int row0 = blockIdx.x * 2 * nfft, n1 = N + 1;
+    const int logL = LOGL ? LOGL : ax.logL, row0 = blockIdx.x * 2 * (C >> logL);
     const int rd = (a.it + 1) & 1, wr = a.it & 1;
     const long pb = b * G.plane;
     double alpha = 0.0, beta = 0.0;
@@ -1071,18 +1018,14 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_adj_rows_fwd(Geom 
         if (!start) return;
     } else {
         if (!st[b].ci_active[rd]) {
-            if (blockIdx.x == 0 && tid == 0) {
-                st[b].ci_active[wr] = 0;
-                st[b].ci_it[wr] = st[b].ci_it[rd];
-                st[b].ci_gamma[wr] = st[b].ci_gamma[rd];
-            }
+            if (blockIdx.x == 0 && tid == 0) ci_hand_on(st[b], rd, wr);
             return;
         }
         const double gamma_old = st[b].ci_gamma[rd], tol = st[b].lin_reltol, r0sq = st[b].aux[0], rhsn = st[b].lin_r0;
         const int it_old = st[b].ci_it[rd], n = gridDim.x;
         adj_sums4<T>(a.gpart, a.gpart2, a.it >= 2 ? a.gpart3 + (long)rd * a.nbatch * n * 2 : nullptr, n, b, s4);
-        const CgNextAdj nx = cg_next_adj(s4[0], s4[1], a.it >= 2 ? s4[2] : gamma_old, a.it >= 2 ? s4[3] : r0sq, rhsn, it_old, tol,
-                                         a.maxit);
+        const CgNext nx = cg_next_adj(s4[0], s4[1], a.it >= 2 ? s4[2] : gamma_old, a.it >= 2 ? s4[3] : r0sq, rhsn, it_old, tol,
+                                      a.maxit);
         if (blockIdx.x == 0 && tid == 0) {
             adj_record(st[b], nx, wr);
             if (nx.it > st[b].step_lin_max) st[b].step_lin_max = nx.it;
@@ -1090,14 +1033,7 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_adj_rows_fwd(Geom 
         alpha = nx.alpha;
         beta = nx.beta;
         if (!nx.active) {
-            if (!nx.breakdown)
-                for (int idx = tid; idx < 2 * nfft * n1; idx += T) {
-                    const int rr = idx / n1, k = idx - rr * n1, row = row0 + rr;
-                    if (row < G.ns) {
-                        const long o = pb + (long)row * G.pitch + k;
-                        a.y[o] += alpha * a.p_old[o];
-                    }
-                }
+            if (!nx.breakdown) rows_axpy<C, LOGL>(a.y + pb, a.p_old + pb, alpha, logL, row0, G);
             return;
         }
     }
@@ -1130,74 +1066,11 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_adj_rows_fwd(Geom 
     };
     double *ob = out + pb;
     auto put = [&](int row, int k, double e) { ob[(long)row * G.pitch + k] = e; };
-    constexpr bool DIRECT = LOGL >= 9 && LOGL <= 11;
-    if (DIRECT) {
-        struct Emit {
-            enum { ACTIVE = 1, TO_LDS = 0 };
-            decltype(put) &put_;
-            int row0_, ns_;
-            __device__ __forceinline__ void operator()(int idx, double2 v) const {
-                constexpr int LL = 1 << (LOGL ? LOGL : 1);
-                const int f = idx >> (LOGL ? LOGL : 1), k = idx & (LL - 1);
-                if (k <= LL / 2) {
-                    const int ra = row0_ + 2 * f;
-                    if (ra < ns_) put_(ra, k, v.x);
-                    if (ra + 1 < ns_) put_(ra + 1, k, v.y);
-                }
-            }
-        };
-        // every node once (no second visit for the mirror half of the even extension): stage the image, then transform
-        // (feeding the first FFT pass from global memory reads each operand twice; staging: -5 % on the march,
-        // profiles/r02_fft_variants.txt)
-        for (int idx = tid; idx < nfft * n1; idx += T) {
-            const int f = nfft == 1 ? 0 : idx / n1, j = idx - f * n1;
-            const int ra = row0 + 2 * f;
-            const double2 v = make_double2(node(ra, j, true), node(ra + 1, j, true));
-            buf[swz<LOGL>(f * L + j)] = v;
-            if (j > 0 && j < N) buf[swz<LOGL>(f * L + L - j)] = v;
-        }
-        __syncthreads();
-        fft_lds<C, LOGL>(buf, ax, Emit{put, row0, G.ns});
-    } else {
-        const float inv_n1 = 1.0f / (float)n1;
-        for (int idx = tid; idx < nfft * n1; idx += T) {
-            const int f = nfft == 1 ? 0 : (int)(((float)idx + 0.5f) * inv_n1), j = idx - f * n1;
-            const int ra = row0 + 2 * f;
-            const double2 v = make_double2(node(ra, j, true), node(ra + 1, j, true));
-            buf[swz<LOGL>(f * L + j)] = v;
-            if (j > 0 && j < N) buf[swz<LOGL>(f * L + L - j)] = v;
-        }
-        __syncthreads();
-        fft_lds<C, LOGL>(buf, ax);
-        for (int idx = tid; idx < 2 * nfft * n1; idx += T) {
-            const int rr = nfft == 1 ? (idx >= n1 ? 1 : 0) : (int)(((float)idx + 0.5f) * inv_n1), k = idx - rr * n1;
-            const int row = row0 + rr;
-            if (row < G.ns) {
-                const double2 c = buf[swz<LOGL>((rr >> 1) * L + k)];
-                put(row, k, (rr & 1) ? c.y : c.x);
-            }
-        }
-    }
-    if (!FIRST) {
-        acc = wave_sum(acc);
-        acc2 = wave_sum(acc2);
-        __syncthreads();
-        double *sred = reinterpret_cast<double *>(buf);
-        if ((tid & 63) == 0) {
-            sred[tid >> 6] = acc;
-            sred[T / 64 + (tid >> 6)] = acc2;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            double tot = 0.0, tot2 = 0.0;
-            for (int w = 0; w < T / 64; ++w) {
-                tot += sred[w];
-                tot2 += sred[T / 64 + w];
-            }
-            double *dst = a.gpart3 + (((long)wr * a.nbatch + b) * gridDim.x + blockIdx.x) * 2;
-            dst[0] = tot;
-            dst[1] = tot2;
-        }
+    rows_node_transform<C, LOGL>(buf, ax, logL, row0, G.ns, node, put);
+    if (!FIRST && rows_partials<T, RED_SUM>(buf, acc, acc2)) {
+        double *dst = a.gpart3 + (((long)wr * a.nbatch + b) * gridDim.x + blockIdx.x) * 2;
+        dst[0] = acc;
+        dst[1] = acc2;
     }
 }
 

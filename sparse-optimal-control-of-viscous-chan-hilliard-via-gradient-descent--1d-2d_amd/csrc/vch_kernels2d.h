@@ -2006,13 +2006,16 @@ struct CgNext {
     int active, breakdown, it;
     double alpha, beta, gamma, rel;
 };
-__device__ __forceinline__ CgNext cg_next(double pq, double qq, double gamma, double gamma0, int it_old, double tol,
-                                          int maxit) {
+// The step every CG form shares: breakdown test, alpha, the predicted gamma' = alpha^2 <q,q> - gamma with its restart,
+// beta, the iteration count and the stop test.  The forms differ in the relative residual only: rel_bd() is its value on
+// breakdown, rel_step(gamma') its prediction after a step.
+template <class RelBd, class RelStep>
+__device__ __forceinline__ CgNext cg_step(double pq, double qq, double gamma, int it_old, double tol, int maxit, RelBd rel_bd,
+                                          RelStep rel_step) {
     CgNext n;
     n.it = it_old;
     if (!(pq > 0.0) || !(gamma > 0.0)) {     // round-off level residual: stop here, no step
-        n.active = 0; n.breakdown = 1; n.alpha = 0.0; n.beta = 0.0; n.gamma = fmax(gamma, 0.0);
-        n.rel = gamma0 > 0.0 ? sqrt(fmax(gamma, 0.0) / gamma0) : 0.0;
+        n.active = 0; n.breakdown = 1; n.alpha = 0.0; n.beta = 0.0; n.gamma = fmax(gamma, 0.0); n.rel = rel_bd();
         return n;
     }
     n.breakdown = 0;
@@ -2026,9 +2029,14 @@ __device__ __forceinline__ CgNext cg_next(double pq, double qq, double gamma, do
     }
     n.gamma = gn;
     n.it = it_old + 1;
-    n.rel = sqrt(gn / gamma0);
+    n.rel = rel_step(gn);
     n.active = (n.rel > tol && n.it < maxit) ? 1 : 0;
     return n;
+}
+__device__ __forceinline__ CgNext cg_next(double pq, double qq, double gamma, double gamma0, int it_old, double tol,
+                                          int maxit) {
+    return cg_step(pq, qq, gamma, it_old, tol, maxit, [&] { return gamma0 > 0.0 ? sqrt(fmax(gamma, 0.0) / gamma0) : 0.0; },
+                   [&](double gn) { return sqrt(gn / gamma0); });
 }
 
 // the three sums, one wavefront each (fixed order); all threads of the workgroup call it (>= 192 threads)
