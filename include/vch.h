@@ -546,6 +546,49 @@ int vch1d_second_order(vch1d_ctx *ctx, const double *phi_hist, const double *u, 
                        double *dphi_hist_out, double *d2phi_hist_out      /* [B][rows][N+1] or NULL */,
                        vch_stats *stats);
 
+/* Exact discrete gradient field and Hessian-vector product of the smooth part J1 + J2 + J3 of the 1D cost: one launch,
+ * one persistent workgroup per direction (k1d_hessvec).  The tangent step of vch1d_second_order is a linear
+ * map on (dphi, dmu, dw) driven by (h_n, h_{n+1}); the exact adjoint of the DISCRETE cost is that map run backwards over
+ * the steps with the transposed Newton matrix J(phi*)^T, and a second transposed sweep beside it, fed by the tangent of h,
+ * gives H h.  With wx = h trapz, wt the trapezoid weights of t_hist (row 0: 0), e = phi - phi_Q, al = (gamma/dt - 1/2) /
+ * (gamma/dt + 1/2), be = (1/2) / (gamma/dt + 1/2), Kp = (tau/dt + 2 c2) I + kappa/2 L, multipliers starting at zero,
+ * G = b3 wt (x) wx . u, Hh = b3 wt (x) wx . h, and for k = M-1 .. 0 (phi* = row k+2, step k has dt_k):
+ *     l_phi += wt[k+2] b1 wx . e[k+2]                  (+ b2 wx . (phi_M - phi_T) at k = M-1)
+ *     l_v    = l_phi - wx sum(l_phi) / Lx              (transpose of the mean removal; plain node sum)
+ *     J(phi*)^T [yp; ym] = [l_v; l_mu]
+ *     l_dw   = yp/2 + l_w;   G[k] += be l_dw;   G[k+1] += be l_dw
+ *     (l_phi, l_mu, l_w) <- (Kp^T yp + ym/dt,  yp/2 + L^T ym / 2,  yp/2 + al l_dw)
+ *   order 2, same loop, with v_k = dphi* of step k of the tangent of h before its mean removal and dphi its history:
+ *     L_phi += wt[k+2] b1 wx . dphi[k+2]               (+ b2 wx . dphi_M at k = M-1)
+ *     L_v    = L_phi - wx sum(L_phi) / Lx - c1 rho(phi*) yp v_k,        rho(p) = 4 p / (1 - p^2)^2
+ *     J(phi*)^T [Yp; Ym] = [L_v; L_mu];   Hh and (L_phi, L_mu, L_w) as above.
+ * L is not symmetric (the mirrored-Neumann rows carry a 2): the transposed rows take each neighbour's weight from the
+ * neighbour's row.  Cost: one linear solve per step for the gradient; one tangent and two transposed solves per step for
+ * H h.  No nonlinear march, no finite differences, no host round trip.
+ * EUCLIDEAN convention: grad_out[b][row][i] = d(J1+J2+J3)/du[row][i] and hv_out = (d^2(J1+J2+J3)/du^2) h, derivatives with
+ * respect to the entries of u, NOT divided by quadrature weights: J'(u)h = sum(grad . h) and J''(u)[h,h] = sum(h . hv) as
+ * plain node sums, the s_state + s_ctrl and c_gn + c_state + c_ctrl of vch1d_second_order.  Row 0 has quadrature weight 0
+ * but drives step 0, so grad[0] != 0; the last row drives no step and holds b3 wt wx u (resp. h) alone.
+ * Arguments and conventions are those of vch1d_second_order (n_base, NULL = zeros, VCH_RESIDENT, resident history,
+ * dt == NULL, only b1, b2, b3 of opts are read, the clip taken as the identity with the same caveats), except:
+ *   h        [B][rows][N+1] direction; NULL allowed iff order 1 (the gradient does not depend on it)
+ *   order    1: gradient alone; 2: gradient and H h
+ *   grad_out [B][rows][N+1] or NULL;   hv_out [B][rows][N+1], required iff order 2 (with order 1: NULL, or zero-filled)
+ *   dots_out [B][2] or NULL = { sum grad . h, sum h . hv }, reduced on the device in a fixed order; NaN where the factor
+ *            does not exist (NULL h; order 1)
+ *   stats (or NULL): launches = 1, linear_solves = B M (order == 1 ? 1 : 3), device seconds.
+ * A trajectory with h == 0 gets hv exactly zero.  VCH_ERR_ARG / VCH_ERR_STATE as for vch1d_second_order, with the same
+ * messages and before anything is copied or launched (NULL hv_out with order 2 in place of NULL out).  The call is
+ * stateless in the same sense: it leaves every resident buffer and the PGD bookkeeping as it found them, and a trajectory's
+ * outputs are bitwise independent of the batch.  The ABI version stays 3: callers detect the entry point by symbol. */
+int vch1d_hessvec(vch1d_ctx *ctx, const double *phi_hist, const double *u, int n_base,
+                  const double *h /* NULL allowed iff order 1 */, int rows, const double *dt, const double *t_hist,
+                  const double *x, const double *phi_Q, const double *phi_T,
+                  const vch_opt_params *opts, int n_opts,                 /* 1 or B; only b1,b2,b3 are read */
+                  int order /* 1 or 2 */,
+                  double *grad_out /* [B][rows][N+1] or NULL */, double *hv_out /* [B][rows][N+1], required iff order 2 */,
+                  double *dots_out /* [B][2] or NULL */, vch_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,8 @@
 """Host-side mirror of src/1D/Vch_control_1D/second_order_conditions.py: finite-difference
 coercivity test with the kink-aware critical cone; forward marches and costs run on the GPU.
 `approximate_second_order_condition` is the reference's formula, `exact_second_order_condition` gives the exact
-second derivative by tangent marches on the device."""
+second derivative by tangent marches on the device, `reduced_hessian_extremes` the extreme eigenvalues of the reduced
+Hessian on the free set by Lanczos on exact Hessian-vector products."""
 from __future__ import annotations
 
 import contextlib
@@ -154,3 +155,73 @@ def exact_second_order_condition(fwd_config: ForwardSolverConfig, u_star, r_star
             print(f"  Direction {k0 + i + 1}/{num_directions}: exact d²J/dh² = {d2:.6e}   exact slope J'h = {slope:.6e}   "
                   f"adjoint sum(g·h) = {np.sum(grad_star * h):.6e}")
     return out
+
+
+def free_set(u_star, u_min, u_max, tol=1e-8):
+    """Nodes where the critical cone is a linear space: strictly inside the box and off the kink of the L1 term, with the
+    `tol` of `_cone_sign_codes` (whose rules leave exactly these nodes free whatever the adjoint is)."""
+    u_star = np.asarray(u_star)
+    return (u_star > u_min + tol) & (u_star < u_max - tol) & (np.abs(u_star) > tol)
+
+
+def reduced_hessian_extremes(fwd_config: ForwardSolverConfig, u_star, phi_star, x, t_hist, b1, b2, b3, kappa, phi_Q_target,
+                             phi_T_target, u_min, u_max, k: int = 30, seed=None, tol: float = 1e-8) -> dict:
+    """Extreme eigenvalues of the reduced Hessian P H P of the smooth part J1 + J2 + J3 of the discrete cost at `u_star`,
+    by host Lanczos with full reorthogonalisation.  H is the exact Euclidean Hessian with respect to the entries of u
+    (Engine1D.hessvec: one tangent and two transposed solves per time step, about `phi_star` as given, one call per
+    Lanczos step with a shared base point); P masks to the free set `free_set(u_star, u_min, u_max, tol)`.  At most
+    min(k, size of the free set) steps; with k >= that size the Ritz values are all eigenvalues of P H P on the free set.
+
+    Returns dict(theta_min, theta_max: the extreme Ritz values; res_min, res_max: their residual norms
+    |beta_m s_m| (an eigenvalue of P H P lies within that distance of each); ritz: all Ritz values, ascending; n_free: the
+    size of the free set; steps: Lanczos steps taken).  The values are Rayleigh quotients h.Hh / h.h in the Euclidean
+    norm of h, the scale of the curvatures `exact_second_order_condition` returns for its unit directions; theta_min is
+    not larger than any of those whose direction is supported on the free set.
+
+    What is left out.  The second-order sufficient condition asks for coercivity on the critical cone.  On the free set
+    the cone is a linear space and the smallest eigenvalue is the coercivity constant there, which random directions only
+    bound from above.  At a node on the kink u* = 0 of kappa |u|_1 the cone admits one sign at most (none where
+    |r + b3 u| < kappa), and at a node on the active box it admits the inward sign only: there the cone is a half-line or
+    a point per node, the minimum of the quadratic form over it is no eigenvalue problem, and the L1 term adds no
+    curvature along an admitted sign.  Those nodes are pinned to zero here, so theta_min bounds the cone's constant from
+    above: a cone direction that mixes free and one-signed nodes can still see less curvature.  `kappa` therefore does
+    not enter.  The clip of the march is taken as inactive, as in `exact_second_order_condition`."""
+    from ..engine import make_opt
+    from ._ctx import engine_for_config
+    cfg = fwd_config if fwd_config is not None else ForwardSolverConfig()
+    rng = _as_generator(seed)
+    u_star = np.asarray(u_star, dtype=np.float64)
+    t_hist = np.asarray(t_hist, dtype=np.float64)
+    mask = free_set(u_star, u_min, u_max, tol)
+    n_free = int(mask.sum())
+    if n_free == 0:
+        raise ValueError("reduced_hessian_extremes: the free set is empty")
+    opt = make_opt(b1=b1, b2=b2, b3=b3, kappa_sparsity=0.0)
+    eng = engine_for_config(cfg, batch=1, max_steps=max(t_hist.size - 2, 1))
+
+    def apply(q):
+        res = eng.hessvec(q, t_hist, opt, phi_hist=phi_star, u=u_star, phi_Q=phi_Q_target, phi_T=phi_T_target, x=x,
+                          shared_base=True)
+        return np.where(mask, res["hv"][0], 0.0)
+
+    q = np.where(mask, rng.standard_normal(u_star.shape), 0.0)
+    q /= np.linalg.norm(q)
+    Q, alphas, betas = [q], [], []
+    steps = min(int(k), n_free)
+    for j in range(steps):
+        w = apply(Q[j])
+        alphas.append(float(np.sum(Q[j] * w)))
+        for _ in range(2):                                   # full reorthogonalisation, twice is enough
+            for v in Q:
+                w -= np.sum(v * w) * v
+        beta = float(np.linalg.norm(w))
+        betas.append(beta)
+        if j + 1 == steps or beta <= 1e-14 * max(abs(a) for a in alphas):     # done, or an invariant subspace
+            break
+        Q.append(w / beta)
+    m = len(alphas)
+    T = np.diag(alphas) + np.diag(betas[:m - 1], 1) + np.diag(betas[:m - 1], -1)
+    theta, S = np.linalg.eigh(T)
+    resid = np.abs(betas[m - 1] * S[m - 1])
+    return dict(theta_min=float(theta[0]), theta_max=float(theta[-1]), res_min=float(resid[0]), res_max=float(resid[-1]),
+                ritz=theta, n_free=n_free, steps=m)

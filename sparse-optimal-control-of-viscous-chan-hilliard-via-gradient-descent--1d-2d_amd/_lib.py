@@ -163,6 +163,8 @@ SIGNATURES = {
     "vch1d_pgd_get": (C.c_int, [_P, C.c_int, _D]),
     "vch1d_second_order": (C.c_int, [_P, _D, _D, C.c_int, _D, C.c_int, _D, _D, _D, _D, _D, C.POINTER(OptParams), C.c_int,
                                      C.c_int, _D, _D, _D, C.POINTER(Stats)]),
+    "vch1d_hessvec": (C.c_int, [_P, _D, _D, C.c_int, _D, C.c_int, _D, _D, _D, _D, _D, C.POINTER(OptParams), C.c_int,
+                                C.c_int, _D, _D, _D, C.POINTER(Stats)]),
     "vch2d_counters": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "vch_comm_unique_id": (C.c_int, [C.POINTER(C.c_ubyte)]),
     "vch_comm_create": (_P, [C.POINTER(C.c_ubyte), C.c_int, C.c_int, C.c_int]),

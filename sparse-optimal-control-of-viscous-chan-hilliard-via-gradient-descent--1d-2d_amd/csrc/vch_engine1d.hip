@@ -42,6 +42,9 @@ struct vch1d_ctx {
     // every resident buffer as it found it
     double *so_base = nullptr, *so_u = nullptr, *so_pq = nullptr, *so_h = nullptr, *so_d1 = nullptr, *so_d2 = nullptr;   // [B][Mmax+2][n]
     double *so_pt = nullptr, *so_dts = nullptr, *so_t = nullptr, *so_wx = nullptr, *so_wts = nullptr, *so_out = nullptr;
+    // vch1d_hessvec (lazy; it shares the base point, direction and grid buffers above): G, Hh and the tangent's v_k
+    // [B][Mmax+2][n], the time weights [Mmax+2], the removed means [B][Mmax+2], the two dot products [B][2]
+    double *hv_g = nullptr, *hv_hv = nullptr, *hv_v = nullptr, *hv_wt = nullptr, *hv_mean = nullptr, *hv_dots = nullptr;
 };
 
 // no launch bookkeeping (LAUNCH_LDS, vch_common.h)
@@ -144,6 +147,8 @@ extern "C" vch1d_ctx *vch1d_create(const vch1d_params *p, int batch, int max_ste
     hipFuncSetAttribute((const void *)k1d_solve<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes);
     hipFuncSetAttribute((const void *)k1d_tangent<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes);
     hipFuncSetAttribute((const void *)k1d_tangent<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes);
+    hipFuncSetAttribute((const void *)k1d_hessvec<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes);
+    hipFuncSetAttribute((const void *)k1d_hessvec<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes);
     if (hipStreamSynchronize(c->stream) != hipSuccess) return fail("hipStreamSynchronize");
     return c;
 }
@@ -156,7 +161,7 @@ extern "C" void vch1d_destroy(vch1d_ctx *c) {
                      c->phiT, c->dts, c->tgrid, c->wx, c->alpha_dev, c->cost_lvl, c->hist_dev, c->phi_hist, c->u_hist,
                      c->u_trial, c->phiQ, c->p_hist, c->q_hist, c->r_hist, c->phi0_dev, c->phi_trial, c->chg_dev, c->tp_dev,
                      c->opt_tab, c->seam_tab, c->kkt_nrm, c->so_base, c->so_u, c->so_pq, c->so_h, c->so_d1, c->so_d2, c->so_pt, c->so_dts,
-                     c->so_t, c->so_wx, c->so_wts, c->so_out};
+                     c->so_t, c->so_wx, c->so_wts, c->so_out, c->hv_g, c->hv_hv, c->hv_v, c->hv_wt, c->hv_mean, c->hv_dots};
     for (double *q : all)
         if (q) hipFree(q);
     hipFree(c->stats_dev);
@@ -700,31 +705,32 @@ static int up_hist_n(vch1d_ctx *c, double *dev, const double *host, int rows, in
     return 0;
 }
 
-extern "C" int vch1d_second_order(vch1d_ctx *c, const double *phi_hist, const double *u, int n_base, const double *h,
-                                  int rows, const double *dt, const double *t_hist, const double *x, const double *phi_Q,
-                                  const double *phi_T, const vch_opt_params *opts, int n_opts, int order, double *out,
-                                  double *dphi_hist_out, double *d2phi_hist_out, vch_stats *stats) {
-    CTXCHK(c);
-    const int B = c->B, n = c->n;
-    const char *fn = "vch1d_second_order";
+// What vch1d_second_order and vch1d_hessvec check alike, in two parts around the caller's own NULL checks; nothing is
+// copied or launched by either.  The second part fills the step sizes and the [B][3] weight table.
+static int so1_check_shape(vch1d_ctx *c, const char *fn, int n_base, int rows, int n_opts, int order) {
+    const int B = c->B;
     if (rows < 3 || rows > c->Mmax + 2)
         return vch_fail(VCH_ERR_ARG, "%s: rows = %d outside 3..%d (max_steps + 2)", fn, rows, c->Mmax + 2);
     if (n_base != 1 && n_base != B) return vch_fail(VCH_ERR_ARG, "%s: n_base = %d is neither 1 nor the batch %d", fn, n_base, B);
     if (n_opts != 1 && n_opts != B) return vch_fail(VCH_ERR_ARG, "%s: n_opts = %d is neither 1 nor the batch %d", fn, n_opts, B);
     if (order != 1 && order != 2) return vch_fail(VCH_ERR_ARG, "%s: order = %d is neither 1 nor 2", fn, order);
-    if (!h) return vch_fail(VCH_ERR_ARG, "%s: NULL direction h", fn);
+    return 0;
+}
+static int so1_check_rest(vch1d_ctx *c, const char *fn, const double *phi_hist, const double *u, int rows, const double *dt,
+                          const double *t_hist, const double *x, const double *phi_Q, const double *phi_T,
+                          const vch_opt_params *opts, int n_opts, std::vector<double> &dts, std::vector<double> &wts) {
+    const int B = c->B;
     if (!t_hist) return vch_fail(VCH_ERR_ARG, "%s: NULL t_hist", fn);
     if (!x) return vch_fail(VCH_ERR_ARG, "%s: NULL x", fn);
-    if (!out) return vch_fail(VCH_ERR_ARG, "%s: NULL out", fn);
     if (!opts) return vch_fail(VCH_ERR_ARG, "%s: NULL opts", fn);
     const int M = rows - 2;
-    std::vector<double> dts(M);
+    dts.resize(M);
     for (int k = 0; k < M; ++k) {
         dts[k] = dt ? dt[k] : t_hist[k + 2] - t_hist[k + 1];
         if (!(dts[k] > 0.0) || !std::isfinite(dts[k]))
             return vch_fail(VCH_ERR_ARG, "%s: step %d: dt = %g must be positive and finite", fn, k, dts[k]);
     }
-    std::vector<double> wts(3 * (size_t)B);
+    wts.resize(3 * (size_t)B);
     for (int b = 0; b < B; ++b) {
         const vch_opt_params &o = vch_pgd_opt(opts, n_opts, b);
         if (const char *bad = vch_pgd_check_weights(opts, n_opts, b)) return vch_fail(VCH_ERR_ARG, "%s: trajectory %d: %s", fn, b, bad);
@@ -736,58 +742,91 @@ extern "C" int vch1d_second_order(vch1d_ctx *c, const double *phi_hist, const do
         return vch_fail(VCH_ERR_STATE, "%s: VCH_RESIDENT control or targets before vch1d_pgd_init", fn);
     if ((u == VCH_RESIDENT || phi_Q == VCH_RESIDENT) && c->pgd_rows != rows)
         return vch_fail(VCH_ERR_STATE, "%s: the resident PGD problem has %d rows, not %d", fn, c->pgd_rows, rows);
-    // ---- nothing was launched or copied up to here
-    const long hs = hs1(c), bs = n_base == 1 ? 0 : hs;
-    Tan1Args G{};
-    G.hs = hs;
+    return 0;
+}
+
+// The base point of both calls on the device: the caller's arrays in the call's own buffers, or the resident ones.
+struct So1Base {
+    const double *phi = nullptr, *u = nullptr, *pq = nullptr, *pt = nullptr;
+    long bs = 0, pts = 0;          // strides per trajectory of the histories and of phi_T (0: one base for the batch)
+};
+static int so1_base(vch1d_ctx *c, const double *phi_hist, const double *u, const double *phi_Q, const double *phi_T, int n_base,
+                    int rows, So1Base &S) {
+    const int B = c->B, n = c->n;
+    S.bs = n_base == 1 ? 0 : hs1(c);
+    S.pts = n_base == 1 ? 0 : n;
     if (phi_hist) {
         VCHCHK(ensure1(c, &c->so_base));
         VCHCHK(up_hist_n(c, c->so_base, phi_hist, rows, n_base));
-        G.phi = c->so_base;
+        S.phi = c->so_base;
     } else {
-        G.phi = c->phi_hist;
+        S.phi = c->phi_hist;
     }
-    G.phi_s = bs;
     if (u == VCH_RESIDENT) {
-        G.u = c->u_hist;
+        S.u = c->u_hist;
     } else if (u) {
         VCHCHK(ensure1(c, &c->so_u));
         VCHCHK(up_hist_n(c, c->so_u, u, rows, n_base));
-        G.u = c->so_u;
+        S.u = c->so_u;
     }
-    G.u_s = bs;
     if (phi_Q == VCH_RESIDENT) {
-        G.pq = c->phiQ;
+        S.pq = c->phiQ;
     } else if (phi_Q) {
         VCHCHK(ensure1(c, &c->so_pq));
         VCHCHK(up_hist_n(c, c->so_pq, phi_Q, rows, n_base));
-        G.pq = c->so_pq;
+        S.pq = c->so_pq;
     }
-    G.pq_s = bs;
     if (phi_T == VCH_RESIDENT) {
-        G.pt = c->phiT;
+        S.pt = c->phiT;
     } else if (phi_T) {
         if (!c->so_pt) VCHCHK(dalloc1(&c->so_pt, (size_t)B * n, c->stream));
         VCHCHK(up(c, c->so_pt, phi_T, (size_t)n_base * n));
-        G.pt = c->so_pt;
+        S.pt = c->so_pt;
     }
-    G.pt_s = n_base == 1 ? 0 : n;
-    VCHCHK(ensure1(c, &c->so_h));
-    VCHCHK(up_hist(c, c->so_h, h, rows));
-    G.hd = c->so_h;
+    return 0;
+}
+// step sizes, t_hist, the trapezoid weights of x and the weight table (host vectors: the caller synchronises before they go)
+static int so1_grids(vch1d_ctx *c, const std::vector<double> &dts, const double *t_hist, int rows, const std::vector<double> &wx,
+                     const std::vector<double> &wts) {
     if (!c->so_dts) {
         VCHCHK(dalloc1(&c->so_dts, c->Mmax + 2, c->stream));
         VCHCHK(dalloc1(&c->so_t, c->Mmax + 2, c->stream));
-        VCHCHK(dalloc1(&c->so_wx, n, c->stream));
-        VCHCHK(dalloc1(&c->so_wts, 3 * (size_t)B, c->stream));
-        VCHCHK(dalloc1(&c->so_out, 6 * (size_t)B, c->stream));
+        VCHCHK(dalloc1(&c->so_wx, c->n, c->stream));
+        VCHCHK(dalloc1(&c->so_wts, 3 * (size_t)c->B, c->stream));
+        VCHCHK(dalloc1(&c->so_out, 6 * (size_t)c->B, c->stream));
     }
-    std::vector<double> wx;
-    trapz_x(c, x, wx);
-    VCHCHK(up(c, c->so_dts, dts.data(), M));
+    VCHCHK(up(c, c->so_dts, dts.data(), rows - 2));
     VCHCHK(up(c, c->so_t, t_hist, rows));
-    VCHCHK(up(c, c->so_wx, wx.data(), n));
-    VCHCHK(up(c, c->so_wts, wts.data(), wts.size()));
+    VCHCHK(up(c, c->so_wx, wx.data(), c->n));
+    return up(c, c->so_wts, wts.data(), wts.size());
+}
+
+extern "C" int vch1d_second_order(vch1d_ctx *c, const double *phi_hist, const double *u, int n_base, const double *h,
+                                  int rows, const double *dt, const double *t_hist, const double *x, const double *phi_Q,
+                                  const double *phi_T, const vch_opt_params *opts, int n_opts, int order, double *out,
+                                  double *dphi_hist_out, double *d2phi_hist_out, vch_stats *stats) {
+    CTXCHK(c);
+    const int B = c->B, n = c->n;
+    const char *fn = "vch1d_second_order";
+    VCHCHK(so1_check_shape(c, fn, n_base, rows, n_opts, order));
+    if (!h) return vch_fail(VCH_ERR_ARG, "%s: NULL direction h", fn);
+    if (!out) return vch_fail(VCH_ERR_ARG, "%s: NULL out", fn);
+    std::vector<double> dts, wts, wx;
+    VCHCHK(so1_check_rest(c, fn, phi_hist, u, rows, dt, t_hist, x, phi_Q, phi_T, opts, n_opts, dts, wts));
+    // ---- nothing was launched or copied up to here
+    const int M = rows - 2;
+    So1Base S;
+    VCHCHK(so1_base(c, phi_hist, u, phi_Q, phi_T, n_base, rows, S));
+    Tan1Args G{};
+    G.hs = hs1(c);
+    G.phi = S.phi; G.u = S.u; G.pq = S.pq; G.pt = S.pt;
+    G.phi_s = G.u_s = G.pq_s = S.bs;
+    G.pt_s = S.pts;
+    VCHCHK(ensure1(c, &c->so_h));
+    VCHCHK(up_hist(c, c->so_h, h, rows));
+    G.hd = c->so_h;
+    trapz_x(c, x, wx);
+    VCHCHK(so1_grids(c, dts, t_hist, rows, wx, wts));
     G.dts = c->so_dts; G.t = c->so_t; G.wx = c->so_wx; G.wts = c->so_wts; G.out = c->so_out;
     if (dphi_hist_out) { VCHCHK(ensure1(c, &c->so_d1)); G.d1 = c->so_d1; }
     if (d2phi_hist_out && order == 2) { VCHCHK(ensure1(c, &c->so_d2)); G.d2 = c->so_d2; }
@@ -808,6 +847,82 @@ extern "C" int vch1d_second_order(vch1d_ctx *c, const double *phi_hist, const do
         hipEventElapsedTime(&ms, c->ev0, c->ev1);
         memset(stats, 0, sizeof(*stats));
         stats->linear_solves = (int64_t)order * M * B;
+        stats->launches = 1;
+        stats->seconds = ms * 1e-3;
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------
+// exact discrete gradient field and Hessian-vector product by transposed tangent sweeps (k1d_hessvec)
+// ------------------------------------------------------------------------------------
+extern "C" int vch1d_hessvec(vch1d_ctx *c, const double *phi_hist, const double *u, int n_base, const double *h, int rows,
+                             const double *dt, const double *t_hist, const double *x, const double *phi_Q,
+                             const double *phi_T, const vch_opt_params *opts, int n_opts, int order, double *grad_out,
+                             double *hv_out, double *dots_out, vch_stats *stats) {
+    CTXCHK(c);
+    const int B = c->B, n = c->n;
+    const char *fn = "vch1d_hessvec";
+    VCHCHK(so1_check_shape(c, fn, n_base, rows, n_opts, order));
+    if (!h && order == 2) return vch_fail(VCH_ERR_ARG, "%s: NULL direction h", fn);
+    if (!hv_out && order == 2) return vch_fail(VCH_ERR_ARG, "%s: NULL hv_out", fn);
+    std::vector<double> dts, wts, wx;
+    VCHCHK(so1_check_rest(c, fn, phi_hist, u, rows, dt, t_hist, x, phi_Q, phi_T, opts, n_opts, dts, wts));
+    // ---- nothing was launched or copied up to here
+    const int M = rows - 2;
+    So1Base S;
+    VCHCHK(so1_base(c, phi_hist, u, phi_Q, phi_T, n_base, rows, S));
+    Hv1Args G{};
+    G.hs = hs1(c);
+    G.phi = S.phi; G.u = S.u; G.pq = S.pq; G.pt = S.pt;
+    G.phi_s = G.u_s = G.pq_s = S.bs;
+    G.pt_s = S.pts;
+    if (h) {
+        VCHCHK(ensure1(c, &c->so_h));
+        VCHCHK(up_hist(c, c->so_h, h, rows));
+        G.hd = c->so_h;
+    }
+    trapz_x(c, x, wx);
+    VCHCHK(so1_grids(c, dts, t_hist, rows, wx, wts));
+    // trapezoid weights of t_hist (np.trapezoid over all rows, C1:55-73): the duplicated t = 0 row gets 0
+    std::vector<double> wt(rows, 0.0);
+    for (int r = 0; r + 1 < rows; ++r) {
+        const double d = t_hist[r + 1] - t_hist[r];
+        wt[r] += 0.5 * d;
+        wt[r + 1] += 0.5 * d;
+    }
+    if (!c->hv_wt) {
+        VCHCHK(dalloc1(&c->hv_wt, c->Mmax + 2, c->stream));
+        VCHCHK(dalloc1(&c->hv_mean, (size_t)B * (c->Mmax + 2), c->stream));
+        VCHCHK(dalloc1(&c->hv_dots, 2 * (size_t)B, c->stream));
+    }
+    VCHCHK(up(c, c->hv_wt, wt.data(), rows));
+    VCHCHK(ensure1(c, &c->hv_g));
+    G.dts = c->so_dts; G.wt = c->hv_wt; G.wx = c->so_wx; G.wts = c->so_wts;
+    G.g = c->hv_g; G.mean = c->hv_mean; G.dots = c->hv_dots;
+    if (order == 2) {
+        VCHCHK(ensure1(c, &c->hv_hv));
+        VCHCHK(ensure1(c, &c->hv_v));
+        G.hv = c->hv_hv; G.v = c->hv_v;
+    }
+    HIPCHK(hipEventRecord(c->ev0, c->stream));
+    if (order == 2)
+        LAUNCH_LDS(-1, (k1d_hessvec<2>), dim3(B), dim3(T1), c->lds_bytes, c->P, n, c->h, c->lvl, rows, G, c->scratch);
+    else
+        LAUNCH_LDS(-1, (k1d_hessvec<1>), dim3(B), dim3(T1), c->lds_bytes, c->P, n, c->h, c->lvl, rows, G, c->scratch);
+    HIPCHK(hipEventRecord(c->ev1, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));                 // the host vectors above are done with
+    if (dots_out) VCHCHK(down(c, dots_out, c->hv_dots, 2 * (size_t)B));
+    if (grad_out) VCHCHK(down_hist(c, grad_out, c->hv_g, rows));
+    if (hv_out) {
+        if (order == 2) VCHCHK(down_hist(c, hv_out, c->hv_hv, rows));
+        else memset(hv_out, 0, sizeof(double) * B * rows * n);
+    }
+    if (stats) {
+        float ms = 0;
+        hipEventElapsedTime(&ms, c->ev0, c->ev1);
+        memset(stats, 0, sizeof(*stats));
+        stats->linear_solves = (int64_t)(order == 1 ? 1 : 3) * M * B;
         stats->launches = 1;
         stats->seconds = ms * 1e-3;
     }

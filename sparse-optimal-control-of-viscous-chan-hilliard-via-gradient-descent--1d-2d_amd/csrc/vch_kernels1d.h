@@ -53,7 +53,10 @@ struct Row {           // A x_{i-s} + B x_i + C x_{i+s} = d
     V2 d;
 };
 
-// Level-0 rows.  SYS 0: Newton system at iterate phi (F1:111-137); SYS 1: adjoint system at phi_n.
+// Level-0 rows.  SYS 0: Newton system at iterate phi (F1:111-137); SYS 1: adjoint system at phi_n; SYS 2: the transpose of
+// the Newton system (k1d_hessvec).  L is not symmetric (the mirrored rows 0 and n-1 carry a 2), so the transposed row i
+// takes the weight of neighbour i-1 from row i-1's upper entry and that of neighbour i+1 from row i+1's lower entry; the
+// diagonal 2x2 block is transposed, the off-diagonal blocks are diagonal.
 struct SysArgs {
     const double *phi;       // D_i from phi_i
     const double *r0, *r1;   // right-hand side components (r1 may be NULL = 0)
@@ -64,13 +67,13 @@ struct SysArgs {
 
 template <int SYS>
 __device__ __forceinline__ Row row0(const SysArgs &S, int i) {
-    const double fl = i == 0 ? 0.0 : (i == S.n - 1 ? 2.0 : 1.0);      // weight of neighbour i-1
-    const double fu = i == S.n - 1 ? 0.0 : (i == 0 ? 2.0 : 1.0);      // weight of neighbour i+1
+    const double fl = i == 0 ? 0.0 : (SYS == 2 ? (i == 1 ? 2.0 : 1.0) : (i == S.n - 1 ? 2.0 : 1.0));      // weight of neighbour i-1
+    const double fu = i == S.n - 1 ? 0.0 : (SYS == 2 ? (i == S.n - 2 ? 2.0 : 1.0) : (i == 0 ? 2.0 : 1.0));  // weight of neighbour i+1
     Row R;
     const double ph = S.phi[i];
-    if (SYS == 0) {
+    if (SYS == 0 || SYS == 2) {
         const double D = S.tau / S.dt + 2.0 * S.c1 / (1.0 - ph * ph);           // F1:122-124 (not clipped)
-        R.B = M2{S.kappa * S.a + D, -0.5, 1.0 / S.dt, S.a};
+        R.B = SYS == 0 ? M2{S.kappa * S.a + D, -0.5, 1.0 / S.dt, S.a} : M2{S.kappa * S.a + D, 1.0 / S.dt, -0.5, S.a};
         R.A = M2{-0.5 * S.kappa * S.a * fl, 0.0, 0.0, -0.5 * S.a * fl};
         R.C = M2{-0.5 * S.kappa * S.a * fu, 0.0, 0.0, -0.5 * S.a * fu};
     } else {
@@ -257,6 +260,12 @@ __device__ __forceinline__ double lap1(const double *v, int i, int n, double a) 
     if (i == 0) return 2.0 * a * (v[1] - v[0]);
     if (i == n - 1) return 2.0 * a * (v[n - 2] - v[n - 1]);
     return a * ((v[i - 1] + v[i + 1]) - 2.0 * v[i]);
+}
+// transpose of lap1: (L^T v)_i = sum_j L_ji v_j; the 2 of the mirrored rows 0 and n-1 sits in columns 1 and n-2
+__device__ __forceinline__ double lap1t(const double *v, int i, int n, double a) {
+    const double lo = i == 0 ? 0.0 : (i == 1 ? 2.0 : 1.0) * v[i - 1];
+    const double hi = i == n - 1 ? 0.0 : (i == n - 2 ? 2.0 : 1.0) * v[i + 1];
+    return a * ((lo + hi) - 2.0 * v[i]);
 }
 __device__ __forceinline__ double reglog1(double phi) {                                  // F1:57-62
     const double eps = 0.5 * DSEP1;
@@ -680,6 +689,177 @@ __global__ __launch_bounds__(T1) void k1d_tangent(Phys1 P, int n, double h, int 
         o[3] = ORDER == 2 ? b1 * I[2] + b2 * T[1] : (double)NAN;
         o[4] = b3 * I[4];
         o[5] = I[4];
+    }
+}
+
+// ---------------------------------------------------------------------------------
+// exact discrete gradient and Hessian-vector product (vch1d_hessvec): the tangent step above is a linear
+// map on (dphi, dmu, dw) driven by (h_s, h_{s+1}); its transpose run backwards over the steps, fed by the derivative of
+// the cost with respect to the tangent state, is the exact adjoint of the discrete cost.  grid = B workgroups, one
+// direction each.  With wx = h trapz, wt the trapezoid weights of t (row 0: 0), e = phi - phi_Q, al = (gamma/dt - 1/2) /
+// (gamma/dt + 1/2), be = (1/2) / (gamma/dt + 1/2), Kp = (tau/dt + 2 c2) I + kappa/2 L, all multipliers zero at the start,
+// G = b3 wt (x) wx . u, and for k = M-1 .. 0 (phi* = row k+2):
+//   l_phi += wt[k+2] b1 wx . e[k+2]   (+ b2 wx . (phi_M - phi_T) at k = M-1)
+//   l_v    = l_phi - wx sum(l_phi) / Lx                       (transpose of the mean removal; plain node sum)
+//   J(phi*)^T [yp; ym] = [l_v; l_mu]                          (row0<2>)
+//   l_dw   = yp/2 + l_w;   G[k] += be l_dw;   G[k+1] += be l_dw
+//   (l_phi, l_mu, l_w) <- (Kp^T yp + ym/dt,  yp/2 + L^T ym / 2,  yp/2 + al l_dw)
+// ORDER 2 first marches the order-1 tangent of h, keeping every step's dphi* BEFORE its mean removal (v_k, row k+2 of
+// G.v) and the mean it removed (G.mean[k]), then runs a second sweep (capital letters) in lockstep, so yp is never stored:
+//   L_phi += wt[k+2] b1 wx . dphi[k+2]   (+ b2 wx . dphi_M at k = M-1),      dphi[k+2] = v_k - mean_k
+//   L_v    = L_phi - wx sum(L_phi) / Lx - c1 rho(phi*) yp v_k,               rho(p) = 4 p / (1 - p^2)^2
+//   J(phi*)^T [Yp; Ym] = [L_v; L_mu];   Hh and (L_phi, L_mu, L_w) as above, Hh starting from b3 wt (x) wx . h.
+// G and Hh are Euclidean derivatives with respect to the entries of u (no division by quadrature weights): row 0 has
+// wt = 0 but drives step 0, the last row drives no step and keeps its b3 term alone.  One solve per step (ORDER 1), one
+// tangent and two transposed solves (ORDER 2).  The clip is the identity, as in k1d_tangent.  Every reduction runs in
+// block_red's order: a trajectory's results do not depend on the batch.
+// ---------------------------------------------------------------------------------
+struct Hv1Args {
+    const double *phi; long phi_s;      // base point: state history, stride per trajectory (0 = one base for the batch)
+    const double *u; long u_s;          // control (or NULL = zeros)
+    const double *pq; long pq_s;        // phi_Q (or NULL)
+    const double *pt; long pt_s;        // phi_T (or NULL)
+    const double *hd; long hs;          // direction [B][hs] (NULL allowed with ORDER 1)
+    const double *dts, *wt, *wx, *wts;  // [rows-2], [rows] trapezoid weights of t, [n] of x, [B][3] = {b1, b2, b3}
+    double *g, *hv;                     // G, Hh [B][hs] (hv: ORDER 2)
+    double *v, *mean;                   // ORDER 2: v_k [B][hs], removed means [B][rows]
+    double *dots;                       // [B][2] = {sum G h, sum h Hh}
+};
+
+template <int ORDER>
+__global__ __launch_bounds__(T1) void k1d_hessvec(Phys1 P, int n, double h, int lvl, int rows, Hv1Args G, double *scratch) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    __shared__ double sk[2 * (T1 / 64)];
+    const int b = blockIdx.x, tid = threadIdx.x, M = rows - 2;
+    const double a = 1.0 / (h * h);
+    double *q = scratch + (long)b * NSCR1 * n;
+    double *lphi = q, *lmu = q + n, *lw = q + 2 * n, *rv = q + 3 * n, *yp = q + 4 * n, *ym = q + 5 * n;
+    double *Lphi = q + 6 * n, *Lmu = q + 7 * n, *Lw = q + 8 * n, *Rv = q + 9 * n, *Yp = q + 10 * n, *Ym = q + 11 * n;
+    const double *ph = G.phi + b * G.phi_s;
+    const double *uu = G.u ? G.u + b * G.u_s : nullptr;
+    const double *pq = G.pq ? G.pq + b * G.pq_s : nullptr;
+    const double *pt = G.pt ? G.pt + b * G.pt_s : nullptr;
+    const double *hd = G.hd ? G.hd + b * G.hs : nullptr;
+    double *g = G.g + b * G.hs, *hv = ORDER == 2 ? G.hv + b * G.hs : nullptr;
+    double *vb = ORDER == 2 ? G.v + b * G.hs : nullptr, *mean = ORDER == 2 ? G.mean + (long)b * rows : nullptr;
+    const double b1 = G.wts[3 * b], b2 = G.wts[3 * b + 1], b3 = G.wts[3 * b + 2];
+    for (int row = 0; row < rows; ++row) {
+        const long o = (long)row * n;
+        const double wr = G.wt[row];
+        for (int i = tid; i < n; i += T1) {
+            const double w = b3 * (wr * G.wx[i]);
+            g[o + i] = w * (uu ? uu[o + i] : 0.0);
+            if (ORDER == 2) hv[o + i] = w * hd[o + i];
+        }
+    }
+    if (ORDER == 2) {
+        // the order-1 tangent march of k1d_tangent, on the planes the second sweep takes over afterwards
+        double *dphi = Lphi, *dmu = Lmu, *dw = Lw, *rp = Rv, *rm = Yp, *nphi = Ym, *nmu = q + 12 * n;
+        for (int i = tid; i < n; i += T1) dphi[i] = dmu[i] = dw[i] = 0.0;
+        __syncthreads();
+        for (int s = 0; s < M; ++s) {
+            const double dt = G.dts[s], gdt = P.gamma / dt;
+            const double *ps = ph + (long)(s + 2) * n;
+            const double *h0 = hd + (long)s * n, *h1 = h0 + n;
+            for (int i = tid; i < n; i += T1) {
+                const double wo = dw[i], wn = ((gdt - 0.5) * wo + 0.5 * (h1[i] + h0[i])) / (gdt + 0.5);
+                const double d = dphi[i];
+                rp[i] = (P.tau / dt) * d + 0.5 * P.kappa * lap1(dphi, i, n, a) + 2.0 * P.c2 * d + 0.5 * dmu[i] + 0.5 * (wn + wo);
+                rm[i] = d / dt + 0.5 * lap1(dmu, i, n, a);
+                dw[i] = wn;
+            }
+            __syncthreads();
+            SysArgs A{ps, rp, rm, dt, a, P.tau, P.c1, P.c2, P.kappa, n};
+            cr_solve<0>(A, lvl, lds, nphi, nmu);
+            double ms = 0.0;
+            for (int i = tid; i < n; i += T1) ms += ((i == 0 || i == n - 1) ? 0.5 : 1.0) * h * nphi[i];
+            const double m1 = block_red<0>(ms, sk) / P.Lx;
+            for (int i = tid; i < n; i += T1) {
+                const double v = nphi[i];
+                vb[(long)(s + 2) * n + i] = v;
+                dphi[i] = v - m1;
+                dmu[i] = nmu[i];
+            }
+            if (tid == 0) mean[s] = m1;
+            __syncthreads();
+        }
+    }
+    for (int i = tid; i < n; i += T1) {
+        lphi[i] = lmu[i] = lw[i] = 0.0;
+        if (ORDER == 2) Lphi[i] = Lmu[i] = Lw[i] = 0.0;
+    }
+    __syncthreads();
+    for (int k = M - 1; k >= 0; --k) {
+        const double dt = G.dts[k], gdt = P.gamma / dt, al = (gdt - 0.5) / (gdt + 0.5), be = 0.5 / (gdt + 0.5);
+        const long o = (long)(k + 2) * n;
+        const double *ps = ph + o;
+        const double wb = G.wt[k + 2] * b1, mk = ORDER == 2 ? mean[k] : 0.0;
+        const bool term = k == M - 1;
+        double S[ORDER];
+        for (int j = 0; j < ORDER; ++j) S[j] = 0.0;
+        for (int i = tid; i < n; i += T1) {
+            const double w = G.wx[i], p = ps[i];
+            double l = lphi[i] + wb * (w * (p - (pq ? pq[o + i] : 0.0)));
+            if (term) l += b2 * (w * (p - (pt ? pt[i] : 0.0)));
+            lphi[i] = l;
+            S[0] += l;
+            if (ORDER == 2) {
+                const double d = vb[o + i] - mk;
+                double L = Lphi[i] + wb * (w * d);
+                if (term) L += b2 * (w * d);
+                Lphi[i] = L;
+                S[ORDER - 1] += L;
+            }
+        }
+        block_sums<ORDER>(S, sk);
+        for (int i = tid; i < n; i += T1) rv[i] = lphi[i] - G.wx[i] * (S[0] / P.Lx);
+        __syncthreads();
+        SysArgs A{ps, rv, lmu, dt, a, P.tau, P.c1, P.c2, P.kappa, n};
+        cr_solve<2>(A, lvl, lds, yp, ym);
+        if (ORDER == 2) {
+            for (int i = tid; i < n; i += T1) {
+                const double p = ps[i], om = 1.0 - p * p;
+                Rv[i] = (Lphi[i] - G.wx[i] * (S[ORDER - 1] / P.Lx)) - P.c1 * (4.0 * p / (om * om)) * (yp[i] * vb[o + i]);
+            }
+            __syncthreads();
+            SysArgs A2{ps, Rv, Lmu, dt, a, P.tau, P.c1, P.c2, P.kappa, n};
+            cr_solve<2>(A2, lvl, lds, Yp, Ym);
+        }
+        // the multipliers of the step before, and this step's share of rows k and k+1 (each thread its own nodes)
+        const double kd = P.tau / dt + 2.0 * P.c2;
+        for (int i = tid; i < n; i += T1) {
+            const double y = yp[i], ldw = 0.5 * y + lw[i];
+            g[(long)k * n + i] += be * ldw;
+            g[(long)(k + 1) * n + i] += be * ldw;
+            lphi[i] = kd * y + 0.5 * P.kappa * lap1t(yp, i, n, a) + ym[i] / dt;
+            lmu[i] = 0.5 * y + 0.5 * lap1t(ym, i, n, a);
+            lw[i] = 0.5 * y + al * ldw;
+            if (ORDER == 2) {
+                const double Y = Yp[i], Ldw = 0.5 * Y + Lw[i];
+                hv[(long)k * n + i] += be * Ldw;
+                hv[(long)(k + 1) * n + i] += be * Ldw;
+                Lphi[i] = kd * Y + 0.5 * P.kappa * lap1t(Yp, i, n, a) + Ym[i] / dt;
+                Lmu[i] = 0.5 * Y + 0.5 * lap1t(Ym, i, n, a);
+                Lw[i] = 0.5 * Y + al * Ldw;
+            }
+        }
+        __syncthreads();
+    }
+    // sum G h and sum h Hh as plain node sums: rows in order per thread, then one reduction
+    double D[2] = {0.0, 0.0};
+    if (hd)
+        for (int row = 0; row < rows; ++row) {
+            const long o = (long)row * n;
+            for (int i = tid; i < n; i += T1) {
+                const double hh = hd[o + i];
+                D[0] += g[o + i] * hh;
+                if (ORDER == 2) D[1] += hh * hv[o + i];
+            }
+        }
+    block_sums<2>(D, sk);
+    if (tid == 0) {
+        G.dots[2 * b] = hd ? D[0] : (double)NAN;
+        G.dots[2 * b + 1] = ORDER == 2 ? D[1] : (double)NAN;
     }
 }
 

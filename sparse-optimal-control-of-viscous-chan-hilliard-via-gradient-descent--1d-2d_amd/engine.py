@@ -654,20 +654,11 @@ class Engine1D:
     SECOND_ORDER_KEYS = Engine2D.SECOND_ORDER_KEYS
     RESIDENT = "resident"
 
-    def second_order(self, h, t_hist, opt, phi_hist=None, u=None, phi_Q=None, phi_T=None, dt=None, x=None, order=2,
-                     histories=False, shared_base=False):
-        """Exact J'(u)h and J''(u)[h,h] of the smooth part J1 + J2 + J3 (vch1d_second_order): one tangent march per
-        direction on the device, two linear solves per step, no finite differences and no nonlinear march.
-        h: (B, rows, N+1) directions, rows = M + 2 = len(t_hist).  phi_hist None: the resident history (last forward() or
-        the PGD iterate).  u / phi_Q / phi_T: arrays, None (zeros) or Engine1D.RESIDENT (the PGD's control / targets).
-        shared_base=True: phi_hist, u, phi_Q are (rows, N+1) and phi_T (N+1,), one base point for all B directions (of
-        resident arrays, trajectory 0's).  dt None: t_hist[n+2] - t_hist[n+1]; x None: the engine's grid.  opt: one
-        parameter object or a sequence of B (only b1, b2, b3 are read).
-        Returns a dict of [B] arrays: the six scalars of SECOND_ORDER_KEYS, slope = s_state + s_ctrl, curvature = c_gn +
-        c_state + c_ctrl (NaN with order=1), `stats`, and with histories=True dphi, d2phi (B, rows, N+1)."""
+    def _base_point(self, t_hist, phi_hist, u, phi_Q, phi_T, dt, x, opt, shared_base):
+        """The arguments second_order and hessvec share, checked and as ctypes pointers: (t_hist, rows, n_base,
+        [(array kept alive, pointer)] of phi_hist / u / phi_Q / phi_T, dt, x, the OptParams array)."""
         t_hist = np.ascontiguousarray(t_hist, dtype=np.float64)
         rows = int(t_hist.size)
-        h = self._hist(h, rows, "h")
         nb = 1 if shared_base else self.B
         resident = C.cast(C.c_void_p(1), _lib._D)
 
@@ -698,12 +689,27 @@ class Engine1D:
             raise ValueError(f"x must have {self.n} entries")
         seq = list(opt) if isinstance(opt, (list, tuple)) else [opt]
         arr = (OptParams * len(seq))(*[o if isinstance(o, OptParams) else make_opt(o) for o in seq])
+        return t_hist, rows, nb, keep, dt, x, arr
+
+    def second_order(self, h, t_hist, opt, phi_hist=None, u=None, phi_Q=None, phi_T=None, dt=None, x=None, order=2,
+                     histories=False, shared_base=False):
+        """Exact J'(u)h and J''(u)[h,h] of the smooth part J1 + J2 + J3 (vch1d_second_order): one tangent march per
+        direction on the device, two linear solves per step, no finite differences and no nonlinear march.
+        h: (B, rows, N+1) directions, rows = M + 2 = len(t_hist).  phi_hist None: the resident history (last forward() or
+        the PGD iterate).  u / phi_Q / phi_T: arrays, None (zeros) or Engine1D.RESIDENT (the PGD's control / targets).
+        shared_base=True: phi_hist, u, phi_Q are (rows, N+1) and phi_T (N+1,), one base point for all B directions (of
+        resident arrays, trajectory 0's).  dt None: t_hist[n+2] - t_hist[n+1]; x None: the engine's grid.  opt: one
+        parameter object or a sequence of B (only b1, b2, b3 are read).
+        Returns a dict of [B] arrays: the six scalars of SECOND_ORDER_KEYS, slope = s_state + s_ctrl, curvature = c_gn +
+        c_state + c_ctrl (NaN with order=1), `stats`, and with histories=True dphi, d2phi (B, rows, N+1)."""
+        t_hist, rows, nb, keep, dt, x, arr = self._base_point(t_hist, phi_hist, u, phi_Q, phi_T, dt, x, opt, shared_base)
+        h = self._hist(h, rows, "h")
         out = np.empty((self.B, 6))
         d1 = np.empty((self.B, rows, self.n)) if histories else None
         d2 = np.empty((self.B, rows, self.n)) if histories else None
         st = Stats()
         check(self.lib.vch1d_second_order(self.ctx, keep[0][1], keep[1][1], nb, _dp(h), rows, _dp(dt), _dp(t_hist), _dp(x),
-                                          keep[2][1], keep[3][1], arr, len(seq), int(order), _dp(out), _dp(d1), _dp(d2),
+                                          keep[2][1], keep[3][1], arr, len(arr), int(order), _dp(out), _dp(d1), _dp(d2),
                                           C.byref(st)))
         res = {k: out[:, i].copy() for i, k in enumerate(self.SECOND_ORDER_KEYS)}
         res["slope"] = out[:, 0] + out[:, 1]
@@ -712,3 +718,33 @@ class Engine1D:
         if histories:
             res["dphi"], res["d2phi"] = d1, d2
         return res
+
+    def hessvec(self, h, t_hist, opt, phi_hist=None, u=None, phi_Q=None, phi_T=None, dt=None, x=None, order=2,
+                shared_base=False):
+        """Exact gradient field and Hessian-vector product of the smooth part J1 + J2 + J3 of the discrete cost
+        (vch1d_hessvec): transposed tangent sweeps on the device, one launch, one linear solve per step for the gradient,
+        one tangent and two transposed solves per step for H h; no finite differences and no nonlinear march.
+        Arguments as for second_order; h may be None with order=1.
+        Returns dict(grad, hv: (B, rows, N+1); gh = sum(grad h), hHh = sum(h hv): [B], reduced on the device; stats).
+        grad and hv are EUCLIDEAN derivatives with respect to the entries of u, not divided by quadrature weights:
+        J'(u)h = sum(grad * h) and J''(u)[h,h] = sum(h * hv) as plain sums (row 0 has quadrature weight 0 and still a
+        non-zero gradient; the last row holds its b3 term alone).  With order=1 hv is None and hHh NaN; without h, gh is
+        NaN."""
+        t_hist, rows, nb, keep, dt, x, arr = self._base_point(t_hist, phi_hist, u, phi_Q, phi_T, dt, x, opt, shared_base)
+        h = None if h is None else self._hist(h, rows, "h")
+        order = int(order)
+        grad = np.empty((self.B, rows, self.n))
+        hv = np.empty((self.B, rows, self.n)) if order == 2 else None
+        dots = np.empty((self.B, 2))
+        st = Stats()
+        check(self.lib.vch1d_hessvec(self.ctx, keep[0][1], keep[1][1], nb, _dp(h), rows, _dp(dt), _dp(t_hist), _dp(x),
+                                     keep[2][1], keep[3][1], arr, len(arr), order, _dp(grad), _dp(hv), _dp(dots),
+                                     C.byref(st)))
+        return dict(grad=grad, hv=hv, gh=dots[:, 0].copy(), hHh=dots[:, 1].copy(), stats=st.as_dict())
+
+    def exact_gradient(self, t_hist, opt, phi_hist=None, u=None, phi_Q=None, phi_T=None, dt=None, x=None,
+                       shared_base=False):
+        """The exact discrete gradient d(J1+J2+J3)/du as a field (B, rows, N+1): hessvec with order=1 and no direction.
+        Euclidean, see hessvec; on the run-time physical parameters, unlike the hand-derived adjoint of backward()."""
+        return self.hessvec(None, t_hist, opt, phi_hist=phi_hist, u=u, phi_Q=phi_Q, phi_T=phi_T, dt=dt, x=x, order=1,
+                            shared_base=shared_base)["grad"]
