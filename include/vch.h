@@ -297,6 +297,44 @@ int vch2d_second_order(vch2d_ctx *ctx, const double *h, int h_rows, const double
  * it.  Returns M, the steps of that history.  ABI version stays 3: detect this entry point by symbol.  VCH_ERR_STATE without a resident state history that
  * vch2d_forward or vch2d_pgd_init / _iterate of this context wrote. */
 int vch2d_mass_shifts(vch2d_ctx *ctx, double *out /* [B][M] */);
+/* Exact gradient field and Hessian-vector product of the smooth part J1 + J2 + J3 of the DISCRETE cost about the resident
+ * control and state history: the transposed sweep of vch2d_second_order's tangent march (ABI version stays 3:
+ * detect this entry point by symbol).  grad = d(J1+J2+J3)/du and hv = H h are Euclidean fields: J'(u) h = sum grad . h and
+ * J''(u)[h,h] = sum h . hv are plain node sums, the s_state + s_ctrl and c_gn + c_state + c_ctrl of vch2d_second_order
+ * (the reference's hand-derived adjoint r + b3 u is not this field: it carries no quadrature weights and ignores the mass
+ * fix).  The Newton matrix obeys J^T = S J S^-1 with S = diag(-(2/dt) wq, wq), wq the trapezoid weights of the plane as
+ * stored, so every transposed solve is the tangent's own solve between two diagonal scalings: one solve per step for the
+ * gradient, and for H h one tangent solve, one gradient solve and one more transposed solve per step (3 M per trajectory).
+ * The linearised mass fix enters by its transpose, the clip is taken as the identity (as in vch2d_second_order).
+ *   h        [B][h_rows][Nx+1][Ny+1] direction (row rule of a control) or NULL (allowed iff order 1)
+ *   g_rows   rows of the control the gradient refers to: M + 1 about a resident PGD iterate; min(rows of the control, M + 1)
+ *            after vch2d_forward with a control; any of 1..M+1 after a forward without one (the zero control of that many
+ *            rows gives the same march).  Rows (k, k+1) take part in step k only while k < rows - 1 (F2:545-548), so
+ *            sum grad . h equals vch2d_second_order's slope exactly when h_rows == g_rows.
+ *   order    1: gradient only; 2: gradient and H h
+ *   rtol     relative residual at which the linear solves stop (<= 0: 1e-12)
+ *   grad_out [B][g_rows][Nx+1][Ny+1] or NULL;  hv_out [B][h_rows][Nx+1][Ny+1], required iff order 2
+ *   dots_out [B][2] or NULL: { sum grad . h over the rows both have, sum h . hv }, NaN where a factor is missing
+ * Base point, dt, t_hist, x, y, phi_Q, phi_T, opts / n_opts: the rules of vch2d_second_order, in both of its modes; the state
+ * history must be one a march of this context wrote (VCH_ERR_STATE otherwise: the shifts would be unknown).  VCH_ERR_ARG
+ * also for a g_rows that breaks the rule above, NULL h or NULL hv_out at order 2.  Every error is returned before anything
+ * is enqueued, copied or allocated; a failed lazy allocation returns VCH_ERR_NOMEM with the context usable and unchanged.
+ * Device storage, allocated on first use, history layout [B][max_steps+1][plane]: grad, and for order 2 hv, the raw
+ * tangent solves v_k and the tangent after the mean removal -- four histories beyond the direction (the trial-control
+ * scratch), 16.8 GB each at 512^2 x 1000 steps x 8 trajectories.
+ * Stateless like vch2d_second_order: the control, the state history, the adjoint, the shift record, the PGD bookkeeping and
+ * the solver tolerance are left as found; a following vch2d_pgd_iterate is bit for bit that of an uninterrupted run.  No
+ * atomics: up to 32 trajectories, a trajectory's outputs are bitwise those of a single-trajectory context, and h == 0 gives
+ * hv exactly zero.  stats (or NULL): launches, looks, linear solves (B M for order 1, 3 B M for order 2) and iterations, the
+ * worst final relative residual, device seconds of the call. */
+int vch2d_hessvec(vch2d_ctx *ctx, const double *h /* NULL allowed iff order 1 */, int h_rows, int g_rows,
+                  const double *dt, int M, const double *t_hist, const double *x, const double *y,
+                  const double *phi_Q, const double *phi_T, const vch_opt_params *opts, int n_opts,
+                  int order /* 1: gradient; 2: gradient and H h */, double rtol,
+                  double *grad_out /* [B][g_rows][Nx+1][Ny+1] or NULL */,
+                  double *hv_out   /* [B][h_rows][Nx+1][Ny+1], required iff order 2 */,
+                  double *dots_out /* [B][2] or NULL */,
+                  vch_stats *stats);
 /* Per-trajectory cost scalars {J1,J2,J3,J4,J} of the current iterate on the DEVICE
  * (5*B doubles), for the caller's RCCL all-reduce; returns a device pointer via *ptr_dev. */
 int vch2d_pgd_cost_dev(vch2d_ctx *ctx, double **ptr_dev);

@@ -150,6 +150,85 @@ def exact_second_order_condition_2d(u_star, r_star, phi_star, x, y, t_hist,
     return out
 
 
+def free_set(u_star, u_min, u_max, tol=1e-8):
+    """Nodes where the critical cone is a linear space: strictly inside the box and off the kink of the L1 term, with the
+    `tol` of `_generate_direction` (whose rules leave exactly these nodes free whatever the adjoint is)."""
+    u_star = np.asarray(u_star)
+    return (u_star > u_min + tol) & (u_star < u_max - tol) & (np.abs(u_star) > tol)
+
+
+def reduced_hessian_extremes_2d(u_star, x, y, t_hist, opt_config: Optional[OptimizationConfig] = None, b1=None, b2=None,
+                                b3=None, phi_Q_target=None, phi_T_target=None, u_min: float = -np.inf,
+                                u_max: float = np.inf, k: int = 30, seed=None, tol: float = 1e-8,
+                                fwd_config: Optional[ForwardSolverConfig] = None) -> dict:
+    """Extreme eigenvalues of the reduced Hessian P H P of the smooth part J1 + J2 + J3 of the discrete cost at `u_star`,
+    by host Lanczos with full reorthogonalisation.  H is the exact Euclidean Hessian with respect to the entries of u
+    (Engine2D.hessvec: one tangent and two transposed solves per time step); P masks to the free set
+    `free_set(u_star, u_min, u_max, tol)`.  One forward march of u*, as in `exact_second_order_condition_2d`, then one
+    hessvec call per Lanczos step.  At most min(k, size of the free set) steps; with k >= that size the Ritz values are all
+    eigenvalues of P H P on the free set.
+
+    Returns dict(theta_min, theta_max: the extreme Ritz values; res_min, res_max: their residual norms
+    |beta_m s_m| (an eigenvalue of P H P lies within that distance of each); ritz: all Ritz values, ascending; n_free: the
+    size of the free set; steps: Lanczos steps taken).  The values are Rayleigh quotients h.Hh / h.h in the Euclidean
+    norm of h, the scale of the curvatures `exact_second_order_condition_2d` returns for its unit directions; theta_min is
+    not larger than any of those whose direction is supported on the free set.
+
+    What is left out.  The second-order sufficient condition asks for coercivity on the critical cone.  On the free set
+    the cone is a linear space and the smallest eigenvalue is the coercivity constant there, which random directions only
+    bound from above.  At a node on the kink u* = 0 of kappa |u|_1 the cone admits one sign at most, and at a node on the
+    active box it admits the inward sign only: there the cone is a half-line or a point per node, the minimum of the
+    quadratic form over it is no eigenvalue problem, and the L1 term adds no curvature along an admitted sign.  Those
+    nodes are pinned to zero here, so theta_min bounds the cone's constant from above: a cone direction that mixes free
+    and one-signed nodes can still see less curvature.  The sparsity parameter therefore does not enter.  The clip of the
+    march is taken as inactive, as in `exact_second_order_condition_2d`."""
+    from ..engine import time_grid
+    from ._ctx import engine_for_config
+    from .Forward2_solver import init_phi_random, DELTA_SEP
+    rng = np.random.default_rng(seed)
+    opt = _ensure_opt_config(b1, b2, b3, 0.0, opt_config)
+    cfg = fwd_config
+    t_grid, dts = time_grid(float(cfg.T), float(cfg.dt_initial))
+    M = len(dts)
+    u_star = np.asarray(u_star, dtype=np.float64)[:M + 1]           # rows beyond the march are never read (F2:545-548)
+    mask = free_set(u_star, u_min, u_max, tol)
+    n_free = int(mask.sum())
+    if n_free == 0:
+        raise ValueError("reduced_hessian_extremes_2d: the free set is empty")
+    phi0 = init_phi_random(int(cfg.Nx), int(cfg.Ny), DELTA_SEP, amp=0.1, seed=42)
+    eng = engine_for_config(cfg, batch=1, max_steps=max(M, 1))
+    one = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a)[None])
+    eng.forward(one(phi0), dts, u=one(u_star), store=False)
+    pq = None if phi_Q_target is None else one(np.asarray(phi_Q_target)[:M + 1])
+    pt = one(phi_T_target)
+
+    def apply(q):
+        res = eng.hessvec(one(q), dts, t_grid, opt, phi_Q=pq, phi_T=pt, x=x, y=y)
+        return np.where(mask, res["hv"][0], 0.0)
+
+    q = np.where(mask, rng.standard_normal(u_star.shape), 0.0)
+    q /= np.linalg.norm(q)
+    Q, alphas, betas = [q], [], []
+    steps = min(int(k), n_free)
+    for j in range(steps):
+        w = apply(Q[j])
+        alphas.append(float(np.sum(Q[j] * w)))
+        for _ in range(2):                                   # full reorthogonalisation, twice is enough
+            for v in Q:
+                w -= np.sum(v * w) * v
+        beta = float(np.linalg.norm(w))
+        betas.append(beta)
+        if j + 1 == steps or beta <= 1e-14 * max(abs(a) for a in alphas):     # done, or an invariant subspace
+            break
+        Q.append(w / beta)
+    m = len(alphas)
+    T = np.diag(alphas) + np.diag(betas[:m - 1], 1) + np.diag(betas[:m - 1], -1)
+    theta, S = np.linalg.eigh(T)
+    resid = np.abs(betas[m - 1] * S[m - 1])
+    return dict(theta_min=float(theta[0]), theta_max=float(theta[-1]), res_min=float(resid[0]), res_max=float(resid[-1]),
+                ritz=theta, n_free=n_free, steps=m)
+
+
 def sparsity_statistics(u_optimal, r_optimal, kappa: float, tol: float = 1e-6):
     """Counts behind the KKT sparsity check `u* = 0 <=> |r*| <= kappa`: (nodes with |u*| < tol, nodes with
     |r*| <= kappa, nodes where the two predicates agree, nodes in total)."""

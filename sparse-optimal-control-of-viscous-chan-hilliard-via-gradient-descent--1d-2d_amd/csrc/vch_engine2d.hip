@@ -206,6 +206,10 @@ struct vch2d_ctx {
     // under (0: none)
     double *tan_part = nullptr, *tan_lvl = nullptr, *tan_t = nullptr, *tan_out = nullptr;
     int fwd_u_rows = 0;
+    // vch2d_hessvec (lazy): histories of G, H h, the raw tangent solves v_k and the tangent after the mean removal; one
+    // block {partials [2][B][nblk][NPART], time weights [Mmax+1], dots [B][2]}
+    double *hv_G = nullptr, *hv_H = nullptr, *hv_V = nullptr, *hv_DP = nullptr, *hv_part = nullptr, *hv_wt = nullptr,
+           *hv_dots = nullptr;
     bool res_pgd = false;                 // the resident state history is the resident PGD problem's iterate
     vch_pgd_state pgd;                    // the line search's books and the error metrics of the driver loop (vch_pgd.h)
     std::vector<double> J_host;           // [B][5] cost terms of the accepted iterate, the source of J_dev and the ring
@@ -630,7 +634,7 @@ extern "C" void vch2d_destroy(vch2d_ctx *c) {
                      c->phiT, c->phi0, c->wts_mass, c->W_cost, c->part, c->part_mass, c->hist_dev, c->shift_hist, c->shift_trial, c->alpha_dev, c->opt_tab, c->seam_tab, c->J_dev, c->Q1f,
                      c->Q2f, c->Q1s, c->Q2s, c->mf, c->ms, c->phi_hist, c->u_hist, c->u_trial, c->phi_trial, c->phiQ,
                      c->r_hist, c->p_hist, c->q_hist, c->cost_part, c->cost_lvl, c->tfrac_dev, c->tan_part, c->tan_lvl, c->tan_t,
-                     c->tan_out};
+                     c->tan_out, c->hv_G, c->hv_H, c->hv_V, c->hv_DP, c->hv_part};
     for (double *q : all)
         if (q) hipFree(q);
     hipFree(c->st);
@@ -2468,54 +2472,227 @@ static int second_order_core(vch2d_ctx *c, const double *h, int h_rows, const do
     return reset_counters(c);       // the records as the end of a PGD iteration leaves them
 }
 
+// The argument rules vch2d_second_order and vch2d_hessvec share, in the order their messages are pinned: checked before
+// anything is enqueued or any resident state changes.  fn = the calling entry point's name.  With a resident PGD problem
+// NULL dt / t_hist are replaced by the problem's.
+#define TANCHK(cond, msg)                                                  \
+    do {                                                                   \
+        if (!(cond)) return vch_fail(VCH_ERR_ARG, "%s: %s", fn, msg);      \
+    } while (0)
+static int tan_check_state(const vch2d_ctx *c, const char *fn) {
+    if (c->M_res < 1 || !c->phi_hist)
+        return vch_fail(VCH_ERR_STATE, "%s: no resident state history (call vch2d_forward or vch2d_pgd_init first)", fn);
+    return 0;
+}
+static int tan_check_args(const vch2d_ctx *c, const char *fn, int h_rows, const double **dt, int M, const double **t_hist,
+                          const double *x, const double *y, const double *phi_Q, const double *phi_T,
+                          const vch_opt_params *opts, int n_opts, int order, bool *pgd_out) {
+    TANCHK(M == c->M_res, "M differs from the steps of the resident state history");
+    TANCHK(n_opts == 1 || n_opts == c->B, "n_opts must be 1 or the context's batch");
+    TANCHK(order == 1 || order == 2, "order must be 1 or 2");
+    TANCHK(h_rows >= 1 && h_rows <= c->Mmax + 1, "direction rows out of range (1..max_steps+1)");
+    for (int b = 0; b < c->B; ++b)
+        if (const char *bad = vch_pgd_check_weights(opts, n_opts, b))
+            return vch_fail(VCH_ERR_ARG, "%s: trajectory %d: %s", fn, b, bad);
+    const bool pgd = c->pgd_ready && c->res_pgd;
+    if (pgd) {
+        TANCHK(!phi_Q && !phi_T, "the resident problem's targets are used: pass phi_Q = phi_T = NULL");
+        if (x) for (int i = 0; i <= c->prm.Nx; ++i) TANCHK(x[i] == c->xg[i], "x differs from the resident problem's grid");
+        if (y) for (int j = 0; j <= c->prm.Ny; ++j) TANCHK(y[j] == c->yg[j], "y differs from the resident problem's grid");
+        if (!*dt) *dt = c->dt.data();
+        if (!*t_hist) *t_hist = c->t_hist.data();
+    } else {
+        TANCHK(*dt && *t_hist && x && y, "NULL dt, t_hist, x or y without a resident problem");
+    }
+    for (int k = 0; k < M; ++k) TANCHK((*dt)[k] > 0, "dt must be positive");
+    *pgd_out = pgd;
+    return 0;
+}
+// The targets and cost weights of the call on the device: the resident problem's, or the caller's (NULL = zeros).
+static int tan_targets(vch2d_ctx *c, bool pgd, const double *x, const double *y, const double *phi_Q, const double *phi_T, int M,
+                       const double **pq, const double **pt) {
+    *pq = *pt = nullptr;
+    if (pgd) {
+        *pq = c->phiQ;
+        *pt = c->phiT;
+        return 0;
+    }
+    VCHCHK(set_cost_weights(c, x, y));
+    if (phi_Q) {
+        VCHCHK(ensure_hist(c, &c->phiQ));
+        VCHCHK(h2d_hist(c, c->phiQ, phi_Q, M + 1));
+        *pq = c->phiQ;
+    }
+    if (phi_T) {
+        VCHCHK(h2d(c, c->phiT, phi_T, c->B));
+        *pt = c->phiT;
+    }
+    return 0;
+}
+
 extern "C" int vch2d_second_order(vch2d_ctx *c, const double *h, int h_rows, const double *dt, int M, const double *t_hist,
                                   const double *x, const double *y, const double *phi_Q, const double *phi_T,
                                   const vch_opt_params *opts, int n_opts, int order, double rtol, double *out,
                                   double *dphi_hist_out, double *d2phi_hist_out, vch_stats *stats) {
     CTXCHK(c);
     // everything below is checked before anything is enqueued or any resident state changes
-    if (c->M_res < 1 || !c->phi_hist)
-        return vch_fail(VCH_ERR_STATE, "vch2d_second_order: no resident state history (call vch2d_forward or vch2d_pgd_init first)");
+    VCHCHK(tan_check_state(c, __func__));
     ARGCHK(h && opts && out, "NULL h, opts or out");
-    ARGCHK(M == c->M_res, "M differs from the steps of the resident state history");
-    ARGCHK(n_opts == 1 || n_opts == c->B, "n_opts must be 1 or the context's batch");
-    ARGCHK(order == 1 || order == 2, "order must be 1 or 2");
-    ARGCHK(h_rows >= 1 && h_rows <= c->Mmax + 1, "direction rows out of range (1..max_steps+1)");
-    for (int b = 0; b < c->B; ++b)
-        if (const char *bad = vch_pgd_check_weights(opts, n_opts, b))
-            return vch_fail(VCH_ERR_ARG, "vch2d_second_order: trajectory %d: %s", b, bad);
-    const bool pgd = c->pgd_ready && c->res_pgd;
-    if (pgd) {
-        ARGCHK(!phi_Q && !phi_T, "the resident problem's targets are used: pass phi_Q = phi_T = NULL");
-        if (x) for (int i = 0; i <= c->prm.Nx; ++i) ARGCHK(x[i] == c->xg[i], "x differs from the resident problem's grid");
-        if (y) for (int j = 0; j <= c->prm.Ny; ++j) ARGCHK(y[j] == c->yg[j], "y differs from the resident problem's grid");
-        if (!dt) dt = c->dt.data();
-        if (!t_hist) t_hist = c->t_hist.data();
-    } else {
-        ARGCHK(dt && t_hist && x && y, "NULL dt, t_hist, x or y without a resident problem");
-    }
-    for (int k = 0; k < M; ++k) ARGCHK(dt[k] > 0, "dt must be positive");
+    bool pgd = false;
+    VCHCHK(tan_check_args(c, __func__, h_rows, &dt, M, &t_hist, x, y, phi_Q, phi_T, opts, n_opts, order, &pgd));
     const double *pq = nullptr, *pt = nullptr;
-    if (pgd) {
-        pq = c->phiQ;
-        pt = c->phiT;
-    } else {
-        VCHCHK(set_cost_weights(c, x, y));
-        if (phi_Q) {
-            VCHCHK(ensure_hist(c, &c->phiQ));
-            VCHCHK(h2d_hist(c, c->phiQ, phi_Q, M + 1));
-            pq = c->phiQ;
-        }
-        if (phi_T) {
-            VCHCHK(h2d(c, c->phiT, phi_T, c->B));
-            pt = c->phiT;
-        }
-    }
+    VCHCHK(tan_targets(c, pgd, x, y, phi_Q, phi_T, M, &pq, &pt));
     // the solves stop at rtol (relative residual); the context's own tolerance comes back on every path out
     const double keep_tol = c->lin_tol;
     c->lin_tol = rtol > 0 ? rtol : 1e-12;
     const int rc = second_order_core(c, h, h_rows, dt, M, t_hist, pq, pt, opts, n_opts, order, out, dphi_hist_out, d2phi_hist_out,
                                      stats);
+    c->lin_tol = keep_tol;
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------
+// exact gradient field and Hessian-vector product: the transposed sweep of the tangent march (kernels: "Transposed
+// (adjoint) sweep" in vch_kernels2d.h)
+// ------------------------------------------------------------------------------------
+static int hessvec_core(vch2d_ctx *c, const double *h, int h_rows, int g_rows, const double *dt, int M, const double *t_hist,
+                        const double *pq, const double *pt, const vch_opt_params *opts, int n_opts, int order,
+                        double *grad_out, double *hv_out, double *dots_out, vch_stats *stats) {
+    const Geom &G = c->G;
+    const int B = c->B, levels = M + 1;
+    const long hs = hist_stride(c);
+    std::vector<double> wt = trapz_w(t_hist, levels);            // lives until the final synchronisation below
+    wt.resize((size_t)c->Mmax + 1, 0.0);                         // a direction's rows beyond the march carry no weight
+    if (h) VCHCHK(h2d_hist(c, c->u_trial, h, h_rows));           // the direction lives in the trial-control scratch
+    VCHCHK(write_opt_tab(c, c->seam_tab, opts, n_opts));
+    HIPCHK(hipMemcpyAsync(c->hv_wt, wt.data(), sizeof(double) * wt.size(), hipMemcpyHostToDevice, c->stream));
+    VCHCHK(reset_counters(c));
+    HIPCHK(hipEventRecord(c->ev0, c->stream));
+    c->guess_wr = -1;          // the back substitution keeps no increment for a march's starting guesses
+    c->cheb_enq = -1;
+    const int u_rows = c->res_pgd ? levels : std::min(c->fwd_u_rows, levels);
+    const long rec_stride = (long)c->Mmax * SHIFT_REC;
+    const long pstride = (long)B * c->nblk * NPART;
+    auto rec_of = [&](int n) { return c->shift_res ? (const double *)c->shift_hist + (long)n * SHIFT_REC : (const double *)nullptr; };
+    auto level_of = [&](const double *hist, int lvl) { return hist ? hist + (long)lvl * G.plane : (const double *)nullptr; };
+    LAUNCH(k_hv_init, c->grid, dim3(NTH), G, g_rows, u_rows > 0 ? (const double *)c->u_hist : (const double *)nullptr, u_rows,
+           (const double *)c->hv_wt, (const double *)c->seam_tab, (const double *)c->W_cost, hs, c->hv_G);
+    if (order == 2) {
+        LAUNCH(k_hv_init, c->grid, dim3(NTH), G, h_rows, (const double *)c->u_trial, h_rows, (const double *)c->hv_wt,
+               (const double *)c->seam_tab, (const double *)c->W_cost, hs, c->hv_H);
+        // the order-1 tangent of h, keeping every step's raw solve (v_k) and the field after the mean removal (dphi')
+        double *dphi = c->tmp[0], *dmu = c->tmp[1], *dw[2] = {c->tmp[4], c->tmp[5]};
+        for (int k : {0, 1, 4, 5}) HIPCHK(hipMemsetAsync(c->tmp[k], 0, sizeof(double) * B * G.plane, c->stream));
+        for (int n = 0; n < M; ++n) {
+            const double *phi1 = c->phi_hist + (long)(n + 1) * G.plane;
+            const bool live = n < h_rows - 1;           // F2:545-548
+            TanRhsArgs a1{dphi, dmu, dw[n & 1], dw[(n + 1) & 1], live ? c->u_trial + (long)n * G.plane : (const double *)nullptr,
+                          live ? c->u_trial + (long)(n + 1) * G.plane : (const double *)nullptr, phi1, hs, nullptr, nullptr,
+                          nullptr, nullptr, rec_of(n), rec_stride, nullptr};
+            LAUNCH((k_tan_rhs<0>), c->grid, dim3(NTH), G, c->P, a1, dt[n], c->Rphi_s, c->rhs_s, c->D_s, c->part);
+            VCHCHK(tangent_solve(c, dt[n], phi1, rec_of(n)));
+            LAUNCH(k_hv_keep, c->grid, dim3(NTH), G, (const double *)c->xf, (const double *)c->dmu, phi1, hs, rec_of(n), rec_stride,
+                   (const double *)c->part_mass, c->P.LxLy, c->hv_V + (long)n * G.plane, c->hv_DP + (long)(n + 1) * G.plane, dphi,
+                   dmu);
+        }
+    }
+    // the two sweeps in lockstep: multipliers of the gradient in tmp[0..2], of H h in tmp[3..5]; partials of the
+    // transposed fix in the two halves of hv_part
+    const int nsweep = order == 2 ? 2 : 1;
+    auto emit = [&](int sw, int k /* the step just solved, M = the start */) -> int {
+        const int lvl = k;                                       // the level whose multipliers this launch leaves
+        const bool start = k == M;
+        const double dtk = start ? 1.0 : dt[k], gdt = c->P.gamma / dtk;
+        const int rows = sw == 0 ? g_rows : h_rows;
+        double *out = sw == 0 ? c->hv_G : c->hv_H;
+        const bool live = !start && k < rows - 1;                // F2:545-548
+        const double *src_a = lvl == 0 ? nullptr : (sw == 0 ? level_of(c->phi_hist, lvl) : level_of(c->hv_DP, lvl));
+        HvEmitArgs a{start ? nullptr : (const double *)c->xf, start ? nullptr : (const double *)c->dmu,
+                     c->tmp[3 * sw], c->tmp[3 * sw + 1], c->tmp[3 * sw + 2],
+                     live ? out + (long)k * G.plane : nullptr, live ? out + (long)(k + 1) * G.plane : nullptr,
+                     src_a, (sw == 0 && lvl > 0) ? level_of(pq, lvl) : nullptr, sw == 0 ? pt : nullptr, lvl == M ? 1 : 0, hs,
+                     wt[lvl], (const double *)c->seam_tab, (const double *)c->W_cost, (const double *)c->wts_mass,
+                     lvl > 0 ? level_of(c->phi_hist, lvl) : nullptr, lvl > 0 ? rec_of(lvl - 1) : nullptr, rec_stride,
+                     c->hv_part + sw * pstride, dtk, c->P.tau / dtk + 2.0 * c->P.c2, 0.5 * c->P.kappa,
+                     (gdt - 0.5) / (gdt + 0.5), 0.5 / (gdt + 0.5)};
+        LAUNCH(k_hv_emit, c->grid, dim3(NTH), G, a);
+        return 0;
+    };
+    for (int sw = 0; sw < nsweep; ++sw) VCHCHK(emit(sw, M));
+    for (int k = M - 1; k >= 0; --k) {
+        const double *phi1 = c->phi_hist + (long)(k + 1) * G.plane;
+        for (int sw = 0; sw < nsweep; ++sw) {
+            // the second sweep's right-hand side reads y^p of the first from the solver's output plane before its own
+            // solve reuses it (the emit kernel in between leaves that plane alone)
+            HvRhsArgs a{c->tmp[3 * sw], c->tmp[3 * sw + 1], phi1, hs, rec_of(k), rec_stride,
+                        (const double *)(c->hv_part + sw * pstride), (const double *)c->wts_mass,
+                        sw ? (const double *)c->xf : nullptr, sw ? (const double *)(c->hv_V + (long)k * G.plane) : nullptr};
+            if (sw == 0) LAUNCH((k_hv_rhs<0>), c->grid, dim3(NTH), G, c->P, a, dt[k], c->Rphi_s, c->rhs_s, c->D_s, c->part);
+            else LAUNCH((k_hv_rhs<1>), c->grid, dim3(NTH), G, c->P, a, dt[k], c->Rphi_s, c->rhs_s, c->D_s, c->part);
+            VCHCHK(tangent_solve(c, dt[k], phi1, nullptr));
+            VCHCHK(emit(sw, k));
+        }
+    }
+    if (dots_out) {
+        if (h)
+            LAUNCH(k_hv_dots, c->grid, dim3(NTH), G, (const double *)c->hv_G, g_rows, (const double *)c->u_trial, h_rows,
+                   order == 2 ? (const double *)c->hv_H : (const double *)nullptr, hs, c->hv_part);
+        LAUNCH(k_hv_dots_fin, dim3(B), dim3(64), (const double *)c->hv_part, c->nblk, h ? 1 : 0, order == 2 ? 1 : 0, c->hv_dots);
+    }
+    HIPCHK(hipEventRecord(c->ev1, c->stream));
+    if (dots_out) HIPCHK(hipMemcpyAsync(dots_out, c->hv_dots, sizeof(double) * 2 * B, hipMemcpyDeviceToHost, c->stream));
+    VCHCHK(sync_state(c));
+    if (grad_out) VCHCHK(d2h_hist(c, grad_out, c->hv_G, g_rows));
+    if (order == 2) VCHCHK(d2h_hist(c, hv_out, c->hv_H, h_rows));
+    float ms = 0;
+    hipEventElapsedTime(&ms, c->ev0, c->ev1);
+    fill_stats(c, stats, ms);
+    return reset_counters(c);       // the records as the end of a PGD iteration leaves them
+}
+
+extern "C" int vch2d_hessvec(vch2d_ctx *c, const double *h, int h_rows, int g_rows, const double *dt, int M,
+                             const double *t_hist, const double *x, const double *y, const double *phi_Q, const double *phi_T,
+                             const vch_opt_params *opts, int n_opts, int order, double rtol, double *grad_out, double *hv_out,
+                             double *dots_out, vch_stats *stats) {
+    CTXCHK(c);
+    // everything below is checked before anything is enqueued, copied or allocated
+    VCHCHK(tan_check_state(c, __func__));
+    ARGCHK(opts, "NULL opts");
+    bool pgd = false;
+    VCHCHK(tan_check_args(c, __func__, h ? h_rows : 1, &dt, M, &t_hist, x, y, phi_Q, phi_T, opts, n_opts, order, &pgd));
+    ARGCHK(h || order == 1, "NULL h with order 2");
+    ARGCHK(order == 1 || hv_out, "NULL hv_out with order 2");
+    if (!c->shift_res)
+        return vch_fail(VCH_ERR_STATE, "vch2d_hessvec: the resident state history is not one a march of this context wrote");
+    if (c->res_pgd) ARGCHK(g_rows == M + 1, "g_rows must be M + 1 about a resident PGD iterate");
+    else if (c->fwd_u_rows > 0) ARGCHK(g_rows == std::min(c->fwd_u_rows, M + 1), "g_rows differs from the rows of the march's control");
+    else ARGCHK(g_rows >= 1 && g_rows <= M + 1, "g_rows out of range (1..M+1)");
+    // lazy storage next: a failed allocation leaves the context as it was
+    VCHCHK(ensure_hist(c, &c->u_trial));
+    VCHCHK(ensure_hist(c, &c->hv_G));
+    if (order == 2) {
+        VCHCHK(ensure_hist(c, &c->hv_H));
+        VCHCHK(ensure_hist(c, &c->hv_V));
+        VCHCHK(ensure_hist(c, &c->hv_DP));
+    }
+    if (!pgd && phi_Q) VCHCHK(ensure_hist(c, &c->phiQ));
+    if (!c->hv_part) {
+        double *p = nullptr;
+        const size_t n = (size_t)2 * c->B * c->nblk * NPART + (size_t)c->Mmax + 1 + 2 * (size_t)c->B;
+        if (hipMalloc((void **)&p, n * 8) != hipSuccess) {
+            (void)hipGetLastError();
+            return vch_fail(VCH_ERR_NOMEM, "vch2d_hessvec: hipMalloc of the partials failed");
+        }
+        c->hv_part = p;
+        c->hv_wt = p + (size_t)2 * c->B * c->nblk * NPART;
+        c->hv_dots = c->hv_wt + c->Mmax + 1;
+    }
+    const double *pq = nullptr, *pt = nullptr;
+    VCHCHK(tan_targets(c, pgd, x, y, phi_Q, phi_T, M, &pq, &pt));
+    // the solves stop at rtol (relative residual); the context's own tolerance comes back on every path out
+    const double keep_tol = c->lin_tol;
+    c->lin_tol = rtol > 0 ? rtol : 1e-12;
+    const int rc = hessvec_core(c, h, h_rows, g_rows, dt, M, t_hist, pq, pt, opts, n_opts, order, grad_out, hv_out, dots_out, stats);
     c->lin_tol = keep_tol;
     return rc;
 }

@@ -2855,3 +2855,252 @@ __global__ void k_tan_scalars(int M, const double *__restrict__ lvl, const doubl
     o[4] = b3 * I[4];
     o[5] = I[4];
 }
+
+// ---------------------------------------------------------------------------------
+// Transposed (adjoint) sweep of the tangent march, vch2d_hessvec: the exact gradient field G = d(J1+J2+J3)/du and the
+// Hessian-vector product H h as Euclidean fields.
+//
+// The Newton matrix J = [[Kpp, -I/2], [I/dt, -L/2]] obeys J^T = S J S^-1 with S = diag(-(2/dt) wq, wq), wq = the trapezoid
+// weights of the plane as it is stored (wdev): wq L is symmetric and the off-diagonal blocks are multiples of I.  In the
+// scaled multipliers lam^ = lam / wq every transposed stencil is the plain one again, so a transposed solve is the tangent's
+// own solve chain between two diagonal scalings.  Backward over the steps, k = M-1 .. 0, dt = dt_k:
+//   lam^phi += wt[k+1] b1 (Wc/wq) e[k+1]                                   (+ b2 (Wc/wq) (phi_M - phi_T) at k = M-1)
+//   lam^v    = lam^phi - (wts/wq) sum_int(wq lam^phi) / W_k               (where s_k != 0: transpose of the linearised fix)
+//   J(phi*) [xp; xm] = [ -(dt/2) lam^v ; lam^mu ],   y^p = -(2/dt) xp,  y^m = xm
+//   lam^dw = y^p / 2 + lam^w;   G[k] += beta wq lam^dw,  G[k+1] += beta wq lam^dw            (while k < rows - 1)
+//   lam^  <- ( Kp y^p + y^m / dt,  y^p / 2 + L y^m / 2,  y^p / 2 + alpha lam^dw )
+// Kp = (tau/dt + 2 c2) I + kappa/2 L, alpha = (gamma/dt - 1/2) / (gamma/dt + 1/2), beta = (1/2) / (gamma/dt + 1/2).
+// The second sweep (H h) runs beside the first with the same matrix: its level source is the tangent of h after the mean
+// removal instead of e, and its right-hand side carries - c1 rho(phi*) y^p v_k, v_k the tangent's raw solve of step k.
+// No atomics: every thread updates its own nodes, every sum goes through workgroup partials read in a fixed order.
+// ---------------------------------------------------------------------------------
+struct HvRhsArgs {
+    const double *lphi, *lmu;       // [B][plane] scaled multipliers lam^phi, lam^mu
+    const double *phi1;             // level k+1 of the state history
+    long hist_stride;               // trajectory stride of phi1 and v
+    const double *rec;              // step k's cell of the shift record ([B] cells rec_stride apart), NULL = no shifts
+    long rec_stride;
+    const double *mpart;            // partials {sum_int wq lam^phi, sum_int wts} of the emit kernel that wrote lphi
+    const double *wts;              // the mass fix's weights (one plane)
+    const double *xp1;              // SECOND: xp of the first sweep's solve of this step (y^p = -(2/dt) xp) ...
+    const double *v;                // ... and level k of the history of raw tangent solves
+};
+
+// Right-hand side of a transposed solve in the form k_solve_setup / k_tan_rhs leave: A = -(dt/2) lam^v on the tile and its
+// one-node halo (a pointwise function of the mirrored node), R_phi := -A, rhs := lam^mu - L A, D and the partials
+// {-, sum rhs^2, min D, max D} for k_fin_lin_begin (mode 2).  D and rho are taken at phi* = phi_{k+1} + s_k.
+template <int SECOND>
+__global__ __launch_bounds__(NTH) void k_hv_rhs(Geom G, Phys P, HvRhsArgs a, double dt, double *__restrict__ Rphi,
+                                                double *__restrict__ rhs, double *__restrict__ D, double *__restrict__ part) {
+    TILE_COORDS;
+    __shared__ double sr[(TY + 2) * (TX + 2)];
+    __shared__ double sred[NPART * 4];
+    __shared__ double s_fix[2];
+    constexpr int W = TX + 2;
+    const long pb = b * G.plane, hb = b * a.hist_stride;
+    const double *rec = a.rec ? a.rec + b * a.rec_stride : (const double *)nullptr;
+    const double shift = rec ? rec[0] : 0.0;
+    if (shift != 0.0) {                 // uniform over the workgroup
+        post_sums(a.mpart, nblk, (int)b, s_fix);
+        __syncthreads();
+    }
+    const TanFix tf(s_fix, rec, P.LxLy);
+    const double ys = -2.0 / dt;
+    for (int e = threadIdx.x; e < W * (TY + 2); e += NTH) {
+        const int ly = e / W, lxx = e - ly * W;
+        const int gr = refl(r0 - 1 + ly, G.ns), gc = refl(c0 - 1 + lxx, G.nf);
+        const long o = (long)gr * G.pitch + gc;
+        double v = a.lphi[pb + o];
+        if (tf.mean != 0.0) v -= (a.wts[o] / wdev(gr, gc, G)) * tf.mean;
+        if (SECOND) v -= P.c1 * tan_rho(a.phi1[hb + o] + shift) * (ys * a.xp1[pb + o]) * a.v[hb + o];
+        sr[e] = -(0.5 * dt) * v;
+    }
+    __syncthreads();
+    double acc[4] = {0.0, 0.0, 1e300, -1e300};
+    for (int k = 0; k < TY / 4; ++k) {
+        int ly = ly0 + 4 * k, r = r0 + ly, c = c0 + lx;
+        if (r < G.ns && c < G.nf) {
+            const int p = (ly + 1) * W + lx + 1;
+            const long o = (long)r * G.pitch + c;
+            const double rh = a.lmu[pb + o] - lap_at<W>(sr, p, G.ax, G.ay);
+            const double d = jac_diag(a.phi1[hb + o] + shift, P.tau / dt, P.c1);
+            Rphi[pb + o] = -sr[p];
+            rhs[pb + o] = rh;
+            D[pb + o] = d;
+            acc[1] += rh * rh;
+            acc[2] = fmin(acc[2], d);
+            acc[3] = fmax(acc[3], d);
+        }
+    }
+    const int op[4] = {0, 0, 1, 2};
+    block_reduce_store<4>(acc, op, sred, part + ((long)b * nblk + blk) * NPART);
+}
+
+struct HvEmitArgs {
+    const double *xp, *xm;          // [B][plane] output of the transposed solve; NULL: the start of the sweep (y = 0)
+    double *lphi, *lmu, *lw;        // [B][plane] scaled multipliers, updated in place (every thread its own nodes)
+    double *out_k, *out_k1;         // rows k, k+1 of G or Hh (history layout), NULL = the rows drive no step (F2:545-548)
+    const double *src_a, *src_b;    // the new level's source field src_a - src_b (history layout; src_b NULL = zeros;
+                                    // src_a NULL = no source: level 0)
+    const double *src_T;            // terminal level: [B][plane] target taken off src_a in the b2 term (NULL = zeros)
+    int terminal;
+    long hist_stride;
+    double wt;                      // trapezoid weight in t of the new level
+    const double *opt_tab;          // b1, b2 of every trajectory
+    const double *Wc, *wts;         // the cost's and the mass fix's weights (one plane each)
+    const double *phi_fix;          // the new level of the state history: phi* of the step below it is phi_fix + its shift
+    const double *rec;              // that step's cell of the shift record, NULL = no shifts (or no step below)
+    long rec_stride;
+    double *part;                   // [B][nblk][NPART] partials {sum_int wq lam^phi, sum_int wts} for that step's k_hv_rhs
+    double dt, kp, half_kappa, alpha, beta;
+};
+
+// After a transposed solve: y^, lam^dw, the two row updates of G (or Hh), the multipliers of the level below with that
+// level's source, and the partials of the next step's transposed fix.  Reads xp, xm with a one-node halo.
+__global__ __launch_bounds__(NTH) void k_hv_emit(Geom G, HvEmitArgs a) {
+    TILE_COORDS;
+    __shared__ double sp[(TY + 2) * (TX + 2)];
+    __shared__ double sm[(TY + 2) * (TX + 2)];
+    __shared__ double sred[NPART * 4];
+    constexpr int W = TX + 2;
+    const long pb = b * G.plane, hb = b * a.hist_stride;
+    const bool start = a.xp == nullptr;
+    if (!start) {
+        load_tile<1>(sp, a.xp + pb, G, c0, r0);
+        load_tile<1>(sm, a.xm + pb, G, c0, r0);
+    }
+    __syncthreads();
+    const double *rec = a.rec ? a.rec + b * a.rec_stride : (const double *)nullptr;
+    const double shift = rec ? rec[0] : 0.0;
+    const bool all = rec && rec[1] == 0.0;
+    const double thr = (1.0 - DELTA_SEP) - 5e-3;
+    const double b1 = a.opt_tab[b * OPT_STRIDE + OPT_B1], b2 = a.opt_tab[b * OPT_STRIDE + OPT_B2];
+    const double ys = -2.0 / a.dt;
+    double acc[2] = {0.0, 0.0};
+    for (int k = 0; k < TY / 4; ++k) {
+        int ly = ly0 + 4 * k, r = r0 + ly, c = c0 + lx;
+        if (r < G.ns && c < G.nf) {
+            const int p = (ly + 1) * W + lx + 1;
+            const long o = (long)r * G.pitch + c;
+            const double wq = wdev(r, c, G);
+            double nphi = 0.0, nmu = 0.0, nw = 0.0;
+            if (!start) {
+                const double yp = ys * sp[p], ym = sm[p];
+                const double ldw = 0.5 * yp + a.lw[pb + o];
+                if (a.out_k) {
+                    const double g = a.beta * wq * ldw;
+                    a.out_k[hb + o] += g;
+                    a.out_k1[hb + o] += g;
+                }
+                nphi = a.kp * yp + a.half_kappa * (ys * lap_at<W>(sp, p, G.ax, G.ay)) + ym / a.dt;
+                nmu = 0.5 * yp + 0.5 * lap_at<W>(sm, p, G.ax, G.ay);
+                nw = 0.5 * yp + a.alpha * ldw;
+            }
+            if (a.src_a) {
+                const double sa = a.src_a[hb + o];
+                double s = a.wt * b1 * (sa - (a.src_b ? a.src_b[hb + o] : 0.0));
+                if (a.terminal) s += b2 * (sa - (a.src_T ? a.src_T[pb + o] : 0.0));
+                nphi += (a.Wc[o] / wq) * s;
+            }
+            a.lphi[pb + o] = nphi;
+            a.lmu[pb + o] = nmu;
+            a.lw[pb + o] = nw;
+            if (shift != 0.0 && (all || fabs(a.phi_fix[hb + o] + shift) < thr)) {
+                acc[0] += wq * nphi;
+                acc[1] += a.wts[o];
+            }
+        }
+    }
+    if (shift == 0.0) return;           // uniform over the workgroup: nobody reads the partials of a step without a shift
+    const int op[2] = {0, 0};
+    block_reduce_store<2>(acc, op, sred, a.part + ((long)b * nblk + blk) * NPART);
+}
+
+// The start of the fields: out[lvl] = b3 wt[lvl] Wc src[lvl] for lvl < src_rows (src NULL: none), zeros up to rows.
+__global__ __launch_bounds__(NTH) void k_hv_init(Geom G, int rows, const double *__restrict__ src, int src_rows,
+                                                 const double *__restrict__ wt, const double *__restrict__ opt_tab,
+                                                 const double *__restrict__ Wc, long hist_stride, double *__restrict__ out) {
+    TILE_COORDS;
+    const long hb = b * hist_stride;
+    const double b3 = opt_tab[b * OPT_STRIDE + OPT_B3];
+    for (int k = 0; k < TY / 4; ++k) {
+        int r = r0 + ly0 + 4 * k, c = c0 + lx;
+        if (r < G.ns && c < G.nf) {
+            const long o = (long)r * G.pitch + c;
+            const double w = Wc[o];
+            for (int lvl = 0; lvl < rows; ++lvl) {
+                const long q = hb + (long)lvl * G.plane + o;
+                out[q] = (src && lvl < src_rows) ? (b3 * wt[lvl]) * (w * src[q]) : 0.0;
+            }
+        }
+    }
+}
+
+// Order 2, one step of the tangent of h: keeps the raw solve x (v_k), applies the linearised mass fix (TanFix, sums from
+// k_tan_mass's partials) and stores the fixed field into the history dphi' and the plane the next step reads; dmu' moves on.
+__global__ __launch_bounds__(NTH) void k_hv_keep(Geom G, const double *__restrict__ x, const double *__restrict__ m,
+                                                 const double *__restrict__ phi1, long hist_stride,
+                                                 const double *__restrict__ rec_, long rec_stride,
+                                                 const double *__restrict__ mpart, double LxLy, double *__restrict__ v_k,
+                                                 double *__restrict__ dp_k1, double *__restrict__ dphi,
+                                                 double *__restrict__ dmu) {
+    TILE_COORDS;
+    __shared__ double s_fix[2];
+    const long pb = b * G.plane, hb = b * hist_stride;
+    const double *rec = rec_ ? rec_ + b * rec_stride : (const double *)nullptr;
+    const double shift = rec ? rec[0] : 0.0;
+    if (shift != 0.0) {                 // uniform over the workgroup
+        post_sums(mpart, nblk, (int)b, s_fix);
+        __syncthreads();
+    }
+    const TanFix tf(s_fix, rec, LxLy);
+    for (int k = 0; k < TY / 4; ++k) {
+        int r = r0 + ly0 + 4 * k, c = c0 + lx;
+        if (r < G.ns && c < G.nf) {
+            const long o = (long)r * G.pitch + c;
+            const double v = x[pb + o];
+            const double f = tf.apply(v, phi1[hb + o] + shift);
+            v_k[hb + o] = v;
+            dp_k1[hb + o] = f;
+            dphi[pb + o] = f;
+            dmu[pb + o] = m[pb + o];
+        }
+    }
+}
+
+// Workgroup partials {sum G h over the rows both have, sum h Hh} of a trajectory, the levels summed in order per node.
+__global__ __launch_bounds__(NTH) void k_hv_dots(Geom G, const double *__restrict__ g, int g_rows, const double *__restrict__ h,
+                                                 int h_rows, const double *__restrict__ hv, long hist_stride,
+                                                 double *__restrict__ part) {
+    TILE_COORDS;
+    __shared__ double sred[NPART * 4];
+    const long hb = b * hist_stride;
+    double acc[2] = {0.0, 0.0};
+    for (int k = 0; k < TY / 4; ++k) {
+        int r = r0 + ly0 + 4 * k, c = c0 + lx;
+        if (r < G.ns && c < G.nf) {
+            const long o = (long)r * G.pitch + c;
+            for (int lvl = 0; lvl < h_rows; ++lvl) {
+                const long q = hb + (long)lvl * G.plane + o;
+                const double hh = h[q];
+                if (lvl < g_rows) acc[0] += g[q] * hh;
+                if (hv) acc[1] += hh * hv[q];
+            }
+        }
+    }
+    const int op[2] = {0, 0};
+    block_reduce_store<2>(acc, op, sred, part + ((long)b * nblk + blk) * NPART);
+}
+
+// dots[b] = the two sums from the partials in a fixed order (post_sums); NaN where a factor is missing.  grid = B, 64 threads
+__global__ void k_hv_dots_fin(const double *__restrict__ part, int nblk, int have_h, int have_hv, double *__restrict__ out) {
+    __shared__ double s[2];
+    const int b = blockIdx.x;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    if (have_h) post_sums(part, nblk, b, s);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        out[2 * b] = have_h ? s[0] : nan;
+        out[2 * b + 1] = (have_h && have_hv) ? s[1] : nan;
+    }
+}

@@ -212,6 +212,7 @@ class Engine2D:
         out = self._out(rows=M + 1) if store else None
         st = Stats()
         check(self.lib.vch2d_forward(self.ctx, _dp(phi0), up, rows, _dp(dt), M, _dp(out), C.byref(st)))
+        self._base = ("forward", M, rows if up is not None else 0)      # what hessvec's g_rows=None resolves against
         return (self._sq(out) if store else None), st.as_dict()
 
     def backward(self, phi_hist, t_hist, b1, b2, phi_Q=None, phi_T=None, hx=None, hy=None,
@@ -284,6 +285,7 @@ class Engine2D:
             check(self.lib.vch2d_pgd_init_v(self.ctx, _dp(phi0), _dp(phi_T), _dp(pq), int(bool(ramp)), Tq, _dp(t_hist), M,
                                             _dp(x), _dp(y), arr, len(seq), _dp(uu), _dp(al), _dp(J0)))
         self._pgd_M = M
+        self._base = ("pgd", M, M + 1)
         return J0
 
     def pgd_kkt(self, refresh=True, tol=1e-6):
@@ -307,6 +309,7 @@ class Engine2D:
         sec = np.zeros(5)
         done = check(self.lib.vch2d_pgd_iterate(self.ctx, n, _dp(cost), _dp(alpha), att.ctypes.data_as(_lib._I32),
                                                 _dp(chg), _dp(sec)))
+        self._base = ("pgd", self._pgd_M, self._pgd_M + 1)
         trk, trm = np.full((self.B, n), np.nan), np.full((self.B, n), np.nan)
         check(self.lib.vch2d_pgd_errors(self.ctx, n, _dp(trk), _dp(trm)))
         return dict(iters=done, cost=cost, alpha=alpha, attempts=att, change=chg, tracking_error=trk, terminal_error=trm,
@@ -368,6 +371,64 @@ class Engine2D:
         if histories:
             res["dphi"], res["d2phi"] = d1, d2
         return res
+
+    def hessvec(self, h, dt=None, t_hist=None, opt=None, phi_Q=None, phi_T=None, x=None, y=None, order=2, rtol=0.0,
+                g_rows=None):
+        """Exact gradient field and Hessian-vector product of the smooth part J1 + J2 + J3 of the discrete cost about the
+        resident control and state history (vch2d_hessvec): the transposed sweep of second_order's tangent march, one
+        linear solve per step for the gradient, three for H h; no finite differences and no nonlinear march.
+        Base point and arguments as for second_order (after forward(): dt, t_hist required; after pgd_init() /
+        pgd_iterate(): leave dt, t_hist, x, y, phi_Q, phi_T None).  h: (B, rows, Nx+1, Ny+1) or None with order=1.
+        g_rows: rows of the control the gradient refers to; None resolves to M + 1 about a PGD iterate, to
+        min(rows of the control, M + 1) after forward() with a control, and to M + 1 after a forward() without one.
+        Returns dict(grad (B, g_rows, ..), hv (B, rows, ..) or None, dots (B, 2), slope = sum(grad h), curvature =
+        sum(h hv): [B], reduced on the device, NaN where a factor is missing; stats).  grad and hv are EUCLIDEAN
+        derivatives with respect to the entries of u: J'(u)h = sum(grad * h) and J''(u)[h,h] = sum(h * hv) as plain
+        sums, second_order's slope and curvature when h has g_rows rows."""
+        order = int(order)
+        h = None if h is None else self._hist(h, 0, "h")
+        if dt is None or t_hist is None:
+            if not hasattr(self, "_pgd_M"):
+                raise ValueError("dt and t_hist are required without a resident PGD problem")
+            dt = t_hist = None
+            M = self._pgd_M
+        else:
+            dt = np.ascontiguousarray(dt, dtype=np.float64)
+            t_hist = np.ascontiguousarray(t_hist, dtype=np.float64)
+            M = int(dt.size)
+            if t_hist.size != M + 1:
+                raise ValueError("t_hist must have len(dt) + 1 entries")
+            x = self.x if x is None else x
+            y = self.y if y is None else y
+        if x is not None or y is not None:
+            x = np.ascontiguousarray(self.x if x is None else x, dtype=np.float64)
+            y = np.ascontiguousarray(self.y if y is None else y, dtype=np.float64)
+            if x.shape != (self.Nx + 1,) or y.shape != (self.Ny + 1,):
+                raise ValueError("x, y must have Nx+1, Ny+1 entries")
+        if g_rows is None:
+            kind, _, rows = getattr(self, "_base", ("forward", M, 0))
+            g_rows = M + 1 if (kind == "pgd" or rows == 0) else min(rows, M + 1)
+        g_rows = int(g_rows)
+        pq = None if phi_Q is None else self._hist(phi_Q, M + 1, "phi_Q_target")
+        pt = None if phi_T is None else self._fld(phi_T, "phi_T_target")
+        seq = list(opt) if isinstance(opt, (list, tuple)) else [opt]
+        arr = (OptParams * len(seq))(*[o if isinstance(o, OptParams) else make_opt(o) for o in seq])
+        h_rows = 1 if h is None else int(h.shape[1])
+        grad = np.empty((self.B, max(g_rows, 0)) + self.shape)
+        hv = np.empty((self.B, h_rows) + self.shape) if order == 2 and h is not None else None
+        dots = np.full((self.B, 2), np.nan)
+        st = Stats()
+        check(self.lib.vch2d_hessvec(self.ctx, _dp(h), h_rows, g_rows, _dp(dt), M, _dp(t_hist), _dp(x), _dp(y), _dp(pq),
+                                     _dp(pt), arr, len(seq), order, float(rtol), _dp(grad), _dp(hv), _dp(dots),
+                                     C.byref(st)))
+        return dict(grad=grad, hv=hv, dots=dots, slope=dots[:, 0].copy(), curvature=dots[:, 1].copy(), stats=st.as_dict())
+
+    def exact_gradient(self, dt=None, t_hist=None, opt=None, phi_Q=None, phi_T=None, x=None, y=None, rtol=0.0, g_rows=None):
+        """The exact discrete gradient d(J1+J2+J3)/du about the resident base point as a field (B, g_rows, Nx+1, Ny+1):
+        hessvec with order=1 and no direction.  Euclidean, see hessvec; unlike the hand-derived adjoint of backward() it
+        carries the cost's quadrature weights and the transpose of the mass fix."""
+        return self.hessvec(None, dt=dt, t_hist=t_hist, opt=opt, phi_Q=phi_Q, phi_T=phi_T, x=x, y=y, order=1, rtol=rtol,
+                            g_rows=g_rows)["grad"]
 
     def mass_shifts(self):
         """(B, M): what the march's interior mass fix subtracted at the end of every step of the resident state history
