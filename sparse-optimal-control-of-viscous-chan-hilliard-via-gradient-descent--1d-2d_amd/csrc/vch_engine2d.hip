@@ -162,6 +162,9 @@ struct vch2d_ctx {
     //   VCH_FIN_PUBLISH  the k_fin_residual<1> in front of a look publishes the state itself (no k_publish_state launch)
     //   VCH_CEIL_CELL    the ceiling of a reduction-free solve goes through one cell per trajectory (no k_fin_ceiling launch)
     bool mass_early, fin_publish, ceil_cell_on;
+    // VCH_EVAL_HOIST (default 1; 0 = A/B and tests): k_eval with the step start's operands and the guess tail's planes requested
+    // ahead of the barriers that use them (vch_kernels2d.h); 0 launches k_eval_plain, the same arithmetic without that
+    bool eval_hoist;
     unsigned long long *ceil_cell;        // [B][CeilCell::STRIDE] (vch_kernels2d.h)
     bool cell_now;                        // the level being enqueued uses the cells
     int trial_enq;                        // sweeps of the reduction-free solve the NEXT trial launch arms the trial for (-1: none)
@@ -455,6 +458,7 @@ extern "C" vch2d_ctx *vch2d_create(const vch2d_params *p, int batch, int max_ste
     c->mass_early = env_on("VCH_MASS_EARLY");
     c->fin_publish = env_on("VCH_FIN_PUBLISH");
     c->ceil_cell_on = env_on("VCH_CEIL_CELL");
+    c->eval_hoist = env_on("VCH_EVAL_HOIST");
     c->ceil_cell = nullptr;
     c->cell_now = c->mass_done = false;
     c->trial_enq = -1;
@@ -961,7 +965,8 @@ static int residual_trial(vch2d_ctx *c, double dt, bool inline_dmu, bool fused, 
         EvalFin ef = efin;
         ef.cheb_enq = c->trial_enq;
         c->trial_enq = -1;
-        auto k_trial = fin_inside ? k_eval<2, true> : k_eval<2, false>;
+        auto k_trial = c->eval_hoist ? (fin_inside ? k_eval<2, true> : k_eval<2, false>)
+                                     : (fin_inside ? k_eval_plain<2, true> : k_eval_plain<2, false>);
         LAUNCHC(PC_RESIDUAL, k_trial, c->grid, dim3(NTH), c->G, c->P, c->st, c->slot_stride, c->phi_s, c->mu_s, c->Rphi_s, c->rhs_s,
                 c->D_s, (const double *)c->xf, c->cphi, c->cmu, dt, c->part, (const double *)nullptr, (const double *)nullptr,
                 (const double *)nullptr, 0L, (double *)nullptr, gt, c->x0g, ef, PostArgs{nullptr, nullptr, 0});
@@ -1030,7 +1035,8 @@ static int newton_level(vch2d_ctx *c, double dt, const double *un, const double 
         const PostArgs post_{c->post_pending ? (const double *)c->part_mass : (const double *)nullptr, c->post_hist, hist_stride(c), c->post_rec,
                              (long)c->Mmax * SHIFT_REC};
         c->post_pending = false;
-        auto k_start = fin_inside ? k_eval<0, true> : k_eval<0, false>;
+        auto k_start = c->eval_hoist ? (fin_inside ? k_eval<0, true> : k_eval<0, false>)
+                                     : (fin_inside ? k_eval_plain<0, true> : k_eval_plain<0, false>);
         LAUNCHC(PC_RESIDUAL0, k_start, c->grid, dim3(NTH), c->G, c->P, c->st, c->slot_stride, c->phi_s, c->mu_s, c->Rphi_s, c->rhs_s,
                 c->D_s, (const double *)nullptr, c->cphi, c->cmu, dt, c->part, (const double *)c->w, un, unp1, u_stride, c->wnew, g1_,
                 c->x0g, efin_, post_);

@@ -1629,12 +1629,27 @@ __device__ __forceinline__ void fin_reduce_agent(const double *part, int nblk, i
 // the register cap lifted to fit them all, 122 VGPRs = 4 workgroups per CU: 0.551 s; profiles/r03_fused_ab.txt).
 // FIN_INSIDE: the hand-off variant (VCH_FUSED=1).  The default variant ends with the partials and carries neither the record
 // copy of the fin step (584 B of private memory per thread) nor the counter traffic.
-template <int MODE, bool FIN_INSIDE>
-__global__ __launch_bounds__(NTH, EVAL_MINBLK) void k_eval(Geom G, Phys P, TrajState *st, long slot_stride, double *phi_s, double *mu_s,
-                                              double *Rphi_s, double *rhs_s, double *D_s, const double *dphi, double *cphi,
-                                              double *cmu, double dt, double *part, const double *w, const double *un,
-                                              const double *unp1, long u_stride, double *wnew, GuessArgs ga, double *x0,
-                                              EvalFin fin, PostArgs post) {
+//
+// HOIST (the default; VCH_EVAL_HOIST=0 selects the kernels without it, k_eval_plain): the same is done for the step start
+// and for the guess tail.  Values, expressions and summation orders are those of the plain form, only the place where a load
+// is issued and where a value is kept differs, so the two forms agree bit for bit.
+//   step start   every global operand -- k_mass's partials (first wavefront), raw phi, mu of the old level, w, u_n, u_{n+1}
+//                -- is requested before the first barrier; the partials are summed in post_sums' order behind the requests,
+//                and sp / sm are written from registers behind post_sums' barrier.  The plain form asks for mu, w and the
+//                u pair only behind that barrier: two global latencies in series for every workgroup.
+//   guess tail   plane 0 of the increments is requested behind the last halo-1 pass and arrives under the own-node pass, every
+//                further plane is read with the thread's halo-2 elements in flight together, and the sum is kept in registers
+//                up to the tail's barrier.  D on halo 1 needs no pass and no barrier of its own: MODE 2 writes it into sd in
+//                the last halo-1 pass, which has phi in a register; MODE 0 (no free LDS plane) takes it from sp in front of
+//                the tail's barrier.  (Two planes in flight, or MODE 0's D in registers from the halo-1 pass on, spill at
+//                EVAL_MINBLK workgroups per CU: DESIGN.md 4.)
+constexpr int POST_PU = 5;     // partials of k_mass held per lane of the first wavefront (64 * POST_PU workgroups per round)
+template <int MODE, bool FIN_INSIDE, bool HOIST>
+__device__ __forceinline__ void eval_body(const Geom &G, const Phys &P, TrajState *st, long slot_stride, double *phi_s, double *mu_s,
+                                          double *Rphi_s, double *rhs_s, double *D_s, const double *dphi, double *cphi,
+                                          double *cmu, double dt, double *part, const double *w, const double *un,
+                                          const double *unp1, long u_stride, double *wnew, const GuessArgs &ga, double *x0,
+                                          const EvalFin &fin, const PostArgs &post) {
     TILE_COORDS;
     // only the few fields the evaluation needs are read here; the record as a whole is read, advanced and written back by
     // one thread of the workgroup that finishes last (a per-thread copy of the record would live in private memory)
@@ -1675,53 +1690,165 @@ __global__ __launch_bounds__(NTH, EVAL_MINBLK) void k_eval(Geom G, Phys P, TrajS
     const bool do_guess = gcf[0] != 0.0 && (MODE == 0 || S_iters == 1);
     double rm[TY / 4], rh[TY / 4];
     double acc[5] = {0.0, 0.0, 1e300, -1e300, 0.0};
+    // HOIST, guess tail: D on halo 1 (MODE 0; MODE 2 has sd free for it) and an increment plane on halo 2 (plane 0 in gT[0], every
+    // further one in turn in gT[1]), per thread
+    constexpr int GN2 = W2 * (TY + 4), GI2 = (GN2 + NTH - 1) / NTH, GN1 = (TY + 2) * W1, GI1 = (GN1 + NTH - 1) / NTH;
+    double gD[GI1], gT[2][GI2];
+    auto guess_load = [&](int j) {
+#pragma unroll
+        for (int i = 0; i < GI2; ++i) {
+            const int e = threadIdx.x + i * NTH;
+            gT[j != 0][i] = 0.0;
+            if (e < GN2) {
+                int ly = e / W2, lxx = e - ly * W2;
+                int gr = refl(r0 - 2 + ly, G.ns), gc = refl(c0 - 2 + lxx, G.nf);
+                gT[j != 0][i] = ga.d[j][pb + (long)gr * G.pitch + gc];
+            }
+        }
+    };
     if (MODE == 0) {
         // ---- k_prepare + k_residual<0> ----
         constexpr int N1 = (TY + 2) * W1, I1 = (N1 + NTH - 1) / NTH;      // halo-1 elements, per thread
-        if (post.part) {
-            // the end of the previous step (F2:562-577: clip, mass fix, history) applied to the level as it is loaded: the sums
-            // of k_mass's partials by the first wavefront while everybody's loads are in flight, then the fix in registers
+        double vW[I1], vU0[I1], vU1[I1];
+        if (HOIST) {
             __shared__ double s_post[2];
-            constexpr int I2 = (W2 * (TY + 4) + NTH - 1) / NTH;
-            double raw[I2];
+            constexpr int N2 = W2 * (TY + 4), I2 = (N2 + NTH - 1) / NTH;
+            // k_mass's partials first (the longest dependent chain hangs on them): post_sums' lanes and order, POST_PU
+            // partials per lane in flight instead of one
+            const bool sums = post.part && threadIdx.x < 64;
+            const double *pq = post.part ? post.part + (long)b * nblk * NPART : nullptr;
+            double q0[POST_PU], q1[POST_PU];
+            if (sums) {
+#pragma unroll
+                for (int k = 0; k < POST_PU; ++k) {
+                    const int t = threadIdx.x + 64 * k;
+                    q0[k] = q1[k] = 0.0;
+                    if (t < nblk) {
+                        q0[k] = pq[(long)t * NPART];
+                        q1[k] = pq[(long)t * NPART + 1];
+                    }
+                }
+            }
+            const double mass0 = st[b].mass0;
+            double raw[I2], vM[I1];
 #pragma unroll
             for (int i = 0; i < I2; ++i) {
                 const int e = threadIdx.x + i * NTH;
                 raw[i] = 0.0;
-                if (e < W2 * (TY + 4)) {
+                if (e < N2) {
                     int ly = e / W2, lxx = e - ly * W2;
                     int gr = refl(r0 - 2 + ly, G.ns), gc = refl(c0 - 2 + lxx, G.nf);
                     raw[i] = phi_s[src * slot_stride + pb + (long)gr * G.pitch + gc];
                 }
             }
-            post_sums(post.part, nblk, (int)b, s_post);
-            __syncthreads();
-            const PostFix pf(s_post, st[b].mass0, P.LxLy);
-            if (post.rec && blk == 0 && threadIdx.x == 0) pf.record(post.rec + b * post.rec_stride);
+#pragma unroll
+            for (int i = 0; i < I1; ++i) {                                   // mu first: it goes to LDS with phi
+                const int e = threadIdx.x + i * NTH;
+                vM[i] = 0.0;
+                if (e < N1) {
+                    int ly = e / W1, lxx = e - ly * W1;
+                    int gr = refl(r0 - 1 + ly, G.ns), gc = refl(c0 - 1 + lxx, G.nf);
+                    vM[i] = mu_s[src * slot_stride + pb + (long)gr * G.pitch + gc];
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < I1; ++i) {
+                const int e = threadIdx.x + i * NTH;
+                vW[i] = vU0[i] = vU1[i] = 0.0;
+                if (e < N1) {
+                    int ly = e / W1, lxx = e - ly * W1;
+                    int gr = refl(r0 - 1 + ly, G.ns), gc = refl(c0 - 1 + lxx, G.nf);
+                    long o = (long)gr * G.pitch + gc;
+                    vW[i] = w[pb + o];
+                    vU0[i] = un ? un[b * u_stride + o] : 0.0;
+                    vU1[i] = unp1 ? unp1[b * u_stride + o] : 0.0;
+                }
+            }
+            if (post.part) {
+                if (sums) {
+                    double a0 = 0.0, a1 = 0.0;
+#pragma unroll
+                    for (int k = 0; k < POST_PU; ++k)
+                        if ((int)threadIdx.x + 64 * k < nblk) {
+                            a0 += q0[k];
+                            a1 += q1[k];
+                        }
+                    for (int t = threadIdx.x + 64 * POST_PU; t < nblk; t += 64) {     // grids of more than 64 * POST_PU tiles
+                        a0 += pq[(long)t * NPART];
+                        a1 += pq[(long)t * NPART + 1];
+                    }
+                    a0 = wave_sum(a0);
+                    a1 = wave_sum(a1);
+                    if (threadIdx.x == 0) {
+                        s_post[0] = a0;
+                        s_post[1] = a1;
+                    }
+                }
+                __syncthreads();
+                const PostFix pf(s_post, mass0, P.LxLy);
+                if (post.rec && blk == 0 && threadIdx.x == 0) pf.record(post.rec + b * post.rec_stride);
+#pragma unroll
+                for (int i = 0; i < I2; ++i) raw[i] = pf.apply(raw[i]);
+            }
 #pragma unroll
             for (int i = 0; i < I2; ++i) {
                 const int e = threadIdx.x + i * NTH;
-                if (e < W2 * (TY + 4)) sp[e] = pf.apply(raw[i]);
+                if (e < N2) sp[e] = raw[i];
             }
-        } else {
-            load_tile<2>(sp, phi_s + src * slot_stride + pb, G, c0, r0);
-        }
-        load_tile<1>(sm, mu_s + src * slot_stride + pb, G, c0, r0);          // mu of the old level
-        double vW[I1], vU0[I1], vU1[I1];
 #pragma unroll
-        for (int i = 0; i < I1; ++i) {
-            const int e = threadIdx.x + i * NTH;
-            vW[i] = vU0[i] = vU1[i] = 0.0;
-            if (e < N1) {
-                int ly = e / W1, lxx = e - ly * W1;
-                int gr = refl(r0 - 1 + ly, G.ns), gc = refl(c0 - 1 + lxx, G.nf);
-                long o = (long)gr * G.pitch + gc;
-                vW[i] = w[pb + o];
-                vU0[i] = un ? un[b * u_stride + o] : 0.0;
-                vU1[i] = unp1 ? unp1[b * u_stride + o] : 0.0;
+            for (int i = 0; i < I1; ++i) {
+                const int e = threadIdx.x + i * NTH;
+                if (e < N1) sm[e] = vM[i];
+            }
+        } else {                                                             // the plain form
+            if (post.part) {
+                // the end of the previous step (F2:562-577: clip, mass fix, history) applied to the level as it is loaded: the sums
+                // of k_mass's partials by the first wavefront while everybody's loads are in flight, then the fix in registers
+                __shared__ double s_post[2];
+                constexpr int I2 = (W2 * (TY + 4) + NTH - 1) / NTH;
+                double raw[I2];
+#pragma unroll
+                for (int i = 0; i < I2; ++i) {
+                    const int e = threadIdx.x + i * NTH;
+                    raw[i] = 0.0;
+                    if (e < W2 * (TY + 4)) {
+                        int ly = e / W2, lxx = e - ly * W2;
+                        int gr = refl(r0 - 2 + ly, G.ns), gc = refl(c0 - 2 + lxx, G.nf);
+                        raw[i] = phi_s[src * slot_stride + pb + (long)gr * G.pitch + gc];
+                    }
+                }
+                post_sums(post.part, nblk, (int)b, s_post);
+                __syncthreads();
+                const PostFix pf(s_post, st[b].mass0, P.LxLy);
+                if (post.rec && blk == 0 && threadIdx.x == 0) pf.record(post.rec + b * post.rec_stride);
+#pragma unroll
+                for (int i = 0; i < I2; ++i) {
+                    const int e = threadIdx.x + i * NTH;
+                    if (e < W2 * (TY + 4)) sp[e] = pf.apply(raw[i]);
+                }
+            } else {
+                load_tile<2>(sp, phi_s + src * slot_stride + pb, G, c0, r0);
+            }
+            load_tile<1>(sm, mu_s + src * slot_stride + pb, G, c0, r0);          // mu of the old level
+#pragma unroll
+            for (int i = 0; i < I1; ++i) {
+                const int e = threadIdx.x + i * NTH;
+                vW[i] = vU0[i] = vU1[i] = 0.0;
+                if (e < N1) {
+                    int ly = e / W1, lxx = e - ly * W1;
+                    int gr = refl(r0 - 1 + ly, G.ns), gc = refl(c0 - 1 + lxx, G.nf);
+                    long o = (long)gr * G.pitch + gc;
+                    vW[i] = w[pb + o];
+                    vU0[i] = un ? un[b * u_stride + o] : 0.0;
+                    vU1[i] = unp1 ? unp1[b * u_stride + o] : 0.0;
+                }
             }
         }
         __syncthreads();
+        if (HOIST) {                                                         // the u pair is needed as its sum only
+#pragma unroll
+            for (int i = 0; i < I1; ++i) vU1[i] = vU1[i] + vU0[i];
+        }
         for (int k = 0; k < TY / 4; ++k) {                                   // c_mu needs the Laplacian of the old mu
             int ly = ly0 + 4 * k, r = r0 + ly, c = c0 + lx;
             rm[k] = 0.0;
@@ -1743,8 +1870,8 @@ __global__ __launch_bounds__(NTH, EVAL_MINBLK) void k_eval(Geom G, Phys P, TrajS
             int gr = refl(rr, G.ns), gc = refl(cc, G.nf);
             int p2 = (ly + 1) * W2 + lxx + 1;
             long o = (long)gr * G.pitch + gc, ob = pb + o;
-            const double u0 = vU0[i], u1 = vU1[i], wo = vW[i];
-            const double wn = ((gdt - 0.5) * wo + 0.5 * (u1 + u0)) / (gdt + 0.5);
+            const double us = HOIST ? vU1[i] : vU1[i] + vU0[i], wo = vW[i];
+            const double wn = ((gdt - 0.5) * wo + 0.5 * us) / (gdt + 0.5);
             const double ph = sp[p2], lp = lap_at<W2>(sp, p2, G.ax, G.ay);
             const double m0 = -P.kappa * lp + (P.c1 * reglog(ph) - 2.0 * P.c2 * ph) - wn;
             const double cp = -(P.tau / dt) * ph - 0.5 * P.kappa * lp - 2.0 * P.c2 * ph - 0.5 * sm[e] - 0.5 * (wn + wo);
@@ -1754,6 +1881,9 @@ __global__ __launch_bounds__(NTH, EVAL_MINBLK) void k_eval(Geom G, Phys P, TrajS
                 wnew[ob] = wn;
                 cphi[ob] = cp;
             }
+        }
+        if (HOIST && do_guess) {                                             // the hoisted operands are dead from here on
+            guess_load(0);
         }
         __syncthreads();
         for (int k = 0; k < TY / 4; ++k) {
@@ -1857,7 +1987,11 @@ __global__ __launch_bounds__(NTH, EVAL_MINBLK) void k_eval(Geom G, Phys P, TrajS
                 const double cp = vC[i];
                 double ph = sp[p2];
                 sm[e] = tdt * ph - 0.5 * P.kappa * lap_at<W2>(sp, p2, G.ax, G.ay) + P.c1 * reglog(ph) - 0.5 * sm[e] + cp;
+                if (HOIST && do_guess) sd[e] = jac_diag(ph, tdt, P.c1);      // the guess tail's D on the tile + halo 1 (sd is free)
             }
+        }
+        if (HOIST && do_guess) {                                             // the prefetched operands are dead from here on
+            guess_load(0);
         }
         __syncthreads();
         for (int k = 0; k < TY / 4; ++k) {
@@ -1882,29 +2016,71 @@ __global__ __launch_bounds__(NTH, EVAL_MINBLK) void k_eval(Geom G, Phys P, TrajS
     }
     // ---- k_guess: x0 = sum c_j d_j, rhs -= A x0 (A with the D of the iterate just evaluated), sum rhs^2 before / after ----
     if (do_guess) {
-        double *X = MODE == 0 ? sp : sd;          // x0 with halo 2 (MODE 0: phi is not needed once D has been taken)
-        double *STT = MODE == 0 ? sr : sp;        // kappa/2 M x0 + D x0 with halo 1
-        __syncthreads();                          // everybody is done with sm / sr (and sd)
-        for (int e = threadIdx.x; e < (TY + 2) * W1; e += NTH) {
-            int ly = e / W1, lxx = e - ly * W1;
-            sm[e] = jac_diag(sp[(ly + 1) * W2 + lxx + 1], tdt, P.c1);        // D on the tile + halo 1
-        }
-        __syncthreads();
-        for (int e = threadIdx.x; e < W2 * (TY + 4); e += NTH) {
-            int ly = e / W2, lxx = e - ly * W2;
-            int gr = refl(r0 - 2 + ly, G.ns), gc = refl(c0 - 2 + lxx, G.nf);
-            long o = pb + (long)gr * G.pitch + gc;
-            double v = gcf[0] * ga.d[0][o];
+        // plain form      MODE 0: X = sp (phi is not needed once D has been taken), STT = sr;  MODE 2: X = sd, STT = sp;  D in sm
+        // HOIST, MODE 2   D went into sd while phi (sp) was still needed: X = sp, STT = sm
+        double *X = (MODE == 0 || HOIST) ? sp : sd;                          // x0 with halo 2
+        double *STT = MODE == 0 ? sr : (HOIST ? sm : sp);                    // kappa/2 M x0 + D x0 with halo 1
+        const double *Dg = (MODE == 2 && HOIST) ? sd : sm;                   // D with halo 1
+        if (HOIST) {
+            // plane 0 is on its way since the last halo-1 pass; of every further plane the thread's elements are in flight together
+            if (MODE == 0) {
+                // D on the tile + halo 1 from phi, which stays in sp up to the barrier below (held in registers across the halo-1
+                // and own-node passes, two or three of the five values spill at 5 workgroups per CU)
+#pragma unroll
+                for (int i = 0; i < GI1; ++i) {
+                    const int e = threadIdx.x + i * NTH;
+                    if (e < GN1) {
+                        int ly = e / W1, lxx = e - ly * W1;
+                        gD[i] = jac_diag(sp[(ly + 1) * W2 + lxx + 1], tdt, P.c1);
+                    }
+                }
+            }
+            double v[GI2];
+#pragma unroll
+            for (int i = 0; i < GI2; ++i) v[i] = gcf[0] * gT[0][i];
 #pragma unroll
             for (int j = 1; j < GUESS_ORD; ++j)
-                if (gcf[j] != 0.0) v += gcf[j] * ga.d[j][o];
-            X[e] = isfinite(v) ? v : 0.0;
+                if (gcf[j] != 0.0) {
+                    guess_load(j);
+#pragma unroll
+                    for (int i = 0; i < GI2; ++i) v[i] += gcf[j] * gT[j != 0][i];
+                }
+            __syncthreads();                      // everybody is done with sp / sm / sr (and sd)
+            if (MODE == 0) {
+#pragma unroll
+                for (int i = 0; i < GI1; ++i) {
+                    const int e = threadIdx.x + i * NTH;
+                    if (e < GN1) sm[e] = gD[i];
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < GI2; ++i) {
+                const int e = threadIdx.x + i * NTH;
+                if (e < GN2) X[e] = isfinite(v[i]) ? v[i] : 0.0;
+            }
+        } else {
+            __syncthreads();                      // everybody is done with sm / sr (and sd)
+            for (int e = threadIdx.x; e < (TY + 2) * W1; e += NTH) {
+                int ly = e / W1, lxx = e - ly * W1;
+                sm[e] = jac_diag(sp[(ly + 1) * W2 + lxx + 1], tdt, P.c1);    // D on the tile + halo 1
+            }
+            __syncthreads();
+            for (int e = threadIdx.x; e < W2 * (TY + 4); e += NTH) {
+                int ly = e / W2, lxx = e - ly * W2;
+                int gr = refl(r0 - 2 + ly, G.ns), gc = refl(c0 - 2 + lxx, G.nf);
+                long o = pb + (long)gr * G.pitch + gc;
+                double v = gcf[0] * ga.d[0][o];
+#pragma unroll
+                for (int j = 1; j < GUESS_ORD; ++j)
+                    if (gcf[j] != 0.0) v += gcf[j] * ga.d[j][o];
+                X[e] = isfinite(v) ? v : 0.0;
+            }
         }
         __syncthreads();
-        for (int e = threadIdx.x; e < (TY + 2) * W1; e += NTH) {             // STT is neither X nor sm in either mode
+        for (int e = threadIdx.x; e < (TY + 2) * W1; e += NTH) {             // STT is neither X nor Dg in any form
             int ly = e / W1, lxx = e - ly * W1;
             int p2 = (ly + 1) * W2 + lxx + 1;
-            STT[e] = -0.5 * P.kappa * lap_at<W2>(X, p2, G.ax, G.ay) + sm[e] * X[p2];
+            STT[e] = -0.5 * P.kappa * lap_at<W2>(X, p2, G.ax, G.ay) + Dg[e] * X[p2];
         }
         double xv[TY / 4];
         for (int k = 0; k < TY / 4; ++k) xv[k] = X[(ly0 + 4 * k + 2) * W2 + lx + 2];
@@ -1976,6 +2152,22 @@ __global__ __launch_bounds__(NTH, EVAL_MINBLK) void k_eval(Geom G, Phys P, TrajS
         st[b] = S;
     }
 }
+#define EVAL_PARAMS                                                                                                          \
+    Geom G, Phys P, TrajState *st, long slot_stride, double *phi_s, double *mu_s, double *Rphi_s, double *rhs_s, double *D_s, \
+        const double *dphi, double *cphi, double *cmu, double dt, double *part, const double *w, const double *un,           \
+        const double *unp1, long u_stride, double *wnew, GuessArgs ga, double *x0, EvalFin fin, PostArgs post
+#define EVAL_ARGS                                                                                                            \
+    G, P, st, slot_stride, phi_s, mu_s, Rphi_s, rhs_s, D_s, dphi, cphi, cmu, dt, part, w, un, unp1, u_stride, wnew, ga, x0, fin, post
+template <int MODE, bool FIN_INSIDE>
+__global__ __launch_bounds__(NTH, EVAL_MINBLK) void k_eval(EVAL_PARAMS) {
+    eval_body<MODE, FIN_INSIDE, true>(EVAL_ARGS);
+}
+template <int MODE, bool FIN_INSIDE>
+__global__ __launch_bounds__(NTH, EVAL_MINBLK) void k_eval_plain(EVAL_PARAMS) {      // VCH_EVAL_HOIST=0
+    eval_body<MODE, FIN_INSIDE, false>(EVAL_ARGS);
+}
+#undef EVAL_PARAMS
+#undef EVAL_ARGS
 
 // ---- CG scalar updates (one thread per trajectory does the arithmetic; fin_sum1 is above k_fin_residual) ----
 // forward set-up: gamma0 = <z, z>_Z with z = P^-1 rhs (from the GEMM epilogue)
