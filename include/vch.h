@@ -627,6 +627,17 @@ int vch1d_hessvec(vch1d_ctx *ctx, const double *phi_hist, const double *u, int n
                   double *grad_out /* [B][rows][N+1] or NULL */, double *hv_out /* [B][rows][N+1], required iff order 2 */,
                   double *dots_out /* [B][2] or NULL */, vch_stats *stats);
 
+/* ---------------------------------------------------------- diagnostics ---- */
+
+/* Every device and pinned-host block of a context belongs to the context's pool (csrc/vch_mem.h): vchNd_destroy, and a
+ * vchNd_create that fails, free all of them.  Number of blocks that pools of this process own now (one atomic counter): */
+int vch_mem_live(void);
+/* The allocation request number k of this process, counted from this call (0 = the next one), is refused once, as an
+ * out-of-memory answer of the runtime would refuse it but without a call to the runtime; k < 0 disarms.  For tests of the
+ * failure paths: a refused vchNd_create returns NULL with nothing left behind, a refused lazy allocation fails its call with
+ * VCH_ERR_HIP or VCH_ERR_NOMEM and leaves its group of buffers unallocated, so the same call succeeds when repeated. */
+void vch_mem_refuse_after(int k);
+
 #ifdef __cplusplus
 }
 #endif

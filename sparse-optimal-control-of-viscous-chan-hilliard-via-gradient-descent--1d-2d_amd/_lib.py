@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("VCH_LIB") or os.path.join(HERE, "libvch_hip.so")     # VCH_LIB: A/B builds
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 SOURCES = ["vch_hip.hip"]
-DEPS = ["vch_hip.hip", "vch_comm.hip", "vch_engine2d.hip", "vch_kernels2d.h", "vch_gemm.h", "vch_fft.h", "vch_common.h", "vch_engine1d.hip", "vch_kernels1d.h", "vch_pgd.h",
+DEPS = ["vch_hip.hip", "vch_comm.hip", "vch_engine2d.hip", "vch_kernels2d.h", "vch_gemm.h", "vch_fft.h", "vch_common.h", "vch_mem.h", "vch_engine1d.hip", "vch_kernels1d.h", "vch_pgd.h",
         os.path.join(ROOT, "include", "vch.h")]
 
 
@@ -109,6 +109,8 @@ SIGNATURES = {
     "vch_last_error": (C.c_char_p, []),
     "vch_abi_version": (C.c_int, []),
     "vch_device_count": (C.c_int, []),
+    "vch_mem_live": (C.c_int, []),
+    "vch_mem_refuse_after": (None, [C.c_int]),
     "vch2d_create": (_P, [C.POINTER(Params2D), C.c_int, C.c_int, C.c_int]),
     "vch2d_destroy": (None, [_P]),
     "vch2d_batch": (C.c_int, [_P]),

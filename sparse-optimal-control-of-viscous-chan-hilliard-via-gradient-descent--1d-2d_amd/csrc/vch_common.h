@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 #include "../../include/vch.h"
+#include "vch_mem.h"
 
 // ----------------------------------------------------------------------------------
 // error plumbing
@@ -30,6 +31,11 @@ static inline int vch_fail(int code, const char *fmt, ...) {
                             __FILE__, __LINE__);                                            \
         }                                                                                   \
     } while (0)
+// A request to a context's pool (vch_mem.h), checked like the HIP call behind it: the pool hands the runtime's status through,
+// and a refused request (vch_mem_refuse_after) reads as hipErrorOutOfMemory.  vch_hip_mem() is the runtime table of every pool.
+static_assert(VCH_MEM_REFUSED == (int)hipErrorOutOfMemory, "a refused request must read as out of memory");
+const vch_mem_fns *vch_hip_mem();
+#define MEMCHK(call) HIPCHK((hipError_t)(call))
 #define VCHCHK(call)                   \
     do {                               \
         int r_ = (call);               \

@@ -8,20 +8,22 @@
 #include <cmath>
 #include <vector>
 
+// Made by `new vch1d_ctx()` alone: a member without an initialiser starts as zero (NULL).
 struct vch1d_ctx {
+    vch_pool pool{vch_hip_mem()};  // owns every device and pinned buffer below (vch_mem.h); teardown() releases it
     vch1d_params prm;
     int B, Mmax, device, n, lvl;
     double h;
     Phys1 P, F;                    // run-time parameters; frozen defaults for the adjoint (B1:29-33)
-    hipStream_t stream;
-    hipEvent_t ev0, ev1;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double *scratch;               // [B][NSCR1][n]
     double *tmp[8];                // [B][n]
     double *phi_hist, *u_hist, *u_trial, *phiQ, *p_hist, *q_hist, *r_hist;   // [B][Mmax+2][n], lazy
     double *phiT, *dts, *tgrid, *wx, *alpha_dev, *cost_lvl, *hist_dev;
     double *cost_host;
     int *stats_dev, *stats_host;
-    size_t lds_bytes;
+    size_t lds_bytes = sizeof(double) * 14 * NR_MAX;
     int rows_res;
     // device-resident PGD (vch1d_pgd_*)
     bool pgd_ready = false;
@@ -51,24 +53,22 @@ struct vch1d_ctx {
 static bool launch_begin(vch1d_ctx *, int) { return false; }
 static void launch_end(vch1d_ctx *, int, bool) {}
 
-static int dalloc1(double **p, size_t n, hipStream_t s) {
-    *p = nullptr;
-    HIPCHK(hipMalloc((void **)p, n * sizeof(double)));
-    HIPCHK(hipMemsetAsync(*p, 0, n * sizeof(double), s));
+// n zeroed doubles into *p, unless it has them already
+static int dalloc1(vch1d_ctx *c, double **p, size_t n) {
+    if (*p) return 0;
+    MEMCHK(c->pool.dev(p, n * sizeof(double)));
+    HIPCHK(hipMemsetAsync(*p, 0, n * sizeof(double), c->stream));
     return 0;
 }
 static inline long hs1(const vch1d_ctx *c) { return (long)(c->Mmax + 2) * c->n; }
-static int ensure1(vch1d_ctx *c, double **p) {
-    if (*p) return 0;
-    return dalloc1(p, (size_t)c->B * hs1(c), c->stream);
-}
+static int ensure1(vch1d_ctx *c, double **p) { return dalloc1(c, p, (size_t)c->B * hs1(c)); }
 static int up(vch1d_ctx *c, double *dev, const double *host, size_t n) {
     HIPCHK(hipMemcpyAsync(dev, host, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     return 0;
 }
 // the function seams' scalar parameters as one table row on the device (read by every trajectory: stride 0)
 static int seam_row(vch1d_ctx *c, double b1, double b2, double b3, double ks, double umin, double umax) {
-    if (!c->seam_tab) VCHCHK(dalloc1(&c->seam_tab, OPT1_STRIDE, c->stream));
+    VCHCHK(dalloc1(c, &c->seam_tab, OPT1_STRIDE));
     double *row = c->seam_tab_host;
     row[OPT1_B1] = b1; row[OPT1_B2] = b2; row[OPT1_B3] = b3; row[OPT1_KS] = ks; row[OPT1_UMIN] = umin; row[OPT1_UMAX] = umax;
     return up(c, c->seam_tab, row, OPT1_STRIDE);
@@ -89,6 +89,16 @@ static int down_hist(vch1d_ctx *c, double *host, const double *dev, int rows) {
                               hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
+}
+
+// Everything a context holds, in the order that is safe for one that vch1d_create only half built.
+static void teardown(vch1d_ctx *c) {
+    if (c->stream) hipStreamSynchronize(c->stream);
+    c->pool.release();
+    if (c->ev0) hipEventDestroy(c->ev0);
+    if (c->ev1) hipEventDestroy(c->ev1);
+    if (c->stream) hipStreamDestroy(c->stream);
+    delete c;
 }
 
 extern "C" vch1d_ctx *vch1d_create(const vch1d_params *p, int batch, int max_steps, int device) {
@@ -117,38 +127,30 @@ extern "C" vch1d_ctx *vch1d_create(const vch1d_params *p, int batch, int max_ste
     c->h = p->Lx / p->N;
     c->P = Phys1{p->tau, p->gamma, p->c1, p->c2, p->kappa, p->Lx};
     c->F = Phys1{0.05, 10.0, 0.75, 1.0, 0.03 * 0.03, 1.0};      // K1:95-102 defaults, frozen at import in B1:29-33
-    c->rows_res = 0;
     auto fail = [&](const char *what) {
         vch_fail(VCH_ERR_HIP, "vch1d_create: %s failed: %s", what, hipGetErrorString(hipGetLastError()));
+        teardown(c);
         return (vch1d_ctx *)nullptr;
     };
     if (hipStreamCreate(&c->stream) != hipSuccess) return fail("hipStreamCreate");
     hipEventCreate(&c->ev0);
     hipEventCreate(&c->ev1);
-    const size_t bn = (size_t)batch * c->n;
-    if (dalloc1(&c->scratch, bn * NSCR1, c->stream)) return fail("hipMalloc");
+    const size_t bn = (size_t)batch * c->n, lv = (size_t)batch * (max_steps + 2) * 4;
+    if (dalloc1(c, &c->scratch, bn * NSCR1)) return fail("hipMalloc");
     for (auto &t : c->tmp)
-        if (dalloc1(&t, bn, c->stream)) return fail("hipMalloc");
-    if (dalloc1(&c->phiT, bn, c->stream) || dalloc1(&c->dts, max_steps + 2, c->stream) ||
-        dalloc1(&c->tgrid, max_steps + 2, c->stream) || dalloc1(&c->wx, c->n, c->stream) ||
-        dalloc1(&c->alpha_dev, batch, c->stream) || dalloc1(&c->cost_lvl, (size_t)batch * (max_steps + 2) * 4, c->stream) ||
-        dalloc1(&c->hist_dev, (size_t)batch * 64, c->stream))
+        if (dalloc1(c, &t, bn)) return fail("hipMalloc");
+    if (dalloc1(c, &c->phiT, bn) || dalloc1(c, &c->dts, max_steps + 2) || dalloc1(c, &c->tgrid, max_steps + 2) ||
+        dalloc1(c, &c->wx, c->n) || dalloc1(c, &c->alpha_dev, batch) || dalloc1(c, &c->cost_lvl, lv) ||
+        dalloc1(c, &c->hist_dev, (size_t)batch * 64))
         return fail("hipMalloc");
-    if (hipMalloc((void **)&c->stats_dev, sizeof(int) * 8 * batch) != hipSuccess) return fail("hipMalloc");
-    if (hipHostMalloc((void **)&c->stats_host, sizeof(int) * 8 * batch) != hipSuccess) return fail("hipHostMalloc");
-    if (hipHostMalloc((void **)&c->cost_host, sizeof(double) * batch * (max_steps + 2) * 4) != hipSuccess) return fail("hipHostMalloc");
-    c->phi_hist = c->u_hist = c->u_trial = c->phiQ = c->p_hist = c->q_hist = c->r_hist = nullptr;
-    c->lds_bytes = sizeof(double) * 14 * NR_MAX;
+    if (c->pool.dev(&c->stats_dev, sizeof(int) * 8 * batch)) return fail("hipMalloc");
+    if (c->pool.host(&c->stats_host, sizeof(int) * 8 * batch)) return fail("hipHostMalloc");
+    if (c->pool.host(&c->cost_host, sizeof(double) * lv)) return fail("hipHostMalloc");
     // > 64 KiB of dynamic LDS needs the opt-in attribute
-    hipFuncSetAttribute((const void *)k1d_forward, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes);
-    hipFuncSetAttribute((const void *)k1d_newton, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes);
-    hipFuncSetAttribute((const void *)k1d_backward, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes);
-    hipFuncSetAttribute((const void *)k1d_solve<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes);
-    hipFuncSetAttribute((const void *)k1d_solve<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes);
-    hipFuncSetAttribute((const void *)k1d_tangent<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes);
-    hipFuncSetAttribute((const void *)k1d_tangent<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes);
-    hipFuncSetAttribute((const void *)k1d_hessvec<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes);
-    hipFuncSetAttribute((const void *)k1d_hessvec<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes);
+    for (const void *k : {(const void *)k1d_forward, (const void *)k1d_newton, (const void *)k1d_backward, (const void *)k1d_solve<0>,
+                          (const void *)k1d_solve<1>, (const void *)k1d_tangent<1>, (const void *)k1d_tangent<2>,
+                          (const void *)k1d_hessvec<1>, (const void *)k1d_hessvec<2>})
+        hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes);
     if (hipStreamSynchronize(c->stream) != hipSuccess) return fail("hipStreamSynchronize");
     return c;
 }
@@ -156,23 +158,7 @@ extern "C" vch1d_ctx *vch1d_create(const vch1d_params *p, int batch, int max_ste
 extern "C" void vch1d_destroy(vch1d_ctx *c) {
     if (!c) return;
     hipSetDevice(c->device);
-    hipStreamSynchronize(c->stream);
-    double *all[] = {c->scratch, c->tmp[0], c->tmp[1], c->tmp[2], c->tmp[3], c->tmp[4], c->tmp[5], c->tmp[6], c->tmp[7],
-                     c->phiT, c->dts, c->tgrid, c->wx, c->alpha_dev, c->cost_lvl, c->hist_dev, c->phi_hist, c->u_hist,
-                     c->u_trial, c->phiQ, c->p_hist, c->q_hist, c->r_hist, c->phi0_dev, c->phi_trial, c->chg_dev, c->tp_dev,
-                     c->opt_tab, c->seam_tab, c->kkt_nrm, c->so_base, c->so_u, c->so_pq, c->so_h, c->so_d1, c->so_d2, c->so_pt, c->so_dts,
-                     c->so_t, c->so_wx, c->so_wts, c->so_out, c->hv_g, c->hv_hv, c->hv_v, c->hv_wt, c->hv_mean, c->hv_dots};
-    for (double *q : all)
-        if (q) hipFree(q);
-    hipFree(c->stats_dev);
-    if (c->skip_dev) hipFree(c->skip_dev);
-    if (c->kkt_cnt) hipFree(c->kkt_cnt);
-    hipHostFree(c->stats_host);
-    hipHostFree(c->cost_host);
-    hipEventDestroy(c->ev0);
-    hipEventDestroy(c->ev1);
-    hipStreamDestroy(c->stream);
-    delete c;
+    teardown(c);
 }
 
 extern "C" int vch1d_apply_laplacian(vch1d_ctx *c, const double *v, double *out) {
@@ -524,15 +510,19 @@ extern "C" int vch1d_pgd_init_v(vch1d_ctx *c, const double *phi0, const double *
     c->pgd_r_valid = false;
     c->pgd_rows = rows;
     c->t_host.assign(t_hist, t_hist + rows);
-    double **hs[] = {&c->phi_hist, &c->u_hist, &c->u_trial, &c->phiQ, &c->p_hist, &c->q_hist, &c->r_hist, &c->phi_trial};
-    for (auto p : hs) VCHCHK(ensure1(c, p));
-    if (!c->phi0_dev) VCHCHK(dalloc1(&c->phi0_dev, (size_t)B * c->n, c->stream));
-    if (!c->chg_dev) VCHCHK(dalloc1(&c->chg_dev, (size_t)B * (c->Mmax + 2) * 2, c->stream));
-    if (!c->tp_dev) VCHCHK(dalloc1(&c->tp_dev, c->Mmax + 2, c->stream));
-    if (!c->skip_dev) HIPCHK(hipMalloc((void **)&c->skip_dev, sizeof(int) * B));
-    if (!c->opt_tab) VCHCHK(dalloc1(&c->opt_tab, tab.size(), c->stream));
-    if (!c->kkt_cnt) HIPCHK(hipMalloc((void **)&c->kkt_cnt, sizeof(long long) * 4 * B));
-    if (!c->kkt_nrm) VCHCHK(dalloc1(&c->kkt_nrm, 2 * (size_t)B, c->stream));
+    {   // what the resident problem needs beyond the buffers of vch1d_create: all of it, or nothing more than there was
+        vch_group g(c->pool);
+        double **hs[] = {&c->phi_hist, &c->u_hist, &c->u_trial, &c->phiQ, &c->p_hist, &c->q_hist, &c->r_hist, &c->phi_trial};
+        for (auto p : hs) VCHCHK(ensure1(c, p));
+        VCHCHK(dalloc1(c, &c->phi0_dev, (size_t)B * c->n));
+        VCHCHK(dalloc1(c, &c->chg_dev, (size_t)B * (c->Mmax + 2) * 2));
+        VCHCHK(dalloc1(c, &c->tp_dev, c->Mmax + 2));
+        if (!c->skip_dev) MEMCHK(c->pool.dev(&c->skip_dev, sizeof(int) * B));
+        VCHCHK(dalloc1(c, &c->opt_tab, tab.size()));
+        if (!c->kkt_cnt) MEMCHK(c->pool.dev(&c->kkt_cnt, sizeof(long long) * 4 * B));
+        VCHCHK(dalloc1(c, &c->kkt_nrm, 2 * (size_t)B));
+        g.keep();
+    }
     VCHCHK(up(c, c->opt_tab, tab.data(), tab.size()));
     c->chg_host.assign((size_t)B * rows * 2, 0.0);
     VCHCHK(up(c, c->phi0_dev, phi0, (size_t)B * c->n));
@@ -779,7 +769,7 @@ static int so1_base(vch1d_ctx *c, const double *phi_hist, const double *u, const
     if (phi_T == VCH_RESIDENT) {
         S.pt = c->phiT;
     } else if (phi_T) {
-        if (!c->so_pt) VCHCHK(dalloc1(&c->so_pt, (size_t)B * n, c->stream));
+        VCHCHK(dalloc1(c, &c->so_pt, (size_t)B * n));
         VCHCHK(up(c, c->so_pt, phi_T, (size_t)n_base * n));
         S.pt = c->so_pt;
     }
@@ -788,12 +778,14 @@ static int so1_base(vch1d_ctx *c, const double *phi_hist, const double *u, const
 // step sizes, t_hist, the trapezoid weights of x and the weight table (host vectors: the caller synchronises before they go)
 static int so1_grids(vch1d_ctx *c, const std::vector<double> &dts, const double *t_hist, int rows, const std::vector<double> &wx,
                      const std::vector<double> &wts) {
-    if (!c->so_dts) {
-        VCHCHK(dalloc1(&c->so_dts, c->Mmax + 2, c->stream));
-        VCHCHK(dalloc1(&c->so_t, c->Mmax + 2, c->stream));
-        VCHCHK(dalloc1(&c->so_wx, c->n, c->stream));
-        VCHCHK(dalloc1(&c->so_wts, 3 * (size_t)c->B, c->stream));
-        VCHCHK(dalloc1(&c->so_out, 6 * (size_t)c->B, c->stream));
+    if (!c->so_out) {              // the last of the group: there are all five or none
+        vch_group g(c->pool);
+        VCHCHK(dalloc1(c, &c->so_dts, c->Mmax + 2));
+        VCHCHK(dalloc1(c, &c->so_t, c->Mmax + 2));
+        VCHCHK(dalloc1(c, &c->so_wx, c->n));
+        VCHCHK(dalloc1(c, &c->so_wts, 3 * (size_t)c->B));
+        VCHCHK(dalloc1(c, &c->so_out, 6 * (size_t)c->B));
+        g.keep();
     }
     VCHCHK(up(c, c->so_dts, dts.data(), rows - 2));
     VCHCHK(up(c, c->so_t, t_hist, rows));
@@ -891,10 +883,12 @@ extern "C" int vch1d_hessvec(vch1d_ctx *c, const double *phi_hist, const double 
         wt[r] += 0.5 * d;
         wt[r + 1] += 0.5 * d;
     }
-    if (!c->hv_wt) {
-        VCHCHK(dalloc1(&c->hv_wt, c->Mmax + 2, c->stream));
-        VCHCHK(dalloc1(&c->hv_mean, (size_t)B * (c->Mmax + 2), c->stream));
-        VCHCHK(dalloc1(&c->hv_dots, 2 * (size_t)B, c->stream));
+    if (!c->hv_dots) {             // all three or none
+        vch_group g(c->pool);
+        VCHCHK(dalloc1(c, &c->hv_wt, c->Mmax + 2));
+        VCHCHK(dalloc1(c, &c->hv_mean, (size_t)B * (c->Mmax + 2)));
+        VCHCHK(dalloc1(c, &c->hv_dots, 2 * (size_t)B));
+        g.keep();
     }
     VCHCHK(up(c, c->hv_wt, wt.data(), rows));
     VCHCHK(ensure1(c, &c->hv_g));

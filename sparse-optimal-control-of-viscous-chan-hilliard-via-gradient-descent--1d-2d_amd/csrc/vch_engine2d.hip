@@ -15,6 +15,15 @@
 
 thread_local char g_vch_err[512] = "";
 
+// the runtime behind every context's pool (vch_mem.h): the only callers of these four
+const vch_mem_fns *vch_hip_mem() {
+    static const vch_mem_fns hip = {[](void **p, size_t bytes) { return (int)hipMalloc(p, bytes); },
+                                    [](void *p) { return (int)hipFree(p); },
+                                    [](void **p, size_t bytes, unsigned flags) { return (int)hipHostMalloc(p, bytes, flags); },
+                                    [](void *p) { return (int)hipHostFree(p); }};
+    return &hip;
+}
+
 extern "C" const char *vch_last_error(void) { return g_vch_err; }
 extern "C" int vch_abi_version(void) { return 3; }
 extern "C" int vch_device_count(void) {
@@ -77,14 +86,17 @@ struct GuessPolicy {
     }
 };
 
+// Made by `new vch2d_ctx()` alone: a member without an initialiser starts as zero (false, NULL), and vch2d_create assigns only
+// what depends on its arguments or on the environment.
 struct vch2d_ctx {
+    vch_pool pool{vch_hip_mem()};          // owns every device and pinned buffer below (vch_mem.h); teardown() releases it
     vch2d_params prm;
     int B, Mmax, device;
     Geom G;
     Phys P;
     double hx, hy;
-    hipStream_t stream;
-    hipEvent_t ev0, ev1;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     dim3 grid;
     int nblk;
     long slot_stride;
@@ -100,7 +112,7 @@ struct vch2d_ctx {
     // off), chosen for the step being enqueued, sweeps enqueued by the last cheb_solve (-1: the last solve was a CG solve),
     // sweeps per Newton slot of the schedule, and the margin added to what the previous step's plans asked for
     bool cheb_on;
-    int spec_form[4];                     // per Newton slot: bit 0 = enqueue the reduction-free sequence, bit 1 = the CG sequence
+    int spec_form[4] = {3, 3, 3, 3};      // per Newton slot: bit 0 = enqueue the reduction-free sequence, bit 1 = the CG sequence
     bool debug_guess;                     // VCH_DEBUG_GUESS, read once at creation
     bool adj_guess_off, adj_safe;         // VCH_ADJ_GUESS_OFF, VCH_ADJ_SAFE (diagnostics), read at the start of every sweep
     long redo_iters;                      // sweeps of an adjoint pass that had to be repeated (0 otherwise)
@@ -110,7 +122,7 @@ struct vch2d_ctx {
     bool fused_on;
     int fused_mode;                       // 0 separate kernels, 1 fused with the fin step inside, 2 fused + fin launches
     unsigned *fin_counter;
-    int cheb_enq, spec_chn[4], cheb_margin, cheb_max;
+    int cheb_enq = -1, spec_chn[4] = {2, 2, 2, 2}, cheb_margin, cheb_max;
     double pgd_adj_tol;                   // relative residual at which the adjoint solves of the PGD loop stop (VCH_ADJ_TOL)
     double eta1_factor;                   // first solve of a step: target = max(lin_eta, eta1_factor x recent ||R_1||) (VCH_ETA1; 0 = off)
     double cg_scale_ratio;                // CG form: Dmax / Dmin beyond which a solve runs right-scaled (0 = never; VCH_CG_SCALE)
@@ -120,7 +132,7 @@ struct vch2d_ctx {
     // increment goes to
     double *dprev[GUESS_RING], *x0g;
     bool guess_on;
-    int guess_wr, guess_step;             // ring slot of this step's increment (-1: not kept); step index within the march
+    int guess_wr = -1, guess_step;        // ring slot of this step's increment (-1: not kept); step index within the march
     int guess_max;                        // largest order allowed
     // per trajectory (a trajectory's orders follow from its own history, whatever its batch mates do): order policies of the
     // first / second solve, orders used in the step being enqueued, length of the run of steps with a second solve
@@ -167,7 +179,7 @@ struct vch2d_ctx {
     bool eval_hoist;
     unsigned long long *ceil_cell;        // [B][CeilCell::STRIDE] (vch_kernels2d.h)
     bool cell_now;                        // the level being enqueued uses the cells
-    int trial_enq;                        // sweeps of the reduction-free solve the NEXT trial launch arms the trial for (-1: none)
+    int trial_enq = -1;                   // sweeps of the reduction-free solve the NEXT trial launch arms the trial for (-1: none)
     unsigned long long pub_pending;       // sequence number a fin launch already enqueued will publish (0: none)
     bool mass_done;                       // newton_level has enqueued the step's k_mass
     int *frozen_dev;                      // [B] line-search flags for k_set_frozen
@@ -187,7 +199,7 @@ struct vch2d_ctx {
     double *cost_part, *cost_lvl;         // cost partials
     double *cost_lvl_host;
     double *alpha_dev;
-    int M_res;                            // steps of the resident state history (-1 none)
+    int M_res = -1;                       // steps of the resident state history (-1 none)
     int u_rows_res;                       // rows of the resident control (0 none)
     // resident PGD problem
     bool pgd_ready;
@@ -221,21 +233,22 @@ struct vch2d_ctx {
     // that the collective of iteration k (vch_comm_allreduce_cost) reads iteration k's values even when the context
     // has already gone on; J_ring_host is the pinned staging copy
     double *J_ring_dev, *J_ring_host;
-    std::atomic<long> pgd_iter_total;     // iterations performed since vch2d_pgd_init (read by the collective's thread)
+    std::atomic<long> pgd_iter_total{0};  // iterations performed since vch2d_pgd_init (read by the collective's thread)
     long tot_launch, tot_sync;            // launches / looks accumulated over the context's life (vch2d_counters)
     // per-kernel-class HIP-event timing (bench.py roofline leg)
     bool prof_on;
     std::vector<hipEvent_t> prof_ev;
     std::vector<int> prof_cls;
     size_t prof_used;
-    // knobs
-    int lin_maxit;
+    // knobs (read_knobs)
+    bool knob_gemm_dct, knob_dct_half, knob_guess;   // VCH_FORCE_GEMM_DCT, VCH_DCT_HALF, VCH_GUESS as make_plan takes them
+    int lin_maxit = 4000;
     double lin_tol;
     double lin_eta;                       // target for the Schur residual a Newton solve inside a march leaves (0 = lin_tol)
     // speculative launch schedule of a time step (newton_level): Newton slots and CG sweeps per slot, adapted from the
     // state the host reads once per step
     bool spec;
-    int spec_slots, spec_cgb[4];
+    int spec_slots = 2, spec_cgb[4] = {12, 12, 12, 12};
     // counters since the last reset_counters(): kernel launches and blocking looks at the device state
     long n_launch, n_sync;
 };
@@ -266,10 +279,9 @@ static void launch_end(vch2d_ctx *c, int cls, bool rec) {
 }
 #define LAUNCHC(cls, kern, grid, block, ...) LAUNCH_LDS(cls, kern, grid, block, 0, __VA_ARGS__)
 
-static int dalloc(double **p, size_t n, hipStream_t s) {
-    *p = nullptr;
-    HIPCHK(hipMalloc((void **)p, n * sizeof(double)));
-    HIPCHK(hipMemsetAsync(*p, 0, n * sizeof(double), s));
+static int dalloc(vch2d_ctx *c, double **p, size_t n) {
+    MEMCHK(c->pool.dev(p, n * sizeof(double)));
+    HIPCHK(hipMemsetAsync(*p, 0, n * sizeof(double), c->stream));
     return 0;
 }
 
@@ -305,9 +317,8 @@ static int d2h_hist(vch2d_ctx *c, double *host, const double *dev, int rows) {
 static int ensure_hist(vch2d_ctx *c, double **p) {
     if (*p) return 0;
     size_t n = (size_t)c->B * (c->Mmax + 1) * c->G.plane;
-    hipError_t e = hipMalloc((void **)p, n * sizeof(double));
+    const hipError_t e = (hipError_t)c->pool.dev(p, n * sizeof(double));
     if (e != hipSuccess) {
-        *p = nullptr;
         return vch_fail(VCH_ERR_NOMEM, "hipMalloc of a %.2f GB history failed: %s", n * 8e-9, hipGetErrorString(e));
     }
     HIPCHK(hipMemsetAsync(*p, 0, n * sizeof(double), c->stream));
@@ -390,17 +401,9 @@ static void dct_tables(int N, double h, std::vector<double> &Q1, std::vector<dou
     }
 }
 
-extern "C" vch2d_ctx *vch2d_create(const vch2d_params *p, int batch, int max_steps, int device) {
-    if (!p || p->Nx < 2 || p->Ny < 2 || batch < 1 || max_steps < 1 || !(p->Lx > 0) || !(p->Ly > 0)) {
-        vch_fail(VCH_ERR_ARG, "vch2d_create: bad arguments (Nx,Ny >= 2, batch >= 1, max_steps >= 1)");
-        return nullptr;
-    }
-    if (hipSetDevice(device) != hipSuccess) {
-        (void)hipGetLastError();          // do not leave the sticky error for the next launch check
-        vch_fail(VCH_ERR_HIP, "hipSetDevice(%d) failed", device);
-        return nullptr;
-    }
-    vch2d_ctx *c = new vch2d_ctx();
+// ---- vch2d_create in its parts: geometry, knobs, allocations, table uploads, plan.  The last three return NULL, or the name of
+// the step that failed for vch2d_create's message.
+static void set_geometry(vch2d_ctx *c, const vch2d_params *p, int batch, int max_steps, int device) {
     c->prm = *p;
     c->B = batch;
     c->Mmax = max_steps;
@@ -420,12 +423,19 @@ extern "C" vch2d_ctx *vch2d_create(const vch2d_params *p, int batch, int max_ste
     c->grid = dim3(G.tiles_f, G.tiles_s, batch);
     c->nblk = G.tiles_f * G.tiles_s;
     c->slot_stride = (long)batch * G.plane;
-    c->M_res = -1;
-    c->u_rows_res = 0;
-    c->pgd_ready = false;
-    c->prof_on = false;
-    c->prof_used = 0;
-    c->lin_maxit = 4000;
+    c->gnblk = ((G.nf + GN - 1) / GN) * ((G.ns + GM - 1) / GM);      // the GEMM epilogue's workgroups: gpart is sized by them
+    c->pol1.resize(batch);
+    c->pol2.resize(batch);
+    c->used1.assign(batch, 0);
+    c->used2.assign(batch, 0);
+    c->run2.assign(batch, 0);
+}
+
+// Every environment knob that is read once, at creation (VCH_ADJ_GUESS_OFF and VCH_ADJ_SAFE are read at the start of every
+// sweep, backward_core).  A switch is either on unless it is set to 0 (env_on) or on when it is set at all (env_set).
+static void read_knobs(vch2d_ctx *c) {
+    auto env_on = [](const char *name) { const char *e = getenv(name); return !(e && atoi(e) == 0); };
+    auto env_set = [](const char *name) { return getenv(name) != nullptr; };
     c->lin_tol = 1e-15;
     if (const char *e = getenv("VCH_LIN_TOL")) c->lin_tol = atof(e);      // tuning/experiments only
     // Newton solves inside a march are stopped when the Schur residual they leave is 5 % of the Newton tolerance
@@ -434,15 +444,9 @@ extern "C" vch2d_ctx *vch2d_create(const vch2d_params *p, int batch, int max_ste
     if (const char *e = getenv("VCH_LIN_ETA")) c->lin_eta = atof(e);
     c->cols_c = 1024;          // 2048 equal, 4096 slower (profiles/r02_cols_width.txt)
     if (const char *e = getenv("VCH_COLS_C")) c->cols_c = atoi(e);
-    c->spec = getenv("VCH_NO_SPEC") == nullptr;
-    c->spec_slots = 2;
-    for (int &n : c->spec_cgb) n = 12;
-    c->cheb_on = !(getenv("VCH_CHEB") && atoi(getenv("VCH_CHEB")) == 0);
-    for (int &f : c->spec_form) f = 3;
-    c->debug_guess = getenv("VCH_DEBUG_GUESS") != nullptr;
-    c->adj_guess_off = c->adj_safe = false;
-    c->redo_iters = 0;
-    c->cheb_enq = -1;
+    c->spec = !env_set("VCH_NO_SPEC");
+    c->cheb_on = env_on("VCH_CHEB");
+    c->debug_guess = env_set("VCH_DEBUG_GUESS");
     // measured on the 512^2 x 1000 x 8 march (profiles/r03_fused_ab.txt): separate kernels 0.564 s, fused with the fin step
     // by the last-finishing workgroup 0.566 s (the serial tail of that workgroup costs what the saved launch gained), fused
     // with the fin step as its own launch 0.523 s -- the default
@@ -450,20 +454,10 @@ extern "C" vch2d_ctx *vch2d_create(const vch2d_params *p, int batch, int max_ste
     c->fused_on = c->fused_mode != 0;
     c->post_fold = true;
     if (const char *e = getenv("VCH_POST_FOLD")) c->post_fold = atoi(e) != 0;
-    c->post_pending = false;
-    c->post_hist = nullptr;
-    c->post_rec = nullptr;
-    c->fin_counter = nullptr;
-    auto env_on = [](const char *name) { const char *e = getenv(name); return !(e && atoi(e) == 0); };
     c->mass_early = env_on("VCH_MASS_EARLY");
     c->fin_publish = env_on("VCH_FIN_PUBLISH");
     c->ceil_cell_on = env_on("VCH_CEIL_CELL");
     c->eval_hoist = env_on("VCH_EVAL_HOIST");
-    c->ceil_cell = nullptr;
-    c->cell_now = c->mass_done = false;
-    c->trial_enq = -1;
-    c->pub_pending = 0;
-    for (int &n : c->spec_chn) n = 2;
     c->cheb_margin = 1;
     if (const char *e = getenv("VCH_CHEB_MARGIN")) c->cheb_margin = std::max(0, atoi(e));
     c->cheb_max = 6;           // plans longer than this (a wide spectrum: CG's adaptivity pays) keep the CG form
@@ -474,157 +468,184 @@ extern "C" vch2d_ctx *vch2d_create(const vch2d_params *p, int batch, int max_ste
     if (const char *e = getenv("VCH_ETA1")) c->eta1_factor = atof(e);
     c->cg_scale_ratio = 4.0;
     if (const char *e = getenv("VCH_CG_SCALE")) c->cg_scale_ratio = atof(e);
-    c->n_launch = c->n_sync = 0;
+    c->look_spin = env_on("VCH_LOOK_SPIN");
+    // consumed by make_plan
+    c->knob_gemm_dct = env_set("VCH_FORCE_GEMM_DCT");
+    c->knob_dct_half = env_set("VCH_DCT_HALF");
+    c->knob_guess = env_on("VCH_GUESS");
+    c->guess2_on = env_on("VCH_GUESS2");
+    c->guess_max = 6;          // beyond, the weights (sum |c_j| = 2^order - 1) amplify what the inexact solves left in the increments
+    if (const char *e = getenv("VCH_GUESS_MAX")) c->guess_max = std::max(1, std::min(GUESS_ORD, atoi(e)));
+}
+
+// The buffers every context has (histories and the buffers of single calls come lazily).  zero(): doubles, cleared on the
+// stream; dev(): bytes of any type, cleared where a kernel reads them before anything writes them.
+static const char *alloc_buffers(vch2d_ctx *c) {
+    const Geom &G = c->G;
+    const size_t B = c->B, bp = B * G.plane, ng = B * (c->gnblk + G.ns);
+    bool ok = true;                    // nothing more is requested after the first refusal
+    auto zero = [&](double **q, size_t n) { ok = ok && dalloc(c, q, n) == 0; };
+    auto dev = [&](auto **q, size_t bytes, bool clear) {
+        ok = ok && c->pool.dev(q, bytes) == 0;
+        if (ok && clear) hipMemsetAsync(*q, 0, bytes, c->stream);
+    };
+    for (double **q : {&c->phi_s, &c->mu_s, &c->Rphi_s, &c->rhs_s, &c->D_s}) zero(q, 2 * bp);
+    for (double **q : {&c->w, &c->wnew, &c->mu0, &c->cphi, &c->cmu, &c->x, &c->r, &c->dmu, &c->t1, &c->t2, &c->cg_p[0],
+                       &c->cg_p[1], &c->cg_v, &c->cg_q, &c->cg_z2, &c->xf})
+        zero(q, bp);
+    for (double *&q : c->dprev) zero(&q, bp);
+    for (double *&q : c->dprev2) zero(&q, bp);
+    zero(&c->x0g, bp);
+    for (double *&q : c->tmp) zero(&q, bp);
+    zero(&c->phiT, bp);
+    zero(&c->phi0, bp);
+    zero(&c->wts_mass, G.plane);
+    zero(&c->W_cost, G.plane);
+    zero(&c->part, B * c->nblk * NPART);
+    zero(&c->part_mass, B * c->nblk * NPART);
+    zero(&c->gpart, 2 * ng);
+    c->gpart2 = c->gpart + ng;
+    zero(&c->gpart3, 4 * ng);
+    zero(&c->hist_dev, B * HIST_CAP);
+    zero(&c->shift_hist, B * c->Mmax * SHIFT_REC);
+    zero(&c->shift_trial, B * c->Mmax * SHIFT_REC);
+    zero(&c->alpha_dev, B);
+    zero(&c->J_dev, 5 * B);
+    zero(&c->opt_tab, OPT_STRIDE * B);
+    zero(&c->seam_tab, OPT_STRIDE * B);
+    dev(&c->kkt_dev, sizeof(unsigned long long) * 3 * B * (c->Mmax + 2), false);
+    zero(&c->J_ring_dev, J_RING * 5 * B);
+    if (!ok) return "hipMalloc";
+    if (c->pool.host(&c->J_ring_host, sizeof(double) * J_RING * 5 * B)) return "hipHostMalloc";
+    dev(&c->st, sizeof(TrajState) * B, true);
+    dev(&c->frozen_dev, sizeof(int) * B, false);
+    dev(&c->fin_counter, sizeof(unsigned) * B, true);
+    dev(&c->ceil_cell, sizeof(unsigned long long) * CeilCell::STRIDE * B, true);
+    if (!ok) return "hipMalloc";
+    if (c->pool.host(&c->st_host, sizeof(TrajState) * B)) return "hipHostMalloc";
+    // looks through mapped host memory (sync_state); where the platform refuses mapped coherent memory the looks fall back
+    // to a copy command and a stream synchronisation
+    if (c->look_spin) {
+        const unsigned mapped = hipHostMallocMapped | hipHostMallocCoherent;
+        vch_group look(c->pool);
+        if (c->pool.host(&c->st_pub, sizeof(TrajState) * B, mapped) ||
+            c->pool.host(&c->seq_pub, std::max<size_t>(64, sizeof(unsigned long long) * B), mapped)) {
+            (void)hipGetLastError();
+            c->look_spin = false;      // and the group takes st_pub back
+        } else {
+            for (size_t b = 0; b < B; ++b) c->seq_pub[b] = 0;
+            look.keep();
+        }
+    }
+    if (c->pool.host(&c->hist_host, sizeof(double) * B * HIST_CAP)) return "hipHostMalloc";
+    return nullptr;
+}
+
+static const char *upload_tables(vch2d_ctx *c) {
+    const Geom &G = c->G;
+    // mass weights hx*hy*outer(trapz(Nx+1), trapz(Ny+1)) on the TRUE (i, j) of each flat entry (F2:528-531)
+    std::vector<double> wm((size_t)G.plane, 0.0);
+    const int nx1 = c->prm.Nx + 1, ny1 = c->prm.Ny + 1;
+    for (int i = 0; i < nx1; ++i)
+        for (int j = 0; j < ny1; ++j) {
+            long f = (long)i * ny1 + j;
+            double wi = (i == 0 || i == nx1 - 1) ? 0.5 : 1.0, wj = (j == 0 || j == ny1 - 1) ? 0.5 : 1.0;
+            wm[(f / G.nf) * G.pitch + (f % G.nf)] = c->hx * c->hy * (wi * wj);
+        }
+    if (hipMemcpy(c->wts_mass, wm.data(), wm.size() * 8, hipMemcpyHostToDevice) != hipSuccess) return "hipMemcpy";
+    // DCT tables
+    std::vector<double> Q1, Q2, m;
+    auto up = [&](double **d, const std::vector<double> &v) {
+        return c->pool.dev(d, v.size() * 8) == 0 && hipMemcpy(*d, v.data(), v.size() * 8, hipMemcpyHostToDevice) == hipSuccess;
+    };
+    dct_tables(c->prm.Nx, c->hx, Q1, Q2, m);
+    if (!up(&c->Q1f, Q1) || !up(&c->Q2f, Q2) || !up(&c->mf, m)) return "DCT table upload";
+    dct_tables(c->prm.Ny, c->hy, Q1, Q2, m);
+    if (!up(&c->Q1s, Q1) || !up(&c->Q2s, Q2) || !up(&c->ms, m)) return "DCT table upload";
+    return nullptr;
+}
+
+// FFT plan (power-of-two grids) and what follows from it
+static const char *make_plan(vch2d_ctx *c) {
+    const vch2d_params *p = &c->prm;
+    const Geom &G = c->G;
+    auto pow2 = [](int n) { return n >= 16 && n <= 2048 && (n & (n - 1)) == 0; };
+    c->use_fft = pow2(p->Nx) && pow2(p->Ny) && !c->knob_gemm_dct;
+    if (c->use_fft) {
+        auto mk = [&](int N, double2 **tw, FftAxis &ax) {
+            const int L = 2 * N;
+            std::vector<double2> t(L);
+            const long double pi = 3.14159265358979323846264338327950288L;
+            for (int m = 0; m < L; ++m) {
+                long double a = -2.0L * pi * m / L;
+                t[m] = make_double2((double)cosl(a), (double)sinl(a));
+            }
+            if (c->pool.dev(tw, sizeof(double2) * L)) return false;
+            if (hipMemcpy(*tw, t.data(), sizeof(double2) * L, hipMemcpyHostToDevice) != hipSuccess) return false;
+            int lg = 0;
+            while ((1 << lg) < L) ++lg;
+            ax = FftAxis{N, L, lg, *tw};
+            return true;
+        };
+        if (!mk(p->Nx, &c->tw_f, c->fax) || !mk(p->Ny, &c->tw_s, c->sax)) return "FFT twiddle upload";
+        // half-size DCT-I (vch_fft.h, k_dcth_*) where the axis has 512 intervals: opt-in (VCH_DCT_HALF=1), it does half
+        // the butterflies but measured 5-30 % slower per pass on MI355X (profiles/r01_c_fft_variants.txt)
+        if (c->knob_dct_half && p->Nx == HN) {
+            if (!mk(HN / 2, &c->tw_fh, c->fax_h)) return "FFT twiddle upload";
+            c->half_f = true;
+        }
+        if (c->knob_dct_half && p->Ny == HN) {
+            if (!mk(HN / 2, &c->tw_sh, c->sax_h)) return "FFT twiddle upload";
+            c->half_s = true;
+        }
+        if (c->half_f) {
+            c->gnblk = (G.ns + 3) / 4;
+        } else {
+            const int Cc = c->fax.L <= 1024 ? 1024 : c->fax.L;
+            const int rpw = 2 * (Cc >> c->fax.logL);
+            c->gnblk = (G.ns + rpw - 1) / rpw;
+        }
+    }
+    // starting guess of a step's first Newton solve (k_guess): stencil-free sweep only; VCH_GUESS=0 turns it off
+    c->guess_on = c->use_fft && !c->half_f && !c->half_s && c->knob_guess;
+    return nullptr;
+}
+
+// Everything a context holds, in the order that is safe for one that vch2d_create only half built.
+static void teardown(vch2d_ctx *c) {
+    if (c->stream) hipStreamSynchronize(c->stream);
+    c->pool.release();
+    for (hipEvent_t e : c->prof_ev) hipEventDestroy(e);
+    if (c->ev0) hipEventDestroy(c->ev0);
+    if (c->ev1) hipEventDestroy(c->ev1);
+    if (c->stream) hipStreamDestroy(c->stream);
+    delete c;
+}
+
+extern "C" vch2d_ctx *vch2d_create(const vch2d_params *p, int batch, int max_steps, int device) {
+    if (!p || p->Nx < 2 || p->Ny < 2 || batch < 1 || max_steps < 1 || !(p->Lx > 0) || !(p->Ly > 0)) {
+        vch_fail(VCH_ERR_ARG, "vch2d_create: bad arguments (Nx,Ny >= 2, batch >= 1, max_steps >= 1)");
+        return nullptr;
+    }
+    if (hipSetDevice(device) != hipSuccess) {
+        (void)hipGetLastError();          // do not leave the sticky error for the next launch check
+        vch_fail(VCH_ERR_HIP, "hipSetDevice(%d) failed", device);
+        return nullptr;
+    }
+    vch2d_ctx *c = new vch2d_ctx();
+    set_geometry(c, p, batch, max_steps, device);
+    read_knobs(c);
     auto fail = [&](const char *what) {
         vch_fail(VCH_ERR_HIP, "vch2d_create: %s failed: %s", what, hipGetErrorString(hipGetLastError()));
+        teardown(c);
         return (vch2d_ctx *)nullptr;
     };
     if (hipStreamCreate(&c->stream) != hipSuccess) return fail("hipStreamCreate");
     hipEventCreate(&c->ev0);
     hipEventCreate(&c->ev1);
-    const size_t bp = (size_t)batch * G.plane;
-    double **two[] = {&c->phi_s, &c->mu_s, &c->Rphi_s, &c->rhs_s, &c->D_s};
-    for (auto q : two)
-        if (dalloc(q, 2 * bp, c->stream)) return fail("hipMalloc");
-    double **one[] = {&c->w, &c->wnew, &c->mu0, &c->cphi, &c->cmu, &c->x, &c->r, &c->dmu, &c->t1, &c->t2,
-                      &c->cg_p[0], &c->cg_p[1], &c->cg_v, &c->cg_q, &c->cg_z2, &c->xf, &c->dprev[0], &c->dprev[1], &c->dprev[2], &c->dprev[3], &c->dprev[4], &c->dprev[5], &c->dprev[6], &c->dprev[7], &c->dprev2[0], &c->dprev2[1], &c->dprev2[2], &c->dprev2[3], &c->dprev2[4], &c->dprev2[5], &c->dprev2[6], &c->dprev2[7], &c->x0g, &c->tmp[0], &c->tmp[1], &c->tmp[2], &c->tmp[3], &c->tmp[4], &c->tmp[5], &c->phiT, &c->phi0};
-    for (auto q : one)
-        if (dalloc(q, bp, c->stream)) return fail("hipMalloc");
-    if (dalloc(&c->wts_mass, G.plane, c->stream) || dalloc(&c->W_cost, G.plane, c->stream)) return fail("hipMalloc");
-    if (dalloc(&c->part, (size_t)batch * c->nblk * NPART, c->stream)) return fail("hipMalloc");
-    if (dalloc(&c->part_mass, (size_t)batch * c->nblk * NPART, c->stream)) return fail("hipMalloc");
-    c->gnblk = ((G.nf + GN - 1) / GN) * ((G.ns + GM - 1) / GM);
-    if (dalloc(&c->gpart, 2 * (size_t)batch * (c->gnblk + G.ns), c->stream)) return fail("hipMalloc");
-    c->gpart2 = c->gpart + (size_t)batch * (c->gnblk + G.ns);
-    if (dalloc(&c->gpart3, 4 * (size_t)batch * (c->gnblk + G.ns), c->stream)) return fail("hipMalloc");
-    if (dalloc(&c->hist_dev, (size_t)batch * HIST_CAP, c->stream)) return fail("hipMalloc");
-    if (dalloc(&c->shift_hist, (size_t)batch * max_steps * SHIFT_REC, c->stream) ||
-        dalloc(&c->shift_trial, (size_t)batch * max_steps * SHIFT_REC, c->stream))
-        return fail("hipMalloc");
-    if (dalloc(&c->alpha_dev, batch, c->stream) || dalloc(&c->J_dev, 5 * (size_t)batch, c->stream)) return fail("hipMalloc");
-    if (dalloc(&c->opt_tab, (size_t)OPT_STRIDE * batch, c->stream) || dalloc(&c->seam_tab, (size_t)OPT_STRIDE * batch, c->stream))
-        return fail("hipMalloc");
-    if (hipMalloc((void **)&c->kkt_dev, sizeof(unsigned long long) * 3 * batch * (max_steps + 2)) != hipSuccess)
-        return fail("hipMalloc");
-    c->pgd_r_valid = false;
-    if (dalloc(&c->J_ring_dev, (size_t)J_RING * 5 * batch, c->stream)) return fail("hipMalloc");
-    if (hipHostMalloc((void **)&c->J_ring_host, sizeof(double) * J_RING * 5 * batch) != hipSuccess) return fail("hipHostMalloc");
-    c->pgd_iter_total = 0;
-    c->tot_launch = c->tot_sync = 0;
-    if (hipMalloc((void **)&c->st, sizeof(TrajState) * batch) != hipSuccess) return fail("hipMalloc");
-    hipMemsetAsync(c->st, 0, sizeof(TrajState) * batch, c->stream);
-    if (hipMalloc((void **)&c->frozen_dev, sizeof(int) * batch) != hipSuccess) return fail("hipMalloc");
-    if (hipMalloc((void **)&c->fin_counter, sizeof(unsigned) * batch) != hipSuccess) return fail("hipMalloc");
-    hipMemsetAsync(c->fin_counter, 0, sizeof(unsigned) * batch, c->stream);
-    if (hipMalloc((void **)&c->ceil_cell, sizeof(unsigned long long) * CeilCell::STRIDE * batch) != hipSuccess) return fail("hipMalloc");
-    hipMemsetAsync(c->ceil_cell, 0, sizeof(unsigned long long) * CeilCell::STRIDE * batch, c->stream);
-    if (hipHostMalloc((void **)&c->st_host, sizeof(TrajState) * batch) != hipSuccess) return fail("hipHostMalloc");
-    // looks through mapped host memory (sync_state); where the platform refuses mapped coherent memory the looks fall back
-    // to a copy command and a stream synchronisation
-    c->st_pub = nullptr;
-    c->seq_pub = nullptr;
-    c->seq_next = 0;
-    c->look_spin = !(getenv("VCH_LOOK_SPIN") && atoi(getenv("VCH_LOOK_SPIN")) == 0);
-    if (c->look_spin) {
-        if (hipHostMalloc((void **)&c->st_pub, sizeof(TrajState) * batch, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-            hipHostMalloc((void **)&c->seq_pub, std::max<size_t>(64, sizeof(unsigned long long) * batch),
-                          hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
-            (void)hipGetLastError();
-            if (c->st_pub) hipHostFree(c->st_pub);
-            c->st_pub = nullptr;
-            c->seq_pub = nullptr;
-            c->look_spin = false;
-        } else {
-            for (int b = 0; b < batch; ++b) c->seq_pub[b] = 0;
-        }
-    }
-    if (hipHostMalloc((void **)&c->hist_host, sizeof(double) * batch * HIST_CAP) != hipSuccess) return fail("hipHostMalloc");
-    c->phi_hist = c->u_hist = c->u_trial = c->phi_trial = c->phiQ = c->r_hist = c->p_hist = c->q_hist = nullptr;
-    c->cost_part = c->cost_lvl = nullptr;
-    c->cost_lvl_host = nullptr;
-    c->tfrac_dev = nullptr;
-    // mass weights hx*hy*outer(trapz(Nx+1), trapz(Ny+1)) on the TRUE (i, j) of each flat entry (F2:528-531)
-    {
-        std::vector<double> wm((size_t)G.plane, 0.0);
-        const int nx1 = p->Nx + 1, ny1 = p->Ny + 1;
-        for (int i = 0; i < nx1; ++i)
-            for (int j = 0; j < ny1; ++j) {
-                long f = (long)i * ny1 + j;
-                double wi = (i == 0 || i == nx1 - 1) ? 0.5 : 1.0, wj = (j == 0 || j == ny1 - 1) ? 0.5 : 1.0;
-                wm[(f / G.nf) * G.pitch + (f % G.nf)] = c->hx * c->hy * (wi * wj);
-            }
-        if (hipMemcpy(c->wts_mass, wm.data(), wm.size() * 8, hipMemcpyHostToDevice) != hipSuccess) return fail("hipMemcpy");
-    }
-    // DCT tables
-    {
-        std::vector<double> Q1, Q2, m;
-        auto up = [&](double **d, const std::vector<double> &v) {
-            if (hipMalloc((void **)d, v.size() * 8) != hipSuccess) return false;
-            return hipMemcpy(*d, v.data(), v.size() * 8, hipMemcpyHostToDevice) == hipSuccess;
-        };
-        dct_tables(p->Nx, c->hx, Q1, Q2, m);
-        if (!up(&c->Q1f, Q1) || !up(&c->Q2f, Q2) || !up(&c->mf, m)) return fail("DCT table upload");
-        dct_tables(p->Ny, c->hy, Q1, Q2, m);
-        if (!up(&c->Q1s, Q1) || !up(&c->Q2s, Q2) || !up(&c->ms, m)) return fail("DCT table upload");
-    }
-    // FFT plan (power-of-two grids)
-    {
-        auto pow2 = [](int n) { return n >= 16 && n <= 2048 && (n & (n - 1)) == 0; };
-        c->use_fft = pow2(p->Nx) && pow2(p->Ny) && getenv("VCH_FORCE_GEMM_DCT") == nullptr;
-        c->tw_f = c->tw_s = nullptr;
-        if (c->use_fft) {
-            auto mk = [&](int N, double2 **tw, FftAxis &ax) {
-                const int L = 2 * N;
-                std::vector<double2> t(L);
-                const long double pi = 3.14159265358979323846264338327950288L;
-                for (int m = 0; m < L; ++m) {
-                    long double a = -2.0L * pi * m / L;
-                    t[m] = make_double2((double)cosl(a), (double)sinl(a));
-                }
-                if (hipMalloc((void **)tw, sizeof(double2) * L) != hipSuccess) return false;
-                if (hipMemcpy(*tw, t.data(), sizeof(double2) * L, hipMemcpyHostToDevice) != hipSuccess) return false;
-                int lg = 0;
-                while ((1 << lg) < L) ++lg;
-                ax = FftAxis{N, L, lg, *tw};
-                return true;
-            };
-            if (!mk(p->Nx, &c->tw_f, c->fax) || !mk(p->Ny, &c->tw_s, c->sax)) return fail("FFT twiddle upload");
-            // half-size DCT-I (vch_fft.h, k_dcth_*) where the axis has 512 intervals: opt-in (VCH_DCT_HALF=1), it does half
-            // the butterflies but measured 5-30 % slower per pass on MI355X (profiles/r01_c_fft_variants.txt)
-            const bool want_half = getenv("VCH_DCT_HALF") != nullptr;
-            if (want_half && p->Nx == HN) {
-                if (!mk(HN / 2, &c->tw_fh, c->fax_h)) return fail("FFT twiddle upload");
-                c->half_f = true;
-            }
-            if (want_half && p->Ny == HN) {
-                if (!mk(HN / 2, &c->tw_sh, c->sax_h)) return fail("FFT twiddle upload");
-                c->half_s = true;
-            }
-            if (c->half_f) {
-                c->gnblk = (G.ns + 3) / 4;
-            } else {
-                const int Cc = c->fax.L <= 1024 ? 1024 : c->fax.L;
-                const int rpw = 2 * (Cc >> c->fax.logL);
-                c->gnblk = (G.ns + rpw - 1) / rpw;
-            }
-        }
-    }
-    // starting guess of a step's first Newton solve (k_guess): stencil-free sweep only; VCH_GUESS=0 turns it off
-    c->guess_on = c->use_fft && !c->half_f && !c->half_s && !(getenv("VCH_GUESS") && atoi(getenv("VCH_GUESS")) == 0);
-    memset(&c->gtab1, 0, sizeof(c->gtab1));
-    memset(&c->gtab2, 0, sizeof(c->gtab2));
-    c->gmask1 = c->gmask2 = 0;
-    c->pol1.resize(batch);
-    c->pol2.resize(batch);
-    c->used1.assign(batch, 0);
-    c->used2.assign(batch, 0);
-    c->run2.assign(batch, 0);
-    c->run2_all = 0;
-    c->guess2_on = !(getenv("VCH_GUESS2") && atoi(getenv("VCH_GUESS2")) == 0);
-    c->guess_wr = -1;
-    c->guess_step = 0;
-    c->guess_max = 6;          // beyond, the weights (sum |c_j| = 2^order - 1) amplify what the inexact solves left in the increments
-    if (const char *e = getenv("VCH_GUESS_MAX")) c->guess_max = std::max(1, std::min(GUESS_ORD, atoi(e)));
+    if (const char *what = alloc_buffers(c)) return fail(what);
+    if (const char *what = upload_tables(c)) return fail(what);
+    if (const char *what = make_plan(c)) return fail(what);
     if (hipStreamSynchronize(c->stream) != hipSuccess) return fail("hipStreamSynchronize");
     return c;
 }
@@ -632,36 +653,7 @@ extern "C" vch2d_ctx *vch2d_create(const vch2d_params *p, int batch, int max_ste
 extern "C" void vch2d_destroy(vch2d_ctx *c) {
     if (!c) return;
     hipSetDevice(c->device);
-    hipStreamSynchronize(c->stream);
-    double *all[] = {c->phi_s, c->mu_s, c->Rphi_s, c->rhs_s, c->D_s, c->w, c->wnew, c->mu0, c->cphi, c->cmu, c->x,
-                     c->r, c->dmu, c->t1, c->t2, c->cg_p[0], c->cg_p[1], c->cg_v, c->cg_q, c->cg_z2, c->xf, c->dprev[0], c->dprev[1], c->dprev[2], c->dprev[3], c->dprev[4], c->dprev[5], c->dprev[6], c->dprev[7], c->dprev2[0], c->dprev2[1], c->dprev2[2], c->dprev2[3], c->dprev2[4], c->dprev2[5], c->dprev2[6], c->dprev2[7], c->x0g, c->gpart, c->gpart3, c->tmp[0], c->tmp[1], c->tmp[2], c->tmp[3], c->tmp[4], c->tmp[5],
-                     c->phiT, c->phi0, c->wts_mass, c->W_cost, c->part, c->part_mass, c->hist_dev, c->shift_hist, c->shift_trial, c->alpha_dev, c->opt_tab, c->seam_tab, c->J_dev, c->Q1f,
-                     c->Q2f, c->Q1s, c->Q2s, c->mf, c->ms, c->phi_hist, c->u_hist, c->u_trial, c->phi_trial, c->phiQ,
-                     c->r_hist, c->p_hist, c->q_hist, c->cost_part, c->cost_lvl, c->tfrac_dev, c->tan_part, c->tan_lvl, c->tan_t,
-                     c->tan_out, c->hv_G, c->hv_H, c->hv_V, c->hv_DP, c->hv_part};
-    for (double *q : all)
-        if (q) hipFree(q);
-    hipFree(c->st);
-    hipFree(c->frozen_dev);
-    if (c->kkt_dev) hipFree(c->kkt_dev);
-    if (c->fin_counter) hipFree(c->fin_counter);
-    if (c->ceil_cell) hipFree(c->ceil_cell);
-    if (c->tw_fh) hipFree(c->tw_fh);
-    if (c->tw_sh) hipFree(c->tw_sh);
-    if (c->tw_f) hipFree(c->tw_f);
-    if (c->tw_s) hipFree(c->tw_s);
-    hipHostFree(c->st_host);
-    if (c->st_pub) hipHostFree(c->st_pub);
-    if (c->seq_pub) hipHostFree(c->seq_pub);
-    hipHostFree(c->hist_host);
-    hipHostFree(c->J_ring_host);
-    hipFree(c->J_ring_dev);
-    if (c->cost_lvl_host) hipHostFree(c->cost_lvl_host);
-    for (hipEvent_t e : c->prof_ev) hipEventDestroy(e);
-    hipEventDestroy(c->ev0);
-    hipEventDestroy(c->ev1);
-    hipStreamDestroy(c->stream);
-    delete c;
+    teardown(c);
 }
 
 extern "C" int vch2d_batch(const vch2d_ctx *c) { return c ? c->B : VCH_ERR_ARG; }
@@ -1813,8 +1805,9 @@ static int backward_core(vch2d_ctx *c, const double *phi_hist_dev, int M, const 
     for (double *o : outs)
         if (o) nsave += keep.size();
     double *save = nullptr;
+    vch_group scope(c->pool);                  // save goes away on every path out
     if (nsave) {
-        HIPCHK(hipMalloc((void **)&save, nsave * blk * sizeof(double)));
+        MEMCHK(c->pool.dev(&save, nsave * blk * sizeof(double)));
         size_t k = 0;
         for (double *o : outs)
             for (size_t i = 0; o && i < keep.size(); ++i, ++k)
@@ -1829,7 +1822,6 @@ static int backward_core(vch2d_ctx *c, const double *phi_hist_dev, int M, const 
             for (size_t i = 0; o && i < keep.size(); ++i, ++k)
                 HIPCHK(hipMemcpyAsync(o + keep[i] * hs, save + k * blk, blk * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
-        HIPCHK(hipFree(save));
     }
     c->redo_iters = iters;                     // the first pass stays in the books (fill_stats, counters)
     c->n_sync += syncs;
@@ -1922,6 +1914,18 @@ static int set_cost_weights(vch2d_ctx *c, const double *x, const double *y) {
     return 0;
 }
 
+// workgroup partials [B][Mmax+1][nblk][4] and level sums [B][Mmax+1][4] (device and pinned) of the cost, the norms, the free
+// energy and the prox step's change: all three or none
+static int ensure_cost_bufs(vch2d_ctx *c) {
+    if (c->cost_part) return 0;
+    const size_t lv = (size_t)c->B * (c->Mmax + 1) * 4 * 8;
+    vch_group g(c->pool);
+    MEMCHK(c->pool.dev(&c->cost_part, lv * c->nblk));
+    MEMCHK(c->pool.dev(&c->cost_lvl, lv));
+    MEMCHK(c->pool.host(&c->cost_lvl_host, lv));
+    return g.keep();
+}
+
 // J_out [B][5]; arrays on the device in history layout; phiQ_dev NULL + ramp => on-the-fly ramp target
 static int cost_core(vch2d_ctx *c, const double *phi_dev, const double *u_dev, const double *pq_dev, const double *pt_dev,
                      bool ramp, int M, const double *t_hist, const vch_opt_params *opts, double *J_out,
@@ -1929,12 +1933,7 @@ static int cost_core(vch2d_ctx *c, const double *phi_dev, const double *u_dev, c
                      int n_opts = 1 /* 1: opts[0] weighs every trajectory; B: trajectory b takes opts[b] */) {
     const Geom &G = c->G;
     const int levels = M + 1, ntiles = c->nblk;
-    if (!c->cost_part) {
-        const size_t n = (size_t)c->B * (c->Mmax + 1) * ntiles * 4;
-        HIPCHK(hipMalloc((void **)&c->cost_part, n * 8));
-        HIPCHK(hipMalloc((void **)&c->cost_lvl, (size_t)c->B * (c->Mmax + 1) * 4 * 8));
-        HIPCHK(hipHostMalloc((void **)&c->cost_lvl_host, (size_t)c->B * (c->Mmax + 1) * 4 * 8));
-    }
+    VCHCHK(ensure_cost_bufs(c));
     dim3 g(ntiles, levels, c->B);
     LAUNCHC(PC_COST, k_cost, g, dim3(NTH), G, G.tiles_f, phi_dev, u_dev, pq_dev, pt_dev, (const double *)c->phi0,
            (const double *)((ramp && !pq_dev) ? c->tfrac_dev : nullptr), hist_stride(c), M, (const double *)c->W_cost,
@@ -1970,12 +1969,7 @@ static int cost_core(vch2d_ctx *c, const double *phi_dev, const double *u_dev, c
 static int l2sq_core(vch2d_ctx *c, const double *arr, long stride, int levels, const double *t_hist, double *out) {
     const Geom &G = c->G;
     const int ntiles = c->nblk;
-    if (!c->cost_part) {
-        const size_t n = (size_t)c->B * (c->Mmax + 1) * ntiles * 4;
-        HIPCHK(hipMalloc((void **)&c->cost_part, n * 8));
-        HIPCHK(hipMalloc((void **)&c->cost_lvl, (size_t)c->B * (c->Mmax + 1) * 4 * 8));
-        HIPCHK(hipHostMalloc((void **)&c->cost_lvl_host, (size_t)c->B * (c->Mmax + 1) * 4 * 8));
-    }
+    VCHCHK(ensure_cost_bufs(c));
     LAUNCH(k_cost, dim3(ntiles, levels, c->B), dim3(NTH), G, G.tiles_f, arr, (const double *)nullptr, (const double *)nullptr,
            (const double *)nullptr, (const double *)nullptr, (const double *)nullptr, stride, -1, (const double *)c->W_cost,
            c->cost_part);
@@ -2054,12 +2048,7 @@ extern "C" int vch2d_free_energy(vch2d_ctx *c, const double *phi_hist, int rows,
         wd = c->phi_trial;
     }
     const int ntiles = c->nblk, A0 = c->prm.Nx + 1, A1 = c->prm.Ny + 1;
-    if (!c->cost_part) {
-        const size_t n = (size_t)c->B * (c->Mmax + 1) * ntiles * 4;
-        HIPCHK(hipMalloc((void **)&c->cost_part, n * 8));
-        HIPCHK(hipMalloc((void **)&c->cost_lvl, (size_t)c->B * (c->Mmax + 1) * 4 * 8));
-        HIPCHK(hipHostMalloc((void **)&c->cost_lvl_host, (size_t)c->B * (c->Mmax + 1) * 4 * 8));
-    }
+    VCHCHK(ensure_cost_bufs(c));
     const int nt = (A0 * A1 + 1023) / 1024;            // <= tiles_f * tiles_s
     LAUNCH(k_energy, dim3(nt, rows, c->B), dim3(NTH), c->G, A0, A1, c->P.c1, c->P.c2, eps > 0 ? eps : 1e-8, pd, wd,
            hist_stride(c), c->cost_part);
@@ -2081,12 +2070,7 @@ extern "C" int vch2d_free_energy(vch2d_ctx *c, const double *phi_hist, int rows,
 static int grad_prox_core(vch2d_ctx *c, const double *u_dev, const double *r_dev, int rows, const double *alpha_host,
                           const double *opt_tab, double *uout_dev, double *change_out) {
     HIPCHK(hipMemcpyAsync(c->alpha_dev, alpha_host, sizeof(double) * c->B, hipMemcpyHostToDevice, c->stream));
-    if (!c->cost_part) {
-        const size_t n = (size_t)c->B * (c->Mmax + 1) * c->nblk * 4;
-        HIPCHK(hipMalloc((void **)&c->cost_part, n * 8));
-        HIPCHK(hipMalloc((void **)&c->cost_lvl, (size_t)c->B * (c->Mmax + 1) * 4 * 8));
-        HIPCHK(hipHostMalloc((void **)&c->cost_lvl_host, (size_t)c->B * (c->Mmax + 1) * 4 * 8));
-    }
+    VCHCHK(ensure_cost_bufs(c));
     dim3 g(c->nblk, rows, c->B);
     HIPCHK(hipMemsetAsync(c->cost_part, 0, (size_t)c->B * rows * c->nblk * 4 * 8, c->stream));
     LAUNCHC(PC_PROX, k_grad_prox, g, dim3(NTH), c->G, c->G.tiles_f, u_dev, r_dev, hist_stride(c), (const double *)c->alpha_dev, opt_tab,
@@ -2176,7 +2160,7 @@ extern "C" int vch2d_pgd_init_v(vch2d_ctx *c, const double *phi0, const double *
         c->rampT = T;
         c->tfrac.resize(M + 1);
         for (int n = 0; n <= M; ++n) c->tfrac[n] = t_hist[n] / T;      // G2:221
-        if (!c->tfrac_dev) HIPCHK(hipMalloc((void **)&c->tfrac_dev, sizeof(double) * (c->Mmax + 1)));
+        if (!c->tfrac_dev) MEMCHK(c->pool.dev(&c->tfrac_dev, sizeof(double) * (c->Mmax + 1)));
         HIPCHK(hipMemcpyAsync(c->tfrac_dev, c->tfrac.data(), sizeof(double) * (M + 1), hipMemcpyHostToDevice, c->stream));
         // materialise phi_Q once on the device (the adjoint source reads it every step)
         VCHCHK(ensure_hist(c, &c->phiQ));
@@ -2409,10 +2393,14 @@ static int second_order_core(vch2d_ctx *c, const double *h, int h_rows, const do
     const Geom &G = c->G;
     const int B = c->B, levels = M + 1;
     const long hs = hist_stride(c);
-    if (!c->tan_part) HIPCHK(hipMalloc((void **)&c->tan_part, (size_t)B * (c->Mmax + 1) * c->nblk * TAN_NSUM * 8));
-    if (!c->tan_lvl) HIPCHK(hipMalloc((void **)&c->tan_lvl, (size_t)B * (c->Mmax + 1) * TAN_NSUM * 8));
-    if (!c->tan_t) HIPCHK(hipMalloc((void **)&c->tan_t, (size_t)(c->Mmax + 1) * 8));
-    if (!c->tan_out) HIPCHK(hipMalloc((void **)&c->tan_out, (size_t)B * 6 * 8));
+    if (!c->tan_out) {              // all four or none
+        vch_group g(c->pool);
+        MEMCHK(c->pool.dev(&c->tan_part, (size_t)B * (c->Mmax + 1) * c->nblk * TAN_NSUM * 8));
+        MEMCHK(c->pool.dev(&c->tan_lvl, (size_t)B * (c->Mmax + 1) * TAN_NSUM * 8));
+        MEMCHK(c->pool.dev(&c->tan_t, (size_t)(c->Mmax + 1) * 8));
+        MEMCHK(c->pool.dev(&c->tan_out, (size_t)B * 6 * 8));
+        g.keep();
+    }
     VCHCHK(ensure_hist(c, &c->u_trial));            // the direction lives in the trial-control scratch
     VCHCHK(h2d_hist(c, c->u_trial, h, h_rows));
     VCHCHK(write_opt_tab(c, c->seam_tab, opts, n_opts));
@@ -2683,14 +2671,12 @@ extern "C" int vch2d_hessvec(vch2d_ctx *c, const double *h, int h_rows, int g_ro
     }
     if (!pgd && phi_Q) VCHCHK(ensure_hist(c, &c->phiQ));
     if (!c->hv_part) {
-        double *p = nullptr;
         const size_t n = (size_t)2 * c->B * c->nblk * NPART + (size_t)c->Mmax + 1 + 2 * (size_t)c->B;
-        if (hipMalloc((void **)&p, n * 8) != hipSuccess) {
+        if (c->pool.dev(&c->hv_part, n * 8)) {
             (void)hipGetLastError();
             return vch_fail(VCH_ERR_NOMEM, "vch2d_hessvec: hipMalloc of the partials failed");
         }
-        c->hv_part = p;
-        c->hv_wt = p + (size_t)2 * c->B * c->nblk * NPART;
+        c->hv_wt = c->hv_part + (size_t)2 * c->B * c->nblk * NPART;
         c->hv_dots = c->hv_wt + c->Mmax + 1;
     }
     const double *pq = nullptr, *pt = nullptr;
