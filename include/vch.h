@@ -247,18 +247,24 @@ int vch2d_pgd_kkt(vch2d_ctx *ctx, int refresh, double tol, int64_t *counts_out /
  * control and state history (ABI version stays 3: detect this entry point by symbol).  No adjoint and no nonlinear march:
  * the derivative of one Crank-Nicolson / Newton time level with respect to its inputs is one linear solve with the Newton
  * matrix J(phi*) of vch2d_jacobian_apply at the converged new level, its second derivative one more solve with the
- * same matrix.  phi* = phi_{n+1} + s_n is the Newton solution of step n before the march's interior mass fix
- * subtracted the shift s_n (vch2d_mass_shifts).  With dphi_0 = dmu_0 = dw_0 = 0 and d2phi_0 = d2mu_0 = 0, per step n:
+ * same matrix.  phi* is the Newton solution of step n before the march's interior mass fix subtracted the
+ * shift s_n (vch2d_mass_shifts) on its set I_n (the interior nodes |phi_c| < 1 - delta_sep - 5e-3 of the clipped solution;
+ * every node in the all-node form): phi* = phi_{n+1} + s_n on I_n, phi_{n+1} on the nodes the fix skipped.  With dphi_0 = dmu_0 = dw_0 = 0 and d2phi_0 = d2mu_0 = 0, per step n:
  *   dw'  = ((gamma/dt - 1/2) dw + 1/2 (h_{n+1} + h_n)) / (gamma/dt + 1/2)
  *   J [dphi*; dmu']   = [ tau dphi/dt + kappa/2 L dphi + 2 c2 dphi + 1/2 dmu + 1/2 (dw' + dw) ;  dphi/dt + 1/2 L dmu ]
  *   J [d2phi*; d2mu'] = [ tau d2phi/dt + kappa/2 L d2phi + 2 c2 d2phi + 1/2 d2mu - c1 rho(phi*) (dphi*)^2 ;
  *                         d2phi/dt + 1/2 L d2mu ],      rho(p) = 4 p / (1 - p^2)^2
- *   dphi' = dphi* - sum(wts dphi*) / W_int,   d2phi' = d2phi* - sum(wts d2phi*) / W_int      (where s_n != 0)
+ *   dphi' = dphi* - sum(wts dphi*) / W_int,   d2phi' = d2phi* - sum(wts d2phi*) / W_int      (on I_n, where s_n != 0)
  * The mass fix is linearised: the linearised step conserves the mass of dphi only in the weights of the Laplacian (its
  * Kronecker-order quirk), which are the fix's weights wts = hx hy outer(trapz_x, trapz_y) only for Nx == Ny.  The weighted
- * mean leaves the interior nodes (|phi*| < 1 - delta_sep - 5e-3, W_int their weight); dmu' and dw' are carried as they are.
- * The end-of-step clip is taken as the identity (inactive wherever |phi| < 1 - delta_sep); the call does NOT detect an active
- * clip or nodes outside the interior band.  Behind a state history the caller uploaded (vch2d_backward, vch2d_cost,
+ * mean leaves the nodes of I_n (W_int their weight, as the march recorded it); dmu' and dw' are carried as they are.
+ * Nodes outside the interior band are linearised exactly or REFUSED: the march keeps s_n and W_int but not I_n, and the call
+ * takes a node for interior where |phi_{n+1} + s_n| < 1 - delta_sep - 5e-3.  A skipped node within |s_n| of that threshold
+ * passes too; the classified weight then differs from W_int (by more than n eps, n nodes; checked in both directions)
+ * and the call returns VCH_ERR_STATE with
+ * "trajectory b, step n: interior set of the mass fix not recoverable ..." in vch_last_error (outputs are then undefined,
+ * the context stays usable and unchanged).  The end-of-step clip is taken as the identity (inactive wherever
+ * |phi| < 1 - delta_sep); an ACTIVE CLIP IS STILL NOT DETECTED.  Behind a state history the caller uploaded (vch2d_backward, vch2d_cost,
  * vch2d_free_energy) there is no march of this context and the shifts count as zero.  The L1 term J4 has no curvature away
  * from its kink and is left out.
  *   h       [B][h_rows][Nx+1][Ny+1] direction, row rule of a control: rows (n, n+1) drive step n while n < h_rows-1, zeros
@@ -305,7 +311,8 @@ int vch2d_mass_shifts(vch2d_ctx *ctx, double *out /* [B][M] */);
  * fix).  The Newton matrix obeys J^T = S J S^-1 with S = diag(-(2/dt) wq, wq), wq the trapezoid weights of the plane as
  * stored, so every transposed solve is the tangent's own solve between two diagonal scalings: one solve per step for the
  * gradient, and for H h one tangent solve, one gradient solve and one more transposed solve per step (3 M per trajectory).
- * The linearised mass fix enters by its transpose, the clip is taken as the identity (as in vch2d_second_order).
+ * The linearised mass fix enters by its transpose, the clip is taken as the identity, and a state history whose interior
+ * set of the mass fix is not recoverable is refused with VCH_ERR_STATE (all as in vch2d_second_order).
  *   h        [B][h_rows][Nx+1][Ny+1] direction (row rule of a control) or NULL (allowed iff order 1)
  *   g_rows   rows of the control the gradient refers to: M + 1 about a resident PGD iterate; min(rows of the control, M + 1)
  *            after vch2d_forward with a control; any of 1..M+1 after a forward without one (the zero control of that many

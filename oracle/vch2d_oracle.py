@@ -351,7 +351,10 @@ def forward(P: Params2D, control=None, phi0=None, seed=42, amp=0.1, max_steps=No
     mu and w are carried un-recomputed after the clip/mass fix (F2:579).
 
     `stats` (optional dict) also collects, per step, "mass_shifts" (the value the mass fix subtracted, 0.0 where it was not
-    applied) and "mass_shift_interior" (True where it was subtracted on the interior nodes only, F2:567-574)."""
+    applied), "mass_shift_interior" (True where it was subtracted on the interior nodes only, F2:567-574), "mass_masks" (the
+    boolean plane of the nodes it was subtracted on: the interior set, every node for the all-node form, none where it was not
+    applied), "mass_w_int" (the weight it divided by: W_int, Lx Ly for the all-node form, 0.0 where it was not applied) and
+    "phi_clipped" (the clipped Newton solution phi_c the set was read from)."""
     Nx, Ny = int(P.Nx), int(P.Ny)
     hx, hy = P.Lx / Nx, P.Ly / Ny
     x = np.linspace(0.0, P.Lx, Nx + 1)
@@ -384,19 +387,25 @@ def forward(P: Params2D, control=None, phi0=None, seed=42, amp=0.1, max_steps=No
         phi = np.clip(phi_new, lo, hi)
         err = np.sum(wts_h * phi) - mass0
         shift, shift_interior = 0.0, False
+        mask, w_div, phi_c = np.zeros(phi.shape, dtype=bool), 0.0, phi.copy()
         if abs(err) > 1e-16:                                   # F2:567-577
             interior = np.abs(phi) < (1.0 - DELTA_SEP - 5e-3)
             Wint = float(np.sum(wts_h[interior]))
             if Wint > 0.0:
                 shift, shift_interior = err / Wint, True
+                mask, w_div = interior, Wint
                 phi[interior] -= err / Wint
             else:
                 shift = err / (P.Lx * P.Ly)
+                mask, w_div = np.ones(phi.shape, dtype=bool), P.Lx * P.Ly
                 phi -= err / (P.Lx * P.Ly)
                 phi = np.clip(phi, lo, hi)
         if stats is not None:
             stats.setdefault("mass_shifts", []).append(float(shift))
             stats.setdefault("mass_shift_interior", []).append(shift_interior)
+            stats.setdefault("mass_masks", []).append(mask)
+            stats.setdefault("mass_w_int", []).append(float(w_div))
+            stats.setdefault("phi_clipped", []).append(phi_c)
         mu, w = mu_new, w_new
         t += dts
         step += 1

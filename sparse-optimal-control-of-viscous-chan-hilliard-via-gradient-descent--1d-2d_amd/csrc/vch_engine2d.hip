@@ -158,9 +158,12 @@ struct vch2d_ctx {
     double *post_hist;                    // ... its history level (or NULL)
     double *post_rec;                     // ... and its cell of the shift record (or NULL)
     // what the mass fix subtracted at the end of every step of a march, beside the history the march wrote:
-    // [B][Mmax][SHIFT_REC] = {shift, 1.0 where it went to the interior nodes only}; shift_hist belongs to phi_hist,
-    // shift_trial to phi_trial (a line-search trial's record moves with its history, copy_traj_shifts)
+    // [B][Mmax][SHIFT_REC] = {shift, the weight it was divided by: W_int where it went to the interior nodes only, 0.0 for the
+    // all-node form, 1.0 where no fix ran}; shift_hist belongs to phi_hist, shift_trial to phi_trial (a line-search trial's
+    // record moves with its history, copy_traj_shifts)
     double *shift_hist, *shift_trial;
+    int *fix_bad = nullptr;               // [B] refusal cells of vch2d_second_order / vch2d_hessvec (FixCheck); lazy, so that
+                                          // the buffers every context has stay where they were
     bool shift_res = false;               // shift_hist is the record of the resident state history
     TrajState *st, *st_host;
     // look at the device state without a copy command and a stream wait: a one-workgroup kernel writes the records into
@@ -2360,6 +2363,35 @@ extern "C" int vch2d_pgd_kkt(vch2d_ctx *c, int refresh, double tol, int64_t *cou
 // exact second-order check: tangent marches about the resident control and state history (kernels: "Tangent march" in
 // vch_kernels2d.h)
 // ------------------------------------------------------------------------------------
+// The refusal cells of a linearisation call (FixCheck in vch_kernels2d.h): cleared before the first kernel of the call, read
+// with the look that closes it.  A step whose classified interior weight exceeds the weight the march recorded has a skipped
+// node that passes for an interior one: the derivative would be that of another scheme, so the call returns an error.  The
+// context stays as a successful call leaves it.
+static int ensure_fix_bad(vch2d_ctx *c) {
+    if (c->fix_bad) return 0;
+    if (c->pool.dev(&c->fix_bad, sizeof(int) * c->B)) {
+        (void)hipGetLastError();
+        return vch_fail(VCH_ERR_NOMEM, "hipMalloc of the mass fix's refusal cells failed");
+    }
+    return 0;
+}
+static int fix_check_begin(vch2d_ctx *c) {
+    HIPCHK(hipMemsetAsync(c->fix_bad, 0xff, sizeof(int) * c->B, c->stream));
+    return 0;
+}
+static FixCheck fix_check_of(const vch2d_ctx *c, int step) {
+    return FixCheck{c->fix_bad, step, (double)c->G.ns * c->G.nf * 2.220446049250313e-16};
+}
+static int fix_check_end(const char *fn, const std::vector<int> &bad) {
+    for (size_t b = 0; b < bad.size(); ++b)
+        if (bad[b] >= 0)
+            return vch_fail(VCH_ERR_STATE,
+                            "%s: trajectory %d, step %d: interior set of the mass fix not recoverable from the state history "
+                            "(a node the fix skipped lies within its shift of the band's threshold); the linearisation is refused",
+                            fn, (int)b, bad[b]);
+    return 0;
+}
+
 // One tangent solve: the right-hand side is in slot 0 (k_tan_rhs); x = 0 start, the context's lin_tol, every trajectory
 // gated by its own lin_active; on return dphi* is in c->xf and dmu' in c->dmu.  With a shift record (rec: the step's cell)
 // the partials of the fix's weighted mean of dphi* follow in c->part_mass, for the kernel that reads c->xf next.
@@ -2393,6 +2425,7 @@ static int second_order_core(vch2d_ctx *c, const double *h, int h_rows, const do
     const Geom &G = c->G;
     const int B = c->B, levels = M + 1;
     const long hs = hist_stride(c);
+    VCHCHK(ensure_fix_bad(c));
     if (!c->tan_out) {              // all four or none
         vch_group g(c->pool);
         MEMCHK(c->pool.dev(&c->tan_part, (size_t)B * (c->Mmax + 1) * c->nblk * TAN_NSUM * 8));
@@ -2406,6 +2439,7 @@ static int second_order_core(vch2d_ctx *c, const double *h, int h_rows, const do
     VCHCHK(write_opt_tab(c, c->seam_tab, opts, n_opts));
     HIPCHK(hipMemcpyAsync(c->tan_t, t_hist, sizeof(double) * levels, hipMemcpyHostToDevice, c->stream));
     VCHCHK(reset_counters(c));
+    VCHCHK(fix_check_begin(c));
     HIPCHK(hipEventRecord(c->ev0, c->stream));
     // planes: dphi, dmu, d2phi, d2mu, and dw in two copies
     double *dphi = c->tmp[0], *dmu = c->tmp[1], *d2phi = c->tmp[2], *d2mu = c->tmp[3], *dw[2] = {c->tmp[4], c->tmp[5]};
@@ -2424,7 +2458,7 @@ static int second_order_core(vch2d_ctx *c, const double *h, int h_rows, const do
                        lvl < h_rows ? c->u_trial + (long)lvl * G.plane : (const double *)nullptr,
                        hs, pt, lvl == M ? 1 : 0, d1, d2, c->xf, c->dmu, dst_phi, dst_mu, c->W_cost,
                        lvl == 0 ? 0 : (d2 ? 2 : 1), lvl == 0 ? (const double *)nullptr : rec_of(lvl - 1), rec_stride,
-                       (const double *)c->part_mass, c->P.LxLy};
+                       (const double *)c->part_mass, c->P.LxLy, fix_check_of(c, lvl - 1)};
         LAUNCH(k_tan_level, c->grid, dim3(NTH), G, a, c->tan_part + (long)lvl * c->nblk * TAN_NSUM, part_stride);
         return 0;
     };
@@ -2458,12 +2492,15 @@ static int second_order_core(vch2d_ctx *c, const double *h, int h_rows, const do
     LAUNCH(k_tan_scalars, dim3(B), dim3(64), M, (const double *)c->tan_lvl, (const double *)c->tan_t, (const double *)c->seam_tab,
            order, c->tan_out);
     HIPCHK(hipEventRecord(c->ev1, c->stream));
+    std::vector<int> bad(B, -1);
     HIPCHK(hipMemcpyAsync(out, c->tan_out, sizeof(double) * 6 * B, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(bad.data(), c->fix_bad, sizeof(int) * B, hipMemcpyDeviceToHost, c->stream));
     VCHCHK(sync_state(c));
     float ms = 0;
     hipEventElapsedTime(&ms, c->ev0, c->ev1);
     fill_stats(c, stats, ms);
-    return reset_counters(c);       // the records as the end of a PGD iteration leaves them
+    VCHCHK(reset_counters(c));      // the records as the end of a PGD iteration leaves them
+    return fix_check_end("vch2d_second_order", bad);
 }
 
 // The argument rules vch2d_second_order and vch2d_hessvec share, in the order their messages are pinned: checked before
@@ -2561,6 +2598,7 @@ static int hessvec_core(vch2d_ctx *c, const double *h, int h_rows, int g_rows, c
     VCHCHK(write_opt_tab(c, c->seam_tab, opts, n_opts));
     HIPCHK(hipMemcpyAsync(c->hv_wt, wt.data(), sizeof(double) * wt.size(), hipMemcpyHostToDevice, c->stream));
     VCHCHK(reset_counters(c));
+    VCHCHK(fix_check_begin(c));
     HIPCHK(hipEventRecord(c->ev0, c->stream));
     c->guess_wr = -1;          // the back substitution keeps no increment for a march's starting guesses
     c->cheb_enq = -1;
@@ -2586,7 +2624,7 @@ static int hessvec_core(vch2d_ctx *c, const double *h, int h_rows, int g_rows, c
             LAUNCH((k_tan_rhs<0>), c->grid, dim3(NTH), G, c->P, a1, dt[n], c->Rphi_s, c->rhs_s, c->D_s, c->part);
             VCHCHK(tangent_solve(c, dt[n], phi1, rec_of(n)));
             LAUNCH(k_hv_keep, c->grid, dim3(NTH), G, (const double *)c->xf, (const double *)c->dmu, phi1, hs, rec_of(n), rec_stride,
-                   (const double *)c->part_mass, c->P.LxLy, c->hv_V + (long)n * G.plane, c->hv_DP + (long)(n + 1) * G.plane, dphi,
+                   (const double *)c->part_mass, c->P.LxLy, fix_check_of(c, n), c->hv_V + (long)n * G.plane, c->hv_DP + (long)(n + 1) * G.plane, dphi,
                    dmu);
         }
     }
@@ -2620,7 +2658,8 @@ static int hessvec_core(vch2d_ctx *c, const double *h, int h_rows, int g_rows, c
             // solve reuses it (the emit kernel in between leaves that plane alone)
             HvRhsArgs a{c->tmp[3 * sw], c->tmp[3 * sw + 1], phi1, hs, rec_of(k), rec_stride,
                         (const double *)(c->hv_part + sw * pstride), (const double *)c->wts_mass,
-                        sw ? (const double *)c->xf : nullptr, sw ? (const double *)(c->hv_V + (long)k * G.plane) : nullptr};
+                        sw ? (const double *)c->xf : nullptr, sw ? (const double *)(c->hv_V + (long)k * G.plane) : nullptr,
+                        fix_check_of(c, k)};
             if (sw == 0) LAUNCH((k_hv_rhs<0>), c->grid, dim3(NTH), G, c->P, a, dt[k], c->Rphi_s, c->rhs_s, c->D_s, c->part);
             else LAUNCH((k_hv_rhs<1>), c->grid, dim3(NTH), G, c->P, a, dt[k], c->Rphi_s, c->rhs_s, c->D_s, c->part);
             VCHCHK(tangent_solve(c, dt[k], phi1, nullptr));
@@ -2634,14 +2673,17 @@ static int hessvec_core(vch2d_ctx *c, const double *h, int h_rows, int g_rows, c
         LAUNCH(k_hv_dots_fin, dim3(B), dim3(64), (const double *)c->hv_part, c->nblk, h ? 1 : 0, order == 2 ? 1 : 0, c->hv_dots);
     }
     HIPCHK(hipEventRecord(c->ev1, c->stream));
+    std::vector<int> bad(B, -1);
     if (dots_out) HIPCHK(hipMemcpyAsync(dots_out, c->hv_dots, sizeof(double) * 2 * B, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(bad.data(), c->fix_bad, sizeof(int) * B, hipMemcpyDeviceToHost, c->stream));
     VCHCHK(sync_state(c));
     if (grad_out) VCHCHK(d2h_hist(c, grad_out, c->hv_G, g_rows));
     if (order == 2) VCHCHK(d2h_hist(c, hv_out, c->hv_H, h_rows));
     float ms = 0;
     hipEventElapsedTime(&ms, c->ev0, c->ev1);
     fill_stats(c, stats, ms);
-    return reset_counters(c);       // the records as the end of a PGD iteration leaves them
+    VCHCHK(reset_counters(c));      // the records as the end of a PGD iteration leaves them
+    return fix_check_end("vch2d_hessvec", bad);
 }
 
 extern "C" int vch2d_hessvec(vch2d_ctx *c, const double *h, int h_rows, int g_rows, const double *dt, int M,
@@ -2670,6 +2712,7 @@ extern "C" int vch2d_hessvec(vch2d_ctx *c, const double *h, int h_rows, int g_ro
         VCHCHK(ensure_hist(c, &c->hv_DP));
     }
     if (!pgd && phi_Q) VCHCHK(ensure_hist(c, &c->phiQ));
+    VCHCHK(ensure_fix_bad(c));
     if (!c->hv_part) {
         const size_t n = (size_t)2 * c->B * c->nblk * NPART + (size_t)c->Mmax + 1 + 2 * (size_t)c->B;
         if (c->pool.dev(&c->hv_part, n * 8)) {

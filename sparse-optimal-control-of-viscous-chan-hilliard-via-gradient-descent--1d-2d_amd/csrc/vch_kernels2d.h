@@ -791,11 +791,12 @@ struct PostFix {
         }
         return ph;
     }
-    // the step's cell of the shift record (vch2d_second_order linearises the fix about it): what was subtracted, and whether
-    // on the interior nodes only; written by one lane of one workgroup per trajectory
-    __device__ __forceinline__ void record(double *rec) const {
+    // the step's cell of the shift record (vch2d_second_order and vch2d_hessvec linearise the fix about it): what was
+    // subtracted, and the weight it was divided by -- W_int (sm2[1], the sums the fix was built from) where it went to the
+    // interior nodes only, 0.0 for the all-node form, 1.0 where no fix ran; written by one lane of one workgroup per trajectory
+    __device__ __forceinline__ void record(double *rec, const double *sm2) const {
         rec[0] = shift;
-        rec[1] = (fix && !interior_ok) ? 0.0 : 1.0;
+        rec[1] = fix ? (interior_ok ? sm2[1] : 0.0) : 1.0;
     }
 };
 constexpr int SHIFT_REC = 2;
@@ -818,7 +819,7 @@ __global__ __launch_bounds__(NTH) void k_post(Geom G, Phys P, const TrajState *_
     post_sums(part, nblk, b, sm);
     __syncthreads();
     const PostFix pf(sm, S.mass0, P.LxLy);
-    if (rec && blk == 0 && threadIdx.x == 0) pf.record(rec + b * rec_stride);
+    if (rec && blk == 0 && threadIdx.x == 0) pf.record(rec + b * rec_stride, sm);
     for (int k = 0; k < TY / 4; ++k) {
         int r = r0 + ly0 + 4 * k, c = c0 + lx;
         if (r < G.ns && c < G.nf) {
@@ -1786,7 +1787,7 @@ __device__ __forceinline__ void eval_body(const Geom &G, const Phys &P, TrajStat
                 }
                 __syncthreads();
                 const PostFix pf(s_post, mass0, P.LxLy);
-                if (post.rec && blk == 0 && threadIdx.x == 0) pf.record(post.rec + b * post.rec_stride);
+                if (post.rec && blk == 0 && threadIdx.x == 0) pf.record(post.rec + b * post.rec_stride, s_post);
 #pragma unroll
                 for (int i = 0; i < I2; ++i) raw[i] = pf.apply(raw[i]);
             }
@@ -1820,7 +1821,7 @@ __device__ __forceinline__ void eval_body(const Geom &G, const Phys &P, TrajStat
                 post_sums(post.part, nblk, (int)b, s_post);
                 __syncthreads();
                 const PostFix pf(s_post, st[b].mass0, P.LxLy);
-                if (post.rec && blk == 0 && threadIdx.x == 0) pf.record(post.rec + b * post.rec_stride);
+                if (post.rec && blk == 0 && threadIdx.x == 0) pf.record(post.rec + b * post.rec_stride, s_post);
 #pragma unroll
                 for (int i = 0; i < I2; ++i) {
                     const int e = threadIdx.x + i * NTH;
@@ -2792,15 +2793,26 @@ __global__ __launch_bounds__(NTH) void k_cg_update_adj(Geom G, const TrajState *
 //   J(phi*) [dphi*; dmu']   = [ tau dphi/dt + kappa/2 L dphi + 2 c2 dphi + 1/2 dmu + 1/2 (dw' + dw) ;  dphi/dt + 1/2 L dmu ]
 //   J(phi*) [d2phi*; d2mu'] = [ tau d2phi/dt + kappa/2 L d2phi + 2 c2 d2phi + 1/2 d2mu - c1 rho(phi*) (dphi*)^2 ;
 //                               d2phi/dt + 1/2 L d2mu ],             rho(p) = 4 p / (1 - p^2)^2 = reglog''(p)
-//   dphi' = dphi* - sum(wts dphi*) / W_int,   d2phi' = d2phi* - sum(wts d2phi*) / W_int
-// phi* = phi_{n+1} + s_n is the Newton solution of the step before the march's mass fix subtracted s_n (the shift record the
-// march keeps beside its history, PostFix::record), J = the Newton matrix of k_jac_apply there: one linear solve per field
+//   dphi' = dphi* - sum(wts dphi*) / W_int,   d2phi' = d2phi* - sum(wts d2phi*) / W_int            (on the fix's set I_n only)
+// phi* is the Newton solution of the step before the march's mass fix subtracted s_n ON ITS SET I_n (the interior nodes, or
+// every node in the all-node form): phi* = phi_{n+1} + s_n on I_n and phi_{n+1} elsewhere; s_n and the weight W_int the fix
+// divided by come from the shift record the march keeps beside its history (PostFix::record).  J = the Newton matrix of
+// k_jac_apply at phi*: one linear solve per field
 // and step, by the Schur reduction + preconditioned CG of the Newton solves (k_fin_lin_begin -> schur_solve -> dmu_ceiling).
 // The mass fix is linearised, not taken as the identity: the linearised step conserves the mass of dphi in the weights of
 // the Laplacian (its Kronecker-order quirk), which are the fix's weights wts = hx hy outer(trapz_x, trapz_y) only for
-// Nx == Ny.  The weighted mean leaves the interior nodes (|phi*| < 1 - delta_sep - 5e-3, W_int their weight), as the shift
-// did; where the march did not apply the fix (s_n == 0) nothing is subtracted; dmu' and dw' are carried as they are.  The clip
-// is inactive wherever |phi| < 1 - delta_sep.  An active clip, or nodes outside the interior band, are NOT detected.
+// Nx == Ny.  The weighted mean leaves the nodes of I_n, as the shift did; where the march did not apply the fix (s_n == 0)
+// nothing is subtracted; dmu' and dw' are carried as they are.
+// I_n is not kept by the march and is NOT recoverable from phi_{n+1} and s_n in general: the sweeps classify a node as
+// interior where |phi_{n+1} + s_n| < 1 - delta_sep - 5e-3, which every interior node passes, and so does a skipped node that
+// lies within |s_n| of the threshold with s_n pointing inward.  In exact arithmetic misclassification can only add weight
+// (in floating point (phi_c - s) + s may also round an interior node one ulp under the threshold up to it, which takes
+// weight away), so the classified weight (k_tan_mass slot 1, k_hv_emit acc[1]) equals the recorded W_int when every node is
+// classified right: where the two differ by more than round-off, in either direction (TanFix::unrecoverable; one node
+// changes the sum by at least hx hy / 4) the step is marked in the
+// context's refusal cells and the call returns an error instead of a wrong derivative.  So nodes outside the interior band
+// are linearised exactly or refused.  The clip is inactive wherever |phi| < 1 - delta_sep; an ACTIVE CLIP IS STILL NOT
+// DETECTED.
 // ---------------------------------------------------------------------------------
 __device__ __forceinline__ double tan_rho(double phi) {      // reglog''(p), p clipped to the band of jac_diag
     const double lim = sqrt(1.0 - DELTA_SEP * DELTA_SEP);
@@ -2808,18 +2820,44 @@ __device__ __forceinline__ double tan_rho(double phi) {      // reglog''(p), p c
     return 4.0 * p / (q * q);
 }
 
-// The linearised mass fix of one solve's output x: sums = {sum wts x, W_int} (k_tan_mass's partials through post_sums, read
-// only where the step has a shift), rec = the step's cell of the shift record.
+// The set the mass fix of a step shifted, as far as the history tells: phi1 = the stored level (after the fix), s = the
+// step's shift, all = the all-node form.  s == 0 (no fix): phi* = phi1 whatever the answer.
+__device__ __forceinline__ bool fix_in_set(double phi1, double s, bool all) {
+    return all || fabs(phi1 + s) < (1.0 - DELTA_SEP) - 5e-3;
+}
+__device__ __forceinline__ double fix_phi_star(double phi1, double s, bool all) { return fix_in_set(phi1, s, all) ? phi1 + s : phi1; }
+__device__ __forceinline__ bool fix_all(const double *rec) { return rec && rec[1] == 0.0; }
+
+// The linearised mass fix of one solve's output x: sums = {sum wts x, classified interior weight} (k_tan_mass's partials
+// through post_sums, read only where the step has a shift), rec = the step's cell of the shift record {s_n, W_int}.
 struct TanFix {
-    double mean, thr;
+    double mean, shift, w_rec;
     bool all;
     __device__ __forceinline__ TanFix(const double *sums, const double *rec, double LxLy) {
-        thr = (1.0 - DELTA_SEP) - 5e-3;
-        all = rec && rec[1] == 0.0;              // the march fell back to the all-node form (no interior node)
-        mean = (rec && rec[0] != 0.0) ? sums[0] / (all ? LxLy : sums[1]) : 0.0;
+        shift = rec ? rec[0] : 0.0;
+        w_rec = rec ? rec[1] : 1.0;
+        all = fix_all(rec);                      // the march fell back to the all-node form (no interior node)
+        mean = shift != 0.0 ? sums[0] / (all ? LxLy : w_rec) : 0.0;
     }
-    __device__ __forceinline__ double apply(double v, double phi_star) const {
-        return (all || fabs(phi_star) < thr) ? v - mean : v;
+    __device__ __forceinline__ double apply(double v, double phi1) const {
+        return fix_in_set(phi1, shift, all) ? v - mean : v;
+    }
+    // The classified weight is not the weight the march divided by.  Above it: a skipped node passes for an interior one.
+    // Below it, in exact arithmetic impossible (an interior node has |phi_c| < thr and phi1 + s = phi_c), in floating point
+    // possible where (phi_c - s) + s rounds up to the threshold for an interior node one ulp under it: then the node is
+    // taken for a skipped one.  Either way the set is not the march's, so the check is two-sided.
+    __device__ __forceinline__ bool unrecoverable(const double *sums, double wtol) const {
+        return shift != 0.0 && !all && fabs(sums[1] - w_rec) > w_rec * wtol;
+    }
+};
+// Refusal cells of a call, one int per trajectory: the first step whose interior set is not recoverable, -1 = none.  Written
+// by one lane of one workgroup per trajectory in the kernels that have just reduced the sums (no per-node pass of its own).
+struct FixCheck {
+    int *bad;           // [B]
+    int step;
+    double wtol;        // round-off allowance of the weight comparison: nodes x eps
+    __device__ __forceinline__ void look(const TanFix &tf, const double *sums, long b, int blk) const {
+        if (blk == 0 && threadIdx.x == 0 && tf.unrecoverable(sums, wtol) && (bad[b] < 0 || step < bad[b])) bad[b] = step;
     }
 };
 
@@ -2832,7 +2870,7 @@ __global__ __launch_bounds__(NTH) void k_tan_mass(Geom G, const double *__restri
     __shared__ double sred[NPART * 4];
     const double s = rec[b * rec_stride];
     if (s == 0.0) return;
-    const double thr = (1.0 - DELTA_SEP) - 5e-3;
+    const bool all = fix_all(rec + b * rec_stride);
     const long pb = b * G.plane, hb = b * hist_stride;
     double acc[2] = {0.0, 0.0};
     for (int k = 0; k < TY / 4; ++k) {
@@ -2841,7 +2879,7 @@ __global__ __launch_bounds__(NTH) void k_tan_mass(Geom G, const double *__restri
             const long o = (long)r * G.pitch + c;
             const double w = wts[o];
             acc[0] += w * x[pb + o];
-            if (fabs(phi1[hb + o] + s) < thr) acc[1] += w;
+            if (fix_in_set(phi1[hb + o], s, all)) acc[1] += w;
         }
     }
     const int op[2] = {0, 0};
@@ -2865,7 +2903,7 @@ struct TanRhsArgs {
 // Right-hand side of a tangent solve in the form k_solve_setup leaves: with [A; Bv] the right-hand side above,
 // R_phi := -A, rhs := Bv - L A (Schur), D from phi_{n+1}, partials {-, sum rhs^2, min D, max D} for k_fin_lin_begin (mode 2).
 // A is evaluated on the tile and its one-node halo (from dphi with a two-node halo), so that L A needs no second launch.
-// D and rho are taken at phi* = phi_{n+1} + s_n.
+// D and rho are taken at phi* (fix_phi_star).
 template <int SECOND>
 __global__ __launch_bounds__(NTH) void k_tan_rhs(Geom G, Phys P, TanRhsArgs a, double dt, double *__restrict__ Rphi,
                                                  double *__restrict__ rhs, double *__restrict__ D, double *__restrict__ part) {
@@ -2879,6 +2917,7 @@ __global__ __launch_bounds__(NTH) void k_tan_rhs(Geom G, Phys P, TanRhsArgs a, d
     const long pb = b * G.plane, hb = b * a.hist_stride;
     const double *rec = a.rec ? a.rec + b * a.rec_stride : (const double *)nullptr;
     const double shift = rec ? rec[0] : 0.0;
+    const bool all = fix_all(rec);
     load_tile<2>(sa, a.a + pb, G, c0, r0);
     load_tile<1>(sm, a.m + pb, G, c0, r0);
     if (SECOND && shift != 0.0) post_sums(a.mpart, nblk, (int)b, s_fix);
@@ -2898,7 +2937,7 @@ __global__ __launch_bounds__(NTH) void k_tan_rhs(Geom G, Phys P, TanRhsArgs a, d
         double v = P.tau * av / dt + 0.5 * P.kappa * lap_at<W2>(sa, p2, G.ax, G.ay) + 2.0 * P.c2 * av + 0.5 * sm[e];
         if (SECOND) {
             const double d = a.d1[pb + o];
-            v -= P.c1 * tan_rho(a.phi1[hb + o] + shift) * (d * d);
+            v -= P.c1 * tan_rho(fix_phi_star(a.phi1[hb + o], shift, all)) * (d * d);
         } else {
             const double w0 = a.w_in[pb + o];
             v += 0.5 * (w_new(o, w0) + w0);
@@ -2914,13 +2953,13 @@ __global__ __launch_bounds__(NTH) void k_tan_rhs(Geom G, Phys P, TanRhsArgs a, d
             const long o = (long)r * G.pitch + c;
             const double rm = sa[(ly + 2) * W2 + lx + 2] / dt + 0.5 * lap_at<W>(sm, p, G.ax, G.ay);
             const double rh = rm - lap_at<W>(sr, p, G.ax, G.ay);
-            const double ps = a.phi1[hb + o] + shift;
-            const double d = jac_diag(ps, P.tau / dt, P.c1);
+            const double p1 = a.phi1[hb + o];
+            const double d = jac_diag(fix_phi_star(p1, shift, all), P.tau / dt, P.c1);
             Rphi[pb + o] = -sr[p];
             rhs[pb + o] = rh;
             D[pb + o] = d;
             if (SECOND) {
-                a.keep_phi[pb + o] = tf.apply(a.d1[pb + o], ps);
+                a.keep_phi[pb + o] = tf.apply(a.d1[pb + o], p1);
                 a.keep_mu[pb + o] = a.m1[pb + o];
             } else {
                 a.w_out[pb + o] = w_new(o, a.w_in[pb + o]);
@@ -2966,6 +3005,7 @@ struct TanLevelArgs {
     long rec_stride;
     const double *mpart;                // k_tan_mass's partials of the field to fix
     double LxLy;
+    FixCheck chk;                       // the step that led to this level
 };
 __global__ __launch_bounds__(NTH) void k_tan_level(Geom G, TanLevelArgs a, double *__restrict__ part /* this level's [B][nblk][8] */,
                                                    long part_stride) {
@@ -2980,6 +3020,7 @@ __global__ __launch_bounds__(NTH) void k_tan_level(Geom G, TanLevelArgs a, doubl
         __syncthreads();
     }
     const TanFix tf(s_fix, rec, a.LxLy);
+    a.chk.look(tf, s_fix, b, blk);
     double acc[TAN_NSUM] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int k = 0; k < TY / 4; ++k) {
         int r = r0 + ly0 + 4 * k, c = c0 + lx;
@@ -2989,8 +3030,8 @@ __global__ __launch_bounds__(NTH) void k_tan_level(Geom G, TanLevelArgs a, doubl
             const double e = ph - (a.pq ? a.pq[hb + o] : 0.0);
             const double uu = a.u ? a.u[hb + o] : 0.0, hh = a.h ? a.h[hb + o] : 0.0;
             double d1 = a.d1 ? a.d1[pb + o] : 0.0, d2 = a.d2 ? a.d2[pb + o] : 0.0;
-            if (a.fix == 1) d1 = tf.apply(d1, ph + shift);
-            else if (a.fix == 2) d2 = tf.apply(d2, ph + shift);
+            if (a.fix == 1) d1 = tf.apply(d1, ph);
+            else if (a.fix == 2) d2 = tf.apply(d2, ph);
             acc[0] += w * (e * d1);
             acc[1] += w * (d1 * d1);
             acc[2] += w * (e * d2);
@@ -3076,11 +3117,12 @@ struct HvRhsArgs {
     const double *wts;              // the mass fix's weights (one plane)
     const double *xp1;              // SECOND: xp of the first sweep's solve of this step (y^p = -(2/dt) xp) ...
     const double *v;                // ... and level k of the history of raw tangent solves
+    FixCheck chk;                   // step k
 };
 
 // Right-hand side of a transposed solve in the form k_solve_setup / k_tan_rhs leave: A = -(dt/2) lam^v on the tile and its
 // one-node halo (a pointwise function of the mirrored node), R_phi := -A, rhs := lam^mu - L A, D and the partials
-// {-, sum rhs^2, min D, max D} for k_fin_lin_begin (mode 2).  D and rho are taken at phi* = phi_{k+1} + s_k.
+// {-, sum rhs^2, min D, max D} for k_fin_lin_begin (mode 2).  D and rho are taken at phi* (fix_phi_star).
 template <int SECOND>
 __global__ __launch_bounds__(NTH) void k_hv_rhs(Geom G, Phys P, HvRhsArgs a, double dt, double *__restrict__ Rphi,
                                                 double *__restrict__ rhs, double *__restrict__ D, double *__restrict__ part) {
@@ -3097,6 +3139,7 @@ __global__ __launch_bounds__(NTH) void k_hv_rhs(Geom G, Phys P, HvRhsArgs a, dou
         __syncthreads();
     }
     const TanFix tf(s_fix, rec, P.LxLy);
+    a.chk.look(tf, s_fix, b, blk);
     const double ys = -2.0 / dt;
     for (int e = threadIdx.x; e < W * (TY + 2); e += NTH) {
         const int ly = e / W, lxx = e - ly * W;
@@ -3104,7 +3147,7 @@ __global__ __launch_bounds__(NTH) void k_hv_rhs(Geom G, Phys P, HvRhsArgs a, dou
         const long o = (long)gr * G.pitch + gc;
         double v = a.lphi[pb + o];
         if (tf.mean != 0.0) v -= (a.wts[o] / wdev(gr, gc, G)) * tf.mean;
-        if (SECOND) v -= P.c1 * tan_rho(a.phi1[hb + o] + shift) * (ys * a.xp1[pb + o]) * a.v[hb + o];
+        if (SECOND) v -= P.c1 * tan_rho(fix_phi_star(a.phi1[hb + o], shift, tf.all)) * (ys * a.xp1[pb + o]) * a.v[hb + o];
         sr[e] = -(0.5 * dt) * v;
     }
     __syncthreads();
@@ -3115,7 +3158,7 @@ __global__ __launch_bounds__(NTH) void k_hv_rhs(Geom G, Phys P, HvRhsArgs a, dou
             const int p = (ly + 1) * W + lx + 1;
             const long o = (long)r * G.pitch + c;
             const double rh = a.lmu[pb + o] - lap_at<W>(sr, p, G.ax, G.ay);
-            const double d = jac_diag(a.phi1[hb + o] + shift, P.tau / dt, P.c1);
+            const double d = jac_diag(fix_phi_star(a.phi1[hb + o], shift, tf.all), P.tau / dt, P.c1);
             Rphi[pb + o] = -sr[p];
             rhs[pb + o] = rh;
             D[pb + o] = d;
@@ -3140,10 +3183,10 @@ struct HvEmitArgs {
     double wt;                      // trapezoid weight in t of the new level
     const double *opt_tab;          // b1, b2 of every trajectory
     const double *Wc, *wts;         // the cost's and the mass fix's weights (one plane each)
-    const double *phi_fix;          // the new level of the state history: phi* of the step below it is phi_fix + its shift
+    const double *phi_fix;          // the new level of the state history: the step below it shifted the nodes fix_in_set names
     const double *rec;              // that step's cell of the shift record, NULL = no shifts (or no step below)
     long rec_stride;
-    double *part;                   // [B][nblk][NPART] partials {sum_int wq lam^phi, sum_int wts} for that step's k_hv_rhs
+    double *part;                   // [B][nblk][NPART] partials {sum_int wq lam^phi, sum_int wts (the classified weight)} for that step's k_hv_rhs
     double dt, kp, half_kappa, alpha, beta;
 };
 
@@ -3164,8 +3207,7 @@ __global__ __launch_bounds__(NTH) void k_hv_emit(Geom G, HvEmitArgs a) {
     __syncthreads();
     const double *rec = a.rec ? a.rec + b * a.rec_stride : (const double *)nullptr;
     const double shift = rec ? rec[0] : 0.0;
-    const bool all = rec && rec[1] == 0.0;
-    const double thr = (1.0 - DELTA_SEP) - 5e-3;
+    const bool all = fix_all(rec);
     const double b1 = a.opt_tab[b * OPT_STRIDE + OPT_B1], b2 = a.opt_tab[b * OPT_STRIDE + OPT_B2];
     const double ys = -2.0 / a.dt;
     double acc[2] = {0.0, 0.0};
@@ -3197,7 +3239,7 @@ __global__ __launch_bounds__(NTH) void k_hv_emit(Geom G, HvEmitArgs a) {
             a.lphi[pb + o] = nphi;
             a.lmu[pb + o] = nmu;
             a.lw[pb + o] = nw;
-            if (shift != 0.0 && (all || fabs(a.phi_fix[hb + o] + shift) < thr)) {
+            if (shift != 0.0 && fix_in_set(a.phi_fix[hb + o], shift, all)) {
                 acc[0] += wq * nphi;
                 acc[1] += a.wts[o];
             }
@@ -3233,7 +3275,8 @@ __global__ __launch_bounds__(NTH) void k_hv_init(Geom G, int rows, const double 
 __global__ __launch_bounds__(NTH) void k_hv_keep(Geom G, const double *__restrict__ x, const double *__restrict__ m,
                                                  const double *__restrict__ phi1, long hist_stride,
                                                  const double *__restrict__ rec_, long rec_stride,
-                                                 const double *__restrict__ mpart, double LxLy, double *__restrict__ v_k,
+                                                 const double *__restrict__ mpart, double LxLy, FixCheck chk,
+                                                 double *__restrict__ v_k,
                                                  double *__restrict__ dp_k1, double *__restrict__ dphi,
                                                  double *__restrict__ dmu) {
     TILE_COORDS;
@@ -3246,12 +3289,13 @@ __global__ __launch_bounds__(NTH) void k_hv_keep(Geom G, const double *__restric
         __syncthreads();
     }
     const TanFix tf(s_fix, rec, LxLy);
+    chk.look(tf, s_fix, b, blk);
     for (int k = 0; k < TY / 4; ++k) {
         int r = r0 + ly0 + 4 * k, c = c0 + lx;
         if (r < G.ns && c < G.nf) {
             const long o = (long)r * G.pitch + c;
             const double v = x[pb + o];
-            const double f = tf.apply(v, phi1[hb + o] + shift);
+            const double f = tf.apply(v, phi1[hb + o]);
             v_k[hb + o] = v;
             dp_k1[hb + o] = f;
             dphi[pb + o] = f;

@@ -18,6 +18,7 @@ import numpy as np
 from scipy.sparse.linalg import splu
 
 from oracle import vch2d_oracle as o
+from _tangent_ref import fix_sets
 
 
 def trapz_w(x):
@@ -31,11 +32,12 @@ def trapz_w(x):
 
 
 def adjoint_reference(P, phi_hist, t_hist, shifts, u, phi_Q, phi_T, x, y, b1, b2, b3, h=None, g_rows=None,
-                      rho_source=True, fix_transpose=True, cache=None):
+                      rho_source=True, fix_transpose=True, cache=None, masks=None, pstar_all=False):
     """(G, Hh): G (g_rows, Nx+1, Ny+1) and, with a direction h (h_rows, Nx+1, Ny+1), Hh shaped like h (else None).
     u: the control of the march (rows beyond its last count as zero; None = zero control).  The two switches leave a term
     of the scheme out, for the tests that show the term is needed.  cache: a dict that keeps the factorisations between calls
-    about one base point (a dense Hessian is one call per unit direction)."""
+    about one base point (a dense Hessian is one call per unit direction).  masks, pstar_all: the nodes the march's mass fix
+    shifted and phi* on the others (_tangent_ref.fix_sets)."""
     Nx, Ny = int(P.Nx), int(P.Ny)
     hx, hy = P.Lx / Nx, P.Ly / Ny
     shape = phi_hist.shape[1:]
@@ -57,8 +59,9 @@ def adjoint_reference(P, phi_hist, t_hist, shifts, u, phi_Q, phi_T, x, y, b1, b2
         r = min(g_rows, u.shape[0])
         G[:r] = b3 * wt[:r, None] * Wc * u[:r].reshape(r, n)
 
-    pstar = [phi[k + 1] + shifts[k] for k in range(M)]
-    interior = [np.abs(p) < 1.0 - o.DELTA_SEP - 5e-3 for p in pstar]
+    sets = fix_sets(phi_hist, shifts, masks, pstar_all)
+    pstar = [p.reshape(n) for p, _ in sets]
+    interior = [I.reshape(n) for _, I in sets]
     dts = [float(t_hist[k + 1] - t_hist[k]) for k in range(M)]
 
     cache = {} if cache is None else cache

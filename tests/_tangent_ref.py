@@ -3,17 +3,21 @@ Newton matrix and a sparse direct solve.  Shared by test_tangent_cpu.py (which p
 oracle's nonlinear march) and test_gpu_second_order.py (which compares the engine with it).
 
 With dphi_0 = dmu_0 = dw_0 = 0 and d2phi_0 = d2mu_0 = 0, per step n (dt = t_{n+1} - t_n), with s_n the shift the march's
-mass fix subtracted at the end of step n and phi* = phi_{n+1} + s_n the Newton solution before it, J = jac_matrix(phi*):
+mass fix subtracted at the end of step n ON THE NODES OF ITS SET I_n ONLY (the interior nodes |phi_c| < 1 - delta_sep - 5e-3 of
+the clipped Newton solution phi_c; every node in the all-node form), phi* = phi_{n+1} + (s_n on I_n, 0 elsewhere) the Newton
+solution before it, J = jac_matrix(phi*):
     dw'  = w_filter(dw, dt, gamma, h_n, h_{n+1})                       rows (n, n+1) while n < len(h) - 1, zeros afterwards
     J [dphi*; dmu']   = [tau dphi/dt + kappa/2 L dphi + 2 c2 dphi + dmu/2 + (dw' + dw)/2 ;  dphi/dt + L dmu / 2]
     J [d2phi*; d2mu'] = [tau d2phi/dt + kappa/2 L d2phi + 2 c2 d2phi + d2mu/2 - c1 rho(phi*) dphi*^2 ;  d2phi/dt + L d2mu / 2]
     rho(p) = 4 p / (1 - p^2)^2
     dphi' = dphi* - sum(wts dphi*) / W_int,   d2phi' = d2phi* - sum(wts d2phi*) / W_int       (where s_n != 0)
-wts = hx hy outer(trapz_x, trapz_y) are the mass fix's own weights and W_int their sum over the interior nodes
-(|phi*| < 1 - delta_sep - 5e-3), on which alone the mean is subtracted; dmu' and dw' are carried as they are, like the march
-carries mu (F2:579).  The mass fix is NOT the identity: the linearised step conserves the mass of dphi only in the weights
+wts = hx hy outer(trapz_x, trapz_y) are the mass fix's own weights and W_int their sum over I_n, on which alone the mean
+is subtracted; dmu' and dw' are carried as they are, like the march carries mu (F2:579).  I_n is the march's own (`masks`,
+from o.forward's stats): it is NOT recoverable from phi_{n+1} and s_n -- a skipped node within |s_n| of the threshold looks
+like an interior one that was shifted outward -- so the re-derivation |phi_{n+1} + s_n| < 1 - delta_sep - 5e-3 (masks=None)
+is right only where no skipped node lies that close.  The mass fix is NOT the identity: the linearised step conserves the mass of dphi only in the weights
 of the Laplacian (its Kronecker-order quirk, oracle.lap), which are the fix's weights only for Nx == Ny.  The clip is taken
-as the identity and so is the interior set (callers assert max|phi| < 1 - delta_sep - 5e-3 - |s|)."""
+as the identity (callers assert max|phi_c| < 1 - delta_sep) and the set I_n as locally constant in u."""
 import numpy as np
 from scipy.sparse.linalg import splu
 
@@ -29,9 +33,42 @@ def march_with_shifts(P, **kw):
     return phi, xy, t, np.array(st.get("mass_shifts", []), dtype=float)
 
 
-def tangent_reference(P, phi_hist, t_hist, h, shifts=None):
+THR = 1.0 - o.DELTA_SEP - 5e-3
+
+
+def march_with_fix(P, **kw):
+    """o.forward plus everything its mass fix did: (phi_hist, (x, y), t_hist, shifts, fix) with fix = dict(masks=the M boolean
+    planes the shift was subtracted on, w_int=the M weights it divided by, interior=the M flags "interior form",
+    phi_c=the M clipped Newton solutions the sets were read from, newton_its=per-step residual counts)."""
+    st = {}
+    phi, xy, t = o.forward(P, stats=st, **kw)
+    fix = dict(masks=np.array(st["mass_masks"]), w_int=np.array(st["mass_w_int"]),
+               interior=np.array(st["mass_shift_interior"]), phi_c=np.array(st["phi_clipped"]),
+               newton_its=np.array([c[0] for c in st["step_counts"]]))
+    return phi, xy, t, np.array(st["mass_shifts"], dtype=float), fix
+
+
+def fix_sets(phi_hist, shifts, masks=None, pstar_all=False):
+    """Per step (phi*, I_n).  masks None: I_n re-derived as |phi_{n+1} + s_n| < THR (every node where that leaves none: the
+    all-node form), which is what can be known from the history and the shifts alone.  pstar_all: phi* = phi_{n+1} + s_n at
+    every node (the scheme as it was; for the tests that show the difference)."""
+    out = []
+    for k, s in enumerate(shifts):
+        p1 = phi_hist[k + 1]
+        if masks is None:
+            I = np.abs(p1 + s) < THR
+            if not I.any():
+                I = np.ones(p1.shape, dtype=bool)
+        else:
+            I = np.asarray(masks[k], dtype=bool)
+        out.append((p1 + s if pstar_all else p1 + np.where(I, s, 0.0), I))
+    return out
+
+
+def tangent_reference(P, phi_hist, t_hist, h, shifts=None, masks=None, pstar_all=False):
     """(dphi_hist, d2phi_hist), both shaped like phi_hist, for the direction h (rows, Nx+1, Ny+1).  `shifts` (M,): what the
-    march's mass fix subtracted at the end of each step (None or zeros: the fix taken as the identity)."""
+    march's mass fix subtracted at the end of each step (None or zeros: the fix taken as the identity); `masks`, `pstar_all`:
+    fix_sets."""
     Nx, Ny = int(P.Nx), int(P.Ny)
     hx, hy = P.Lx / Nx, P.Ly / Ny
     L = o.lap_matrix(Nx, Ny, hx, hy)
@@ -40,6 +77,7 @@ def tangent_reference(P, phi_hist, t_hist, h, shifts=None):
     shifts = np.zeros(M) if shifts is None else np.asarray(shifts, dtype=float)
     assert shifts.shape == (M,)
     wts = hx * hy * np.outer(o.trapz_weights(Nx + 1), o.trapz_weights(Ny + 1))
+    sets = fix_sets(phi_hist, shifts, masks, pstar_all)
     d1 = np.zeros_like(phi_hist)
     d2 = np.zeros_like(phi_hist)
     z = np.zeros(phi_hist.shape[1:])
@@ -62,14 +100,13 @@ def tangent_reference(P, phi_hist, t_hist, h, shifts=None):
         dt = float(t_hist[k + 1] - t_hist[k])
         hn, hp = (h[k], h[k + 1]) if k < h.shape[0] - 1 else (z, z)
         dw_new = o.w_filter(dw, dt, P.gamma, hn, hp)
-        p = phi_hist[k + 1] + shifts[k]
+        p, interior = sets[k]
         J = splu(o.jac_matrix(p, dt, P, L).tocsc())         # one factorisation serves both solves of the step
         rp, rm = rhs(dphi, dmu, dt)
         nphi, nmu = solve(J, rp + 0.5 * (dw_new + dw), rm)
         rp, rm = rhs(ephi, emu, dt)
         ephi, emu = solve(J, rp - P.c1 * (4.0 * p / (1.0 - p * p) ** 2) * nphi ** 2, rm)
         if shifts[k] != 0.0:
-            interior = np.abs(p) < 1.0 - o.DELTA_SEP - 5e-3
             nphi, ephi = unmean(nphi, interior), unmean(ephi, interior)
         dphi, dmu, dw = nphi, nmu, dw_new
         d1[k + 1], d2[k + 1] = dphi, ephi

@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 from oracle import vch2d_oracle as o
+import _fix_band as fb
 from _tangent_ref import march_with_shifts, tangent_reference, tangent_scalars
 
 N, T, DT, EPS = 16, 0.2, 0.02, 1e-2
@@ -157,3 +158,147 @@ def test_direction_row_rule_and_linearity(march):
     assert np.abs(s1[4] - c1[4]).max() > 1e-3 * np.abs(s1[4]).max()
     z1, z2 = tangent_reference(P, phi, t, np.zeros_like(h))
     assert not z1.any() and not z2.any()
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# States OUTSIDE the interior band of the mass fix (tests/_fix_band.py): plateaus in [0.985, 0.99), fronts inside the band.
+# The fix shifts the interior nodes only, so phi* = phi_{n+1} + s_n there and phi_{n+1} elsewhere, and the linearised fix
+# subtracts its mean on the march's own set.
+#
+# Measured against central differences at EPS = 1e-2 (relative max-norm: dphi, d2phi, curvature, slope; smooth / noise):
+#     32x16    2.7e-7 1.5e-5 1.0e-7 9.5e-8  /  1.2e-7 4.0e-5 2.9e-7 1.1e-8
+#     128x32   1.3e-9 1.3e-5 2.1e-8 4.5e-11 /  7.9e-10 9.6e-5 1.8e-7 1.5e-10
+#     50x36    3.6e-8 3.4e-5 4.2e-8 5.6e-8  /  6.8e-8 4.0e-5 9.6e-8 1.8e-9
+#     12x9     3.7e-8 1.9e-5 2.7e-7 2.1e-9  /  1.3e-7 9.5e-5 1.8e-6 7.3e-8
+#     ambiguous, with the march's own sets   2.2e-7 1.6e-5 7.6e-9 1.1e-8  /  2.4e-7 7.3e-5 8.7e-8 4.4e-8
+# under the file's own bounds 1e-5, 3e-4, 1e-5, 1e-5 (d2phi needs no higher floor here).  The scheme as it was
+# (phi* = phi_{n+1} + s_n at every node, sets re-derived from it) misses dphi by 5.2e-3 / 6.1e-3 on 12x9 and by
+# 4.5e-3 / 7.2e-3 on the ambiguous input; with phi* corrected and the sets still re-derived the ambiguous input misses by
+# 3.0e-3 / 5.8e-3.
+# ------------------------------------------------------------------------------------------------------------------------
+
+
+def _band_errors(m, h, **kw):
+    d1, d2 = tangent_reference(m["P"], m["phi"], m["t"], h, m["shifts"], **kw)
+    O = m["O"]
+    S = tangent_scalars(m["phi"], d1, d2, m["u"], h, m["phi_Q"], m["phi_T"], m["x"], m["y"], m["t"], O.b1, O.b2, O.b3)
+    assert EPS == fb.EPS
+    (p0, c0), ((pp, cp), (pm, cm)) = m["base"], fb.central(m, next(k for k, v in m["dirs"].items() if v is h))
+    return (np.abs((pp - pm) / (2 * EPS) - d1).max() / np.abs(d1).max(),
+            np.abs((pp - 2 * p0 + pm) / EPS ** 2 - d2).max() / np.abs(d2).max(),
+            abs((cp - 2 * c0 + cm) / EPS ** 2 / S["curvature"] - 1.0),
+            abs((cp - cm) / (2 * EPS) / S["slope"] - 1.0))
+
+
+@pytest.mark.parametrize("name", fb.QUALIFIED)
+def test_band_inputs_meet_their_premises(name):
+    """Every premise of tests/_fix_band.py, measured on the oracle's march; the sets are the same at u +- EPS h, so the
+    central differences below differentiate one smooth branch of the march."""
+    m = fb.build(name)
+    q = fb.qualify(m)
+    print(name, q, "shifts", m["shifts"])
+    assert q["converged"] and q["interior_form"]
+    assert q["max_phi_c"] < 1.0 - o.DELTA_SEP - fb.CLIP_MARGIN
+    assert q["frac_in"] >= 0.1 and q["frac_out"] >= 0.1
+    assert q["min_shift"] > 1e-6
+    assert not any(q["ambiguous"]) and not any(q["near"]) and all(q["rederived_ok"])
+    assert fb.is_qualified(q)
+    for h in m["dirs"].values():
+        for sg in (1.0, -1.0):
+            masks = fb.march_with_fix(m["P"], control=m["u"] + sg * EPS * h, phi0=m["phi0"])[4]["masks"]
+            assert np.array_equal(masks, m["masks"])
+
+
+def test_band_diagonals_exceed_the_right_scaling_threshold():
+    """The engine's CG-form solves run right-scaled where Dmax > 4 Dmin (cg_scale_ratio).  On the FFT band inputs the Newton
+    diagonal tau / dt + 2 c1 / (1 - phi*^2) spans 6.2 (128x32) and 7.5 (32x16): 5 + 30 on the plateaus against 5 + 0.8 on the
+    fronts; no state of init_phi_random(amp=0.1) comes near (1.01)."""
+    for name in ("32x16", "128x32"):
+        r = fb.diag_ratio(fb.build(name))
+        print(f"{name}: Dmax / Dmin {r:.2f}")
+        assert r > 4.0
+    P = fb.params("32x16")
+    flat = o.jac_diag(o.init_phi_random(P.Nx, P.Ny, o.DELTA_SEP, amp=0.1, seed=43), fb.DT, P)
+    assert flat.max() / flat.min() < 1.1
+
+
+def test_the_ambiguous_input_is_ambiguous():
+    """The issue's own recipe: converged, clip inactive, the fix at work -- and skipped nodes that the re-derivation
+    |phi_{n+1} + s_n| < THR takes for interior ones (it can only ADD nodes: it is a superset of the march's set)."""
+    m = fb.build(fb.AMBIGUOUS)
+    q = fb.qualify(m)
+    print(q)
+    assert q["converged"] and q["interior_form"] and q["max_phi_c"] < 1.0 - o.DELTA_SEP - fb.CLIP_MARGIN
+    assert q["frac_in"] >= 0.1 and q["frac_out"] >= 0.1 and q["min_shift"] > 1e-6
+    assert not all(q["rederived_ok"]) and not fb.is_qualified(q)
+    for k, s in enumerate(m["shifts"]):
+        red = np.abs(m["phi"][k + 1] + s) < fb.THR
+        assert not np.any(m["masks"][k] & ~red)
+
+
+@pytest.mark.parametrize("dirname", ["smooth", "noise"])
+@pytest.mark.parametrize("name", fb.QUALIFIED + [fb.AMBIGUOUS])
+def test_tangent_reference_outside_the_interior_band(name, dirname):
+    m = fb.build(name)
+    h = m["dirs"][dirname]
+    e1, e2, ec, es = _band_errors(m, h, masks=m["masks"])
+    print(f"{name} {dirname}: dphi {e1:.2e} d2phi {e2:.2e} curvature {ec:.2e} slope {es:.2e}")
+    assert e1 < 1e-5
+    assert e2 < 3e-4
+    assert ec < 1e-5
+    assert es < 1e-5
+    if name != fb.AMBIGUOUS:        # qualified: what the history and the shifts alone tell is the march's own set
+        a1, a2 = tangent_reference(m["P"], m["phi"], m["t"], h, m["shifts"])
+        b1, b2 = tangent_reference(m["P"], m["phi"], m["t"], h, m["shifts"], masks=m["masks"])
+        assert np.array_equal(a1, b1) and np.array_equal(a2, b2)
+
+
+@pytest.mark.parametrize("dirname", ["smooth", "noise"])
+def test_phi_star_shifted_on_every_node_is_not_the_derivative(dirname):
+    """phi* = phi_{n+1} + s_n at every node -- the scheme as it was -- with the march's own sets misses dphi by more than
+    1e-3 on the ambiguous input and on 12x9, where D = 2 c1 / (1 - phi^2) is at its steepest on the skipped plateaus."""
+    for name in (fb.AMBIGUOUS, "12x9"):
+        m = fb.build(name)
+        e1 = _band_errors(m, m["dirs"][dirname], masks=m["masks"], pstar_all=True)[0]
+        g1 = _band_errors(m, m["dirs"][dirname], masks=m["masks"])[0]
+        print(f"{name} {dirname}: dphi with phi* shifted everywhere {e1:.2e}, corrected {g1:.2e}")
+        assert e1 > 1e-3
+        assert g1 < 1e-5
+
+
+@pytest.mark.parametrize("dirname", ["smooth", "noise"])
+def test_sets_rederived_from_the_history_are_not_the_marchs_on_the_ambiguous_input(dirname):
+    """phi* corrected, but the sets re-derived as |phi_{n+1} + s_n| < THR: misses dphi by more than 1e-3."""
+    m = fb.build(fb.AMBIGUOUS)
+    e1 = _band_errors(m, m["dirs"][dirname])[0]
+    g1 = _band_errors(m, m["dirs"][dirname], masks=m["masks"])[0]
+    print(f"{dirname}: dphi with re-derived sets {e1:.2e}, with the march's {g1:.2e}")
+    assert e1 > 1e-3
+    assert g1 < 1e-5
+
+
+@pytest.mark.parametrize("dirname", ["smooth", "noise"])
+def test_tangent_reference_in_the_all_node_form_of_the_fix(dirname):
+    """fb.FALLBACK: no node inside the band at any step, the clip inactive before and after the shift, and the march takes
+    err / (Lx Ly) ~ 1e-6 off every node.  phi* = phi_{n+1} + s_n at every node and the plain weighted mean is removed.
+    Measured: dphi 3.1e-6 / 3.2e-6, d2phi 1.6e-4 / 1.4e-4, curvature 2.3e-7 / 4.6e-7, slope 1.3e-7 / 9.0e-10."""
+    m = fb.build(fb.FALLBACK)
+    fix = m["fix"]
+    hi = 1.0 - o.DELTA_SEP - fb.CLIP_MARGIN
+    assert not fix["interior"].any() and fix["masks"].all()
+    assert np.all(fix["newton_its"] < o.NEWTON_MAXIT)
+    assert fb.THR + 1e-4 < np.abs(fix["phi_c"]).min() and np.abs(fix["phi_c"]).max() < hi
+    assert fb.THR + 1e-4 < np.abs(m["phi"][1:]).min() and np.abs(m["phi"][1:]).max() < hi
+    assert np.abs(m["shifts"]).min() > 1e-6
+    assert np.allclose(fix["w_int"], m["P"].Lx * m["P"].Ly, rtol=0, atol=0)
+    h = m["dirs"][dirname]
+    e1, e2, ec, es = _band_errors(m, h, masks=m["masks"])
+    print(f"fallback {dirname}: dphi {e1:.2e} d2phi {e2:.2e} curvature {ec:.2e} slope {es:.2e}")
+    assert e1 < 1e-5
+    assert e2 < 3e-4
+    assert ec < 1e-5
+    assert es < 1e-5
+    # what the history and the shifts alone tell (no node passes |phi_{n+1} + s_n| < THR: every node) is the same scheme
+    a1, a2 = tangent_reference(m["P"], m["phi"], m["t"], h, m["shifts"])
+    b1, b2 = tangent_reference(m["P"], m["phi"], m["t"], h, m["shifts"], masks=m["masks"])
+    assert np.array_equal(a1, b1) and np.array_equal(a2, b2)
