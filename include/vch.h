@@ -342,6 +342,48 @@ int vch2d_hessvec(vch2d_ctx *ctx, const double *h /* NULL allowed iff order 1 */
                   double *hv_out   /* [B][h_rows][Nx+1][Ny+1], required iff order 2 */,
                   double *dots_out /* [B][2] or NULL */,
                   vch_stats *stats);
+/* Lanczos on the reduced Hessian P H P of J1 + J2 + J3 about the resident control and state history, with the basis, the free
+ * set and the three-term recurrence in device memory (ABI version stays 3: detect both entry points by
+ * symbol).  H q comes from the transposed sweeps of vch2d_hessvec; P masks to the free set.  Only the tridiagonal
+ * coefficients cross to the host: T = tridiag(beta, alpha, beta) of a trajectory has the Ritz values of P H P.
+ *   Base point, dt, M, t_hist, x, y, phi_Q, phi_T, opts / n_opts, rtol: the rules of vch2d_hessvec, in both of its modes.  The
+ *   direction has M + 1 rows, so after a vch2d_forward with a control that control must have at least M + 1 rows
+ *   (VCH_ERR_ARG otherwise).  Beyond b1, b2, b3 the call reads u_min, u_max of opts[b].
+ *   mask     [B][M+1][Nx+1][Ny+1] bytes, non-zero = free; NULL: built on the device from the resident control with
+ *            trajectory b's own box, u > u_min + tol && u < u_max - tol && |u| > tol (tol <= 0: 1e-8)
+ *   q0       [B][M+1][Nx+1][Ny+1] start vector; q_0 = P q0 / ||P q0||
+ *   k        steps at most; trajectory b stops after min(k, n_free_b) steps, when beta_j <= 1e-14 max_i |alpha_i| (an
+ *            invariant subspace) or when beta_j is not finite; a stopped trajectory's vectors are left alone, the others go on
+ *   reorth   1: classical Gram-Schmidt, twice, against all of q_0 .. q_j (k + 1 resident vectors); 0: the same two rounds
+ *            against q_{j-1}, q_j only (three resident vectors)
+ *   alpha_out, beta_out [B][k]: alpha_j = the sum of the two rounds' coefficients on q_j, beta_j = ||w|| after both rounds;
+ *            entries beyond steps_out[b] are NaN.  n_free_out[b]: the size of the free set, counted on the device.
+ * The gradient sweep's multipliers are computed once, before step 0 (M solves per trajectory), and kept in one further
+ * history; every step then runs the tangent march of q_j and the second transposed sweep only: 2 M solves per trajectory
+ * and step instead of vch2d_hessvec's 3 M, with the bits of vch2d_hessvec's hv (VCH_KRYLOV_NOCACHE=1 repeats the gradient
+ * sweep in every step: A/B and tests).  The host looks once for the size of the free set, once for ||P q0|| and once per
+ * step (B betas and stop cells), beside the looks of the solves.
+ * Errors: VCH_ERR_ARG for k < 1, NULL q0 or outputs, reorth outside 0 / 1 and the row rule, VCH_ERR_STATE as for
+ * vch2d_hessvec -- all before anything is enqueued, copied or allocated.  Two errors depend on the data and come later, both
+ * VCH_ERR_ARG naming the trajectory: an empty free set (after the mask launch, its sum and one look; nothing else has run),
+ * and a start vector that vanishes on the free set.  Device storage, allocated on first use as one group: the basis (k + 1
+ * or 3 histories), one history for the cached sweep, the mask (one byte per node of a history) and the partials; a refused
+ * request releases what the call got and returns VCH_ERR_NOMEM with the context usable and unchanged and a message that
+ * states the bytes the group needs (at 512^2 x 1000 steps x 8 trajectories a history is 16.8 GB: use reorth = 0 there).
+ * Stateless like vch2d_hessvec (the direction goes through the trial-control scratch); no atomics: up to 32 trajectories, a
+ * trajectory's alpha, beta and steps are bitwise those of a single-trajectory context, whatever its batch mates do.
+ * stats: linear solves B M (2 s + 1) for a batch whose members all take s steps. */
+int vch2d_hess_lanczos(vch2d_ctx *ctx, const double *dt, int M, const double *t_hist, const double *x, const double *y,
+                       const double *phi_Q, const double *phi_T, const vch_opt_params *opts, int n_opts, double rtol,
+                       const uint8_t *mask /* [B][M+1][Nx+1][Ny+1] or NULL */, double tol,
+                       const double *q0 /* [B][M+1][Nx+1][Ny+1] */, int k, int reorth /* 0 | 1 */,
+                       double *alpha_out /* [B][k] */, double *beta_out /* [B][k] */,
+                       int32_t *steps_out /* [B] */, int64_t *n_free_out /* [B] */, vch_stats *stats);
+/* out[b] = sum_{j<m} coef[b][j] q_j from the basis the last vch2d_hess_lanczos of this context left resident: the Ritz vector
+ * of a Ritz value (coef = an eigenvector of T), or one basis vector (a unit coef).  Masked-off nodes are exact zeros.
+ * VCH_ERR_STATE without a resident basis, and after a reorth = 0 run when m exceeds the vectors still held; VCH_ERR_ARG for
+ * m < 1 or m above the smallest step count of the batch plus one. */
+int vch2d_krylov_vector(vch2d_ctx *ctx, const double *coef /* [B][m] */, int m, double *out /* [B][M+1][Nx+1][Ny+1] */);
 /* Per-trajectory cost scalars {J1,J2,J3,J4,J} of the current iterate on the DEVICE
  * (5*B doubles), for the caller's RCCL all-reduce; returns a device pointer via *ptr_dev. */
 int vch2d_pgd_cost_dev(vch2d_ctx *ctx, double **ptr_dev);

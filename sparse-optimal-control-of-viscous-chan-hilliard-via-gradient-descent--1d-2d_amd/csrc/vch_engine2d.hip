@@ -228,6 +228,17 @@ struct vch2d_ctx {
     // block {partials [2][B][nblk][NPART], time weights [Mmax+1], dots [B][2]}
     double *hv_G = nullptr, *hv_H = nullptr, *hv_V = nullptr, *hv_DP = nullptr, *hv_part = nullptr, *hv_wt = nullptr,
            *hv_dots = nullptr;
+    // vch2d_hess_lanczos (lazy, one group): the basis [kr_slots][B][Mmax+1][plane], the gradient sweep's xp of every step
+    // [Mmax][B][plane] (level-major: k_hv_rhs<1> reads one step's planes with the trajectory stride of a work plane), the
+    // free set as bytes [B][Mmax+1][plane] and one block of partials and scalars (KrLayout); what the last run left
+    // for vch2d_krylov_vector
+    double *kr_Q = nullptr, *kr_X = nullptr, *kr_sc = nullptr;
+    unsigned char *kr_mask = nullptr;
+    int kr_slots = 0, kr_kcap = 0;        // capacity: basis slots, entries of alpha / beta per trajectory
+    int kr_lchunk;                        // VCH_KR_LCHUNK: levels per workgroup of the Krylov kernels
+    bool kr_nocache;                      // VCH_KRYLOV_NOCACHE=1 (A/B and tests): every step repeats the gradient sweep
+    bool kr_valid = false;                // a basis is resident
+    int kr_levels, kr_run_slots, kr_window, kr_min_steps;   // its rows, ring size, addressable vectors, smallest step count
     bool res_pgd = false;                 // the resident state history is the resident PGD problem's iterate
     vch_pgd_state pgd;                    // the line search's books and the error metrics of the driver loop (vch_pgd.h)
     std::vector<double> J_host;           // [B][5] cost terms of the accepted iterate, the source of J_dev and the ring
@@ -260,7 +271,7 @@ struct vch2d_ctx {
 enum { PC_SCHUR_P = 0, PC_GEMM = 1, PC_RESIDUAL = 2, PC_ADJ_Q = 3, PC_CG_UPDATE = 4, PC_ADJ_RHS = 5, PC_COST = 6,
        PC_PROX = 7, PC_DCT_R0 = 8, PC_DCT_C = 9, PC_DCT_R3 = 10, PC_SCHUR_P1 = 11, PC_CG_ROWS = 12, PC_CG_ROWS1 = 13,
        PC_NOOP = 14, PC_GUESS = 15, PC_ADJ_GUESS = 16, PC_CHEB_ROWS = 17, PC_CHEB_ROWS0 = 18, PC_RESIDUAL0 = 19,
-       PC_NCLS = 20 };
+       PC_KRYLOV = 20 /* the streaming passes of vch2d_hess_lanczos, all in one class */, PC_NCLS = 21 };
 
 // an empty kernel: what an event pair measures around it is the cost of the pair itself (vch2d_prof_begin)
 __global__ void k_noop() {}
@@ -479,6 +490,9 @@ static void read_knobs(vch2d_ctx *c) {
     c->guess2_on = env_on("VCH_GUESS2");
     c->guess_max = 6;          // beyond, the weights (sum |c_j| = 2^order - 1) amplify what the inexact solves left in the increments
     if (const char *e = getenv("VCH_GUESS_MAX")) c->guess_max = std::max(1, std::min(GUESS_ORD, atoi(e)));
+    c->kr_lchunk = 16;         // 512^2, one trajectory of 1001 levels: 297 tiles x 63 chunks of workgroups
+    if (const char *e = getenv("VCH_KR_LCHUNK")) c->kr_lchunk = std::max(1, atoi(e));
+    c->kr_nocache = getenv("VCH_KRYLOV_NOCACHE") && atoi(getenv("VCH_KRYLOV_NOCACHE")) != 0;
 }
 
 // The buffers every context has (histories and the buffers of single calls come lazily).  zero(): doubles, cleared on the
@@ -2586,56 +2600,81 @@ extern "C" int vch2d_second_order(vch2d_ctx *c, const double *h, int h_rows, con
 // exact gradient field and Hessian-vector product: the transposed sweep of the tangent march (kernels: "Transposed
 // (adjoint) sweep" in vch_kernels2d.h)
 // ------------------------------------------------------------------------------------
-static int hessvec_core(vch2d_ctx *c, const double *h, int h_rows, int g_rows, const double *dt, int M, const double *t_hist,
-                        const double *pq, const double *pt, const vch_opt_params *opts, int n_opts, int order,
-                        double *grad_out, double *hv_out, double *dots_out, vch_stats *stats) {
-    const Geom &G = c->G;
-    const int B = c->B, levels = M + 1;
-    const long hs = hist_stride(c);
-    std::vector<double> wt = trapz_w(t_hist, levels);            // lives until the final synchronisation below
-    wt.resize((size_t)c->Mmax + 1, 0.0);                         // a direction's rows beyond the march carry no weight
-    if (h) VCHCHK(h2d_hist(c, c->u_trial, h, h_rows));           // the direction lives in the trial-control scratch
+// What the pieces of a transposed-sweep call share (vch2d_hessvec runs them in one order, vch2d_hess_lanczos in another).
+struct HvRun {
+    const double *dt;
+    int M;
+    const double *pq, *pt;
+    int g_rows, h_rows;
+    std::vector<double> wt;            // trapezoid weights in t; lives until the call's final synchronisation
+};
+// Tables, counters, refusal cells, the start of the timed span.
+static int hv_begin(vch2d_ctx *c, HvRun &r, const double *t_hist, const vch_opt_params *opts, int n_opts) {
+    r.wt = trapz_w(t_hist, r.M + 1);
+    r.wt.resize((size_t)c->Mmax + 1, 0.0);                       // a direction's rows beyond the march carry no weight
     VCHCHK(write_opt_tab(c, c->seam_tab, opts, n_opts));
-    HIPCHK(hipMemcpyAsync(c->hv_wt, wt.data(), sizeof(double) * wt.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->hv_wt, r.wt.data(), sizeof(double) * r.wt.size(), hipMemcpyHostToDevice, c->stream));
     VCHCHK(reset_counters(c));
     VCHCHK(fix_check_begin(c));
     HIPCHK(hipEventRecord(c->ev0, c->stream));
     c->guess_wr = -1;          // the back substitution keeps no increment for a march's starting guesses
     c->cheb_enq = -1;
-    const int u_rows = c->res_pgd ? levels : std::min(c->fwd_u_rows, levels);
-    const long rec_stride = (long)c->Mmax * SHIFT_REC;
-    const long pstride = (long)B * c->nblk * NPART;
-    auto rec_of = [&](int n) { return c->shift_res ? (const double *)c->shift_hist + (long)n * SHIFT_REC : (const double *)nullptr; };
-    auto level_of = [&](const double *hist, int lvl) { return hist ? hist + (long)lvl * G.plane : (const double *)nullptr; };
-    LAUNCH(k_hv_init, c->grid, dim3(NTH), G, g_rows, u_rows > 0 ? (const double *)c->u_hist : (const double *)nullptr, u_rows,
-           (const double *)c->hv_wt, (const double *)c->seam_tab, (const double *)c->W_cost, hs, c->hv_G);
-    if (order == 2) {
-        LAUNCH(k_hv_init, c->grid, dim3(NTH), G, h_rows, (const double *)c->u_trial, h_rows, (const double *)c->hv_wt,
-               (const double *)c->seam_tab, (const double *)c->W_cost, hs, c->hv_H);
-        // the order-1 tangent of h, keeping every step's raw solve (v_k) and the field after the mean removal (dphi')
-        double *dphi = c->tmp[0], *dmu = c->tmp[1], *dw[2] = {c->tmp[4], c->tmp[5]};
-        for (int k : {0, 1, 4, 5}) HIPCHK(hipMemsetAsync(c->tmp[k], 0, sizeof(double) * B * G.plane, c->stream));
-        for (int n = 0; n < M; ++n) {
-            const double *phi1 = c->phi_hist + (long)(n + 1) * G.plane;
-            const bool live = n < h_rows - 1;           // F2:545-548
-            TanRhsArgs a1{dphi, dmu, dw[n & 1], dw[(n + 1) & 1], live ? c->u_trial + (long)n * G.plane : (const double *)nullptr,
-                          live ? c->u_trial + (long)(n + 1) * G.plane : (const double *)nullptr, phi1, hs, nullptr, nullptr,
-                          nullptr, nullptr, rec_of(n), rec_stride, nullptr};
-            LAUNCH((k_tan_rhs<0>), c->grid, dim3(NTH), G, c->P, a1, dt[n], c->Rphi_s, c->rhs_s, c->D_s, c->part);
-            VCHCHK(tangent_solve(c, dt[n], phi1, rec_of(n)));
-            LAUNCH(k_hv_keep, c->grid, dim3(NTH), G, (const double *)c->xf, (const double *)c->dmu, phi1, hs, rec_of(n), rec_stride,
-                   (const double *)c->part_mass, c->P.LxLy, fix_check_of(c, n), c->hv_V + (long)n * G.plane, c->hv_DP + (long)(n + 1) * G.plane, dphi,
-                   dmu);
-        }
+    return 0;
+}
+static const double *hv_rec_of(const vch2d_ctx *c, int n) {
+    return c->shift_res ? (const double *)c->shift_hist + (long)n * SHIFT_REC : (const double *)nullptr;
+}
+// The start of the gradient field.
+static int hv_grad_init(vch2d_ctx *c, const HvRun &r) {
+    const int u_rows = c->res_pgd ? r.M + 1 : std::min(c->fwd_u_rows, r.M + 1);
+    LAUNCH(k_hv_init, c->grid, dim3(NTH), c->G, r.g_rows, u_rows > 0 ? (const double *)c->u_hist : (const double *)nullptr, u_rows,
+           (const double *)c->hv_wt, (const double *)c->seam_tab, (const double *)c->W_cost, hist_stride(c), c->hv_G);
+    return 0;
+}
+// The start of H h and the order-1 tangent of the direction in the trial-control scratch, keeping every step's raw solve
+// (v_k) and the field after the mean removal (dphi').
+static int hv_tangent(vch2d_ctx *c, const HvRun &r) {
+    const Geom &G = c->G;
+    const int B = c->B, M = r.M, h_rows = r.h_rows;
+    const long hs = hist_stride(c), rec_stride = (long)c->Mmax * SHIFT_REC;
+    const double *dt = r.dt;
+    auto rec_of = [&](int n) { return hv_rec_of(c, n); };
+    LAUNCH(k_hv_init, c->grid, dim3(NTH), G, h_rows, (const double *)c->u_trial, h_rows, (const double *)c->hv_wt,
+           (const double *)c->seam_tab, (const double *)c->W_cost, hs, c->hv_H);
+    double *dphi = c->tmp[0], *dmu = c->tmp[1], *dw[2] = {c->tmp[4], c->tmp[5]};
+    for (int k : {0, 1, 4, 5}) HIPCHK(hipMemsetAsync(c->tmp[k], 0, sizeof(double) * B * G.plane, c->stream));
+    for (int n = 0; n < M; ++n) {
+        const double *phi1 = c->phi_hist + (long)(n + 1) * G.plane;
+        const bool live = n < h_rows - 1;           // F2:545-548
+        TanRhsArgs a1{dphi, dmu, dw[n & 1], dw[(n + 1) & 1], live ? c->u_trial + (long)n * G.plane : (const double *)nullptr,
+                      live ? c->u_trial + (long)(n + 1) * G.plane : (const double *)nullptr, phi1, hs, nullptr, nullptr,
+                      nullptr, nullptr, rec_of(n), rec_stride, nullptr};
+        LAUNCH((k_tan_rhs<0>), c->grid, dim3(NTH), G, c->P, a1, dt[n], c->Rphi_s, c->rhs_s, c->D_s, c->part);
+        VCHCHK(tangent_solve(c, dt[n], phi1, rec_of(n)));
+        LAUNCH(k_hv_keep, c->grid, dim3(NTH), G, (const double *)c->xf, (const double *)c->dmu, phi1, hs, rec_of(n), rec_stride,
+               (const double *)c->part_mass, c->P.LxLy, fix_check_of(c, n), c->hv_V + (long)n * G.plane, c->hv_DP + (long)(n + 1) * G.plane, dphi,
+               dmu);
     }
-    // the two sweeps in lockstep: multipliers of the gradient in tmp[0..2], of H h in tmp[3..5]; partials of the
-    // transposed fix in the two halves of hv_part
-    const int nsweep = order == 2 ? 2 : 1;
+    return 0;
+}
+// The sweeps sw0 .. sw1 (0: the gradient, 1: H h) in lockstep: multipliers of the gradient in tmp[0..2], of H h in
+// tmp[3..5]; partials of the transposed fix in the two halves of hv_part.  The second sweep needs the first one's xp of
+// every step (y^p = -(2/dt) xp): beside the first it reads the solver's output plane; alone it reads xp_cached, the planes
+// [M][B][plane] an earlier first sweep left through xp_keep.  The solves are deterministic, so either way gives the same bits.
+static int hv_sweeps(vch2d_ctx *c, const HvRun &r, int sw0, int sw1, double *xp_keep, const double *xp_cached) {
+    const Geom &G = c->G;
+    const int B = c->B, M = r.M;
+    const long hs = hist_stride(c), rec_stride = (long)c->Mmax * SHIFT_REC;
+    const long pstride = (long)B * c->nblk * NPART;
+    const double *dt = r.dt, *pq = r.pq, *pt = r.pt;
+    const std::vector<double> &wt = r.wt;
+    auto rec_of = [&](int n) { return hv_rec_of(c, n); };
+    auto level_of = [&](const double *hist, int lvl) { return hist ? hist + (long)lvl * G.plane : (const double *)nullptr; };
     auto emit = [&](int sw, int k /* the step just solved, M = the start */) -> int {
         const int lvl = k;                                       // the level whose multipliers this launch leaves
         const bool start = k == M;
         const double dtk = start ? 1.0 : dt[k], gdt = c->P.gamma / dtk;
-        const int rows = sw == 0 ? g_rows : h_rows;
+        const int rows = sw == 0 ? r.g_rows : r.h_rows;
         double *out = sw == 0 ? c->hv_G : c->hv_H;
         const bool live = !start && k < rows - 1;                // F2:545-548
         const double *src_a = lvl == 0 ? nullptr : (sw == 0 ? level_of(c->phi_hist, lvl) : level_of(c->hv_DP, lvl));
@@ -2650,22 +2689,41 @@ static int hessvec_core(vch2d_ctx *c, const double *h, int h_rows, int g_rows, c
         LAUNCH(k_hv_emit, c->grid, dim3(NTH), G, a);
         return 0;
     };
-    for (int sw = 0; sw < nsweep; ++sw) VCHCHK(emit(sw, M));
+    for (int sw = sw0; sw <= sw1; ++sw) VCHCHK(emit(sw, M));
     for (int k = M - 1; k >= 0; --k) {
         const double *phi1 = c->phi_hist + (long)(k + 1) * G.plane;
-        for (int sw = 0; sw < nsweep; ++sw) {
-            // the second sweep's right-hand side reads y^p of the first from the solver's output plane before its own
-            // solve reuses it (the emit kernel in between leaves that plane alone)
+        for (int sw = sw0; sw <= sw1; ++sw) {
+            // beside the first sweep, the second's right-hand side reads y^p of the first from the solver's output plane
+            // before its own solve reuses it (the emit kernel in between leaves that plane alone)
+            const double *xp1 = xp_cached ? xp_cached + (long)k * B * G.plane : (const double *)c->xf;
             HvRhsArgs a{c->tmp[3 * sw], c->tmp[3 * sw + 1], phi1, hs, rec_of(k), rec_stride,
                         (const double *)(c->hv_part + sw * pstride), (const double *)c->wts_mass,
-                        sw ? (const double *)c->xf : nullptr, sw ? (const double *)(c->hv_V + (long)k * G.plane) : nullptr,
+                        sw ? xp1 : nullptr, sw ? (const double *)(c->hv_V + (long)k * G.plane) : nullptr,
                         fix_check_of(c, k)};
             if (sw == 0) LAUNCH((k_hv_rhs<0>), c->grid, dim3(NTH), G, c->P, a, dt[k], c->Rphi_s, c->rhs_s, c->D_s, c->part);
             else LAUNCH((k_hv_rhs<1>), c->grid, dim3(NTH), G, c->P, a, dt[k], c->Rphi_s, c->rhs_s, c->D_s, c->part);
             VCHCHK(tangent_solve(c, dt[k], phi1, nullptr));
+            if (sw == 0 && xp_keep)
+                HIPCHK(hipMemcpyAsync(xp_keep + (long)k * B * G.plane, c->xf, sizeof(double) * B * G.plane, hipMemcpyDeviceToDevice,
+                                      c->stream));
             VCHCHK(emit(sw, k));
         }
     }
+    return 0;
+}
+
+static int hessvec_core(vch2d_ctx *c, const double *h, int h_rows, int g_rows, const double *dt, int M, const double *t_hist,
+                        const double *pq, const double *pt, const vch_opt_params *opts, int n_opts, int order,
+                        double *grad_out, double *hv_out, double *dots_out, vch_stats *stats) {
+    const Geom &G = c->G;
+    const int B = c->B;
+    const long hs = hist_stride(c);
+    HvRun r{dt, M, pq, pt, g_rows, h_rows, {}};
+    if (h) VCHCHK(h2d_hist(c, c->u_trial, h, h_rows));           // the direction lives in the trial-control scratch
+    VCHCHK(hv_begin(c, r, t_hist, opts, n_opts));
+    VCHCHK(hv_grad_init(c, r));
+    if (order == 2) VCHCHK(hv_tangent(c, r));
+    VCHCHK(hv_sweeps(c, r, 0, order == 2 ? 1 : 0, nullptr, nullptr));
     if (dots_out) {
         if (h)
             LAUNCH(k_hv_dots, c->grid, dim3(NTH), G, (const double *)c->hv_G, g_rows, (const double *)c->u_trial, h_rows,
@@ -2684,6 +2742,19 @@ static int hessvec_core(vch2d_ctx *c, const double *h, int h_rows, int g_rows, c
     fill_stats(c, stats, ms);
     VCHCHK(reset_counters(c));      // the records as the end of a PGD iteration leaves them
     return fix_check_end("vch2d_hessvec", bad);
+}
+
+// The block of vch2d_hessvec beside its histories: {partials [2][B][nblk][NPART], time weights [Mmax+1], dots [B][2]}.
+static int ensure_hv_part(vch2d_ctx *c, const char *fn) {
+    if (c->hv_part) return 0;
+    const size_t n = (size_t)2 * c->B * c->nblk * NPART + (size_t)c->Mmax + 1 + 2 * (size_t)c->B;
+    if (c->pool.dev(&c->hv_part, n * 8)) {
+        (void)hipGetLastError();
+        return vch_fail(VCH_ERR_NOMEM, "%s: hipMalloc of the partials failed", fn);
+    }
+    c->hv_wt = c->hv_part + (size_t)2 * c->B * c->nblk * NPART;
+    c->hv_dots = c->hv_wt + c->Mmax + 1;
+    return 0;
 }
 
 extern "C" int vch2d_hessvec(vch2d_ctx *c, const double *h, int h_rows, int g_rows, const double *dt, int M,
@@ -2713,15 +2784,7 @@ extern "C" int vch2d_hessvec(vch2d_ctx *c, const double *h, int h_rows, int g_ro
     }
     if (!pgd && phi_Q) VCHCHK(ensure_hist(c, &c->phiQ));
     VCHCHK(ensure_fix_bad(c));
-    if (!c->hv_part) {
-        const size_t n = (size_t)2 * c->B * c->nblk * NPART + (size_t)c->Mmax + 1 + 2 * (size_t)c->B;
-        if (c->pool.dev(&c->hv_part, n * 8)) {
-            (void)hipGetLastError();
-            return vch_fail(VCH_ERR_NOMEM, "vch2d_hessvec: hipMalloc of the partials failed");
-        }
-        c->hv_wt = c->hv_part + (size_t)2 * c->B * c->nblk * NPART;
-        c->hv_dots = c->hv_wt + c->Mmax + 1;
-    }
+    VCHCHK(ensure_hv_part(c, __func__));
     const double *pq = nullptr, *pt = nullptr;
     VCHCHK(tan_targets(c, pgd, x, y, phi_Q, phi_T, M, &pq, &pt));
     // the solves stop at rtol (relative residual); the context's own tolerance comes back on every path out
@@ -2730,6 +2793,251 @@ extern "C" int vch2d_hessvec(vch2d_ctx *c, const double *h, int h_rows, int g_ro
     const int rc = hessvec_core(c, h, h_rows, g_rows, dt, M, t_hist, pq, pt, opts, n_opts, order, grad_out, hv_out, dots_out, stats);
     c->lin_tol = keep_tol;
     return rc;
+}
+
+// ------------------------------------------------------------------------------------
+// Lanczos on the reduced Hessian P H P with the basis, the free set and the recurrence on the device (kernels: "Device-
+// resident Lanczos" in vch_kernels2d.h)
+// ------------------------------------------------------------------------------------
+// The block of partials and scalars behind kr_sc, in doubles; S = basis slots (the stride of a partial and of a
+// coefficient row), K = entries of alpha / beta per trajectory.
+struct KrLayout {
+    size_t part, coef1, coef2, ucoef, alpha, beta, look, scal, amax, nfree, lim, stop, total;
+};
+static KrLayout kr_layout(const vch2d_ctx *c, int S, int K) {
+    const size_t B = c->B, nch = ((size_t)c->Mmax + c->kr_lchunk) / c->kr_lchunk;
+    KrLayout L;
+    size_t at = 0;
+    auto take = [&](size_t n) { const size_t o = at; at += n; return o; };
+    L.part = take(B * nch * c->nblk * S);
+    L.coef1 = take(B * S);
+    L.coef2 = take(B * S);
+    L.ucoef = take(B * S);
+    L.alpha = take(B * K);
+    L.beta = take(B * K);
+    L.look = take(2 * B);
+    L.scal = take(B);
+    L.amax = take(B);
+    L.nfree = take(B);
+    L.lim = take(B);
+    L.stop = take(B);
+    L.total = at;
+    return L;
+}
+static KrCells kr_cells(const vch2d_ctx *c, const KrLayout &L) {
+    double *p = c->kr_sc;
+    return KrCells{p + L.coef1, p + L.coef2, p + L.alpha, p + L.beta, p + L.look, p + L.scal, p + L.amax,
+                   (long long *)(p + L.nfree), (long long *)(p + L.lim), (long long *)(p + L.stop)};
+}
+// a look of the Krylov iteration: n doubles behind everything enqueued so far
+static int kr_look(vch2d_ctx *c, void *host, const void *dev, size_t bytes) {
+    c->n_sync++;
+    HIPCHK(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int vch2d_hess_lanczos(vch2d_ctx *c, const double *dt, int M, const double *t_hist, const double *x, const double *y,
+                                  const double *phi_Q, const double *phi_T, const vch_opt_params *opts, int n_opts, double rtol,
+                                  const uint8_t *mask, double tol, const double *q0, int k, int reorth, double *alpha_out,
+                                  double *beta_out, int32_t *steps_out, int64_t *n_free_out, vch_stats *stats) {
+    CTXCHK(c);
+    // everything below is checked before anything is enqueued, copied or allocated
+    VCHCHK(tan_check_state(c, __func__));
+    ARGCHK(opts, "NULL opts");
+    ARGCHK(q0, "NULL q0");
+    ARGCHK(alpha_out && beta_out && steps_out && n_free_out, "NULL alpha_out, beta_out, steps_out or n_free_out");
+    ARGCHK(k >= 1, "k must be >= 1");
+    ARGCHK(reorth == 0 || reorth == 1, "reorth must be 0 or 1");
+    bool pgd = false;
+    VCHCHK(tan_check_args(c, __func__, 1, &dt, M, &t_hist, x, y, phi_Q, phi_T, opts, n_opts, 2, &pgd));
+    if (!c->shift_res)
+        return vch_fail(VCH_ERR_STATE, "vch2d_hess_lanczos: the resident state history is not one a march of this context wrote");
+    // the direction has M + 1 rows: the g_rows the rule of vch2d_hessvec must allow
+    if (!c->res_pgd && c->fwd_u_rows > 0)
+        ARGCHK(c->fwd_u_rows >= M + 1, "the march's control has fewer than M + 1 rows");
+    const Geom &G = c->G;
+    const int B = c->B, levels = M + 1, slots = reorth ? k + 1 : 3;
+    const long hs = hist_stride(c);
+    const size_t hist_bytes = (size_t)B * (c->Mmax + 1) * G.plane * 8;
+    // lazy storage, one group: a refused request gives back what this call got and leaves the context as it was
+    c->kr_valid = false;
+    if (c->kr_Q && (slots > c->kr_slots || k > c->kr_kcap)) {       // a larger basis than the resident storage holds
+        c->pool.drop((void **)&c->kr_sc);
+        c->pool.drop((void **)&c->kr_mask);
+        c->pool.drop((void **)&c->kr_X);
+        c->pool.drop((void **)&c->kr_Q);
+        c->kr_slots = c->kr_kcap = 0;
+    }
+    {
+        vch_group g(c->pool);
+        VCHCHK(ensure_hist(c, &c->u_trial));
+        VCHCHK(ensure_hist(c, &c->hv_G));
+        VCHCHK(ensure_hist(c, &c->hv_H));
+        VCHCHK(ensure_hist(c, &c->hv_V));
+        VCHCHK(ensure_hist(c, &c->hv_DP));
+        if (!pgd && phi_Q) VCHCHK(ensure_hist(c, &c->phiQ));
+        VCHCHK(ensure_fix_bad(c));
+        VCHCHK(ensure_hv_part(c, __func__));
+        if (!c->kr_Q) {
+            const KrLayout L = kr_layout(c, slots, k);
+            const size_t need = (size_t)slots * hist_bytes + hist_bytes + hist_bytes / 8 + L.total * 8;
+            const bool ok = c->pool.dev(&c->kr_Q, (size_t)slots * hist_bytes) == 0 && c->pool.dev(&c->kr_X, hist_bytes) == 0 &&
+                            c->pool.dev(&c->kr_mask, hist_bytes / 8) == 0 && c->pool.dev(&c->kr_sc, L.total * 8) == 0;
+            if (!ok) {
+                (void)hipGetLastError();
+                return vch_fail(VCH_ERR_NOMEM,
+                                "vch2d_hess_lanczos: the Krylov storage needs %zu bytes (%d basis vectors of %zu bytes, one more "
+                                "history for the cached sweep, %zu bytes of mask, %zu of partials) and was refused",
+                                need, slots, hist_bytes, hist_bytes / 8, L.total * 8);
+            }
+            c->kr_slots = slots;
+            c->kr_kcap = k;
+        }
+        g.keep();
+    }
+    const KrLayout L = kr_layout(c, c->kr_slots, c->kr_kcap);
+    const KrCells cells = kr_cells(c, L);
+    double *part = c->kr_sc + L.part;
+    const int S = c->kr_slots, nch = (levels + c->kr_lchunk - 1) / c->kr_lchunk;
+    const long nsum = (long)nch * c->nblk;
+    const dim3 kgrid(c->nblk, nch, B);
+    auto kr_args = [&](int first, int nv) {
+        return KrArgs{c->kr_Q, (long)B * hs, hs, levels, c->kr_lchunk, first, nv, slots, S, c->kr_mask, cells.stop};
+    };
+    auto slot_of = [&](int i) { return c->kr_Q + (long)(i % slots) * B * hs; };
+    // the free set and its size: one mask launch, its sum and one look
+    VCHCHK(write_opt_tab(c, c->seam_tab, opts, n_opts));
+    if (mask)
+        for (int b = 0; b < B; ++b)
+            HIPCHK(hipMemcpy2DAsync(c->kr_mask + (size_t)b * hs, (size_t)G.pitch, mask + (size_t)b * levels * G.ns * G.nf, (size_t)G.nf,
+                                    (size_t)G.nf, (size_t)G.ns * levels, hipMemcpyHostToDevice, c->stream));
+    const int u_rows = c->res_pgd ? levels : std::min(c->fwd_u_rows, levels);
+    LAUNCHC(PC_KRYLOV, k_kr_mask, kgrid, dim3(NTH), G, kr_args(0, 0), u_rows > 0 ? (const double *)c->u_hist : (const double *)nullptr, u_rows,
+           (const double *)c->seam_tab, tol > 0 ? tol : 1e-8, mask ? 0 : 1, c->kr_mask, part);
+    LAUNCHC(PC_KRYLOV, k_kr_fin, dim3(B), dim3(NTH), cells, (const double *)part, nsum, S, 0, 0, 0, k);
+    std::vector<long long> nfree(B);
+    VCHCHK(kr_look(c, nfree.data(), cells.nfree, sizeof(long long) * B));
+    for (int b = 0; b < B; ++b)
+        if (nfree[b] < 1) return vch_fail(VCH_ERR_ARG, "vch2d_hess_lanczos: trajectory %d: the free set is empty", b);
+    const double *pq = nullptr, *pt = nullptr;
+    VCHCHK(tan_targets(c, pgd, x, y, phi_Q, phi_T, M, &pq, &pt));
+    // the solves stop at rtol (relative residual); the context's own tolerance comes back on every path out
+    const double keep_tol = c->lin_tol;
+    c->lin_tol = rtol > 0 ? rtol : 1e-12;
+    std::vector<int> bad(B, -1);
+    std::vector<double> look(2 * (size_t)B);
+    int hi = 0;                                     // the highest basis vector stored
+    auto run = [&]() -> int {
+        HvRun r{dt, M, pq, pt, levels, levels, {}};
+        VCHCHK(h2d_hist(c, c->u_trial, q0, levels));            // the direction lives in the trial-control scratch
+        VCHCHK(hv_begin(c, r, t_hist, opts, n_opts));
+        // q_0 = P q0 / ||P q0||
+        LAUNCHC(PC_KRYLOV, k_kr_start, kgrid, dim3(NTH), G, kr_args(0, 0), (const double *)c->u_trial, slot_of(0), part);
+        LAUNCHC(PC_KRYLOV, k_kr_fin, dim3(B), dim3(NTH), cells, (const double *)part, nsum, S, 1, 0, 0, k);
+        VCHCHK(kr_look(c, look.data(), cells.look, sizeof(double) * 2 * B));
+        for (int b = 0; b < B; ++b)
+            if (!(look[2 * b] > 0.0) || !std::isfinite(look[2 * b]))
+                return vch_fail(VCH_ERR_ARG, "vch2d_hess_lanczos: trajectory %d: the start vector vanishes on the free set (or is not finite)", b);
+        LAUNCHC(PC_KRYLOV, k_kr_next, kgrid, dim3(NTH), G, kr_args(0, 0), (const double *)slot_of(0), (const double *)cells.scal, slot_of(0),
+               c->u_trial);
+        HIPCHK(hipMemsetAsync(cells.alpha, 0xff, sizeof(double) * 2 * B * c->kr_kcap, c->stream));      // NaN: alpha, then beta
+        if (!c->kr_nocache) {           // the gradient sweep once per base point: its xp of every step stays in kr_X
+            VCHCHK(hv_grad_init(c, r));
+            VCHCHK(hv_sweeps(c, r, 0, 0, c->kr_X, nullptr));
+        }
+        std::vector<char> active(B, 1);
+        for (int b = 0; b < B; ++b) steps_out[b] = 0;
+        for (int j = 0; j < k; ++j) {
+            if (c->kr_nocache) {
+                VCHCHK(hv_grad_init(c, r));
+                VCHCHK(hv_tangent(c, r));
+                VCHCHK(hv_sweeps(c, r, 0, 1, nullptr, nullptr));
+            } else {
+                VCHCHK(hv_tangent(c, r));
+                VCHCHK(hv_sweeps(c, r, 1, 1, nullptr, c->kr_X));
+            }
+            // w = P H q_j in hv_H; classical Gram-Schmidt twice against q_first .. q_j
+            const int first = reorth ? 0 : std::max(j - 1, 0), nv = j + 1 - first;
+            const KrArgs a = kr_args(first % slots, nv);
+            LAUNCHC(PC_KRYLOV, (k_kr_pass<0>), kgrid, dim3(NTH), G, a, c->hv_H, (const double *)nullptr, part);
+            LAUNCHC(PC_KRYLOV, k_kr_fin, dim3(B), dim3(NTH), cells, (const double *)part, nsum, S, 2, nv, j, k);
+            LAUNCHC(PC_KRYLOV, (k_kr_pass<1>), kgrid, dim3(NTH), G, a, c->hv_H, (const double *)cells.coef1, part);
+            LAUNCHC(PC_KRYLOV, k_kr_fin, dim3(B), dim3(NTH), cells, (const double *)part, nsum, S, 3, nv, j, k);
+            LAUNCHC(PC_KRYLOV, (k_kr_pass<2>), kgrid, dim3(NTH), G, a, c->hv_H, (const double *)cells.coef2, part);
+            LAUNCHC(PC_KRYLOV, k_kr_fin, dim3(B), dim3(NTH), cells, (const double *)part, nsum, S, 4, nv, j, k);
+            LAUNCHC(PC_KRYLOV, k_kr_next, kgrid, dim3(NTH), G, a, (const double *)c->hv_H, (const double *)cells.scal, slot_of(j + 1), c->u_trial);
+            hi = j + 1;
+            // the one look of the step: beta_j and the stop cell of every trajectory
+            VCHCHK(kr_look(c, look.data(), cells.look, sizeof(double) * 2 * B));
+            bool any = false;
+            for (int b = 0; b < B; ++b) {
+                if (!active[b]) continue;
+                steps_out[b] = j + 1;
+                if (look[2 * b + 1] != 0.0) active[b] = 0;
+                else any = true;
+            }
+            if (!any) break;
+        }
+        HIPCHK(hipEventRecord(c->ev1, c->stream));
+        for (int b = 0; b < B; ++b) {
+            HIPCHK(hipMemcpyAsync(alpha_out + (size_t)b * k, cells.alpha + (size_t)b * k, sizeof(double) * k, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(beta_out + (size_t)b * k, cells.beta + (size_t)b * k, sizeof(double) * k, hipMemcpyDeviceToHost, c->stream));
+        }
+        HIPCHK(hipMemcpyAsync(bad.data(), c->fix_bad, sizeof(int) * B, hipMemcpyDeviceToHost, c->stream));
+        VCHCHK(sync_state(c));
+        return 0;
+    };
+    int rc = run();
+    c->lin_tol = keep_tol;
+    if (rc < 0) {
+        (void)reset_counters(c);    // the records as the end of a PGD iteration leaves them
+        return rc;
+    }
+    float ms = 0;
+    hipEventElapsedTime(&ms, c->ev0, c->ev1);
+    fill_stats(c, stats, ms);
+    if (stats) {                    // the launches and the look of the free set, made before the counters were reset
+        stats->launches += 2;
+        stats->host_syncs += 1;
+    }
+    VCHCHK(reset_counters(c));      // the records as the end of a PGD iteration leaves them
+    rc = fix_check_end("vch2d_hess_lanczos", bad);
+    if (rc < 0) return rc;
+    int smin = steps_out[0];
+    for (int b = 0; b < B; ++b) {
+        n_free_out[b] = nfree[b];
+        smin = std::min(smin, (int)steps_out[b]);
+    }
+    c->kr_valid = true;
+    c->kr_levels = levels;
+    c->kr_run_slots = slots;
+    c->kr_min_steps = smin;
+    c->kr_window = reorth ? INT32_MAX : (hi <= 2 ? 3 : 0);   // three resident vectors: q_0 is gone once q_3 is stored
+    return 0;
+}
+
+extern "C" int vch2d_krylov_vector(vch2d_ctx *c, const double *coef, int m, double *out) {
+    CTXCHK(c);
+    ARGCHK(coef && out, "NULL coef or out");
+    ARGCHK(m >= 1, "m must be >= 1");
+    if (!c->kr_valid || !c->kr_Q || !c->hv_H)
+        return vch_fail(VCH_ERR_STATE, "vch2d_krylov_vector: no resident basis (call vch2d_hess_lanczos first)");
+    if (m > c->kr_window)
+        return vch_fail(VCH_ERR_STATE, "vch2d_krylov_vector: m = %d exceeds the %d vectors a run without reorthogonalisation still holds",
+                        m, c->kr_window);
+    ARGCHK(m <= c->kr_min_steps + 1, "m exceeds the smallest step count of the batch plus one");
+    const int B = c->B, S = c->kr_slots, levels = c->kr_levels;
+    const long hs = hist_stride(c);
+    const KrLayout L = kr_layout(c, c->kr_slots, c->kr_kcap);
+    const KrCells cells = kr_cells(c, L);
+    double *ucoef = c->kr_sc + L.ucoef;
+    HIPCHK(hipMemcpy2DAsync(ucoef, sizeof(double) * S, coef, sizeof(double) * m, sizeof(double) * m, (size_t)B, hipMemcpyHostToDevice,
+                            c->stream));
+    const int nch = (levels + c->kr_lchunk - 1) / c->kr_lchunk;
+    const KrArgs a{c->kr_Q, (long)B * hs, hs, levels, c->kr_lchunk, 0, m, c->kr_run_slots, S, c->kr_mask, cells.stop};
+    LAUNCH(k_kr_lincomb, dim3(c->nblk, nch, B), dim3(NTH), c->G, a, (const double *)ucoef, c->hv_H);
+    return d2h_hist(c, out, c->hv_H, levels);
 }
 
 extern "C" int vch2d_mass_shifts(vch2d_ctx *c, double *out) {

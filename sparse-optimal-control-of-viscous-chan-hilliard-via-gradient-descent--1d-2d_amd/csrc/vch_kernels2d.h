@@ -3340,3 +3340,242 @@ __global__ void k_hv_dots_fin(const double *__restrict__ part, int nblk, int hav
         out[2 * b + 1] = (have_h && have_hv) ? s[1] : nan;
     }
 }
+
+// ---------------------------------------------------------------------------------
+// Device-resident Lanczos on the reduced Hessian P H P (vch2d_hess_lanczos): the streaming passes between two
+// transposed sweeps.  Every vector is a history [B][max_steps+1][plane]; the basis is a ring of `nslots` of them, vector i
+// of the `nv` a pass works against sits in slot (first + i) % nslots.  A workgroup owns one plane tile of one chunk of
+// levels of one trajectory: grid = (tiles, chunks, B), so that a single trajectory of 1000 levels still fills the device.
+// Partials are [B][chunks][tiles][pstride]; k_kr_fin sums them per trajectory in a fixed order.  No atomics.  A trajectory
+// whose iteration has stopped (stop[b] != 0) is skipped by every pass.
+// ---------------------------------------------------------------------------------
+constexpr int KR_GROUP = 8;           // basis vectors a pass holds accumulators for at a time
+struct KrArgs {
+    const double *Q;                  // the basis
+    long slot_stride, hist_stride;    // doubles between two slots / two trajectories
+    int levels, lchunk;               // rows of a vector (M + 1), levels per workgroup
+    int first, nv, nslots;
+    int pstride;                      // slots per workgroup partial
+    const unsigned char *mask;        // [B][max_steps+1][plane] bytes, non-zero = free
+    const long long *stop;            // [B]
+};
+#define KR_COORDS                                                                       \
+    const int b = blockIdx.z, blk = blockIdx.x;                                         \
+    const int c0 = (blk / G.tiles_s) * TX, r0 = (blk % G.tiles_s) * TY;                 \
+    const int c = c0 + (threadIdx.x & 63), ly0 = threadIdx.x >> 6;                      \
+    const int l0 = blockIdx.y * a.lchunk, l1 = min(l0 + a.lchunk, a.levels);            \
+    const long hb = (long)b * a.hist_stride;                                            \
+    double *const my_part = part ? part + (((long)b * gridDim.y + blockIdx.y) * gridDim.x + blk) * a.pstride : nullptr; \
+    (void)my_part
+// the nodes of the workgroup's tile and chunk that this thread owns: o = offset inside the trajectory's history
+#define KR_NODES(body)                                                                  \
+    for (int lvl = l0; lvl < l1; ++lvl)                                                 \
+        for (int k = 0; k < TY / 4; ++k) {                                              \
+            const int r = r0 + ly0 + 4 * k;                                             \
+            if (r < G.ns && c < G.nf) {                                                 \
+                const long o = hb + (long)lvl * G.plane + (long)r * G.pitch + c;        \
+                body                                                                    \
+            }                                                                           \
+        }
+__device__ __forceinline__ const double *kr_slot(const KrArgs &a, int i) {
+    return a.Q + (long)((a.first + i) % a.nslots) * a.slot_stride;
+}
+
+// The free set of a trajectory and its size.  build: from the resident control (rows beyond u_rows are zeros) and the
+// trajectory's own box, mask = u > u_min + tol && u < u_max - tol && |u| > tol, stored as bytes; otherwise the bytes are
+// the caller's.  Partial slot 0 = the count (exact in a double).
+__global__ __launch_bounds__(NTH) void k_kr_mask(Geom G, KrArgs a, const double *__restrict__ u, int u_rows,
+                                                 const double *__restrict__ opt_tab, double tol, int build,
+                                                 unsigned char *__restrict__ mask, double *__restrict__ part) {
+    KR_COORDS;
+    __shared__ double sred[NPART * 4];
+    const double lo = opt_tab[b * OPT_STRIDE + OPT_UMIN] + tol, hi = opt_tab[b * OPT_STRIDE + OPT_UMAX] - tol;
+    double acc[1] = {0.0};
+    KR_NODES(
+        bool m;
+        if (build) {
+            const double v = (u && lvl < u_rows) ? u[o] : 0.0;
+            m = v > lo && v < hi && fabs(v) > tol;
+            mask[o] = m ? 1 : 0;
+        } else {
+            m = mask[o] != 0;
+        }
+        acc[0] += m ? 1.0 : 0.0;
+    )
+    const int op[1] = {0};
+    block_reduce_store<1>(acc, op, sred, my_part);
+}
+
+// The start: dst = P src (dst and src may be the same history), partial slot 0 = sum (P src)^2.
+__global__ __launch_bounds__(NTH) void k_kr_start(Geom G, KrArgs a, const double *src, double *dst, double *__restrict__ part) {
+    KR_COORDS;
+    __shared__ double sred[NPART * 4];
+    double acc[1] = {0.0};
+    KR_NODES(
+        const double v = a.mask[o] ? src[o] : 0.0;
+        dst[o] = v;
+        acc[0] += v * v;
+    )
+    const int op[1] = {0};
+    block_reduce_store<1>(acc, op, sred, my_part);
+}
+
+// One pass of the Gram-Schmidt step over w (in place), 8 - 16 B per node and vector:
+//   MODE 0   partials i = sum q_i (P w)                                            (w is read through the mask, not written)
+//   MODE 1   w := P w - sum_i coef[b][i] q_i, then partials i = sum q_i w          (round 1's subtraction, round 2's products)
+//   MODE 2   w := w - sum_i coef[b][i] q_i, partial 0 = sum w^2                    (round 2's subtraction, the norm)
+// Masked-off nodes of every q_i are exact zeros, so w leaves MODE 1 with exact zeros there.  The products run over the
+// basis in groups of KR_GROUP accumulators; w is read again per group (the workgroup's own lines, just touched).
+template <int MODE>
+__global__ __launch_bounds__(NTH) void k_kr_pass(Geom G, KrArgs a, double *w, const double *__restrict__ coef,
+                                                 double *__restrict__ part) {
+    KR_COORDS;
+    if (a.stop[b]) return;                  // uniform over the workgroup
+    __shared__ double sred[KR_GROUP * 4];
+    if (MODE != 0) {
+        const double *cf = coef + (long)b * a.pstride;
+        double nrm[1] = {0.0};
+        KR_NODES(
+            double v = w[o];
+            if (MODE == 1) v = a.mask[o] ? v : 0.0;
+            for (int i = 0; i < a.nv; ++i) v -= cf[i] * kr_slot(a, i)[o];
+            w[o] = v;
+            nrm[0] += v * v;
+        )
+        if (MODE == 2) {
+            const int op[1] = {0};
+            block_reduce_store<1>(nrm, op, sred, my_part);
+            return;
+        }
+    }
+    for (int g0 = 0; g0 < a.nv; g0 += KR_GROUP) {
+        double acc[KR_GROUP];
+        const double *q[KR_GROUP];
+#pragma unroll
+        for (int i = 0; i < KR_GROUP; ++i) {
+            acc[i] = 0.0;
+            q[i] = kr_slot(a, min(g0 + i, a.nv - 1));       // past the end: the last vector again, its sum is not stored
+        }
+        KR_NODES(
+            double v = w[o];
+            if (MODE == 0) v = a.mask[o] ? v : 0.0;
+            _Pragma("unroll")
+            for (int i = 0; i < KR_GROUP; ++i) acc[i] += q[i][o] * v;
+        )
+        int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+        for (int i = 0; i < KR_GROUP; ++i) {
+            const double s = wave_sum(acc[i]);
+            if (lane == 0) sred[i * 4 + wv] = s;
+        }
+        __syncthreads();
+        if (threadIdx.x < KR_GROUP && g0 + (int)threadIdx.x < a.nv) {
+            const int i = threadIdx.x;
+            my_part[g0 + i] = (sred[i * 4] + sred[i * 4 + 1]) + (sred[i * 4 + 2] + sred[i * 4 + 3]);
+        }
+        __syncthreads();
+    }
+}
+
+// q_{j+1} = w / beta_j into its basis slot and into the direction buffer of the next sweep.  By the trajectory's stop cell:
+// 0 both stores; 1 (the last step, a valid q_{j+1}) the slot only; 2 (no valid q_{j+1}) zeros into the slot; 3 nothing.
+__global__ __launch_bounds__(NTH) void k_kr_next(Geom G, KrArgs a, const double *src, const double *__restrict__ scal,
+                                                 double *slot, double *__restrict__ dir) {
+    double *part = nullptr;
+    KR_COORDS;
+    const long long st = a.stop[b];
+    if (st == 3) return;
+    const double s = scal[b];
+    KR_NODES(
+        const double v = st == 2 ? 0.0 : src[o] / s;
+        slot[o] = v;
+        if (st == 0) dir[o] = v;
+    )
+}
+
+// out = sum_{i<nv} coef[b][i] q_i  (vch2d_krylov_vector)
+__global__ __launch_bounds__(NTH) void k_kr_lincomb(Geom G, KrArgs a, const double *__restrict__ coef, double *__restrict__ out) {
+    double *part = nullptr;
+    KR_COORDS;
+    const double *cf = coef + (long)b * a.pstride;
+    KR_NODES(
+        double v = 0.0;
+        for (int i = 0; i < a.nv; ++i) v += cf[i] * kr_slot(a, i)[o];
+        out[o] = v;
+    )
+}
+
+// The scalars of a pass, one workgroup of NTH threads per trajectory: the partials summed in a fixed order (thread t takes
+// elements t, t + NTH, ... in turn, then a tree over the threads).
+struct KrCells {
+    double *coef1, *coef2;            // [B][pstride] coefficients of the two Gram-Schmidt rounds
+    double *alpha, *beta;             // [B][k]
+    double *look;                     // [B][2] what the host reads per step: beta_j, the stop cell
+    double *scal;                     // [B] the divisor of the next k_kr_next
+    double *amax;                     // [B] max_i |alpha_i| so far
+    long long *nfree, *lim, *stop;    // [B] size of the free set, min(k, n_free), the stop cell
+};
+__device__ __forceinline__ double kr_sum(const double *__restrict__ part, long n, int pstride, int slot, double *sh) {
+    double s = 0.0;
+    for (long e = threadIdx.x; e < n; e += NTH) s += part[e * pstride + slot];
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    for (int h = NTH / 2; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) sh[threadIdx.x] += sh[threadIdx.x + h];
+        __syncthreads();
+    }
+    const double r = sh[0];
+    __syncthreads();
+    return r;
+}
+// mode 0: the count of k_kr_mask -> nfree, lim = min(k, nfree), the cells of a new iteration
+// mode 1: the start's norm -> scal, look[0]
+// mode 2 / 3: the nv products of round 1 / 2 -> coef1 / coef2
+// mode 4: step j's norm -> beta_j, alpha_j = coef1 + coef2 on q_j, the stop rules and the stop cell
+__global__ __launch_bounds__(NTH) void k_kr_fin(KrCells x, const double *__restrict__ part, long n, int pstride, int mode, int nv,
+                                                int j, int k) {
+    __shared__ double sh[NTH];
+    const int b = blockIdx.x;
+    const double *p = part + (long)b * n * pstride;
+    if (mode == 0) {
+        const double cnt = kr_sum(p, n, pstride, 0, sh);
+        if (threadIdx.x == 0) {
+            x.nfree[b] = (long long)cnt;
+            x.lim[b] = min((long long)k, (long long)cnt);
+            x.stop[b] = 0;
+            x.amax[b] = 0.0;
+        }
+        return;
+    }
+    if (mode == 1) {
+        const double s = sqrt(kr_sum(p, n, pstride, 0, sh));
+        if (threadIdx.x == 0) x.scal[b] = x.look[2 * b] = s;
+        return;
+    }
+    if (x.stop[b]) {                       // uniform: stopped at an earlier step
+        if (threadIdx.x == 0 && mode == 4) x.stop[b] = 3;
+        return;
+    }
+    if (mode == 2 || mode == 3) {
+        double *cf = (mode == 2 ? x.coef1 : x.coef2) + (long)b * pstride;
+        for (int i = 0; i < nv; ++i) {
+            const double s = kr_sum(p, n, pstride, i, sh);
+            if (threadIdx.x == 0) cf[i] = s;
+        }
+        return;
+    }
+    const double beta = sqrt(kr_sum(p, n, pstride, 0, sh));
+    if (threadIdx.x != 0) return;
+    const double alpha = x.coef1[(long)b * pstride + nv - 1] + x.coef2[(long)b * pstride + nv - 1];
+    const double am = fmax(x.amax[b], fabs(alpha));
+    x.amax[b] = am;
+    x.alpha[(long)b * k + j] = alpha;
+    x.beta[(long)b * k + j] = beta;
+    const bool broke = !isfinite(beta) || beta <= 1e-14 * am;          // an invariant subspace, or nothing to go on with
+    const bool last = j + 1 >= x.lim[b];
+    const long long st = broke || j + 1 >= x.nfree[b] ? 2 : (last ? 1 : 0);
+    x.stop[b] = st;
+    x.scal[b] = beta;
+    x.look[2 * b] = beta;
+    x.look[2 * b + 1] = (double)st;
+}

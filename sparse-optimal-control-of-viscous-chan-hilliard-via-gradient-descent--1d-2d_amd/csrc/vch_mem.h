@@ -66,6 +66,18 @@ public:
         }
     }
     void release() { rollback(0); }
+    // free the one block made into `owner` (any age) and NULL the owner; not inside a vch_group's scope, whose mark counts
+    // the blocks in front of it
+    void drop(void **owner) {
+        for (size_t i = 0; i < recs.size(); ++i)
+            if (recs[i].owner == owner) {
+                (recs[i].host ? fns->host_free : fns->dev_free)(*owner);
+                *owner = nullptr;
+                recs.erase(recs.begin() + (long)i);
+                --g_vch_mem_live;
+                return;
+            }
+    }
 };
 
 // What a scope allocates goes away with the scope unless keep() is reached: a lazy group whose second member was refused

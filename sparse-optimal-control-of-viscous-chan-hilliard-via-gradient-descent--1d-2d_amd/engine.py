@@ -430,6 +430,68 @@ class Engine2D:
         return self.hessvec(None, dt=dt, t_hist=t_hist, opt=opt, phi_Q=phi_Q, phi_T=phi_T, x=x, y=y, order=1, rtol=rtol,
                             g_rows=g_rows)["grad"]
 
+    def hess_lanczos(self, q0, k, dt=None, t_hist=None, opt=None, phi_Q=None, phi_T=None, x=None, y=None, mask=None, tol=0.0,
+                     reorth=True, rtol=0.0):
+        """Lanczos on the reduced Hessian P H P about the resident base point with the basis, the free set and the
+        recurrence on the device (vch2d_hess_lanczos); base point and arguments as for hessvec.  q0: (B, M+1, Nx+1, Ny+1)
+        start vector.  mask: the free set as (B, M+1, Nx+1, Ny+1) booleans / bytes, or None: built on the device from the
+        resident control and every trajectory's own u_min, u_max of `opt` with `tol` (<= 0: 1e-8).  reorth: full
+        reorthogonalisation (k + 1 resident vectors) or the three-term recurrence (3 resident vectors).
+        Returns dict(alpha, beta: (B, k), NaN beyond steps; steps, n_free: [B]; stats)."""
+        k = int(k)
+        if dt is None or t_hist is None:
+            if not hasattr(self, "_pgd_M"):
+                raise ValueError("dt and t_hist are required without a resident PGD problem")
+            dt = t_hist = None
+            M = self._pgd_M
+        else:
+            dt = np.ascontiguousarray(dt, dtype=np.float64)
+            t_hist = np.ascontiguousarray(t_hist, dtype=np.float64)
+            M = int(dt.size)
+            if t_hist.size != M + 1:
+                raise ValueError("t_hist must have len(dt) + 1 entries")
+            x = self.x if x is None else x
+            y = self.y if y is None else y
+        if x is not None or y is not None:
+            x = np.ascontiguousarray(self.x if x is None else x, dtype=np.float64)
+            y = np.ascontiguousarray(self.y if y is None else y, dtype=np.float64)
+            if x.shape != (self.Nx + 1,) or y.shape != (self.Ny + 1,):
+                raise ValueError("x, y must have Nx+1, Ny+1 entries")
+        q0 = None if q0 is None else self._hist(q0, M + 1, "q0")
+        if mask is not None:
+            mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+            if mask.ndim == 3 and self.B == 1:
+                mask = mask.reshape((1,) + mask.shape)
+            if mask.shape != (self.B, M + 1) + self.shape:
+                raise ValueError(f"mask must have shape ({self.B}, {M + 1}, {self.Nx + 1}, {self.Ny + 1}), got {mask.shape}")
+        pq = None if phi_Q is None else self._hist(phi_Q, M + 1, "phi_Q_target")
+        pt = None if phi_T is None else self._fld(phi_T, "phi_T_target")
+        seq = list(opt) if isinstance(opt, (list, tuple)) else [opt]
+        arr = (OptParams * len(seq))(*[o if isinstance(o, OptParams) else make_opt(o) for o in seq])
+        kk = max(k, 1)
+        alpha, beta = np.full((self.B, kk), np.nan), np.full((self.B, kk), np.nan)
+        steps, n_free = np.zeros(self.B, dtype=np.int32), np.zeros(self.B, dtype=np.int64)
+        st = Stats()
+        check(self.lib.vch2d_hess_lanczos(self.ctx, _dp(dt), M, _dp(t_hist), _dp(x), _dp(y), _dp(pq), _dp(pt), arr, len(seq),
+                                          float(rtol), None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                          float(tol), _dp(q0), k, int(reorth), _dp(alpha), _dp(beta),
+                                          steps.ctypes.data_as(_lib._I32), n_free.ctypes.data_as(C.POINTER(C.c_int64)),
+                                          C.byref(st)))
+        self._kr_rows = M + 1
+        return dict(alpha=alpha, beta=beta, steps=steps, n_free=n_free, stats=st.as_dict())
+
+    def krylov_vector(self, coef):
+        """(B, M+1, Nx+1, Ny+1): sum_j coef[b][j] q_j from the basis the last hess_lanczos left resident
+        (vch2d_krylov_vector).  coef: (B, m), or (m,) with batch 1."""
+        coef = np.ascontiguousarray(coef, dtype=np.float64)
+        if coef.ndim == 1 and self.B == 1:
+            coef = coef.reshape(1, -1)
+        if coef.ndim != 2 or coef.shape[0] != self.B:
+            raise ValueError(f"coef must have shape ({self.B}, m), got {coef.shape}")
+        out = self._out(rows=getattr(self, "_kr_rows", 1))
+        check(self.lib.vch2d_krylov_vector(self.ctx, _dp(coef), int(coef.shape[1]), _dp(out)))
+        return out
+
     def mass_shifts(self):
         """(B, M): what the march's interior mass fix subtracted at the end of every step of the resident state history
         (vch2d_mass_shifts; zeros where the fix was not applied); M = the steps of that history."""
