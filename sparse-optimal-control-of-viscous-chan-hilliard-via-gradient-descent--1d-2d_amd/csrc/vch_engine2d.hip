@@ -180,6 +180,10 @@ struct vch2d_ctx {
     // VCH_EVAL_HOIST (default 1; 0 = A/B and tests): k_eval with the step start's operands and the guess tail's planes requested
     // ahead of the barriers that use them (vch_kernels2d.h); 0 launches k_eval_plain, the same arithmetic without that
     bool eval_hoist;
+    // VCH_ROWS_BATCH (default 1; 0 = A/B and tests): k_dct_cols and k_cheb_rows with a phase's global operands requested
+    // together (vch_fft.h: column data, multiplier entries, the operands of the Chebyshev update); 0 launches
+    // k_dct_cols_plain and k_cheb_rows_plain, the same arithmetic one node at a time
+    bool rows_batch;
     unsigned long long *ceil_cell;        // [B][CeilCell::STRIDE] (vch_kernels2d.h)
     bool cell_now;                        // the level being enqueued uses the cells
     int trial_enq = -1;                   // sweeps of the reduction-free solve the NEXT trial launch arms the trial for (-1: none)
@@ -472,6 +476,7 @@ static void read_knobs(vch2d_ctx *c) {
     c->fin_publish = env_on("VCH_FIN_PUBLISH");
     c->ceil_cell_on = env_on("VCH_CEIL_CELL");
     c->eval_hoist = env_on("VCH_EVAL_HOIST");
+    c->rows_batch = env_on("VCH_ROWS_BATCH");
     c->cheb_margin = 1;
     if (const char *e = getenv("VCH_CHEB_MARGIN")) c->cheb_margin = std::max(0, atoi(e));
     c->cheb_max = 6;           // plans longer than this (a wide spectrum: CG's adaptivity pays) keep the CG form
@@ -720,7 +725,8 @@ static int dcth_rows(vch2d_ctx *c, const double *in, long in_slot_stride, double
 template <int C, int LOGL>
 static int dct_cols_plan(vch2d_ctx *c, const SpecArgs &sp, double scale, int gate) {
     const int cpw = 2 * (C >> c->sax.logL);
-    LAUNCHC(PC_DCT_C, (k_dct_cols<C, LOGL>), dim3((c->G.nf + cpw - 1) / cpw, 1, c->B), dim3(FftThreads<C, LOGL>::T), c->G,
+    auto k_cols = c->rows_batch ? k_dct_cols<C, LOGL> : k_dct_cols_plain<C, LOGL>;
+    LAUNCHC(PC_DCT_C, k_cols, dim3((c->G.nf + cpw - 1) / cpw, 1, c->B), dim3(FftThreads<C, LOGL>::T), c->G,
             c->sax, (const double *)c->t1, c->t2, scale, sp, c->st, gate);
     return 0;
 }
@@ -747,7 +753,8 @@ static int cg_rows(vch2d_ctx *c, const CgSweepArgs &a, bool first) {
 static int cheb_rows(vch2d_ctx *c, const ChebSweepArgs &a, bool first) {
     return with_plan(c->fax, [&](auto C, auto LG) {
         const RowsDims d = rows_dims<C, LG>(c);
-        auto k_rows = first ? k_cheb_rows<C, LG, 1> : k_cheb_rows<C, LG, 0>;
+        auto k_rows = c->rows_batch ? (first ? k_cheb_rows<C, LG, 1> : k_cheb_rows<C, LG, 0>)
+                                    : (first ? k_cheb_rows_plain<C, LG, 1> : k_cheb_rows_plain<C, LG, 0>);
         LAUNCHC(first ? PC_CHEB_ROWS0 : PC_CHEB_ROWS, k_rows, d.grid, d.block, c->G, c->fax, a, (const double *)c->t2, c->t1,
                 (const TrajState *)c->st);
         return 0;

@@ -102,10 +102,37 @@ struct FftThreads {
 // back into the image like those of every other pass.  Otherwise emit(index in the image, value) is called for each
 // output instead -- the kernels store the wanted half of the spectrum straight to global memory (Emit::TO_LDS = 0: no
 // barriers at all around the last pass) or write it back scaled (TO_LDS = 1: the spectral multiplier costs no pass).
+//
+// Two-phase emits (FETCH != 0, compile-time plans).  The indices the last pass hands to a thread are known from tid alone
+// (fft_last_out), so an emit can request its global operands for all of them at once: prefetch() only issues loads,
+// apply(slot, index, value) does the arithmetic and the stores, slot = the position of the output in the thread's
+// emission order.
+//   FETCH_EARLY  prefetch() at the top of the last pass: the operands arrive under its butterflies.  An emit with
+//                ACTIVE = 0 gets only this call (k_dct_cols requests its multiplier entries that way).
+//   FETCH_PARK   (TO_LDS emits) for kernels without the registers to hold operands across the butterflies: between the
+//                emit's two barriers the thread parks the last pass's outputs at their own places in the image (which it
+//                alone reads and rewrites there), requests its operands, and takes the outputs back one by one as it
+//                applies them.
+enum { FETCH_NONE = 0, FETCH_EARLY = 1, FETCH_PARK = 3 };
 struct FftNoEmit {
-    static constexpr int ACTIVE = 0, TO_LDS = 1;
+    static constexpr int ACTIVE = 0, TO_LDS = 1, FETCH = FETCH_NONE;
     __device__ __forceinline__ void operator()(int, double2) const {}
 };
+template <class Emit>
+__device__ __forceinline__ void emit_prefetch(Emit &emit, int when) {
+    if constexpr (Emit::FETCH != FETCH_NONE) {
+        if (Emit::FETCH == when) {
+            // parking exists for the registers: keep the scheduler from moving the requests up into the butterflies
+            if (when == FETCH_PARK) __builtin_amdgcn_sched_barrier(0);
+            emit.prefetch();
+        }
+    }
+}
+template <class Emit>
+__device__ __forceinline__ void emit_out(Emit &emit, int slot, int idx, double2 v) {
+    if constexpr (Emit::FETCH != FETCH_NONE) emit.apply(slot, idx, v);
+    else emit(idx, v);
+}
 
 // Ingest: where the FIRST pass takes its inputs from (same lengths).  Default: the image.  Otherwise ingest(index in the
 // image) supplies them -- the kernels read global memory directly, so the image is never staged (no fill loop, no barrier
@@ -124,10 +151,26 @@ template <int C, int LOGL>
 struct FftRegOk {
     static constexpr bool V = (LOGL == 9 || ((LOGL == 10 || LOGL == 11) && C == (1 << LOGL)));
 };
+// Image index of output `slot` (0..7, in emission order) of the last pass of a compile-time plan for this thread: the
+// 8x8x8 plan ends with a radix-8 pass with Ns = L/8 (outputs j + slot L/8), the others with a radix-4 pass with Ns = L/4 and
+// two butterflies idx = tid + i T per thread (slot = 4 i + r: outputs j + r L/4).  Of these the entries k <= L/2 that a
+// row kernel keeps are slots 0..3 (radix 8) or r = 0, 1 (radix 4) for every thread, and the entry L/2 itself (slot 4 or
+// r = 2) for the thread with j = 0.
+template <int C, int LOGL>
+__device__ __forceinline__ int fft_last_out(int slot) {
+    static_assert(LOGL >= 9 && LOGL <= 11, "compile-time plans only");
+    constexpr int T = C / 8, L = 1 << LOGL;
+    const int tid = threadIdx.x;
+    if (LOGL == 9) return (tid >> (LOGL - 3)) * L + (tid & ((L >> 3) - 1)) + slot * (L >> 3);
+    const int idx = tid + (slot >> 2) * T;
+    return (idx >> (LOGL - 2)) * L + (idx & ((L >> 2) - 1)) + (slot & 3) * (L >> 2);
+}
+
 template <int C, int LOGL, class Emit = FftNoEmit, class Ingest = FftNoIngest, int REGMODE = 0>
 __device__ __forceinline__ void fft_lds(double2 *buf, const FftAxis ax, Emit emit = Emit(), Ingest ingest = Ingest(),
                                         double2 *xr = nullptr) {
     static_assert(REGMODE == 0 || FftRegOk<C, LOGL>::V, "register hand-over needs a compile-time radix-8 plan");
+    static_assert(Emit::FETCH == FETCH_NONE || (LOGL >= 9 && LOGL <= 11), "two-phase emits need a compile-time plan");
     constexpr bool EMIT = Emit::ACTIVE && LOGL >= 9 && LOGL <= 11;
     constexpr bool INGEST = Ingest::ACTIVE && LOGL >= 9 && LOGL <= 11;
     constexpr int T = FftThreads<C, LOGL>::T;
@@ -144,6 +187,7 @@ __device__ __forceinline__ void fft_lds(double2 *buf, const FftAxis ax, Emit emi
 #pragma unroll
         for (int ps = 0; ps < NR8; ++ps) {
             const int lNs = 3 * ps, Ns = 1 << lNs, k = j & (Ns - 1);
+            if (3 * (ps + 1) == LOGL) emit_prefetch(emit, FETCH_EARLY);
             double2 a[8];
 #pragma unroll
             for (int r = 0; r < 8; ++r) {
@@ -188,8 +232,16 @@ __device__ __forceinline__ void fft_lds(double2 *buf, const FftAxis ax, Emit emi
                 for (int r = 0; r < 8; ++r) xr[r] = o[r];
             } else if (EMIT && 3 * (ps + 1) == LOGL) {   // last pass of the 8x8x8 plan
                 if (Emit::TO_LDS) __syncthreads();
+                if constexpr (Emit::FETCH == FETCH_PARK) {
 #pragma unroll
-                for (int r = 0; r < 8; ++r) emit(wb + r * Ns, o[r]);
+                    for (int r = 0; r < 8; ++r) emit.park(wb + r * Ns, o[r]);
+                    emit_prefetch(emit, FETCH_PARK);
+#pragma unroll
+                    for (int r = 0; r < 8; ++r) emit.apply(r, wb + r * Ns, emit.parked(wb + r * Ns));
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 8; ++r) emit_out(emit, r, wb + r * Ns, o[r]);
+                }
                 if (Emit::TO_LDS) __syncthreads();
             } else {
                 if (!(INGEST && ps == 0)) __syncthreads();          // nobody has read the image yet in an ingesting first pass
@@ -217,6 +269,7 @@ __device__ __forceinline__ void fft_lds(double2 *buf, const FftAxis ax, Emit emi
             w2 = ax.tw[2 * ti];
             w3 = ax.tw[3 * ti];
         }
+        if (logNs + 2 == logL) emit_prefetch(emit, FETCH_EARLY);
 #pragma unroll
         for (int i = 0; i < NB4; ++i) {
             const int idx = tid + i * T;
@@ -252,10 +305,22 @@ __device__ __forceinline__ void fft_lds(double2 *buf, const FftAxis ax, Emit emi
                 for (int r = 0; r < 4; ++r) xr[(i + 2 * r) & 7] = v[i][r];
         } else if (EMIT && logNs + 2 == logL) {
             if (Emit::TO_LDS) __syncthreads();
+            if constexpr (Emit::FETCH == FETCH_PARK) {
 #pragma unroll
-            for (int i = 0; i < NB4; ++i)
+                for (int i = 0; i < NB4; ++i)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) emit(wbase[i] + r * Ns, v[i][r]);
+                    for (int r = 0; r < 4; ++r) emit.park(wbase[i] + r * Ns, v[i][r]);
+                emit_prefetch(emit, FETCH_PARK);
+#pragma unroll
+                for (int i = 0; i < NB4; ++i)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) emit.apply(4 * i + r, wbase[i] + r * Ns, emit.parked(wbase[i] + r * Ns));
+            } else {
+#pragma unroll
+                for (int i = 0; i < NB4; ++i)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) emit_out(emit, 4 * i + r, wbase[i] + r * Ns, v[i][r]);
+            }
             if (Emit::TO_LDS) __syncthreads();
         } else {
             __syncthreads();
@@ -296,7 +361,7 @@ __device__ __forceinline__ void fft_lds(double2 *buf, const FftAxis ax, Emit emi
 // upper half of the spectrum is its mirror image and is dropped)
 template <int LOGL, class Put>
 struct RowEmit {
-    enum { ACTIVE = 1, TO_LDS = 0 };
+    enum { ACTIVE = 1, TO_LDS = 0, FETCH = 0 };
     Put &put_;
     int row0_, ns_;
     __device__ __forceinline__ void operator()(int idx, double2 v) const {
@@ -322,6 +387,116 @@ struct RowIngest {
         const int ra = row0_ + 2 * f;
         const double *p = ib_ + (long)ra * pitch_ + m;
         return make_double2(ra < ns_ ? p[0] : 0.0, ra + 1 < ns_ ? p[pitch_] : 0.0);
+    }
+};
+
+// Outputs per request of k_cheb_rows' two-phase update: 4 = all of a thread's nodes, 2 = one butterfly's (A/B knob).  All
+// of them need 182 VGPRs at lengths 1024 / 2048 in the sweeps j >= 1 (six operands a node), more than the three waves per
+// SIMD of the plain form allow; half of them fit (profiles/rows_batch_resources.txt).
+#ifndef CHEB_NB
+#define CHEB_NB (FIRST ? 4 : 2)
+#endif
+
+// A per-node functor in two halves: fetch(row, k, ops, form) only issues the node's global loads into an operand struct
+// Ops, apply(row, k, ops, e) does the arithmetic, the stores and returns what goes back into the image (if anything).
+// form = RowPlain: the loads under the conditions of the arithmetic that uses them, node by node (the plain kernels call
+// fetch and apply back to back).  form = RowBatched: the loads of a batch of nodes are to be issued back to back, so the
+// ones that every sweep needs come without a branch (a load whose value the arithmetic will not use reads a valid
+// address instead: the caller clamps the row, the functor substitutes a plane that exists); fetch_more, under the
+// workgroup-uniform more(), adds the ones only some launches need.
+using RowPlain = std::integral_constant<int, 0>;
+using RowBatched = std::integral_constant<int, 1>;
+template <class OpsT, class Fetch, class FetchMore, class Apply>
+struct RowNode {
+    using Ops = OpsT;
+    Fetch &fetch_;
+    FetchMore &more_;
+    Apply &apply_;
+    bool has_more_;
+    __device__ __forceinline__ void fetch(int row, int k, Ops &q) const { fetch_(row, k, q, RowBatched()); }
+    __device__ __forceinline__ bool more() const { return has_more_; }
+    __device__ __forceinline__ void fetch_more(int row, int k, Ops &q) const { more_(row, k, q); }
+    __device__ __forceinline__ double apply(int row, int k, const Ops &q, double e) const { return apply_(row, k, q, e); }
+};
+template <class OpsT, class Fetch, class FetchMore, class Apply>
+__device__ __forceinline__ RowNode<OpsT, Fetch, FetchMore, Apply> row_node(Fetch &f, FetchMore &m, Apply &a, bool has_more) {
+    return {f, m, a, has_more};
+}
+
+// Two-phase emit of a row kernel (see fft_lds).  Every thread emits four outputs k <= L/2, two rows each: prefetch()
+// requests the operands of the first NB outputs' nodes back to back, apply() runs the nodes in the order of the plain
+// form (RowEmit / the update of k_cheb_rows) and, with NB < 4, requests the next NB outputs' when it reaches them.  The
+// one thread per transform that also emits entry L/2 fetches that node where it applies it.
+// Every node is loaded and stored by exactly one thread, and by no other thread of the launch, so loading a whole batch
+// before its first store reads the same values even where a store's plane is a load's plane (y_new is the buffer of
+// y_prev).  TO_LDS_: what apply returns goes back into the image as the even extension of the next transform's input,
+// unless write_ is off.
+template <int C, int LOGL, class Node, int WHEN, int TO_LDS_, int NB = 4>
+struct RowEmit2 {
+    enum { ACTIVE = 1, TO_LDS = TO_LDS_, FETCH = WHEN, BATCH = NB };
+    static_assert(NB == 4 || NB == 2, "all of a thread's outputs or half of them");
+    static_assert(WHEN != FETCH_PARK || TO_LDS_, "parking needs the emit's barriers");
+    Node node_;
+    double2 *buf_;
+    int row0_, ns_;
+    bool write_;
+    typename Node::Ops ops_[BATCH][2];
+    // slot of the d-th output that every thread emits, and back (-1: not one of them)
+    static __device__ __forceinline__ constexpr int slot_of(int d) { return LOGL == 9 ? d : 4 * (d >> 1) + (d & 1); }
+    static __device__ __forceinline__ constexpr int dense_of(int slot) {
+        return LOGL == 9 ? (slot < 4 ? slot : -1) : ((slot & 3) < 2 ? 2 * (slot >> 2) + (slot & 3) : -1);
+    }
+    __device__ __forceinline__ void request(int d0) {
+        constexpr int LL = 1 << (LOGL ? LOGL : 1), LG = LOGL ? LOGL : 1;
+#pragma unroll
+        for (int d = 0; d < BATCH; ++d) {
+            const int idx = fft_last_out<C, LG>(slot_of(d0 + d)), f = idx >> LG, k = idx & (LL - 1);
+            const int ra = row0_ + 2 * f;
+            node_.fetch(min(ra, ns_ - 1), k, ops_[d][0]);            // rows >= ns: a valid address, the value is not used
+            node_.fetch(min(ra + 1, ns_ - 1), k, ops_[d][1]);
+        }
+        if (node_.more()) {
+#pragma unroll
+            for (int d = 0; d < BATCH; ++d) {
+                const int idx = fft_last_out<C, LG>(slot_of(d0 + d)), f = idx >> LG, k = idx & (LL - 1);
+                const int ra = row0_ + 2 * f;
+                node_.fetch_more(min(ra, ns_ - 1), k, ops_[d][0]);
+                node_.fetch_more(min(ra + 1, ns_ - 1), k, ops_[d][1]);
+            }
+        }
+    }
+    __device__ __forceinline__ typename Node::Ops fetch_one(int row, int k) const {
+        typename Node::Ops q;
+        node_.fetch(row, k, q);
+        if (node_.more()) node_.fetch_more(row, k, q);
+        return q;
+    }
+    __device__ __forceinline__ void prefetch() { request(0); }
+    // FETCH_PARK: an output the thread keeps waits at its own place in the image (a volatile read takes it back: the
+    // value must not be forwarded past the requests in registers)
+    __device__ __forceinline__ void park(int idx, double2 v) {
+        constexpr int LL = 1 << (LOGL ? LOGL : 1);
+        if ((idx & (LL - 1)) <= LL / 2) buf_[swz<LOGL>(idx)] = v;
+    }
+    __device__ __forceinline__ double2 parked(int idx) const {
+        constexpr int LL = 1 << (LOGL ? LOGL : 1);
+        if ((idx & (LL - 1)) > LL / 2) return make_double2(0.0, 0.0);
+        const volatile double *p = reinterpret_cast<const volatile double *>(buf_ + swz<LOGL>(idx));
+        return make_double2(p[0], p[1]);
+    }
+    __device__ __forceinline__ void apply(int slot, int idx, double2 v) {
+        constexpr int LL = 1 << (LOGL ? LOGL : 1), LG = LOGL ? LOGL : 1;
+        const int f = idx >> LG, k = idx & (LL - 1);
+        if (k > LL / 2) return;
+        const int ra = row0_ + 2 * f, dd = dense_of(slot), d = dd < 0 ? 0 : dd % BATCH;
+        if (BATCH < 4 && dd > 0 && dd % BATCH == 0) request(dd);      // the next batch's operands, into the same registers
+        double2 w = make_double2(0.0, 0.0);
+        if (ra < ns_) w.x = node_.apply(ra, k, dd >= 0 ? ops_[d][0] : fetch_one(ra, k), v.x);
+        if (ra + 1 < ns_) w.y = node_.apply(ra + 1, k, dd >= 0 ? ops_[d][1] : fetch_one(ra + 1, k), v.y);
+        if (TO_LDS_ && write_) {
+            buf_[swz<LOGL>(idx)] = w;
+            if (k > 0 && k < LL / 2) buf_[swz<LOGL>(f * LL + LL - k)] = w;
+        }
     }
 };
 
@@ -744,9 +919,16 @@ struct ChebSweepArgs {
 #ifndef CHEB_MINW
 #define CHEB_MINW 1            // minimum waves per SIMD the register allocation of k_cheb_rows must allow (A/B knob)
 #endif
-template <int C, int LOGL, int FIRST>
-__global__ __launch_bounds__((FftThreads<C, LOGL>::T), CHEB_MINW) void k_cheb_rows(Geom G, FftAxis ax, ChebSweepArgs a_, const double *__restrict__ in,
-                                                                       double *__restrict__ out, const TrajState *__restrict__ st) {
+// BATCH (here and in k_dct_cols; compile-time plans, the default): a phase's global operands are requested together, here
+// the operands of the update for a batch of a thread's nodes (RowEmit2).  BATCH = 0 is the plain form, one node at a time,
+// launched as k_..._plain (VCH_ROWS_BATCH=0); both forms run the same per-node arithmetic function on the same values.
+// Length 512 keeps the plain update in both: the parked form of its radix-8 last pass does not reproduce the plain
+// form's bits (the compiler contracts the update differently there).
+// The update's operands at a node: D, y_j, y_{j-1}, b~ and, on a trajectory's last sweep, x0 and phi
+struct ChebOps { double D, yc, yp, bt, x0, ph; };
+template <int C, int LOGL, int FIRST, int BATCH>
+__device__ __forceinline__ void cheb_rows_body(const Geom &G, const FftAxis &ax, const ChebSweepArgs &a_, const double *__restrict__ in,
+                                               double *__restrict__ out, const TrajState *__restrict__ st) {
     const int b = blockIdx.z;
     ChebSweepArgs a = a_;
     if (FIRST) a.j = 0;
@@ -778,23 +960,50 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T), CHEB_MINW) void k_cheb_ro
     const double *php = a.phi_s + st[b].slot * a.d_slot_stride + pb;
     double *const keepp = st[b].iters == 1 ? a.keep1 : (st[b].iters == 2 ? a.keep2 : nullptr);
     // node (row, k): g = the transform's output there; returns Delta y_{j+1}, the next transform's input
-    auto upd = [&](int row, int k, double g) -> double {
+    // RowBatched: planes that exist where this sweep does not read y_j, y_{j-1} or b~ (the values are not used then)
+    const double *ycv = a.j != 0 ? a.y_cur + pb : Dp, *ypv = a.j >= 2 ? a.y_prev + pb : Dp, *btv = a.j != 0 ? a.bt_in + pb : Dp;
+    auto upd_more = [&](int row, int k, ChebOps &q) {      // a trajectory's last sweep
+        const long o = (long)row * G.pitch + k;
+        if (primed) q.x0 = a.x0[pb + o];
+        q.ph = php[o];
+    };
+    auto upd_fetch = [&](int row, int k, ChebOps &q, auto form) {
+        const long o = (long)row * G.pitch + k;
+        q.D = q.yc = q.yp = q.bt = q.x0 = q.ph = 0.0;
+        if (decltype(form)::value) {
+            q.D = Dp[o];
+            if (!FIRST) {
+                q.yc = ycv[o];
+                q.yp = ypv[o];
+                q.bt = btv[o];
+            }
+        } else {
+            if (need_norm || !last) q.D = Dp[o];
+            if (a.j != 0) {
+                q.yc = a.y_cur[pb + o];
+                if (a.j >= 2) q.yp = a.y_prev[pb + o];
+                q.bt = a.bt_in[pb + o];
+            }
+            if (last) upd_more(row, k, q);
+        }
+    };
+    auto upd_apply = [&](int row, int k, const ChebOps &q, double g) -> double {
         const long o = (long)row * G.pitch + k;
         const double gg = a.scale * g;
         double z, yn, dl = 0.0;
-        if (need_norm || !last) dl = Dp[o] - dbar;
+        if (need_norm || !last) dl = q.D - dbar;
         if (a.j == 0) {
             z = gg;
             yn = ej * z;
             if (!last) a.bt_out[pb + o] = gg;
         } else {
-            const double yc = a.y_cur[pb + o], yp = a.j >= 2 ? a.y_prev[pb + o] : 0.0;
-            z = a.bt_in[pb + o] - yc - gg;
+            const double yc = q.yc, yp = a.j >= 2 ? q.yp : 0.0;
+            z = q.bt - yc - gg;
             yn = yc + cj * (yc - yp) + ej * z;
         }
         if (need_norm) acc += wdev(row, k, G) * dl * (z * z);
         if (last) {
-            const double d = primed ? a.x0[pb + o] + yn : yn, ph = php[o];
+            const double d = primed ? q.x0 + yn : yn, ph = q.ph;
             a.x_out[pb + o] = d;
             if (keepp) keepp[pb + o] = d;
             if (d > 0.0) cmin = fmin(cmin, (1.0 - DELTA_SEP - ph) / d);
@@ -804,16 +1013,27 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T), CHEB_MINW) void k_cheb_ro
         }
         return dl * yn;
     };
+    auto upd = [&](int row, int k, double g) -> double {
+        ChebOps q;
+        upd_fetch(row, k, q, RowPlain());
+        return upd_apply(row, k, q, g);
+    };
     const double *ib = in + pb;
     double *ob = out + pb;
     auto put = [&](int row, int k, double e) { ob[(long)row * G.pitch + k] = e; };
     constexpr bool DIRECT = LOGL >= 9 && LOGL <= 11;
-    if (DIRECT) {
+    if constexpr (DIRECT && BATCH && LOGL != 9) {
+        // as below, with the update's operands of a batch of the thread's nodes requested together (CHEB_NB)
+        auto nd = row_node<ChebOps>(upd_fetch, upd_more, upd_apply, last);
+        fft_lds<C, LOGL, RowEmit2<C, LOGL, decltype(nd), FETCH_PARK, 1, CHEB_NB>>(
+            buf, ax, {nd, buf, row0, G.ns, !last}, RowIngest<LOGL>{ib, (long)G.pitch, row0, G.ns});
+        if (!last) fft_lds<C, LOGL>(buf, ax, RowEmit<LOGL, decltype(put)>{put, row0, G.ns});
+    } else if (DIRECT) {
         constexpr int LL = 1 << (LOGL ? LOGL : 1), LG = LOGL ? LOGL : 1;
         // the first transform's last pass hands its outputs to the update; what the update returns goes back into the
         // image as the even extension of the next transform's input (entry k and its mirror L - k from the same thread)
         struct UpdEmit {
-            enum { ACTIVE = 1, TO_LDS = 1 };
+            enum { ACTIVE = 1, TO_LDS = 1, FETCH = 0 };
             decltype(upd) &upd_;
             double2 *buf_;
             int row0_, ns_;
@@ -865,6 +1085,16 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T), CHEB_MINW) void k_cheb_ro
             else a.cmin[(long)b * gridDim.x + blockIdx.x] = cmin;
         }
     }
+}
+template <int C, int LOGL, int FIRST>
+__global__ __launch_bounds__((FftThreads<C, LOGL>::T), CHEB_MINW) void k_cheb_rows(Geom G, FftAxis ax, ChebSweepArgs a_, const double *__restrict__ in,
+                                                                       double *__restrict__ out, const TrajState *__restrict__ st) {
+    cheb_rows_body<C, LOGL, FIRST, 1>(G, ax, a_, in, out, st);
+}
+template <int C, int LOGL, int FIRST>
+__global__ __launch_bounds__((FftThreads<C, LOGL>::T), CHEB_MINW) void k_cheb_rows_plain(Geom G, FftAxis ax, ChebSweepArgs a_, const double *__restrict__ in,
+                                                                             double *__restrict__ out, const TrajState *__restrict__ st) {
+    cheb_rows_body<C, LOGL, FIRST, 0>(G, ax, a_, in, out, st);
 }
 
 // =====================================================================================================
@@ -1075,10 +1305,13 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_adj_rows_fwd(Geom 
 }
 
 // E along the slow axis, spectral multiplier 1/(c0 + m (c1 + c2 m)) (m = ms[k] + mf[col]), E again.
-template <int C, int LOGL>
-__global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_dct_cols(Geom G, FftAxis ax, const double *__restrict__ in,
-                                                  double *__restrict__ out, double scale, SpecArgs sp,
-                                                  const TrajState *__restrict__ st, int gate) {
+// BATCH (compile-time plans): the column data of all of a thread's rows are requested before the first one is written to
+// the image, and the multiplier entries ms / mf at the top of the first transform's last pass (their indices depend on
+// tid only), so that they arrive under its butterflies.
+template <int C, int LOGL, int BATCH>
+__device__ __forceinline__ void dct_cols_body(const Geom &G, const FftAxis &ax, const double *__restrict__ in,
+                                              double *__restrict__ out, double scale, const SpecArgs &sp,
+                                              const TrajState *__restrict__ st, int gate) {
     const int b = blockIdx.z;
     if (gate && !gate_open(st[b], gate)) return;
     __shared__ double2 buf[C];
@@ -1093,15 +1326,42 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_dct_cols(Geom G, F
     // a column pair is 16 contiguous, 16-byte aligned bytes of a row (col0 even, pitch a multiple of 8): one b128 load
     // and one b128 LDS store per row instead of two 8-byte ones from two lanes (-1.3 % on the march,
     // profiles/r02_fft_variants.txt)
-    for (int idx = tid; idx < n1 * nfft; idx += T) {
-        const int r = nfft == 1 ? idx : idx / nfft, f = nfft == 1 ? 0 : idx - r * nfft;
-        const int ca = col0 + 2 * f;
-        const double *p = ib + (long)r * G.pitch + ca;
-        double2 v = make_double2(0.0, 0.0);
-        if (ca + 1 < G.nf) v = *reinterpret_cast<const double2 *>(p);
-        else if (ca < G.nf) v.x = p[0];
-        buf[swz<LOGL>(f * L + r)] = v;
-        if (r > 0 && r < N) buf[swz<LOGL>(f * L + L - r)] = v;
+    if constexpr (DIRECT && BATCH) {
+        // the same loop with a compile-time trip count (5 for every plan), loads first
+        constexpr int NIT = ((LL / 2 + 1) * (C >> LG) + T - 1) / T;
+        double2 cv[NIT];
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            const int idx = tid + it * T;
+            const int r = nfft == 1 ? idx : idx / nfft, f = nfft == 1 ? 0 : idx - r * nfft;
+            const int ca = col0 + 2 * f;
+            const double *p = ib + (long)r * G.pitch + ca;
+            cv[it] = make_double2(0.0, 0.0);
+            if (idx < n1 * nfft) {
+                if (ca + 1 < G.nf) cv[it] = *reinterpret_cast<const double2 *>(p);
+                else if (ca < G.nf) cv[it].x = p[0];
+            }
+        }
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            const int idx = tid + it * T;
+            const int r = nfft == 1 ? idx : idx / nfft, f = nfft == 1 ? 0 : idx - r * nfft;
+            if (idx < n1 * nfft) {
+                buf[swz<LOGL>(f * L + r)] = cv[it];
+                if (r > 0 && r < N) buf[swz<LOGL>(f * L + L - r)] = cv[it];
+            }
+        }
+    } else {
+        for (int idx = tid; idx < n1 * nfft; idx += T) {
+            const int r = nfft == 1 ? idx : idx / nfft, f = nfft == 1 ? 0 : idx - r * nfft;
+            const int ca = col0 + 2 * f;
+            const double *p = ib + (long)r * G.pitch + ca;
+            double2 v = make_double2(0.0, 0.0);
+            if (ca + 1 < G.nf) v = *reinterpret_cast<const double2 *>(p);
+            else if (ca < G.nf) v.x = p[0];
+            buf[swz<LOGL>(f * L + r)] = v;
+            if (r > 0 && r < N) buf[swz<LOGL>(f * L + L - r)] = v;
+        }
     }
     __syncthreads();
     const double c1 = sp.c1a + sp.c1b * st[b].dbar;
@@ -1110,7 +1370,7 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_dct_cols(Geom G, F
     // forward transform; with a compile-time plan its last pass writes the outputs back already multiplied by the
     // spectral multiplier, otherwise a separate pass over the image does
     struct ScaleEmit {
-        enum { ACTIVE = 1, TO_LDS = 1 };
+        enum { ACTIVE = 1, TO_LDS = 1, FETCH = 0 };
         double2 *buf_;
         const SpecArgs &sp_;
         double c1_, scale_;
@@ -1128,7 +1388,38 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_dct_cols(Geom G, F
         }
     };
     constexpr bool FUSE = DIRECT && FftRegOk<C, LOGL>::V;
-    if constexpr (FUSE) {
+    if constexpr (FUSE && BATCH) {
+        // as below; the multiplier entries are requested at the top of the first transform's last pass
+        struct SpecFetch {
+            enum { ACTIVE = 0, TO_LDS = 1, FETCH = FETCH_EARLY };
+            const SpecArgs &sp_;
+            double (&msk_)[8], &mfa_, &mfb_;
+            int col0_, nf_;
+            __device__ __forceinline__ void prefetch() {
+                const int tid = threadIdx.x, f = tid >> (LG - 3), j = tid & ((LL >> 3) - 1);
+                const int ca = col0_ + 2 * f, cb = ca + 1;
+#pragma unroll
+                for (int s = 0; s < 8; ++s) {
+                    const int k = j + s * (LL >> 3), ks = k <= LL / 2 ? k : LL - k;
+                    msk_[s] = sp_.ms[ks];
+                }
+                mfa_ = sp_.mf[ca < nf_ ? ca : nf_ - 1];
+                mfb_ = sp_.mf[cb < nf_ ? cb : nf_ - 1];
+            }
+            __device__ __forceinline__ void apply(int, int, double2) const {}
+        };
+        double2 xr[8];
+        double msk[8], mfa, mfb;
+        fft_lds<C, LOGL, SpecFetch, FftNoIngest, 1>(buf, ax, SpecFetch{sp, msk, mfa, mfb, col0, G.nf}, FftNoIngest(), xr);
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+            double fa, fb;
+            spec_mult2(sp, c1, scale, msk[s] + mfa, msk[s] + mfb, fa, fb, mmode);
+            xr[s].x *= fa;
+            xr[s].y *= fb;
+        }
+        fft_lds<C, LOGL, FftNoEmit, FftNoIngest, 2>(buf, ax, FftNoEmit(), FftNoIngest(), xr);
+    } else if constexpr (FUSE) {
         // first transform, its last pass kept in registers; multiplier; second transform fed from those registers: one
         // LDS round trip and one barrier pair less than ScaleEmit, same arithmetic
         double2 xr[8];
@@ -1175,6 +1466,18 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_dct_cols(Geom G, F
         if (ca + 1 < G.nf) *reinterpret_cast<double2 *>(p) = v;
         else if (ca < G.nf) p[0] = v.x;
     }
+}
+template <int C, int LOGL>
+__global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_dct_cols(Geom G, FftAxis ax, const double *__restrict__ in,
+                                                  double *__restrict__ out, double scale, SpecArgs sp,
+                                                  const TrajState *__restrict__ st, int gate) {
+    dct_cols_body<C, LOGL, 1>(G, ax, in, out, scale, sp, st, gate);
+}
+template <int C, int LOGL>
+__global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_dct_cols_plain(Geom G, FftAxis ax, const double *__restrict__ in,
+                                                  double *__restrict__ out, double scale, SpecArgs sp,
+                                                  const TrajState *__restrict__ st, int gate) {
+    dct_cols_body<C, LOGL, 0>(G, ax, in, out, scale, sp, st, gate);
 }
 
 // =====================================================================================================
