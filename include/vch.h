@@ -676,6 +676,54 @@ int vch1d_hessvec(vch1d_ctx *ctx, const double *phi_hist, const double *u, int n
                   double *grad_out /* [B][rows][N+1] or NULL */, double *hv_out /* [B][rows][N+1], required iff order 2 */,
                   double *dots_out /* [B][2] or NULL */, vch_stats *stats);
 
+/* Lanczos on the reduced Hessian P H P of J1 + J2 + J3 of the 1D cost, with the basis, the free set and the recurrence in
+ * device memory (the 1D counterpart of vch2d_hess_lanczos; ABI version stays 3: detect both entry points by
+ * symbol).  H q comes from the transposed sweeps of vch1d_hessvec; P masks to the free set.  Only the tridiagonal coefficients
+ * cross to the host: T = tridiag(beta, alpha, beta) of a trajectory has the Ritz values of P H P.
+ *   Base point (phi_hist, u, n_base, rows, dt, t_hist, x, phi_Q, phi_T, opts / n_opts): the rules of vch1d_hessvec, with
+ *   NULL = zeros, VCH_RESIDENT, the resident history and the stop quirk.  Beyond b1, b2, b3 the call reads u_min, u_max of
+ *   opts[b].
+ *   mask     [n_base][rows][N+1] bytes, non-zero = free (one for the batch, or one per trajectory); NULL: built on the
+ *            device from the base control with trajectory b's own box, u > u_min + tol && u < u_max - tol && |u| > tol
+ *            (tol <= 0: 1e-8).  All rows take part, the duplicated t = 0 row included.  NULL mask with NULL u is
+ *            VCH_ERR_ARG: a zero control has no free node.
+ *   q0       [B][rows][N+1] start vector; q_0 = P q0 / ||P q0||
+ *   k        steps at most; trajectory b stops after min(k, n_free_b) steps, when beta_j <= 1e-14 max_i |alpha_i| (an
+ *            invariant subspace) or when beta_j is not finite; a stopped trajectory's vectors are left alone, the others go on
+ *   reorth   1: classical Gram-Schmidt, twice, against all of q_0 .. q_j (k + 1 resident vectors); 0: the same two rounds
+ *            against q_{j-1}, q_j only (three resident vectors)
+ *   alpha_out, beta_out [B][k]: alpha_j = the sum of the two rounds' coefficients on q_j, beta_j = ||w|| after both rounds;
+ *            entries beyond steps_out[b] are NaN.  n_free_out[b]: the size of the free set, counted on the device.
+ * The set-up launch (one persistent workgroup per trajectory) builds the free set, q_0 and runs the gradient sweep once,
+ * keeping every step's multiplier yp in one further history; a step then runs the tangent march of q_j and the second
+ * transposed sweep alone: 2 M solves per trajectory and step instead of vch1d_hessvec's 3 M (VCH_KRYLOV_NOCACHE=1 repeats the
+ * gradient sweep in every step, with the same bits: A/B and tests).  The recurrence (products, updates, norm, q_{j+1}) runs
+ * on a device-wide grid with two-stage reductions in a fixed order.  The stop state lives in device cells, the k steps are
+ * enqueued back to back, and the host looks twice: after the set-up (n_free, ||P q0||) and at the end.
+ * Errors: VCH_ERR_ARG / VCH_ERR_STATE as for vch1d_hessvec with the same messages, VCH_ERR_ARG for k < 1, NULL q0 or outputs,
+ * reorth outside 0 / 1 and NULL mask with NULL u -- all before anything is copied, launched or allocated.  Two errors depend
+ * on the data, both VCH_ERR_ARG naming the trajectory: an empty free set, and a start vector that vanishes on the free set;
+ * they come after the set-up launch and one look, before any step, and leave no resident basis.  Device storage, allocated
+ * on first use as one group: the basis (k + 1 or 3 histories), one history each for the cached sweep, the tangent and w, the
+ * mask (one byte per node of a history) and the partials; a refused request releases what the call got and returns
+ * VCH_ERR_NOMEM with the context usable and unchanged and a message that states the bytes the group needs.  A later call with
+ * a larger k replaces the storage.  Stateless like vch1d_hessvec; no atomics: a trajectory's alpha, beta and steps are
+ * bitwise those of a single-trajectory context, whatever its batch mates do.
+ * stats: launches, host_syncs = 2, linear_solves = B M (2 s + 1) for a batch whose members all take s steps (3 B M s with the
+ * switch), device seconds. */
+int vch1d_hess_lanczos(vch1d_ctx *ctx, const double *phi_hist, const double *u, int n_base, int rows,
+                       const double *dt, const double *t_hist, const double *x,
+                       const double *phi_Q, const double *phi_T, const vch_opt_params *opts, int n_opts,
+                       const uint8_t *mask /* [n_base][rows][N+1] or NULL */, double tol,
+                       const double *q0 /* [B][rows][N+1] */, int k, int reorth /* 0 | 1 */,
+                       double *alpha_out /* [B][k] */, double *beta_out /* [B][k] */,
+                       int32_t *steps_out /* [B] */, int64_t *n_free_out /* [B] */, vch_stats *stats);
+/* out[b] = sum_{j<m} coef[b][j] q_j from the basis the last vch1d_hess_lanczos of this context left resident: the Ritz vector
+ * of a Ritz value (coef = an eigenvector of T), or one basis vector (a unit coef).  Masked-off nodes are exact zeros.
+ * VCH_ERR_STATE without a resident basis, and after a reorth = 0 run when m exceeds the vectors still held; VCH_ERR_ARG for
+ * m < 1 or m above the smallest step count of the batch plus one. */
+int vch1d_krylov_vector(vch1d_ctx *ctx, const double *coef /* [B][m] */, int m, double *out /* [B][rows][N+1] */);
+
 /* ---------------------------------------------------------- diagnostics ---- */
 
 /* Every device and pinned-host block of a context belongs to the context's pool (csrc/vch_mem.h): vchNd_destroy, and a

@@ -165,7 +165,8 @@ def free_set(u_star, u_min, u_max, tol=1e-8):
 
 
 def reduced_hessian_extremes(fwd_config: ForwardSolverConfig, u_star, phi_star, x, t_hist, b1, b2, b3, kappa, phi_Q_target,
-                             phi_T_target, u_min, u_max, k: int = 30, seed=None, tol: float = 1e-8) -> dict:
+                             phi_T_target, u_min, u_max, k: int = 30, seed=None, tol: float = 1e-8, on_device: bool = False,
+                             vector: bool = False, reorth: bool = True) -> dict:
     """Extreme eigenvalues of the reduced Hessian P H P of the smooth part J1 + J2 + J3 of the discrete cost at `u_star`,
     by host Lanczos with full reorthogonalisation.  H is the exact Euclidean Hessian with respect to the entries of u
     (Engine1D.hessvec: one tangent and two transposed solves per time step, about `phi_star` as given, one call per
@@ -185,7 +186,17 @@ def reduced_hessian_extremes(fwd_config: ForwardSolverConfig, u_star, phi_star, 
     a point per node, the minimum of the quadratic form over it is no eigenvalue problem, and the L1 term adds no
     curvature along an admitted sign.  Those nodes are pinned to zero here, so theta_min bounds the cone's constant from
     above: a cone direction that mixes free and one-signed nodes can still see less curvature.  `kappa` therefore does
-    not enter.  The clip of the march is taken as inactive, as in `exact_second_order_condition`."""
+    not enter.  The clip of the march is taken as inactive, as in `exact_second_order_condition`.
+
+    on_device=True keeps the iteration on the device (Engine1D.hess_lanczos: the same seeded start vector, the basis and the
+    recurrence in device memory, two linear solves per step and time step instead of three); only the tridiagonal matrix
+    comes back and its eigh is taken here.  The keys are the same.  reorth=False runs the three-term recurrence with three
+    resident vectors (on_device only).  vector=True (on_device with full reorthogonalisation only) adds `v_min`, the unit
+    Ritz vector of theta_min in the shape of u_star.  The default path is the host reference."""
+    if (vector or not reorth) and not on_device:
+        raise ValueError("reduced_hessian_extremes: vector=True and reorth=False need on_device=True")
+    if vector and not reorth:
+        raise ValueError("reduced_hessian_extremes: vector=True needs full reorthogonalisation")
     from ..engine import make_opt
     from ._ctx import engine_for_config
     cfg = fwd_config if fwd_config is not None else ForwardSolverConfig()
@@ -205,6 +216,21 @@ def reduced_hessian_extremes(fwd_config: ForwardSolverConfig, u_star, phi_star, 
         return np.where(mask, res["hv"][0], 0.0)
 
     q = np.where(mask, rng.standard_normal(u_star.shape), 0.0)
+    if on_device:
+        box = make_opt(b1=b1, b2=b2, b3=b3, kappa_sparsity=0.0, u_min=float(u_min), u_max=float(u_max))
+        L = eng.hess_lanczos(q, int(k), t_hist, box, phi_hist=phi_star, u=u_star, phi_Q=phi_Q_target, phi_T=phi_T_target, x=x,
+                             mask=mask, tol=tol, reorth=reorth, shared_base=True)
+        m = int(L["steps"][0])
+        alphas, betas = L["alpha"][0, :m], L["beta"][0, :m]
+        T = np.diag(alphas) + np.diag(betas[:m - 1], 1) + np.diag(betas[:m - 1], -1)
+        theta, S = np.linalg.eigh(T)
+        resid = np.abs(betas[m - 1] * S[m - 1])
+        out = dict(theta_min=float(theta[0]), theta_max=float(theta[-1]), res_min=float(resid[0]), res_max=float(resid[-1]),
+                   ritz=theta, n_free=int(L["n_free"][0]), steps=m)
+        if vector:
+            v = eng.krylov_vector(S[:, 0][None])[0]
+            out["v_min"] = v / np.linalg.norm(v)
+        return out
     q /= np.linalg.norm(q)
     Q, alphas, betas = [q], [], []
     steps = min(int(k), n_free)

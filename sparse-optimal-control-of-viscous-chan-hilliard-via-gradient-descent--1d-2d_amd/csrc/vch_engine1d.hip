@@ -47,6 +47,15 @@ struct vch1d_ctx {
     // vch1d_hessvec (lazy; it shares the base point, direction and grid buffers above): G, Hh and the tangent's v_k
     // [B][Mmax+2][n], the time weights [Mmax+2], the removed means [B][Mmax+2], the two dot products [B][2]
     double *hv_g = nullptr, *hv_hv = nullptr, *hv_v = nullptr, *hv_wt = nullptr, *hv_mean = nullptr, *hv_dots = nullptr;
+    // vch1d_hess_lanczos (lazy, one group): the basis [kr_slots][B][Mmax+2][n], the gradient sweep's yp of every step, the
+    // tangent's v_k and w (one history each), the mask (one byte per node of a history) and the block of partials, scalars
+    // and small tables (Kr1Layout); what the last iteration left for vch1d_krylov_vector
+    double *kr_Q = nullptr, *kr_X = nullptr, *kr_V = nullptr, *kr_W = nullptr, *kr_sc = nullptr;
+    unsigned char *kr_mask = nullptr;
+    int kr_slots = 0, kr_kcap = 0;
+    bool kr_valid = false;
+    int kr_rows = 0, kr_run_slots = 0, kr_min_steps = 0, kr_window = 0;
+    bool kr_nocache = false;               // VCH_KRYLOV_NOCACHE=1 (A/B and tests): every step repeats the gradient sweep
 };
 
 // no launch bookkeeping (LAUNCH_LDS, vch_common.h)
@@ -149,8 +158,10 @@ extern "C" vch1d_ctx *vch1d_create(const vch1d_params *p, int batch, int max_ste
     // > 64 KiB of dynamic LDS needs the opt-in attribute
     for (const void *k : {(const void *)k1d_forward, (const void *)k1d_newton, (const void *)k1d_backward, (const void *)k1d_solve<0>,
                           (const void *)k1d_solve<1>, (const void *)k1d_tangent<1>, (const void *)k1d_tangent<2>,
-                          (const void *)k1d_hessvec<1>, (const void *)k1d_hessvec<2>})
+                          (const void *)k1d_hessvec<1>, (const void *)k1d_hessvec<2>, (const void *)k1d_kr_setup,
+                          (const void *)k1d_kr_step<0>, (const void *)k1d_kr_step<1>})
         hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes);
+    c->kr_nocache = getenv("VCH_KRYLOV_NOCACHE") && atoi(getenv("VCH_KRYLOV_NOCACHE")) != 0;
     if (hipStreamSynchronize(c->stream) != hipSuccess) return fail("hipStreamSynchronize");
     return c;
 }
@@ -776,17 +787,19 @@ static int so1_base(vch1d_ctx *c, const double *phi_hist, const double *u, const
     return 0;
 }
 // step sizes, t_hist, the trapezoid weights of x and the weight table (host vectors: the caller synchronises before they go)
+static int so1_grids_alloc(vch1d_ctx *c) {
+    if (c->so_out) return 0;       // the last of the group: there are all five or none
+    vch_group g(c->pool);
+    VCHCHK(dalloc1(c, &c->so_dts, c->Mmax + 2));
+    VCHCHK(dalloc1(c, &c->so_t, c->Mmax + 2));
+    VCHCHK(dalloc1(c, &c->so_wx, c->n));
+    VCHCHK(dalloc1(c, &c->so_wts, 3 * (size_t)c->B));
+    VCHCHK(dalloc1(c, &c->so_out, 6 * (size_t)c->B));
+    return g.keep();
+}
 static int so1_grids(vch1d_ctx *c, const std::vector<double> &dts, const double *t_hist, int rows, const std::vector<double> &wx,
                      const std::vector<double> &wts) {
-    if (!c->so_out) {              // the last of the group: there are all five or none
-        vch_group g(c->pool);
-        VCHCHK(dalloc1(c, &c->so_dts, c->Mmax + 2));
-        VCHCHK(dalloc1(c, &c->so_t, c->Mmax + 2));
-        VCHCHK(dalloc1(c, &c->so_wx, c->n));
-        VCHCHK(dalloc1(c, &c->so_wts, 3 * (size_t)c->B));
-        VCHCHK(dalloc1(c, &c->so_out, 6 * (size_t)c->B));
-        g.keep();
-    }
+    VCHCHK(so1_grids_alloc(c));
     VCHCHK(up(c, c->so_dts, dts.data(), rows - 2));
     VCHCHK(up(c, c->so_t, t_hist, rows));
     VCHCHK(up(c, c->so_wx, wx.data(), c->n));
@@ -921,4 +934,220 @@ extern "C" int vch1d_hessvec(vch1d_ctx *c, const double *phi_hist, const double 
         stats->seconds = ms * 1e-3;
     }
     return 0;
+}
+
+// ------------------------------------------------------------------------------------
+// Lanczos on the reduced Hessian P H P with the basis, the free set and the recurrence on the device (kernels: "Device-
+// resident Lanczos" in vch_kernels1d.h)
+// ------------------------------------------------------------------------------------
+// The block behind kr_sc, in doubles; S = basis slots (the stride of a partial and of a coefficient row), K = entries of
+// alpha / beta per trajectory.
+struct Kr1Layout {
+    size_t part, coef1, coef2, ucoef, alpha, beta, look, scal, amax, lim, stop, steps, box, wt, mean, total;
+};
+static int kr1_chunks(const vch1d_ctx *c, int rows) { return (int)(((long)rows * c->n + KR1_CHUNK - 1) / KR1_CHUNK); }
+static Kr1Layout kr1_layout(const vch1d_ctx *c, int S, int K) {
+    const size_t B = c->B, R = c->Mmax + 2;
+    Kr1Layout L;
+    size_t at = 0;
+    auto take = [&](size_t n) { const size_t o = at; at += n; return o; };
+    L.part = take(B * kr1_chunks(c, (int)R) * S);
+    L.coef1 = take(B * S);
+    L.coef2 = take(B * S);
+    L.ucoef = take(B * S);
+    L.alpha = take(B * K);
+    L.beta = take(B * K);
+    L.look = take(2 * B);
+    L.scal = take(B);
+    L.amax = take(B);
+    L.lim = take(B);
+    L.stop = take(B);
+    L.steps = take(B);
+    L.box = take(2 * B);
+    L.wt = take(R);
+    L.mean = take(B * R);
+    L.total = at;
+    return L;
+}
+static Kr1Args kr1_args(const vch1d_ctx *c, const Kr1Layout &L, int rows, int slots, long mask_s) {
+    double *p = c->kr_sc;
+    const Kr1Cells x{p + L.coef1, p + L.coef2, p + L.alpha, p + L.beta, p + L.look, p + L.scal, p + L.amax,
+                     (long long *)(p + L.lim), (long long *)(p + L.stop), (long long *)(p + L.steps)};
+    return Kr1Args{c->kr_Q, (long)c->B * hs1(c), hs1(c), (long)rows * c->n, slots, c->kr_slots, c->kr_mask, mask_s, x};
+}
+
+extern "C" int vch1d_hess_lanczos(vch1d_ctx *c, const double *phi_hist, const double *u, int n_base, int rows, const double *dt,
+                                  const double *t_hist, const double *x, const double *phi_Q, const double *phi_T,
+                                  const vch_opt_params *opts, int n_opts, const uint8_t *mask, double tol, const double *q0, int k,
+                                  int reorth, double *alpha_out, double *beta_out, int32_t *steps_out, int64_t *n_free_out,
+                                  vch_stats *stats) {
+    CTXCHK(c);
+    const int B = c->B, n = c->n;
+    const char *fn = "vch1d_hess_lanczos";
+    VCHCHK(so1_check_shape(c, fn, n_base, rows, n_opts, 2));
+    if (!q0) return vch_fail(VCH_ERR_ARG, "%s: NULL q0", fn);
+    if (!alpha_out || !beta_out || !steps_out || !n_free_out)
+        return vch_fail(VCH_ERR_ARG, "%s: NULL alpha_out, beta_out, steps_out or n_free_out", fn);
+    if (k < 1) return vch_fail(VCH_ERR_ARG, "%s: k = %d must be >= 1", fn, k);
+    if (reorth != 0 && reorth != 1) return vch_fail(VCH_ERR_ARG, "%s: reorth = %d is neither 0 nor 1", fn, reorth);
+    if (!mask && !u) return vch_fail(VCH_ERR_ARG, "%s: NULL mask with a NULL (zero) control: no node is free", fn);
+    std::vector<double> dts, wts, wx;
+    VCHCHK(so1_check_rest(c, fn, phi_hist, u, rows, dt, t_hist, x, phi_Q, phi_T, opts, n_opts, dts, wts));
+    // ---- nothing was launched, copied or allocated up to here
+    const int M = rows - 2, slots = reorth ? k + 1 : 3;
+    const long hs = hs1(c);
+    const size_t hist_bytes = (size_t)B * hs * sizeof(double);
+    c->kr_valid = false;
+    if (c->kr_Q && (slots > c->kr_slots || k > c->kr_kcap)) {       // a larger basis than the resident storage holds
+        c->pool.drop((void **)&c->kr_sc);
+        c->pool.drop((void **)&c->kr_mask);
+        c->pool.drop((void **)&c->kr_W);
+        c->pool.drop((void **)&c->kr_V);
+        c->pool.drop((void **)&c->kr_X);
+        c->pool.drop((void **)&c->kr_Q);
+        c->kr_slots = c->kr_kcap = 0;
+    }
+    {   // lazy storage, one group: a refused request gives back what this call got and leaves the context as it was
+        vch_group g(c->pool);
+        if (phi_hist) VCHCHK(ensure1(c, &c->so_base));
+        if (u && u != VCH_RESIDENT) VCHCHK(ensure1(c, &c->so_u));
+        if (phi_Q && phi_Q != VCH_RESIDENT) VCHCHK(ensure1(c, &c->so_pq));
+        if (phi_T && phi_T != VCH_RESIDENT) VCHCHK(dalloc1(c, &c->so_pt, (size_t)B * n));
+        VCHCHK(so1_grids_alloc(c));
+        if (!c->kr_Q) {
+            const Kr1Layout L = kr1_layout(c, slots, k);
+            const size_t need = (size_t)(slots + 3) * hist_bytes + hist_bytes / 8 + L.total * 8;
+            const bool ok = c->pool.dev(&c->kr_Q, (size_t)slots * hist_bytes) == 0 && c->pool.dev(&c->kr_X, hist_bytes) == 0 &&
+                            c->pool.dev(&c->kr_V, hist_bytes) == 0 && c->pool.dev(&c->kr_W, hist_bytes) == 0 &&
+                            c->pool.dev(&c->kr_mask, hist_bytes / 8) == 0 && c->pool.dev(&c->kr_sc, L.total * 8) == 0;
+            if (!ok) {
+                (void)hipGetLastError();
+                return vch_fail(VCH_ERR_NOMEM,
+                                "%s: the Krylov storage needs %zu bytes (%d basis vectors of %zu bytes, three more histories for "
+                                "the cached sweep, the tangent and w, %zu bytes of mask, %zu of partials) and was refused",
+                                fn, need, slots, hist_bytes, hist_bytes / 8, L.total * 8);
+            }
+            c->kr_slots = slots;
+            c->kr_kcap = k;
+        }
+        g.keep();
+    }
+    const Kr1Layout L = kr1_layout(c, c->kr_slots, c->kr_kcap);
+    const bool build = mask == nullptr;
+    const Kr1Args K = kr1_args(c, L, rows, slots, (build || n_base == B) ? hs : 0);
+    double *part = c->kr_sc + L.part;
+    const int S = c->kr_slots, nch = kr1_chunks(c, rows);
+    const dim3 kgrid(nch, B);
+    auto slot_of = [&](int i) { return c->kr_Q + (long)(i % slots) * B * hs; };
+    So1Base Sb;
+    VCHCHK(so1_base(c, phi_hist, u, phi_Q, phi_T, n_base, rows, Sb));
+    trapz_x(c, x, wx);
+    VCHCHK(so1_grids(c, dts, t_hist, rows, wx, wts));
+    // trapezoid weights of t_hist as in vch1d_hessvec, and every trajectory's box
+    std::vector<double> wt(rows, 0.0), box(2 * (size_t)B);
+    for (int r = 0; r + 1 < rows; ++r) {
+        const double d = t_hist[r + 1] - t_hist[r];
+        wt[r] += 0.5 * d;
+        wt[r + 1] += 0.5 * d;
+    }
+    for (int b = 0; b < B; ++b) {
+        const vch_opt_params &o = vch_pgd_opt(opts, n_opts, b);
+        box[2 * b] = o.u_min;
+        box[2 * b + 1] = o.u_max;
+    }
+    VCHCHK(up(c, c->kr_sc + L.wt, wt.data(), rows));
+    VCHCHK(up(c, c->kr_sc + L.box, box.data(), box.size()));
+    VCHCHK(up_hist(c, slot_of(0), q0, rows));
+    if (mask)
+        for (int b = 0; b < n_base; ++b)
+            HIPCHK(hipMemcpyAsync(c->kr_mask + (size_t)b * hs, mask + (size_t)b * rows * n, (size_t)rows * n, hipMemcpyHostToDevice,
+                                  c->stream));
+    HIPCHK(hipMemsetAsync(K.x.alpha, 0xff, sizeof(double) * 2 * B * c->kr_kcap, c->stream));      // NaN: alpha, then beta
+    Hv1Args G{};
+    G.hs = hs;
+    G.phi = Sb.phi; G.u = Sb.u; G.pq = Sb.pq; G.pt = Sb.pt;
+    G.phi_s = G.u_s = G.pq_s = Sb.bs;
+    G.pt_s = Sb.pts;
+    G.dts = c->so_dts; G.wt = c->kr_sc + L.wt; G.wx = c->so_wx; G.wts = c->so_wts;
+    G.hv = c->kr_W; G.v = c->kr_V; G.mean = c->kr_sc + L.mean;
+    HIPCHK(hipEventRecord(c->ev0, c->stream));
+    // the set-up: the free set, q_0 and (once per base point) the gradient sweep, whose yp of every step stays in kr_X
+    LAUNCH_LDS(-1, k1d_kr_setup, dim3(B), dim3(T1), c->lds_bytes, c->P, n, c->h, c->lvl, rows, G, K, (const double *)(c->kr_sc + L.box),
+               tol > 0 ? tol : 1e-8, build ? 1 : 0, k, c->kr_nocache ? 0 : 1, c->kr_X, c->scratch);
+    std::vector<double> look(2 * (size_t)B);
+    VCHCHK(down(c, look.data(), K.x.look, look.size()));            // the first look; the host vectors above are done with
+    for (int b = 0; b < B; ++b) {
+        if (look[2 * b] < 1.0) return vch_fail(VCH_ERR_ARG, "%s: trajectory %d: the free set is empty", fn, b);
+        if (!(look[2 * b + 1] > 0.0) || !std::isfinite(look[2 * b + 1]))
+            return vch_fail(VCH_ERR_ARG, "%s: trajectory %d: the start vector vanishes on the free set (or is not finite)", fn, b);
+    }
+    // k steps back to back: a stopped trajectory's kernels return at once, the host does not look
+    for (int j = 0; j < k; ++j) {
+        G.hd = slot_of(j);
+        if (c->kr_nocache)
+            LAUNCH_LDS(-1, (k1d_kr_step<1>), dim3(B), dim3(T1), c->lds_bytes, c->P, n, c->h, c->lvl, rows, G, (const long long *)K.x.stop,
+                       (const double *)c->kr_X, c->scratch);
+        else
+            LAUNCH_LDS(-1, (k1d_kr_step<0>), dim3(B), dim3(T1), c->lds_bytes, c->P, n, c->h, c->lvl, rows, G, (const long long *)K.x.stop,
+                       (const double *)c->kr_X, c->scratch);
+        // w = H q_j in kr_W; classical Gram-Schmidt twice against q_first .. q_j, the passes reading w through the mask
+        const int first = reorth ? 0 : std::max(j - 1, 0), nv = j + 1 - first;
+        LAUNCH((k1d_kr_pass<0>), kgrid, dim3(KR1_T), K, first, nv, c->kr_W, (const double *)nullptr, part);
+        LAUNCH(k1d_kr_fin, dim3(B), dim3(KR1_T), K.x, (const double *)part, nch, S, 2, nv, j, k);
+        LAUNCH((k1d_kr_pass<1>), kgrid, dim3(KR1_T), K, first, nv, c->kr_W, (const double *)K.x.coef1, part);
+        LAUNCH(k1d_kr_fin, dim3(B), dim3(KR1_T), K.x, (const double *)part, nch, S, 3, nv, j, k);
+        LAUNCH((k1d_kr_pass<2>), kgrid, dim3(KR1_T), K, first, nv, c->kr_W, (const double *)K.x.coef2, part);
+        LAUNCH(k1d_kr_fin, dim3(B), dim3(KR1_T), K.x, (const double *)part, nch, S, 4, nv, j, k);
+        LAUNCH(k1d_kr_next, kgrid, dim3(KR1_T), K, (const double *)c->kr_W, slot_of(j + 1));
+    }
+    HIPCHK(hipEventRecord(c->ev1, c->stream));
+    std::vector<long long> steps(B);
+    HIPCHK(hipMemcpyAsync(alpha_out, K.x.alpha, sizeof(double) * B * k, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(beta_out, K.x.beta, sizeof(double) * B * k, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(steps.data(), K.x.steps, sizeof(long long) * B, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));                        // the second look
+    int smin = (int)steps[0], smax = 0;
+    int64_t solves = 0;
+    for (int b = 0; b < B; ++b) {
+        steps_out[b] = (int32_t)steps[b];
+        n_free_out[b] = (int64_t)look[2 * b];
+        smin = std::min(smin, (int)steps[b]);
+        smax = std::max(smax, (int)steps[b]);
+        solves += c->kr_nocache ? 3 * (int64_t)M * steps[b] : (int64_t)M * (2 * steps[b] + 1);
+    }
+    if (stats) {
+        float ms = 0;
+        hipEventElapsedTime(&ms, c->ev0, c->ev1);
+        memset(stats, 0, sizeof(*stats));
+        stats->linear_solves = solves;
+        stats->launches = 1 + 8 * (int64_t)k;
+        stats->host_syncs = 2;
+        stats->seconds = ms * 1e-3;
+    }
+    c->kr_valid = true;
+    c->kr_rows = rows;
+    c->kr_run_slots = slots;
+    c->kr_min_steps = smin;
+    c->kr_window = reorth ? INT32_MAX : (smax <= 2 ? 3 : 0);        // three resident vectors: q_0 is gone once q_3 is stored
+    return 0;
+}
+
+extern "C" int vch1d_krylov_vector(vch1d_ctx *c, const double *coef, int m, double *out) {
+    CTXCHK(c);
+    ARGCHK(coef && out, "NULL coef or out");
+    ARGCHK(m >= 1, "m must be >= 1");
+    if (!c->kr_valid || !c->kr_Q)
+        return vch_fail(VCH_ERR_STATE, "vch1d_krylov_vector: no resident basis (call vch1d_hess_lanczos first)");
+    if (m > c->kr_window)
+        return vch_fail(VCH_ERR_STATE, "vch1d_krylov_vector: m = %d exceeds the %d vectors a run without reorthogonalisation still holds",
+                        m, c->kr_window);
+    ARGCHK(m <= c->kr_min_steps + 1, "m exceeds the smallest step count of the batch plus one");
+    const int B = c->B, S = c->kr_slots, rows = c->kr_rows;
+    const Kr1Layout L = kr1_layout(c, c->kr_slots, c->kr_kcap);
+    const Kr1Args K = kr1_args(c, L, rows, c->kr_run_slots, 0);
+    double *ucoef = c->kr_sc + L.ucoef;
+    HIPCHK(hipMemcpy2DAsync(ucoef, sizeof(double) * S, coef, sizeof(double) * m, sizeof(double) * m, (size_t)B, hipMemcpyHostToDevice,
+                            c->stream));
+    LAUNCH(k1d_kr_lincomb, dim3(kr1_chunks(c, rows), B), dim3(KR1_T), K, m, (const double *)ucoef, c->kr_W);
+    return down_hist(c, out, c->kr_W, rows);
 }

@@ -1002,3 +1002,401 @@ __global__ __launch_bounds__(T1) void k1d_energy(int n, double c1, double c2, do
     }
 }
 
+// ---------------------------------------------------------------------------------
+// Device-resident Lanczos on the reduced Hessian P H P (vch1d_hess_lanczos).  Every vector is a history
+// [B][max_steps+2][n]; the basis is a ring of `nslots` of them, vector i sits in slot i % nslots.
+//
+// The sequential part stays one persistent workgroup per trajectory, on the planes and with the reductions of k1d_hessvec:
+//   k1d_kr_setup   the free set and its size, q_0 = P q0 / ||P q0||, and the gradient sweep of k1d_hessvec<1> once, whose
+//                  yp of every step goes to row k + 2 of one further history X (all the second sweep needs of the first)
+//   k1d_kr_step    the order-1 tangent march of q_j (v_k, mean_k) and the second transposed sweep alone, yp read from X:
+//                  w = H q_j, 2 M solves.  NOCACHE repeats the gradient sweep in lockstep (3 M solves); the product
+//                  yp v_k is the same expression on the same numbers, so both variants give the same bits.
+// The recurrence is streaming work over (j + 1) histories and runs on a wide grid, (chunks of KR1_CHUNK nodes, B): the
+// passes k1d_kr_pass<MODE> write one partial per workgroup and basis vector into [B][chunks][S], k1d_kr_fin (one workgroup
+// per trajectory) sums them in a fixed order.  No atomics: a trajectory's scalars do not depend on the batch.  The stop
+// state lives in device cells: every kernel of a stopped trajectory returns at once, so the host enqueues k steps back to
+// back and never looks between them.
+// ---------------------------------------------------------------------------------
+constexpr int KR1_T = 256;            // threads of a streaming workgroup
+constexpr int KR1_CHUNK = 4096;       // nodes of a trajectory's history per streaming workgroup
+constexpr int KR1_GROUP = 8;          // basis vectors a pass holds accumulators for at a time
+constexpr int KR1_PER = KR1_CHUNK / KR1_T;      // nodes per thread
+struct Kr1Cells {
+    double *coef1, *coef2;            // [B][S] coefficients of the two Gram-Schmidt rounds
+    double *alpha, *beta;             // [B][k]
+    double *look;                     // [B][2] what the host reads after the set-up: n_free, ||P q0||
+    double *scal;                     // [B] the divisor of the next k1d_kr_next
+    double *amax;                     // [B] max_i |alpha_i| so far
+    long long *lim, *stop, *steps;    // [B] min(k, n_free); 0 running, 1 last step with a valid q_{j+1}, 2 without, 3 over; steps taken
+};
+struct Kr1Args {
+    double *Q;                        // the basis
+    long slot_stride, hs;             // doubles between two slots / two trajectories
+    long tot;                         // nodes of a trajectory's vector (rows * n)
+    int nslots, S;                    // slots of the ring; stride of a partial and of a coefficient row
+    unsigned char *mask;              // [B or 1][hs] bytes, non-zero = free
+    long mask_s;                      // bytes between two trajectories' masks (0: one for the batch)
+    Kr1Cells x;
+};
+__device__ __forceinline__ double *kr1_slot(const Kr1Args &a, int i) { return a.Q + (long)(i % a.nslots) * a.slot_stride; }
+
+// Step k of the gradient sweep of k1d_hessvec on the planes (lphi, lmu, lw, rv, yp, ym) = q .. q + 5 n, in two halves
+// around the caller's use of yp: the solve, and the multipliers of the step before.  G is not accumulated.
+struct Kr1Base {
+    const double *ph, *pq, *pt;       // this trajectory's base point
+    double b1, b2;
+};
+__device__ __forceinline__ void kr1_grad_solve(const Phys1 &P, int n, double a, int lvl, const Hv1Args &G, const Kr1Base &T,
+                                               int k, int M, double *q, double *lds, double *sk) {
+    const int tid = threadIdx.x;
+    double *lphi = q, *lmu = q + n, *rv = q + 3 * n, *yp = q + 4 * n, *ym = q + 5 * n;
+    const long o = (long)(k + 2) * n;
+    const double *ps = T.ph + o;
+    const double wb = G.wt[k + 2] * T.b1;
+    const bool term = k == M - 1;
+    double S[1] = {0.0};
+    for (int i = tid; i < n; i += T1) {
+        const double w = G.wx[i], p = ps[i];
+        double l = lphi[i] + wb * (w * (p - (T.pq ? T.pq[o + i] : 0.0)));
+        if (term) l += T.b2 * (w * (p - (T.pt ? T.pt[i] : 0.0)));
+        lphi[i] = l;
+        S[0] += l;
+    }
+    block_sums<1>(S, sk);
+    for (int i = tid; i < n; i += T1) rv[i] = lphi[i] - G.wx[i] * (S[0] / P.Lx);
+    __syncthreads();
+    SysArgs A{ps, rv, lmu, G.dts[k], a, P.tau, P.c1, P.c2, P.kappa, n};
+    cr_solve<2>(A, lvl, lds, yp, ym);
+}
+__device__ __forceinline__ void kr1_grad_update(const Phys1 &P, int n, double a, const Hv1Args &G, int k, double *q,
+                                                double *keep /* row k + 2 of X or NULL */) {
+    double *lphi = q, *lmu = q + n, *lw = q + 2 * n, *yp = q + 4 * n, *ym = q + 5 * n;
+    const double dt = G.dts[k], gdt = P.gamma / dt, al = (gdt - 0.5) / (gdt + 0.5), kd = P.tau / dt + 2.0 * P.c2;
+    for (int i = threadIdx.x; i < n; i += T1) {
+        const double y = yp[i], ldw = 0.5 * y + lw[i];
+        if (keep) keep[i] = y;
+        lphi[i] = kd * y + 0.5 * P.kappa * lap1t(yp, i, n, a) + ym[i] / dt;
+        lmu[i] = 0.5 * y + 0.5 * lap1t(ym, i, n, a);
+        lw[i] = 0.5 * y + al * ldw;
+    }
+}
+
+// grid = B workgroups.  The start vector is in slot 0 on entry; box [B][2] = {u_min, u_max}.  A trajectory whose free set is
+// empty, or whose start vector vanishes on it (or is not finite), gets stop = 3 and nothing else: the host reads look.
+__global__ __launch_bounds__(T1) void k1d_kr_setup(Phys1 P, int n, double h, int lvl, int rows, Hv1Args G, Kr1Args K,
+                                                   const double *__restrict__ box, double tol, int build, int kmax, int sweep,
+                                                   double *X, double *scratch) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    __shared__ double sk[2 * (T1 / 64)];
+    const int b = blockIdx.x, tid = threadIdx.x, M = rows - 2;
+    const double a = 1.0 / (h * h);
+    const double *uu = G.u ? G.u + b * G.u_s : nullptr;
+    unsigned char *mk = K.mask + b * K.mask_s;
+    double *q0 = K.Q + b * K.hs;
+    const double lo = box[2 * b] + tol, hi = box[2 * b + 1] - tol;
+    double S[2] = {0.0, 0.0};
+    for (long i = tid; i < K.tot; i += T1) {
+        bool m;
+        if (build) {
+            const double v = uu ? uu[i] : 0.0;
+            m = v > lo && v < hi && fabs(v) > tol;
+            mk[i] = m ? 1 : 0;
+        } else {
+            m = mk[i] != 0;
+        }
+        const double v = m ? q0[i] : 0.0;
+        q0[i] = v;
+        S[0] += m ? 1.0 : 0.0;              // exact in a double
+        S[1] += v * v;
+    }
+    block_sums<2>(S, sk);
+    const double nrm = sqrt(S[1]);
+    const bool bad = S[0] < 1.0 || !(nrm > 0.0) || !isfinite(nrm);
+    if (tid == 0) {
+        K.x.look[2 * b] = S[0];
+        K.x.look[2 * b + 1] = nrm;
+        K.x.lim[b] = min((long long)kmax, (long long)S[0]);
+        K.x.stop[b] = bad ? 3 : 0;
+        K.x.steps[b] = 0;
+        K.x.amax[b] = 0.0;
+    }
+    if (bad) return;                        // uniform over the workgroup
+    for (long i = tid; i < K.tot; i += T1) q0[i] = q0[i] / nrm;
+    if (!sweep) return;
+    double *q = scratch + (long)b * NSCR1 * n;
+    const Kr1Base T{G.phi + b * G.phi_s, G.pq ? G.pq + b * G.pq_s : nullptr, G.pt ? G.pt + b * G.pt_s : nullptr, G.wts[3 * b],
+                    G.wts[3 * b + 1]};
+    for (int i = tid; i < n; i += T1) q[i] = q[n + i] = q[2 * n + i] = 0.0;
+    __syncthreads();
+    for (int k = M - 1; k >= 0; --k) {
+        kr1_grad_solve(P, n, a, lvl, G, T, k, M, q, lds, sk);
+        kr1_grad_update(P, n, a, G, k, q, X + b * K.hs + (long)(k + 2) * n);
+        __syncthreads();
+    }
+}
+
+// One Lanczos step's sequential part: G.hd = q_j (a basis slot), G.hv = w, G.v, G.mean the tangent's history; grid = B.
+template <int NOCACHE>
+__global__ __launch_bounds__(T1) void k1d_kr_step(Phys1 P, int n, double h, int lvl, int rows, Hv1Args G,
+                                                  const long long *__restrict__ stop, const double *X, double *scratch) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    __shared__ double sk[2 * (T1 / 64)];
+    const int b = blockIdx.x, tid = threadIdx.x, M = rows - 2;
+    if (stop[b]) return;                    // uniform over the workgroup
+    const double a = 1.0 / (h * h);
+    double *q = scratch + (long)b * NSCR1 * n;
+    double *yp = q + 4 * n;
+    double *Lphi = q + 6 * n, *Lmu = q + 7 * n, *Lw = q + 8 * n, *Rv = q + 9 * n, *Yp = q + 10 * n, *Ym = q + 11 * n;
+    const Kr1Base T{G.phi + b * G.phi_s, G.pq ? G.pq + b * G.pq_s : nullptr, G.pt ? G.pt + b * G.pt_s : nullptr, G.wts[3 * b],
+                    G.wts[3 * b + 1]};
+    const double *ph = T.ph;
+    const double *hd = G.hd + b * G.hs;
+    const double *xb = X + b * G.hs;
+    double *hv = G.hv + b * G.hs, *vb = G.v + b * G.hs, *mean = G.mean + (long)b * rows;
+    const double b3 = G.wts[3 * b + 2];
+    for (int row = 0; row < rows; ++row) {
+        const long o = (long)row * n;
+        const double wr = G.wt[row];
+        for (int i = tid; i < n; i += T1) {
+            const double w = b3 * (wr * G.wx[i]);
+            hv[o + i] = w * hd[o + i];
+        }
+    }
+    {
+        // the order-1 tangent march of k1d_hessvec<2>, on the planes the second sweep takes over afterwards
+        double *dphi = Lphi, *dmu = Lmu, *dw = Lw, *rp = Rv, *rm = Yp, *nphi = Ym, *nmu = q + 12 * n;
+        for (int i = tid; i < n; i += T1) dphi[i] = dmu[i] = dw[i] = 0.0;
+        __syncthreads();
+        for (int s = 0; s < M; ++s) {
+            const double dt = G.dts[s], gdt = P.gamma / dt;
+            const double *ps = ph + (long)(s + 2) * n;
+            const double *h0 = hd + (long)s * n, *h1 = h0 + n;
+            for (int i = tid; i < n; i += T1) {
+                const double wo = dw[i], wn = ((gdt - 0.5) * wo + 0.5 * (h1[i] + h0[i])) / (gdt + 0.5);
+                const double d = dphi[i];
+                rp[i] = (P.tau / dt) * d + 0.5 * P.kappa * lap1(dphi, i, n, a) + 2.0 * P.c2 * d + 0.5 * dmu[i] + 0.5 * (wn + wo);
+                rm[i] = d / dt + 0.5 * lap1(dmu, i, n, a);
+                dw[i] = wn;
+            }
+            __syncthreads();
+            SysArgs A{ps, rp, rm, dt, a, P.tau, P.c1, P.c2, P.kappa, n};
+            cr_solve<0>(A, lvl, lds, nphi, nmu);
+            double ms = 0.0;
+            for (int i = tid; i < n; i += T1) ms += ((i == 0 || i == n - 1) ? 0.5 : 1.0) * h * nphi[i];
+            const double m1 = block_red<0>(ms, sk) / P.Lx;
+            for (int i = tid; i < n; i += T1) {
+                const double v = nphi[i];
+                vb[(long)(s + 2) * n + i] = v;
+                dphi[i] = v - m1;
+                dmu[i] = nmu[i];
+            }
+            if (tid == 0) mean[s] = m1;
+            __syncthreads();
+        }
+    }
+    for (int i = tid; i < n; i += T1) {
+        Lphi[i] = Lmu[i] = Lw[i] = 0.0;
+        if (NOCACHE) q[i] = q[n + i] = q[2 * n + i] = 0.0;
+    }
+    __syncthreads();
+    for (int k = M - 1; k >= 0; --k) {
+        const double dt = G.dts[k], gdt = P.gamma / dt, al = (gdt - 0.5) / (gdt + 0.5), be = 0.5 / (gdt + 0.5);
+        const long o = (long)(k + 2) * n;
+        const double *ps = ph + o;
+        const double wb = G.wt[k + 2] * T.b1, mk = mean[k];
+        const bool term = k == M - 1;
+        if (NOCACHE) kr1_grad_solve(P, n, a, lvl, G, T, k, M, q, lds, sk);
+        const double *ypk = NOCACHE ? yp : xb + o;
+        double S[1] = {0.0};
+        for (int i = tid; i < n; i += T1) {
+            const double d = vb[o + i] - mk;
+            double L = Lphi[i] + wb * (G.wx[i] * d);
+            if (term) L += T.b2 * (G.wx[i] * d);
+            Lphi[i] = L;
+            S[0] += L;
+        }
+        block_sums<1>(S, sk);
+        for (int i = tid; i < n; i += T1) {
+            const double p = ps[i], om = 1.0 - p * p;
+            Rv[i] = (Lphi[i] - G.wx[i] * (S[0] / P.Lx)) - P.c1 * (4.0 * p / (om * om)) * (ypk[i] * vb[o + i]);
+        }
+        __syncthreads();
+        SysArgs A2{ps, Rv, Lmu, dt, a, P.tau, P.c1, P.c2, P.kappa, n};
+        cr_solve<2>(A2, lvl, lds, Yp, Ym);
+        const double kd = P.tau / dt + 2.0 * P.c2;
+        for (int i = tid; i < n; i += T1) {
+            const double Y = Yp[i], Ldw = 0.5 * Y + Lw[i];
+            hv[(long)k * n + i] += be * Ldw;
+            hv[(long)(k + 1) * n + i] += be * Ldw;
+            Lphi[i] = kd * Y + 0.5 * P.kappa * lap1t(Yp, i, n, a) + Ym[i] / dt;
+            Lmu[i] = 0.5 * Y + 0.5 * lap1t(Ym, i, n, a);
+            Lw[i] = 0.5 * Y + al * Ldw;
+        }
+        if (NOCACHE) kr1_grad_update(P, n, a, G, k, q, nullptr);
+        __syncthreads();
+    }
+}
+
+// One pass of the Gram-Schmidt step over w (in place) against q_first .. q_{first+nv-1}; grid = (chunks, B):
+//   MODE 0   partials i = sum q_i (P w)                                            (w is read through the mask, not written)
+//   MODE 1   w := P w - sum_i coef[b][i] q_i, then partials i = sum q_i w          (round 1's subtraction, round 2's products)
+//   MODE 2   w := w - sum_i coef[b][i] q_i, partial 0 = sum w^2                    (round 2's subtraction, the norm)
+// Masked-off nodes of every q_i are exact zeros, so w leaves MODE 1 with exact zeros there.  A thread keeps its
+// KR1_PER nodes of w in registers across the basis vectors: w is read once and written once per pass.
+template <int MODE>
+__global__ __launch_bounds__(KR1_T) void k1d_kr_pass(Kr1Args a, int first, int nv, double *w, const double *__restrict__ coef,
+                                                     double *__restrict__ part) {
+    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (a.x.stop[b]) return;                // uniform over the workgroup
+    __shared__ double sred[KR1_GROUP * (KR1_T / 64)];
+    const long hb = b * a.hs, i0 = (long)blockIdx.x * KR1_CHUNK + tid, i1 = min((long)(blockIdx.x + 1) * KR1_CHUNK, a.tot);
+    const unsigned char *mk = a.mask + b * a.mask_s;
+    double *wb = w + hb;
+    double *my = part + ((long)b * gridDim.x + blockIdx.x) * a.S;
+    double v[KR1_PER];
+#pragma unroll
+    for (int t = 0; t < KR1_PER; ++t) {
+        const long i = i0 + t * KR1_T;
+        v[t] = i < i1 ? wb[i] : 0.0;
+        if (MODE != 2) v[t] = (i < i1 && mk[i]) ? v[t] : 0.0;
+    }
+    if (MODE != 0) {
+        const double *cf = coef + (long)b * a.S;
+        for (int j = 0; j < nv; ++j) {
+            const double cj = cf[j];
+            const double *qj = kr1_slot(a, first + j) + hb;
+#pragma unroll
+            for (int t = 0; t < KR1_PER; ++t) {
+                const long i = i0 + t * KR1_T;
+                if (i < i1) v[t] -= cj * qj[i];
+            }
+        }
+        double nrm = 0.0;
+#pragma unroll
+        for (int t = 0; t < KR1_PER; ++t) {
+            const long i = i0 + t * KR1_T;
+            if (i < i1) {
+                wb[i] = v[t];
+                nrm += v[t] * v[t];
+            }
+        }
+        if (MODE == 2) {
+            nrm = wsum1(nrm);
+            if (lane == 0) sred[wv] = nrm;
+            __syncthreads();
+            if (tid == 0) my[0] = (sred[0] + sred[1]) + (sred[2] + sred[3]);
+            return;
+        }
+    }
+    for (int g0 = 0; g0 < nv; g0 += KR1_GROUP) {
+        double acc[KR1_GROUP];
+        const double *q[KR1_GROUP];
+#pragma unroll
+        for (int j = 0; j < KR1_GROUP; ++j) {
+            acc[j] = 0.0;
+            q[j] = kr1_slot(a, first + min(g0 + j, nv - 1)) + hb;     // past the end: the last vector again, its sum is not stored
+        }
+#pragma unroll
+        for (int t = 0; t < KR1_PER; ++t) {
+            const long i = i0 + t * KR1_T;
+            if (i < i1) {
+#pragma unroll
+                for (int j = 0; j < KR1_GROUP; ++j) acc[j] += q[j][i] * v[t];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < KR1_GROUP; ++j) {
+            const double s = wsum1(acc[j]);
+            if (lane == 0) sred[j * (KR1_T / 64) + wv] = s;
+        }
+        __syncthreads();
+        if (tid < KR1_GROUP && g0 + tid < nv) my[g0 + tid] = (sred[tid * 4] + sred[tid * 4 + 1]) + (sred[tid * 4 + 2] + sred[tid * 4 + 3]);
+        __syncthreads();
+    }
+}
+static_assert(KR1_T / 64 == 4, "the passes add four wave sums");
+
+// q_{j+1} = w / beta_j into its basis slot, by the trajectory's stop cell: 0, 1 the quotient; 2 (no valid q_{j+1}) zeros;
+// 3 nothing.  The next step reads its direction from the slot.
+__global__ __launch_bounds__(KR1_T) void k1d_kr_next(Kr1Args a, const double *__restrict__ w, double *__restrict__ slot) {
+    const int b = blockIdx.y;
+    const long long st = a.x.stop[b];
+    if (st == 3) return;
+    const double s = a.x.scal[b];
+    const long hb = b * a.hs, i0 = (long)blockIdx.x * KR1_CHUNK, i1 = min(i0 + (long)KR1_CHUNK, a.tot);
+    for (long i = i0 + threadIdx.x; i < i1; i += KR1_T) slot[hb + i] = st == 2 ? 0.0 : w[hb + i] / s;
+}
+
+// out = sum_{i<nv} coef[b][i] q_i  (vch1d_krylov_vector)
+__global__ __launch_bounds__(KR1_T) void k1d_kr_lincomb(Kr1Args a, int nv, const double *__restrict__ coef, double *__restrict__ out) {
+    const int b = blockIdx.y;
+    const double *cf = coef + (long)b * a.S;
+    const long hb = b * a.hs, i0 = (long)blockIdx.x * KR1_CHUNK + threadIdx.x, i1 = min((long)(blockIdx.x + 1) * KR1_CHUNK, a.tot);
+    double v[KR1_PER];
+#pragma unroll
+    for (int t = 0; t < KR1_PER; ++t) v[t] = 0.0;
+    for (int j = 0; j < nv; ++j) {
+        const double cj = cf[j];
+        const double *qj = kr1_slot(a, j) + hb;
+#pragma unroll
+        for (int t = 0; t < KR1_PER; ++t) {
+            const long i = i0 + t * KR1_T;
+            if (i < i1) v[t] += cj * qj[i];
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < KR1_PER; ++t) {
+        const long i = i0 + t * KR1_T;
+        if (i < i1) out[hb + i] = v[t];
+    }
+}
+
+// The scalars of a pass, one workgroup per trajectory: the nch partials of a slot summed in a fixed order (thread t takes
+// elements t, t + KR1_T, ... in turn, then a tree over the threads).
+__device__ __forceinline__ double kr1_sum(const double *__restrict__ part, int nch, int S, int slot, double *sh) {
+    double s = 0.0;
+    for (int e = threadIdx.x; e < nch; e += KR1_T) s += part[(long)e * S + slot];
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    for (int hh = KR1_T / 2; hh > 0; hh >>= 1) {
+        if ((int)threadIdx.x < hh) sh[threadIdx.x] += sh[threadIdx.x + hh];
+        __syncthreads();
+    }
+    const double r = sh[0];
+    __syncthreads();
+    return r;
+}
+// mode 2 / 3: the nv products of round 1 / 2 -> coef1 / coef2
+// mode 4: step j's norm -> beta_j, alpha_j = coef1 + coef2 on q_j, the stop rules, the stop cell and the step count
+__global__ __launch_bounds__(KR1_T) void k1d_kr_fin(Kr1Cells x, const double *__restrict__ part, int nch, int S, int mode, int nv,
+                                                    int j, int k) {
+    __shared__ double sh[KR1_T];
+    const int b = blockIdx.x;
+    const double *p = part + (long)b * nch * S;
+    if (x.stop[b]) {                        // uniform: stopped at an earlier step
+        if (threadIdx.x == 0 && mode == 4) x.stop[b] = 3;
+        return;
+    }
+    if (mode == 2 || mode == 3) {
+        double *cf = (mode == 2 ? x.coef1 : x.coef2) + (long)b * S;
+        for (int i = 0; i < nv; ++i) {
+            const double s = kr1_sum(p, nch, S, i, sh);
+            if (threadIdx.x == 0) cf[i] = s;
+        }
+        return;
+    }
+    const double beta = sqrt(kr1_sum(p, nch, S, 0, sh));
+    if (threadIdx.x != 0) return;
+    const double alpha = x.coef1[(long)b * S + nv - 1] + x.coef2[(long)b * S + nv - 1];
+    const double am = fmax(x.amax[b], fabs(alpha));
+    x.amax[b] = am;
+    x.alpha[(long)b * k + j] = alpha;
+    x.beta[(long)b * k + j] = beta;
+    x.steps[b] = j + 1;
+    const bool broke = !isfinite(beta) || beta <= 1e-14 * am;          // an invariant subspace, or nothing to go on with
+    const long long lim = x.lim[b];
+    // n_free steps span the free set: no q_{j+1}
+    x.stop[b] = (broke || j + 1 >= (long long)x.look[2 * b]) ? 2 : (j + 1 >= lim ? 1 : 0);
+    x.scal[b] = beta;
+}

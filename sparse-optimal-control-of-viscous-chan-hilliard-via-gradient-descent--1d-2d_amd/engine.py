@@ -871,3 +871,44 @@ class Engine1D:
         Euclidean, see hessvec; on the run-time physical parameters, unlike the hand-derived adjoint of backward()."""
         return self.hessvec(None, t_hist, opt, phi_hist=phi_hist, u=u, phi_Q=phi_Q, phi_T=phi_T, dt=dt, x=x, order=1,
                             shared_base=shared_base)["grad"]
+
+    def hess_lanczos(self, q0, k, t_hist, opt, phi_hist=None, u=None, phi_Q=None, phi_T=None, dt=None, x=None, mask=None,
+                     tol=0.0, reorth=True, shared_base=False):
+        """Lanczos on the reduced Hessian P H P with the basis, the free set and the recurrence on the device
+        (vch1d_hess_lanczos); base point and arguments as for hessvec.  q0: (B, rows, N+1) start vectors.  mask: the free
+        set as booleans / bytes, (B, rows, N+1), or (rows, N+1) with shared_base=True; None: built on the device from the
+        base control `u` and every trajectory's own u_min, u_max of `opt` with `tol` (<= 0: 1e-8).  reorth: full
+        reorthogonalisation (k + 1 resident vectors) or the three-term recurrence (3 resident vectors).
+        Returns dict(alpha, beta: (B, k), NaN beyond steps; steps, n_free: [B]; stats)."""
+        t_hist, rows, nb, keep, dt, x, arr = self._base_point(t_hist, phi_hist, u, phi_Q, phi_T, dt, x, opt, shared_base)
+        k = int(k)
+        q0 = None if q0 is None else self._hist(q0, rows, "q0")
+        if mask is not None:
+            mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+            if mask.shape == (rows, self.n) and nb == 1:
+                mask = mask.reshape((1,) + mask.shape)
+            if mask.shape != (nb, rows, self.n):
+                raise ValueError(f"mask must have shape ({nb}, {rows}, {self.n}), got {mask.shape}")
+        kk = max(k, 1)
+        alpha, beta = np.full((self.B, kk), np.nan), np.full((self.B, kk), np.nan)
+        steps, n_free = np.zeros(self.B, dtype=np.int32), np.zeros(self.B, dtype=np.int64)
+        st = Stats()
+        check(self.lib.vch1d_hess_lanczos(self.ctx, keep[0][1], keep[1][1], nb, rows, _dp(dt), _dp(t_hist), _dp(x), keep[2][1],
+                                          keep[3][1], arr, len(arr),
+                                          None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint8)), float(tol),
+                                          _dp(q0), k, int(reorth), _dp(alpha), _dp(beta), steps.ctypes.data_as(_lib._I32),
+                                          n_free.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(st)))
+        self._kr_rows = rows
+        return dict(alpha=alpha, beta=beta, steps=steps, n_free=n_free, stats=st.as_dict())
+
+    def krylov_vector(self, coef):
+        """(B, rows, N+1): sum_j coef[b][j] q_j from the basis the last hess_lanczos left resident (vch1d_krylov_vector).
+        coef: (B, m), or (m,) with batch 1."""
+        coef = np.ascontiguousarray(coef, dtype=np.float64)
+        if coef.ndim == 1 and self.B == 1:
+            coef = coef.reshape(1, -1)
+        if coef.ndim != 2 or coef.shape[0] != self.B:
+            raise ValueError(f"coef must have shape ({self.B}, m), got {coef.shape}")
+        out = np.empty((self.B, getattr(self, "_kr_rows", 1), self.n))
+        check(self.lib.vch1d_krylov_vector(self.ctx, _dp(coef), int(coef.shape[1]), _dp(out)))
+        return out

@@ -1,0 +1,527 @@
+"""vch1d_hess_lanczos / vch1d_krylov_vector on the GPU: Lanczos on the reduced Hessian P H P of the 1D engine with the basis, the
+free set and the recurrence in device memory, against eigvalsh of dense masked Hessians assembled from
+Engine1D.hessvec, against the Lanczos relation with Engine1D.hessvec on a second context, and against the NumPy restatement
+of the iteration (tests/_lanczos_ref.py, pinned by test_lanczos_ref_cpu.py).  The matrices come from the existing, already
+pinned entry point: the Lanczos path is compared with hessvec of the same engine, not with itself.
+
+Problems (max_steps = 8, so a trajectory's stride in a history is 10 rows and not its own row count):
+    driver   driver_problem() of _tangent_ref_1d.py: N = 32, 5 steps, 7 rows, 231 nodes, box [-1, 1], 172 free nodes; depth 0,
+             one streaming chunk; the free set is built on the device; the dense symmetrised Hessian from one hessvec call of
+             batch 231 with a shared base
+    n33_off  odd N, off-default physics, ragged last step (depth 0), trajectory 0 of test_gpu_second_order_1d.py's case
+    n1030    depth 1, 3 steps, 5 rows of 1031 nodes: two streaming chunks of 4096 nodes, the last ragged
+    n2051    depth 2, 3 steps, 5 rows of 2052 nodes: three streaming chunks
+    The last three run with an uploaded mask of 12 nodes: i = 0, i = N and interior nodes in rows 0, 1, 2, 3 and the last
+    row, with one interior and one end node of the last row (its entries are b3 wt wx alone: two equal ones would end
+    Lanczos early); the 12 x 12 block comes from one hessvec call of batch 12.
+
+Tolerances, all relative to the largest eigenvalue of the masked matrix.  Where 10 n eps applies it is asserted as is:
+DRIVER_RITZ = 5.2e-13 of test_gpu_hessvec_1d.py (n = 231) for the driver spectrum, relation, orthogonality, stops, driver
+test and slack.  Three kinds are measured on the MI355X and asserted at 10 x the measured value (MEASURED / TOL below): the
+uploaded-mask spectra at depths 0, 1 and 2 and the CPU restatement; the assertion at import keeps each at or below the hv
+tolerance of its depth in test_gpu_hessvec_1d.TOL (7.0e-15, 6.3e-13, 9.0e-12): Lanczos on a 12-node block cannot
+legitimately be further from hessvec's block than hessvec is from the truth.
+    spectrum     driver, both extremes against eigvalsh: measured 2.09e-16 (bound 5.2e-13; 162 steps to an invariant subspace)
+                 n33_off / n1030 / n2051, all 12 Ritz values: measured 5.13e-16 / 1.06e-15 / 1.06e-15, asserted 10 x that
+    relation     max_j ||P H q_j - beta_{j-1} q_{j-1} - alpha_j q_j - beta_j q_{j+1}||_inf / lambda_max and ||Q^T Q - I||_max on
+                 the driver (k = 8): measured 3.92e-17 and 6.66e-16 (bound 5.2e-13)
+    step 0       alpha_0 against sum q_0 . hv of Engine1D.hessvec(q_0): n eps sum|terms| asserted (5.7e-20; measured: equal)
+    CPU          first 4 alpha, beta against tests/_lanczos_ref.py on the dense matrix: measured 2.09e-16, asserted 2.09e-15
+    stops        the three Ritz values of a free set of 3 nodes against eigvalsh of the 3 x 3 block: measured 1.53e-16
+    reorth = 0   every Ritz value within its own residual estimate |beta_m s_m| + 10 n eps lambda_max of an eigenvalue
+                 (k = 40 on the driver: the worst value lies 5.3e-16 lambda_max outside its estimate, inside the slack)"""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from oracle import vch1d_oracle as o
+from _lanczos_ref import lanczos, ritz
+from _tangent_ref_1d import DRIVER, driver_problem
+from test_gpu_forms import _env
+from test_gpu_hessvec_1d import DRIVER_RITZ, TOL as HV_TOL
+from test_gpu_second_order_1d import CASES, V, _engine, _problem  # noqa: F401  (V: fixture)
+
+pytestmark = pytest.mark.gpu
+
+EPS = np.finfo(np.float64).eps
+# measured on an MI355X (the MEASURE lines of this file), relative to lambda_max
+MEASURED = dict(n33_off_ritz=5.13e-16, n1030_ritz=1.06e-15, n2051_ritz=1.06e-15, cpu=2.09e-16)
+TOL = {k: 10 * v for k, v in MEASURED.items()}
+DEPTH = dict(n33_off_ritz=0, n1030_ritz=1, n2051_ritz=2, cpu=0)
+for _k, _v in TOL.items():
+    assert _v <= HV_TOL[DEPTH[_k]][1], (_k, _v)
+
+
+def _tile(a, nb):
+    return np.ascontiguousarray(np.broadcast_to(a, (nb,) + np.shape(a)))
+
+
+class Problem:
+    """One base point (grid, state history, control, targets) from which contexts of any batch are made."""
+
+    def __init__(self, V, P, t, dts, x, phi, u, opt):
+        self.V, self.P, self.t, self.dts, self.x, self.phi, self.u, self.opt = V, P, t, np.asarray(dts), x, phi, u, opt
+        self.M, self.shape = len(dts), u.shape
+        self.phi_T, self.phi_Q = o.build_targets(x, t, phi[0], P.Lx, P.T)
+
+    def context(self, nb):
+        return _engine(self.V, self.P, nb)
+
+    def kw(self, nb=0):
+        """Keyword arguments of hessvec / hess_lanczos: a shared base (nb = 0) or the base tiled nb times."""
+        base = dict(phi_hist=self.phi, u=self.u, phi_Q=self.phi_Q, phi_T=self.phi_T)
+        if nb:
+            base = {k: _tile(v, nb) for k, v in base.items()}
+        return dict(base, dt=self.dts, x=self.x, shared_base=not nb)
+
+    def lanczos(self, eng, q0, k, **kw):
+        args = self.kw()
+        args.update(kw)
+        return eng.hess_lanczos(q0, k, self.t, args.pop("opt", self.opt), **args)
+
+    def hessvec(self, H):
+        """H h for the directions H (nb, rows, N+1) on a context of their own."""
+        eng = self.context(len(H))
+        r = eng.hessvec(np.ascontiguousarray(H), self.t, self.opt, **self.kw())
+        eng.close()
+        return r["hv"]
+
+    def block(self, nodes):
+        """The symmetrised block of the Hessian on the flat node indices `nodes`: one hessvec call of batch len(nodes)."""
+        E = np.zeros((len(nodes), self.u.size))
+        E[np.arange(len(nodes)), nodes] = 1.0
+        hv = self.hessvec(E.reshape((len(nodes),) + self.shape)).reshape(len(nodes), -1)
+        A = hv[:, nodes]
+        return 0.5 * (A + A.T)
+
+
+def _q0(shape, seed):
+    return np.random.default_rng(seed).standard_normal(shape)
+
+
+def _mask_of(shape, nodes):
+    m = np.zeros(int(np.prod(shape)), dtype=bool)
+    m[nodes] = True
+    return m.reshape(shape)
+
+
+def _same(a, b, keys=("alpha", "beta", "steps", "n_free")):
+    for key in keys:
+        assert np.array_equal(a[key], b[key], equal_nan=True), key
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the problems
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def driver(V):
+    S1 = V.module("Vch_control_1D.second_order_conditions")
+    K1 = V.module("Vch_control_1D.config")
+    D = DRIVER
+    P, phi0, u_star, _ = driver_problem()
+    tg, dts = V.time_grid(P.T, P.dt_initial)
+    t = np.concatenate([[0.0], tg])
+    x = np.linspace(0.0, P.Lx, P.N + 1)
+    O = o.OptParams1D()
+    one = _engine(V, P, 1)
+    phi = one.forward(phi0, np.asarray(dts), u=u_star)[0]
+    one.close()
+    assert np.abs(phi).max() < 1.0 - o.DELTA_SEP - 0.1
+    opt = V.make_opt(b1=O.b1, b2=O.b2, b3=O.b3, kappa_sparsity=0.0, u_min=D["u_min"], u_max=D["u_max"])
+    pr = Problem(V, P, t, dts, x, phi, u_star, opt)
+    nd = u_star.size
+    Hd = pr.hessvec(np.eye(nd).reshape((nd,) + u_star.shape)).reshape(nd, nd).T
+    pr.Hm = 0.5 * (Hd + Hd.T)
+    pr.mask = S1.free_set(u_star, D["u_min"], D["u_max"])
+    pr.free = np.flatnonzero(pr.mask.ravel())
+    assert len(pr.free) == 172 and nd == 231 and pr.shape == (7, 33)
+    pr.ev = np.linalg.eigvalsh(pr.Hm[np.ix_(pr.free, pr.free)])
+    pr.cfg, pr.O, pr.S1 = K1.ForwardSolverConfig(N=P.N, T=P.T, dt_initial=P.dt_initial), O, S1
+    return pr
+
+
+@pytest.fixture(scope="module")
+def small(V):
+    """name -> the case's trajectory 0 with an uploaded mask of 12 nodes and the 12 x 12 block (made once, shared)."""
+    cache = {}
+
+    def get(name):
+        if name in cache:
+            return cache[name]
+        p = _problem(V, name)
+        P, N = p["P"], p["P"].N
+        one = _engine(V, P, 1)
+        phi = one.forward(p["phi0"][0], p["dts"], u=p["U"][0])[0]
+        one.close()
+        assert np.abs(phi).max() < 1.0 - o.DELTA_SEP - 0.1
+        pr = Problem(V, P, p["t"], p["dts"], p["x"], phi, p["U"][0], V.make_opt())
+        rows, n = pr.shape
+        last, mid = rows - 1, rows // 2
+        at = [(0, 0), (0, N // 3), (0, N), (1, 5), (1, N // 2), (1, N), (mid, 0), (mid, 2 * N // 3), (mid, N - 1),
+              (last - 1 if last - 1 > mid else 1, N // 5), (last, N // 4), (last, N)]
+        pr.free = np.array(sorted(set(r * n + i for r, i in at)))
+        assert len(pr.free) == 12 and sum(1 for r, _ in at if r == last) == 2
+        pr.mask = _mask_of(pr.shape, pr.free)
+        pr.A = pr.block(pr.free)
+        pr.ev = np.linalg.eigvalsh(pr.A)
+        pr.depth = p["depth"]
+        cache[name] = pr
+        return pr
+
+    return get
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 1. spectrum
+# ---------------------------------------------------------------------------------------------------------------------
+def test_driver_extremes_with_the_free_set_built_on_the_device(driver):
+    pr = driver
+    eng = pr.context(1)
+    R = pr.lanczos(eng, _q0(pr.shape, 1), 172)
+    eng.close()
+    assert R["n_free"][0] == 172 and R["steps"][0] <= 172
+    theta, _, _ = ritz(R["alpha"][0], R["beta"][0], R["steps"][0])
+    dev = max(abs(theta[0] - pr.ev[0]), abs(theta[-1] - pr.ev[-1])) / pr.ev[-1]
+    print(f"MEASURE driver: steps {R['steps'][0]} theta_min {theta[0]:.6e} eigvalsh {pr.ev[0]:.6e} theta_max {theta[-1]:.6e} "
+          f"eigvalsh {pr.ev[-1]:.6e} rel.dev {dev:.2e}; stats {R['stats']}")
+    assert dev < DRIVER_RITZ
+
+
+@pytest.mark.parametrize("name", ["n33_off", "n1030", "n2051"])
+def test_all_ritz_values_of_a_small_uploaded_free_set(small, name):
+    pr = small(name)
+    n = len(pr.free)
+    assert np.diff(pr.ev).min() > 0.0                                # 12 distinct eigenvalues
+    eng = pr.context(1)
+    R = pr.lanczos(eng, _q0(pr.shape, 2), n + 5, mask=pr.mask)
+    Q = np.stack([eng.krylov_vector(np.eye(1, j + 1, j))[0] for j in range(3)])
+    eng.close()
+    assert R["n_free"][0] == n and R["steps"][0] == n
+    assert np.isnan(R["alpha"][0, n:]).all() and np.isnan(R["beta"][0, n:]).all() and np.isfinite(R["alpha"][0, :n]).all()
+    assert not Q[:, ~pr.mask].any() and np.abs(Q).max() > 0          # the basis: masked-off nodes exact zeros
+    theta, _, _ = ritz(R["alpha"][0], R["beta"][0], n)
+    dev = np.abs(theta - pr.ev).max() / pr.ev[-1]
+    print(f"MEASURE {name} depth {pr.depth}: all {n} Ritz values against eigvalsh {dev:.2e}; spectrum {pr.ev[0]:.4e} .. "
+          f"{pr.ev[-1]:.4e}, smallest gap {np.diff(pr.ev).min() / pr.ev[-1]:.2e} of lambda_max")
+    assert dev < TOL[name + "_ritz"]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 2. Lanczos relation and basis, the step-0 identity
+# ---------------------------------------------------------------------------------------------------------------------
+def test_lanczos_relation_and_basis(driver):
+    pr, k = driver, 8
+    eng = pr.context(1)
+    R = pr.lanczos(eng, _q0(pr.shape, 3), k)
+    assert R["steps"][0] == k
+    Q = np.stack([eng.krylov_vector(np.eye(1, j + 1, j))[0] for j in range(k + 1)])
+    eng.close()
+    HQ = pr.hessvec(Q[:k])                                           # Engine1D.hessvec on a second context
+    a, b, lam = R["alpha"][0], R["beta"][0], pr.ev[-1]
+    assert not Q[:, ~pr.mask].any()                                  # masked-off nodes of every q_j are exact zeros
+    rel = 0.0
+    for j in range(k):
+        r = np.where(pr.mask, HQ[j], 0.0) - a[j] * Q[j] - b[j] * Q[j + 1] - (b[j - 1] * Q[j - 1] if j else 0.0)
+        rel = max(rel, np.abs(r).max() / lam)
+    Qf = Q.reshape(k + 1, -1)
+    orth = np.abs(Qf @ Qf.T - np.eye(k + 1)).max()
+    t0 = Q[0] * HQ[0]
+    ident = abs(a[0] - t0.sum()), Q[0].size * EPS * np.abs(t0).sum()
+    print(f"MEASURE driver k=8: relation {rel:.2e} orthogonality {orth:.2e} step-0 identity {ident[0]:.2e} (bound {ident[1]:.2e})")
+    assert rel < DRIVER_RITZ and orth < DRIVER_RITZ
+    assert ident[0] <= ident[1]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 3. against the CPU restatement
+# ---------------------------------------------------------------------------------------------------------------------
+def test_first_steps_agree_with_the_cpu_restatement(driver):
+    pr = driver
+    q0 = _q0(pr.shape, 4)
+    eng = pr.context(1)
+    R = pr.lanczos(eng, q0, 8)
+    eng.close()
+    ref = lanczos(lambda v: pr.Hm @ v, pr.mask, q0, 8)
+    lam = pr.ev[-1]
+    dev = max(np.abs(R["alpha"][0, :4] - ref["alpha"][:4]).max(), np.abs(R["beta"][0, :4] - ref["beta"][:4]).max()) / lam
+    print(f"MEASURE cpu restatement: first 4 alpha, beta {dev:.2e} of lambda_max")
+    assert dev < TOL["cpu"]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 4. a batch of three with different masks and boxes; the stops; the shared base
+# ---------------------------------------------------------------------------------------------------------------------
+def test_batch_of_three_equals_three_single_contexts_and_the_stops(driver):
+    pr, V, O = driver, driver.V, driver.O
+    sets = [pr.free[[4, 77, 150]], pr.free[[0, 20, 40, 90, 120, 160, 171]], pr.free]
+    masks = np.stack([_mask_of(pr.shape, s) for s in sets])
+    w = dict(b1=O.b1, b2=O.b2, b3=O.b3, kappa_sparsity=0.0)
+    opts = [V.make_opt(u_min=-1.0, u_max=1.0, **w), V.make_opt(u_min=-0.3, u_max=0.4, **w), V.make_opt(u_min=-2.0, u_max=2.0, **w)]
+    q0 = _q0((3,) + pr.shape, 5)
+    k = 12
+    eng = pr.context(3)
+    many = eng.hess_lanczos(q0, k, pr.t, opts, mask=masks, **pr.kw(3))
+    eng.close()
+    assert list(many["n_free"]) == [3, 7, 172] and list(many["steps"]) == [3, 7, 12]
+    for b in range(3):
+        eng = pr.context(1)
+        one = eng.hess_lanczos(q0[b], k, pr.t, opts[b], mask=masks[b], **pr.kw())
+        eng.close()
+        for key in ("alpha", "beta", "steps", "n_free"):
+            assert np.array_equal(one[key][0], many[key][b], equal_nan=True), (key, b)
+    a, bt = many["alpha"][0], many["beta"][0]
+    assert np.isnan(a[3:]).all() and np.isnan(bt[3:]).all() and np.isfinite(a[:3]).all() and np.isfinite(bt[:3]).all()
+    assert np.isnan(many["alpha"][1][7:]).all() and np.isfinite(many["alpha"][2]).all()
+    ev3 = np.linalg.eigvalsh(pr.Hm[np.ix_(sets[0], sets[0])])
+    theta, _, _ = ritz(a, bt, 3)
+    dev = np.abs(theta - ev3).max() / ev3[-1]
+    print(f"MEASURE stops: three Ritz values of n_free = 3 against eigvalsh {dev:.2e}")
+    assert dev < DRIVER_RITZ
+    # one shared base and three start vectors, the free sets built on the device from each trajectory's own box
+    eng = pr.context(3)
+    shared = eng.hess_lanczos(q0, 6, pr.t, opts, **pr.kw())
+    tiled = eng.hess_lanczos(q0, 6, pr.t, opts, **pr.kw(3))
+    eng.close()
+    _same(shared, tiled)
+    want = [int(pr.S1.free_set(pr.u, op.u_min, op.u_max).sum()) for op in opts]
+    assert list(shared["n_free"]) == want and want[0] == 172 and len(set(want)) == 3
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 5. the cached gradient sweep: bits, solve counts, looks
+# ---------------------------------------------------------------------------------------------------------------------
+def test_cached_sweep_has_the_bits_of_the_repeated_one_and_the_counts(driver):
+    pr = driver
+    q0, k, B = _q0((2,) + pr.shape, 6), 5, 2
+    eng = pr.context(B)
+    got = pr.lanczos(eng, q0, k)
+    short, longer = pr.lanczos(eng, q0, 2), pr.lanczos(eng, q0, 6)
+    eng.close()
+    with _env(VCH_KRYLOV_NOCACHE=1):
+        eng = pr.context(B)
+    ref = pr.lanczos(eng, q0, k)
+    eng.close()
+    _same(got, ref)
+    assert list(got["steps"]) == [k, k]
+    assert got["stats"]["linear_solves"] == B * pr.M * (2 * k + 1), got["stats"]
+    assert ref["stats"]["linear_solves"] == 3 * B * pr.M * k, ref["stats"]
+    assert got["stats"]["seconds"] > 0 and got["stats"]["launches"] > k
+    assert short["stats"]["host_syncs"] == longer["stats"]["host_syncs"] == 2          # no look between the steps
+    assert longer["stats"]["launches"] > short["stats"]["launches"]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 6. without reorthogonalisation
+# ---------------------------------------------------------------------------------------------------------------------
+def test_three_term_recurrence(driver):
+    pr, V = driver, driver.V
+    eng = pr.context(1)
+    R = pr.lanczos(eng, _q0(pr.shape, 7), 40, reorth=False)
+    assert R["steps"][0] == 40
+    with pytest.raises(V.VchError, match="-3"):          # q_0 is no longer held
+        eng.krylov_vector(np.ones((1, 1)))
+    eng.close()
+    theta, S, res = ritz(R["alpha"][0], R["beta"][0], 40)
+    slack = DRIVER_RITZ * pr.ev[-1]
+    worst = max(np.abs(pr.ev - th).min() - rs for th, rs in zip(theta, res))
+    print(f"MEASURE reorth=0 k=40: worst (distance to an eigenvalue - residual estimate) {worst / pr.ev[-1]:.2e} of lambda_max")
+    for th, rs in zip(theta, res):
+        assert np.abs(pr.ev - th).min() <= rs + slack, (th, rs)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 7. errors
+# ---------------------------------------------------------------------------------------------------------------------
+def test_errors_come_before_any_launch_and_data_errors_name_the_trajectory(driver):
+    pr, V = driver, driver.V
+    lib = V.load()
+    q0 = _q0((2,) + pr.shape, 8)
+    eng = pr.context(2)
+    first = pr.lanczos(eng, q0, 4)
+    e0 = np.eye(2, 5)                                    # q_0 of trajectory 0, q_1 of trajectory 1
+    basis = eng.krylov_vector(e0)
+    live = lib.vch_mem_live()
+    for bad in (dict(k=0), dict(k=-3), dict(q0=None), dict(reorth=2), dict(reorth=-1), dict(u=None),
+                dict(opt=[pr.opt, pr.opt, pr.opt]), dict(dt=-pr.dts)):
+        args = dict(q0=q0, k=4)
+        args.update(bad)
+        with pytest.raises(ValueError):
+            pr.lanczos(eng, **args)
+        assert lib.vch_mem_live() == live, bad
+        assert np.array_equal(eng.krylov_vector(e0), basis), bad             # the resident basis is as it was
+    with pytest.raises(V.VchError, match="-3"):                               # RESIDENT before pgd_init
+        pr.lanczos(eng, q0, 4, u=eng.RESIDENT)
+    assert np.array_equal(eng.krylov_vector(e0), basis)
+    # through the C ABI itself: outputs and stats untouched
+    D = C.POINTER(C.c_double)
+    dp = lambda a: None if a is None else a.ctypes.data_as(D)
+    al, be = np.full((2, 4), 7.0), np.full((2, 4), 7.0)
+    st, nf = np.full(2, 7, dtype=np.int32), np.full(2, 7, dtype=np.int64)
+    stats = V.module("_lib").Stats()
+    stats.launches = 77
+    last_error = V.module("_lib").last_error
+    arr = (type(pr.opt) * 1)(pr.opt)
+    rows = pr.shape[0]
+
+    def raw(u=pr.u, q=q0, k=4, reorth=1, rows=rows, n_base=1, al_=al):
+        return lib.vch1d_hess_lanczos(eng.ctx, dp(pr.phi), dp(u), n_base, rows, dp(pr.dts), dp(pr.t), dp(pr.x), dp(pr.phi_Q),
+                                      dp(pr.phi_T), arr, 1, None, 0.0, dp(q), k, reorth, dp(al_), dp(be),
+                                      st.ctypes.data_as(C.POINTER(C.c_int32)), nf.ctypes.data_as(C.POINTER(C.c_int64)),
+                                      C.byref(stats))
+
+    for kw, what in [(dict(k=0), "k = 0"), (dict(q=None), "NULL q0"), (dict(reorth=2), "reorth"), (dict(al_=None), "NULL alpha_out"),
+                     (dict(u=None), "no node is free"), (dict(rows=2), "rows"), (dict(n_base=3), "n_base")]:
+        assert raw(**kw) == -1, kw
+        assert what in last_error() and "vch1d_hess_lanczos" in last_error(), (what, last_error())
+    assert (al == 7.0).all() and (be == 7.0).all() and (st == 7).all() and (nf == 7).all() and stats.launches == 77
+    assert lib.vch_mem_live() == live and np.array_equal(eng.krylov_vector(e0), basis)
+    # data-dependent: an empty free set, a start vector that vanishes on the free set
+    masks = np.stack([pr.mask, np.zeros_like(pr.mask)])
+    with pytest.raises(ValueError, match="trajectory 1"):
+        eng.hess_lanczos(q0, 4, pr.t, pr.opt, mask=masks, **pr.kw(2))
+    with pytest.raises(V.VchError, match="-3"):          # the failed call left no basis
+        eng.krylov_vector(e0)
+    with pytest.raises(ValueError, match="trajectory 0"):
+        pr.lanczos(eng, q0, 4, opt=[V.make_opt(pr.opt, u_min=1.1, u_max=1.2), pr.opt])      # no node inside that box
+    qz = q0.copy()
+    qz[1][pr.mask] = 0.0
+    with pytest.raises(ValueError, match="trajectory 1"):
+        pr.lanczos(eng, qz, 4)
+    with pytest.raises(V.VchError, match="-3"):
+        eng.krylov_vector(e0)
+    good = pr.lanczos(eng, q0, 4)
+    with pytest.raises(ValueError):
+        eng.krylov_vector(np.ones((2, 6)))               # m above steps + 1
+    with pytest.raises(ValueError):
+        eng.krylov_vector(np.ones((2, 0)))
+    assert np.array_equal(eng.krylov_vector(e0), basis)
+    eng.close()
+    fresh = pr.context(2)
+    want = pr.lanczos(fresh, q0, 4)
+    fresh.close()
+    _same(good, want)
+    _same(first, want)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 8. memory
+# ---------------------------------------------------------------------------------------------------------------------
+def test_refused_allocations_and_the_balance(driver):
+    pr, V = driver, driver.V
+    lib = V.load()
+    q0 = _q0(pr.shape, 9)
+    base = lib.vch_mem_live()
+    eng = pr.context(1)
+    live0 = lib.vch_mem_live()
+    want = pr.lanczos(eng, q0, 6)
+    m = lib.vch_mem_live() - live0
+    again = pr.lanczos(eng, q0, 6)
+    assert lib.vch_mem_live() - live0 == m                # the second invocation allocates nothing
+    bigger = pr.lanczos(eng, q0, 9)
+    assert lib.vch_mem_live() - live0 == m                # a larger basis replaces the storage
+    eng.close()
+    assert lib.vch_mem_live() == base
+    print("lazy requests of the first call:", m)
+    assert m >= 6
+    _same(again, want)
+    assert np.array_equal(bigger["alpha"][:, :6], want["alpha"]) and np.array_equal(bigger["beta"][:, :6], want["beta"])
+    for i in range(m):
+        eng = pr.context(1)
+        live0 = lib.vch_mem_live()
+        lib.vch_mem_refuse_after(i)
+        try:
+            with pytest.raises(V.VchError, match="-2|-4") as err:
+                pr.lanczos(eng, q0, 6)
+        finally:
+            lib.vch_mem_refuse_after(-1)
+        assert lib.vch_mem_live() == live0, (i, lib.vch_mem_live() - live0)
+        if "Krylov storage" in str(err.value):
+            assert "-4" in str(err.value) and "bytes" in str(err.value)
+        with pytest.raises(V.VchError, match="-3"):
+            eng.krylov_vector(np.ones((1, 1)))
+        got = pr.lanczos(eng, q0, 6)
+        assert lib.vch_mem_live() - live0 == m
+        _same(got, want)
+        eng.close()
+        assert lib.vch_mem_live() == base
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 9. about a PGD iterate
+# ---------------------------------------------------------------------------------------------------------------------
+def test_pgd_iterate_free_set_from_the_resident_control_and_an_undisturbed_run(V):
+    S1 = V.module("Vch_control_1D.second_order_conditions")
+    N, T, dt = 32, 0.05, 0.01
+    P = o.Params1D(N=N, T=T, dt_initial=dt)
+    tg, dts = V.time_grid(T, dt)
+    t = np.concatenate([[0.0], tg])
+    x = np.linspace(0.0, 1.0, N + 1)
+    phi0 = np.stack([0.2 * np.cos(np.pi * x + 0.4 * b) for b in range(2)])
+    phi_T = np.stack([0.7 * np.sin(2 * np.pi * x), 0.5 * np.cos(2 * np.pi * x)])
+    w = [dict(b1=0.3, b2=13.0, b3=0.0019, kappa_sparsity=9e-5, alpha_max=100.0),
+         dict(b1=2.0, b2=4.0, b3=1e-3, kappa_sparsity=9e-5, alpha_max=100.0)]
+
+    def start(opts):
+        eng = _engine(V, P, 2)
+        eng.pgd_init(phi0, phi_T, t, dts, opts)
+        eng.pgd_iterate(2)
+        return eng
+
+    # the scale of the control under a wide box, then a box of its own per trajectory that pins part of the nodes
+    probe = start([V.make_opt(u_min=-1e6, u_max=1e6, **w[0]), V.make_opt(u_min=-1e6, u_max=1e6, **w[1])])
+    top = np.abs(probe.pgd_get("u")).reshape(2, -1).max(axis=1)
+    probe.close()
+    assert top.min() > 0
+    opts = [V.make_opt(u_min=-0.5 * top[0], u_max=0.25 * top[0], **w[0]), V.make_opt(u_min=-0.1 * top[1], u_max=0.6 * top[1], **w[1])]
+    plain = start(opts)
+    want = plain.pgd_iterate(1)
+    u_want = plain.pgd_get("u")
+    plain.close()
+    eng = start(opts)
+    u, phi = eng.pgd_get("u"), eng.pgd_get("phi")
+    R = eng.RESIDENT
+    L = eng.hess_lanczos(_q0(u.shape, 10), 5, t, opts, u=R, phi_Q=R, phi_T=R, dt=dts)
+    nf = [int(S1.free_set(u[b], opts[b].u_min, opts[b].u_max).sum()) for b in range(2)]
+    print(f"MEASURE pgd: n_free {list(L['n_free'])} of {u[0].size}, free_set() {nf}, steps {list(L['steps'])}")
+    assert list(L["n_free"]) == nf and 0 < min(nf) and max(nf) < u[0].size
+    assert list(L["steps"]) == [5, 5] and np.isfinite(L["alpha"]).all()
+    assert np.array_equal(eng.pgd_get("u"), u) and np.array_equal(eng.pgd_get("phi"), phi)
+    got = eng.pgd_iterate(1)
+    for key in ("cost", "alpha", "trials", "change", "tracking_error", "terminal_error"):
+        assert np.array_equal(got[key], want[key]), key
+    assert np.array_equal(eng.pgd_get("u"), u_want)
+    eng.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 10. the driver
+# ---------------------------------------------------------------------------------------------------------------------
+def test_driver_on_device(driver):
+    pr, S1, O, D = driver, driver.S1, driver.O, DRIVER
+    args = (pr.cfg, pr.u, pr.phi, pr.x, pr.t, O.b1, O.b2, O.b3, O.kappa_sparsity, pr.phi_Q, pr.phi_T, D["u_min"], D["u_max"])
+    kw = dict(k=pr.u.size, seed=D["seed"])
+    host = S1.reduced_hessian_extremes(*args, **kw)
+    dev = S1.reduced_hessian_extremes(*args, on_device=True, vector=True, **kw)
+    assert set(dev) == set(host) | {"v_min"}
+    assert dev["n_free"] == host["n_free"] == 172 and dev["steps"] <= dev["n_free"] and len(dev["ritz"]) == dev["steps"]
+    lam = pr.ev[-1]
+    for name, R in (("host", host), ("device", dev)):
+        d = max(abs(R["theta_min"] - pr.ev[0]), abs(R["theta_max"] - pr.ev[-1])) / lam
+        print(f"MEASURE driver {name}: steps {R['steps']} theta_min {R['theta_min']:.6e} theta_max {R['theta_max']:.6e} rel.dev {d:.2e} "
+              f"residuals {R['res_min']:.1e} {R['res_max']:.1e}")
+        assert d < DRIVER_RITZ
+    v = dev["v_min"]
+    assert v.shape == pr.u.shape and abs(np.linalg.norm(v) - 1.0) < 10 * EPS and not v[~pr.mask].any()
+    eng = pr.context(1)
+    so = eng.second_order(v[None], pr.t, pr.opt, **pr.kw())
+    eng.close()
+    rq = float(so["curvature"][0])
+    print(f"MEASURE driver: Rayleigh quotient of v_min {rq:.6e} theta_min {dev['theta_min']:.6e} res_min {dev['res_min']:.1e}")
+    assert abs(rq - dev["theta_min"]) <= dev["res_min"] + DRIVER_RITZ * lam
+    few = S1.reduced_hessian_extremes(*args, k=12, seed=D["seed"], on_device=True, reorth=False)
+    assert few["steps"] == 12 and "v_min" not in few
+    with pytest.raises(ValueError):
+        S1.reduced_hessian_extremes(*args, vector=True, **kw)
+    with pytest.raises(ValueError):
+        S1.reduced_hessian_extremes(*args, on_device=True, vector=True, reorth=False, **kw)
