@@ -384,6 +384,53 @@ int vch2d_hess_lanczos(vch2d_ctx *ctx, const double *dt, int M, const double *t_
  * VCH_ERR_STATE without a resident basis, and after a reorth = 0 run when m exceeds the vectors still held; VCH_ERR_ARG for
  * m < 1 or m above the smallest step count of the batch plus one. */
 int vch2d_krylov_vector(vch2d_ctx *ctx, const double *coef /* [B][m] */, int m, double *out /* [B][M+1][Nx+1][Ny+1] */);
+/* Newton-CG on the free set: solves P H P x = P b per trajectory by (preconditioned) conjugate gradients from x_0 = 0 with x,
+ * r, p, the free set and the recurrence in device memory (ABI version stays 3: detect both entry points by
+ * symbol).  H p comes from the sweeps of vch2d_hess_lanczos (the gradient sweep once, then 2 M solves per trajectory and
+ * step; VCH_KRYLOV_NOCACHE=1 repeats it), the direction of a step goes through the trial-control scratch.
+ *   Base point, dt, M, t_hist, x, y, phi_Q, phi_T, opts / n_opts, rtol, mask, tol, the row rule: as for vch2d_hess_lanczos.
+ *   rhs      [B][M+1][Nx+1][Ny+1]: b = rhs.  NULL: the Newton right-hand side of the full cost on the free set, built on the
+ *            device: b = -(grad(J1+J2+J3) + kappa_sparsity_b wt_k W_cost_ij sign(u)); on the free set |u| > tol, so
+ *            J4 = kappa int int |u| is smooth there and this is its exact Euclidean gradient.
+ *   precond  0: D = I.  1: D = diag(wt_k W_cost_ij), the L2(Q) mass of the control (one multiply per node, not stored).
+ *   The iteration: r = P b, z = D^-1 r, p = z, rho = r.z; step j: c = p.P H p, n = p.D p, curv[j] = c / n; c not finite
+ *   stops with VCH_CG_BREAKDOWN, !(c > 0) with VCH_CG_NEGCURV (x stays as it is and p stays resident as the direction of
+ *   non-positive curvature); otherwise alpha = rho / c, x += alpha p, r -= alpha P H p, pred += alpha rho / 2,
+ *   resid[j] = ||r||_2 / ||P b||_2; resid[j] <= cg_tol (<= 0: 1e-8) stops with VCH_CG_CONVERGED (a residual that is not
+ *   finite with VCH_CG_BREAKDOWN); otherwise beta = rho_new / rho, p = z + beta p.  VCH_CG_LIMIT after k steps; there is no cap
+ *   at n_free.  P b == 0 gives zero steps, VCH_CG_CONVERGED and x = 0 (with rhs == NULL: stationarity on the free set).
+ *   resid_out, curv_out [B][k]: steps_out[b] counts the updates of x; entries of resid from steps_out[b] on are NaN, and
+ *            entries of curv too, except that after VCH_CG_NEGCURV / a breakdown of c, curv[steps_out[b]] is the curvature
+ *            that stopped the iteration.
+ *   pred_out [B]: the decrease b.x - x.Hx / 2 of the quadratic model, accumulated on the device in a fixed order.
+ *   rnorm0_out [B]: ||P b||_2.  status_out [B]: VCH_CG_*.  n_free_out [B]: the size of the free set.
+ * The stop state is in device cells: every streaming kernel of a stopped trajectory returns at once and leaves its x, r and
+ * p alone, the others go on; the solves of a stopped trajectory are not gated (as in vch2d_hess_lanczos).  No atomics: up
+ * to 32 trajectories, a trajectory's outputs are bitwise those of a single-trajectory context, whatever its batch mates do.
+ * The host looks once for the size of the free set, once for ||P b|| and once per step (B residuals and stop cells).
+ * Errors: VCH_ERR_ARG for k < 1, precond outside 0 / 1, a cg_tol that is not finite, NULL outputs and the row rule,
+ * VCH_ERR_STATE as for vch2d_hessvec -- all before anything is enqueued, copied or allocated.  Two errors depend on the data,
+ * both VCH_ERR_ARG naming the trajectory: an empty free set (after the mask launch, its sum and one look) and a ||P b|| that
+ * is not finite (after the start's look).  Storage: x, r, p are slots 0, 1, 2 of the basis storage of vch2d_hess_lanczos with
+ * reorth = 0, the cached sweep, the mask and the partials are shared, no further history is allocated; the call invalidates
+ * a resident Lanczos basis (vch2d_krylov_vector: VCH_ERR_STATE) and vch2d_hess_lanczos invalidates x, r, p.  A refused
+ * request releases what the call got and returns VCH_ERR_NOMEM with the bytes in the message; the context stays usable,
+ * and unchanged but for one case: a call that asks for more steps than the resident Krylov storage holds releases that
+ * storage, and the vectors in it, before it asks for the larger one.  Stateless like vch2d_hess_lanczos.  stats: linear solves B M (2 s + 1) when all members take s steps. */
+#define VCH_CG_LIMIT 0
+#define VCH_CG_CONVERGED 1
+#define VCH_CG_NEGCURV 2
+#define VCH_CG_BREAKDOWN 3
+int vch2d_hess_cg(vch2d_ctx *ctx, const double *dt, int M, const double *t_hist, const double *x, const double *y,
+                  const double *phi_Q, const double *phi_T, const vch_opt_params *opts, int n_opts, double rtol,
+                  const uint8_t *mask /* [B][M+1][Nx+1][Ny+1] or NULL */, double tol,
+                  const double *rhs /* [B][M+1][Nx+1][Ny+1] or NULL */, int k, double cg_tol, int precond /* 0 | 1 */,
+                  double *resid_out /* [B][k] */, double *curv_out /* [B][k] */, double *pred_out /* [B] */,
+                  double *rnorm0_out /* [B] */, int32_t *steps_out /* [B] */, int32_t *status_out /* [B] */,
+                  int64_t *n_free_out /* [B] */, vch_stats *stats);
+/* out = x (which 0), r (1) or p (2) of the last vch2d_hess_cg of this context; masked-off nodes are exact zeros.
+ * VCH_ERR_STATE without resident vectors (no call yet, a failed call, or a vch2d_hess_lanczos since). */
+int vch2d_cg_vector(vch2d_ctx *ctx, int which /* 0: x, 1: r, 2: p */, double *out /* [B][M+1][Nx+1][Ny+1] */);
 /* Per-trajectory cost scalars {J1,J2,J3,J4,J} of the current iterate on the DEVICE
  * (5*B doubles), for the caller's RCCL all-reduce; returns a device pointer via *ptr_dev. */
 int vch2d_pgd_cost_dev(vch2d_ctx *ctx, double **ptr_dev);

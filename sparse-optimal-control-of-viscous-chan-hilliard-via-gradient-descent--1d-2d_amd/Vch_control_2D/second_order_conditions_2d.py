@@ -255,6 +255,48 @@ def reduced_hessian_extremes_2d(u_star, x, y, t_hist, opt_config: Optional[Optim
                 ritz=theta, n_free=n_free, steps=m)
 
 
+def reduced_newton_step_2d(u, x, y, t_hist, opt_config: Optional[OptimizationConfig] = None, b1=None, b2=None, b3=None,
+                           kappa=None, phi_Q_target=None, phi_T_target=None, u_min: float = -np.inf,
+                           u_max: float = np.inf, k: int = 50, cg_tol: float = 1e-8, precond: bool = True,
+                           tol: float = 1e-8, fwd_config: Optional[ForwardSolverConfig] = None) -> dict:
+    """The Newton step of the full cost J1 + J2 + J3 + J4 on the free set `free_set(u, u_min, u_max, tol)` of the control
+    `u`: d solves P H P d = -P (grad(J1+J2+J3) + kappa_sparsity wt W_cost sign(u)) by (preconditioned) conjugate
+    gradients that stay on the device (Engine2D.hess_cg with rhs=None).  On the free set |u| > tol, so the L1 term is
+    smooth there and the right-hand side is the exact Euclidean gradient of the full cost; H is the exact Hessian of the
+    smooth part (the L1 term has no curvature off its kink).  One forward march of u, as in
+    `reduced_hessian_extremes_2d`, then one hess_cg call of at most `k` steps: two linear solves per CG step and time
+    step.  `precond` scales by the L2(Q) mass diag(wt W_cost) of the control, the function-space metric.
+
+    Returns dict(d: the step, zero off the free set; steps; status: "converged", "limit", "negcurv" or "breakdown";
+    resid: the relative residuals of the steps taken; pred: the decrease the quadratic model predicts for the full step;
+    rnorm0: the Euclidean norm of the right-hand side; curv_min: the smallest curvature p.Hp / p.Dp seen; n_free; p: the
+    direction of non-positive curvature when the status is "negcurv", else None).  With "negcurv" d is the iterate before
+    that direction (zero when the first direction already has non-positive curvature)."""
+    from ..engine import time_grid, make_opt, Engine2D
+    from ._ctx import engine_for_config
+    from .Forward2_solver import init_phi_random, DELTA_SEP
+    if fwd_config is None:
+        raise ValueError("reduced_newton_step_2d: fwd_config is required (the grid and the time steps of the march of u)")
+    opt = _ensure_opt_config(b1, b2, b3, kappa, opt_config)
+    cfg = fwd_config
+    t_grid, dts = time_grid(float(cfg.T), float(cfg.dt_initial))
+    M = len(dts)
+    u = np.asarray(u, dtype=np.float64)[:M + 1]                     # rows beyond the march are never read (F2:545-548)
+    phi0 = init_phi_random(int(cfg.Nx), int(cfg.Ny), DELTA_SEP, amp=0.1, seed=42)
+    eng = engine_for_config(cfg, batch=1, max_steps=max(M, 1))
+    one = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a)[None])
+    eng.forward(one(phi0), dts, u=one(u), store=False)
+    pq = None if phi_Q_target is None else one(np.asarray(phi_Q_target)[:M + 1])
+    box = make_opt(opt, u_min=float(u_min), u_max=float(u_max))
+    R = eng.hess_cg(int(k), cg_tol=cg_tol, precond=precond, tol=tol, dt=dts, t_hist=t_grid, opt=box, phi_Q=pq,
+                    phi_T=one(phi_T_target), x=x, y=y)
+    m, status = int(R["steps"][0]), Engine2D.CG_STATUS[int(R["status"][0])]
+    curv = R["curv"][0][np.isfinite(R["curv"][0])]
+    return dict(d=eng.cg_vector("x")[0], steps=m, status=status, resid=R["resid"][0, :m].copy(), pred=float(R["pred"][0]),
+                rnorm0=float(R["rnorm0"][0]), curv_min=float(curv.min()) if curv.size else float("nan"),
+                n_free=int(R["n_free"][0]), p=eng.cg_vector("p")[0] if status == "negcurv" else None)
+
+
 def sparsity_statistics(u_optimal, r_optimal, kappa: float, tol: float = 1e-6):
     """Counts behind the KKT sparsity check `u* = 0 <=> |r*| <= kappa`: (nodes with |u*| < tol, nodes with
     |r*| <= kappa, nodes where the two predicates agree, nodes in total)."""

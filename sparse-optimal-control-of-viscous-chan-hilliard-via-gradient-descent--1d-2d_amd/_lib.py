@@ -146,6 +146,10 @@ SIGNATURES = {
                                      C.POINTER(C.c_uint8), C.c_double, _D, C.c_int, C.c_int, _D, _D, _I32,
                                      C.POINTER(C.c_int64), C.POINTER(Stats)]),
     "vch2d_krylov_vector": (C.c_int, [_P, _D, C.c_int, _D]),
+    "vch2d_hess_cg": (C.c_int, [_P, _D, C.c_int, _D, _D, _D, _D, _D, C.POINTER(OptParams), C.c_int, C.c_double,
+                                C.POINTER(C.c_uint8), C.c_double, _D, C.c_int, C.c_double, C.c_int, _D, _D, _D, _D, _I32, _I32,
+                                C.POINTER(C.c_int64), C.POINTER(Stats)]),
+    "vch2d_cg_vector": (C.c_int, [_P, C.c_int, _D]),
     "vch2d_pgd_iterate": (C.c_int, [_P, C.c_int, _D, _D, _I32, _D, _D]),
     "vch2d_pgd_get": (C.c_int, [_P, C.c_int, _D]),
     "vch2d_pgd_errors": (C.c_int, [_P, C.c_int, _D, _D]),

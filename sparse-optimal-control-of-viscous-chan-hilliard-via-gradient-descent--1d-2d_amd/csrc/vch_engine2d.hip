@@ -243,6 +243,9 @@ struct vch2d_ctx {
     bool kr_nocache;                      // VCH_KRYLOV_NOCACHE=1 (A/B and tests): every step repeats the gradient sweep
     bool kr_valid = false;                // a basis is resident
     int kr_levels, kr_run_slots, kr_window, kr_min_steps;   // its rows, ring size, addressable vectors, smallest step count
+    // vch2d_hess_cg keeps x, r, p in slots 0, 1, 2 of kr_Q (either call invalidates what the other left resident)
+    bool ncg_valid = false;
+    int ncg_levels;
     bool res_pgd = false;                 // the resident state history is the resident PGD problem's iterate
     vch_pgd_state pgd;                    // the line search's books and the error metrics of the driver loop (vch_pgd.h)
     std::vector<double> J_host;           // [B][5] cost terms of the accepted iterate, the source of J_dev and the ring
@@ -2843,6 +2846,48 @@ static int kr_look(vch2d_ctx *c, void *host, const void *dev, size_t bytes) {
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
+// The lazy storage of a Krylov call (fn: vch2d_hess_lanczos or vch2d_hess_cg), one group: a refused request gives back what
+// this call got and leaves the context as it was, except that a request for more than the resident storage holds has
+// released that storage (and what it held) first.  On success whatever an earlier call left resident in the basis is no
+// longer valid: the caller overwrites it.
+static int kr_storage(vch2d_ctx *c, const char *fn, int slots, int k, bool want_phiQ) {
+    const size_t hist_bytes = (size_t)c->B * (c->Mmax + 1) * c->G.plane * 8;
+    if (c->kr_Q && (slots > c->kr_slots || k > c->kr_kcap)) {       // a larger basis than the resident storage holds
+        c->kr_valid = c->ncg_valid = false;
+        c->pool.drop((void **)&c->kr_sc);
+        c->pool.drop((void **)&c->kr_mask);
+        c->pool.drop((void **)&c->kr_X);
+        c->pool.drop((void **)&c->kr_Q);
+        c->kr_slots = c->kr_kcap = 0;
+    }
+    vch_group g(c->pool);
+    VCHCHK(ensure_hist(c, &c->u_trial));
+    VCHCHK(ensure_hist(c, &c->hv_G));
+    VCHCHK(ensure_hist(c, &c->hv_H));
+    VCHCHK(ensure_hist(c, &c->hv_V));
+    VCHCHK(ensure_hist(c, &c->hv_DP));
+    if (want_phiQ) VCHCHK(ensure_hist(c, &c->phiQ));
+    VCHCHK(ensure_fix_bad(c));
+    VCHCHK(ensure_hv_part(c, fn));
+    if (!c->kr_Q) {
+        const KrLayout L = kr_layout(c, slots, k);
+        const size_t need = (size_t)slots * hist_bytes + hist_bytes + hist_bytes / 8 + L.total * 8;
+        const bool ok = c->pool.dev(&c->kr_Q, (size_t)slots * hist_bytes) == 0 && c->pool.dev(&c->kr_X, hist_bytes) == 0 &&
+                        c->pool.dev(&c->kr_mask, hist_bytes / 8) == 0 && c->pool.dev(&c->kr_sc, L.total * 8) == 0;
+        if (!ok) {
+            (void)hipGetLastError();
+            return vch_fail(VCH_ERR_NOMEM,
+                            "%s: the Krylov storage needs %zu bytes (%d basis vectors of %zu bytes, one more "
+                            "history for the cached sweep, %zu bytes of mask, %zu of partials) and was refused",
+                            fn, need, slots, hist_bytes, hist_bytes / 8, L.total * 8);
+        }
+        c->kr_slots = slots;
+        c->kr_kcap = k;
+    }
+    g.keep();
+    c->kr_valid = c->ncg_valid = false;
+    return 0;
+}
 
 extern "C" int vch2d_hess_lanczos(vch2d_ctx *c, const double *dt, int M, const double *t_hist, const double *x, const double *y,
                                   const double *phi_Q, const double *phi_T, const vch_opt_params *opts, int n_opts, double rtol,
@@ -2866,43 +2911,7 @@ extern "C" int vch2d_hess_lanczos(vch2d_ctx *c, const double *dt, int M, const d
     const Geom &G = c->G;
     const int B = c->B, levels = M + 1, slots = reorth ? k + 1 : 3;
     const long hs = hist_stride(c);
-    const size_t hist_bytes = (size_t)B * (c->Mmax + 1) * G.plane * 8;
-    // lazy storage, one group: a refused request gives back what this call got and leaves the context as it was
-    c->kr_valid = false;
-    if (c->kr_Q && (slots > c->kr_slots || k > c->kr_kcap)) {       // a larger basis than the resident storage holds
-        c->pool.drop((void **)&c->kr_sc);
-        c->pool.drop((void **)&c->kr_mask);
-        c->pool.drop((void **)&c->kr_X);
-        c->pool.drop((void **)&c->kr_Q);
-        c->kr_slots = c->kr_kcap = 0;
-    }
-    {
-        vch_group g(c->pool);
-        VCHCHK(ensure_hist(c, &c->u_trial));
-        VCHCHK(ensure_hist(c, &c->hv_G));
-        VCHCHK(ensure_hist(c, &c->hv_H));
-        VCHCHK(ensure_hist(c, &c->hv_V));
-        VCHCHK(ensure_hist(c, &c->hv_DP));
-        if (!pgd && phi_Q) VCHCHK(ensure_hist(c, &c->phiQ));
-        VCHCHK(ensure_fix_bad(c));
-        VCHCHK(ensure_hv_part(c, __func__));
-        if (!c->kr_Q) {
-            const KrLayout L = kr_layout(c, slots, k);
-            const size_t need = (size_t)slots * hist_bytes + hist_bytes + hist_bytes / 8 + L.total * 8;
-            const bool ok = c->pool.dev(&c->kr_Q, (size_t)slots * hist_bytes) == 0 && c->pool.dev(&c->kr_X, hist_bytes) == 0 &&
-                            c->pool.dev(&c->kr_mask, hist_bytes / 8) == 0 && c->pool.dev(&c->kr_sc, L.total * 8) == 0;
-            if (!ok) {
-                (void)hipGetLastError();
-                return vch_fail(VCH_ERR_NOMEM,
-                                "vch2d_hess_lanczos: the Krylov storage needs %zu bytes (%d basis vectors of %zu bytes, one more "
-                                "history for the cached sweep, %zu bytes of mask, %zu of partials) and was refused",
-                                need, slots, hist_bytes, hist_bytes / 8, L.total * 8);
-            }
-            c->kr_slots = slots;
-            c->kr_kcap = k;
-        }
-        g.keep();
-    }
+    VCHCHK(kr_storage(c, __func__, slots, k, !pgd && phi_Q));
     const KrLayout L = kr_layout(c, c->kr_slots, c->kr_kcap);
     const KrCells cells = kr_cells(c, L);
     double *part = c->kr_sc + L.part;
@@ -3045,6 +3054,171 @@ extern "C" int vch2d_krylov_vector(vch2d_ctx *c, const double *coef, int m, doub
     const KrArgs a{c->kr_Q, (long)B * hs, hs, levels, c->kr_lchunk, 0, m, c->kr_run_slots, S, c->kr_mask, cells.stop};
     LAUNCH(k_kr_lincomb, dim3(c->nblk, nch, B), dim3(NTH), c->G, a, (const double *)ucoef, c->hv_H);
     return d2h_hist(c, out, c->hv_H, levels);
+}
+
+// ------------------------------------------------------------------------------------
+// Newton-CG on the free set: (preconditioned) conjugate gradients on P H P x = P b with x, r, p, the free set and the
+// recurrence on the device (kernels: "Device-resident Newton-CG" in vch_kernels2d.h).  The storage, the
+// mask launch and the sweeps are those of vch2d_hess_lanczos without reorthogonalisation.
+// ------------------------------------------------------------------------------------
+extern "C" int vch2d_hess_cg(vch2d_ctx *c, const double *dt, int M, const double *t_hist, const double *x, const double *y,
+                             const double *phi_Q, const double *phi_T, const vch_opt_params *opts, int n_opts, double rtol,
+                             const uint8_t *mask, double tol, const double *rhs, int k, double cg_tol, int precond,
+                             double *resid_out, double *curv_out, double *pred_out, double *rnorm0_out, int32_t *steps_out,
+                             int32_t *status_out, int64_t *n_free_out, vch_stats *stats) {
+    CTXCHK(c);
+    // everything below is checked before anything is enqueued, copied or allocated
+    VCHCHK(tan_check_state(c, __func__));
+    ARGCHK(opts, "NULL opts");
+    ARGCHK(resid_out && curv_out && pred_out && rnorm0_out && steps_out && status_out && n_free_out,
+           "NULL resid_out, curv_out, pred_out, rnorm0_out, steps_out, status_out or n_free_out");
+    ARGCHK(k >= 1, "k must be >= 1");
+    ARGCHK(precond == 0 || precond == 1, "precond must be 0 or 1");
+    ARGCHK(std::isfinite(cg_tol), "cg_tol must be finite");
+    bool pgd = false;
+    VCHCHK(tan_check_args(c, __func__, 1, &dt, M, &t_hist, x, y, phi_Q, phi_T, opts, n_opts, 2, &pgd));
+    if (!c->shift_res)
+        return vch_fail(VCH_ERR_STATE, "vch2d_hess_cg: the resident state history is not one a march of this context wrote");
+    // the direction has M + 1 rows: the g_rows the rule of vch2d_hessvec must allow
+    if (!c->res_pgd && c->fwd_u_rows > 0)
+        ARGCHK(c->fwd_u_rows >= M + 1, "the march's control has fewer than M + 1 rows");
+    const Geom &G = c->G;
+    const int B = c->B, levels = M + 1;
+    const long hs = hist_stride(c);
+    VCHCHK(kr_storage(c, __func__, 3, k, !pgd && phi_Q));
+    const KrLayout L = kr_layout(c, c->kr_slots, c->kr_kcap);
+    const KrCells cells = kr_cells(c, L);
+    // the cells of the iteration in the block of the Lanczos scalars: resid, curv where alpha, beta live
+    const NcgCells nc{cells.alpha, cells.beta, cells.look, cells.scal, cells.amax, cells.coef1, cells.coef1 + B, cells.coef1 + 2 * B,
+                      cells.lim, cells.stop};
+    double *part = c->kr_sc + L.part;
+    const int S = c->kr_slots, nch = (levels + c->kr_lchunk - 1) / c->kr_lchunk;
+    const long nsum = (long)nch * c->nblk;
+    const dim3 kgrid(c->nblk, nch, B);
+    const KrArgs a{c->kr_Q, (long)B * hs, hs, levels, c->kr_lchunk, 0, 0, 3, S, c->kr_mask, cells.stop};
+    const double stop_at = cg_tol > 0 ? cg_tol : 1e-8;
+    // the free set and its size: one mask launch, its sum and one look
+    VCHCHK(write_opt_tab(c, c->seam_tab, opts, n_opts));
+    if (mask)
+        for (int b = 0; b < B; ++b)
+            HIPCHK(hipMemcpy2DAsync(c->kr_mask + (size_t)b * hs, (size_t)G.pitch, mask + (size_t)b * levels * G.ns * G.nf, (size_t)G.nf,
+                                    (size_t)G.nf, (size_t)G.ns * levels, hipMemcpyHostToDevice, c->stream));
+    const int u_rows = c->res_pgd ? levels : std::min(c->fwd_u_rows, levels);
+    const double *u_dev = u_rows > 0 ? (const double *)c->u_hist : (const double *)nullptr;
+    LAUNCHC(PC_KRYLOV, k_kr_mask, kgrid, dim3(NTH), G, a, u_dev, u_rows, (const double *)c->seam_tab, tol > 0 ? tol : 1e-8, mask ? 0 : 1,
+            c->kr_mask, part);
+    LAUNCHC(PC_KRYLOV, k_kr_fin, dim3(B), dim3(NTH), cells, (const double *)part, nsum, S, 0, 0, 0, k);
+    std::vector<long long> nfree(B);
+    VCHCHK(kr_look(c, nfree.data(), cells.nfree, sizeof(long long) * B));
+    for (int b = 0; b < B; ++b)
+        if (nfree[b] < 1) return vch_fail(VCH_ERR_ARG, "vch2d_hess_cg: trajectory %d: the free set is empty", b);
+    const double *pq = nullptr, *pt = nullptr;
+    VCHCHK(tan_targets(c, pgd, x, y, phi_Q, phi_T, M, &pq, &pt));
+    // the solves stop at rtol (relative residual); the context's own tolerance comes back on every path out
+    const double keep_tol = c->lin_tol;
+    c->lin_tol = rtol > 0 ? rtol : 1e-12;
+    std::vector<int> bad(B, -1);
+    std::vector<double> look(2 * (size_t)B);
+    std::vector<long long> steps(B), stop(B);
+    auto run = [&]() -> int {
+        HvRun r{dt, M, pq, pt, levels, levels, {}};
+        if (rhs) VCHCHK(h2d_hist(c, c->u_trial, rhs, levels));   // through the trial-control scratch, which then holds p
+        VCHCHK(hv_begin(c, r, t_hist, opts, n_opts));
+        // the gradient sweep once per base point: its xp of every step stays in kr_X, its field is the Newton right-hand
+        // side's; an uploaded right-hand side is looked at first
+        auto grad_sweep = [&]() -> int {
+            VCHCHK(hv_grad_init(c, r));
+            VCHCHK(hv_sweeps(c, r, 0, 0, c->kr_nocache ? nullptr : c->kr_X, nullptr));
+            return 0;
+        };
+        if (!rhs) {
+            VCHCHK(grad_sweep());
+            LAUNCHC(PC_KRYLOV, (k_ncg_start<1>), kgrid, dim3(NTH), G, a, (const double *)c->hv_G, u_dev, u_rows, (const double *)c->hv_wt,
+                    (const double *)c->W_cost, (const double *)c->seam_tab, precond, c->u_trial, part);
+        } else {
+            LAUNCHC(PC_KRYLOV, (k_ncg_start<0>), kgrid, dim3(NTH), G, a, (const double *)c->u_trial, u_dev, u_rows,
+                    (const double *)c->hv_wt, (const double *)c->W_cost, (const double *)c->seam_tab, precond, c->u_trial, part);
+        }
+        LAUNCHC(PC_KRYLOV, k_ncg_fin, dim3(B), dim3(NTH), nc, (const double *)part, nsum, S, 1, 0, k, stop_at);
+        HIPCHK(hipMemsetAsync(nc.resid, 0xff, sizeof(double) * 2 * B * c->kr_kcap, c->stream));         // NaN: resid, then curv
+        VCHCHK(kr_look(c, look.data(), nc.look, sizeof(double) * 2 * B));
+        bool any = false;
+        for (int b = 0; b < B; ++b) {
+            if (!std::isfinite(look[2 * b]))
+                return vch_fail(VCH_ERR_ARG, "vch2d_hess_cg: trajectory %d: the right-hand side is not finite on the free set", b);
+            any = any || look[2 * b + 1] == 0.0;
+        }
+        if (any && rhs && !c->kr_nocache) VCHCHK(grad_sweep());
+        for (int j = 0; any && j < k; ++j) {
+            if (c->kr_nocache) {
+                VCHCHK(hv_grad_init(c, r));
+                VCHCHK(hv_tangent(c, r));
+                VCHCHK(hv_sweeps(c, r, 0, 1, nullptr, nullptr));
+            } else {
+                VCHCHK(hv_tangent(c, r));
+                VCHCHK(hv_sweeps(c, r, 1, 1, nullptr, c->kr_X));
+            }
+            // H p in hv_H
+            LAUNCHC(PC_KRYLOV, k_ncg_curv, kgrid, dim3(NTH), G, a, (const double *)c->hv_H, (const double *)c->hv_wt,
+                    (const double *)c->W_cost, precond, part);
+            LAUNCHC(PC_KRYLOV, k_ncg_fin, dim3(B), dim3(NTH), nc, (const double *)part, nsum, S, 2, j, k, stop_at);
+            LAUNCHC(PC_KRYLOV, k_ncg_update, kgrid, dim3(NTH), G, a, (const double *)c->hv_H, (const double *)nc.alpha,
+                    (const double *)c->hv_wt, (const double *)c->W_cost, precond, part);
+            LAUNCHC(PC_KRYLOV, k_ncg_fin, dim3(B), dim3(NTH), nc, (const double *)part, nsum, S, 3, j, k, stop_at);
+            if (j + 1 < k)
+                LAUNCHC(PC_KRYLOV, k_ncg_dir, kgrid, dim3(NTH), G, a, (const double *)nc.beta, (const double *)c->hv_wt,
+                        (const double *)c->W_cost, precond, c->u_trial);
+            // the one look of the step: the residual and the stop cell of every trajectory
+            VCHCHK(kr_look(c, look.data(), nc.look, sizeof(double) * 2 * B));
+            any = false;
+            for (int b = 0; b < B; ++b) any = any || look[2 * b + 1] == 0.0;
+        }
+        HIPCHK(hipEventRecord(c->ev1, c->stream));
+        for (int b = 0; b < B; ++b) {
+            HIPCHK(hipMemcpyAsync(resid_out + (size_t)b * k, nc.resid + (size_t)b * k, sizeof(double) * k, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(curv_out + (size_t)b * k, nc.curv + (size_t)b * k, sizeof(double) * k, hipMemcpyDeviceToHost, c->stream));
+        }
+        HIPCHK(hipMemcpyAsync(pred_out, nc.pred, sizeof(double) * B, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(rnorm0_out, nc.rnorm0, sizeof(double) * B, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(steps.data(), nc.steps, sizeof(long long) * B, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(stop.data(), nc.stop, sizeof(long long) * B, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(bad.data(), c->fix_bad, sizeof(int) * B, hipMemcpyDeviceToHost, c->stream));
+        VCHCHK(sync_state(c));
+        return 0;
+    };
+    int rc = run();
+    c->lin_tol = keep_tol;
+    if (rc < 0) {
+        (void)reset_counters(c);    // the records as the end of a PGD iteration leaves them
+        return rc;
+    }
+    float ms = 0;
+    hipEventElapsedTime(&ms, c->ev0, c->ev1);
+    fill_stats(c, stats, ms);
+    if (stats) {                    // the launches and the look of the free set, made before the counters were reset
+        stats->launches += 2;
+        stats->host_syncs += 1;
+    }
+    VCHCHK(reset_counters(c));      // the records as the end of a PGD iteration leaves them
+    rc = fix_check_end("vch2d_hess_cg", bad);
+    if (rc < 0) return rc;
+    for (int b = 0; b < B; ++b) {
+        n_free_out[b] = nfree[b];
+        steps_out[b] = (int32_t)steps[b];
+        status_out[b] = (int32_t)stop[b];           // 0: still running after k steps, VCH_CG_LIMIT
+    }
+    c->ncg_valid = true;
+    c->ncg_levels = levels;
+    return 0;
+}
+
+extern "C" int vch2d_cg_vector(vch2d_ctx *c, int which, double *out) {
+    CTXCHK(c);
+    ARGCHK(out, "NULL out");
+    ARGCHK(which >= 0 && which <= 2, "which must be 0 (x), 1 (r) or 2 (p)");
+    if (!c->ncg_valid || !c->kr_Q)
+        return vch_fail(VCH_ERR_STATE, "vch2d_cg_vector: no resident vectors (call vch2d_hess_cg first)");
+    return d2h_hist(c, out, c->kr_Q + (long)which * c->B * hist_stride(c), c->ncg_levels);
 }
 
 extern "C" int vch2d_mass_shifts(vch2d_ctx *c, double *out) {

@@ -3579,3 +3579,181 @@ __global__ __launch_bounds__(NTH) void k_kr_fin(KrCells x, const double *__restr
     x.look[2 * b] = beta;
     x.look[2 * b + 1] = (double)st;
 }
+
+// ---------------------------------------------------------------------------------
+// Device-resident Newton-CG on the free set (vch2d_hess_cg): (preconditioned) conjugate gradients on
+// P H P x = P b from x_0 = 0 with x, r and p in slots 0, 1, 2 of the Krylov basis storage.  Tiling, partials and the
+// fixed-order sums are those of the Lanczos passes above (KrArgs, KR_COORDS / KR_NODES, the order of kr_sum; first, nv and
+// nslots of KrArgs are not read).  D = diag(wt (x) W_cost), the L2(Q) mass of the control, is computed per node from the level's
+// trapezoid weight and the plane's cost weight when precond != 0 and is the identity otherwise.  Masked-off nodes of x, r
+// and p are exact zeros; P is applied where H p is read.  A trajectory whose stop cell is non-zero is skipped by every
+// pass, so its x, r and p stay as the stopping step left them.  No atomics.
+// ---------------------------------------------------------------------------------
+enum { NCG_X = 0, NCG_R = 1, NCG_P = 2 };
+enum { NCG_RUNNING = 0, NCG_CONVERGED = 1, NCG_NEGCURV = 2, NCG_BREAKDOWN = 3 };      // the stop cell: VCH_CG_* of vch.h
+__device__ __forceinline__ double *ncg_slot(const KrArgs &a, int i) { return const_cast<double *>(a.Q) + (long)i * a.slot_stride; }
+#define NCG_D(lvl, r, c) (precond ? wt[lvl] * Wc[(long)(r) * G.pitch + (c)] : 1.0)
+
+// The start: r = P b, x = 0, p = D^-1 r into its slot and into the direction buffer of the first sweep; partials
+// {r.r, r.D^-1 r}.  NEWTON 0: b = src (the uploaded right-hand side; src may be dir).  NEWTON 1: src is the gradient field
+// of J1 + J2 + J3 and b = -(src + kappa_sparsity_b wt_k W_cost_ij sign(u)), the Newton right-hand side of the full cost
+// (rows of the control beyond u_rows are zeros).
+template <int NEWTON>
+__global__ __launch_bounds__(NTH) void k_ncg_start(Geom G, KrArgs a, const double *src, const double *__restrict__ u, int u_rows,
+                                                   const double *__restrict__ wt, const double *__restrict__ Wc,
+                                                   const double *__restrict__ opt_tab, int precond, double *dir,
+                                                   double *__restrict__ part) {
+    KR_COORDS;
+    __shared__ double sred[NPART * 4];
+    const double ks = opt_tab[b * OPT_STRIDE + OPT_KS];
+    double *const xs = ncg_slot(a, NCG_X), *const rs = ncg_slot(a, NCG_R), *const ps = ncg_slot(a, NCG_P);
+    double acc[2] = {0.0, 0.0};
+    KR_NODES(
+        double rv = 0.0;
+        double z = 0.0;
+        if (a.mask[o]) {
+            rv = src[o];
+            if (NEWTON) {
+                const double v = (u && lvl < u_rows) ? u[o] : 0.0;
+                const double sgn = v > 0.0 ? 1.0 : (v < 0.0 ? -1.0 : 0.0);
+                rv = -(rv + (ks * wt[lvl]) * (Wc[(long)r * G.pitch + c] * sgn));
+            }
+            z = rv / NCG_D(lvl, r, c);
+        }
+        xs[o] = 0.0;
+        rs[o] = rv;
+        ps[o] = z;
+        dir[o] = z;
+        acc[0] += rv * rv;
+        acc[1] += rv * z;
+    )
+    const int op[2] = {0, 0};
+    block_reduce_store<2>(acc, op, sred, my_part);
+}
+
+// Partials {p.(P H p), p.D p}; hp = H p of the sweep just run.
+__global__ __launch_bounds__(NTH) void k_ncg_curv(Geom G, KrArgs a, const double *__restrict__ hp, const double *__restrict__ wt,
+                                                  const double *__restrict__ Wc, int precond, double *__restrict__ part) {
+    KR_COORDS;
+    if (a.stop[b]) return;                  // uniform over the workgroup
+    __shared__ double sred[NPART * 4];
+    const double *const ps = ncg_slot(a, NCG_P);
+    double acc[2] = {0.0, 0.0};
+    KR_NODES(
+        const double pv = ps[o];
+        const double hv = a.mask[o] ? hp[o] : 0.0;
+        acc[0] += pv * hv;
+        acc[1] += pv * (NCG_D(lvl, r, c) * pv);
+    )
+    const int op[2] = {0, 0};
+    block_reduce_store<2>(acc, op, sred, my_part);
+}
+
+// x += alpha p, r -= alpha P H p; partials {r.r, r.D^-1 r} of the new residual.
+__global__ __launch_bounds__(NTH) void k_ncg_update(Geom G, KrArgs a, const double *__restrict__ hp, const double *__restrict__ alpha,
+                                                    const double *__restrict__ wt, const double *__restrict__ Wc, int precond,
+                                                    double *__restrict__ part) {
+    KR_COORDS;
+    if (a.stop[b]) return;
+    __shared__ double sred[NPART * 4];
+    double *const xs = ncg_slot(a, NCG_X), *const rs = ncg_slot(a, NCG_R);
+    const double *const ps = ncg_slot(a, NCG_P);
+    const double al = alpha[b];
+    double acc[2] = {0.0, 0.0};
+    KR_NODES(
+        const double pv = ps[o];
+        const double hv = a.mask[o] ? hp[o] : 0.0;
+        xs[o] += al * pv;
+        const double rv = rs[o] - al * hv;
+        rs[o] = rv;
+        acc[0] += rv * rv;
+        acc[1] += rv * (rv / NCG_D(lvl, r, c));
+    )
+    const int op[2] = {0, 0};
+    block_reduce_store<2>(acc, op, sred, my_part);
+}
+
+// p = D^-1 r + beta p into its slot and into the direction buffer of the next sweep.
+__global__ __launch_bounds__(NTH) void k_ncg_dir(Geom G, KrArgs a, const double *__restrict__ beta, const double *__restrict__ wt,
+                                                 const double *__restrict__ Wc, int precond, double *__restrict__ dir) {
+    double *part = nullptr;
+    KR_COORDS;
+    if (a.stop[b]) return;
+    const double *const rs = ncg_slot(a, NCG_R);
+    double *const ps = ncg_slot(a, NCG_P);
+    const double be = beta[b];
+    KR_NODES(
+        const double v = rs[o] / NCG_D(lvl, r, c) + be * ps[o];
+        ps[o] = v;
+        dir[o] = v;
+    )
+}
+#undef NCG_D
+
+// The scalars of the iteration, one workgroup per trajectory, sums in the fixed order of kr_sum (ncg_sum below).
+//   mode 1   the start: ||P b|| -> rnorm0, look[0]; rho = r.D^-1 r; pred = 0; steps = 0; a zero right-hand side has converged
+//   mode 2   step j, after k_ncg_curv: c = p.P H p, n = p.D p, curv[j] = c / n; c not finite: BREAKDOWN; !(c > 0): NEGCURV;
+//            otherwise alpha = rho / c
+//   mode 3   step j, after k_ncg_update: pred += alpha rho / 2, resid[j] = ||r|| / ||P b||, steps = j + 1; not finite:
+//            BREAKDOWN; resid[j] <= cg_tol: CONVERGED; otherwise beta = rho_new / rho
+// look = {mode 1: ||P b||, later: the last residual; the stop cell}.
+struct NcgCells {
+    double *resid, *curv;             // [B][k]
+    double *look;                     // [B][2]
+    double *alpha, *beta;             // [B] the step length of k_ncg_update, the factor of k_ncg_dir
+    double *rho, *rnorm0, *pred;      // [B]
+    long long *steps, *stop;          // [B]
+};
+// kr_sum, word for word (the same order of additions).  A copy, not a call: with a second kernel calling kr_sum its LDS
+// buffer is no longer the same constant at every call site, and k_kr_fin compiles to 17 VGPRs / 57 SGPRs instead of 14 / 56.
+__device__ __forceinline__ double ncg_sum(const double *__restrict__ part, long n, int pstride, int slot, double *sh) {
+    double s = 0.0;
+    for (long e = threadIdx.x; e < n; e += NTH) s += part[e * pstride + slot];
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    for (int h = NTH / 2; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) sh[threadIdx.x] += sh[threadIdx.x + h];
+        __syncthreads();
+    }
+    const double r = sh[0];
+    __syncthreads();
+    return r;
+}
+__global__ __launch_bounds__(NTH) void k_ncg_fin(NcgCells x, const double *__restrict__ part, long n, int pstride, int mode, int j,
+                                                 int k, double cg_tol) {
+    __shared__ double sh[NTH];
+    const int b = blockIdx.x;
+    const double *p = part + (long)b * n * pstride;
+    if (mode != 1 && x.stop[b]) return;     // uniform: stopped at an earlier step
+    const double s0 = ncg_sum(p, n, pstride, 0, sh), s1 = ncg_sum(p, n, pstride, 1, sh);
+    if (threadIdx.x != 0) return;
+    long long st = NCG_RUNNING;
+    if (mode == 1) {
+        const double nb = sqrt(s0);
+        x.rnorm0[b] = nb;
+        x.rho[b] = s1;
+        x.pred[b] = 0.0;
+        x.steps[b] = 0;
+        x.look[2 * b] = nb;
+        st = nb == 0.0 ? NCG_CONVERGED : NCG_RUNNING;
+    } else if (mode == 2) {
+        x.curv[(long)b * k + j] = s0 / s1;
+        if (!isfinite(s0)) st = NCG_BREAKDOWN;
+        else if (!(s0 > 0.0)) st = NCG_NEGCURV;
+        else x.alpha[b] = x.rho[b] / s0;
+    } else {
+        const double rho = x.rho[b], res = sqrt(s0) / x.rnorm0[b];
+        x.pred[b] += 0.5 * x.alpha[b] * rho;
+        x.resid[(long)b * k + j] = res;
+        x.steps[b] = j + 1;
+        x.look[2 * b] = res;
+        if (!isfinite(res) || !isfinite(s1)) st = NCG_BREAKDOWN;
+        else if (res <= cg_tol) st = NCG_CONVERGED;
+        else {
+            x.beta[b] = s1 / rho;
+            x.rho[b] = s1;
+        }
+    }
+    x.stop[b] = st;
+    x.look[2 * b + 1] = (double)st;
+}

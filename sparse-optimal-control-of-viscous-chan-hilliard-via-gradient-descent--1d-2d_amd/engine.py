@@ -492,6 +492,83 @@ class Engine2D:
         check(self.lib.vch2d_krylov_vector(self.ctx, _dp(coef), int(coef.shape[1]), _dp(out)))
         return out
 
+    def _base_point(self, dt, t_hist, x, y):
+        """dt, t_hist, x, y as the calls about a resident base point pass them on, and M: all None about a resident PGD
+        problem, checked arrays (x, y defaulting to the engine's grid) after forward()."""
+        if dt is None or t_hist is None:
+            if not hasattr(self, "_pgd_M"):
+                raise ValueError("dt and t_hist are required without a resident PGD problem")
+            dt = t_hist = None
+            M = self._pgd_M
+        else:
+            dt = np.ascontiguousarray(dt, dtype=np.float64)
+            t_hist = np.ascontiguousarray(t_hist, dtype=np.float64)
+            M = int(dt.size)
+            if t_hist.size != M + 1:
+                raise ValueError("t_hist must have len(dt) + 1 entries")
+            x = self.x if x is None else x
+            y = self.y if y is None else y
+        if x is not None or y is not None:
+            x = np.ascontiguousarray(self.x if x is None else x, dtype=np.float64)
+            y = np.ascontiguousarray(self.y if y is None else y, dtype=np.float64)
+            if x.shape != (self.Nx + 1,) or y.shape != (self.Ny + 1,):
+                raise ValueError("x, y must have Nx+1, Ny+1 entries")
+        return dt, t_hist, x, y, M
+
+    def _free_mask(self, mask, M):
+        """A free set as (B, M+1, Nx+1, Ny+1) bytes (None stays None: built on the device)."""
+        if mask is None:
+            return None
+        mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if mask.ndim == 3 and self.B == 1:
+            mask = mask.reshape((1,) + mask.shape)
+        if mask.shape != (self.B, M + 1) + self.shape:
+            raise ValueError(f"mask must have shape ({self.B}, {M + 1}, {self.Nx + 1}, {self.Ny + 1}), got {mask.shape}")
+        return mask
+
+    CG_STATUS = ("limit", "converged", "negcurv", "breakdown")      # VCH_CG_LIMIT .. VCH_CG_BREAKDOWN
+
+    def hess_cg(self, k, rhs=None, cg_tol=0.0, precond=True, mask=None, tol=0.0, dt=None, t_hist=None, opt=None, phi_Q=None,
+                phi_T=None, x=None, y=None, rtol=0.0):
+        """(Preconditioned) conjugate gradients on P H P x = P b about the resident base point with x, r, p, the free set
+        and the recurrence on the device (vch2d_hess_cg); base point, mask and tol as for hess_lanczos.  rhs: (B, M+1,
+        Nx+1, Ny+1), or None: the Newton right-hand side -(grad(J1+J2+J3) + kappa_sparsity wt W_cost sign(u)) of the full
+        cost on the free set, built on the device.  precond: scale by the L2(Q) mass diag(wt W_cost) of the control.
+        cg_tol: relative residual at which a trajectory stops (<= 0: 1e-8); k: steps at most.
+        Returns dict(steps, status (indices of CG_STATUS), n_free: [B]; resid, curv: (B, k), NaN beyond steps (curv[steps]
+        is the stopping curvature after "negcurv"); pred: [B] decrease of the quadratic model; rnorm0: [B] ||P b||; stats)."""
+        k = int(k)
+        dt, t_hist, x, y, M = self._base_point(dt, t_hist, x, y)
+        rhs = None if rhs is None else self._hist(rhs, M + 1, "rhs")
+        mask = self._free_mask(mask, M)
+        pq = None if phi_Q is None else self._hist(phi_Q, M + 1, "phi_Q_target")
+        pt = None if phi_T is None else self._fld(phi_T, "phi_T_target")
+        seq = list(opt) if isinstance(opt, (list, tuple)) else [opt]
+        arr = (OptParams * len(seq))(*[o if isinstance(o, OptParams) else make_opt(o) for o in seq])
+        kk = max(k, 1)
+        resid, curv = np.full((self.B, kk), np.nan), np.full((self.B, kk), np.nan)
+        pred, rnorm0 = np.full(self.B, np.nan), np.full(self.B, np.nan)
+        steps, status, n_free = np.zeros(self.B, dtype=np.int32), np.zeros(self.B, dtype=np.int32), np.zeros(self.B, dtype=np.int64)
+        st = Stats()
+        precond = int(precond) if isinstance(precond, (bool, int, np.integer)) else -1
+        check(self.lib.vch2d_hess_cg(self.ctx, _dp(dt), M, _dp(t_hist), _dp(x), _dp(y), _dp(pq), _dp(pt), arr, len(seq),
+                                     float(rtol), None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                     float(tol), _dp(rhs), k, float(cg_tol), precond, _dp(resid), _dp(curv), _dp(pred),
+                                     _dp(rnorm0), steps.ctypes.data_as(_lib._I32), status.ctypes.data_as(_lib._I32),
+                                     n_free.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(st)))
+        self._cg_rows = M + 1
+        return dict(steps=steps, status=status, n_free=n_free, resid=resid, curv=curv, pred=pred, rnorm0=rnorm0,
+                    stats=st.as_dict())
+
+    def cg_vector(self, which="x"):
+        """(B, M+1, Nx+1, Ny+1): the solution x, the residual r or the direction p the last hess_cg left resident
+        (vch2d_cg_vector); masked-off nodes are exact zeros."""
+        if which not in ("x", "r", "p"):
+            raise ValueError(f"which must be 'x', 'r' or 'p', got {which!r}")
+        out = self._out(rows=getattr(self, "_cg_rows", 1))
+        check(self.lib.vch2d_cg_vector(self.ctx, "xrp".index(which), _dp(out)))
+        return out
+
     def mass_shifts(self):
         """(B, M): what the march's interior mass fix subtracted at the end of every step of the resident state history
         (vch2d_mass_shifts; zeros where the fix was not applied); M = the steps of that history."""
