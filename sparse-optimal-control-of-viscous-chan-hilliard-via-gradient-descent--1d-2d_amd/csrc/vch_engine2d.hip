@@ -184,6 +184,9 @@ struct vch2d_ctx {
     // together (vch_fft.h: column data, multiplier entries, the operands of the Chebyshev update); 0 launches
     // k_dct_cols_plain and k_cheb_rows_plain, the same arithmetic one node at a time
     bool rows_batch;
+    // VCH_LOADS_BATCH (default 1; 0 = A/B and tests): k_adj_guess, k_adj_finish and k_fin_residual with their global
+    // operands requested together (vch_kernels2d.h); 0 launches their _plain forms, the same arithmetic with one wait per load
+    bool loads_batch;
     unsigned long long *ceil_cell;        // [B][CeilCell::STRIDE] (vch_kernels2d.h)
     bool cell_now;                        // the level being enqueued uses the cells
     int trial_enq = -1;                   // sweeps of the reduction-free solve the NEXT trial launch arms the trial for (-1: none)
@@ -454,6 +457,9 @@ static void set_geometry(vch2d_ctx *c, const vch2d_params *p, int batch, int max
 
 // Every environment knob that is read once, at creation (VCH_ADJ_GUESS_OFF and VCH_ADJ_SAFE are read at the start of every
 // sweep, backward_core).  A switch is either on unless it is set to 0 (env_on) or on when it is set at all (env_set).
+// The kernel a launch takes under VCH_LOADS_BATCH: k (the default) or k_plain; LB_T for a template's instance.
+#define LB(k) (c->loads_batch ? k : k##_plain)
+#define LB_T(k, ...) (c->loads_batch ? k<__VA_ARGS__> : k##_plain<__VA_ARGS__>)
 static void read_knobs(vch2d_ctx *c) {
     auto env_on = [](const char *name) { const char *e = getenv(name); return !(e && atoi(e) == 0); };
     auto env_set = [](const char *name) { return getenv(name) != nullptr; };
@@ -480,6 +486,7 @@ static void read_knobs(vch2d_ctx *c) {
     c->ceil_cell_on = env_on("VCH_CEIL_CELL");
     c->eval_hoist = env_on("VCH_EVAL_HOIST");
     c->rows_batch = env_on("VCH_ROWS_BATCH");
+    c->loads_batch = env_on("VCH_LOADS_BATCH");
     c->cheb_margin = 1;
     if (const char *e = getenv("VCH_CHEB_MARGIN")) c->cheb_margin = std::max(0, atoi(e));
     c->cheb_max = 6;           // plans longer than this (a wide spectrum: CG's adaptivity pays) keep the CG form
@@ -992,7 +999,7 @@ static int residual_trial(vch2d_ctx *c, double dt, bool inline_dmu, bool fused, 
         if (!fin_inside) {
             FinTail tail{ChebFin{ef.cheb_enq, c->gnblk, c->gpart, c->gpart2, nullptr}, nullptr, nullptr, 0};
             if (publish) tail = publish_tail(c, tail);
-            LAUNCH((k_fin_residual<1>), dim3(c->B), dim3(64), c->st, c->part, c->nblk, c->hist_dev, c->P.kappa, dt, c->lin_tol, eta,
+            LAUNCH(LB_T(k_fin_residual, 1), dim3(c->B), dim3(64), c->st, c->part, c->nblk, c->hist_dev, c->P.kappa, dt, c->lin_tol, eta,
                    guess ? (int)c->gmask2 : 0, so, tail);
         }
         return 0;
@@ -1006,7 +1013,7 @@ static int residual_trial(vch2d_ctx *c, double dt, bool inline_dmu, bool fused, 
     if (guess)
         LAUNCHC(PC_GUESS, k_guess, c->grid, dim3(NTH), c->G, c->P, c->st, c->slot_stride, c->gtab2, (const double *)c->D_s, dt,
                 c->rhs_s, c->x0g, c->part, 1);
-    LAUNCH((k_fin_residual<1>), dim3(c->B), dim3(64), c->st, c->part, c->nblk, c->hist_dev, c->P.kappa, dt, c->lin_tol, eta,
+    LAUNCH(LB_T(k_fin_residual, 1), dim3(c->B), dim3(64), c->st, c->part, c->nblk, c->hist_dev, c->P.kappa, dt, c->lin_tol, eta,
            guess ? (int)c->gmask2 : 0, so, NO_FIN_TAIL);
     return 0;
 }
@@ -1060,7 +1067,7 @@ static int newton_level(vch2d_ctx *c, double dt, const double *un, const double 
                 c->D_s, (const double *)nullptr, c->cphi, c->cmu, dt, c->part, (const double *)c->w, un, unp1, u_stride, c->wnew, g1_,
                 c->x0g, efin_, post_);
         if (!fin_inside)
-            LAUNCH((k_fin_residual<2>), dim3(c->B), dim3(64), c->st, c->part, c->nblk, c->hist_dev, c->P.kappa, dt, c->lin_tol, eta_,
+            LAUNCH(LB_T(k_fin_residual, 2), dim3(c->B), dim3(64), c->st, c->part, c->nblk, c->hist_dev, c->P.kappa, dt, c->lin_tol, eta_,
                    guess ? (int)c->gmask1 : 0, so_, NO_FIN_TAIL);
     } else {
         LAUNCH(k_prepare, c->grid, dim3(NTH), c->G, c->P, c->st, c->slot_stride, c->phi_s, c->mu_s, c->w, un, unp1, u_stride,
@@ -1070,7 +1077,7 @@ static int newton_level(vch2d_ctx *c, double dt, const double *un, const double 
         if (guess)
             LAUNCHC(PC_GUESS, k_guess, c->grid, dim3(NTH), c->G, c->P, c->st, c->slot_stride, c->gtab1, (const double *)c->D_s, dt, c->rhs_s,
                    c->x0g, c->part, 0);
-        LAUNCH((k_fin_residual<0>), dim3(c->B), dim3(64), c->st, c->part, c->nblk, c->hist_dev, c->P.kappa, dt, c->lin_tol, eta_,
+        LAUNCH(LB_T(k_fin_residual, 0), dim3(c->B), dim3(64), c->st, c->part, c->nblk, c->hist_dev, c->P.kappa, dt, c->lin_tol, eta_,
                guess ? (int)c->gmask1 : 0, so_, NO_FIN_TAIL);
     }
     if (c->spec) {
@@ -1706,7 +1713,7 @@ static int backward_pass(vch2d_ctx *c, const double *phi_hist_dev, int M, const 
     const bool per_traj = c->B <= GUESS_BMAX;
     std::vector<int> order(per_traj ? c->B : 1, 1);
     int kept = 0;
-    LAUNCH(k_adj_finish, c->grid, dim3(NTH), G, c->x, (const double *)nullptr, qa, rcur, 0.0, 0.0,
+    LAUNCH(LB(k_adj_finish), c->grid, dim3(NTH), G, c->x, (const double *)nullptr, qa, rcur, 0.0, 0.0,
            r_out ? r_out + (long)M * G.plane : (double *)nullptr, p_out ? p_out + (long)M * G.plane : (double *)nullptr,
            q_out ? q_out + (long)M * G.plane : (double *)nullptr, hs);
     for (int n = M - 1; n >= 0; --n) {
@@ -1788,13 +1795,13 @@ static int backward_pass(vch2d_ctx *c, const double *phi_hist_dev, int M, const 
                     cf[0] = 1.0;                             // p_{n+1} as it stands
                 }
             }
-            LAUNCHC(PC_ADJ_GUESS, k_adj_guess, c->grid, dim3(NTH), G, c->x, ga, c->dprev[kept & (GUESS_RING - 1)]);
+            LAUNCHC(PC_ADJ_GUESS, LB(k_adj_guess), c->grid, dim3(NTH), G, c->x, ga, c->dprev[kept & (GUESS_RING - 1)]);
             ++kept;
         }
         VCHCHK(adjoint_solve_cg(c, dtn, sweeps, safe || first_solve));
         if (first_solve) { sweeps = -1; first_solve = false; }       // look again right after it
         const double den = c->P.gamma + 0.5 * dtn;
-        LAUNCH(k_adj_finish, c->grid, dim3(NTH), G, c->x, qa, qb, rcur, (c->P.gamma - 0.5 * dtn) / den, (0.5 * dtn) / den, rl,
+        LAUNCH(LB(k_adj_finish), c->grid, dim3(NTH), G, c->x, qa, qb, rcur, (c->P.gamma - 0.5 * dtn) / den, (0.5 * dtn) / den, rl,
                pl, ql, hs);
         std::swap(qa, qb);
     }

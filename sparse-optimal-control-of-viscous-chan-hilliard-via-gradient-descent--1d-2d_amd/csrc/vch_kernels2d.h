@@ -111,14 +111,56 @@ __device__ __forceinline__ int refl(int i, int n) {
     return i < 0 ? 0 : i;
 }
 
+// Global offset of element e of a thread's share of the haloed tile (e < W * HT).
 template <int H>
+__device__ __forceinline__ long tile_off(int e, const Geom &G, int c0, int r0) {
+    constexpr int W = TX + 2 * H;
+    int ly = e / W, lx = e - ly * W;
+    int gr = refl(r0 - H + ly, G.ns), gc = refl(c0 - H + lx, G.nf);
+    return (long)gr * G.pitch + gc;
+}
+// A thread's share of a haloed tile, requested into registers (tile_fetch) and written to LDS later (tile_put): a kernel
+// puts its other global requests between the two, so that they all travel together.
+template <int H>
+struct TileRegs {
+    static constexpr int N = (TX + 2 * H) * (TY + 2 * H), I = (N + NTH - 1) / NTH;
+    double v[I];
+};
+template <int H>
+__device__ __forceinline__ void tile_fetch(TileRegs<H> &t, const double *__restrict__ g, const Geom &G, int c0, int r0) {
+#pragma unroll
+    for (int i = 0; i < TileRegs<H>::I; ++i) {
+        const int e = threadIdx.x + i * NTH;
+        t.v[i] = 0.0;
+        if (e < TileRegs<H>::N) t.v[i] = g[tile_off<H>(e, G, c0, r0)];
+    }
+}
+template <int H>
+__device__ __forceinline__ void tile_put(double *s, const TileRegs<H> &t) {
+#pragma unroll
+    for (int i = 0; i < TileRegs<H>::I; ++i) {
+        const int e = threadIdx.x + i * NTH;
+        if (e < TileRegs<H>::N) s[e] = t.v[i];
+    }
+}
+
+// BATCH (the default): a compile-time trip count, every element of the thread requested before the first LDS write -- one
+// wait for global memory per tile.  BATCH = false is the rolled loop (one wait per element) that the _plain kernels keep, and
+// k_adj_rhs / k_adj_op, whose batched forms did not pay under the bench's two contexts.
+template <int H, bool BATCH = true>
 __device__ __forceinline__ void load_tile(double *s, const double *__restrict__ g, const Geom &G,
                                           int c0, int r0) {
-    constexpr int W = TX + 2 * H, HT = TY + 2 * H;
-    for (int e = threadIdx.x; e < W * HT; e += NTH) {
-        int ly = e / W, lx = e - ly * W;
-        int gr = refl(r0 - H + ly, G.ns), gc = refl(c0 - H + lx, G.nf);
-        s[e] = g[(long)gr * G.pitch + gc];
+    if (BATCH) {
+        TileRegs<H> t;
+        tile_fetch<H>(t, g, G, c0, r0);
+        tile_put<H>(s, t);
+    } else {
+        constexpr int W = TX + 2 * H, HT = TY + 2 * H;
+        for (int e = threadIdx.x; e < W * HT; e += NTH) {
+            int ly = e / W, lx = e - ly * W;
+            int gr = refl(r0 - H + ly, G.ns), gc = refl(c0 - H + lx, G.nf);
+            s[e] = g[(long)gr * G.pitch + gc];
+        }
     }
 }
 
@@ -694,10 +736,10 @@ __global__ __launch_bounds__(NTH) void k_residual_plain(Geom G, Phys P, const do
     __shared__ double sred[NPART * 4];
     constexpr int W = TX + 2;
     const long pb = b * G.plane;
-    load_tile<1>(s[0], pn + pb, G, c0, r0);
-    load_tile<1>(s[1], po + pb, G, c0, r0);
-    load_tile<1>(s[2], mn + pb, G, c0, r0);
-    load_tile<1>(s[3], mo + pb, G, c0, r0);
+    load_tile<1, false>(s[0], pn + pb, G, c0, r0);
+    load_tile<1, false>(s[1], po + pb, G, c0, r0);
+    load_tile<1, false>(s[2], mn + pb, G, c0, r0);
+    load_tile<1, false>(s[3], mo + pb, G, c0, r0);
     __syncthreads();
     double acc[1] = {0.0};
     for (int k = 0; k < TY / 4; ++k) {
@@ -856,7 +898,7 @@ __global__ __launch_bounds__(NTH) void k_adj_rhs(Geom G, Phys P, const double *_
     __shared__ double sred[NPART * 4];
     constexpr int W = TX + 2;
     const long pb = b * G.plane;
-    load_tile<1>(sq, q + pb, G, c0, r0);
+    load_tile<1, false>(sq, q + pb, G, c0, r0);
     __syncthreads();
     double acc[3] = {1e300, -1e300, 0.0};
     for (int k = 0; k < TY / 4; ++k) {
@@ -895,7 +937,7 @@ __global__ __launch_bounds__(NTH) void k_adj_op(Geom G, Phys P, const TrajState 
     __shared__ double sred[NPART * 4];
     constexpr int W2 = TX + 4, W1 = TX + 2;
     const long pb = b * G.plane;
-    load_tile<2>(sx, x + pb, G, c0, r0);
+    load_tile<2, false>(sx, x + pb, G, c0, r0);
     __syncthreads();
     for (int e = threadIdx.x; e < (TY + 2) * W1; e += NTH) {
         int ly = e / W1, lxx = e - ly * W1;
@@ -928,24 +970,46 @@ __global__ __launch_bounds__(NTH) void k_adj_op(Geom G, Phys P, const TrajState 
 }
 
 // p_n = x (already in place); q_n = -L p_n; r_n = gb r_{n+1} + gs (q_n + q_{n+1}) (B2:233-242).
-__global__ __launch_bounds__(NTH) void k_adj_finish(Geom G, const double *__restrict__ p,
-                                                    const double *__restrict__ q_old, double *__restrict__ q_new,
-                                                    double *__restrict__ r_cur, double gb, double gs,
-                                                    double *__restrict__ r_hist, double *__restrict__ p_hist,
-                                                    double *__restrict__ q_hist, long hist_stride) {
+// BATCH (the default; VCH_LOADS_BATCH=0 launches k_adj_finish_plain): the tile and r, q_old of the thread's TY / 4 own nodes are
+// requested together, in front of the barrier; the nodes are then applied in the same order with the same expressions.
+template <bool BATCH>
+__device__ __forceinline__ void adj_finish_body(const Geom &G, const double *__restrict__ p,
+                                                const double *__restrict__ q_old, double *__restrict__ q_new,
+                                                double *__restrict__ r_cur, double gb, double gs,
+                                                double *__restrict__ r_hist, double *__restrict__ p_hist,
+                                                double *__restrict__ q_hist, long hist_stride) {
     TILE_COORDS;
+    constexpr int K = TY / 4;
     __shared__ double s[(TY + 2) * (TX + 2)];
     constexpr int W = TX + 2;
     const long pb = b * G.plane;
-    load_tile<1>(s, p + pb, G, c0, r0);
+    double vr[K], vq[K];
+    if (BATCH) {
+        TileRegs<1> tp;
+        tile_fetch<1>(tp, p + pb, G, c0, r0);
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            int r = r0 + ly0 + 4 * k, c = c0 + lx;
+            vr[k] = vq[k] = 0.0;
+            if (q_old && r < G.ns && c < G.nf) {
+                long o = (long)r * G.pitch + c;
+                vr[k] = r_cur[pb + o];
+                vq[k] = q_old[pb + o];
+            }
+        }
+        tile_put<1>(s, tp);
+    } else {
+        load_tile<1, false>(s, p + pb, G, c0, r0);
+    }
     __syncthreads();
-    for (int k = 0; k < TY / 4; ++k) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
         int ly = ly0 + 4 * k, r = r0 + ly, c = c0 + lx;
         if (r < G.ns && c < G.nf) {
             int pp = (ly + 1) * W + lx + 1;
             long o = (long)r * G.pitch + c, oh = b * hist_stride + o;
             double qn = -lap_at<W>(s, pp, G.ax, G.ay);
-            double rn = q_old ? gb * r_cur[pb + o] + gs * (qn + q_old[pb + o]) : 0.0;
+            double rn = q_old ? gb * (BATCH ? vr[k] : r_cur[pb + o]) + gs * (qn + (BATCH ? vq[k] : q_old[pb + o])) : 0.0;
             q_new[pb + o] = qn;
             r_cur[pb + o] = rn;
             if (r_hist) r_hist[oh] = rn;
@@ -954,6 +1018,12 @@ __global__ __launch_bounds__(NTH) void k_adj_finish(Geom G, const double *__rest
         }
     }
 }
+#define ADJ_FINISH_PARAMS Geom G, const double *__restrict__ p, const double *__restrict__ q_old, double *__restrict__ q_new, \
+                          double *__restrict__ r_cur, double gb, double gs, double *__restrict__ r_hist,                    \
+                          double *__restrict__ p_hist, double *__restrict__ q_hist, long hist_stride
+#define ADJ_FINISH_ARGS G, p, q_old, q_new, r_cur, gb, gs, r_hist, p_hist, q_hist, hist_stride
+__global__ __launch_bounds__(NTH) void k_adj_finish(ADJ_FINISH_PARAMS) { adj_finish_body<true>(ADJ_FINISH_ARGS); }
+__global__ __launch_bounds__(NTH) void k_adj_finish_plain(ADJ_FINISH_PARAMS) { adj_finish_body<false>(ADJ_FINISH_ARGS); }
 
 // out = a_b*(x - y), a_b = a_tab[b * a_stride] (terminal right-hand side b2 (phi_M - phi_T), B2:183); y may be NULL
 __global__ __launch_bounds__(NTH) void k_scaled_diff(Geom G, const double *__restrict__ x, long xs,
@@ -1209,6 +1279,53 @@ __device__ __forceinline__ void fin_reduce(const double *part, int nblk, int b, 
         if (k < n) out[k] = op[k] == 0 ? wave_sum(a[k]) : (op[k] == 1 ? wave_min(a[k]) : wave_max(a[k]));
 }
 
+// The same reduction with FIN_PU workgroups' partials per lane in flight (VCH_LOADS_BATCH, the default): fin_fetch requests
+// them -- a kernel does so before it waits for anything else -- and fin_reduce folds them in the loop's order, t = lane,
+// lane + 64, ..., with the rolled loop for grids of more than 64 * FIN_PU tiles.
+constexpr int FIN_PU = 5;      // 64 * FIN_PU = 320 tiles: the bench's 512 x 512 grid has 297
+struct FinRegs {
+    double q[FIN_PU][NPART];
+};
+// (a lane past the last workgroup reads the last workgroup's record -- a valid address, no branch -- and leaves it unused;
+// all NPART slots of a record are read, whichever the caller sums)
+__device__ __forceinline__ void fin_fetch(FinRegs &f, const double *part, int nblk, int b) {
+#pragma unroll
+    for (int i = 0; i < FIN_PU; ++i) {
+        const int t = min((int)threadIdx.x + 64 * i, nblk - 1);
+        const double *p = part + ((long)b * nblk + t) * NPART;
+#pragma unroll
+        for (int k = 0; k < NPART; ++k) f.q[i][k] = p[k];
+    }
+}
+__device__ __forceinline__ void fin_reduce(const FinRegs &f, const double *part, int nblk, int b, double (&out)[NPART],
+                                           const int (&op)[NPART], int n) {
+    double a[NPART];
+#pragma unroll
+    for (int k = 0; k < NPART; ++k) a[k] = op[k] == 0 ? 0.0 : (op[k] == 1 ? 1e300 : -1e300);
+#pragma unroll
+    for (int i = 0; i < FIN_PU; ++i)
+        if ((int)threadIdx.x + 64 * i < nblk) {
+#pragma unroll
+            for (int k = 0; k < NPART; ++k)
+                if (k < n) {
+                    const double v = f.q[i][k];
+                    a[k] = op[k] == 0 ? a[k] + v : (op[k] == 1 ? fmin(a[k], v) : fmax(a[k], v));
+                }
+        }
+    for (int t = threadIdx.x + 64 * FIN_PU; t < nblk; t += 64) {
+        const double *p = part + ((long)b * nblk + t) * NPART;
+#pragma unroll
+        for (int k = 0; k < NPART; ++k)
+            if (k < n) {
+                const double v = p[k];
+                a[k] = op[k] == 0 ? a[k] + v : (op[k] == 1 ? fmin(a[k], v) : fmax(a[k], v));
+            }
+    }
+#pragma unroll
+    for (int k = 0; k < NPART; ++k)
+        if (k < n) out[k] = op[k] == 0 ? wave_sum(a[k]) : (op[k] == 1 ? wave_min(a[k]) : wave_max(a[k]));
+}
+
 // The fin kernels work on a trajectory's record in LDS: the 64 lanes copy it in (and out) together, one lane advances it.
 // (A per-thread copy `TrajState S = st[b]` lives in private memory -- the record has arrays indexed at run time -- and
 // costs ~120 scratch instructions and 70 one-lane global loads / stores per launch; through a reference to global memory
@@ -1217,6 +1334,28 @@ __device__ __forceinline__ void traj_copy_in(TrajState &dst, const TrajState *sr
     const unsigned *s = reinterpret_cast<const unsigned *>(src);
     unsigned *d = reinterpret_cast<unsigned *>(&dst);
     for (int i = threadIdx.x; i < (int)(sizeof(TrajState) / 4); i += 64) d[i] = s[i];
+    __syncthreads();
+}
+// ... in two halves (VCH_LOADS_BATCH): every dword of the record requested at once, and written to LDS behind the
+// kernel's other requests.
+struct TrajRegs {
+    static constexpr int N = (int)(sizeof(TrajState) / 4), I = (N + 63) / 64;
+    unsigned v[I];
+};
+__device__ __forceinline__ void traj_fetch(TrajRegs &t, const TrajState *src) {
+    const unsigned *s = reinterpret_cast<const unsigned *>(src);
+#pragma unroll
+    for (int i = 0; i < TrajRegs::I; ++i) {
+        t.v[i] = s[min((int)threadIdx.x + 64 * i, TrajRegs::N - 1)];
+    }
+}
+__device__ __forceinline__ void traj_put(TrajState &dst, const TrajRegs &t) {
+    unsigned *d = reinterpret_cast<unsigned *>(&dst);
+#pragma unroll
+    for (int i = 0; i < TrajRegs::I; ++i) {
+        const int e = threadIdx.x + 64 * i;
+        if (e < TrajRegs::N) d[e] = t.v[i];
+    }
     __syncthreads();
 }
 __device__ __forceinline__ void traj_copy_out(TrajState *dst, const TrajState &src) {
@@ -1376,6 +1515,24 @@ __device__ __forceinline__ double fin_sum1(const double *part, int n, int b, int
     for (int t = threadIdx.x; t < n; t += 64) a += part[((long)b * n + t) * stride + k];
     return wave_sum(a);
 }
+// ... with FIN_PU partials per lane in flight (VCH_LOADS_BATCH): sum1_fetch, then fin_sum1 in the loop's order
+struct Sum1Regs {
+    double q[FIN_PU];
+};
+__device__ __forceinline__ void sum1_fetch(Sum1Regs &f, const double *part, int n, int b, int stride, int k) {
+#pragma unroll
+    for (int i = 0; i < FIN_PU; ++i) {
+        f.q[i] = part[((long)b * n + min((int)threadIdx.x + 64 * i, n - 1)) * stride + k];      // n >= 1
+    }
+}
+__device__ __forceinline__ double fin_sum1(const Sum1Regs &f, const double *part, int n, int b, int stride, int k) {
+    double a = 0.0;
+#pragma unroll
+    for (int i = 0; i < FIN_PU; ++i)
+        if ((int)threadIdx.x + 64 * i < n) a += f.q[i];
+    for (int t = threadIdx.x + 64 * FIN_PU; t < n; t += 64) a += part[((long)b * n + t) * stride + k];
+    return wave_sum(a);
+}
 
 // What k_fin_ceiling gets after a Chebyshev solve with `enq` sweeps enqueued (enq < 0: no such solve).
 struct ChebFin {
@@ -1389,6 +1546,11 @@ struct ChebFin {
 __device__ __forceinline__ double cheb_solve_rel(int cheb_n, const ChebFin &cheb, int b) {
     if (cheb_n < 1) return 1.0;
     const double g0 = fin_sum1(cheb.g0, cheb.gnblk, b, 1, 0), gn = fin_sum1(cheb.gn, cheb.gnblk, b, 1, 0);
+    return g0 > 0.0 ? sqrt(fmax(gn, 0.0) / g0) : 0.0;
+}
+__device__ __forceinline__ double cheb_solve_rel(int cheb_n, const ChebFin &cheb, int b, const Sum1Regs &r0, const Sum1Regs &rn) {
+    if (cheb_n < 1) return 1.0;
+    const double g0 = fin_sum1(r0, cheb.g0, cheb.gnblk, b, 1, 0), gn = fin_sum1(rn, cheb.gn, cheb.gnblk, b, 1, 0);
     return g0 > 0.0 ? sqrt(fmax(gn, 0.0) / g0) : 0.0;
 }
 __device__ __forceinline__ void cheb_close_books(TrajState &S, double rel) {
@@ -1431,13 +1593,33 @@ template <int MODE>
 __device__ __forceinline__ void fin_residual_update(TrajState &S, const double (&v)[NPART], bool primed, double *__restrict__ hist,
                                                     double kappa, double dt, double lin_tol, double eta, SolveOpts so);
 
-template <int MODE>
-__global__ void k_fin_residual(TrajState *st, const double *__restrict__ part, int nblk,
-                               double *__restrict__ hist, double kappa, double dt, double lin_tol, double eta, int guess,
-                               SolveOpts so, FinTail tail) {
+// BATCH (the default; VCH_LOADS_BATCH=0 launches k_fin_residual_plain): everything whose address does not depend on the
+// record -- the partials, the two sums of a reduction-free solve and the ceiling cell, each guarded by kernel arguments only
+// -- is requested with the record, in front of the barrier behind its copy; a path that returns early leaves them unused.
+template <int MODE, bool BATCH>
+__device__ __forceinline__ void fin_residual_body(TrajState *st, const double *__restrict__ part, int nblk,
+                                                  double *__restrict__ hist, double kappa, double dt, double lin_tol, double eta,
+                                                  int guess, SolveOpts so, const FinTail &tail) {
     const int b = blockIdx.x;
     __shared__ TrajState S;
-    traj_copy_in(S, st + b);
+    FinRegs fr;
+    Sum1Regs r0, rn;
+    double cell_v = 1e300;
+    const bool pre_cheb = BATCH && MODE == 1 && tail.cheb.enq >= 0 && tail.cheb.g0 && tail.cheb.gn && tail.cheb.gnblk > 0;
+    const bool pre_cell = BATCH && MODE == 1 && tail.cheb.enq >= 0 && so.cell;
+    if (BATCH) {
+        TrajRegs tr;
+        traj_fetch(tr, st + b);
+        fin_fetch(fr, part, nblk, b);
+        if (pre_cheb) {
+            sum1_fetch(r0, tail.cheb.g0, tail.cheb.gnblk, b, 1, 0);
+            sum1_fetch(rn, tail.cheb.gn, tail.cheb.gnblk, b, 1, 0);
+        }
+        if (pre_cell && threadIdx.x == 0) cell_v = CeilCell::load(so.cell + b * CeilCell::STRIDE);
+        traj_put(S, tr);
+    } else {
+        traj_copy_in(S, st + b);
+    }
     bool go = true;                // (the same for all 64 lanes)
     if (MODE == 2) {               // after k_eval<0> without the fin step inside: the record has not been armed yet
         go = !S.frozen;
@@ -1450,11 +1632,11 @@ __global__ void k_fin_residual(TrajState *st, const double *__restrict__ part, i
     go = go && S.newton_active && S.need_trial;
     if (MODE == 1 && !go && tail.cheb.enq >= 0 && S.newton_active && S.use_cheb && !(S.lin_active && S.cheb_n > tail.cheb.enq)) {
         const int books = S.lin_active;             // as in k_fin_ceiling: not after k_cg_publish has taken the flag back
-        const double rel = books ? cheb_solve_rel(S.cheb_n, tail.cheb, b) : 1.0;
+        const double rel = !books ? 1.0 : (pre_cheb ? cheb_solve_rel(S.cheb_n, tail.cheb, b, r0, rn) : cheb_solve_rel(S.cheb_n, tail.cheb, b));
         __syncthreads();
         if (threadIdx.x == 0) {
             if (books) cheb_close_books(S, rel);
-            ceiling_arm(S, CeilCell::load(so.cell + b * CeilCell::STRIDE), 0);
+            ceiling_arm(S, pre_cell ? cell_v : CeilCell::load(so.cell + b * CeilCell::STRIDE), 0);
         }
         __syncthreads();
         go = true;
@@ -1465,7 +1647,8 @@ __global__ void k_fin_residual(TrajState *st, const double *__restrict__ part, i
         // guess: k_guess has deflated the right-hand side (MODE 0: of the step's first solve; MODE 1: of its second solve, for
         // a trajectory whose first solve is done); slot 1 holds sum (rhs - A x0)^2, slot 4 sum rhs^2
         const bool primed = guess_bit((unsigned)guess, b) && (MODE != 1 || S.iters == 1);
-        fin_reduce(part, nblk, b, v, op, primed ? 5 : 4);
+        if (BATCH) fin_reduce(fr, part, nblk, b, v, op, primed ? 5 : 4);
+        else fin_reduce(part, nblk, b, v, op, primed ? 5 : 4);
         if (so.cell) so.cell += b * CeilCell::STRIDE;
         if (threadIdx.x == 0)
             fin_residual_update<(MODE == 1 ? 1 : 0)>(S, v, primed, hist + (long)b * HIST_CAP, kappa, dt, lin_tol, eta, so);
@@ -1481,6 +1664,13 @@ __global__ void k_fin_residual(TrajState *st, const double *__restrict__ part, i
         if (threadIdx.x == 0) __hip_atomic_store(tail.seq + b, tail.val, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
+#define FIN_RESIDUAL_PARAMS TrajState *st, const double *__restrict__ part, int nblk, double *__restrict__ hist, double kappa, \
+                            double dt, double lin_tol, double eta, int guess, SolveOpts so, FinTail tail
+#define FIN_RESIDUAL_ARGS st, part, nblk, hist, kappa, dt, lin_tol, eta, guess, so, tail
+template <int MODE>
+__global__ void k_fin_residual(FIN_RESIDUAL_PARAMS) { fin_residual_body<MODE, true>(FIN_RESIDUAL_ARGS); }
+template <int MODE>
+__global__ void k_fin_residual_plain(FIN_RESIDUAL_PARAMS) { fin_residual_body<MODE, false>(FIN_RESIDUAL_ARGS); }
 
 template <int MODE>
 __device__ __forceinline__ void fin_residual_update(TrajState &S, const double (&v)[NPART], bool primed, double *__restrict__ hist,
@@ -1828,9 +2018,9 @@ __device__ __forceinline__ void eval_body(const Geom &G, const Phys &P, TrajStat
                     if (e < W2 * (TY + 4)) sp[e] = pf.apply(raw[i]);
                 }
             } else {
-                load_tile<2>(sp, phi_s + src * slot_stride + pb, G, c0, r0);
+                load_tile<2, false>(sp, phi_s + src * slot_stride + pb, G, c0, r0);
             }
-            load_tile<1>(sm, mu_s + src * slot_stride + pb, G, c0, r0);          // mu of the old level
+            load_tile<1, false>(sm, mu_s + src * slot_stride + pb, G, c0, r0);          // mu of the old level
 #pragma unroll
             for (int i = 0; i < I1; ++i) {
                 const int e = threadIdx.x + i * NTH;
@@ -2518,22 +2708,57 @@ __global__ __launch_bounds__(NTH) void k_solve_w(Geom G, const double *__restric
 // level to level and dominates the residual of a guess: p_{n+1} itself leaves ||rhs - A x0|| = 2 ||rhs||, p_{n+2} leaves
 // 1e-3 and the extrapolation over levels of the SAME parity, n+2, n+4, ..., 5e-6 and below (scripts/r2_extrap_adj.py).
 // backward_pass therefore sets c_0 = 0 and weights on j = 1, 3, 5, 7.
-__global__ __launch_bounds__(NTH) void k_adj_guess(Geom G, double *__restrict__ x, GuessArgs ga, double *__restrict__ keep) {
+// BATCH (the default; VCH_LOADS_BATCH=0 launches k_adj_guess_plain): the tests on the coefficients are uniform over the
+// trajectory, so x and every plane with a coefficient are requested for the thread's TY / 4 nodes before the first use; v is
+// then formed in the same order with the same test in front of each term.
+template <bool BATCH>
+__device__ __forceinline__ void adj_guess_body(const Geom &G, double *__restrict__ x, const GuessArgs &ga, double *__restrict__ keep) {
     TILE_COORDS;
-    for (int k = 0; k < TY / 4; ++k) {
+    constexpr int K = TY / 4;
+    double vx[K], vd[K][GUESS_ORD];
+    double cf[GUESS_ORD];          // BATCH: the trajectory's coefficients and the planes' addresses, read once
+    const double *dp[GUESS_ORD];
+    if (BATCH) {
+        const double *gcf = ga.row(b);
+#pragma unroll
+        for (int j = 0; j < GUESS_ORD; ++j) {
+            cf[j] = gcf[j];
+            dp[j] = ga.d[j];
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            int r = r0 + ly0 + 4 * k, c = c0 + lx;
+            const bool in = r < G.ns && c < G.nf;
+            const long o = b * G.plane + (long)r * G.pitch + c;
+            vx[k] = in ? x[o] : 0.0;
+#pragma unroll
+            for (int j = 1; j < GUESS_ORD; ++j) {
+                vd[k][j] = 0.0;
+                if (in && cf[j] != 0.0) vd[k][j] = dp[j][o];
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
         int r = r0 + ly0 + 4 * k, c = c0 + lx;
         if (r < G.ns && c < G.nf) {
             const long o = b * G.plane + (long)r * G.pitch + c;
-            const double p1 = x[o];
-            const double *gcf = ga.row(b);
+            const double p1 = BATCH ? vx[k] : x[o];
+            const double *gcf = BATCH ? cf : ga.row(b);
             double v = gcf[0] * p1;
 #pragma unroll
             for (int j = 1; j < GUESS_ORD; ++j)
-                if (gcf[j] != 0.0) v += gcf[j] * ga.d[j][o];
+                if (gcf[j] != 0.0) v += gcf[j] * (BATCH ? vd[k][j] : ga.d[j][o]);
             keep[o] = p1;
             x[o] = isfinite(v) ? v : p1;
         }
     }
+}
+__global__ __launch_bounds__(NTH) void k_adj_guess(Geom G, double *__restrict__ x, GuessArgs ga, double *__restrict__ keep) {
+    adj_guess_body<true>(G, x, ga, keep);
+}
+__global__ __launch_bounds__(NTH) void k_adj_guess_plain(Geom G, double *__restrict__ x, GuessArgs ga, double *__restrict__ keep) {
+    adj_guess_body<false>(G, x, ga, keep);
 }
 
 // the longest solve since the host's last look (adjoint launch schedule)
