@@ -770,6 +770,46 @@ int vch1d_hess_lanczos(vch1d_ctx *ctx, const double *phi_hist, const double *u, 
  * VCH_ERR_STATE without a resident basis, and after a reorth = 0 run when m exceeds the vectors still held; VCH_ERR_ARG for
  * m < 1 or m above the smallest step count of the batch plus one. */
 int vch1d_krylov_vector(vch1d_ctx *ctx, const double *coef /* [B][m] */, int m, double *out /* [B][rows][N+1] */);
+/* Newton-CG on the free set of the 1D engine: solves P H P x = P b per trajectory by (preconditioned) conjugate gradients
+ * from x_0 = 0 with x, r, p, the free set and the recurrence in device memory (the 1D counterpart of
+ * vch2d_hess_cg; ABI version stays 3: detect both entry points by symbol).  The iteration, the stop rules, the NaN
+ * conventions of resid_out / curv_out, pred_out, rnorm0_out, steps_out, status_out (VCH_CG_*) and n_free_out are those of
+ * vch2d_hess_cg; base point, opts, mask and tol are those of vch1d_hess_lanczos (n_base 1 or B, NULL = zeros, VCH_RESIDENT,
+ * the resident history, the stop quirk, the mask built on the device from trajectory b's own box over all rows, NULL mask
+ * with NULL u is VCH_ERR_ARG).  H p comes from the step kernel of vch1d_hess_lanczos: 2 M solves per product.  Four points
+ * differ from the 2D call:
+ *   1. rhs NULL: the Newton right-hand side b = -(grad(J1+J2+J3) + kappa_sparsity_b wt_k wx_i sign(u)), built by the set-up
+ *      launch, whose gradient sweep then accumulates the gradient field with the expressions of vch1d_hessvec order 1.  wt
+ *      are the trapezoid weights of t_hist over all rows, wx those of x (the weights of the cost).  Row 0 has wt = 0: the
+ *      sign term vanishes there, the gradient does not (row 0 drives step 0).  The call reads kappa_sparsity of opts[b]
+ *      beside b1, b2, b3, u_min, u_max.
+ *   2. precond 1: D = diag(wt'_k wx_i) with wt'_k = wt_k except wt'_0 := wt_1: row 0 is a real unknown with quadrature
+ *      weight zero and takes the weight of the row that duplicates its time.  D is computed per node and not stored.  A
+ *      wt'_k that is not finite or not > 0 with precond 1 is VCH_ERR_ARG naming the row, before anything is enqueued.
+ *   3. The stop state is in device cells and the k steps are enqueued back to back; every kernel of a stopped trajectory
+ *      returns at once, the persistent step kernel included.  The host looks twice: after the set-up (n_free, ||P b||) and
+ *      at the end.  stats: host_syncs = 2, linear_solves = sum_b M (2 p_b + 1) with p_b the products taken: steps_b, plus
+ *      one after an exit on the curvature (VCH_KRYLOV_NOCACHE=1: 3 M p_b, plus the M of the set-up when rhs is NULL).
+ *   4. An empty free set and a ||P b|| that is not finite are both VCH_ERR_ARG naming the trajectory, after the set-up's
+ *      look and before any step; they leave nothing resident.  P b == 0 gives zero steps, VCH_CG_CONVERGED and x = 0.
+ * Further errors, all before anything is copied, launched or allocated: VCH_ERR_ARG / VCH_ERR_STATE as for vch1d_hessvec,
+ * VCH_ERR_ARG for k < 1, precond outside 0 / 1, a cg_tol that is not finite and NULL outputs.  Storage: x, r, p are slots 0,
+ * 1, 2 of the basis storage of vch1d_hess_lanczos with reorth = 0; the cached sweep, the tangent history, w, the mask and the
+ * partials are shared and no further history is allocated.  The call invalidates a resident Lanczos basis
+ * (vch1d_krylov_vector: VCH_ERR_STATE) and vch1d_hess_lanczos invalidates x, r, p.  A refused request releases the group and
+ * returns VCH_ERR_NOMEM with the bytes in the message; the context stays usable.  Stateless like vch1d_hessvec; no atomics:
+ * a trajectory's outputs, x, r and p included, are bitwise those of a single-trajectory context. */
+int vch1d_hess_cg(vch1d_ctx *ctx, const double *phi_hist, const double *u, int n_base, int rows,
+                  const double *dt, const double *t_hist, const double *x,
+                  const double *phi_Q, const double *phi_T, const vch_opt_params *opts, int n_opts,
+                  const uint8_t *mask /* [n_base][rows][N+1] or NULL */, double tol,
+                  const double *rhs  /* [B][rows][N+1] or NULL */, int k, double cg_tol, int precond /* 0 | 1 */,
+                  double *resid_out /* [B][k] */, double *curv_out /* [B][k] */, double *pred_out /* [B] */,
+                  double *rnorm0_out /* [B] */, int32_t *steps_out /* [B] */, int32_t *status_out /* [B] */,
+                  int64_t *n_free_out /* [B] */, vch_stats *stats);
+/* out = x (which 0), r (1) or p (2) of the last vch1d_hess_cg of this context; masked-off nodes are exact zeros.
+ * VCH_ERR_STATE without resident vectors (no call yet, a failed call, or a vch1d_hess_lanczos since). */
+int vch1d_cg_vector(vch1d_ctx *ctx, int which /* 0: x, 1: r, 2: p */, double *out /* [B][rows][N+1] */);
 
 /* ---------------------------------------------------------- diagnostics ---- */
 

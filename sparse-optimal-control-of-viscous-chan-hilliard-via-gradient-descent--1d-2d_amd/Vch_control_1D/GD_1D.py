@@ -231,6 +231,65 @@ def run_sweep(fwd_config: ForwardSolverConfig, opt_configs, n_iter=None, seed=42
     return out
 
 
+def newton_refine(fwd_config: ForwardSolverConfig, opt_config: OptimizationConfig, u, phi_Q_target, phi_T_target,
+                  n_newton=3, k=50, cg_tol=1e-8, max_halvings=10):
+    """Rounds of a damped Newton method on the free set, from the control `u` (for instance what the PGD loop left).
+    Per round: the free set of the iterate (strictly inside the box of `opt_config`, off the kink of the L1 term) and
+    the Newton step d of the full cost on it (second_order_conditions.reduced_newton_step: conjugate gradients on the
+    device, at most `k` steps to `cg_tol`).  Trials are clip(u + s d, box) for s = 1, 1/2, ..., at most `max_halvings`
+    halvings; a free node whose sign the trial flips is set to 0, the kink, where the next round pins it.  The first s
+    with J(trial) <= J(u) - 1e-4 s pred is accepted, J the full cost of a march of the trial from the default start of
+    `run_main_simulation` (Engine1D.forward and Engine1D.cost) and pred the decrease the quadratic model predicts for the
+    full step.  The loop ends after `n_newton` rounds, when the right-hand side vanishes (stationarity on the free set),
+    when the first CG direction already has non-positive curvature, or when no s is accepted.
+
+    Returns (u, records): the final control and one dict per round with cost (before the round), n_free, rnorm0, steps,
+    status, s (None when the round moved nothing) and cost_new (the accepted trial's, else the unchanged cost)."""
+    from ..engine import time_grid
+    from ._ctx import engine_for_config
+    from .Forward_solver import init_phi_random, delta_sep
+    from .second_order_conditions import free_set, reduced_newton_step
+    N = int(fwd_config.N)
+    tg, dts = time_grid(float(fwd_config.T), float(fwd_config.dt_initial))
+    t_hist = np.concatenate([[0.0], tg])
+    M = len(dts)
+    lo, hi = float(opt_config.u_min), float(opt_config.u_max)
+    u = np.asarray(u, dtype=np.float64)[:M + 2]                     # nodes outside the box are not free: the first trial clips them
+    phi0 = init_phi_random(N, delta_sep, amp=0.01, seed=42, enforce_zero_mean=True)
+    x = np.linspace(0.0, float(fwd_config.Lx), N + 1)
+    pq, pt = np.asarray(phi_Q_target, dtype=np.float64)[None, :M + 2], np.asarray(phi_T_target, dtype=np.float64)[None]
+    opt = make_opt(opt_config)
+
+    def full_cost(v):
+        eng = engine_for_config(fwd_config, batch=1, max_steps=max(M, 1))
+        phi, _ = eng.forward(phi0[None], dts, u=v[None], store=True)
+        J = eng.cost(phi.reshape((1, M + 2, N + 1)), v[None], pq, pt, x, t_hist, opt)
+        return float(np.atleast_2d(J)[0, 4])
+
+    cost = full_cost(u)
+    records = []
+    for _ in range(int(n_newton)):
+        S = reduced_newton_step(fwd_config, u, x, t_hist, opt_config, phi_Q_target=phi_Q_target, phi_T_target=phi_T_target,
+                                u_min=lo, u_max=hi, k=k, cg_tol=cg_tol)
+        rec = dict(cost=cost, n_free=S["n_free"], rnorm0=S["rnorm0"], steps=S["steps"], status=S["status"], s=None, cost_new=cost)
+        records.append(rec)
+        if S["rnorm0"] == 0.0 or (S["status"] == "negcurv" and S["steps"] == 0):
+            break
+        d, free, s = S["d"], free_set(u, lo, hi), 1.0
+        for _ in range(int(max_halvings) + 1):
+            trial = np.clip(u + s * d, lo, hi)
+            trial[free & (trial * u < 0.0)] = 0.0
+            J = full_cost(trial)
+            if J <= cost - 1e-4 * s * S["pred"]:
+                rec["s"], rec["cost_new"] = s, J
+                break
+            s *= 0.5
+        if rec["s"] is None:
+            break
+        u, cost = trial, J
+    return u, records
+
+
 def main(n_iter=None, params_file="last_run_config.json", control_file="optimal_control.npy", num_directions=3,
          verbose=True):
     """Non-interactive equivalent of the reference's `__main__` block (G1:256-609) without prompts and

@@ -251,3 +251,50 @@ def reduced_hessian_extremes(fwd_config: ForwardSolverConfig, u_star, phi_star, 
     resid = np.abs(betas[m - 1] * S[m - 1])
     return dict(theta_min=float(theta[0]), theta_max=float(theta[-1]), res_min=float(resid[0]), res_max=float(resid[-1]),
                 ritz=theta, n_free=n_free, steps=m)
+
+
+def reduced_newton_step(fwd_config: ForwardSolverConfig, u, x, t_hist, opt_config=None, b1=None, b2=None, b3=None, kappa=None,
+                        phi_Q_target=None, phi_T_target=None, u_min: float = -np.inf, u_max: float = np.inf, k: int = 50,
+                        cg_tol: float = 1e-8, precond: bool = True, tol: float = 1e-8) -> dict:
+    """The Newton step of the full cost J1 + J2 + J3 + J4 on the free set `free_set(u, u_min, u_max, tol)` of the control
+    `u`: d solves P H P d = -P (grad(J1+J2+J3) + kappa_sparsity wt wx sign(u)) by (preconditioned) conjugate gradients that
+    stay on the device (Engine1D.hess_cg with rhs=None).  On the free set |u| > tol, so the L1 term is smooth there and the
+    right-hand side is the exact Euclidean gradient of the full cost; H is the exact Hessian of the smooth part (the L1
+    term has no curvature off its kink).  One forward march of u from the default start of `run_main_simulation`, then
+    one hess_cg call of at most `k` steps: two linear solves per CG step and time step.  The weights come from
+    `opt_config`, or from b1, b2, b3 and kappa (the sparsity parameter) when it is None.  `precond` scales by the L2(Q)
+    mass diag(wt wx) of the control, row 0 taking the time weight of row 1.
+
+    Returns dict(d: the step, zero off the free set; steps; status: "converged", "limit", "negcurv" or "breakdown";
+    resid: the relative residuals of the steps taken; pred: the decrease the quadratic model predicts for the full step;
+    rnorm0: the Euclidean norm of the right-hand side; curv_min: the smallest curvature p.Hp / p.Dp seen; n_free; p: the
+    direction of non-positive curvature when the status is "negcurv", else None).  With "negcurv" d is the iterate before
+    that direction (zero when the first direction already has non-positive curvature)."""
+    from ..engine import time_grid, make_opt, Engine1D
+    from ._ctx import engine_for_config
+    from .Forward_solver import init_phi_random, delta_sep
+    if fwd_config is None:
+        raise ValueError("reduced_newton_step: fwd_config is required (the grid and the time steps of the march of u)")
+    if opt_config is None and None in (b1, b2, b3, kappa):
+        raise ValueError("reduced_newton_step: give opt_config, or all of b1, b2, b3 and kappa")
+    cfg = fwd_config
+    over = {n: v for n, v in (("b1", b1), ("b2", b2), ("b3", b3), ("kappa_sparsity", kappa)) if v is not None}
+    box = make_opt(opt_config, u_min=float(u_min), u_max=float(u_max), **over)
+    _, dts = time_grid(float(cfg.T), float(cfg.dt_initial))
+    M = len(dts)
+    t_hist = np.asarray(t_hist, dtype=np.float64)
+    if t_hist.size != M + 2:
+        raise ValueError(f"reduced_newton_step: t_hist must have the march's {M + 2} rows, got {t_hist.size}")
+    u = np.asarray(u, dtype=np.float64)[:M + 2]
+    phi0 = init_phi_random(int(cfg.N), delta_sep, amp=0.01, seed=42, enforce_zero_mean=True)
+    eng = engine_for_config(cfg, batch=1, max_steps=max(M, 1))
+    one = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.float64)[None])
+    eng.forward(one(phi0), dts, u=one(u), store=False)
+    R = eng.hess_cg(int(k), t_hist, box, cg_tol=cg_tol, precond=precond, tol=tol, u=one(u),
+                    phi_Q=None if phi_Q_target is None else one(np.asarray(phi_Q_target)[:M + 2]), phi_T=one(phi_T_target),
+                    dt=dts, x=x)
+    m, status = int(R["steps"][0]), Engine1D.CG_STATUS[int(R["status"][0])]
+    curv = R["curv"][0][np.isfinite(R["curv"][0])]
+    return dict(d=eng.cg_vector("x")[0], steps=m, status=status, resid=R["resid"][0, :m].copy(), pred=float(R["pred"][0]),
+                rnorm0=float(R["rnorm0"][0]), curv_min=float(curv.min()) if curv.size else float("nan"),
+                n_free=int(R["n_free"][0]), p=eng.cg_vector("p")[0] if status == "negcurv" else None)

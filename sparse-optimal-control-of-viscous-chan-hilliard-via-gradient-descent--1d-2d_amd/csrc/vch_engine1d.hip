@@ -56,6 +56,9 @@ struct vch1d_ctx {
     bool kr_valid = false;
     int kr_rows = 0, kr_run_slots = 0, kr_min_steps = 0, kr_window = 0;
     bool kr_nocache = false;               // VCH_KRYLOV_NOCACHE=1 (A/B and tests): every step repeats the gradient sweep
+    // vch1d_hess_cg keeps x, r, p in slots 0, 1, 2 of kr_Q (either call invalidates what the other left resident)
+    bool ncg_valid = false;
+    int ncg_rows = 0;
 };
 
 // no launch bookkeeping (LAUNCH_LDS, vch_common.h)
@@ -159,7 +162,8 @@ extern "C" vch1d_ctx *vch1d_create(const vch1d_params *p, int batch, int max_ste
     for (const void *k : {(const void *)k1d_forward, (const void *)k1d_newton, (const void *)k1d_backward, (const void *)k1d_solve<0>,
                           (const void *)k1d_solve<1>, (const void *)k1d_tangent<1>, (const void *)k1d_tangent<2>,
                           (const void *)k1d_hessvec<1>, (const void *)k1d_hessvec<2>, (const void *)k1d_kr_setup,
-                          (const void *)k1d_kr_step<0>, (const void *)k1d_kr_step<1>})
+                          (const void *)k1d_kr_step<0>, (const void *)k1d_kr_step<1>, (const void *)k1d_ncg_setup<0>,
+                          (const void *)k1d_ncg_setup<1>})
         hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes);
     c->kr_nocache = getenv("VCH_KRYLOV_NOCACHE") && atoi(getenv("VCH_KRYLOV_NOCACHE")) != 0;
     if (hipStreamSynchronize(c->stream) != hipSuccess) return fail("hipStreamSynchronize");
@@ -943,7 +947,7 @@ extern "C" int vch1d_hessvec(vch1d_ctx *c, const double *phi_hist, const double 
 // The block behind kr_sc, in doubles; S = basis slots (the stride of a partial and of a coefficient row), K = entries of
 // alpha / beta per trajectory.
 struct Kr1Layout {
-    size_t part, coef1, coef2, ucoef, alpha, beta, look, scal, amax, lim, stop, steps, box, wt, mean, total;
+    size_t part, coef1, coef2, ucoef, alpha, beta, look, scal, amax, lim, stop, steps, box, wt, mean, wtp, ks, total;
 };
 static int kr1_chunks(const vch1d_ctx *c, int rows) { return (int)(((long)rows * c->n + KR1_CHUNK - 1) / KR1_CHUNK); }
 static Kr1Layout kr1_layout(const vch1d_ctx *c, int S, int K) {
@@ -966,6 +970,8 @@ static Kr1Layout kr1_layout(const vch1d_ctx *c, int S, int K) {
     L.box = take(2 * B);
     L.wt = take(R);
     L.mean = take(B * R);
+    L.wtp = take(R);
+    L.ks = take(B);
     L.total = at;
     return L;
 }
@@ -974,6 +980,49 @@ static Kr1Args kr1_args(const vch1d_ctx *c, const Kr1Layout &L, int rows, int sl
     const Kr1Cells x{p + L.coef1, p + L.coef2, p + L.alpha, p + L.beta, p + L.look, p + L.scal, p + L.amax,
                      (long long *)(p + L.lim), (long long *)(p + L.stop), (long long *)(p + L.steps)};
     return Kr1Args{c->kr_Q, (long)c->B * hs1(c), hs1(c), (long)rows * c->n, slots, c->kr_slots, c->kr_mask, mask_s, x};
+}
+
+// The lazy storage of a Krylov call (fn: vch1d_hess_lanczos or vch1d_hess_cg), one group: a refused request gives back what
+// this call got and leaves the context usable.  A request for more than the resident storage holds releases that storage
+// first.  Whatever an earlier call left resident in the basis is no longer valid: the caller overwrites it.
+static int kr1_storage(vch1d_ctx *c, const char *fn, int slots, int k, const double *phi_hist, const double *u, const double *phi_Q,
+                       const double *phi_T) {
+    const int B = c->B, n = c->n;
+    const size_t hist_bytes = (size_t)B * hs1(c) * sizeof(double);
+    c->kr_valid = c->ncg_valid = false;
+    if (c->kr_Q && (slots > c->kr_slots || k > c->kr_kcap)) {       // a larger basis than the resident storage holds
+        c->pool.drop((void **)&c->kr_sc);
+        c->pool.drop((void **)&c->kr_mask);
+        c->pool.drop((void **)&c->kr_W);
+        c->pool.drop((void **)&c->kr_V);
+        c->pool.drop((void **)&c->kr_X);
+        c->pool.drop((void **)&c->kr_Q);
+        c->kr_slots = c->kr_kcap = 0;
+    }
+    vch_group g(c->pool);
+    if (phi_hist) VCHCHK(ensure1(c, &c->so_base));
+    if (u && u != VCH_RESIDENT) VCHCHK(ensure1(c, &c->so_u));
+    if (phi_Q && phi_Q != VCH_RESIDENT) VCHCHK(ensure1(c, &c->so_pq));
+    if (phi_T && phi_T != VCH_RESIDENT) VCHCHK(dalloc1(c, &c->so_pt, (size_t)B * n));
+    VCHCHK(so1_grids_alloc(c));
+    if (!c->kr_Q) {
+        const Kr1Layout L = kr1_layout(c, slots, k);
+        const size_t need = (size_t)(slots + 3) * hist_bytes + hist_bytes / 8 + L.total * 8;
+        const bool ok = c->pool.dev(&c->kr_Q, (size_t)slots * hist_bytes) == 0 && c->pool.dev(&c->kr_X, hist_bytes) == 0 &&
+                        c->pool.dev(&c->kr_V, hist_bytes) == 0 && c->pool.dev(&c->kr_W, hist_bytes) == 0 &&
+                        c->pool.dev(&c->kr_mask, hist_bytes / 8) == 0 && c->pool.dev(&c->kr_sc, L.total * 8) == 0;
+        if (!ok) {
+            (void)hipGetLastError();
+            return vch_fail(VCH_ERR_NOMEM,
+                            "%s: the Krylov storage needs %zu bytes (%d basis vectors of %zu bytes, three more histories for "
+                            "the cached sweep, the tangent and w, %zu bytes of mask, %zu of partials) and was refused",
+                            fn, need, slots, hist_bytes, hist_bytes / 8, L.total * 8);
+        }
+        c->kr_slots = slots;
+        c->kr_kcap = k;
+    }
+    g.keep();
+    return 0;
 }
 
 extern "C" int vch1d_hess_lanczos(vch1d_ctx *c, const double *phi_hist, const double *u, int n_base, int rows, const double *dt,
@@ -996,42 +1045,7 @@ extern "C" int vch1d_hess_lanczos(vch1d_ctx *c, const double *phi_hist, const do
     // ---- nothing was launched, copied or allocated up to here
     const int M = rows - 2, slots = reorth ? k + 1 : 3;
     const long hs = hs1(c);
-    const size_t hist_bytes = (size_t)B * hs * sizeof(double);
-    c->kr_valid = false;
-    if (c->kr_Q && (slots > c->kr_slots || k > c->kr_kcap)) {       // a larger basis than the resident storage holds
-        c->pool.drop((void **)&c->kr_sc);
-        c->pool.drop((void **)&c->kr_mask);
-        c->pool.drop((void **)&c->kr_W);
-        c->pool.drop((void **)&c->kr_V);
-        c->pool.drop((void **)&c->kr_X);
-        c->pool.drop((void **)&c->kr_Q);
-        c->kr_slots = c->kr_kcap = 0;
-    }
-    {   // lazy storage, one group: a refused request gives back what this call got and leaves the context as it was
-        vch_group g(c->pool);
-        if (phi_hist) VCHCHK(ensure1(c, &c->so_base));
-        if (u && u != VCH_RESIDENT) VCHCHK(ensure1(c, &c->so_u));
-        if (phi_Q && phi_Q != VCH_RESIDENT) VCHCHK(ensure1(c, &c->so_pq));
-        if (phi_T && phi_T != VCH_RESIDENT) VCHCHK(dalloc1(c, &c->so_pt, (size_t)B * n));
-        VCHCHK(so1_grids_alloc(c));
-        if (!c->kr_Q) {
-            const Kr1Layout L = kr1_layout(c, slots, k);
-            const size_t need = (size_t)(slots + 3) * hist_bytes + hist_bytes / 8 + L.total * 8;
-            const bool ok = c->pool.dev(&c->kr_Q, (size_t)slots * hist_bytes) == 0 && c->pool.dev(&c->kr_X, hist_bytes) == 0 &&
-                            c->pool.dev(&c->kr_V, hist_bytes) == 0 && c->pool.dev(&c->kr_W, hist_bytes) == 0 &&
-                            c->pool.dev(&c->kr_mask, hist_bytes / 8) == 0 && c->pool.dev(&c->kr_sc, L.total * 8) == 0;
-            if (!ok) {
-                (void)hipGetLastError();
-                return vch_fail(VCH_ERR_NOMEM,
-                                "%s: the Krylov storage needs %zu bytes (%d basis vectors of %zu bytes, three more histories for "
-                                "the cached sweep, the tangent and w, %zu bytes of mask, %zu of partials) and was refused",
-                                fn, need, slots, hist_bytes, hist_bytes / 8, L.total * 8);
-            }
-            c->kr_slots = slots;
-            c->kr_kcap = k;
-        }
-        g.keep();
-    }
+    VCHCHK(kr1_storage(c, fn, slots, k, phi_hist, u, phi_Q, phi_T));
     const Kr1Layout L = kr1_layout(c, c->kr_slots, c->kr_kcap);
     const bool build = mask == nullptr;
     const Kr1Args K = kr1_args(c, L, rows, slots, (build || n_base == B) ? hs : 0);
@@ -1150,4 +1164,160 @@ extern "C" int vch1d_krylov_vector(vch1d_ctx *c, const double *coef, int m, doub
                             c->stream));
     LAUNCH(k1d_kr_lincomb, dim3(kr1_chunks(c, rows), B), dim3(KR1_T), K, m, (const double *)ucoef, c->kr_W);
     return down_hist(c, out, c->kr_W, rows);
+}
+
+// ------------------------------------------------------------------------------------
+// Newton-CG on the free set: (preconditioned) conjugate gradients on P H P x = P b with x, r, p, the free set and the
+// recurrence on the device (kernels: "Device-resident Newton-CG" in vch_kernels1d.h).  The storage, the
+// step kernel and the look schedule are those of vch1d_hess_lanczos without reorthogonalisation.
+// ------------------------------------------------------------------------------------
+extern "C" int vch1d_hess_cg(vch1d_ctx *c, const double *phi_hist, const double *u, int n_base, int rows, const double *dt,
+                             const double *t_hist, const double *x, const double *phi_Q, const double *phi_T,
+                             const vch_opt_params *opts, int n_opts, const uint8_t *mask, double tol, const double *rhs, int k,
+                             double cg_tol, int precond, double *resid_out, double *curv_out, double *pred_out, double *rnorm0_out,
+                             int32_t *steps_out, int32_t *status_out, int64_t *n_free_out, vch_stats *stats) {
+    CTXCHK(c);
+    const int B = c->B, n = c->n;
+    const char *fn = "vch1d_hess_cg";
+    VCHCHK(so1_check_shape(c, fn, n_base, rows, n_opts, 2));
+    if (!resid_out || !curv_out || !pred_out || !rnorm0_out || !steps_out || !status_out || !n_free_out)
+        return vch_fail(VCH_ERR_ARG, "%s: NULL resid_out, curv_out, pred_out, rnorm0_out, steps_out, status_out or n_free_out", fn);
+    if (k < 1) return vch_fail(VCH_ERR_ARG, "%s: k = %d must be >= 1", fn, k);
+    if (precond != 0 && precond != 1) return vch_fail(VCH_ERR_ARG, "%s: precond = %d is neither 0 nor 1", fn, precond);
+    if (!std::isfinite(cg_tol)) return vch_fail(VCH_ERR_ARG, "%s: cg_tol must be finite", fn);
+    if (!mask && !u) return vch_fail(VCH_ERR_ARG, "%s: NULL mask with a NULL (zero) control: no node is free", fn);
+    std::vector<double> dts, wts, wx;
+    VCHCHK(so1_check_rest(c, fn, phi_hist, u, rows, dt, t_hist, x, phi_Q, phi_T, opts, n_opts, dts, wts));
+    // trapezoid weights of t_hist as in vch1d_hessvec; the preconditioner's wt' gives row 0 (weight zero, but a real unknown)
+    // the weight of row 1, which duplicates its time
+    std::vector<double> wt(rows, 0.0);
+    for (int r = 0; r + 1 < rows; ++r) {
+        const double d = t_hist[r + 1] - t_hist[r];
+        wt[r] += 0.5 * d;
+        wt[r + 1] += 0.5 * d;
+    }
+    std::vector<double> wtp(wt);
+    wtp[0] = wt[1];
+    if (precond)
+        for (int r = 0; r < rows; ++r)
+            if (!(wtp[r] > 0.0) || !std::isfinite(wtp[r]))
+                return vch_fail(VCH_ERR_ARG, "%s: row %d: the preconditioner's time weight %g must be positive and finite (t_hist "
+                                "must increase from row 1 on)", fn, r, wtp[r]);
+    // ---- nothing was launched, copied or allocated up to here
+    const int M = rows - 2;
+    const long hs = hs1(c);
+    VCHCHK(kr1_storage(c, fn, 3, k, phi_hist, u, phi_Q, phi_T));
+    const Kr1Layout L = kr1_layout(c, c->kr_slots, c->kr_kcap);
+    const bool build = mask == nullptr;
+    double *sc = c->kr_sc;
+    // the cells of the iteration in the block of the Lanczos scalars: resid, curv where alpha, beta live
+    const Ncg1Cells cells{sc + L.alpha, sc + L.beta, sc + L.look, sc + L.scal, sc + L.amax, sc + L.coef1, sc + L.coef1 + B,
+                          sc + L.coef1 + 2 * B, (long long *)(sc + L.steps), (long long *)(sc + L.lim), (long long *)(sc + L.stop)};
+    const int S = c->kr_slots, nch = kr1_chunks(c, rows);
+    const Ncg1Args K{c->kr_Q, (long)B * hs, hs, (long)rows * n, n, S, c->kr_mask, (build || n_base == B) ? hs : 0,
+                     sc + L.wtp, c->so_wx, precond, cells};
+    double *part = sc + L.part;
+    const dim3 kgrid(nch, B);
+    double *r_slot = c->kr_Q + (long)NCG1_R * B * hs, *p_slot = c->kr_Q + (long)NCG1_P * B * hs;
+    const double stop_at = cg_tol > 0 ? cg_tol : 1e-8;
+    So1Base Sb;
+    VCHCHK(so1_base(c, phi_hist, u, phi_Q, phi_T, n_base, rows, Sb));
+    trapz_x(c, x, wx);
+    VCHCHK(so1_grids(c, dts, t_hist, rows, wx, wts));
+    std::vector<double> box(2 * (size_t)B), ks(B);
+    for (int b = 0; b < B; ++b) {
+        const vch_opt_params &o = vch_pgd_opt(opts, n_opts, b);
+        box[2 * b] = o.u_min;
+        box[2 * b + 1] = o.u_max;
+        ks[b] = o.kappa_sparsity;
+    }
+    VCHCHK(up(c, sc + L.wt, wt.data(), rows));
+    VCHCHK(up(c, sc + L.wtp, wtp.data(), rows));
+    VCHCHK(up(c, sc + L.box, box.data(), box.size()));
+    VCHCHK(up(c, sc + L.ks, ks.data(), ks.size()));
+    if (rhs) VCHCHK(up_hist(c, r_slot, rhs, rows));
+    if (mask)
+        for (int b = 0; b < n_base; ++b)
+            HIPCHK(hipMemcpyAsync(c->kr_mask + (size_t)b * hs, mask + (size_t)b * rows * n, (size_t)rows * n, hipMemcpyHostToDevice,
+                                  c->stream));
+    HIPCHK(hipMemsetAsync(cells.resid, 0xff, sizeof(double) * 2 * B * c->kr_kcap, c->stream));     // NaN: resid, then curv
+    Hv1Args G{};
+    G.hs = hs;
+    G.phi = Sb.phi; G.u = Sb.u; G.pq = Sb.pq; G.pt = Sb.pt;
+    G.phi_s = G.u_s = G.pq_s = Sb.bs;
+    G.pt_s = Sb.pts;
+    G.dts = c->so_dts; G.wt = sc + L.wt; G.wx = c->so_wx; G.wts = c->so_wts;
+    G.hd = p_slot; G.hv = c->kr_W; G.v = c->kr_V; G.mean = sc + L.mean;
+    HIPCHK(hipEventRecord(c->ev0, c->stream));
+    // the set-up: the free set, the gradient sweep once per base point (yp of every step stays in kr_X), r = P b, x, p
+    double *keepX = c->kr_nocache ? nullptr : c->kr_X;
+    if (rhs)
+        LAUNCH_LDS(-1, (k1d_ncg_setup<0>), dim3(B), dim3(T1), c->lds_bytes, c->P, n, c->h, c->lvl, rows, G, K,
+                   (const double *)(sc + L.box), (const double *)(sc + L.ks), tol > 0 ? tol : 1e-8, build ? 1 : 0,
+                   c->kr_nocache ? 0 : 1, keepX, c->scratch);
+    else
+        LAUNCH_LDS(-1, (k1d_ncg_setup<1>), dim3(B), dim3(T1), c->lds_bytes, c->P, n, c->h, c->lvl, rows, G, K,
+                   (const double *)(sc + L.box), (const double *)(sc + L.ks), tol > 0 ? tol : 1e-8, build ? 1 : 0, 1, keepX,
+                   c->scratch);
+    std::vector<double> look(2 * (size_t)B);
+    VCHCHK(down(c, look.data(), cells.look, look.size()));          // the first look; the host vectors above are done with
+    for (int b = 0; b < B; ++b) {
+        if (look[2 * b] < 1.0) return vch_fail(VCH_ERR_ARG, "%s: trajectory %d: the free set is empty", fn, b);
+        if (!std::isfinite(look[2 * b + 1]))
+            return vch_fail(VCH_ERR_ARG, "%s: trajectory %d: the right-hand side is not finite on the free set", fn, b);
+    }
+    // k steps back to back: a stopped trajectory's kernels return at once, the host does not look
+    for (int j = 0; j < k; ++j) {
+        if (c->kr_nocache)
+            LAUNCH_LDS(-1, (k1d_kr_step<1>), dim3(B), dim3(T1), c->lds_bytes, c->P, n, c->h, c->lvl, rows, G, (const long long *)cells.stop,
+                       (const double *)c->kr_X, c->scratch);
+        else
+            LAUNCH_LDS(-1, (k1d_kr_step<0>), dim3(B), dim3(T1), c->lds_bytes, c->P, n, c->h, c->lvl, rows, G, (const long long *)cells.stop,
+                       (const double *)c->kr_X, c->scratch);
+        // w = H p in kr_W
+        LAUNCH(k1d_ncg_curv, kgrid, dim3(KR1_T), K, (const double *)c->kr_W, part);
+        LAUNCH(k1d_ncg_fin, dim3(B), dim3(KR1_T), cells, (const double *)part, nch, S, 2, j, k, stop_at);
+        LAUNCH(k1d_ncg_update, kgrid, dim3(KR1_T), K, (const double *)c->kr_W, part);
+        LAUNCH(k1d_ncg_fin, dim3(B), dim3(KR1_T), cells, (const double *)part, nch, S, 3, j, k, stop_at);
+        if (j + 1 < k) LAUNCH(k1d_ncg_dir, kgrid, dim3(KR1_T), K);
+    }
+    HIPCHK(hipEventRecord(c->ev1, c->stream));
+    std::vector<long long> steps(B), prods(B), stop(B);
+    HIPCHK(hipMemcpyAsync(resid_out, cells.resid, sizeof(double) * B * k, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(curv_out, cells.curv, sizeof(double) * B * k, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(pred_out, cells.pred, sizeof(double) * B, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(rnorm0_out, cells.rnorm0, sizeof(double) * B, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(steps.data(), cells.steps, sizeof(long long) * B, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(prods.data(), cells.prods, sizeof(long long) * B, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(stop.data(), cells.stop, sizeof(long long) * B, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));                        // the second look
+    int64_t solves = 0;
+    for (int b = 0; b < B; ++b) {
+        steps_out[b] = (int32_t)steps[b];
+        status_out[b] = (int32_t)stop[b];           // 0: still running after k steps, VCH_CG_LIMIT
+        n_free_out[b] = (int64_t)look[2 * b];
+        // the set-up's sweep: always with the cache; with the switch only where the right-hand side is built from it
+        solves += c->kr_nocache ? 3 * (int64_t)M * prods[b] + (rhs ? 0 : M) : (int64_t)M * (2 * prods[b] + 1);
+    }
+    if (stats) {
+        float ms = 0;
+        hipEventElapsedTime(&ms, c->ev0, c->ev1);
+        memset(stats, 0, sizeof(*stats));
+        stats->linear_solves = solves;
+        stats->launches = 6 * (int64_t)k;           // the set-up, five per step, the direction between two steps
+        stats->host_syncs = 2;
+        stats->seconds = ms * 1e-3;
+    }
+    c->ncg_valid = true;
+    c->ncg_rows = rows;
+    return 0;
+}
+
+extern "C" int vch1d_cg_vector(vch1d_ctx *c, int which, double *out) {
+    CTXCHK(c);
+    ARGCHK(out, "NULL out");
+    ARGCHK(which >= 0 && which <= 2, "which must be 0 (x), 1 (r) or 2 (p)");
+    if (!c->ncg_valid || !c->kr_Q)
+        return vch_fail(VCH_ERR_STATE, "vch1d_cg_vector: no resident vectors (call vch1d_hess_cg first)");
+    return down_hist(c, out, c->kr_Q + (long)which * c->B * hs1(c), c->ncg_rows);
 }

@@ -1400,3 +1400,339 @@ __global__ __launch_bounds__(KR1_T) void k1d_kr_fin(Kr1Cells x, const double *__
     x.stop[b] = (broke || j + 1 >= (long long)x.look[2 * b]) ? 2 : (j + 1 >= lim ? 1 : 0);
     x.scal[b] = beta;
 }
+
+// ---------------------------------------------------------------------------------
+// Device-resident Newton-CG on the free set (vch1d_hess_cg): (preconditioned) conjugate gradients on
+// P H P x = P b from x_0 = 0 with x, r and p in slots 0, 1, 2 of the basis storage of the Lanczos iteration above.
+//   k1d_ncg_setup  (persistent, grid B) the free set and its size, the gradient sweep once (yp of every step to X; NEWTON:
+//                  G accumulated with the expressions of k1d_hessvec<1>), r = P b, x = 0, p = D^-1 r, ||P b|| and
+//                  rho = r.D^-1 r by the workgroup's fixed-order sums, the cells of a new iteration
+//   k1d_kr_step    as above, unchanged: G.hd = the p slot, G.hv = w.  The stop cell holds VCH_CG_* of vch.h: running is
+//                  VCH_CG_LIMIT = 0, so every way of stopping is non-zero, which is all k1d_kr_step tests
+//   k1d_ncg_curv, k1d_ncg_update, k1d_ncg_dir   the recurrence on the (chunks of KR1_CHUNK, B) grid, partials
+//                  [B][chunks][S]; k1d_ncg_fin (grid B) sums them in the order of kr1_sum and keeps the scalars
+// D = diag(wt'_k wx_i) with wt' = the trapezoid weights of t_hist except wt'_0 := wt_1 (row 0 has quadrature weight zero
+// but is a real unknown: it drives step 0), computed per node and not stored; the identity without the preconditioner.
+// A thread keeps its KR1_PER nodes in registers and requests every global operand of its chunk before the first use.
+// P is applied where w is read; masked-off nodes of x, r and p are exact zeros.  Every kernel of a stopped trajectory
+// returns at once, so its x, r and p stay as the stopping step left them.  No atomics.
+// ---------------------------------------------------------------------------------
+enum { NCG1_X = 0, NCG1_R = 1, NCG1_P = 2 };
+enum { NCG1_RUNNING = 0, NCG1_CONVERGED = 1, NCG1_NEGCURV = 2, NCG1_BREAKDOWN = 3 };    // the stop cell: VCH_CG_* of vch.h
+struct Ncg1Cells {
+    double *resid, *curv;             // [B][k]
+    double *look;                     // [B][2] what the host reads after the set-up: n_free, ||P b||
+    double *alpha, *beta;             // [B] the step length of k1d_ncg_update, the factor of k1d_ncg_dir
+    double *rho, *rnorm0, *pred;      // [B]
+    long long *steps, *prods, *stop;  // [B] updates of x, products H p taken, VCH_CG_*
+};
+struct Ncg1Args {
+    double *Q;                        // x, r, p: slots 0, 1, 2
+    long slot_stride, hs;             // doubles between two slots / two trajectories
+    long tot;                         // nodes of a trajectory's vector (rows * n)
+    int n, S;                         // nodes of a row; stride of a partial
+    unsigned char *mask;              // [B or 1][hs] bytes, non-zero = free
+    long mask_s;                      // bytes between two trajectories' masks (0: one for the batch)
+    const double *wtp, *wx;           // [rows] wt', [n]
+    int precond;
+    Ncg1Cells x;
+};
+__device__ __forceinline__ double *ncg1_slot(const Ncg1Args &a, int i) { return a.Q + (long)i * a.slot_stride; }
+
+// grid = B workgroups.  NEWTON 0: the right-hand side is in slot 1 on entry.  NEWTON 1: b = -(G + ks_b wt_k wx_i sign(u)),
+// G the gradient field of J1 + J2 + J3 accumulated in slot 1 by the sweep.  box [B][2] = {u_min, u_max}, ks [B].
+// sweep 0: no gradient sweep for an uploaded right-hand side (the steps repeat it); X NULL: yp is not kept.  A trajectory
+// whose free set is empty or whose ||P b|| is not finite gets stop = BREAKDOWN and the host reads look; ||P b|| == 0 is
+// CONVERGED.  With an uploaded right-hand side all three return before the sweep.
+template <int NEWTON>
+__global__ __launch_bounds__(T1) void k1d_ncg_setup(Phys1 P, int n, double h, int lvl, int rows, Hv1Args G, Ncg1Args K,
+                                                    const double *__restrict__ box, const double *__restrict__ ks, double tol,
+                                                    int build, int sweep, double *X, double *scratch) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    __shared__ double sk[3 * (T1 / 64)];
+    const int b = blockIdx.x, tid = threadIdx.x, M = rows - 2;
+    const double a = 1.0 / (h * h);
+    const double *uu = G.u ? G.u + b * G.u_s : nullptr;
+    unsigned char *mk = K.mask + b * K.mask_s;
+    double *xs = ncg1_slot(K, NCG1_X) + b * K.hs, *rs = ncg1_slot(K, NCG1_R) + b * K.hs, *ps = ncg1_slot(K, NCG1_P) + b * K.hs;
+    const double lo = box[2 * b] + tol, hi = box[2 * b + 1] - tol;
+    double S[3] = {0.0, 0.0, 0.0};          // n_free (exact in a double), r.r, r.D^-1 r
+    // r = P b, x = 0, p = D^-1 r of row `row` from the right-hand side bv(o, i), with the sums
+    auto start_row = [&](int row, auto bv) {
+        const long o = (long)row * n;
+        const double wr = K.precond ? K.wtp[row] : 1.0;
+        for (int i = tid; i < n; i += T1) {
+            const double rv = mk[o + i] ? bv(o, i) : 0.0;
+            const double z = rv / (K.precond ? wr * K.wx[i] : 1.0);
+            xs[o + i] = 0.0;
+            rs[o + i] = rv;
+            ps[o + i] = z;
+            S[1] += rv * rv;
+            S[2] += rv * z;
+        }
+    };
+    for (int row = 0; row < rows; ++row) {
+        const long o = (long)row * n;
+        for (int i = tid; i < n; i += T1) {
+            bool m;
+            if (build) {
+                const double v = uu ? uu[o + i] : 0.0;
+                m = v > lo && v < hi && fabs(v) > tol;
+                mk[o + i] = m ? 1 : 0;
+            } else {
+                m = mk[o + i] != 0;
+            }
+            S[0] += m ? 1.0 : 0.0;
+        }
+        if (!NEWTON) start_row(row, [&](long oo, int i) { return rs[oo + i]; });
+    }
+    if (NEWTON) {
+        double C[1] = {S[0]};
+        block_sums<1>(C, sk);
+        if (C[0] < 1.0) {                   // uniform over the workgroup: nothing to sweep for
+            if (tid == 0) {
+                K.x.look[2 * b] = 0.0;
+                K.x.look[2 * b + 1] = 0.0;
+                K.x.stop[b] = NCG1_BREAKDOWN;
+            }
+            return;
+        }
+        // the gradient sweep of k1d_hessvec<1>, G in slot 1: each thread its own nodes of every row
+        double *q = scratch + (long)b * NSCR1 * n;
+        const Kr1Base T{G.phi + b * G.phi_s, G.pq ? G.pq + b * G.pq_s : nullptr, G.pt ? G.pt + b * G.pt_s : nullptr, G.wts[3 * b],
+                        G.wts[3 * b + 1]};
+        const double b3 = G.wts[3 * b + 2];
+        for (int row = 0; row < rows; ++row) {
+            const long o = (long)row * n;
+            const double wr = G.wt[row];
+            for (int i = tid; i < n; i += T1) {
+                const double w = b3 * (wr * G.wx[i]);
+                rs[o + i] = w * (uu ? uu[o + i] : 0.0);
+            }
+        }
+        for (int i = tid; i < n; i += T1) q[i] = q[n + i] = q[2 * n + i] = 0.0;
+        __syncthreads();
+        for (int k = M - 1; k >= 0; --k) {
+            kr1_grad_solve(P, n, a, lvl, G, T, k, M, q, lds, sk);
+            const double gdt = P.gamma / G.dts[k], be = 0.5 / (gdt + 0.5);
+            for (int i = tid; i < n; i += T1) {
+                const double y = q[4 * n + i], ldw = 0.5 * y + q[2 * n + i];
+                rs[(long)k * n + i] += be * ldw;
+                rs[(long)(k + 1) * n + i] += be * ldw;
+            }
+            kr1_grad_update(P, n, a, G, k, q, X ? X + b * K.hs + (long)(k + 2) * n : nullptr);
+            __syncthreads();
+        }
+        const double kb = ks[b];
+        for (int row = 0; row < rows; ++row) {
+            const double kw = kb * G.wt[row];
+            start_row(row, [&](long oo, int i) {
+                const double v = uu ? uu[oo + i] : 0.0;
+                const double sgn = v > 0.0 ? 1.0 : (v < 0.0 ? -1.0 : 0.0);
+                return -(rs[oo + i] + kw * (G.wx[i] * sgn));
+            });
+        }
+        S[0] = 0.0;                         // summed above: the count comes back below
+        block_sums<3>(S, sk);
+        S[0] = C[0];
+    } else {
+        block_sums<3>(S, sk);
+    }
+    const double nrm = sqrt(S[1]);
+    const bool bad = S[0] < 1.0 || !isfinite(nrm);
+    if (tid == 0) {
+        K.x.look[2 * b] = S[0];
+        K.x.look[2 * b + 1] = nrm;
+        K.x.rnorm0[b] = nrm;
+        K.x.rho[b] = S[2];
+        K.x.pred[b] = 0.0;
+        K.x.steps[b] = 0;
+        K.x.prods[b] = 0;
+        K.x.stop[b] = bad ? NCG1_BREAKDOWN : (nrm == 0.0 ? NCG1_CONVERGED : NCG1_RUNNING);
+    }
+    if (NEWTON || bad || nrm == 0.0 || !sweep) return;      // uniform over the workgroup
+    double *q = scratch + (long)b * NSCR1 * n;
+    const Kr1Base T{G.phi + b * G.phi_s, G.pq ? G.pq + b * G.pq_s : nullptr, G.pt ? G.pt + b * G.pt_s : nullptr, G.wts[3 * b],
+                    G.wts[3 * b + 1]};
+    for (int i = tid; i < n; i += T1) q[i] = q[n + i] = q[2 * n + i] = 0.0;
+    __syncthreads();
+    for (int k = M - 1; k >= 0; --k) {
+        kr1_grad_solve(P, n, a, lvl, G, T, k, M, q, lds, sk);
+        kr1_grad_update(P, n, a, G, k, q, X + b * K.hs + (long)(k + 2) * n);
+        __syncthreads();
+    }
+}
+
+// The nodes of a thread of the streaming kernels are i0 + t KR1_T, t < KR1_PER, below i1; d[t] = D of node t (1 beyond i1).
+#define NCG1_COORDS                                                                                                      \
+    const int b = blockIdx.y, tid = threadIdx.x;                                                                         \
+    const long hb = b * a.hs, i0 = (long)blockIdx.x * KR1_CHUNK + tid, i1 = min((long)(blockIdx.x + 1) * KR1_CHUNK, a.tot)
+__device__ __forceinline__ void ncg1_diag(const Ncg1Args &a, long i0, long i1, double (&d)[KR1_PER]) {
+    if (!a.precond) {
+#pragma unroll
+        for (int t = 0; t < KR1_PER; ++t) d[t] = 1.0;
+        return;
+    }
+    long row = i0 / a.n;
+    int col = (int)(i0 - row * a.n);
+#pragma unroll
+    for (int t = 0; t < KR1_PER; ++t) {
+        d[t] = i0 + t * KR1_T < i1 ? a.wtp[row] * a.wx[col] : 1.0;
+        col += KR1_T;
+        const int up = col / a.n;
+        row += up;
+        col -= up * a.n;
+    }
+}
+// The two sums of a workgroup into its partial: wave sums, then the four waves in a fixed order.
+__device__ __forceinline__ void ncg1_store2(double s0, double s1, double *sred, double *my) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    s0 = wsum1(s0);
+    s1 = wsum1(s1);
+    if (lane == 0) {
+        sred[wv] = s0;
+        sred[KR1_T / 64 + wv] = s1;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        const double *s = sred + threadIdx.x * (KR1_T / 64);
+        my[threadIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);
+    }
+}
+
+// Partials {p.(P w), p.D p}; w = H p of the step kernel just run.
+__global__ __launch_bounds__(KR1_T) void k1d_ncg_curv(Ncg1Args a, const double *__restrict__ w, double *__restrict__ part) {
+    NCG1_COORDS;
+    if (a.x.stop[b]) return;                // uniform over the workgroup
+    __shared__ double sred[2 * (KR1_T / 64)];
+    const unsigned char *mk = a.mask + b * a.mask_s;
+    const double *ps = ncg1_slot(a, NCG1_P) + hb, *wb = w + hb;
+    double pv[KR1_PER], hv[KR1_PER], d[KR1_PER];
+    unsigned char m[KR1_PER];
+#pragma unroll
+    for (int t = 0; t < KR1_PER; ++t) {
+        const long i = i0 + t * KR1_T;
+        const bool in = i < i1;
+        pv[t] = in ? ps[i] : 0.0;
+        hv[t] = in ? wb[i] : 0.0;
+        m[t] = in ? mk[i] : 0;
+    }
+    ncg1_diag(a, i0, i1, d);
+    double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+    for (int t = 0; t < KR1_PER; ++t) {
+        s0 += pv[t] * (m[t] ? hv[t] : 0.0);
+        s1 += pv[t] * (d[t] * pv[t]);
+    }
+    ncg1_store2(s0, s1, sred, part + ((long)b * gridDim.x + blockIdx.x) * a.S);
+}
+
+// x += alpha p, r -= alpha P w; partials {r.r, r.D^-1 r} of the new residual.
+__global__ __launch_bounds__(KR1_T) void k1d_ncg_update(Ncg1Args a, const double *__restrict__ w, double *__restrict__ part) {
+    NCG1_COORDS;
+    if (a.x.stop[b]) return;
+    __shared__ double sred[2 * (KR1_T / 64)];
+    const unsigned char *mk = a.mask + b * a.mask_s;
+    double *xs = ncg1_slot(a, NCG1_X) + hb, *rs = ncg1_slot(a, NCG1_R) + hb;
+    const double *ps = ncg1_slot(a, NCG1_P) + hb, *wb = w + hb;
+    const double al = a.x.alpha[b];
+    double xv[KR1_PER], rv[KR1_PER], pv[KR1_PER], hv[KR1_PER], d[KR1_PER];
+    unsigned char m[KR1_PER];
+#pragma unroll
+    for (int t = 0; t < KR1_PER; ++t) {
+        const long i = i0 + t * KR1_T;
+        const bool in = i < i1;
+        xv[t] = in ? xs[i] : 0.0;
+        rv[t] = in ? rs[i] : 0.0;
+        pv[t] = in ? ps[i] : 0.0;
+        hv[t] = in ? wb[i] : 0.0;
+        m[t] = in ? mk[i] : 0;
+    }
+    ncg1_diag(a, i0, i1, d);
+    double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+    for (int t = 0; t < KR1_PER; ++t) {
+        const long i = i0 + t * KR1_T;
+        const double r = rv[t] - al * (m[t] ? hv[t] : 0.0);
+        if (i < i1) {
+            xs[i] = xv[t] + al * pv[t];
+            rs[i] = r;
+        }
+        s0 += r * r;
+        s1 += r * (r / d[t]);
+    }
+    ncg1_store2(s0, s1, sred, part + ((long)b * gridDim.x + blockIdx.x) * a.S);
+}
+
+// p = D^-1 r + beta p, in its slot: the next step kernel reads its direction there.
+__global__ __launch_bounds__(KR1_T) void k1d_ncg_dir(Ncg1Args a) {
+    NCG1_COORDS;
+    if (a.x.stop[b]) return;
+    const double *rs = ncg1_slot(a, NCG1_R) + hb;
+    double *ps = ncg1_slot(a, NCG1_P) + hb;
+    const double be = a.x.beta[b];
+    double rv[KR1_PER], pv[KR1_PER], d[KR1_PER];
+#pragma unroll
+    for (int t = 0; t < KR1_PER; ++t) {
+        const long i = i0 + t * KR1_T;
+        rv[t] = i < i1 ? rs[i] : 0.0;
+        pv[t] = i < i1 ? ps[i] : 0.0;
+    }
+    ncg1_diag(a, i0, i1, d);
+#pragma unroll
+    for (int t = 0; t < KR1_PER; ++t) {
+        const long i = i0 + t * KR1_T;
+        if (i < i1) ps[i] = rv[t] / d[t] + be * pv[t];
+    }
+}
+#undef NCG1_COORDS
+
+// kr1_sum, word for word (the same order of additions).  A copy, not a call: a second kernel calling kr1_sum can change
+// the registers k1d_kr_fin compiles to (DESIGN.md 10g found that for the 2D pair).
+__device__ __forceinline__ double ncg1_sum(const double *__restrict__ part, int nch, int S, int slot, double *sh) {
+    double s = 0.0;
+    for (int e = threadIdx.x; e < nch; e += KR1_T) s += part[(long)e * S + slot];
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    for (int hh = KR1_T / 2; hh > 0; hh >>= 1) {
+        if ((int)threadIdx.x < hh) sh[threadIdx.x] += sh[threadIdx.x + hh];
+        __syncthreads();
+    }
+    const double r = sh[0];
+    __syncthreads();
+    return r;
+}
+// The scalars of a step, one workgroup per trajectory:
+//   mode 2   step j, after k1d_ncg_curv: c = p.P H p, n = p.D p, curv[j] = c / n, one more product taken; c not finite:
+//            BREAKDOWN; !(c > 0): NEGCURV; otherwise alpha = rho / c
+//   mode 3   step j, after k1d_ncg_update: pred += alpha rho / 2, resid[j] = ||r|| / ||P b||, steps = j + 1; not finite:
+//            BREAKDOWN; resid[j] <= cg_tol: CONVERGED; otherwise beta = rho_new / rho
+__global__ __launch_bounds__(KR1_T) void k1d_ncg_fin(Ncg1Cells x, const double *__restrict__ part, int nch, int S, int mode, int j,
+                                                     int k, double cg_tol) {
+    __shared__ double sh[KR1_T];
+    const int b = blockIdx.x;
+    const double *p = part + (long)b * nch * S;
+    if (x.stop[b]) return;                  // uniform: stopped at an earlier step
+    const double s0 = ncg1_sum(p, nch, S, 0, sh), s1 = ncg1_sum(p, nch, S, 1, sh);
+    if (threadIdx.x != 0) return;
+    long long st = NCG1_RUNNING;
+    if (mode == 2) {
+        x.curv[(long)b * k + j] = s0 / s1;
+        x.prods[b] = j + 1;
+        if (!isfinite(s0)) st = NCG1_BREAKDOWN;
+        else if (!(s0 > 0.0)) st = NCG1_NEGCURV;
+        else x.alpha[b] = x.rho[b] / s0;
+    } else {
+        const double rho = x.rho[b], res = sqrt(s0) / x.rnorm0[b];
+        x.pred[b] += 0.5 * x.alpha[b] * rho;
+        x.resid[(long)b * k + j] = res;
+        x.steps[b] = j + 1;
+        if (!isfinite(res) || !isfinite(s1)) st = NCG1_BREAKDOWN;
+        else if (res <= cg_tol) st = NCG1_CONVERGED;
+        else {
+            x.beta[b] = s1 / rho;
+            x.rho[b] = s1;
+        }
+    }
+    x.stop[b] = st;
+}

@@ -949,6 +949,17 @@ class Engine1D:
         return self.hessvec(None, t_hist, opt, phi_hist=phi_hist, u=u, phi_Q=phi_Q, phi_T=phi_T, dt=dt, x=x, order=1,
                             shared_base=shared_base)["grad"]
 
+    def _free_mask(self, mask, rows, nb):
+        """A free set as (nb, rows, N+1) bytes (None stays None: built on the device)."""
+        if mask is None:
+            return None
+        mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if mask.shape == (rows, self.n) and nb == 1:
+            mask = mask.reshape((1,) + mask.shape)
+        if mask.shape != (nb, rows, self.n):
+            raise ValueError(f"mask must have shape ({nb}, {rows}, {self.n}), got {mask.shape}")
+        return mask
+
     def hess_lanczos(self, q0, k, t_hist, opt, phi_hist=None, u=None, phi_Q=None, phi_T=None, dt=None, x=None, mask=None,
                      tol=0.0, reorth=True, shared_base=False):
         """Lanczos on the reduced Hessian P H P with the basis, the free set and the recurrence on the device
@@ -960,12 +971,7 @@ class Engine1D:
         t_hist, rows, nb, keep, dt, x, arr = self._base_point(t_hist, phi_hist, u, phi_Q, phi_T, dt, x, opt, shared_base)
         k = int(k)
         q0 = None if q0 is None else self._hist(q0, rows, "q0")
-        if mask is not None:
-            mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
-            if mask.shape == (rows, self.n) and nb == 1:
-                mask = mask.reshape((1,) + mask.shape)
-            if mask.shape != (nb, rows, self.n):
-                raise ValueError(f"mask must have shape ({nb}, {rows}, {self.n}), got {mask.shape}")
+        mask = self._free_mask(mask, rows, nb)
         kk = max(k, 1)
         alpha, beta = np.full((self.B, kk), np.nan), np.full((self.B, kk), np.nan)
         steps, n_free = np.zeros(self.B, dtype=np.int32), np.zeros(self.B, dtype=np.int64)
@@ -988,4 +994,44 @@ class Engine1D:
             raise ValueError(f"coef must have shape ({self.B}, m), got {coef.shape}")
         out = np.empty((self.B, getattr(self, "_kr_rows", 1), self.n))
         check(self.lib.vch1d_krylov_vector(self.ctx, _dp(coef), int(coef.shape[1]), _dp(out)))
+        return out
+
+    CG_STATUS = ("limit", "converged", "negcurv", "breakdown")      # VCH_CG_LIMIT .. VCH_CG_BREAKDOWN
+
+    def hess_cg(self, k, t_hist, opt, rhs=None, cg_tol=0.0, precond=True, mask=None, tol=0.0, phi_hist=None, u=None,
+                phi_Q=None, phi_T=None, dt=None, x=None, shared_base=False):
+        """(Preconditioned) conjugate gradients on P H P x = P b with x, r, p, the free set and the recurrence on the
+        device (vch1d_hess_cg); base point, mask and tol as for hess_lanczos.  rhs: (B, rows, N+1), or None: the Newton
+        right-hand side -(grad(J1+J2+J3) + kappa_sparsity wt wx sign(u)) of the full cost on the free set, built on the
+        device.  precond: scale by diag(wt' wx), the L2(Q) mass of the control with row 0 taking the time weight of row 1.
+        cg_tol: relative residual at which a trajectory stops (<= 0: 1e-8); k: steps at most.
+        Returns dict(steps, status (indices of CG_STATUS), n_free: [B]; resid, curv: (B, k), NaN beyond steps (curv[steps]
+        is the stopping curvature after "negcurv"); pred: [B] decrease of the quadratic model; rnorm0: [B] ||P b||; stats)."""
+        t_hist, rows, nb, keep, dt, x, arr = self._base_point(t_hist, phi_hist, u, phi_Q, phi_T, dt, x, opt, shared_base)
+        k = int(k)
+        rhs = None if rhs is None else self._hist(rhs, rows, "rhs")
+        mask = self._free_mask(mask, rows, nb)
+        kk = max(k, 1)
+        resid, curv = np.full((self.B, kk), np.nan), np.full((self.B, kk), np.nan)
+        pred, rnorm0 = np.full(self.B, np.nan), np.full(self.B, np.nan)
+        steps, status, n_free = np.zeros(self.B, dtype=np.int32), np.zeros(self.B, dtype=np.int32), np.zeros(self.B, dtype=np.int64)
+        st = Stats()
+        precond = int(precond) if isinstance(precond, (bool, int, np.integer)) else -1
+        check(self.lib.vch1d_hess_cg(self.ctx, keep[0][1], keep[1][1], nb, rows, _dp(dt), _dp(t_hist), _dp(x), keep[2][1],
+                                     keep[3][1], arr, len(arr),
+                                     None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint8)), float(tol),
+                                     _dp(rhs), k, float(cg_tol), precond, _dp(resid), _dp(curv), _dp(pred), _dp(rnorm0),
+                                     steps.ctypes.data_as(_lib._I32), status.ctypes.data_as(_lib._I32),
+                                     n_free.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(st)))
+        self._cg_rows = rows
+        return dict(steps=steps, status=status, n_free=n_free, resid=resid, curv=curv, pred=pred, rnorm0=rnorm0,
+                    stats=st.as_dict())
+
+    def cg_vector(self, which="x"):
+        """(B, rows, N+1): the solution x, the residual r or the direction p the last hess_cg left resident
+        (vch1d_cg_vector); masked-off nodes are exact zeros."""
+        if which not in ("x", "r", "p"):
+            raise ValueError(f"which must be 'x', 'r' or 'p', got {which!r}")
+        out = np.empty((self.B, getattr(self, "_cg_rows", 1), self.n))
+        check(self.lib.vch1d_cg_vector(self.ctx, "xrp".index(which), _dp(out)))
         return out
