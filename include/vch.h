@@ -431,6 +431,57 @@ int vch2d_hess_cg(vch2d_ctx *ctx, const double *dt, int M, const double *t_hist,
 /* out = x (which 0), r (1) or p (2) of the last vch2d_hess_cg of this context; masked-off nodes are exact zeros.
  * VCH_ERR_STATE without resident vectors (no call yet, a failed call, or a vch2d_hess_lanczos since). */
 int vch2d_cg_vector(vch2d_ctx *ctx, int which /* 0: x, 1: r, 2: p */, double *out /* [B][M+1][Nx+1][Ny+1] */);
+/* Damped Newton rounds on the free set about the resident PGD iterate, batched, with every trajectory's own parameters and
+ * decisions (ABI version stays 3: detect both entry points by symbol).  No history crosses the bus.
+ * Per round:
+ *   1. the Newton-CG solve of vch2d_hess_cg in its PGD mode (rhs = NULL, mask = NULL, the problem's targets, trajectory b
+ *      with the opts[b] of vch2d_pgd_init_v; k, cg_tol, precond, tol, rtol as passed).  Storage: that of vch2d_hess_cg and
+ *      the PGD scratch, no further history.
+ *   2. a trajectory ends here without a trial with VCH_NEWTON_STATIONARY (||P b|| == 0 or an empty free set, which is no
+ *      error in this call), VCH_NEWTON_NEGCURV (the first CG direction has non-positive curvature) or
+ *      VCH_NEWTON_BREAKDOWN (CG status VCH_CG_BREAKDOWN: a march under a control that may not be finite is never started).
+ *      Otherwise x after VCH_CG_CONVERGED, VCH_CG_LIMIT or VCH_CG_NEGCURV with steps > 0 is the step.
+ *   3. trials for s = 1, 1/2, ..., at most max_halvings halvings: t = clip(u + s x, box_b), a free node whose sign the
+ *      trial flips is set to 0 (k_nt_trial into the trial-control scratch), a march of t into the trial-state scratch and its
+ *      cost.  The first s with J(t) <= cost_b - 1e-4 s pred_b is accepted: control, state history and shift record are
+ *      copied as the PGD loop copies an accepted trial, and the five cost scalars become the iterate's (VCH_NEWTON_ACCEPTED).
+ *      When no s is accepted the trajectory is left unmoved with VCH_NEWTON_STALLED.
+ * A trajectory that has ended sits out all later rounds: VCH_NEWTON_IDLE, its doubles NaN, its integers 0; its solves are not
+ * gated.  The others go on; the call returns the number of rounds run (it stops early once every trajectory has ended).
+ * Outputs, all [B][n_rounds] and all required: cost_out (the iterate's cost before the round), cost_new_out (the accepted
+ * trial's, else the unchanged cost), s_out (the accepted s, else NaN), pred_out, rnorm0_out, halvings_out (halvings made in the
+ * round), cg_steps_out, cg_status_out (VCH_CG_*), status_out (VCH_NEWTON_*), counts_out [B][n_rounds][3] = {n_free, and of the
+ * round's last trial: nodes pinned to 0, nodes the clip moved}; seconds_out [4] (may be NULL) = {solves, trial kernel, marches,
+ * costs}.  Up to 32 trajectories; a trajectory's outputs and its iterate are bitwise those of a single-trajectory context.
+ * Afterwards vch2d_pgd_get, vch2d_second_order, vch2d_hessvec, vch2d_hess_lanczos and vch2d_hess_cg work about the new iterate,
+ * vch2d_cg_vector returns the last round's vectors, the adjoint r of vch2d_pgd_kkt(refresh = 0) is invalid once any trajectory
+ * moved, and the counters of the PGD loop (iteration count, plateau, next first step, stop flags, cost ring) are untouched:
+ * a following vch2d_pgd_iterate is that of vch2d_pgd_init_v with u0 = the Newton iterate.  The solver tolerance of the context
+ * is restored on every path out.
+ * Errors, all before anything is enqueued, copied or allocated: VCH_ERR_STATE before vch2d_pgd_init / _init_v (or when the
+ * resident state is no longer the PGD iterate); VCH_ERR_ARG for n_rounds < 1, k < 1, max_halvings < 0, precond outside 0 / 1,
+ * a cg_tol that is not finite and NULL outputs.  A ||P b|| that is not finite is VCH_ERR_ARG naming the trajectory, as in
+ * vch2d_hess_cg. */
+#define VCH_NEWTON_ACCEPTED 0
+#define VCH_NEWTON_STATIONARY 1
+#define VCH_NEWTON_NEGCURV 2
+#define VCH_NEWTON_BREAKDOWN 3
+#define VCH_NEWTON_STALLED 4
+#define VCH_NEWTON_IDLE 5
+int vch2d_pgd_newton(vch2d_ctx *ctx, int n_rounds, int k, double cg_tol, int precond /* 0 | 1 */, double tol, double rtol,
+                     int max_halvings, double *cost_out, double *cost_new_out, double *s_out, double *pred_out,
+                     double *rnorm0_out /* [B][n_rounds] */, int32_t *halvings_out, int32_t *cg_steps_out,
+                     int32_t *cg_status_out, int32_t *status_out /* [B][n_rounds] */,
+                     int64_t *counts_out /* [B][n_rounds][3]: n_free, pinned, clipped */, double *seconds_out /* [4] */);
+/* The trial kernel's seam: t = min(max(u + s_b x, u_min_b), u_max_b) with u the resident control (rows beyond the march's
+ * control are zeros), x and the free set those the last successful vch2d_hess_cg (forward or PGD mode) left resident and the
+ * box that call's opts; a free node with t u < 0 becomes 0.  Writes only the trial-control scratch and leaves x, r, p resident.
+ * u_out (may be NULL): the trial; chg_out [B][2] = {sum (t - u)^2, sum u^2} in a fixed order, no atomics; counts_out [B][2] =
+ * {nodes pinned to 0, nodes the clip moved}.  For s a power of two the trial has the bits of NumPy's np.clip(u + s * x, lo,
+ * hi).  VCH_ERR_STATE without resident CG vectors; VCH_ERR_ARG for NULL s, chg_out or counts_out and an s_b that is not
+ * finite or not > 0. */
+int vch2d_newton_trial(vch2d_ctx *ctx, const double *s /* [B] */, double *u_out /* [B][M+1][Nx+1][Ny+1] or NULL */,
+                       double *chg_out /* [B][2] */, int64_t *counts_out /* [B][2]: pinned, clipped */);
 /* Per-trajectory cost scalars {J1,J2,J3,J4,J} of the current iterate on the DEVICE
  * (5*B doubles), for the caller's RCCL all-reduce; returns a device pointer via *ptr_dev. */
 int vch2d_pgd_cost_dev(vch2d_ctx *ctx, double **ptr_dev);

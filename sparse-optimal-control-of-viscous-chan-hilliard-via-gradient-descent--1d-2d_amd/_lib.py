@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("VCH_LIB") or os.path.join(HERE, "libvch_hip.so")     # VCH_LIB: A/B builds
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 SOURCES = ["vch_hip.hip"]
-DEPS = ["vch_hip.hip", "vch_comm.hip", "vch_engine2d.hip", "vch_kernels2d.h", "vch_gemm.h", "vch_fft.h", "vch_common.h", "vch_mem.h", "vch_engine1d.hip", "vch_kernels1d.h", "vch_pgd.h",
+DEPS = ["vch_hip.hip", "vch_comm.hip", "vch_engine2d.hip", "vch_kernels2d.h", "vch_gemm.h", "vch_fft.h", "vch_common.h", "vch_mem.h", "vch_engine1d.hip", "vch_kernels1d.h", "vch_pgd.h", "vch_newton.h",
         os.path.join(ROOT, "include", "vch.h")]
 
 
@@ -150,6 +150,9 @@ SIGNATURES = {
                                 C.POINTER(C.c_uint8), C.c_double, _D, C.c_int, C.c_double, C.c_int, _D, _D, _D, _D, _I32, _I32,
                                 C.POINTER(C.c_int64), C.POINTER(Stats)]),
     "vch2d_cg_vector": (C.c_int, [_P, C.c_int, _D]),
+    "vch2d_pgd_newton": (C.c_int, [_P, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_double, C.c_int, _D, _D, _D, _D, _D,
+                                   _I32, _I32, _I32, _I32, C.POINTER(C.c_int64), _D]),
+    "vch2d_newton_trial": (C.c_int, [_P, _D, _D, _D, C.POINTER(C.c_int64)]),
     "vch2d_pgd_iterate": (C.c_int, [_P, C.c_int, _D, _D, _I32, _D, _D]),
     "vch2d_pgd_get": (C.c_int, [_P, C.c_int, _D]),
     "vch2d_pgd_errors": (C.c_int, [_P, C.c_int, _D, _D]),

@@ -8,6 +8,7 @@
 #include "vch_gemm.h"
 #include "vch_fft.h"
 #include "vch_pgd.h"
+#include "vch_newton.h"
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -3068,31 +3069,33 @@ extern "C" int vch2d_krylov_vector(vch2d_ctx *c, const double *coef, int m, doub
 // recurrence on the device (kernels: "Device-resident Newton-CG" in vch_kernels2d.h).  The storage, the
 // mask launch and the sweeps are those of vch2d_hess_lanczos without reorthogonalisation.
 // ------------------------------------------------------------------------------------
-extern "C" int vch2d_hess_cg(vch2d_ctx *c, const double *dt, int M, const double *t_hist, const double *x, const double *y,
-                             const double *phi_Q, const double *phi_T, const vch_opt_params *opts, int n_opts, double rtol,
-                             const uint8_t *mask, double tol, const double *rhs, int k, double cg_tol, int precond,
-                             double *resid_out, double *curv_out, double *pred_out, double *rnorm0_out, int32_t *steps_out,
-                             int32_t *status_out, int64_t *n_free_out, vch_stats *stats) {
-    CTXCHK(c);
+// The body of vch2d_hess_cg, shared with the rounds of vch2d_pgd_newton.  fn: the entry point the messages name.
+// empty_ok (the Newton rounds): a trajectory with an empty free set is no error; with P b = 0 the start gives it zero steps,
+// VCH_CG_CONVERGED and x = 0.
+static int hess_cg_core(vch2d_ctx *c, const char *fn, bool empty_ok, const double *dt, int M, const double *t_hist, const double *x,
+                        const double *y, const double *phi_Q, const double *phi_T, const vch_opt_params *opts, int n_opts,
+                        double rtol, const uint8_t *mask, double tol, const double *rhs, int k, double cg_tol, int precond,
+                        double *resid_out, double *curv_out, double *pred_out, double *rnorm0_out, int32_t *steps_out,
+                        int32_t *status_out, int64_t *n_free_out, vch_stats *stats) {
     // everything below is checked before anything is enqueued, copied or allocated
-    VCHCHK(tan_check_state(c, __func__));
-    ARGCHK(opts, "NULL opts");
-    ARGCHK(resid_out && curv_out && pred_out && rnorm0_out && steps_out && status_out && n_free_out,
+    VCHCHK(tan_check_state(c, fn));
+    TANCHK(opts, "NULL opts");
+    TANCHK(resid_out && curv_out && pred_out && rnorm0_out && steps_out && status_out && n_free_out,
            "NULL resid_out, curv_out, pred_out, rnorm0_out, steps_out, status_out or n_free_out");
-    ARGCHK(k >= 1, "k must be >= 1");
-    ARGCHK(precond == 0 || precond == 1, "precond must be 0 or 1");
-    ARGCHK(std::isfinite(cg_tol), "cg_tol must be finite");
+    TANCHK(k >= 1, "k must be >= 1");
+    TANCHK(precond == 0 || precond == 1, "precond must be 0 or 1");
+    TANCHK(std::isfinite(cg_tol), "cg_tol must be finite");
     bool pgd = false;
-    VCHCHK(tan_check_args(c, __func__, 1, &dt, M, &t_hist, x, y, phi_Q, phi_T, opts, n_opts, 2, &pgd));
+    VCHCHK(tan_check_args(c, fn, 1, &dt, M, &t_hist, x, y, phi_Q, phi_T, opts, n_opts, 2, &pgd));
     if (!c->shift_res)
-        return vch_fail(VCH_ERR_STATE, "vch2d_hess_cg: the resident state history is not one a march of this context wrote");
+        return vch_fail(VCH_ERR_STATE, "%s: the resident state history is not one a march of this context wrote", fn);
     // the direction has M + 1 rows: the g_rows the rule of vch2d_hessvec must allow
     if (!c->res_pgd && c->fwd_u_rows > 0)
-        ARGCHK(c->fwd_u_rows >= M + 1, "the march's control has fewer than M + 1 rows");
+        TANCHK(c->fwd_u_rows >= M + 1, "the march's control has fewer than M + 1 rows");
     const Geom &G = c->G;
     const int B = c->B, levels = M + 1;
     const long hs = hist_stride(c);
-    VCHCHK(kr_storage(c, __func__, 3, k, !pgd && phi_Q));
+    VCHCHK(kr_storage(c, fn, 3, k, !pgd && phi_Q));
     const KrLayout L = kr_layout(c, c->kr_slots, c->kr_kcap);
     const KrCells cells = kr_cells(c, L);
     // the cells of the iteration in the block of the Lanczos scalars: resid, curv where alpha, beta live
@@ -3118,7 +3121,7 @@ extern "C" int vch2d_hess_cg(vch2d_ctx *c, const double *dt, int M, const double
     std::vector<long long> nfree(B);
     VCHCHK(kr_look(c, nfree.data(), cells.nfree, sizeof(long long) * B));
     for (int b = 0; b < B; ++b)
-        if (nfree[b] < 1) return vch_fail(VCH_ERR_ARG, "vch2d_hess_cg: trajectory %d: the free set is empty", b);
+        if (nfree[b] < 1 && !empty_ok) return vch_fail(VCH_ERR_ARG, "%s: trajectory %d: the free set is empty", fn, b);
     const double *pq = nullptr, *pt = nullptr;
     VCHCHK(tan_targets(c, pgd, x, y, phi_Q, phi_T, M, &pq, &pt));
     // the solves stop at rtol (relative residual); the context's own tolerance comes back on every path out
@@ -3152,7 +3155,7 @@ extern "C" int vch2d_hess_cg(vch2d_ctx *c, const double *dt, int M, const double
         bool any = false;
         for (int b = 0; b < B; ++b) {
             if (!std::isfinite(look[2 * b]))
-                return vch_fail(VCH_ERR_ARG, "vch2d_hess_cg: trajectory %d: the right-hand side is not finite on the free set", b);
+                return vch_fail(VCH_ERR_ARG, "%s: trajectory %d: the right-hand side is not finite on the free set", fn, b);
             any = any || look[2 * b + 1] == 0.0;
         }
         if (any && rhs && !c->kr_nocache) VCHCHK(grad_sweep());
@@ -3207,7 +3210,7 @@ extern "C" int vch2d_hess_cg(vch2d_ctx *c, const double *dt, int M, const double
         stats->host_syncs += 1;
     }
     VCHCHK(reset_counters(c));      // the records as the end of a PGD iteration leaves them
-    rc = fix_check_end("vch2d_hess_cg", bad);
+    rc = fix_check_end(fn, bad);
     if (rc < 0) return rc;
     for (int b = 0; b < B; ++b) {
         n_free_out[b] = nfree[b];
@@ -3219,6 +3222,16 @@ extern "C" int vch2d_hess_cg(vch2d_ctx *c, const double *dt, int M, const double
     return 0;
 }
 
+extern "C" int vch2d_hess_cg(vch2d_ctx *c, const double *dt, int M, const double *t_hist, const double *x, const double *y,
+                             const double *phi_Q, const double *phi_T, const vch_opt_params *opts, int n_opts, double rtol,
+                             const uint8_t *mask, double tol, const double *rhs, int k, double cg_tol, int precond,
+                             double *resid_out, double *curv_out, double *pred_out, double *rnorm0_out, int32_t *steps_out,
+                             int32_t *status_out, int64_t *n_free_out, vch_stats *stats) {
+    CTXCHK(c);
+    return hess_cg_core(c, __func__, false, dt, M, t_hist, x, y, phi_Q, phi_T, opts, n_opts, rtol, mask, tol, rhs, k, cg_tol, precond,
+                        resid_out, curv_out, pred_out, rnorm0_out, steps_out, status_out, n_free_out, stats);
+}
+
 extern "C" int vch2d_cg_vector(vch2d_ctx *c, int which, double *out) {
     CTXCHK(c);
     ARGCHK(out, "NULL out");
@@ -3226,6 +3239,156 @@ extern "C" int vch2d_cg_vector(vch2d_ctx *c, int which, double *out) {
     if (!c->ncg_valid || !c->kr_Q)
         return vch_fail(VCH_ERR_STATE, "vch2d_cg_vector: no resident vectors (call vch2d_hess_cg first)");
     return d2h_hist(c, out, c->kr_Q + (long)which * c->B * hist_stride(c), c->ncg_levels);
+}
+
+// ------------------------------------------------------------------------------------
+// Damped Newton rounds on the free set about the resident PGD iterate (kernels: "Damped Newton rounds" in vch_kernels2d.h,
+// verdicts: vch_newton.h)
+// ------------------------------------------------------------------------------------
+// The trial control of the step lengths s_host [B] into the trial-control scratch, about the resident control, the x, the
+// free set and the box table the last Newton-CG solve left; skip (device flags, or NULL) leaves a trajectory alone.  The
+// partials and the sums go through the cost scratch; sums_out [B][4] = {sum (t - u)^2, sum u^2, pinned, clipped} after one
+// look (the cells of a skipped trajectory are not written).
+static int newton_trial_core(vch2d_ctx *c, const double *s_host, const int *skip, double *sums_out) {
+    const int B = c->B, levels = c->ncg_levels;
+    const long hs = hist_stride(c);
+    VCHCHK(ensure_cost_bufs(c));
+    const KrCells cells = kr_cells(c, kr_layout(c, c->kr_slots, c->kr_kcap));
+    const int nch = (levels + c->kr_lchunk - 1) / c->kr_lchunk;
+    const KrArgs a{c->kr_Q, (long)B * hs, hs, levels, c->kr_lchunk, 0, 0, 3, 4, c->kr_mask, cells.stop};
+    const int u_rows = c->res_pgd ? levels : std::min(c->fwd_u_rows, levels);
+    HIPCHK(hipMemcpyAsync(c->alpha_dev, s_host, sizeof(double) * B, hipMemcpyHostToDevice, c->stream));
+    LAUNCHC(PC_KRYLOV, k_nt_trial, dim3(c->nblk, nch, B), dim3(NTH), c->G, a, u_rows > 0 ? (const double *)c->u_hist : (const double *)nullptr,
+            u_rows, (const double *)c->alpha_dev, (const double *)c->seam_tab, skip, c->u_trial, c->cost_part);
+    LAUNCHC(PC_KRYLOV, k_nt_fin, dim3(B), dim3(NTH), (const double *)c->cost_part, (long)nch * c->nblk, skip, c->cost_lvl);
+    VCHCHK(kr_look(c, c->cost_lvl_host, c->cost_lvl, sizeof(double) * 4 * B));
+    memcpy(sums_out, c->cost_lvl_host, sizeof(double) * 4 * B);
+    return 0;
+}
+
+extern "C" int vch2d_newton_trial(vch2d_ctx *c, const double *s, double *u_out, double *chg_out, int64_t *counts_out) {
+    CTXCHK(c);
+    ARGCHK(s && chg_out && counts_out, "NULL s, chg_out or counts_out");
+    for (int b = 0; b < c->B; ++b) ARGCHK(std::isfinite(s[b]) && s[b] > 0, "s must be finite and > 0");
+    if (!c->ncg_valid || !c->kr_Q || !c->u_trial)
+        return vch_fail(VCH_ERR_STATE, "vch2d_newton_trial: no resident vectors (call vch2d_hess_cg first)");
+    std::vector<double> sums(4 * (size_t)c->B);
+    VCHCHK(newton_trial_core(c, s, nullptr, sums.data()));
+    for (int b = 0; b < c->B; ++b) {
+        chg_out[2 * b] = sums[4 * b];
+        chg_out[2 * b + 1] = sums[4 * b + 1];
+        counts_out[2 * b] = (int64_t)sums[4 * b + 2];
+        counts_out[2 * b + 1] = (int64_t)sums[4 * b + 3];
+    }
+    return u_out ? d2h_hist(c, u_out, c->u_trial, c->ncg_levels) : 0;
+}
+
+extern "C" int vch2d_pgd_newton(vch2d_ctx *c, int n_rounds, int k, double cg_tol, int precond, double tol, double rtol,
+                                int max_halvings, double *cost_out, double *cost_new_out, double *s_out, double *pred_out,
+                                double *rnorm0_out, int32_t *halvings_out, int32_t *cg_steps_out, int32_t *cg_status_out,
+                                int32_t *status_out, int64_t *counts_out, double *seconds_out) {
+    CTXCHK(c);
+    // everything below is checked before anything is enqueued, copied or allocated
+    if (!c->pgd_ready) return vch_fail(VCH_ERR_STATE, "vch2d_pgd_newton: call vch2d_pgd_init first");
+    if (!c->res_pgd || !c->shift_res || c->M_res < 1)
+        return vch_fail(VCH_ERR_STATE, "vch2d_pgd_newton: the resident state history is no longer the PGD iterate's (call vch2d_pgd_init again)");
+    ARGCHK(n_rounds >= 1, "n_rounds must be >= 1");
+    ARGCHK(k >= 1, "k must be >= 1");
+    ARGCHK(max_halvings >= 0, "max_halvings must be >= 0");
+    ARGCHK(precond == 0 || precond == 1, "precond must be 0 or 1");
+    ARGCHK(std::isfinite(cg_tol), "cg_tol must be finite");
+    ARGCHK(cost_out && cost_new_out && s_out && pred_out && rnorm0_out && halvings_out && cg_steps_out && cg_status_out && status_out &&
+               counts_out,
+           "NULL cost_out, cost_new_out, s_out, pred_out, rnorm0_out, halvings_out, cg_steps_out, cg_status_out, status_out or counts_out");
+    const int B = c->B, M = c->M_res, rows = M + 1;
+    const double *pq = (c->phiQ) ? c->phiQ : nullptr;
+    const double nan = std::nan("");
+    for (size_t i = 0; i < (size_t)B * n_rounds; ++i) {
+        cost_out[i] = cost_new_out[i] = s_out[i] = pred_out[i] = rnorm0_out[i] = nan;
+        halvings_out[i] = cg_steps_out[i] = cg_status_out[i] = 0;
+        status_out[i] = VCH_NEWTON_IDLE;
+        counts_out[3 * i] = counts_out[3 * i + 1] = counts_out[3 * i + 2] = 0;
+    }
+    double sec[4] = {0, 0, 0, 0};
+    hipEvent_t e0 = c->ev0, e1 = c->ev1;
+    vch_newton_state nt;
+    nt.reset(B);
+    std::vector<double> resid((size_t)B * k), curv((size_t)B * k), pred(B), rn0(B), Jt(5 * (size_t)B), sums(4 * (size_t)B);
+    std::vector<int32_t> steps(B), cgst(B);
+    std::vector<int64_t> nfree(B);
+    bool moved = false;
+    int done_rounds = 0;
+    auto run = [&]() -> int {
+        for (int r = 0; r < n_rounds; ++r) {
+            if (!nt.begin_round()) break;
+            // --- the Newton step of every trajectory on its free set; the solves of an idle one are not gated
+            vch_stats cg;
+            VCHCHK(hess_cg_core(c, "vch2d_pgd_newton", true, nullptr, M, nullptr, nullptr, nullptr, nullptr, nullptr, c->opts.data(), B, rtol,
+                                nullptr, tol, nullptr, k, cg_tol, precond, resid.data(), curv.data(), pred.data(), rn0.data(),
+                                steps.data(), cgst.data(), nfree.data(), &cg));
+            sec[0] += cg.seconds;
+            for (int b = 0; b < B; ++b) {
+                if (nt.idle(b)) continue;
+                const size_t i = (size_t)b * n_rounds + r;
+                cost_out[i] = cost_new_out[i] = c->J_host[5 * b + 4];
+                pred_out[i] = pred[b];
+                rnorm0_out[i] = rn0[b];
+                cg_steps_out[i] = steps[b];
+                cg_status_out[i] = cgst[b];
+                counts_out[3 * i] = nfree[b];
+                status_out[i] = nt.after_solve(b, nfree[b], rn0[b], cgst[b], steps[b]);
+            }
+            // --- trials s = 1, 1/2, ...: a trajectory whose verdict is in sits the trial out
+            while (!nt.all_decided()) {
+                VCHCHK(reset_counters(c));
+                VCHCHK(freeze(c, nt.decided));
+                HIPCHK(hipEventRecord(e0, c->stream));
+                VCHCHK(newton_trial_core(c, nt.s.data(), (const int *)c->frozen_dev, sums.data()));
+                HIPCHK(hipEventRecord(e1, c->stream));
+                sec[1] += elapsed_s(c, e0, e1);
+                HIPCHK(hipEventRecord(e0, c->stream));
+                HIPCHK(hipMemcpyAsync(c->phi_s, c->phi0, sizeof(double) * B * c->G.plane, hipMemcpyDeviceToDevice, c->stream));
+                VCHCHK(forward_core(c, c->u_trial, rows, c->dt.data(), M, c->phi_trial));
+                HIPCHK(hipEventRecord(e1, c->stream));
+                sec[2] += elapsed_s(c, e0, e1);
+                HIPCHK(hipEventRecord(e0, c->stream));
+                VCHCHK(cost_core(c, c->phi_trial, c->u_trial, pq, c->phiT, false, M, c->t_hist.data(), c->opts.data(), Jt.data(), nullptr, B));
+                HIPCHK(hipEventRecord(e1, c->stream));
+                sec[3] += elapsed_s(c, e0, e1);
+                for (int b = 0; b < B; ++b) {
+                    if (nt.decided[b]) continue;
+                    const size_t i = (size_t)b * n_rounds + r;
+                    halvings_out[i] = nt.halvings[b];
+                    counts_out[3 * i + 1] = (int64_t)sums[4 * b + 2];
+                    counts_out[3 * i + 2] = (int64_t)sums[4 * b + 3];
+                    const double s = nt.s[b];
+                    const vch_newton_verdict v = nt.judge(b, c->J_host[5 * b + 4], pred[b], Jt[5 * b + 4], max_halvings);
+                    if (v == VCH_NT_STALL) status_out[i] = VCH_NEWTON_STALLED;
+                    if (v != VCH_NT_ACCEPT) continue;
+                    // accepted: the trial becomes the iterate, as in the PGD loop
+                    std::copy_n(&Jt[5 * b], 5, &c->J_host[5 * b]);
+                    c->pgd.cost[b] = Jt[5 * b + 4];
+                    VCHCHK(copy_traj(c, c->u_hist, c->u_trial, b, rows));
+                    VCHCHK(copy_traj(c, c->phi_hist, c->phi_trial, b, rows));
+                    VCHCHK(copy_traj_shifts(c, b));
+                    moved = true;
+                    cost_new_out[i] = Jt[5 * b + 4];
+                    s_out[i] = s;
+                }
+            }
+            VCHCHK(reset_counters(c));
+            done_rounds = r + 1;
+        }
+        return 0;
+    };
+    const int rc = run();
+    if (moved) c->pgd_r_valid = false;      // r_hist is the adjoint of an iterate that has been replaced
+    if (rc < 0) (void)reset_counters(c);
+    HIPCHK(hipMemcpyAsync(c->J_dev, c->J_host.data(), sizeof(double) * 5 * B, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (rc < 0) return rc;
+    if (seconds_out) memcpy(seconds_out, sec, sizeof(sec));
+    return done_rounds;
 }
 
 extern "C" int vch2d_mass_shifts(vch2d_ctx *c, double *out) {

@@ -3982,3 +3982,69 @@ __global__ __launch_bounds__(NTH) void k_ncg_fin(NcgCells x, const double *__res
     x.stop[b] = st;
     x.look[2 * b + 1] = (double)st;
 }
+
+// ---------------------------------------------------------------------------------
+// Damped Newton rounds on the free set (vch2d_pgd_newton, vch2d_newton_trial): the trial control of a step
+// length.  Tiling and partials are those of the Newton-CG passes above (KrArgs, KR_COORDS / KR_NODES; x is slot NCG_X), the
+// partials here have 4 slots per workgroup: {sum (t - u)^2, sum u^2, nodes pinned to 0, nodes the clip moved}, the counts
+// exact in a double.  No atomics.  A trajectory whose verdict is in (skip[b] != 0; skip may be NULL) is left alone.
+//
+// Per node t = min(max(u + s_b x, u_min_b), u_max_b) with NumPy's order of comparisons (a NaN stays a NaN); a free node with
+// t u < 0 becomes 0, the kink, where the next round pins it.  Rows of u beyond u_rows are zeros.  Every s the rounds use is
+// a power of two, so s x is exact (short of an underflow) and u + s x rounds once whether or not the compiler fuses the
+// multiply-add: the trial has the bits of np.clip(u + s * d, lo, hi).  A node's three operands (u, x, the mask byte) are
+// requested together, in front of the first use of any of them.
+// ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(NTH) void k_nt_trial(Geom G, KrArgs a, const double *__restrict__ u, int u_rows,
+                                                  const double *__restrict__ s_tab, const double *__restrict__ opt_tab,
+                                                  const int *__restrict__ skip, double *__restrict__ trial,
+                                                  double *__restrict__ part) {
+    KR_COORDS;
+    if (skip && skip[b]) return;            // uniform over the workgroup
+    __shared__ double sred[NPART * 4];
+    const double s = s_tab[b], lo = opt_tab[b * OPT_STRIDE + OPT_UMIN], hi = opt_tab[b * OPT_STRIDE + OPT_UMAX];
+    const double *const xs = ncg_slot(a, NCG_X);
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    KR_NODES(
+        const bool have_u = u && lvl < u_rows;
+        const double uv = have_u ? u[o] : 0.0;
+        const double xv = xs[o];
+        const unsigned char fr = a.mask[o];
+        const double v = uv + s * xv;
+        double t = (v != v || v > lo) ? v : lo;
+        t = (t != t || t < hi) ? t : hi;
+        const bool moved = t != v;
+        const bool pin = fr && t * uv < 0.0;
+        t = pin ? 0.0 : t;
+        trial[o] = t;
+        const double d = t - uv;
+        acc[0] += d * d;
+        acc[1] += uv * uv;
+        acc[2] += pin ? 1.0 : 0.0;
+        acc[3] += moved ? 1.0 : 0.0;
+    )
+    const int op[4] = {0, 0, 0, 0};
+    block_reduce_store<4>(acc, op, sred, my_part);
+}
+
+// The four sums of a trajectory's partials, one workgroup of NTH threads per trajectory, in the fixed order of kr_sum (a
+// copy, as ncg_sum is, so that k_kr_fin and k_ncg_fin keep their registers).  out [B][4].
+__global__ __launch_bounds__(NTH) void k_nt_fin(const double *__restrict__ part, long n, const int *__restrict__ skip,
+                                                double *__restrict__ out) {
+    __shared__ double sh[NTH];
+    const int b = blockIdx.x;
+    if (skip && skip[b]) return;
+    const double *p = part + (long)b * n * 4;
+    for (int slot = 0; slot < 4; ++slot) {
+        double s = 0.0;
+        for (long e = threadIdx.x; e < n; e += NTH) s += p[e * 4 + slot];
+        sh[threadIdx.x] = s;
+        __syncthreads();
+        for (int h = NTH / 2; h > 0; h >>= 1) {
+            if ((int)threadIdx.x < h) sh[threadIdx.x] += sh[threadIdx.x + h];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) out[4 * b + slot] = sh[0];
+        __syncthreads();
+    }
+}
