@@ -861,6 +861,63 @@ int vch1d_hess_cg(vch1d_ctx *ctx, const double *phi_hist, const double *u, int n
 /* out = x (which 0), r (1) or p (2) of the last vch1d_hess_cg of this context; masked-off nodes are exact zeros.
  * VCH_ERR_STATE without resident vectors (no call yet, a failed call, or a vch1d_hess_lanczos since). */
 int vch1d_cg_vector(vch1d_ctx *ctx, int which /* 0: x, 1: r, 2: p */, double *out /* [B][rows][N+1] */);
+/* Damped Newton rounds on the free set about the resident PGD iterate of the 1D engine, batched, with every trajectory's own
+ * parameters and decisions (the 1D counterpart of vch2d_pgd_newton, whose comment holds every rule not
+ * repeated here; ABI version stays 3: detect both entry points by symbol).  The rounds run about the iterate of
+ * vch1d_pgd_init / _init_v and whatever vch1d_pgd_iterate did since.  No history crosses the bus.  There is no rtol: the 1D
+ * solves are direct.  Three things differ from the 2D round: there is no shift record; the control has rows = M + 2 rows
+ * like the state; the free set and the step cover all rows, the duplicated t = 0 row included.  Per round and trajectory:
+ *   1. the Newton-CG solve of vch1d_hess_cg in its resident mode (resident phi_hist, u = phi_Q = phi_T = VCH_RESIDENT,
+ *      rhs = NULL, mask = NULL, the dt, t_hist, x of vch1d_pgd_init and opts[b]; k, cg_tol, precond, tol as passed).  An empty
+ *      free set is no error here: zero steps, VCH_CG_CONVERGED, pred = rnorm0 = 0, and vch1d_cg_vector returns zeros for it.
+ *   2. the verdict after the solve, as in 2D: VCH_NEWTON_STATIONARY, VCH_NEWTON_NEGCURV, VCH_NEWTON_BREAKDOWN, or x is the step.
+ *   3. trials for s = 1, 1/2, ..., at most max_halvings halvings: t = min(max(u + s x, u_min_b), u_max_b), a free node with
+ *      t u < 0 becomes 0 (k1d_nt_trial into the trial-control scratch), a march of t into the trial-state scratch and its
+ *      cost.  The first s with J(t) <= cost_b - 1e-4 s pred_b is accepted: control and state history are copied as the PGD
+ *      loop copies an accepted trial and the stored cost becomes the trial's (VCH_NEWTON_ACCEPTED).  When no s is accepted
+ *      the trajectory is left unmoved with VCH_NEWTON_STALLED.
+ * A trajectory that has ended is VCH_NEWTON_IDLE in all later rounds, its doubles NaN, its integers 0; its solves are not
+ * gated.  The call returns the number of rounds run and stops early once every trajectory has ended.  The outputs are those of
+ * vch2d_pgd_newton (all [B][n_rounds] and required, counts_out [B][n_rounds][3] = {n_free, and of the round's last trial:
+ * nodes pinned to 0, nodes the clip moved}; seconds_out [4], may be NULL, = {solves, trial kernel, marches, costs}).  No
+ * atomics: a trajectory's outputs and its iterate are bitwise those of a single-trajectory context.
+ * Three departures from the host loop GD_1D.newton_refine:
+ *   (1) a CG breakdown ends the trajectory; no march is started under a control that may not be finite (as in 2D);
+ *   (2) a trial march that reports a non-finite mass defect does not fail the call: that trajectory's trial counts as not
+ *       accepted and s is halved (a cost that is not finite is never accepted);
+ *   (3) the 1D stop quirk: after a trajectory's PGD stop rule fired the resident control is the new iterate and the
+ *       resident state and the stored cost are the previous one's.  Before round 0 the call marches the resident control of
+ *       every such trajectory once (one batched march, the other members sit it out), takes its cost, copies the state into
+ *       the resident history and stores the cost.  A stopped trajectory is never iterated again, so this changes nothing
+ *       that a later vch1d_pgd_iterate computes.
+ * Afterwards vch1d_pgd_get, vch1d_second_order, vch1d_hessvec, vch1d_hess_lanczos and vch1d_hess_cg (resident mode) work about
+ * the new iterate, vch1d_cg_vector returns the last round's vectors, the adjoint r of vch1d_pgd_kkt(refresh = 0) is invalid
+ * once any trajectory moved, and the counters of the PGD loop (iteration count, plateau, next first step, stop flags, error
+ * histories) are untouched: a following vch1d_pgd_iterate is bit for bit that of vch1d_pgd_init_v with u0 = the Newton
+ * iterate, and after a call that accepted nothing that of an undisturbed run.
+ * Storage beyond that of vch1d_hess_cg and the PGD buffers: the [B] step table, the skip flags and the partials of the trial
+ * kernel's four sums, which have cells of their own in the block of the Krylov scalars (the same group: a refused request
+ * releases the group and returns VCH_ERR_NOMEM with the bytes in the message; the context stays usable).
+ * Errors, all before anything is enqueued, copied or allocated: VCH_ERR_STATE before vch1d_pgd_init / _init_v; VCH_ERR_ARG for
+ * n_rounds < 1, k < 1, max_halvings < 0, precond outside 0 / 1, a cg_tol that is not finite and NULL outputs, and with
+ * precond 1 for the time-weight check of vch1d_hess_cg.  A ||P b|| that is not finite is VCH_ERR_ARG naming the trajectory,
+ * after the set-up's look, as in vch1d_hess_cg. */
+int vch1d_pgd_newton(vch1d_ctx *ctx, int n_rounds, int k, double cg_tol, int precond /* 0 | 1 */, double tol, int max_halvings,
+                     double *cost_out, double *cost_new_out, double *s_out, double *pred_out,
+                     double *rnorm0_out /* [B][n_rounds] */, int32_t *halvings_out, int32_t *cg_steps_out,
+                     int32_t *cg_status_out, int32_t *status_out /* [B][n_rounds] */,
+                     int64_t *counts_out /* [B][n_rounds][3]: n_free, pinned, clipped */,
+                     double *seconds_out /* [4] or NULL: solves, trial kernel, marches, costs */);
+/* The trial kernel's seam, after any successful vch1d_hess_cg, stateless or resident: t = min(max(u + s_b x, u_min_b),
+ * u_max_b) with u that call's base control (a shared base: one for the batch; NULL: zeros), x, the free set and the box the
+ * ones it left resident; a free node with t u < 0 becomes 0.  Writes only the trial-control scratch (allocated on first use
+ * when no PGD problem was loaded) and leaves x, r, p resident.  u_out (may be NULL): the trial; chg_out [B][2] =
+ * {sum (t - u)^2, sum u^2} in a fixed order, no atomics; counts_out [B][2] = {nodes pinned to 0, nodes the clip moved}.  For
+ * s a power of two the trial has the bits of NumPy's np.clip(u + s * x, lo, hi).  VCH_ERR_STATE without resident CG vectors
+ * (or when a later call has overwritten the copy of an uploaded base control); VCH_ERR_ARG for NULL s, chg_out or
+ * counts_out and an s_b that is not finite or not > 0. */
+int vch1d_newton_trial(vch1d_ctx *ctx, const double *s /* [B] */, double *u_out /* [B][rows][N+1] or NULL */,
+                       double *chg_out /* [B][2] */, int64_t *counts_out /* [B][2]: pinned, clipped */);
 
 /* ---------------------------------------------------------- diagnostics ---- */
 

@@ -183,7 +183,7 @@ def run_optimization_resident(fwd_config: ForwardSolverConfig, opt_config: Optim
 
 
 def run_sweep(fwd_config: ForwardSolverConfig, opt_configs, n_iter=None, seed=42, amp=0.01, initial_phi=None, choice_t=1,
-              choice_q=1, u0=None, return_controls=False):
+              choice_q=1, u0=None, return_controls=False, n_newton=0):
     """A parameter sweep as ONE batch: member b runs the PGD loop with opt_configs[b] (weights, sparsity parameter, box,
     alpha_max), all members from the same initial state (`initial_phi` (N+1,), else `seed`, `amp`) and targets, so that
     they differ by their parameters only.  `u0`: start control, one (rows, N+1) array for every member or one per member
@@ -191,7 +191,10 @@ def run_sweep(fwd_config: ForwardSolverConfig, opt_configs, n_iter=None, seed=42
     largest max_iter of the members (the loop length is one for the batch).  Returns dict(costs [B][it+1], alphas, trials,
     changes, tracking_error, terminal_error, iters, seconds, kkt = Engine1D.pgd_kkt(refresh=True) -- the sparsity
     statistic and the stationarity measure of every member, counted on the device -- phi_T, t_hist, x, and u only with
-    return_controls); the state history never leaves the device."""
+    return_controls); the state history never leaves the device.  `n_newton` > 0 polishes every member after its PGD
+    iterations by that many damped Newton rounds on its free set (Engine1D.pgd_newton, on the device) and adds `newton`
+    (its records) and `costs_newton` [B][n_newton+1] (the cost before the first round, then after every round); kkt and u
+    are then those of the polished iterate.  0 leaves the result as it is without the polish."""
     from ..engine import Engine1D, time_grid
     from .Forward_solver import init_phi_random, delta_sep
     opt_configs = list(opt_configs)
@@ -220,10 +223,17 @@ def run_sweep(fwd_config: ForwardSolverConfig, opt_configs, n_iter=None, seed=42
                           phi_Q=phi_Q, x=x, u0=u0)
         n = int(max(int(o.max_iter) for o in opt_configs) if n_iter is None else n_iter)
         res = eng.pgd_iterate(n)
+        newton = eng.pgd_newton(int(n_newton)) if int(n_newton) > 0 else None
         out = dict(costs=np.concatenate([J0[:, 4:5], res["cost"]], axis=1), alphas=res["alpha"], trials=res["trials"],
                    changes=res["change"], tracking_error=res["tracking_error"], terminal_error=res["terminal_error"],
                    iters=res["iters"], seconds=res["seconds"], kkt=eng.pgd_kkt(refresh=True), phi_T=phi_T, t_hist=t_hist,
                    x=x)
+        if newton is not None:
+            # an idle round carries the cost the member ended with
+            cn = np.concatenate([newton["cost"][:, :1], newton["cost_new"]], axis=1)
+            for r in range(1, cn.shape[1]):
+                cn[:, r] = np.where(np.isnan(cn[:, r]), cn[:, r - 1], cn[:, r])
+            out["newton"], out["costs_newton"] = newton, cn
         if return_controls:
             out["u"] = eng.pgd_get("u").reshape(B, len(t_hist), N + 1)
     finally:
@@ -232,7 +242,7 @@ def run_sweep(fwd_config: ForwardSolverConfig, opt_configs, n_iter=None, seed=42
 
 
 def newton_refine(fwd_config: ForwardSolverConfig, opt_config: OptimizationConfig, u, phi_Q_target, phi_T_target,
-                  n_newton=3, k=50, cg_tol=1e-8, max_halvings=10):
+                  n_newton=3, k=50, cg_tol=1e-8, max_halvings=10, on_device=False):
     """Rounds of a damped Newton method on the free set, from the control `u` (for instance what the PGD loop left).
     Per round: the free set of the iterate (strictly inside the box of `opt_config`, off the kink of the L1 term) and
     the Newton step d of the full cost on it (second_order_conditions.reduced_newton_step: conjugate gradients on the
@@ -244,7 +254,15 @@ def newton_refine(fwd_config: ForwardSolverConfig, opt_config: OptimizationConfi
     when the first CG direction already has non-positive curvature, or when no s is accepted.
 
     Returns (u, records): the final control and one dict per round with cost (before the round), n_free, rnorm0, steps,
-    status, s (None when the round moved nothing) and cost_new (the accepted trial's, else the unchanged cost)."""
+    status, s (None when the round moved nothing) and cost_new (the accepted trial's, else the unchanged cost).
+
+    on_device=True runs the rounds on the device (Engine1D.pgd_newton): one context, one pgd_init(u0=u) with this loop's
+    own start state and targets, the step, the trials and the decisions without a history crossing the bus; the records
+    have the same keys.  Two departures: a CG breakdown ends the rounds there (no march under a control that may not be
+    finite), where the host loop tries the step; a trial whose march reports a non-finite mass defect counts as not
+    accepted there, where the host loop raises."""
+    if on_device:
+        return _newton_refine_device(fwd_config, opt_config, u, phi_Q_target, phi_T_target, n_newton, k, cg_tol, max_halvings)
     from ..engine import time_grid
     from ._ctx import engine_for_config
     from .Forward_solver import init_phi_random, delta_sep
@@ -288,6 +306,33 @@ def newton_refine(fwd_config: ForwardSolverConfig, opt_config: OptimizationConfi
             break
         u, cost = trial, J
     return u, records
+
+
+def _newton_refine_device(fwd_config, opt_config, u, phi_Q_target, phi_T_target, n_newton, k, cg_tol, max_halvings):
+    """newton_refine(on_device=True): the problem of the host loop as a resident PGD problem, then Engine1D.pgd_newton."""
+    from ..engine import Engine1D, time_grid
+    from ._ctx import engine_for_config
+    from .Forward_solver import init_phi_random, delta_sep
+    N = int(fwd_config.N)
+    tg, dts = time_grid(float(fwd_config.T), float(fwd_config.dt_initial))
+    t_hist = np.concatenate([[0.0], tg])
+    M = len(dts)
+    u = np.asarray(u, dtype=np.float64)[:M + 2]
+    phi0 = init_phi_random(N, delta_sep, amp=0.01, seed=42, enforce_zero_mean=True)
+    x = np.linspace(0.0, float(fwd_config.Lx), N + 1)
+    eng = engine_for_config(fwd_config, batch=1, max_steps=max(M, 1))
+    eng.pgd_init(phi0[None], np.asarray(phi_T_target, dtype=np.float64)[None], t_hist, dts, [make_opt(opt_config)],
+                 phi_Q=np.asarray(phi_Q_target, dtype=np.float64)[None, :M + 2], x=x, u0=u[None])
+    R = eng.pgd_newton(int(n_newton), k=k, cg_tol=cg_tol, max_halvings=max_halvings)
+    records = []
+    for r in range(int(R["rounds"])):
+        if Engine1D.NEWTON_STATUS[int(R["status"][0, r])] == "idle":
+            break
+        s = float(R["s"][0, r])
+        records.append(dict(cost=float(R["cost"][0, r]), n_free=int(R["n_free"][0, r]), rnorm0=float(R["rnorm0"][0, r]),
+                            steps=int(R["cg_steps"][0, r]), status=Engine1D.CG_STATUS[int(R["cg_status"][0, r])],
+                            s=None if np.isnan(s) else s, cost_new=float(R["cost_new"][0, r])))
+    return eng.pgd_get("u"), records
 
 
 def main(n_iter=None, params_file="last_run_config.json", control_file="optimal_control.npy", num_directions=3,

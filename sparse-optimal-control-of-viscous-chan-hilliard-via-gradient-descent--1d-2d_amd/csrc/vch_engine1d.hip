@@ -4,6 +4,7 @@
 #include "vch_common.h"
 #include "vch_kernels1d.h"
 #include "vch_pgd.h"
+#include "vch_newton.h"
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -59,6 +60,15 @@ struct vch1d_ctx {
     // vch1d_hess_cg keeps x, r, p in slots 0, 1, 2 of kr_Q (either call invalidates what the other left resident)
     bool ncg_valid = false;
     int ncg_rows = 0;
+    // what vch1d_newton_trial needs of the last vch1d_hess_cg beside x: its base control (NULL: zeros) with its stride and
+    // the stride of its mask; ncg_u_live: the call's own copy of an uploaded control has not been overwritten since
+    const double *ncg_u = nullptr;
+    long ncg_us = 0, ncg_mask_s = 0;
+    bool ncg_u_live = false;
+    // vch1d_pgd_newton: the PGD problem's own dt and x on the host, and who of the trajectories the stop rule ended has had
+    // its state history and stored cost brought up to its control (the stop quirk)
+    std::vector<double> dt_host, x_host;
+    std::vector<int> pgd_synced;
 };
 
 // no launch bookkeeping (LAUNCH_LDS, vch_common.h)
@@ -476,14 +486,21 @@ static int l2sq1_core(vch1d_ctx *c, const double *arr, long stride, int rows, do
     return 0;
 }
 
-static int fwd1_core(vch1d_ctx *c, const double *u_dev, int rows, double *hist_dev, const int *skip_dev) {
+// bad_out (NULL for every caller but the Newton rounds): [B], a march that reports a non-finite mass defect does not fail
+// the call; bad_out[b] says whose did, and that trajectory's flag is cleared on the device, where a later march that it
+// sits out would find it again.  A skipped trajectory's entry is what its last march left.
+static int fwd1_core(vch1d_ctx *c, const double *u_dev, int rows, double *hist_dev, const int *skip_dev, int *bad_out = nullptr) {
     const int M = rows - 2;
     LAUNCH_LDS(-1, k1d_forward, dim3(c->B), dim3(T1), c->lds_bytes, c->P, c->n, c->h, c->lvl, M, (const double *)c->dts,
             (const double *)c->phi0_dev, u_dev, rows, hs1(c), hist_dev, hs1(c), c->scratch, c->stats_dev, skip_dev);
     HIPCHK(hipMemcpyAsync(c->stats_host, c->stats_dev, sizeof(int) * 8 * c->B, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    for (int b = 0; b < c->B; ++b)
-        if (c->stats_host[b * 8 + 4]) return vch_fail(VCH_ERR_STATE, "Non-finite mass_defect; check phi bounds/log regularization.");
+    for (int b = 0; b < c->B; ++b) {
+        const bool bad = c->stats_host[b * 8 + 4] != 0;
+        if (bad && !bad_out) return vch_fail(VCH_ERR_STATE, "Non-finite mass_defect; check phi bounds/log regularization.");
+        if (bad_out) bad_out[b] = bad;
+        if (bad) HIPCHK(hipMemsetAsync(c->stats_dev + b * 8 + 4, 0, sizeof(int), c->stream));
+    }
     return 0;
 }
 
@@ -525,6 +542,9 @@ extern "C" int vch1d_pgd_init_v(vch1d_ctx *c, const double *phi0, const double *
     c->pgd_r_valid = false;
     c->pgd_rows = rows;
     c->t_host.assign(t_hist, t_hist + rows);
+    c->dt_host.assign(dt, dt + M);
+    c->x_host.assign(x, x + c->n);
+    c->pgd_synced.assign(B, 0);
     {   // what the resident problem needs beyond the buffers of vch1d_create: all of it, or nothing more than there was
         vch_group g(c->pool);
         double **hs[] = {&c->phi_hist, &c->u_hist, &c->u_trial, &c->phiQ, &c->p_hist, &c->q_hist, &c->r_hist, &c->phi_trial};
@@ -771,6 +791,7 @@ static int so1_base(vch1d_ctx *c, const double *phi_hist, const double *u, const
         S.u = c->u_hist;
     } else if (u) {
         VCHCHK(ensure1(c, &c->so_u));
+        c->ncg_u_live = false;          // vch1d_newton_trial: the copy an earlier vch1d_hess_cg made is gone
         VCHCHK(up_hist_n(c, c->so_u, u, rows, n_base));
         S.u = c->so_u;
     }
@@ -948,6 +969,7 @@ extern "C" int vch1d_hessvec(vch1d_ctx *c, const double *phi_hist, const double 
 // alpha / beta per trajectory.
 struct Kr1Layout {
     size_t part, coef1, coef2, ucoef, alpha, beta, look, scal, amax, lim, stop, steps, box, wt, mean, wtp, ks, total;
+    size_t ntpart, nts, ntsum;      // vch1d_newton_trial: its partials [B][chunks][4], the step table [B], the sums [B][4]
 };
 static int kr1_chunks(const vch1d_ctx *c, int rows) { return (int)(((long)rows * c->n + KR1_CHUNK - 1) / KR1_CHUNK); }
 static Kr1Layout kr1_layout(const vch1d_ctx *c, int S, int K) {
@@ -972,6 +994,9 @@ static Kr1Layout kr1_layout(const vch1d_ctx *c, int S, int K) {
     L.mean = take(B * R);
     L.wtp = take(R);
     L.ks = take(B);
+    L.ntpart = take(B * kr1_chunks(c, (int)R) * 4);
+    L.nts = take(B);
+    L.ntsum = take(4 * B);
     L.total = at;
     return L;
 }
@@ -1171,14 +1196,42 @@ extern "C" int vch1d_krylov_vector(vch1d_ctx *c, const double *coef, int m, doub
 // recurrence on the device (kernels: "Device-resident Newton-CG" in vch_kernels1d.h).  The storage, the
 // step kernel and the look schedule are those of vch1d_hess_lanczos without reorthogonalisation.
 // ------------------------------------------------------------------------------------
-extern "C" int vch1d_hess_cg(vch1d_ctx *c, const double *phi_hist, const double *u, int n_base, int rows, const double *dt,
-                             const double *t_hist, const double *x, const double *phi_Q, const double *phi_T,
-                             const vch_opt_params *opts, int n_opts, const uint8_t *mask, double tol, const double *rhs, int k,
-                             double cg_tol, int precond, double *resid_out, double *curv_out, double *pred_out, double *rnorm0_out,
-                             int32_t *steps_out, int32_t *status_out, int64_t *n_free_out, vch_stats *stats) {
-    CTXCHK(c);
+// The trapezoid weights wt of t_hist as in vch1d_hessvec and the preconditioner's wt', which gives row 0 (weight zero, but a
+// real unknown) the weight of row 1, which duplicates its time; with precond every wt' must be positive and finite.
+static int ncg1_weights(const char *fn, const double *t_hist, int rows, int precond, std::vector<double> &wt, std::vector<double> &wtp) {
+    wt.assign(rows, 0.0);
+    for (int r = 0; r + 1 < rows; ++r) {
+        const double d = t_hist[r + 1] - t_hist[r];
+        wt[r] += 0.5 * d;
+        wt[r + 1] += 0.5 * d;
+    }
+    wtp = wt;
+    wtp[0] = wt[1];
+    if (precond)
+        for (int r = 0; r < rows; ++r)
+            if (!(wtp[r] > 0.0) || !std::isfinite(wtp[r]))
+                return vch_fail(VCH_ERR_ARG, "%s: row %d: the preconditioner's time weight %g must be positive and finite (t_hist "
+                                "must increase from row 1 on)", fn, r, wtp[r]);
+    return 0;
+}
+// the cells of the iteration in the block of the Lanczos scalars: resid, curv where alpha, beta live
+static Ncg1Cells ncg1_cells(const vch1d_ctx *c, const Kr1Layout &L) {
+    double *sc = c->kr_sc;
+    const int B = c->B;
+    return Ncg1Cells{sc + L.alpha, sc + L.beta, sc + L.look, sc + L.scal, sc + L.amax, sc + L.coef1, sc + L.coef1 + B,
+                     sc + L.coef1 + 2 * B, (long long *)(sc + L.steps), (long long *)(sc + L.lim), (long long *)(sc + L.stop)};
+}
+
+// The body of vch1d_hess_cg, shared with the rounds of vch1d_pgd_newton.  fn: the entry point the messages name.
+// empty_ok (the Newton rounds): a trajectory with an empty free set is no error.  The set-up returns for it before it
+// writes x, r, p and its cells, so the host takes n_free = 0 from the look alone: zero steps, VCH_CG_CONVERGED,
+// pred = rnorm0 = 0, none of the stale cells read, and its three slots zeroed for vch1d_cg_vector.
+static int hess_cg1_core(vch1d_ctx *c, const char *fn, bool empty_ok, const double *phi_hist, const double *u, int n_base, int rows,
+                         const double *dt, const double *t_hist, const double *x, const double *phi_Q, const double *phi_T,
+                         const vch_opt_params *opts, int n_opts, const uint8_t *mask, double tol, const double *rhs, int k,
+                         double cg_tol, int precond, double *resid_out, double *curv_out, double *pred_out, double *rnorm0_out,
+                         int32_t *steps_out, int32_t *status_out, int64_t *n_free_out, vch_stats *stats) {
     const int B = c->B, n = c->n;
-    const char *fn = "vch1d_hess_cg";
     VCHCHK(so1_check_shape(c, fn, n_base, rows, n_opts, 2));
     if (!resid_out || !curv_out || !pred_out || !rnorm0_out || !steps_out || !status_out || !n_free_out)
         return vch_fail(VCH_ERR_ARG, "%s: NULL resid_out, curv_out, pred_out, rnorm0_out, steps_out, status_out or n_free_out", fn);
@@ -1188,21 +1241,8 @@ extern "C" int vch1d_hess_cg(vch1d_ctx *c, const double *phi_hist, const double 
     if (!mask && !u) return vch_fail(VCH_ERR_ARG, "%s: NULL mask with a NULL (zero) control: no node is free", fn);
     std::vector<double> dts, wts, wx;
     VCHCHK(so1_check_rest(c, fn, phi_hist, u, rows, dt, t_hist, x, phi_Q, phi_T, opts, n_opts, dts, wts));
-    // trapezoid weights of t_hist as in vch1d_hessvec; the preconditioner's wt' gives row 0 (weight zero, but a real unknown)
-    // the weight of row 1, which duplicates its time
-    std::vector<double> wt(rows, 0.0);
-    for (int r = 0; r + 1 < rows; ++r) {
-        const double d = t_hist[r + 1] - t_hist[r];
-        wt[r] += 0.5 * d;
-        wt[r + 1] += 0.5 * d;
-    }
-    std::vector<double> wtp(wt);
-    wtp[0] = wt[1];
-    if (precond)
-        for (int r = 0; r < rows; ++r)
-            if (!(wtp[r] > 0.0) || !std::isfinite(wtp[r]))
-                return vch_fail(VCH_ERR_ARG, "%s: row %d: the preconditioner's time weight %g must be positive and finite (t_hist "
-                                "must increase from row 1 on)", fn, r, wtp[r]);
+    std::vector<double> wt, wtp;
+    VCHCHK(ncg1_weights(fn, t_hist, rows, precond, wt, wtp));
     // ---- nothing was launched, copied or allocated up to here
     const int M = rows - 2;
     const long hs = hs1(c);
@@ -1210,9 +1250,7 @@ extern "C" int vch1d_hess_cg(vch1d_ctx *c, const double *phi_hist, const double 
     const Kr1Layout L = kr1_layout(c, c->kr_slots, c->kr_kcap);
     const bool build = mask == nullptr;
     double *sc = c->kr_sc;
-    // the cells of the iteration in the block of the Lanczos scalars: resid, curv where alpha, beta live
-    const Ncg1Cells cells{sc + L.alpha, sc + L.beta, sc + L.look, sc + L.scal, sc + L.amax, sc + L.coef1, sc + L.coef1 + B,
-                          sc + L.coef1 + 2 * B, (long long *)(sc + L.steps), (long long *)(sc + L.lim), (long long *)(sc + L.stop)};
+    const Ncg1Cells cells = ncg1_cells(c, L);
     const int S = c->kr_slots, nch = kr1_chunks(c, rows);
     const Ncg1Args K{c->kr_Q, (long)B * hs, hs, (long)rows * n, n, S, c->kr_mask, (build || n_base == B) ? hs : 0,
                      sc + L.wtp, c->so_wx, precond, cells};
@@ -1262,10 +1300,15 @@ extern "C" int vch1d_hess_cg(vch1d_ctx *c, const double *phi_hist, const double 
     std::vector<double> look(2 * (size_t)B);
     VCHCHK(down(c, look.data(), cells.look, look.size()));          // the first look; the host vectors above are done with
     for (int b = 0; b < B; ++b) {
-        if (look[2 * b] < 1.0) return vch_fail(VCH_ERR_ARG, "%s: trajectory %d: the free set is empty", fn, b);
+        if (look[2 * b] < 1.0 && !empty_ok) return vch_fail(VCH_ERR_ARG, "%s: trajectory %d: the free set is empty", fn, b);
         if (!std::isfinite(look[2 * b + 1]))
             return vch_fail(VCH_ERR_ARG, "%s: trajectory %d: the right-hand side is not finite on the free set", fn, b);
     }
+    // an empty free set (empty_ok): the set-up wrote nothing of x, r, p; its stop cell keeps the kernels below off them
+    for (int b = 0; b < B; ++b)
+        if (look[2 * b] < 1.0)
+            for (int slot = 0; slot < 3; ++slot)
+                HIPCHK(hipMemsetAsync(c->kr_Q + (long)slot * B * hs + b * hs, 0, sizeof(double) * rows * n, c->stream));
     // k steps back to back: a stopped trajectory's kernels return at once, the host does not look
     for (int j = 0; j < k; ++j) {
         if (c->kr_nocache)
@@ -1293,6 +1336,13 @@ extern "C" int vch1d_hess_cg(vch1d_ctx *c, const double *phi_hist, const double 
     HIPCHK(hipStreamSynchronize(c->stream));                        // the second look
     int64_t solves = 0;
     for (int b = 0; b < B; ++b) {
+        if (look[2 * b] < 1.0) {                    // empty_ok: the cells of this trajectory are stale, and there was no sweep
+            steps_out[b] = 0;
+            status_out[b] = VCH_CG_CONVERGED;
+            n_free_out[b] = 0;
+            pred_out[b] = rnorm0_out[b] = 0.0;
+            continue;
+        }
         steps_out[b] = (int32_t)steps[b];
         status_out[b] = (int32_t)stop[b];           // 0: still running after k steps, VCH_CG_LIMIT
         n_free_out[b] = (int64_t)look[2 * b];
@@ -1310,7 +1360,21 @@ extern "C" int vch1d_hess_cg(vch1d_ctx *c, const double *phi_hist, const double 
     }
     c->ncg_valid = true;
     c->ncg_rows = rows;
+    c->ncg_u = Sb.u;
+    c->ncg_us = Sb.bs;
+    c->ncg_mask_s = K.mask_s;
+    c->ncg_u_live = true;
     return 0;
+}
+
+extern "C" int vch1d_hess_cg(vch1d_ctx *c, const double *phi_hist, const double *u, int n_base, int rows, const double *dt,
+                             const double *t_hist, const double *x, const double *phi_Q, const double *phi_T,
+                             const vch_opt_params *opts, int n_opts, const uint8_t *mask, double tol, const double *rhs, int k,
+                             double cg_tol, int precond, double *resid_out, double *curv_out, double *pred_out, double *rnorm0_out,
+                             int32_t *steps_out, int32_t *status_out, int64_t *n_free_out, vch_stats *stats) {
+    CTXCHK(c);
+    return hess_cg1_core(c, "vch1d_hess_cg", false, phi_hist, u, n_base, rows, dt, t_hist, x, phi_Q, phi_T, opts, n_opts, mask, tol, rhs,
+                         k, cg_tol, precond, resid_out, curv_out, pred_out, rnorm0_out, steps_out, status_out, n_free_out, stats);
 }
 
 extern "C" int vch1d_cg_vector(vch1d_ctx *c, int which, double *out) {
@@ -1320,4 +1384,186 @@ extern "C" int vch1d_cg_vector(vch1d_ctx *c, int which, double *out) {
     if (!c->ncg_valid || !c->kr_Q)
         return vch_fail(VCH_ERR_STATE, "vch1d_cg_vector: no resident vectors (call vch1d_hess_cg first)");
     return down_hist(c, out, c->kr_Q + (long)which * c->B * hs1(c), c->ncg_rows);
+}
+
+// ------------------------------------------------------------------------------------
+// Damped Newton rounds on the free set about the resident PGD iterate (kernels: "Damped Newton rounds" in vch_kernels1d.h,
+// verdicts: vch_newton.h)
+// ------------------------------------------------------------------------------------
+// The trial control of the step lengths s_host [B] into the trial-control scratch, about the base control, the x, the free
+// set and the box table the last Newton-CG solve left; skip (device flags, or NULL) leaves a trajectory alone.  The step
+// table, the partials and the sums have cells of their own in the block of the Krylov scalars; sums_out [B][4] =
+// {sum (t - u)^2, sum u^2, pinned, clipped} after one look (the cells of a skipped trajectory are not written).
+static int newton_trial1_core(vch1d_ctx *c, const double *s_host, const int *skip, double *sums_out) {
+    const int B = c->B, rows = c->ncg_rows, nch = kr1_chunks(c, rows);
+    const long hs = hs1(c);
+    const Kr1Layout L = kr1_layout(c, c->kr_slots, c->kr_kcap);
+    double *sc = c->kr_sc;
+    const Ncg1Args K{c->kr_Q, (long)B * hs, hs, (long)rows * c->n, c->n, c->kr_slots, c->kr_mask, c->ncg_mask_s,
+                     sc + L.wtp, c->so_wx, 0, ncg1_cells(c, L)};
+    VCHCHK(up(c, sc + L.nts, s_host, B));
+    LAUNCH(k1d_nt_trial, dim3(nch, B), dim3(KR1_T), K, c->ncg_u, c->ncg_us, (const double *)(sc + L.nts), (const double *)(sc + L.box),
+           skip, c->u_trial, sc + L.ntpart);
+    LAUNCH(k1d_nt_fin, dim3(B), dim3(KR1_T), (const double *)(sc + L.ntpart), nch, skip, sc + L.ntsum);
+    return down(c, sums_out, sc + L.ntsum, 4 * (size_t)B);         // synchronises: s_host is done with
+}
+
+extern "C" int vch1d_newton_trial(vch1d_ctx *c, const double *s, double *u_out, double *chg_out, int64_t *counts_out) {
+    CTXCHK(c);
+    ARGCHK(s && chg_out && counts_out, "NULL s, chg_out or counts_out");
+    for (int b = 0; b < c->B; ++b) ARGCHK(std::isfinite(s[b]) && s[b] > 0, "s must be finite and > 0");
+    if (!c->ncg_valid || !c->kr_Q)
+        return vch_fail(VCH_ERR_STATE, "vch1d_newton_trial: no resident vectors (call vch1d_hess_cg first)");
+    if (c->ncg_u && c->ncg_u == c->so_u && !c->ncg_u_live)
+        return vch_fail(VCH_ERR_STATE, "vch1d_newton_trial: the base control of the last vch1d_hess_cg has been replaced by a later call");
+    VCHCHK(ensure1(c, &c->u_trial));
+    std::vector<double> sums(4 * (size_t)c->B);
+    VCHCHK(newton_trial1_core(c, s, nullptr, sums.data()));
+    for (int b = 0; b < c->B; ++b) {
+        chg_out[2 * b] = sums[4 * b];
+        chg_out[2 * b + 1] = sums[4 * b + 1];
+        counts_out[2 * b] = (int64_t)sums[4 * b + 2];
+        counts_out[2 * b + 1] = (int64_t)sums[4 * b + 3];
+    }
+    return u_out ? down_hist(c, u_out, c->u_trial, c->ncg_rows) : 0;
+}
+
+extern "C" int vch1d_pgd_newton(vch1d_ctx *c, int n_rounds, int k, double cg_tol, int precond, double tol, int max_halvings,
+                                double *cost_out, double *cost_new_out, double *s_out, double *pred_out, double *rnorm0_out,
+                                int32_t *halvings_out, int32_t *cg_steps_out, int32_t *cg_status_out, int32_t *status_out,
+                                int64_t *counts_out, double *seconds_out) {
+    CTXCHK(c);
+    const char *fn = "vch1d_pgd_newton";
+    // everything below is checked before anything is enqueued, copied or allocated
+    if (!c->pgd_ready) return vch_fail(VCH_ERR_STATE, "%s: call vch1d_pgd_init first", fn);
+    ARGCHK(n_rounds >= 1, "n_rounds must be >= 1");
+    ARGCHK(k >= 1, "k must be >= 1");
+    ARGCHK(max_halvings >= 0, "max_halvings must be >= 0");
+    ARGCHK(precond == 0 || precond == 1, "precond must be 0 or 1");
+    ARGCHK(std::isfinite(cg_tol), "cg_tol must be finite");
+    ARGCHK(cost_out && cost_new_out && s_out && pred_out && rnorm0_out && halvings_out && cg_steps_out && cg_status_out && status_out &&
+               counts_out,
+           "NULL cost_out, cost_new_out, s_out, pred_out, rnorm0_out, halvings_out, cg_steps_out, cg_status_out, status_out or counts_out");
+    const int B = c->B, rows = c->pgd_rows;
+    {   // what the solve of a round checks, here as well: the stop quirk below marches before the first solve
+        std::vector<double> dts, wts, wt, wtp;
+        VCHCHK(so1_check_shape(c, fn, B, rows, B, 2));
+        VCHCHK(so1_check_rest(c, fn, nullptr, VCH_RESIDENT, rows, c->dt_host.data(), c->t_host.data(), c->x_host.data(), VCH_RESIDENT,
+                              VCH_RESIDENT, c->opts.data(), B, dts, wts));
+        VCHCHK(ncg1_weights(fn, c->t_host.data(), rows, precond, wt, wtp));
+    }
+    const double nan = std::nan("");
+    for (size_t i = 0; i < (size_t)B * n_rounds; ++i) {
+        cost_out[i] = cost_new_out[i] = s_out[i] = pred_out[i] = rnorm0_out[i] = nan;
+        halvings_out[i] = cg_steps_out[i] = cg_status_out[i] = 0;
+        status_out[i] = VCH_NEWTON_IDLE;
+        counts_out[3 * i] = counts_out[3 * i + 1] = counts_out[3 * i + 2] = 0;
+    }
+    double sec[4] = {0, 0, 0, 0};
+    auto tick = [&](hipEvent_t e) { return hipEventRecord(e, c->stream); };
+    auto lap = [&]() {
+        float ms = 0;
+        hipEventSynchronize(c->ev1);
+        hipEventElapsedTime(&ms, c->ev0, c->ev1);
+        return (double)ms * 1e-3;
+    };
+    vch_newton_state nt;
+    nt.reset(B);
+    std::vector<double> resid((size_t)B * k), curv((size_t)B * k), pred(B), rn0(B), Jt(5 * (size_t)B), sums(4 * (size_t)B);
+    std::vector<int32_t> steps(B), cgst(B);
+    std::vector<int64_t> nfree(B);
+    std::vector<int> bad(B), sit(B);
+    bool moved = false;
+    int done_rounds = 0;
+    auto run = [&]() -> int {
+        // --- the stop quirk: a trajectory the PGD stop rule ended holds the new control beside the previous iterate's state
+        // and cost (G1:462-465).  One march of the resident control, the others sitting it out, brings both up to the control.
+        bool stale = false;
+        for (int b = 0; b < B; ++b) {
+            sit[b] = !(c->pgd.done[b] && !c->pgd_synced[b]);
+            stale = stale || !sit[b];
+        }
+        if (stale) {
+            HIPCHK(tick(c->ev0));
+            HIPCHK(hipMemcpyAsync(c->skip_dev, sit.data(), sizeof(int) * B, hipMemcpyHostToDevice, c->stream));
+            VCHCHK(fwd1_core(c, c->u_hist, rows, c->phi_trial, c->skip_dev));
+            HIPCHK(tick(c->ev1));
+            sec[2] += lap();
+            HIPCHK(tick(c->ev0));
+            VCHCHK(cost1_core(c, c->phi_trial, c->u_hist, rows, Jt.data()));
+            HIPCHK(tick(c->ev1));
+            sec[3] += lap();
+            for (int b = 0; b < B; ++b) {
+                if (sit[b]) continue;
+                VCHCHK(copy_traj1(c, c->phi_hist, c->phi_trial, b, rows));
+                c->pgd.cost[b] = Jt[5 * b + 4];
+                c->pgd_synced[b] = 1;
+            }
+            HIPCHK(hipStreamSynchronize(c->stream));
+        }
+        for (int r = 0; r < n_rounds; ++r) {
+            if (!nt.begin_round()) break;
+            // --- the Newton step of every trajectory on its free set; the solves of an idle one are not gated
+            vch_stats cg;
+            VCHCHK(hess_cg1_core(c, fn, true, nullptr, VCH_RESIDENT, B, rows, c->dt_host.data(), c->t_host.data(), c->x_host.data(),
+                                 VCH_RESIDENT, VCH_RESIDENT, c->opts.data(), B, nullptr, tol, nullptr, k, cg_tol, precond, resid.data(),
+                                 curv.data(), pred.data(), rn0.data(), steps.data(), cgst.data(), nfree.data(), &cg));
+            sec[0] += cg.seconds;
+            for (int b = 0; b < B; ++b) {
+                if (nt.idle(b)) continue;
+                const size_t i = (size_t)b * n_rounds + r;
+                cost_out[i] = cost_new_out[i] = c->pgd.cost[b];
+                pred_out[i] = pred[b];
+                rnorm0_out[i] = rn0[b];
+                cg_steps_out[i] = steps[b];
+                cg_status_out[i] = cgst[b];
+                counts_out[3 * i] = nfree[b];
+                status_out[i] = nt.after_solve(b, nfree[b], rn0[b], cgst[b], steps[b]);
+            }
+            // --- trials s = 1, 1/2, ...: a trajectory whose verdict is in sits the trial out
+            while (!nt.all_decided()) {
+                HIPCHK(tick(c->ev0));
+                HIPCHK(hipMemcpyAsync(c->skip_dev, nt.decided.data(), sizeof(int) * B, hipMemcpyHostToDevice, c->stream));
+                VCHCHK(newton_trial1_core(c, nt.s.data(), c->skip_dev, sums.data()));
+                HIPCHK(tick(c->ev1));
+                sec[1] += lap();
+                HIPCHK(tick(c->ev0));
+                VCHCHK(fwd1_core(c, c->u_trial, rows, c->phi_trial, c->skip_dev, bad.data()));
+                HIPCHK(tick(c->ev1));
+                sec[2] += lap();
+                HIPCHK(tick(c->ev0));
+                VCHCHK(cost1_core(c, c->phi_trial, c->u_trial, rows, Jt.data()));
+                HIPCHK(tick(c->ev1));
+                sec[3] += lap();
+                for (int b = 0; b < B; ++b) {
+                    if (nt.decided[b]) continue;
+                    const size_t i = (size_t)b * n_rounds + r;
+                    halvings_out[i] = nt.halvings[b];
+                    counts_out[3 * i + 1] = (int64_t)sums[4 * b + 2];
+                    counts_out[3 * i + 2] = (int64_t)sums[4 * b + 3];
+                    const double s = nt.s[b];
+                    // a march that reported a non-finite mass defect: the trial counts as not accepted
+                    const double c_new = bad[b] ? nan : Jt[5 * b + 4];
+                    const vch_newton_verdict v = nt.judge(b, c->pgd.cost[b], pred[b], c_new, max_halvings);
+                    if (v == VCH_NT_STALL) status_out[i] = VCH_NEWTON_STALLED;
+                    if (v != VCH_NT_ACCEPT) continue;
+                    // accepted: the trial becomes the iterate, as in the PGD loop
+                    c->pgd.cost[b] = c_new;
+                    VCHCHK(copy_traj1(c, c->u_hist, c->u_trial, b, rows));
+                    VCHCHK(copy_traj1(c, c->phi_hist, c->phi_trial, b, rows));
+                    moved = true;
+                    cost_new_out[i] = c_new;
+                    s_out[i] = s;
+                }
+                HIPCHK(hipStreamSynchronize(c->stream));
+            }
+            done_rounds = r + 1;
+        }
+        return 0;
+    };
+    const int rc = run();
+    if (moved) c->pgd_r_valid = false;      // r_hist is the adjoint of an iterate that has been replaced
+    if (rc < 0) return rc;
+    if (seconds_out) memcpy(seconds_out, sec, sizeof(sec));
+    return done_rounds;
 }

@@ -1685,8 +1685,6 @@ __global__ __launch_bounds__(KR1_T) void k1d_ncg_dir(Ncg1Args a) {
         if (i < i1) ps[i] = rv[t] / d[t] + be * pv[t];
     }
 }
-#undef NCG1_COORDS
-
 // kr1_sum, word for word (the same order of additions).  A copy, not a call: a second kernel calling kr1_sum can change
 // the registers k1d_kr_fin compiles to (DESIGN.md 10g found that for the 2D pair).
 __device__ __forceinline__ double ncg1_sum(const double *__restrict__ part, int nch, int S, int slot, double *sh) {
@@ -1735,4 +1733,104 @@ __global__ __launch_bounds__(KR1_T) void k1d_ncg_fin(Ncg1Cells x, const double *
         }
     }
     x.stop[b] = st;
+}
+
+// ---------------------------------------------------------------------------------
+// Damped Newton rounds on the free set (vch1d_pgd_newton, vch1d_newton_trial): the trial control of a step
+// length, on the streaming grid of the Newton-CG kernels above (chunks of KR1_CHUNK nodes, B) with their indexing: node i of
+// trajectory b sits at b hs + i, hs the stride of a history of max_steps + 2 rows, not rows n.  x is slot NCG1_X, the mask
+// the bytes of the set-up, box [B][2] its table, s_tab [B] the step lengths; u is the base control of the solve (stride u_s,
+// 0 for a shared base; NULL: zeros).  A trajectory whose verdict is in (skip[b] != 0; skip may be NULL) returns at once.
+//
+// Per node t = min(max(u + s_b x, u_min_b), u_max_b) with NumPy's order of comparisons (a NaN stays a NaN); a free node with
+// t u < 0 becomes 0, the kink, where the next round pins it.  Every s the rounds use is a power of two, so s x is exact
+// (short of an underflow) and u + s x rounds once whether or not the compiler fuses the multiply-add: the trial has the
+// bits of np.clip(u + s * d, lo, hi).  A thread keeps its KR1_PER nodes in registers and requests u, x and the mask byte of
+// all of them before the first use: 17 bytes read and 8 written per node.  Partials [B][chunks][4] = {sum (t - u)^2,
+// sum u^2, nodes pinned to 0, nodes the clip moved} (the counts exact in a double): lane shuffle, then the four wave sums
+// in turn.  No atomics.
+// ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(KR1_T) void k1d_nt_trial(Ncg1Args a, const double *__restrict__ u, long u_s,
+                                                      const double *__restrict__ s_tab, const double *__restrict__ box,
+                                                      const int *__restrict__ skip, double *__restrict__ trial,
+                                                      double *__restrict__ part) {
+    NCG1_COORDS;
+    if (skip && skip[b]) return;            // uniform over the workgroup
+    __shared__ double sred[4 * (KR1_T / 64)];
+    const unsigned char *mk = a.mask + b * a.mask_s;
+    const double *xs = ncg1_slot(a, NCG1_X) + hb;
+    const double *ub = u ? u + b * u_s : nullptr;
+    double *tb = trial + hb;
+    const double s = s_tab[b], lo = box[2 * b], hi = box[2 * b + 1];
+    double uv[KR1_PER], xv[KR1_PER];
+    unsigned int m[KR1_PER];
+#pragma unroll
+    for (int t = 0; t < KR1_PER; ++t) {
+        const long i = i0 + t * KR1_T;
+        const bool in = i < i1;
+        uv[t] = (in && ub) ? ub[i] : 0.0;
+        xv[t] = in ? xs[i] : 0.0;
+        m[t] = in ? (unsigned int)mk[i] : 0u;
+    }
+    // the mask bytes stay in registers as they came: a test of one here would wait for it in front of the next node's requests
+#pragma unroll
+    for (int t = 0; t < KR1_PER; ++t) asm volatile("" : "+v"(m[t]));
+    // no branch between the requests and the stores: a node beyond the chunk adds zeros, and its trial (in xv) is not stored
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int t = 0; t < KR1_PER; ++t) {
+        const bool in = i0 + t * KR1_T < i1;
+        const double v = uv[t] + s * xv[t];
+        double tv = (v != v || v > lo) ? v : lo;
+        tv = (tv != tv || tv < hi) ? tv : hi;
+        const bool moved = tv != v;
+        const bool pin = m[t] != 0u && tv * uv[t] < 0.0;
+        tv = pin ? 0.0 : tv;
+        const double d = in ? tv - uv[t] : 0.0;
+        acc[0] += d * d;
+        acc[1] += uv[t] * uv[t];
+        acc[2] += (in && pin) ? 1.0 : 0.0;
+        acc[3] += (in && moved) ? 1.0 : 0.0;
+        xv[t] = tv;
+    }
+#pragma unroll
+    for (int t = 0; t < KR1_PER; ++t) {
+        const long i = i0 + t * KR1_T;
+        if (i < i1) tb[i] = xv[t];
+    }
+    const int lane = tid & 63, wv = tid >> 6;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const double w = wsum1(acc[q]);
+        if (lane == 0) sred[q * (KR1_T / 64) + wv] = w;
+    }
+    __syncthreads();
+    if (tid < 4) {
+        const double *w = sred + tid * (KR1_T / 64);
+        part[((long)b * gridDim.x + blockIdx.x) * 4 + tid] = ((w[0] + w[1]) + w[2]) + w[3];
+    }
+}
+#undef NCG1_COORDS
+
+// The four sums of a trajectory's partials, one workgroup of KR1_T threads per trajectory, in the order of kr1_sum (a copy,
+// as ncg1_sum is, so that k1d_kr_fin and k1d_ncg_fin keep their registers).  out [B][4]; a skipped trajectory's cells are
+// left alone.
+__global__ __launch_bounds__(KR1_T) void k1d_nt_fin(const double *__restrict__ part, int nch, const int *__restrict__ skip,
+                                                    double *__restrict__ out) {
+    __shared__ double sh[KR1_T];
+    const int b = blockIdx.x;
+    if (skip && skip[b]) return;            // uniform over the workgroup
+    const double *p = part + (long)b * nch * 4;
+    for (int slot = 0; slot < 4; ++slot) {
+        double s = 0.0;
+        for (int e = threadIdx.x; e < nch; e += KR1_T) s += p[(long)e * 4 + slot];
+        sh[threadIdx.x] = s;
+        __syncthreads();
+        for (int hh = KR1_T / 2; hh > 0; hh >>= 1) {
+            if ((int)threadIdx.x < hh) sh[threadIdx.x] += sh[threadIdx.x + hh];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) out[4 * b + slot] = sh[0];
+        __syncthreads();
+    }
 }

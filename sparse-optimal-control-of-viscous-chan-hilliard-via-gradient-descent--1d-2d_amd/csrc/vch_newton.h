@@ -1,6 +1,7 @@
-// vch_newton.h — the verdicts of the device-resident damped Newton rounds (vch2d_pgd_newton): who ends after
-// the solve, the Armijo test and the halving of the trials, who sits a trial or a round out.  Host arithmetic only (no HIP,
-// no I/O): the engine acts on its verdicts, tests/newton_replay_main.cpp replays it on the CPU.
+// vch_newton.h — the verdicts of the device-resident damped Newton rounds of both engines (vch2d_pgd_newton, DESIGN.md 10i;
+// vch1d_pgd_newton): who ends after the solve, the Armijo test and the halving of the trials, who sits a trial
+// or a round out.  Host arithmetic only (no HIP, no I/O): the engines act on its verdicts, tests/newton_replay_main.cpp
+// replays it on the CPU.
 #pragma once
 #include "../../include/vch.h"
 #include <algorithm>

@@ -1078,3 +1078,47 @@ class Engine1D:
         out = np.empty((self.B, getattr(self, "_cg_rows", 1), self.n))
         check(self.lib.vch1d_cg_vector(self.ctx, "xrp".index(which), _dp(out)))
         return out
+
+    NEWTON_STATUS = Engine2D.NEWTON_STATUS      # VCH_NEWTON_ACCEPTED .. _IDLE
+
+    def pgd_newton(self, n_rounds, k=50, cg_tol=1e-8, precond=True, tol=0.0, max_halvings=10):
+        """Damped Newton rounds on the free set about the resident PGD iterate (vch1d_pgd_newton), every trajectory with
+        its own parameters and decisions; no history crosses the bus.  Per round: the Newton-CG step of hess_cg(rhs=None)
+        in its resident mode on the free set of the iterate (all rows, the duplicated t = 0 row included), then trials
+        clip(u + s x, box) for s = 1, 1/2, ... (a free node whose sign the trial flips is set to 0), at most `max_halvings`
+        halvings; the first s with J(trial) <= J(u) - 1e-4 s pred is accepted.  A trajectory ends with "stationary" (zero
+        right-hand side or empty free set), "negcurv" (the first CG direction has non-positive curvature), "breakdown" (CG
+        broke down: no march is started) or "stalled" (no s accepted) and is "idle" in all later rounds.  A trial whose march
+        reports a non-finite mass defect counts as not accepted.  A trajectory that the PGD stop rule ended has its state and
+        stored cost brought up to its control first.  Returns the keys of Engine2D.pgd_newton: dict(rounds: rounds run;
+        cost, cost_new, s, pred, rnorm0: (B, n_rounds), NaN where idle; halvings, cg_steps, cg_status (indices of
+        CG_STATUS), status (indices of NEWTON_STATUS): int32 (B, n_rounds); n_free, pinned, clipped: int64 (B, n_rounds);
+        seconds).  pgd_get, hess_cg, ... then work about the new iterate and a following pgd_iterate is that of
+        pgd_init(u0 = the Newton iterate)."""
+        n = max(int(n_rounds), 1)
+        dbl = [np.full((self.B, n), np.nan) for _ in range(5)]
+        i32 = [np.zeros((self.B, n), dtype=np.int32) for _ in range(4)]
+        cnt = np.zeros((self.B, n, 3), dtype=np.int64)
+        sec = np.zeros(4)
+        precond = int(precond) if isinstance(precond, (bool, int, np.integer)) else -1
+        done = check(self.lib.vch1d_pgd_newton(self.ctx, int(n_rounds), int(k), float(cg_tol), precond, float(tol), int(max_halvings),
+                                               *[_dp(a) for a in dbl], *[a.ctypes.data_as(_lib._I32) for a in i32],
+                                               cnt.ctypes.data_as(C.POINTER(C.c_int64)), _dp(sec)))
+        self._cg_rows = self._pgd_rows
+        out = dict(zip(("cost", "cost_new", "s", "pred", "rnorm0"), dbl), rounds=done)
+        out.update(zip(("halvings", "cg_steps", "cg_status", "status"), i32))
+        out.update(n_free=cnt[:, :, 0].copy(), pinned=cnt[:, :, 1].copy(), clipped=cnt[:, :, 2].copy(),
+                   seconds=dict(zip(("solve", "trial", "forward", "cost"), sec)))
+        return out
+
+    def newton_trial(self, s, want_u=True):
+        """The trial control t = clip(u + s_b x, box_b) of the step lengths `s` ([B] or a scalar, finite and > 0) about the
+        base control of the last hess_cg (stateless or resident), with its x, free set and box (vch1d_newton_trial): a free
+        node with t u < 0 becomes 0.  Writes only the trial-control scratch.  Returns dict(u: (B, rows, N+1) or None,
+        change: (B, 2) = {sum (t - u)^2, sum u^2}, pinned, clipped: int64 [B])."""
+        s = np.ascontiguousarray(np.broadcast_to(np.asarray(s, dtype=np.float64), (self.B,)))
+        out = np.empty((self.B, getattr(self, "_cg_rows", 1), self.n)) if want_u else None
+        chg = np.full((self.B, 2), np.nan)
+        cnt = np.zeros((self.B, 2), dtype=np.int64)
+        check(self.lib.vch1d_newton_trial(self.ctx, _dp(s), _dp(out), _dp(chg), cnt.ctypes.data_as(C.POINTER(C.c_int64))))
+        return dict(u=out, change=chg, pinned=cnt[:, 0].copy(), clipped=cnt[:, 1].copy())
