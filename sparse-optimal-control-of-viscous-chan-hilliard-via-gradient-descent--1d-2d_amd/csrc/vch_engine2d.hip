@@ -1204,6 +1204,7 @@ static int reset_counters(vch2d_ctx *c) {
     c->tot_launch += c->n_launch;
     c->tot_sync += c->n_sync;
     c->n_launch = c->n_sync = 0;
+    c->redo_iters = 0;        // the books of a repeated adjoint sweep close with the call that made them (fill_stats)
     return 0;
 }
 
@@ -1688,7 +1689,11 @@ static int write_opt_tab(vch2d_ctx *c, double *tab_dev, const vch_opt_params *o,
 // Launch schedule: the sweeps a solve needs change slowly along the sweep (the start p_{n+1} is a good guess), so the
 // host looks at the device state only every ADJ_LOOK steps and enqueues (longest solve so far) + 1 sweeps per step, within
 // the rigorous bound; solves are gated per trajectory, and one that its sweeps did not finish is counted on the device
-// (lin_unconv).  safe = true: a look and the rigorous budget at every step (the fallback of backward_core).
+// (lin_unconv).  In a batch of at most GUESS_BMAX every trajectory has a sweep cap of its own -- its own longest solve since
+// the last look + 1 (+ 2 at a look that changed its own guess order), within its own bound -- written into its record at
+// the look (k_adj_caps); its solves stop there, and the host enqueues the largest cap of the batch: the sweeps a
+// trajectory's solve gets are those of its single run (vch.h, vch2d_create).  Larger batches share one count, from the
+// longest solve of the batch.  safe = true: a look and the rigorous budget at every step (the fallback of backward_core).
 constexpr int ADJ_LOOK = 8, ADJ_SETTLE = 16;
 // opt_tab: the device table whose rows give every trajectory its b1 (adjoint source) and b2 (terminal condition).
 static int backward_pass(vch2d_ctx *c, const double *phi_hist_dev, int M, const double *t_hist, const double *opt_tab,
@@ -1697,6 +1702,8 @@ static int backward_pass(vch2d_ctx *c, const double *phi_hist_dev, int M, const 
     const Geom &G = c->G;
     double *rhs = c->cphi, *Dn = c->cmu, *rcur = c->wnew;
     double *qa = c->mu0, *qb = c->dmu;
+    // no sweep caps from an earlier sweep: the terminal solve, the first solve and the safe schedule run without
+    LAUNCH(k_adj_caps, dim3(c->B), dim3(64), c->st, AdjCaps{}, 0);
     // terminal condition (B2:183-187): (I - tau L) p_M = b2 (phi_M - phi_T), q_M = -L p_M, r_M = 0
     LAUNCH(k_scaled_diff, c->grid, dim3(NTH), G, phi_hist_dev + (long)M * G.plane, hs, phiT_dev, G.plane, opt_tab + OPT_B2, OPT_STRIDE, rhs,
            c->part);
@@ -1742,6 +1749,7 @@ static int backward_pass(vch2d_ctx *c, const double *phi_hist_dev, int M, const 
             for (int b = 0; b < c->B; ++b) longest = std::max(longest, c->st_host[b].step_lin_max);
             const int bound = cg_budget(c, false);
             int margin = 1;
+            std::vector<char> moved(order.size(), 0);         // trajectories whose guess order this look changed
             if (guess && !first_solve) {
                 // the state shows the solve of the previous level, started from a guess of the trajectory's current order
                 bool changed = false;
@@ -1750,10 +1758,11 @@ static int backward_pass(vch2d_ctx *c, const double *phi_hist_dev, int M, const 
                     if (ratio < 0.25) ord = std::min(ord + 1, GUESS_ORD / 2);
                     else if (ratio > 0.7) ord = std::max(ord - 1, 1);
                     changed |= ord != before;
+                    return ord != before;
                 };
                 auto fin = [](double r) { return std::isfinite(r) ? r : 1e300; };
                 if (per_traj) {
-                    for (int b = 0; b < c->B; ++b) adapt(order[b], fin(c->st_host[b].guess_ratio));
+                    for (int b = 0; b < c->B; ++b) moved[b] = adapt(order[b], fin(c->st_host[b].guess_ratio));
                 } else {
                     double worst = 0.0;
                     for (int b = 0; b < c->B; ++b) worst = std::max(worst, fin(c->st_host[b].guess_ratio));
@@ -1763,10 +1772,24 @@ static int backward_pass(vch2d_ctx *c, const double *phi_hist_dev, int M, const 
                 if (c->debug_guess)
                     fprintf(stderr, "adjoint level %d: order (traj 0) %d ratio %.3e longest %d\n", n, order[0],
                             c->st_host[0].guess_ratio, longest);
-                LAUNCH(k_reset_longest, dim3((c->B + 63) / 64), dim3(64), c->st, c->B);     // longest = since this look
+                if (!per_traj) LAUNCH(k_reset_longest, dim3((c->B + 63) / 64), dim3(64), c->st, c->B);     // longest = since this look
             }
-            // the first solve of the sweep has nothing to go by: rigorous bound, with looks
-            sweeps = (safe || first_solve) ? bound : std::max(2, std::min(longest + margin, bound));
+            if (safe || first_solve) {
+                sweeps = bound;       // the first solve of the sweep has nothing to go by: rigorous bound, with looks
+            } else if (per_traj) {
+                // every trajectory's cap from its own record; the host enqueues the largest
+                AdjCaps caps{};
+                sweeps = 2;
+                for (int b = 0; b < c->B; ++b) {
+                    const TrajState &S = c->st_host[b];
+                    const int own = S.lin_active ? std::min(S.lin_budget, c->lin_maxit) : 0;
+                    caps.cap[b] = std::max(2, std::min(S.step_lin_max + (moved[b] ? 2 : 1), own));
+                    sweeps = std::max(sweeps, caps.cap[b]);
+                }
+                LAUNCH(k_adj_caps, dim3(c->B), dim3(64), c->st, caps, guess ? 1 : 0);      // reset: longest = since this look
+            } else {
+                sweeps = std::max(2, std::min(longest + margin, bound));
+            }
         }
         ++steps_since_look;
         if (guess) {
@@ -1826,7 +1849,7 @@ static int backward_core(vch2d_ctx *c, const double *phi_hist_dev, int M, const 
         const TrajState &S = c->st_host[b];
         iters += S.lin_total;
         // a solve that ran out of sweeps above the solve tolerance's class: the schedule was too short somewhere
-        if ((S.lin_unconv > 0 && S.lin_maxrel > accept) || (S.lin_active && S.lin_rel > accept)) redo = true;
+        if ((S.lin_unconv > 0 && S.lin_maxrel > accept) || ((S.lin_active || S.lin_capped) && S.lin_rel > accept)) redo = true;
         else keep.push_back(b);
     }
     if (!redo) return 0;

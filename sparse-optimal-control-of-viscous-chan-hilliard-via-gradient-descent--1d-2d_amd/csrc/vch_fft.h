@@ -1131,7 +1131,9 @@ __device__ __forceinline__ CgNext cg_next_adj(double pq, double qq, double gamma
     return cg_step(pq, qq, gamma, it_old, tol, maxit, [&] { return rel_now; },
                    [&](double gn) { return sqrt(gn / gamma) * rel_now; });
 }
-__device__ __forceinline__ void adj_record(TrajState &S, const CgNext &n, int wr) {
+// limit = the sweeps this solve may take (lin_limit), maxit = the engine's: a solve that ends on a limit below maxit above
+// its tolerance ended on the trajectory's own cap (lin_capped; counted by the next k_fin_lin_begin)
+__device__ __forceinline__ void adj_record(TrajState &S, const CgNext &n, int wr, double tol, int limit, int maxit) {
     S.cg_alpha = n.alpha;
     S.cg_beta = n.beta;
     S.cg_gamma = n.gamma;
@@ -1141,6 +1143,7 @@ __device__ __forceinline__ void adj_record(TrajState &S, const CgNext &n, int wr
         S.lin_total++;
     }
     if (!n.active && n.rel > S.lin_maxrel) S.lin_maxrel = n.rel;
+    S.lin_capped = (!n.active && !n.breakdown && n.rel > tol && limit < maxit && n.it >= limit) ? 1 : 0;
     S.ci_active[wr] = n.active;
     S.ci_it[wr] = n.it;
     S.ci_gamma[wr] = n.gamma;
@@ -1178,9 +1181,11 @@ __global__ void k_fin_adj_step(TrajState *st, const double *__restrict__ gpart, 
     }
     adj_sums4<192>(gpart, gpart2, direct ? gpart3_rd : nullptr, gnblk, b, s4);
     if (threadIdx.x != 0) return;
+    const double tol = S.lin_reltol;
+    const int limit = lin_limit(S, maxit);
     const CgNext n = cg_next_adj(s4[0], s4[1], direct ? s4[2] : S.ci_gamma[rd], direct ? s4[3] : S.aux[0], S.lin_r0,
-                                 S.ci_it[rd], S.lin_reltol, maxit);
-    adj_record(S, n, rd ^ 1);
+                                 S.ci_it[rd], tol, limit);
+    adj_record(S, n, rd ^ 1, tol, limit, maxit);
     if (n.it > S.step_lin_max) S.step_lin_max = n.it;
     S.cg_pending = n.breakdown ? 0 : 1;
     S.cg_pbuf = pbuf;
@@ -1253,11 +1258,12 @@ __global__ __launch_bounds__((FftThreads<C, LOGL>::T)) void k_adj_rows_fwd(Geom 
         }
         const double gamma_old = st[b].ci_gamma[rd], tol = st[b].lin_reltol, r0sq = st[b].aux[0], rhsn = st[b].lin_r0;
         const int it_old = st[b].ci_it[rd], n = gridDim.x;
+        const int limit = lin_limit(st[b], a.maxit);      // read with the other fields of the record, in front of the sums
         adj_sums4<T>(a.gpart, a.gpart2, a.it >= 2 ? a.gpart3 + (long)rd * a.nbatch * n * 2 : nullptr, n, b, s4);
         const CgNext nx = cg_next_adj(s4[0], s4[1], a.it >= 2 ? s4[2] : gamma_old, a.it >= 2 ? s4[3] : r0sq, rhsn, it_old, tol,
-                                      a.maxit);
+                                      limit);
         if (blockIdx.x == 0 && tid == 0) {
-            adj_record(st[b], nx, wr);
+            adj_record(st[b], nx, wr, tol, limit, a.maxit);
             if (nx.it > st[b].step_lin_max) st[b].step_lin_max = nx.it;
         }
         alpha = nx.alpha;

@@ -66,7 +66,8 @@ struct TrajState {
     int step_form[4];          // use_cheb of the step's first four solves (host: which launch sequences the next step needs)
     // CG form on a diagonal that spans a wide range (a few nodes near |phi| = 1 among ordinary ones): the solve runs on the
     // right-scaled system  P^-1 A S y = P^-1 rhs,  x = S y,  S = dbar / D  (see cg_scaled below)
-    int scaled, scaled_pad;
+    int scaled;
+    int lin_capped;            // adjoint sweep: this solve ended on the trajectory's own sweep cap (lin_cap) above its tolerance
     double step_R[4];          // residual norms of the step's first four iterates (R_0 .. R_3), for the host's statistics
     // ||R_1|| (the residual after the first Newton iteration) of the last three time steps, newest first; 0 = not known yet.
     // It is the quadratic remainder of the first iteration, three to four orders above the Newton tolerance in the bench
@@ -74,7 +75,11 @@ struct TrajState {
     // profiles/r03_first_solve_slack.txt): the first solve of the next step need not be more accurate than a small fraction of it
     double R1_hist[3];
     int lin_took, lin_unconv;  // adjoint: this solve started (its y is valid); solves the enqueued sweeps did not finish
-    int cg_pending, cg_pbuf, cg_pad;   // forward CG: step (alpha, p[cg_pbuf]) computed but not yet added to x
+    int cg_pending, cg_pbuf;   // forward CG: step (alpha, p[cg_pbuf]) computed but not yet added to x
+    // adjoint sweep: the sweeps a solve of this trajectory may take, from its own record at the host's last look
+    // (backward_pass, k_adj_caps); 0 = no cap.  The host enqueues the largest cap of the batch, so what a trajectory's
+    // solve gets does not depend on its batch mates
+    int lin_cap;
     // forward CG, per-iteration state in two copies: iteration k's stencil kernel derives the step of
     // iteration k-1 itself (every workgroup, redundantly), reading copy (k-1)&1 while one workgroup
     // writes copy k&1 -- no workgroup ever reads a field that another one writes in the same launch
@@ -95,6 +100,11 @@ __device__ __forceinline__ bool gate_open(const TrajState &S, int gate) {
     if (gate == 5) return S.lin_active != 0 && S.use_cheb == 0;
     if (gate == 8) return S.lin_active != 0 && S.use_cheb != 0;
     return gate == 1 ? S.lin_active != 0 : (gate == 4 ? S.lin_took != 0 : S.ci_active[gate - 2] != 0);
+}
+
+// sweeps a solve may take: the engine's limit, or below it the trajectory's own cap (adjoint sweep)
+__device__ __forceinline__ int lin_limit(const TrajState &S, int maxit) {
+    return S.lin_cap > 0 && S.lin_cap < maxit ? S.lin_cap : maxit;
 }
 
 struct Phys {
@@ -2522,12 +2532,14 @@ __global__ void k_fin_cg_beta(TrajState *st, const double *__restrict__ part, in
         S.cg_gamma = gn;
         S.lin_it++;
         S.lin_total++;
+        if (S.lin_it > S.step_lin_max) S.step_lin_max = S.lin_it;      // the host's schedule (backward_pass)
     }
     S.lin_rel = mode == 1 ? (S.lin_r0 > 0.0 ? sqrt(rr) / S.lin_r0 : 0.0)
                           : (S.cg_gamma0 > 0.0 ? sqrt(gn / S.cg_gamma0) : 0.0);
-    if (!(S.lin_rel > tol) || S.lin_it >= maxit) {
+    if (!(S.lin_rel > tol) || S.lin_it >= lin_limit(S, maxit)) {
         S.lin_active = 0;
         if (S.lin_rel > S.lin_maxrel) S.lin_maxrel = S.lin_rel;
+        if (S.lin_rel > tol && S.lin_cap > 0 && S.lin_it >= S.lin_cap) S.lin_capped = 1;
     }
 }
 
@@ -2600,7 +2612,7 @@ __global__ void k_fin_lin_begin(TrajState *st, const double *__restrict__ part, 
                                 double tau, double kappa, double dt, double lin_tol, double scale_ratio) {
     const int b = blockIdx.x;
     TrajState &S = st[b];
-    if (threadIdx.x == 0 && S.lin_active) {      // the previous solve of this trajectory ended on its sweep budget
+    if (threadIdx.x == 0 && (S.lin_active || S.lin_capped)) {      // the previous solve of this trajectory ended on its sweep budget
         S.lin_unconv++;
         if (S.lin_rel > S.lin_maxrel) S.lin_maxrel = S.lin_rel;
     }
@@ -2622,6 +2634,7 @@ __global__ void k_fin_lin_begin(TrajState *st, const double *__restrict__ part, 
     else cg_setup(S, tau + 2.0 * sqrt(0.5 * dt), 0.5 * dt, lin_tol);
     S.lin_r0 = r0;
     S.lin_active = (mode == 2 || r0 > 0.0) ? 1 : 0;
+    S.lin_capped = 0;
     S.lin_it = 0;
     S.lin_prev = 1e300;
     S.lin_rel = 1.0;
@@ -2765,6 +2778,19 @@ __global__ __launch_bounds__(NTH) void k_adj_guess_plain(Geom G, double *__restr
 __global__ void k_reset_longest(TrajState *st, int B) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b < B) st[b].step_lin_max = 0;
+}
+
+// The sweep caps of the adjoint launch schedule, written at the host's look (batches of at most GUESS_BMAX): the solves of
+// trajectory b stop after cap[b] sweeps (0 = no cap), whatever the host enqueues for its batch mates.  reset: the longest
+// solve counts from this look on.  One workgroup per trajectory: the table is indexed by a wave-uniform value.
+struct AdjCaps {
+    int cap[GUESS_BMAX];
+};
+__global__ void k_adj_caps(TrajState *st, AdjCaps caps, int reset) {
+    const int b = blockIdx.x;
+    if (threadIdx.x != 0) return;
+    st[b].lin_cap = b < GUESS_BMAX ? caps.cap[b] : 0;
+    if (reset) st[b].step_lin_max = 0;
 }
 
 // zero-fill / constant fill of valid nodes
