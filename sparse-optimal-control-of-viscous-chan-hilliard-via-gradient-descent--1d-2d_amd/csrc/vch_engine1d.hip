@@ -347,6 +347,18 @@ extern "C" int vch1d_backward(vch1d_ctx *c, const double *phi_hist, int rows, co
     return 0;
 }
 
+// np.trapezoid weights of the n abscissae t: of the caller's grid (C1:57), or of t_hist over all rows (C1:55-73), where the
+// duplicated t = 0 row gets 0
+static std::vector<double> trapz_w1(const double *t, int n) {
+    std::vector<double> w(n, 0.0);
+    for (int i = 0; i + 1 < n; ++i) {
+        const double d = t[i + 1] - t[i];
+        w[i] += 0.5 * d;
+        w[i + 1] += 0.5 * d;
+    }
+    return w;
+}
+
 extern "C" int vch1d_cost(vch1d_ctx *c, const double *phi_hist, const double *u, const double *phi_Q, const double *phi_T,
                           int rows, const double *x, const double *t_hist, const vch_opt_params *o, double *J_out) {
     CTXCHK(c);
@@ -357,12 +369,7 @@ extern "C" int vch1d_cost(vch1d_ctx *c, const double *phi_hist, const double *u,
     if (u) { VCHCHK(ensure1(c, &c->u_hist)); VCHCHK(up_hist(c, c->u_hist, u, rows)); }
     if (phi_Q) { VCHCHK(ensure1(c, &c->phiQ)); VCHCHK(up_hist(c, c->phiQ, phi_Q, rows)); }
     if (phi_T) VCHCHK(up(c, c->phiT, phi_T, (size_t)c->B * c->n));
-    std::vector<double> wx(c->n, 0.0);         // np.trapezoid weights from the caller's grid (C1:57)
-    for (int i = 0; i + 1 < c->n; ++i) {
-        const double d = x[i + 1] - x[i];
-        wx[i] += 0.5 * d;
-        wx[i + 1] += 0.5 * d;
-    }
+    const std::vector<double> wx = trapz_w1(x, c->n);
     VCHCHK(up(c, c->wx, wx.data(), c->n));
     LAUNCH(k1d_cost, dim3(rows, c->B), dim3(T1), c->n, rows, (const double *)c->wx, (const double *)c->phi_hist,
             (const double *)(u ? c->u_hist : nullptr), (const double *)(phi_Q ? c->phiQ : nullptr),
@@ -430,15 +437,6 @@ extern "C" int vch1d_free_energy(vch1d_ctx *c, const double *phi_hist, int rows,
 // ------------------------------------------------------------------------------------
 // device-resident PGD loop (G1:333-477): control, state history, adjoint and targets stay in HBM
 // ------------------------------------------------------------------------------------
-static void trapz_x(const vch1d_ctx *c, const double *x, std::vector<double> &wx) {
-    wx.assign(c->n, 0.0);                      // np.trapezoid weights from the caller's grid (C1:57)
-    for (int i = 0; i + 1 < c->n; ++i) {
-        const double d = x[i + 1] - x[i];
-        wx[i] += 0.5 * d;
-        wx[i + 1] += 0.5 * d;
-    }
-}
-
 // J[b][5] of (phi, u) on the device; wx already uploaded
 static int cost1_core(vch1d_ctx *c, const double *phi_dev, const double *u_dev, int rows, double *J_out,
                       double *raw_out = nullptr /* [B][2] = {int int (phi - phi_Q)^2, int (phi_end - phi_T)^2} */) {
@@ -564,8 +562,7 @@ extern "C" int vch1d_pgd_init_v(vch1d_ctx *c, const double *phi0, const double *
     VCHCHK(up(c, c->phiT, phi_T, (size_t)B * c->n));
     VCHCHK(up(c, c->dts, dt, M));
     VCHCHK(up(c, c->tgrid, t_hist, rows));
-    std::vector<double> wx;
-    trapz_x(c, x, wx);
+    const std::vector<double> wx = trapz_w1(x, c->n);
     VCHCHK(up(c, c->wx, wx.data(), c->n));
     HIPCHK(hipStreamSynchronize(c->stream));          // wx is a local
     // u = 0 and the uncontrolled march (G1:341), or the caller's u0 as given (not clipped) and the march under it
@@ -830,6 +827,25 @@ static int so1_grids(vch1d_ctx *c, const std::vector<double> &dts, const double 
     VCHCHK(up(c, c->so_wx, wx.data(), c->n));
     return up(c, c->so_wts, wts.data(), wts.size());
 }
+// the base point of a call in the arguments of its kernel (Tan1Args, Hv1Args)
+template <class A>
+static void so1_args(const vch1d_ctx *c, const So1Base &S, A &G) {
+    G.hs = hs1(c);
+    G.phi = S.phi; G.u = S.u; G.pq = S.pq; G.pt = S.pt;
+    G.phi_s = G.u_s = G.pq_s = S.bs;
+    G.pt_s = S.pts;
+}
+// the stats of a call timed between the context's two events
+static void so1_stats(vch1d_ctx *c, vch_stats *stats, int64_t solves, int64_t launches, int64_t host_syncs) {
+    if (!stats) return;
+    float ms = 0;
+    hipEventElapsedTime(&ms, c->ev0, c->ev1);
+    memset(stats, 0, sizeof(*stats));
+    stats->linear_solves = solves;
+    stats->launches = launches;
+    stats->host_syncs = host_syncs;
+    stats->seconds = ms * 1e-3;
+}
 
 extern "C" int vch1d_second_order(vch1d_ctx *c, const double *phi_hist, const double *u, int n_base, const double *h,
                                   int rows, const double *dt, const double *t_hist, const double *x, const double *phi_Q,
@@ -848,14 +864,11 @@ extern "C" int vch1d_second_order(vch1d_ctx *c, const double *phi_hist, const do
     So1Base S;
     VCHCHK(so1_base(c, phi_hist, u, phi_Q, phi_T, n_base, rows, S));
     Tan1Args G{};
-    G.hs = hs1(c);
-    G.phi = S.phi; G.u = S.u; G.pq = S.pq; G.pt = S.pt;
-    G.phi_s = G.u_s = G.pq_s = S.bs;
-    G.pt_s = S.pts;
+    so1_args(c, S, G);
     VCHCHK(ensure1(c, &c->so_h));
     VCHCHK(up_hist(c, c->so_h, h, rows));
     G.hd = c->so_h;
-    trapz_x(c, x, wx);
+    wx = trapz_w1(x, c->n);
     VCHCHK(so1_grids(c, dts, t_hist, rows, wx, wts));
     G.dts = c->so_dts; G.t = c->so_t; G.wx = c->so_wx; G.wts = c->so_wts; G.out = c->so_out;
     if (dphi_hist_out) { VCHCHK(ensure1(c, &c->so_d1)); G.d1 = c->so_d1; }
@@ -872,14 +885,7 @@ extern "C" int vch1d_second_order(vch1d_ctx *c, const double *phi_hist, const do
         if (order == 2) VCHCHK(down_hist(c, d2phi_hist_out, c->so_d2, rows));
         else memset(d2phi_hist_out, 0, sizeof(double) * B * rows * n);
     }
-    if (stats) {
-        float ms = 0;
-        hipEventElapsedTime(&ms, c->ev0, c->ev1);
-        memset(stats, 0, sizeof(*stats));
-        stats->linear_solves = (int64_t)order * M * B;
-        stats->launches = 1;
-        stats->seconds = ms * 1e-3;
-    }
+    so1_stats(c, stats, (int64_t)order * M * B, 1, 0);
     return 0;
 }
 
@@ -903,24 +909,15 @@ extern "C" int vch1d_hessvec(vch1d_ctx *c, const double *phi_hist, const double 
     So1Base S;
     VCHCHK(so1_base(c, phi_hist, u, phi_Q, phi_T, n_base, rows, S));
     Hv1Args G{};
-    G.hs = hs1(c);
-    G.phi = S.phi; G.u = S.u; G.pq = S.pq; G.pt = S.pt;
-    G.phi_s = G.u_s = G.pq_s = S.bs;
-    G.pt_s = S.pts;
+    so1_args(c, S, G);
     if (h) {
         VCHCHK(ensure1(c, &c->so_h));
         VCHCHK(up_hist(c, c->so_h, h, rows));
         G.hd = c->so_h;
     }
-    trapz_x(c, x, wx);
+    wx = trapz_w1(x, c->n);
     VCHCHK(so1_grids(c, dts, t_hist, rows, wx, wts));
-    // trapezoid weights of t_hist (np.trapezoid over all rows, C1:55-73): the duplicated t = 0 row gets 0
-    std::vector<double> wt(rows, 0.0);
-    for (int r = 0; r + 1 < rows; ++r) {
-        const double d = t_hist[r + 1] - t_hist[r];
-        wt[r] += 0.5 * d;
-        wt[r + 1] += 0.5 * d;
-    }
+    const std::vector<double> wt = trapz_w1(t_hist, rows);
     if (!c->hv_dots) {             // all three or none
         vch_group g(c->pool);
         VCHCHK(dalloc1(c, &c->hv_wt, c->Mmax + 2));
@@ -950,14 +947,7 @@ extern "C" int vch1d_hessvec(vch1d_ctx *c, const double *phi_hist, const double 
         if (order == 2) VCHCHK(down_hist(c, hv_out, c->hv_hv, rows));
         else memset(hv_out, 0, sizeof(double) * B * rows * n);
     }
-    if (stats) {
-        float ms = 0;
-        hipEventElapsedTime(&ms, c->ev0, c->ev1);
-        memset(stats, 0, sizeof(*stats));
-        stats->linear_solves = (int64_t)(order == 1 ? 1 : 3) * M * B;
-        stats->launches = 1;
-        stats->seconds = ms * 1e-3;
-    }
+    so1_stats(c, stats, (int64_t)(order == 1 ? 1 : 3) * M * B, 1, 0);
     return 0;
 }
 
@@ -1009,13 +999,14 @@ static Kr1Args kr1_args(const vch1d_ctx *c, const Kr1Layout &L, int rows, int sl
 
 // The lazy storage of a Krylov call (fn: vch1d_hess_lanczos or vch1d_hess_cg), one group: a refused request gives back what
 // this call got and leaves the context usable.  A request for more than the resident storage holds releases that storage
-// first.  Whatever an earlier call left resident in the basis is no longer valid: the caller overwrites it.
+// first.  kr_valid / ncg_valid, in both engines: what an earlier call left resident stays valid until this call has released
+// it or has all of its storage, so a refused request leaves the context as it was; then the caller overwrites it.
 static int kr1_storage(vch1d_ctx *c, const char *fn, int slots, int k, const double *phi_hist, const double *u, const double *phi_Q,
                        const double *phi_T) {
     const int B = c->B, n = c->n;
     const size_t hist_bytes = (size_t)B * hs1(c) * sizeof(double);
-    c->kr_valid = c->ncg_valid = false;
     if (c->kr_Q && (slots > c->kr_slots || k > c->kr_kcap)) {       // a larger basis than the resident storage holds
+        c->kr_valid = c->ncg_valid = false;
         c->pool.drop((void **)&c->kr_sc);
         c->pool.drop((void **)&c->kr_mask);
         c->pool.drop((void **)&c->kr_W);
@@ -1047,6 +1038,83 @@ static int kr1_storage(vch1d_ctx *c, const char *fn, int slots, int k, const dou
         c->kr_kcap = k;
     }
     g.keep();
+    c->kr_valid = c->ncg_valid = false;
+    return 0;
+}
+
+// The trapezoid weights wt of t_hist as in vch1d_hessvec and the preconditioner's wt', which gives row 0 (weight zero, but a
+// real unknown) the weight of row 1, which duplicates its time; with precond every wt' must be positive and finite.
+static int ncg1_weights(const char *fn, const double *t_hist, int rows, int precond, std::vector<double> &wt, std::vector<double> &wtp) {
+    wt = trapz_w1(t_hist, rows);
+    wtp = wt;
+    wtp[0] = wt[1];
+    if (precond)
+        for (int r = 0; r < rows; ++r)
+            if (!(wtp[r] > 0.0) || !std::isfinite(wtp[r]))
+                return vch_fail(VCH_ERR_ARG, "%s: row %d: the preconditioner's time weight %g must be positive and finite (t_hist "
+                                "must increase from row 1 on)", fn, r, wtp[r]);
+    return 0;
+}
+
+// What vch1d_hess_lanczos and vch1d_hess_cg have in common once kr1_open is through.
+struct Kr1Call {
+    std::vector<double> dts, wts, wx, wt, wtp, box, ks;    // host vectors: they live until the first look
+    Kr1Layout L;
+    long mask_s;
+    So1Base Sb;
+    Hv1Args G;                          // all but hd
+};
+// After so1_check_shape and the entry's own checks: the rest of the checks (precond: of the preconditioner's weights), then
+// everything ahead of the set-up kernel and the start of the timed span.  cg: the tables of vch1d_hess_cg (wt', kappa_sparsity)
+// go up as well.  v0 (or NULL): the start vector or right-hand side, into slot v0_slot of the basis.
+static int kr1_open(vch1d_ctx *c, const char *fn, Kr1Call &C, int slots, int k, bool cg, int precond, const double *phi_hist,
+                    const double *u, int n_base, int rows, const double *dt, const double *t_hist, const double *x, const double *phi_Q,
+                    const double *phi_T, const vch_opt_params *opts, int n_opts, const uint8_t *mask, const double *v0, int v0_slot) {
+    if (!mask && !u) return vch_fail(VCH_ERR_ARG, "%s: NULL mask with a NULL (zero) control: no node is free", fn);
+    VCHCHK(so1_check_rest(c, fn, phi_hist, u, rows, dt, t_hist, x, phi_Q, phi_T, opts, n_opts, C.dts, C.wts));
+    VCHCHK(ncg1_weights(fn, t_hist, rows, precond, C.wt, C.wtp));
+    // ---- nothing was launched, copied or allocated up to here
+    const int B = c->B, n = c->n;
+    const long hs = hs1(c);
+    VCHCHK(kr1_storage(c, fn, slots, k, phi_hist, u, phi_Q, phi_T));
+    const Kr1Layout &L = C.L = kr1_layout(c, c->kr_slots, c->kr_kcap);
+    C.mask_s = (!mask || n_base == B) ? hs : 0;
+    double *sc = c->kr_sc;
+    VCHCHK(so1_base(c, phi_hist, u, phi_Q, phi_T, n_base, rows, C.Sb));
+    C.wx = trapz_w1(x, c->n);
+    VCHCHK(so1_grids(c, C.dts, t_hist, rows, C.wx, C.wts));
+    C.box.resize(2 * (size_t)B); C.ks.resize(B);
+    for (int b = 0; b < B; ++b) {
+        const vch_opt_params &o = vch_pgd_opt(opts, n_opts, b);
+        C.box[2 * b] = o.u_min;
+        C.box[2 * b + 1] = o.u_max;
+        C.ks[b] = o.kappa_sparsity;
+    }
+    VCHCHK(up(c, sc + L.wt, C.wt.data(), rows));
+    if (cg) VCHCHK(up(c, sc + L.wtp, C.wtp.data(), rows));
+    VCHCHK(up(c, sc + L.box, C.box.data(), C.box.size()));
+    if (cg) VCHCHK(up(c, sc + L.ks, C.ks.data(), C.ks.size()));
+    if (v0) VCHCHK(up_hist(c, c->kr_Q + (long)v0_slot * B * hs, v0, rows));
+    if (mask)
+        for (int b = 0; b < n_base; ++b)
+            HIPCHK(hipMemcpyAsync(c->kr_mask + (size_t)b * hs, mask + (size_t)b * rows * n, (size_t)rows * n, hipMemcpyHostToDevice,
+                                  c->stream));
+    HIPCHK(hipMemsetAsync(sc + L.alpha, 0xff, sizeof(double) * 2 * B * c->kr_kcap, c->stream));    // NaN: alpha, beta (resid, curv)
+    Hv1Args &G = C.G = Hv1Args{};
+    so1_args(c, C.Sb, G);
+    G.dts = c->so_dts; G.wt = sc + L.wt; G.wx = c->so_wx; G.wts = c->so_wts;
+    G.hv = c->kr_W; G.v = c->kr_V; G.mean = sc + L.mean;
+    HIPCHK(hipEventRecord(c->ev0, c->stream));
+    return 0;
+}
+// One product w = H hd into kr_W: the step kernel with or without the cached sweep; a stopped trajectory returns at once.
+static int kr1_step(vch1d_ctx *c, int rows, const Hv1Args &G, const long long *stop) {
+    if (c->kr_nocache)
+        LAUNCH_LDS(-1, (k1d_kr_step<1>), dim3(c->B), dim3(T1), c->lds_bytes, c->P, c->n, c->h, c->lvl, rows, G, stop, (const double *)c->kr_X,
+                   c->scratch);
+    else
+        LAUNCH_LDS(-1, (k1d_kr_step<0>), dim3(c->B), dim3(T1), c->lds_bytes, c->P, c->n, c->h, c->lvl, rows, G, stop, (const double *)c->kr_X,
+                   c->scratch);
     return 0;
 }
 
@@ -1064,55 +1132,17 @@ extern "C" int vch1d_hess_lanczos(vch1d_ctx *c, const double *phi_hist, const do
         return vch_fail(VCH_ERR_ARG, "%s: NULL alpha_out, beta_out, steps_out or n_free_out", fn);
     if (k < 1) return vch_fail(VCH_ERR_ARG, "%s: k = %d must be >= 1", fn, k);
     if (reorth != 0 && reorth != 1) return vch_fail(VCH_ERR_ARG, "%s: reorth = %d is neither 0 nor 1", fn, reorth);
-    if (!mask && !u) return vch_fail(VCH_ERR_ARG, "%s: NULL mask with a NULL (zero) control: no node is free", fn);
-    std::vector<double> dts, wts, wx;
-    VCHCHK(so1_check_rest(c, fn, phi_hist, u, rows, dt, t_hist, x, phi_Q, phi_T, opts, n_opts, dts, wts));
-    // ---- nothing was launched, copied or allocated up to here
     const int M = rows - 2, slots = reorth ? k + 1 : 3;
-    const long hs = hs1(c);
-    VCHCHK(kr1_storage(c, fn, slots, k, phi_hist, u, phi_Q, phi_T));
-    const Kr1Layout L = kr1_layout(c, c->kr_slots, c->kr_kcap);
-    const bool build = mask == nullptr;
-    const Kr1Args K = kr1_args(c, L, rows, slots, (build || n_base == B) ? hs : 0);
-    double *part = c->kr_sc + L.part;
+    Kr1Call C;
+    VCHCHK(kr1_open(c, fn, C, slots, k, false, 0, phi_hist, u, n_base, rows, dt, t_hist, x, phi_Q, phi_T, opts, n_opts, mask, q0, 0));
+    const Kr1Args K = kr1_args(c, C.L, rows, slots, C.mask_s);
+    double *part = c->kr_sc + C.L.part;
     const int S = c->kr_slots, nch = kr1_chunks(c, rows);
     const dim3 kgrid(nch, B);
-    auto slot_of = [&](int i) { return c->kr_Q + (long)(i % slots) * B * hs; };
-    So1Base Sb;
-    VCHCHK(so1_base(c, phi_hist, u, phi_Q, phi_T, n_base, rows, Sb));
-    trapz_x(c, x, wx);
-    VCHCHK(so1_grids(c, dts, t_hist, rows, wx, wts));
-    // trapezoid weights of t_hist as in vch1d_hessvec, and every trajectory's box
-    std::vector<double> wt(rows, 0.0), box(2 * (size_t)B);
-    for (int r = 0; r + 1 < rows; ++r) {
-        const double d = t_hist[r + 1] - t_hist[r];
-        wt[r] += 0.5 * d;
-        wt[r + 1] += 0.5 * d;
-    }
-    for (int b = 0; b < B; ++b) {
-        const vch_opt_params &o = vch_pgd_opt(opts, n_opts, b);
-        box[2 * b] = o.u_min;
-        box[2 * b + 1] = o.u_max;
-    }
-    VCHCHK(up(c, c->kr_sc + L.wt, wt.data(), rows));
-    VCHCHK(up(c, c->kr_sc + L.box, box.data(), box.size()));
-    VCHCHK(up_hist(c, slot_of(0), q0, rows));
-    if (mask)
-        for (int b = 0; b < n_base; ++b)
-            HIPCHK(hipMemcpyAsync(c->kr_mask + (size_t)b * hs, mask + (size_t)b * rows * n, (size_t)rows * n, hipMemcpyHostToDevice,
-                                  c->stream));
-    HIPCHK(hipMemsetAsync(K.x.alpha, 0xff, sizeof(double) * 2 * B * c->kr_kcap, c->stream));      // NaN: alpha, then beta
-    Hv1Args G{};
-    G.hs = hs;
-    G.phi = Sb.phi; G.u = Sb.u; G.pq = Sb.pq; G.pt = Sb.pt;
-    G.phi_s = G.u_s = G.pq_s = Sb.bs;
-    G.pt_s = Sb.pts;
-    G.dts = c->so_dts; G.wt = c->kr_sc + L.wt; G.wx = c->so_wx; G.wts = c->so_wts;
-    G.hv = c->kr_W; G.v = c->kr_V; G.mean = c->kr_sc + L.mean;
-    HIPCHK(hipEventRecord(c->ev0, c->stream));
+    auto slot_of = [&](int i) { return c->kr_Q + (long)(i % slots) * B * hs1(c); };
     // the set-up: the free set, q_0 and (once per base point) the gradient sweep, whose yp of every step stays in kr_X
-    LAUNCH_LDS(-1, k1d_kr_setup, dim3(B), dim3(T1), c->lds_bytes, c->P, n, c->h, c->lvl, rows, G, K, (const double *)(c->kr_sc + L.box),
-               tol > 0 ? tol : 1e-8, build ? 1 : 0, k, c->kr_nocache ? 0 : 1, c->kr_X, c->scratch);
+    LAUNCH_LDS(-1, k1d_kr_setup, dim3(B), dim3(T1), c->lds_bytes, c->P, n, c->h, c->lvl, rows, C.G, K, (const double *)(c->kr_sc + C.L.box),
+               tol > 0 ? tol : 1e-8, mask ? 0 : 1, k, c->kr_nocache ? 0 : 1, c->kr_X, c->scratch);
     std::vector<double> look(2 * (size_t)B);
     VCHCHK(down(c, look.data(), K.x.look, look.size()));            // the first look; the host vectors above are done with
     for (int b = 0; b < B; ++b) {
@@ -1122,13 +1152,8 @@ extern "C" int vch1d_hess_lanczos(vch1d_ctx *c, const double *phi_hist, const do
     }
     // k steps back to back: a stopped trajectory's kernels return at once, the host does not look
     for (int j = 0; j < k; ++j) {
-        G.hd = slot_of(j);
-        if (c->kr_nocache)
-            LAUNCH_LDS(-1, (k1d_kr_step<1>), dim3(B), dim3(T1), c->lds_bytes, c->P, n, c->h, c->lvl, rows, G, (const long long *)K.x.stop,
-                       (const double *)c->kr_X, c->scratch);
-        else
-            LAUNCH_LDS(-1, (k1d_kr_step<0>), dim3(B), dim3(T1), c->lds_bytes, c->P, n, c->h, c->lvl, rows, G, (const long long *)K.x.stop,
-                       (const double *)c->kr_X, c->scratch);
+        C.G.hd = slot_of(j);
+        VCHCHK(kr1_step(c, rows, C.G, K.x.stop));
         // w = H q_j in kr_W; classical Gram-Schmidt twice against q_first .. q_j, the passes reading w through the mask
         const int first = reorth ? 0 : std::max(j - 1, 0), nv = j + 1 - first;
         LAUNCH((k1d_kr_pass<0>), kgrid, dim3(KR1_T), K, first, nv, c->kr_W, (const double *)nullptr, part);
@@ -1154,15 +1179,7 @@ extern "C" int vch1d_hess_lanczos(vch1d_ctx *c, const double *phi_hist, const do
         smax = std::max(smax, (int)steps[b]);
         solves += c->kr_nocache ? 3 * (int64_t)M * steps[b] : (int64_t)M * (2 * steps[b] + 1);
     }
-    if (stats) {
-        float ms = 0;
-        hipEventElapsedTime(&ms, c->ev0, c->ev1);
-        memset(stats, 0, sizeof(*stats));
-        stats->linear_solves = solves;
-        stats->launches = 1 + 8 * (int64_t)k;
-        stats->host_syncs = 2;
-        stats->seconds = ms * 1e-3;
-    }
+    so1_stats(c, stats, solves, 1 + 8 * (int64_t)k, 2);
     c->kr_valid = true;
     c->kr_rows = rows;
     c->kr_run_slots = slots;
@@ -1196,30 +1213,17 @@ extern "C" int vch1d_krylov_vector(vch1d_ctx *c, const double *coef, int m, doub
 // recurrence on the device (kernels: "Device-resident Newton-CG" in vch_kernels1d.h).  The storage, the
 // step kernel and the look schedule are those of vch1d_hess_lanczos without reorthogonalisation.
 // ------------------------------------------------------------------------------------
-// The trapezoid weights wt of t_hist as in vch1d_hessvec and the preconditioner's wt', which gives row 0 (weight zero, but a
-// real unknown) the weight of row 1, which duplicates its time; with precond every wt' must be positive and finite.
-static int ncg1_weights(const char *fn, const double *t_hist, int rows, int precond, std::vector<double> &wt, std::vector<double> &wtp) {
-    wt.assign(rows, 0.0);
-    for (int r = 0; r + 1 < rows; ++r) {
-        const double d = t_hist[r + 1] - t_hist[r];
-        wt[r] += 0.5 * d;
-        wt[r + 1] += 0.5 * d;
-    }
-    wtp = wt;
-    wtp[0] = wt[1];
-    if (precond)
-        for (int r = 0; r < rows; ++r)
-            if (!(wtp[r] > 0.0) || !std::isfinite(wtp[r]))
-                return vch_fail(VCH_ERR_ARG, "%s: row %d: the preconditioner's time weight %g must be positive and finite (t_hist "
-                                "must increase from row 1 on)", fn, r, wtp[r]);
-    return 0;
-}
 // the cells of the iteration in the block of the Lanczos scalars: resid, curv where alpha, beta live
 static Ncg1Cells ncg1_cells(const vch1d_ctx *c, const Kr1Layout &L) {
     double *sc = c->kr_sc;
     const int B = c->B;
     return Ncg1Cells{sc + L.alpha, sc + L.beta, sc + L.look, sc + L.scal, sc + L.amax, sc + L.coef1, sc + L.coef1 + B,
                      sc + L.coef1 + 2 * B, (long long *)(sc + L.steps), (long long *)(sc + L.lim), (long long *)(sc + L.stop)};
+}
+static Ncg1Args ncg1_args(const vch1d_ctx *c, const Kr1Layout &L, int rows, long mask_s, int precond) {
+    const long hs = hs1(c);
+    return Ncg1Args{c->kr_Q, (long)c->B * hs, hs, (long)rows * c->n, c->n, c->kr_slots, c->kr_mask, mask_s,
+                    c->kr_sc + L.wtp, c->so_wx, precond, ncg1_cells(c, L)};
 }
 
 // The body of vch1d_hess_cg, shared with the rounds of vch1d_pgd_newton.  fn: the entry point the messages name.
@@ -1238,64 +1242,27 @@ static int hess_cg1_core(vch1d_ctx *c, const char *fn, bool empty_ok, const doub
     if (k < 1) return vch_fail(VCH_ERR_ARG, "%s: k = %d must be >= 1", fn, k);
     if (precond != 0 && precond != 1) return vch_fail(VCH_ERR_ARG, "%s: precond = %d is neither 0 nor 1", fn, precond);
     if (!std::isfinite(cg_tol)) return vch_fail(VCH_ERR_ARG, "%s: cg_tol must be finite", fn);
-    if (!mask && !u) return vch_fail(VCH_ERR_ARG, "%s: NULL mask with a NULL (zero) control: no node is free", fn);
-    std::vector<double> dts, wts, wx;
-    VCHCHK(so1_check_rest(c, fn, phi_hist, u, rows, dt, t_hist, x, phi_Q, phi_T, opts, n_opts, dts, wts));
-    std::vector<double> wt, wtp;
-    VCHCHK(ncg1_weights(fn, t_hist, rows, precond, wt, wtp));
-    // ---- nothing was launched, copied or allocated up to here
     const int M = rows - 2;
     const long hs = hs1(c);
-    VCHCHK(kr1_storage(c, fn, 3, k, phi_hist, u, phi_Q, phi_T));
-    const Kr1Layout L = kr1_layout(c, c->kr_slots, c->kr_kcap);
-    const bool build = mask == nullptr;
-    double *sc = c->kr_sc;
-    const Ncg1Cells cells = ncg1_cells(c, L);
+    Kr1Call C;
+    VCHCHK(kr1_open(c, fn, C, 3, k, true, precond, phi_hist, u, n_base, rows, dt, t_hist, x, phi_Q, phi_T, opts, n_opts, mask, rhs, NCG1_R));
+    const Kr1Layout &L = C.L;
+    double *sc = c->kr_sc, *part = sc + L.part;
+    const Ncg1Args K = ncg1_args(c, L, rows, C.mask_s, precond);
+    const Ncg1Cells &cells = K.x;
     const int S = c->kr_slots, nch = kr1_chunks(c, rows);
-    const Ncg1Args K{c->kr_Q, (long)B * hs, hs, (long)rows * n, n, S, c->kr_mask, (build || n_base == B) ? hs : 0,
-                     sc + L.wtp, c->so_wx, precond, cells};
-    double *part = sc + L.part;
     const dim3 kgrid(nch, B);
-    double *r_slot = c->kr_Q + (long)NCG1_R * B * hs, *p_slot = c->kr_Q + (long)NCG1_P * B * hs;
     const double stop_at = cg_tol > 0 ? cg_tol : 1e-8;
-    So1Base Sb;
-    VCHCHK(so1_base(c, phi_hist, u, phi_Q, phi_T, n_base, rows, Sb));
-    trapz_x(c, x, wx);
-    VCHCHK(so1_grids(c, dts, t_hist, rows, wx, wts));
-    std::vector<double> box(2 * (size_t)B), ks(B);
-    for (int b = 0; b < B; ++b) {
-        const vch_opt_params &o = vch_pgd_opt(opts, n_opts, b);
-        box[2 * b] = o.u_min;
-        box[2 * b + 1] = o.u_max;
-        ks[b] = o.kappa_sparsity;
-    }
-    VCHCHK(up(c, sc + L.wt, wt.data(), rows));
-    VCHCHK(up(c, sc + L.wtp, wtp.data(), rows));
-    VCHCHK(up(c, sc + L.box, box.data(), box.size()));
-    VCHCHK(up(c, sc + L.ks, ks.data(), ks.size()));
-    if (rhs) VCHCHK(up_hist(c, r_slot, rhs, rows));
-    if (mask)
-        for (int b = 0; b < n_base; ++b)
-            HIPCHK(hipMemcpyAsync(c->kr_mask + (size_t)b * hs, mask + (size_t)b * rows * n, (size_t)rows * n, hipMemcpyHostToDevice,
-                                  c->stream));
-    HIPCHK(hipMemsetAsync(cells.resid, 0xff, sizeof(double) * 2 * B * c->kr_kcap, c->stream));     // NaN: resid, then curv
-    Hv1Args G{};
-    G.hs = hs;
-    G.phi = Sb.phi; G.u = Sb.u; G.pq = Sb.pq; G.pt = Sb.pt;
-    G.phi_s = G.u_s = G.pq_s = Sb.bs;
-    G.pt_s = Sb.pts;
-    G.dts = c->so_dts; G.wt = sc + L.wt; G.wx = c->so_wx; G.wts = c->so_wts;
-    G.hd = p_slot; G.hv = c->kr_W; G.v = c->kr_V; G.mean = sc + L.mean;
-    HIPCHK(hipEventRecord(c->ev0, c->stream));
+    C.G.hd = c->kr_Q + (long)NCG1_P * B * hs;
     // the set-up: the free set, the gradient sweep once per base point (yp of every step stays in kr_X), r = P b, x, p
     double *keepX = c->kr_nocache ? nullptr : c->kr_X;
     if (rhs)
-        LAUNCH_LDS(-1, (k1d_ncg_setup<0>), dim3(B), dim3(T1), c->lds_bytes, c->P, n, c->h, c->lvl, rows, G, K,
-                   (const double *)(sc + L.box), (const double *)(sc + L.ks), tol > 0 ? tol : 1e-8, build ? 1 : 0,
+        LAUNCH_LDS(-1, (k1d_ncg_setup<0>), dim3(B), dim3(T1), c->lds_bytes, c->P, n, c->h, c->lvl, rows, C.G, K,
+                   (const double *)(sc + L.box), (const double *)(sc + L.ks), tol > 0 ? tol : 1e-8, mask ? 0 : 1,
                    c->kr_nocache ? 0 : 1, keepX, c->scratch);
     else
-        LAUNCH_LDS(-1, (k1d_ncg_setup<1>), dim3(B), dim3(T1), c->lds_bytes, c->P, n, c->h, c->lvl, rows, G, K,
-                   (const double *)(sc + L.box), (const double *)(sc + L.ks), tol > 0 ? tol : 1e-8, build ? 1 : 0, 1, keepX,
+        LAUNCH_LDS(-1, (k1d_ncg_setup<1>), dim3(B), dim3(T1), c->lds_bytes, c->P, n, c->h, c->lvl, rows, C.G, K,
+                   (const double *)(sc + L.box), (const double *)(sc + L.ks), tol > 0 ? tol : 1e-8, mask ? 0 : 1, 1, keepX,
                    c->scratch);
     std::vector<double> look(2 * (size_t)B);
     VCHCHK(down(c, look.data(), cells.look, look.size()));          // the first look; the host vectors above are done with
@@ -1311,12 +1278,7 @@ static int hess_cg1_core(vch1d_ctx *c, const char *fn, bool empty_ok, const doub
                 HIPCHK(hipMemsetAsync(c->kr_Q + (long)slot * B * hs + b * hs, 0, sizeof(double) * rows * n, c->stream));
     // k steps back to back: a stopped trajectory's kernels return at once, the host does not look
     for (int j = 0; j < k; ++j) {
-        if (c->kr_nocache)
-            LAUNCH_LDS(-1, (k1d_kr_step<1>), dim3(B), dim3(T1), c->lds_bytes, c->P, n, c->h, c->lvl, rows, G, (const long long *)cells.stop,
-                       (const double *)c->kr_X, c->scratch);
-        else
-            LAUNCH_LDS(-1, (k1d_kr_step<0>), dim3(B), dim3(T1), c->lds_bytes, c->P, n, c->h, c->lvl, rows, G, (const long long *)cells.stop,
-                       (const double *)c->kr_X, c->scratch);
+        VCHCHK(kr1_step(c, rows, C.G, cells.stop));
         // w = H p in kr_W
         LAUNCH(k1d_ncg_curv, kgrid, dim3(KR1_T), K, (const double *)c->kr_W, part);
         LAUNCH(k1d_ncg_fin, dim3(B), dim3(KR1_T), cells, (const double *)part, nch, S, 2, j, k, stop_at);
@@ -1349,19 +1311,11 @@ static int hess_cg1_core(vch1d_ctx *c, const char *fn, bool empty_ok, const doub
         // the set-up's sweep: always with the cache; with the switch only where the right-hand side is built from it
         solves += c->kr_nocache ? 3 * (int64_t)M * prods[b] + (rhs ? 0 : M) : (int64_t)M * (2 * prods[b] + 1);
     }
-    if (stats) {
-        float ms = 0;
-        hipEventElapsedTime(&ms, c->ev0, c->ev1);
-        memset(stats, 0, sizeof(*stats));
-        stats->linear_solves = solves;
-        stats->launches = 6 * (int64_t)k;           // the set-up, five per step, the direction between two steps
-        stats->host_syncs = 2;
-        stats->seconds = ms * 1e-3;
-    }
+    so1_stats(c, stats, solves, 6 * (int64_t)k, 2);       // the set-up, five per step, the direction between two steps
     c->ncg_valid = true;
     c->ncg_rows = rows;
-    c->ncg_u = Sb.u;
-    c->ncg_us = Sb.bs;
+    c->ncg_u = C.Sb.u;
+    c->ncg_us = C.Sb.bs;
     c->ncg_mask_s = K.mask_s;
     c->ncg_u_live = true;
     return 0;
@@ -1396,11 +1350,9 @@ extern "C" int vch1d_cg_vector(vch1d_ctx *c, int which, double *out) {
 // {sum (t - u)^2, sum u^2, pinned, clipped} after one look (the cells of a skipped trajectory are not written).
 static int newton_trial1_core(vch1d_ctx *c, const double *s_host, const int *skip, double *sums_out) {
     const int B = c->B, rows = c->ncg_rows, nch = kr1_chunks(c, rows);
-    const long hs = hs1(c);
     const Kr1Layout L = kr1_layout(c, c->kr_slots, c->kr_kcap);
     double *sc = c->kr_sc;
-    const Ncg1Args K{c->kr_Q, (long)B * hs, hs, (long)rows * c->n, c->n, c->kr_slots, c->kr_mask, c->ncg_mask_s,
-                     sc + L.wtp, c->so_wx, 0, ncg1_cells(c, L)};
+    const Ncg1Args K = ncg1_args(c, L, rows, c->ncg_mask_s, 0);
     VCHCHK(up(c, sc + L.nts, s_host, B));
     LAUNCH(k1d_nt_trial, dim3(nch, B), dim3(KR1_T), K, c->ncg_u, c->ncg_us, (const double *)(sc + L.nts), (const double *)(sc + L.box),
            skip, c->u_trial, sc + L.ntpart);
@@ -1436,15 +1388,10 @@ extern "C" int vch1d_pgd_newton(vch1d_ctx *c, int n_rounds, int k, double cg_tol
     const char *fn = "vch1d_pgd_newton";
     // everything below is checked before anything is enqueued, copied or allocated
     if (!c->pgd_ready) return vch_fail(VCH_ERR_STATE, "%s: call vch1d_pgd_init first", fn);
-    ARGCHK(n_rounds >= 1, "n_rounds must be >= 1");
-    ARGCHK(k >= 1, "k must be >= 1");
-    ARGCHK(max_halvings >= 0, "max_halvings must be >= 0");
-    ARGCHK(precond == 0 || precond == 1, "precond must be 0 or 1");
-    ARGCHK(std::isfinite(cg_tol), "cg_tol must be finite");
-    ARGCHK(cost_out && cost_new_out && s_out && pred_out && rnorm0_out && halvings_out && cg_steps_out && cg_status_out && status_out &&
-               counts_out,
-           "NULL cost_out, cost_new_out, s_out, pred_out, rnorm0_out, halvings_out, cg_steps_out, cg_status_out, status_out or counts_out");
     const int B = c->B, rows = c->pgd_rows;
+    const vch_newton_call call{B, n_rounds, k, cg_tol, precond, max_halvings, cost_out, cost_new_out, s_out, pred_out, rnorm0_out,
+                               halvings_out, cg_steps_out, cg_status_out, status_out, counts_out};
+    if (const char *bad = vch_newton_check(call)) return vch_fail(VCH_ERR_ARG, "%s: %s", fn, bad);
     {   // what the solve of a round checks, here as well: the stop quirk below marches before the first solve
         std::vector<double> dts, wts, wt, wtp;
         VCHCHK(so1_check_shape(c, fn, B, rows, B, 2));
@@ -1452,46 +1399,40 @@ extern "C" int vch1d_pgd_newton(vch1d_ctx *c, int n_rounds, int k, double cg_tol
                               VCH_RESIDENT, c->opts.data(), B, dts, wts));
         VCHCHK(ncg1_weights(fn, c->t_host.data(), rows, precond, wt, wtp));
     }
-    const double nan = std::nan("");
-    for (size_t i = 0; i < (size_t)B * n_rounds; ++i) {
-        cost_out[i] = cost_new_out[i] = s_out[i] = pred_out[i] = rnorm0_out[i] = nan;
-        halvings_out[i] = cg_steps_out[i] = cg_status_out[i] = 0;
-        status_out[i] = VCH_NEWTON_IDLE;
-        counts_out[3 * i] = counts_out[3 * i + 1] = counts_out[3 * i + 2] = 0;
-    }
-    double sec[4] = {0, 0, 0, 0};
-    auto tick = [&](hipEvent_t e) { return hipEventRecord(e, c->stream); };
-    auto lap = [&]() {
-        float ms = 0;
-        hipEventSynchronize(c->ev1);
-        hipEventElapsedTime(&ms, c->ev0, c->ev1);
-        return (double)ms * 1e-3;
-    };
-    vch_newton_state nt;
-    nt.reset(B);
-    std::vector<double> resid((size_t)B * k), curv((size_t)B * k), pred(B), rn0(B), Jt(5 * (size_t)B), sums(4 * (size_t)B);
-    std::vector<int32_t> steps(B), cgst(B);
-    std::vector<int64_t> nfree(B);
-    std::vector<int> bad(B), sit(B);
-    bool moved = false;
-    int done_rounds = 0;
-    auto run = [&]() -> int {
-        // --- the stop quirk: a trajectory the PGD stop rule ended holds the new control beside the previous iterate's state
-        // and cost (G1:462-465).  One march of the resident control, the others sitting it out, brings both up to the control.
-        bool stale = false;
-        for (int b = 0; b < B; ++b) {
-            sit[b] = !(c->pgd.done[b] && !c->pgd_synced[b]);
-            stale = stale || !sit[b];
+    // the engine's side of the rounds (vch_newton.h); sec = {solves, trial controls, marches, costs}
+    struct Rounds {
+        vch1d_ctx *c;
+        const char *fn;
+        int rows, k, precond;
+        double cg_tol, tol;
+        std::vector<double> resid, curv, Jt;
+        std::vector<int> bad;
+        double sec[4];
+        double lap() {
+            float ms = 0;
+            hipEventSynchronize(c->ev1);
+            hipEventElapsedTime(&ms, c->ev0, c->ev1);
+            return (double)ms * 1e-3;
         }
-        if (stale) {
-            HIPCHK(tick(c->ev0));
+        // The stop quirk: a trajectory the PGD stop rule ended holds the new control beside the previous iterate's state and
+        // cost (G1:462-465).  One march of the resident control, the others sitting it out, brings both up to the control.
+        int stop_quirk() {
+            const int B = c->B;
+            std::vector<int> sit(B);
+            bool stale = false;
+            for (int b = 0; b < B; ++b) {
+                sit[b] = !(c->pgd.done[b] && !c->pgd_synced[b]);
+                stale = stale || !sit[b];
+            }
+            if (!stale) return 0;
+            HIPCHK(hipEventRecord(c->ev0, c->stream));
             HIPCHK(hipMemcpyAsync(c->skip_dev, sit.data(), sizeof(int) * B, hipMemcpyHostToDevice, c->stream));
             VCHCHK(fwd1_core(c, c->u_hist, rows, c->phi_trial, c->skip_dev));
-            HIPCHK(tick(c->ev1));
+            HIPCHK(hipEventRecord(c->ev1, c->stream));
             sec[2] += lap();
-            HIPCHK(tick(c->ev0));
+            HIPCHK(hipEventRecord(c->ev0, c->stream));
             VCHCHK(cost1_core(c, c->phi_trial, c->u_hist, rows, Jt.data()));
-            HIPCHK(tick(c->ev1));
+            HIPCHK(hipEventRecord(c->ev1, c->stream));
             sec[3] += lap();
             for (int b = 0; b < B; ++b) {
                 if (sit[b]) continue;
@@ -1500,70 +1441,51 @@ extern "C" int vch1d_pgd_newton(vch1d_ctx *c, int n_rounds, int k, double cg_tol
                 c->pgd_synced[b] = 1;
             }
             HIPCHK(hipStreamSynchronize(c->stream));
+            return 0;
         }
-        for (int r = 0; r < n_rounds; ++r) {
-            if (!nt.begin_round()) break;
-            // --- the Newton step of every trajectory on its free set; the solves of an idle one are not gated
-            vch_stats cg;
-            VCHCHK(hess_cg1_core(c, fn, true, nullptr, VCH_RESIDENT, B, rows, c->dt_host.data(), c->t_host.data(), c->x_host.data(),
-                                 VCH_RESIDENT, VCH_RESIDENT, c->opts.data(), B, nullptr, tol, nullptr, k, cg_tol, precond, resid.data(),
-                                 curv.data(), pred.data(), rn0.data(), steps.data(), cgst.data(), nfree.data(), &cg));
-            sec[0] += cg.seconds;
-            for (int b = 0; b < B; ++b) {
-                if (nt.idle(b)) continue;
-                const size_t i = (size_t)b * n_rounds + r;
-                cost_out[i] = cost_new_out[i] = c->pgd.cost[b];
-                pred_out[i] = pred[b];
-                rnorm0_out[i] = rn0[b];
-                cg_steps_out[i] = steps[b];
-                cg_status_out[i] = cgst[b];
-                counts_out[3 * i] = nfree[b];
-                status_out[i] = nt.after_solve(b, nfree[b], rn0[b], cgst[b], steps[b]);
-            }
-            // --- trials s = 1, 1/2, ...: a trajectory whose verdict is in sits the trial out
-            while (!nt.all_decided()) {
-                HIPCHK(tick(c->ev0));
-                HIPCHK(hipMemcpyAsync(c->skip_dev, nt.decided.data(), sizeof(int) * B, hipMemcpyHostToDevice, c->stream));
-                VCHCHK(newton_trial1_core(c, nt.s.data(), c->skip_dev, sums.data()));
-                HIPCHK(tick(c->ev1));
-                sec[1] += lap();
-                HIPCHK(tick(c->ev0));
-                VCHCHK(fwd1_core(c, c->u_trial, rows, c->phi_trial, c->skip_dev, bad.data()));
-                HIPCHK(tick(c->ev1));
-                sec[2] += lap();
-                HIPCHK(tick(c->ev0));
-                VCHCHK(cost1_core(c, c->phi_trial, c->u_trial, rows, Jt.data()));
-                HIPCHK(tick(c->ev1));
-                sec[3] += lap();
-                for (int b = 0; b < B; ++b) {
-                    if (nt.decided[b]) continue;
-                    const size_t i = (size_t)b * n_rounds + r;
-                    halvings_out[i] = nt.halvings[b];
-                    counts_out[3 * i + 1] = (int64_t)sums[4 * b + 2];
-                    counts_out[3 * i + 2] = (int64_t)sums[4 * b + 3];
-                    const double s = nt.s[b];
-                    // a march that reported a non-finite mass defect: the trial counts as not accepted
-                    const double c_new = bad[b] ? nan : Jt[5 * b + 4];
-                    const vch_newton_verdict v = nt.judge(b, c->pgd.cost[b], pred[b], c_new, max_halvings);
-                    if (v == VCH_NT_STALL) status_out[i] = VCH_NEWTON_STALLED;
-                    if (v != VCH_NT_ACCEPT) continue;
-                    // accepted: the trial becomes the iterate, as in the PGD loop
-                    c->pgd.cost[b] = c_new;
-                    VCHCHK(copy_traj1(c, c->u_hist, c->u_trial, b, rows));
-                    VCHCHK(copy_traj1(c, c->phi_hist, c->phi_trial, b, rows));
-                    moved = true;
-                    cost_new_out[i] = c_new;
-                    s_out[i] = s;
-                }
-                HIPCHK(hipStreamSynchronize(c->stream));
-            }
-            done_rounds = r + 1;
+        int solve(double *pred, double *rnorm0, int32_t *steps, int32_t *status, int64_t *n_free) {
+            vch_stats st;
+            VCHCHK(hess_cg1_core(c, fn, true, nullptr, VCH_RESIDENT, c->B, rows, c->dt_host.data(), c->t_host.data(), c->x_host.data(),
+                                 VCH_RESIDENT, VCH_RESIDENT, c->opts.data(), c->B, nullptr, tol, nullptr, k, cg_tol, precond, resid.data(),
+                                 curv.data(), pred, rnorm0, steps, status, n_free, &st));
+            sec[0] += st.seconds;
+            return 0;
         }
-        return 0;
-    };
-    const int rc = run();
+        double cost(int b) const { return c->pgd.cost[b]; }
+        int trial(const std::vector<int> &decided, const std::vector<double> &s, double *sums, double *c_new) {
+            HIPCHK(hipEventRecord(c->ev0, c->stream));
+            HIPCHK(hipMemcpyAsync(c->skip_dev, decided.data(), sizeof(int) * c->B, hipMemcpyHostToDevice, c->stream));
+            VCHCHK(newton_trial1_core(c, s.data(), c->skip_dev, sums));
+            HIPCHK(hipEventRecord(c->ev1, c->stream));
+            sec[1] += lap();
+            HIPCHK(hipEventRecord(c->ev0, c->stream));
+            VCHCHK(fwd1_core(c, c->u_trial, rows, c->phi_trial, c->skip_dev, bad.data()));
+            HIPCHK(hipEventRecord(c->ev1, c->stream));
+            sec[2] += lap();
+            HIPCHK(hipEventRecord(c->ev0, c->stream));
+            VCHCHK(cost1_core(c, c->phi_trial, c->u_trial, rows, Jt.data()));
+            HIPCHK(hipEventRecord(c->ev1, c->stream));
+            sec[3] += lap();
+            // a march that reported a non-finite mass defect: the trial counts as not accepted
+            for (int b = 0; b < c->B; ++b) c_new[b] = bad[b] ? std::nan("") : Jt[5 * b + 4];
+            return 0;
+        }
+        int accept(int b, double c_new) {
+            c->pgd.cost[b] = c_new;
+            VCHCHK(copy_traj1(c, c->u_hist, c->u_trial, b, rows));
+            return copy_traj1(c, c->phi_hist, c->phi_trial, b, rows);
+        }
+        int after_trial() {
+            HIPCHK(hipStreamSynchronize(c->stream));
+            return 0;
+        }
+        int after_round() { return 0; }
+    } eng{c, fn, rows, k, precond, cg_tol, tol, std::vector<double>((size_t)B * k), std::vector<double>((size_t)B * k),
+          std::vector<double>(5 * (size_t)B), std::vector<int>(B), {0, 0, 0, 0}};
+    VCHCHK(eng.stop_quirk());
+    bool moved = false;
+    const int rc = vch_newton_rounds(eng, call, moved);
     if (moved) c->pgd_r_valid = false;      // r_hist is the adjoint of an iterate that has been replaced
-    if (rc < 0) return rc;
-    if (seconds_out) memcpy(seconds_out, sec, sizeof(sec));
-    return done_rounds;
+    if (rc >= 0 && seconds_out) memcpy(seconds_out, eng.sec, sizeof(eng.sec));
+    return rc;
 }

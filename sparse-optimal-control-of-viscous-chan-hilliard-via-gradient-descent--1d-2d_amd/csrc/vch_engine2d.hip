@@ -2878,9 +2878,9 @@ static int kr_look(vch2d_ctx *c, void *host, const void *dev, size_t bytes) {
     return 0;
 }
 // The lazy storage of a Krylov call (fn: vch2d_hess_lanczos or vch2d_hess_cg), one group: a refused request gives back what
-// this call got and leaves the context as it was, except that a request for more than the resident storage holds has
-// released that storage (and what it held) first.  On success whatever an earlier call left resident in the basis is no
-// longer valid: the caller overwrites it.
+// this call got and leaves the context usable.  A request for more than the resident storage holds releases that storage
+// first.  kr_valid / ncg_valid, in both engines: what an earlier call left resident stays valid until this call has released
+// it or has all of its storage, so a refused request leaves the context as it was; then the caller overwrites it.
 static int kr_storage(vch2d_ctx *c, const char *fn, int slots, int k, bool want_phiQ) {
     const size_t hist_bytes = (size_t)c->B * (c->Mmax + 1) * c->G.plane * 8;
     if (c->kr_Q && (slots > c->kr_slots || k > c->kr_kcap)) {       // a larger basis than the resident storage holds
@@ -2919,74 +2919,129 @@ static int kr_storage(vch2d_ctx *c, const char *fn, int slots, int k, bool want_
     c->kr_valid = c->ncg_valid = false;
     return 0;
 }
+// The arguments of the Krylov kernels over vectors of `levels` rows: vectors first .. first + nv - 1 of a ring of `slots`,
+// partials of `pstride` cells per workgroup.
+static KrArgs kr_args(const vch2d_ctx *c, int levels, int first, int nv, int slots, int pstride) {
+    const long hs = hist_stride(c);
+    return KrArgs{c->kr_Q, (long)c->B * hs, hs, levels, c->kr_lchunk, first, nv, slots, pstride, c->kr_mask,
+                  kr_cells(c, kr_layout(c, c->kr_slots, c->kr_kcap)).stop};
+}
+
+// What vch2d_hess_lanczos and vch2d_hess_cg have in common between kr_open and kr_close.
+struct KrCall {
+    KrCells cells;
+    double *part;                       // the partials: S cells per workgroup, nsum workgroups per trajectory; kgrid: the passes' grid
+    long nsum;
+    dim3 kgrid;
+    int S, u_rows;                      // u_rows: rows of the resident control that bound the free set (u_dev NULL: none)
+    const double *u_dev, *pq, *pt;
+    std::vector<long long> nfree;
+    std::vector<int> bad;               // the mass fix's refusals, read with the call's last look
+    double keep_tol;                    // the context's lin_tol while the call runs at rtol
+};
+// After tan_check_state and the entry's own checks: the rest of the checks, before anything is enqueued, copied or allocated.
+// Then the storage of `slots` vectors and k steps, the free set (mask NULL: built from the control and the box at tol; empty_ok:
+// an empty one is no error) with its one mask launch, its sum and one look, the targets; the solves stop at rtol until kr_close.
+static int kr_open(vch2d_ctx *c, const char *fn, KrCall &K, int slots, int k, bool empty_ok, const double **dt, int M,
+                   const double **t_hist, const double *x, const double *y, const double *phi_Q, const double *phi_T,
+                   const vch_opt_params *opts, int n_opts, double rtol, const uint8_t *mask, double tol) {
+    bool pgd = false;
+    VCHCHK(tan_check_args(c, fn, 1, dt, M, t_hist, x, y, phi_Q, phi_T, opts, n_opts, 2, &pgd));
+    if (!c->shift_res)
+        return vch_fail(VCH_ERR_STATE, "%s: the resident state history is not one a march of this context wrote", fn);
+    // the direction has M + 1 rows: the g_rows the rule of vch2d_hessvec must allow
+    if (!c->res_pgd && c->fwd_u_rows > 0)
+        TANCHK(c->fwd_u_rows >= M + 1, "the march's control has fewer than M + 1 rows");
+    const Geom &G = c->G;
+    const int B = c->B, levels = M + 1, nch = (levels + c->kr_lchunk - 1) / c->kr_lchunk;
+    const long hs = hist_stride(c);
+    VCHCHK(kr_storage(c, fn, slots, k, !pgd && phi_Q));
+    const KrLayout L = kr_layout(c, c->kr_slots, c->kr_kcap);
+    K.cells = kr_cells(c, L);
+    K.part = c->kr_sc + L.part;
+    K.S = c->kr_slots;
+    K.nsum = (long)nch * c->nblk;
+    K.kgrid = dim3(c->nblk, nch, B);
+    VCHCHK(write_opt_tab(c, c->seam_tab, opts, n_opts));
+    if (mask)
+        for (int b = 0; b < B; ++b)
+            HIPCHK(hipMemcpy2DAsync(c->kr_mask + (size_t)b * hs, (size_t)G.pitch, mask + (size_t)b * levels * G.ns * G.nf, (size_t)G.nf,
+                                    (size_t)G.nf, (size_t)G.ns * levels, hipMemcpyHostToDevice, c->stream));
+    K.u_rows = c->res_pgd ? levels : std::min(c->fwd_u_rows, levels);
+    K.u_dev = K.u_rows > 0 ? (const double *)c->u_hist : (const double *)nullptr;
+    LAUNCHC(PC_KRYLOV, k_kr_mask, K.kgrid, dim3(NTH), G, kr_args(c, levels, 0, 0, slots, K.S), K.u_dev, K.u_rows,
+            (const double *)c->seam_tab, tol > 0 ? tol : 1e-8, mask ? 0 : 1, c->kr_mask, K.part);
+    LAUNCHC(PC_KRYLOV, k_kr_fin, dim3(B), dim3(NTH), K.cells, (const double *)K.part, K.nsum, K.S, 0, 0, 0, k);
+    K.nfree.resize(B);
+    VCHCHK(kr_look(c, K.nfree.data(), K.cells.nfree, sizeof(long long) * B));
+    for (int b = 0; b < B; ++b)
+        if (K.nfree[b] < 1 && !empty_ok) return vch_fail(VCH_ERR_ARG, "%s: trajectory %d: the free set is empty", fn, b);
+    VCHCHK(tan_targets(c, pgd, x, y, phi_Q, phi_T, M, &K.pq, &K.pt));
+    K.bad.assign(B, -1);
+    K.keep_tol = c->lin_tol;
+    c->lin_tol = rtol > 0 ? rtol : 1e-12;
+    return 0;
+}
+// One product H d into hv_H, d the direction in the trial-control scratch: with the gradient sweep's xp of every step from
+// kr_X, or (kr_nocache) with that sweep run again.
+static int kr_product(vch2d_ctx *c, const HvRun &r) {
+    if (c->kr_nocache) VCHCHK(hv_grad_init(c, r));
+    VCHCHK(hv_tangent(c, r));
+    return c->kr_nocache ? hv_sweeps(c, r, 0, 1, nullptr, nullptr) : hv_sweeps(c, r, 1, 1, nullptr, c->kr_X);
+}
+// rc: what the call's own enqueues returned.  The context's own tolerance comes back on every path out.
+static int kr_close(vch2d_ctx *c, const char *fn, const KrCall &K, int rc, vch_stats *stats) {
+    c->lin_tol = K.keep_tol;
+    if (rc < 0) {
+        (void)reset_counters(c);    // the records as the end of a PGD iteration leaves them
+        return rc;
+    }
+    float ms = 0;
+    hipEventElapsedTime(&ms, c->ev0, c->ev1);
+    fill_stats(c, stats, ms);
+    if (stats) {                    // the launches and the look of the free set, made before the counters were reset
+        stats->launches += 2;
+        stats->host_syncs += 1;
+    }
+    VCHCHK(reset_counters(c));      // the records as the end of a PGD iteration leaves them
+    return fix_check_end(fn, K.bad);
+}
 
 extern "C" int vch2d_hess_lanczos(vch2d_ctx *c, const double *dt, int M, const double *t_hist, const double *x, const double *y,
                                   const double *phi_Q, const double *phi_T, const vch_opt_params *opts, int n_opts, double rtol,
                                   const uint8_t *mask, double tol, const double *q0, int k, int reorth, double *alpha_out,
                                   double *beta_out, int32_t *steps_out, int64_t *n_free_out, vch_stats *stats) {
     CTXCHK(c);
+    const char *fn = "vch2d_hess_lanczos";
     // everything below is checked before anything is enqueued, copied or allocated
-    VCHCHK(tan_check_state(c, __func__));
-    ARGCHK(opts, "NULL opts");
-    ARGCHK(q0, "NULL q0");
-    ARGCHK(alpha_out && beta_out && steps_out && n_free_out, "NULL alpha_out, beta_out, steps_out or n_free_out");
-    ARGCHK(k >= 1, "k must be >= 1");
-    ARGCHK(reorth == 0 || reorth == 1, "reorth must be 0 or 1");
-    bool pgd = false;
-    VCHCHK(tan_check_args(c, __func__, 1, &dt, M, &t_hist, x, y, phi_Q, phi_T, opts, n_opts, 2, &pgd));
-    if (!c->shift_res)
-        return vch_fail(VCH_ERR_STATE, "vch2d_hess_lanczos: the resident state history is not one a march of this context wrote");
-    // the direction has M + 1 rows: the g_rows the rule of vch2d_hessvec must allow
-    if (!c->res_pgd && c->fwd_u_rows > 0)
-        ARGCHK(c->fwd_u_rows >= M + 1, "the march's control has fewer than M + 1 rows");
+    VCHCHK(tan_check_state(c, fn));
+    TANCHK(opts, "NULL opts");
+    TANCHK(q0, "NULL q0");
+    TANCHK(alpha_out && beta_out && steps_out && n_free_out, "NULL alpha_out, beta_out, steps_out or n_free_out");
+    TANCHK(k >= 1, "k must be >= 1");
+    TANCHK(reorth == 0 || reorth == 1, "reorth must be 0 or 1");
     const Geom &G = c->G;
     const int B = c->B, levels = M + 1, slots = reorth ? k + 1 : 3;
-    const long hs = hist_stride(c);
-    VCHCHK(kr_storage(c, __func__, slots, k, !pgd && phi_Q));
-    const KrLayout L = kr_layout(c, c->kr_slots, c->kr_kcap);
-    const KrCells cells = kr_cells(c, L);
-    double *part = c->kr_sc + L.part;
-    const int S = c->kr_slots, nch = (levels + c->kr_lchunk - 1) / c->kr_lchunk;
-    const long nsum = (long)nch * c->nblk;
-    const dim3 kgrid(c->nblk, nch, B);
-    auto kr_args = [&](int first, int nv) {
-        return KrArgs{c->kr_Q, (long)B * hs, hs, levels, c->kr_lchunk, first, nv, slots, S, c->kr_mask, cells.stop};
-    };
-    auto slot_of = [&](int i) { return c->kr_Q + (long)(i % slots) * B * hs; };
-    // the free set and its size: one mask launch, its sum and one look
-    VCHCHK(write_opt_tab(c, c->seam_tab, opts, n_opts));
-    if (mask)
-        for (int b = 0; b < B; ++b)
-            HIPCHK(hipMemcpy2DAsync(c->kr_mask + (size_t)b * hs, (size_t)G.pitch, mask + (size_t)b * levels * G.ns * G.nf, (size_t)G.nf,
-                                    (size_t)G.nf, (size_t)G.ns * levels, hipMemcpyHostToDevice, c->stream));
-    const int u_rows = c->res_pgd ? levels : std::min(c->fwd_u_rows, levels);
-    LAUNCHC(PC_KRYLOV, k_kr_mask, kgrid, dim3(NTH), G, kr_args(0, 0), u_rows > 0 ? (const double *)c->u_hist : (const double *)nullptr, u_rows,
-           (const double *)c->seam_tab, tol > 0 ? tol : 1e-8, mask ? 0 : 1, c->kr_mask, part);
-    LAUNCHC(PC_KRYLOV, k_kr_fin, dim3(B), dim3(NTH), cells, (const double *)part, nsum, S, 0, 0, 0, k);
-    std::vector<long long> nfree(B);
-    VCHCHK(kr_look(c, nfree.data(), cells.nfree, sizeof(long long) * B));
-    for (int b = 0; b < B; ++b)
-        if (nfree[b] < 1) return vch_fail(VCH_ERR_ARG, "vch2d_hess_lanczos: trajectory %d: the free set is empty", b);
-    const double *pq = nullptr, *pt = nullptr;
-    VCHCHK(tan_targets(c, pgd, x, y, phi_Q, phi_T, M, &pq, &pt));
-    // the solves stop at rtol (relative residual); the context's own tolerance comes back on every path out
-    const double keep_tol = c->lin_tol;
-    c->lin_tol = rtol > 0 ? rtol : 1e-12;
-    std::vector<int> bad(B, -1);
+    KrCall K;
+    VCHCHK(kr_open(c, fn, K, slots, k, false, &dt, M, &t_hist, x, y, phi_Q, phi_T, opts, n_opts, rtol, mask, tol));
+    const KrCells &cells = K.cells;
+    const int S = K.S;
+    auto kr_args = [&](int first, int nv) { return ::kr_args(c, levels, first, nv, slots, S); };
+    auto slot_of = [&](int i) { return c->kr_Q + (long)(i % slots) * B * hist_stride(c); };
     std::vector<double> look(2 * (size_t)B);
     int hi = 0;                                     // the highest basis vector stored
     auto run = [&]() -> int {
-        HvRun r{dt, M, pq, pt, levels, levels, {}};
+        HvRun r{dt, M, K.pq, K.pt, levels, levels, {}};
         VCHCHK(h2d_hist(c, c->u_trial, q0, levels));            // the direction lives in the trial-control scratch
         VCHCHK(hv_begin(c, r, t_hist, opts, n_opts));
         // q_0 = P q0 / ||P q0||
-        LAUNCHC(PC_KRYLOV, k_kr_start, kgrid, dim3(NTH), G, kr_args(0, 0), (const double *)c->u_trial, slot_of(0), part);
-        LAUNCHC(PC_KRYLOV, k_kr_fin, dim3(B), dim3(NTH), cells, (const double *)part, nsum, S, 1, 0, 0, k);
+        LAUNCHC(PC_KRYLOV, k_kr_start, K.kgrid, dim3(NTH), G, kr_args(0, 0), (const double *)c->u_trial, slot_of(0), K.part);
+        LAUNCHC(PC_KRYLOV, k_kr_fin, dim3(B), dim3(NTH), cells, (const double *)K.part, K.nsum, S, 1, 0, 0, k);
         VCHCHK(kr_look(c, look.data(), cells.look, sizeof(double) * 2 * B));
         for (int b = 0; b < B; ++b)
             if (!(look[2 * b] > 0.0) || !std::isfinite(look[2 * b]))
-                return vch_fail(VCH_ERR_ARG, "vch2d_hess_lanczos: trajectory %d: the start vector vanishes on the free set (or is not finite)", b);
-        LAUNCHC(PC_KRYLOV, k_kr_next, kgrid, dim3(NTH), G, kr_args(0, 0), (const double *)slot_of(0), (const double *)cells.scal, slot_of(0),
+                return vch_fail(VCH_ERR_ARG, "%s: trajectory %d: the start vector vanishes on the free set (or is not finite)", fn, b);
+        LAUNCHC(PC_KRYLOV, k_kr_next, K.kgrid, dim3(NTH), G, kr_args(0, 0), (const double *)slot_of(0), (const double *)cells.scal, slot_of(0),
                c->u_trial);
         HIPCHK(hipMemsetAsync(cells.alpha, 0xff, sizeof(double) * 2 * B * c->kr_kcap, c->stream));      // NaN: alpha, then beta
         if (!c->kr_nocache) {           // the gradient sweep once per base point: its xp of every step stays in kr_X
@@ -2996,24 +3051,17 @@ extern "C" int vch2d_hess_lanczos(vch2d_ctx *c, const double *dt, int M, const d
         std::vector<char> active(B, 1);
         for (int b = 0; b < B; ++b) steps_out[b] = 0;
         for (int j = 0; j < k; ++j) {
-            if (c->kr_nocache) {
-                VCHCHK(hv_grad_init(c, r));
-                VCHCHK(hv_tangent(c, r));
-                VCHCHK(hv_sweeps(c, r, 0, 1, nullptr, nullptr));
-            } else {
-                VCHCHK(hv_tangent(c, r));
-                VCHCHK(hv_sweeps(c, r, 1, 1, nullptr, c->kr_X));
-            }
+            VCHCHK(kr_product(c, r));
             // w = P H q_j in hv_H; classical Gram-Schmidt twice against q_first .. q_j
             const int first = reorth ? 0 : std::max(j - 1, 0), nv = j + 1 - first;
             const KrArgs a = kr_args(first % slots, nv);
-            LAUNCHC(PC_KRYLOV, (k_kr_pass<0>), kgrid, dim3(NTH), G, a, c->hv_H, (const double *)nullptr, part);
-            LAUNCHC(PC_KRYLOV, k_kr_fin, dim3(B), dim3(NTH), cells, (const double *)part, nsum, S, 2, nv, j, k);
-            LAUNCHC(PC_KRYLOV, (k_kr_pass<1>), kgrid, dim3(NTH), G, a, c->hv_H, (const double *)cells.coef1, part);
-            LAUNCHC(PC_KRYLOV, k_kr_fin, dim3(B), dim3(NTH), cells, (const double *)part, nsum, S, 3, nv, j, k);
-            LAUNCHC(PC_KRYLOV, (k_kr_pass<2>), kgrid, dim3(NTH), G, a, c->hv_H, (const double *)cells.coef2, part);
-            LAUNCHC(PC_KRYLOV, k_kr_fin, dim3(B), dim3(NTH), cells, (const double *)part, nsum, S, 4, nv, j, k);
-            LAUNCHC(PC_KRYLOV, k_kr_next, kgrid, dim3(NTH), G, a, (const double *)c->hv_H, (const double *)cells.scal, slot_of(j + 1), c->u_trial);
+            LAUNCHC(PC_KRYLOV, (k_kr_pass<0>), K.kgrid, dim3(NTH), G, a, c->hv_H, (const double *)nullptr, K.part);
+            LAUNCHC(PC_KRYLOV, k_kr_fin, dim3(B), dim3(NTH), cells, (const double *)K.part, K.nsum, S, 2, nv, j, k);
+            LAUNCHC(PC_KRYLOV, (k_kr_pass<1>), K.kgrid, dim3(NTH), G, a, c->hv_H, (const double *)cells.coef1, K.part);
+            LAUNCHC(PC_KRYLOV, k_kr_fin, dim3(B), dim3(NTH), cells, (const double *)K.part, K.nsum, S, 3, nv, j, k);
+            LAUNCHC(PC_KRYLOV, (k_kr_pass<2>), K.kgrid, dim3(NTH), G, a, c->hv_H, (const double *)cells.coef2, K.part);
+            LAUNCHC(PC_KRYLOV, k_kr_fin, dim3(B), dim3(NTH), cells, (const double *)K.part, K.nsum, S, 4, nv, j, k);
+            LAUNCHC(PC_KRYLOV, k_kr_next, K.kgrid, dim3(NTH), G, a, (const double *)c->hv_H, (const double *)cells.scal, slot_of(j + 1), c->u_trial);
             hi = j + 1;
             // the one look of the step: beta_j and the stop cell of every trajectory
             VCHCHK(kr_look(c, look.data(), cells.look, sizeof(double) * 2 * B));
@@ -3031,29 +3079,14 @@ extern "C" int vch2d_hess_lanczos(vch2d_ctx *c, const double *dt, int M, const d
             HIPCHK(hipMemcpyAsync(alpha_out + (size_t)b * k, cells.alpha + (size_t)b * k, sizeof(double) * k, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(hipMemcpyAsync(beta_out + (size_t)b * k, cells.beta + (size_t)b * k, sizeof(double) * k, hipMemcpyDeviceToHost, c->stream));
         }
-        HIPCHK(hipMemcpyAsync(bad.data(), c->fix_bad, sizeof(int) * B, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(K.bad.data(), c->fix_bad, sizeof(int) * B, hipMemcpyDeviceToHost, c->stream));
         VCHCHK(sync_state(c));
         return 0;
     };
-    int rc = run();
-    c->lin_tol = keep_tol;
-    if (rc < 0) {
-        (void)reset_counters(c);    // the records as the end of a PGD iteration leaves them
-        return rc;
-    }
-    float ms = 0;
-    hipEventElapsedTime(&ms, c->ev0, c->ev1);
-    fill_stats(c, stats, ms);
-    if (stats) {                    // the launches and the look of the free set, made before the counters were reset
-        stats->launches += 2;
-        stats->host_syncs += 1;
-    }
-    VCHCHK(reset_counters(c));      // the records as the end of a PGD iteration leaves them
-    rc = fix_check_end("vch2d_hess_lanczos", bad);
-    if (rc < 0) return rc;
+    VCHCHK(kr_close(c, fn, K, run(), stats));
     int smin = steps_out[0];
     for (int b = 0; b < B; ++b) {
-        n_free_out[b] = nfree[b];
+        n_free_out[b] = K.nfree[b];
         smin = std::min(smin, (int)steps_out[b]);
     }
     c->kr_valid = true;
@@ -3075,15 +3108,11 @@ extern "C" int vch2d_krylov_vector(vch2d_ctx *c, const double *coef, int m, doub
                         m, c->kr_window);
     ARGCHK(m <= c->kr_min_steps + 1, "m exceeds the smallest step count of the batch plus one");
     const int B = c->B, S = c->kr_slots, levels = c->kr_levels;
-    const long hs = hist_stride(c);
-    const KrLayout L = kr_layout(c, c->kr_slots, c->kr_kcap);
-    const KrCells cells = kr_cells(c, L);
-    double *ucoef = c->kr_sc + L.ucoef;
+    double *ucoef = c->kr_sc + kr_layout(c, c->kr_slots, c->kr_kcap).ucoef;
     HIPCHK(hipMemcpy2DAsync(ucoef, sizeof(double) * S, coef, sizeof(double) * m, sizeof(double) * m, (size_t)B, hipMemcpyHostToDevice,
                             c->stream));
     const int nch = (levels + c->kr_lchunk - 1) / c->kr_lchunk;
-    const KrArgs a{c->kr_Q, (long)B * hs, hs, levels, c->kr_lchunk, 0, m, c->kr_run_slots, S, c->kr_mask, cells.stop};
-    LAUNCH(k_kr_lincomb, dim3(c->nblk, nch, B), dim3(NTH), c->G, a, (const double *)ucoef, c->hv_H);
+    LAUNCH(k_kr_lincomb, dim3(c->nblk, nch, B), dim3(NTH), c->G, kr_args(c, levels, 0, m, c->kr_run_slots, S), (const double *)ucoef, c->hv_H);
     return d2h_hist(c, out, c->hv_H, levels);
 }
 
@@ -3108,53 +3137,20 @@ static int hess_cg_core(vch2d_ctx *c, const char *fn, bool empty_ok, const doubl
     TANCHK(k >= 1, "k must be >= 1");
     TANCHK(precond == 0 || precond == 1, "precond must be 0 or 1");
     TANCHK(std::isfinite(cg_tol), "cg_tol must be finite");
-    bool pgd = false;
-    VCHCHK(tan_check_args(c, fn, 1, &dt, M, &t_hist, x, y, phi_Q, phi_T, opts, n_opts, 2, &pgd));
-    if (!c->shift_res)
-        return vch_fail(VCH_ERR_STATE, "%s: the resident state history is not one a march of this context wrote", fn);
-    // the direction has M + 1 rows: the g_rows the rule of vch2d_hessvec must allow
-    if (!c->res_pgd && c->fwd_u_rows > 0)
-        TANCHK(c->fwd_u_rows >= M + 1, "the march's control has fewer than M + 1 rows");
+    KrCall K;
+    VCHCHK(kr_open(c, fn, K, 3, k, empty_ok, &dt, M, &t_hist, x, y, phi_Q, phi_T, opts, n_opts, rtol, mask, tol));
     const Geom &G = c->G;
-    const int B = c->B, levels = M + 1;
-    const long hs = hist_stride(c);
-    VCHCHK(kr_storage(c, fn, 3, k, !pgd && phi_Q));
-    const KrLayout L = kr_layout(c, c->kr_slots, c->kr_kcap);
-    const KrCells cells = kr_cells(c, L);
+    const int B = c->B, levels = M + 1, S = K.S;
+    const KrCells &cells = K.cells;
     // the cells of the iteration in the block of the Lanczos scalars: resid, curv where alpha, beta live
     const NcgCells nc{cells.alpha, cells.beta, cells.look, cells.scal, cells.amax, cells.coef1, cells.coef1 + B, cells.coef1 + 2 * B,
                       cells.lim, cells.stop};
-    double *part = c->kr_sc + L.part;
-    const int S = c->kr_slots, nch = (levels + c->kr_lchunk - 1) / c->kr_lchunk;
-    const long nsum = (long)nch * c->nblk;
-    const dim3 kgrid(c->nblk, nch, B);
-    const KrArgs a{c->kr_Q, (long)B * hs, hs, levels, c->kr_lchunk, 0, 0, 3, S, c->kr_mask, cells.stop};
+    const KrArgs a = kr_args(c, levels, 0, 0, 3, S);
     const double stop_at = cg_tol > 0 ? cg_tol : 1e-8;
-    // the free set and its size: one mask launch, its sum and one look
-    VCHCHK(write_opt_tab(c, c->seam_tab, opts, n_opts));
-    if (mask)
-        for (int b = 0; b < B; ++b)
-            HIPCHK(hipMemcpy2DAsync(c->kr_mask + (size_t)b * hs, (size_t)G.pitch, mask + (size_t)b * levels * G.ns * G.nf, (size_t)G.nf,
-                                    (size_t)G.nf, (size_t)G.ns * levels, hipMemcpyHostToDevice, c->stream));
-    const int u_rows = c->res_pgd ? levels : std::min(c->fwd_u_rows, levels);
-    const double *u_dev = u_rows > 0 ? (const double *)c->u_hist : (const double *)nullptr;
-    LAUNCHC(PC_KRYLOV, k_kr_mask, kgrid, dim3(NTH), G, a, u_dev, u_rows, (const double *)c->seam_tab, tol > 0 ? tol : 1e-8, mask ? 0 : 1,
-            c->kr_mask, part);
-    LAUNCHC(PC_KRYLOV, k_kr_fin, dim3(B), dim3(NTH), cells, (const double *)part, nsum, S, 0, 0, 0, k);
-    std::vector<long long> nfree(B);
-    VCHCHK(kr_look(c, nfree.data(), cells.nfree, sizeof(long long) * B));
-    for (int b = 0; b < B; ++b)
-        if (nfree[b] < 1 && !empty_ok) return vch_fail(VCH_ERR_ARG, "%s: trajectory %d: the free set is empty", fn, b);
-    const double *pq = nullptr, *pt = nullptr;
-    VCHCHK(tan_targets(c, pgd, x, y, phi_Q, phi_T, M, &pq, &pt));
-    // the solves stop at rtol (relative residual); the context's own tolerance comes back on every path out
-    const double keep_tol = c->lin_tol;
-    c->lin_tol = rtol > 0 ? rtol : 1e-12;
-    std::vector<int> bad(B, -1);
     std::vector<double> look(2 * (size_t)B);
     std::vector<long long> steps(B), stop(B);
     auto run = [&]() -> int {
-        HvRun r{dt, M, pq, pt, levels, levels, {}};
+        HvRun r{dt, M, K.pq, K.pt, levels, levels, {}};
         if (rhs) VCHCHK(h2d_hist(c, c->u_trial, rhs, levels));   // through the trial-control scratch, which then holds p
         VCHCHK(hv_begin(c, r, t_hist, opts, n_opts));
         // the gradient sweep once per base point: its xp of every step stays in kr_X, its field is the Newton right-hand
@@ -3166,13 +3162,13 @@ static int hess_cg_core(vch2d_ctx *c, const char *fn, bool empty_ok, const doubl
         };
         if (!rhs) {
             VCHCHK(grad_sweep());
-            LAUNCHC(PC_KRYLOV, (k_ncg_start<1>), kgrid, dim3(NTH), G, a, (const double *)c->hv_G, u_dev, u_rows, (const double *)c->hv_wt,
-                    (const double *)c->W_cost, (const double *)c->seam_tab, precond, c->u_trial, part);
+            LAUNCHC(PC_KRYLOV, (k_ncg_start<1>), K.kgrid, dim3(NTH), G, a, (const double *)c->hv_G, K.u_dev, K.u_rows, (const double *)c->hv_wt,
+                    (const double *)c->W_cost, (const double *)c->seam_tab, precond, c->u_trial, K.part);
         } else {
-            LAUNCHC(PC_KRYLOV, (k_ncg_start<0>), kgrid, dim3(NTH), G, a, (const double *)c->u_trial, u_dev, u_rows,
-                    (const double *)c->hv_wt, (const double *)c->W_cost, (const double *)c->seam_tab, precond, c->u_trial, part);
+            LAUNCHC(PC_KRYLOV, (k_ncg_start<0>), K.kgrid, dim3(NTH), G, a, (const double *)c->u_trial, K.u_dev, K.u_rows,
+                    (const double *)c->hv_wt, (const double *)c->W_cost, (const double *)c->seam_tab, precond, c->u_trial, K.part);
         }
-        LAUNCHC(PC_KRYLOV, k_ncg_fin, dim3(B), dim3(NTH), nc, (const double *)part, nsum, S, 1, 0, k, stop_at);
+        LAUNCHC(PC_KRYLOV, k_ncg_fin, dim3(B), dim3(NTH), nc, (const double *)K.part, K.nsum, S, 1, 0, k, stop_at);
         HIPCHK(hipMemsetAsync(nc.resid, 0xff, sizeof(double) * 2 * B * c->kr_kcap, c->stream));         // NaN: resid, then curv
         VCHCHK(kr_look(c, look.data(), nc.look, sizeof(double) * 2 * B));
         bool any = false;
@@ -3183,23 +3179,16 @@ static int hess_cg_core(vch2d_ctx *c, const char *fn, bool empty_ok, const doubl
         }
         if (any && rhs && !c->kr_nocache) VCHCHK(grad_sweep());
         for (int j = 0; any && j < k; ++j) {
-            if (c->kr_nocache) {
-                VCHCHK(hv_grad_init(c, r));
-                VCHCHK(hv_tangent(c, r));
-                VCHCHK(hv_sweeps(c, r, 0, 1, nullptr, nullptr));
-            } else {
-                VCHCHK(hv_tangent(c, r));
-                VCHCHK(hv_sweeps(c, r, 1, 1, nullptr, c->kr_X));
-            }
+            VCHCHK(kr_product(c, r));
             // H p in hv_H
-            LAUNCHC(PC_KRYLOV, k_ncg_curv, kgrid, dim3(NTH), G, a, (const double *)c->hv_H, (const double *)c->hv_wt,
-                    (const double *)c->W_cost, precond, part);
-            LAUNCHC(PC_KRYLOV, k_ncg_fin, dim3(B), dim3(NTH), nc, (const double *)part, nsum, S, 2, j, k, stop_at);
-            LAUNCHC(PC_KRYLOV, k_ncg_update, kgrid, dim3(NTH), G, a, (const double *)c->hv_H, (const double *)nc.alpha,
-                    (const double *)c->hv_wt, (const double *)c->W_cost, precond, part);
-            LAUNCHC(PC_KRYLOV, k_ncg_fin, dim3(B), dim3(NTH), nc, (const double *)part, nsum, S, 3, j, k, stop_at);
+            LAUNCHC(PC_KRYLOV, k_ncg_curv, K.kgrid, dim3(NTH), G, a, (const double *)c->hv_H, (const double *)c->hv_wt,
+                    (const double *)c->W_cost, precond, K.part);
+            LAUNCHC(PC_KRYLOV, k_ncg_fin, dim3(B), dim3(NTH), nc, (const double *)K.part, K.nsum, S, 2, j, k, stop_at);
+            LAUNCHC(PC_KRYLOV, k_ncg_update, K.kgrid, dim3(NTH), G, a, (const double *)c->hv_H, (const double *)nc.alpha,
+                    (const double *)c->hv_wt, (const double *)c->W_cost, precond, K.part);
+            LAUNCHC(PC_KRYLOV, k_ncg_fin, dim3(B), dim3(NTH), nc, (const double *)K.part, K.nsum, S, 3, j, k, stop_at);
             if (j + 1 < k)
-                LAUNCHC(PC_KRYLOV, k_ncg_dir, kgrid, dim3(NTH), G, a, (const double *)nc.beta, (const double *)c->hv_wt,
+                LAUNCHC(PC_KRYLOV, k_ncg_dir, K.kgrid, dim3(NTH), G, a, (const double *)nc.beta, (const double *)c->hv_wt,
                         (const double *)c->W_cost, precond, c->u_trial);
             // the one look of the step: the residual and the stop cell of every trajectory
             VCHCHK(kr_look(c, look.data(), nc.look, sizeof(double) * 2 * B));
@@ -3215,28 +3204,13 @@ static int hess_cg_core(vch2d_ctx *c, const char *fn, bool empty_ok, const doubl
         HIPCHK(hipMemcpyAsync(rnorm0_out, nc.rnorm0, sizeof(double) * B, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipMemcpyAsync(steps.data(), nc.steps, sizeof(long long) * B, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipMemcpyAsync(stop.data(), nc.stop, sizeof(long long) * B, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(bad.data(), c->fix_bad, sizeof(int) * B, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(K.bad.data(), c->fix_bad, sizeof(int) * B, hipMemcpyDeviceToHost, c->stream));
         VCHCHK(sync_state(c));
         return 0;
     };
-    int rc = run();
-    c->lin_tol = keep_tol;
-    if (rc < 0) {
-        (void)reset_counters(c);    // the records as the end of a PGD iteration leaves them
-        return rc;
-    }
-    float ms = 0;
-    hipEventElapsedTime(&ms, c->ev0, c->ev1);
-    fill_stats(c, stats, ms);
-    if (stats) {                    // the launches and the look of the free set, made before the counters were reset
-        stats->launches += 2;
-        stats->host_syncs += 1;
-    }
-    VCHCHK(reset_counters(c));      // the records as the end of a PGD iteration leaves them
-    rc = fix_check_end(fn, bad);
-    if (rc < 0) return rc;
+    VCHCHK(kr_close(c, fn, K, run(), stats));
     for (int b = 0; b < B; ++b) {
-        n_free_out[b] = nfree[b];
+        n_free_out[b] = K.nfree[b];
         steps_out[b] = (int32_t)steps[b];
         status_out[b] = (int32_t)stop[b];           // 0: still running after k steps, VCH_CG_LIMIT
     }
@@ -3274,11 +3248,9 @@ extern "C" int vch2d_cg_vector(vch2d_ctx *c, int which, double *out) {
 // look (the cells of a skipped trajectory are not written).
 static int newton_trial_core(vch2d_ctx *c, const double *s_host, const int *skip, double *sums_out) {
     const int B = c->B, levels = c->ncg_levels;
-    const long hs = hist_stride(c);
     VCHCHK(ensure_cost_bufs(c));
-    const KrCells cells = kr_cells(c, kr_layout(c, c->kr_slots, c->kr_kcap));
     const int nch = (levels + c->kr_lchunk - 1) / c->kr_lchunk;
-    const KrArgs a{c->kr_Q, (long)B * hs, hs, levels, c->kr_lchunk, 0, 0, 3, 4, c->kr_mask, cells.stop};
+    const KrArgs a = kr_args(c, levels, 0, 0, 3, 4);        // partials of four sums, whatever the basis holds
     const int u_rows = c->res_pgd ? levels : std::min(c->fwd_u_rows, levels);
     HIPCHK(hipMemcpyAsync(c->alpha_dev, s_host, sizeof(double) * B, hipMemcpyHostToDevice, c->stream));
     LAUNCHC(PC_KRYLOV, k_nt_trial, dim3(c->nblk, nch, B), dim3(NTH), c->G, a, u_rows > 0 ? (const double *)c->u_hist : (const double *)nullptr,
@@ -3315,103 +3287,65 @@ extern "C" int vch2d_pgd_newton(vch2d_ctx *c, int n_rounds, int k, double cg_tol
     if (!c->pgd_ready) return vch_fail(VCH_ERR_STATE, "vch2d_pgd_newton: call vch2d_pgd_init first");
     if (!c->res_pgd || !c->shift_res || c->M_res < 1)
         return vch_fail(VCH_ERR_STATE, "vch2d_pgd_newton: the resident state history is no longer the PGD iterate's (call vch2d_pgd_init again)");
-    ARGCHK(n_rounds >= 1, "n_rounds must be >= 1");
-    ARGCHK(k >= 1, "k must be >= 1");
-    ARGCHK(max_halvings >= 0, "max_halvings must be >= 0");
-    ARGCHK(precond == 0 || precond == 1, "precond must be 0 or 1");
-    ARGCHK(std::isfinite(cg_tol), "cg_tol must be finite");
-    ARGCHK(cost_out && cost_new_out && s_out && pred_out && rnorm0_out && halvings_out && cg_steps_out && cg_status_out && status_out &&
-               counts_out,
-           "NULL cost_out, cost_new_out, s_out, pred_out, rnorm0_out, halvings_out, cg_steps_out, cg_status_out, status_out or counts_out");
-    const int B = c->B, M = c->M_res, rows = M + 1;
-    const double *pq = (c->phiQ) ? c->phiQ : nullptr;
-    const double nan = std::nan("");
-    for (size_t i = 0; i < (size_t)B * n_rounds; ++i) {
-        cost_out[i] = cost_new_out[i] = s_out[i] = pred_out[i] = rnorm0_out[i] = nan;
-        halvings_out[i] = cg_steps_out[i] = cg_status_out[i] = 0;
-        status_out[i] = VCH_NEWTON_IDLE;
-        counts_out[3 * i] = counts_out[3 * i + 1] = counts_out[3 * i + 2] = 0;
-    }
-    double sec[4] = {0, 0, 0, 0};
-    hipEvent_t e0 = c->ev0, e1 = c->ev1;
-    vch_newton_state nt;
-    nt.reset(B);
-    std::vector<double> resid((size_t)B * k), curv((size_t)B * k), pred(B), rn0(B), Jt(5 * (size_t)B), sums(4 * (size_t)B);
-    std::vector<int32_t> steps(B), cgst(B);
-    std::vector<int64_t> nfree(B);
-    bool moved = false;
-    int done_rounds = 0;
-    auto run = [&]() -> int {
-        for (int r = 0; r < n_rounds; ++r) {
-            if (!nt.begin_round()) break;
-            // --- the Newton step of every trajectory on its free set; the solves of an idle one are not gated
-            vch_stats cg;
-            VCHCHK(hess_cg_core(c, "vch2d_pgd_newton", true, nullptr, M, nullptr, nullptr, nullptr, nullptr, nullptr, c->opts.data(), B, rtol,
-                                nullptr, tol, nullptr, k, cg_tol, precond, resid.data(), curv.data(), pred.data(), rn0.data(),
-                                steps.data(), cgst.data(), nfree.data(), &cg));
-            sec[0] += cg.seconds;
-            for (int b = 0; b < B; ++b) {
-                if (nt.idle(b)) continue;
-                const size_t i = (size_t)b * n_rounds + r;
-                cost_out[i] = cost_new_out[i] = c->J_host[5 * b + 4];
-                pred_out[i] = pred[b];
-                rnorm0_out[i] = rn0[b];
-                cg_steps_out[i] = steps[b];
-                cg_status_out[i] = cgst[b];
-                counts_out[3 * i] = nfree[b];
-                status_out[i] = nt.after_solve(b, nfree[b], rn0[b], cgst[b], steps[b]);
-            }
-            // --- trials s = 1, 1/2, ...: a trajectory whose verdict is in sits the trial out
-            while (!nt.all_decided()) {
-                VCHCHK(reset_counters(c));
-                VCHCHK(freeze(c, nt.decided));
-                HIPCHK(hipEventRecord(e0, c->stream));
-                VCHCHK(newton_trial_core(c, nt.s.data(), (const int *)c->frozen_dev, sums.data()));
-                HIPCHK(hipEventRecord(e1, c->stream));
-                sec[1] += elapsed_s(c, e0, e1);
-                HIPCHK(hipEventRecord(e0, c->stream));
-                HIPCHK(hipMemcpyAsync(c->phi_s, c->phi0, sizeof(double) * B * c->G.plane, hipMemcpyDeviceToDevice, c->stream));
-                VCHCHK(forward_core(c, c->u_trial, rows, c->dt.data(), M, c->phi_trial));
-                HIPCHK(hipEventRecord(e1, c->stream));
-                sec[2] += elapsed_s(c, e0, e1);
-                HIPCHK(hipEventRecord(e0, c->stream));
-                VCHCHK(cost_core(c, c->phi_trial, c->u_trial, pq, c->phiT, false, M, c->t_hist.data(), c->opts.data(), Jt.data(), nullptr, B));
-                HIPCHK(hipEventRecord(e1, c->stream));
-                sec[3] += elapsed_s(c, e0, e1);
-                for (int b = 0; b < B; ++b) {
-                    if (nt.decided[b]) continue;
-                    const size_t i = (size_t)b * n_rounds + r;
-                    halvings_out[i] = nt.halvings[b];
-                    counts_out[3 * i + 1] = (int64_t)sums[4 * b + 2];
-                    counts_out[3 * i + 2] = (int64_t)sums[4 * b + 3];
-                    const double s = nt.s[b];
-                    const vch_newton_verdict v = nt.judge(b, c->J_host[5 * b + 4], pred[b], Jt[5 * b + 4], max_halvings);
-                    if (v == VCH_NT_STALL) status_out[i] = VCH_NEWTON_STALLED;
-                    if (v != VCH_NT_ACCEPT) continue;
-                    // accepted: the trial becomes the iterate, as in the PGD loop
-                    std::copy_n(&Jt[5 * b], 5, &c->J_host[5 * b]);
-                    c->pgd.cost[b] = Jt[5 * b + 4];
-                    VCHCHK(copy_traj(c, c->u_hist, c->u_trial, b, rows));
-                    VCHCHK(copy_traj(c, c->phi_hist, c->phi_trial, b, rows));
-                    VCHCHK(copy_traj_shifts(c, b));
-                    moved = true;
-                    cost_new_out[i] = Jt[5 * b + 4];
-                    s_out[i] = s;
-                }
-            }
-            VCHCHK(reset_counters(c));
-            done_rounds = r + 1;
+    const char *fn = "vch2d_pgd_newton";
+    const int B = c->B, M = c->M_res;
+    const vch_newton_call call{B, n_rounds, k, cg_tol, precond, max_halvings, cost_out, cost_new_out, s_out, pred_out, rnorm0_out,
+                               halvings_out, cg_steps_out, cg_status_out, status_out, counts_out};
+    if (const char *bad = vch_newton_check(call)) return vch_fail(VCH_ERR_ARG, "%s: %s", fn, bad);
+    // the engine's side of the rounds (vch_newton.h); sec = {solves, trial controls, marches, costs}
+    struct Rounds {
+        vch2d_ctx *c;
+        const char *fn;
+        int M, k, precond;
+        double cg_tol, tol, rtol;
+        std::vector<double> resid, curv, Jt;
+        double sec[4];
+        int solve(double *pred, double *rnorm0, int32_t *steps, int32_t *status, int64_t *n_free) {
+            vch_stats st;
+            VCHCHK(hess_cg_core(c, fn, true, nullptr, M, nullptr, nullptr, nullptr, nullptr, nullptr, c->opts.data(), c->B, rtol, nullptr,
+                                tol, nullptr, k, cg_tol, precond, resid.data(), curv.data(), pred, rnorm0, steps, status, n_free, &st));
+            sec[0] += st.seconds;
+            return 0;
         }
-        return 0;
-    };
-    const int rc = run();
+        double cost(int b) const { return c->J_host[5 * b + 4]; }
+        int trial(const std::vector<int> &decided, const std::vector<double> &s, double *sums, double *c_new) {
+            VCHCHK(reset_counters(c));
+            VCHCHK(freeze(c, decided));
+            HIPCHK(hipEventRecord(c->ev0, c->stream));
+            VCHCHK(newton_trial_core(c, s.data(), (const int *)c->frozen_dev, sums));
+            HIPCHK(hipEventRecord(c->ev1, c->stream));
+            sec[1] += elapsed_s(c, c->ev0, c->ev1);
+            HIPCHK(hipEventRecord(c->ev0, c->stream));
+            HIPCHK(hipMemcpyAsync(c->phi_s, c->phi0, sizeof(double) * c->B * c->G.plane, hipMemcpyDeviceToDevice, c->stream));
+            VCHCHK(forward_core(c, c->u_trial, M + 1, c->dt.data(), M, c->phi_trial));
+            HIPCHK(hipEventRecord(c->ev1, c->stream));
+            sec[2] += elapsed_s(c, c->ev0, c->ev1);
+            HIPCHK(hipEventRecord(c->ev0, c->stream));
+            VCHCHK(cost_core(c, c->phi_trial, c->u_trial, c->phiQ, c->phiT, false, M, c->t_hist.data(), c->opts.data(), Jt.data(), nullptr, c->B));
+            HIPCHK(hipEventRecord(c->ev1, c->stream));
+            sec[3] += elapsed_s(c, c->ev0, c->ev1);
+            for (int b = 0; b < c->B; ++b) c_new[b] = Jt[5 * b + 4];
+            return 0;
+        }
+        int accept(int b, double c_new) {
+            std::copy_n(&Jt[5 * b], 5, &c->J_host[5 * b]);
+            c->pgd.cost[b] = c_new;
+            VCHCHK(copy_traj(c, c->u_hist, c->u_trial, b, M + 1));
+            VCHCHK(copy_traj(c, c->phi_hist, c->phi_trial, b, M + 1));
+            return copy_traj_shifts(c, b);
+        }
+        int after_trial() { return 0; }
+        int after_round() { return reset_counters(c); }
+    } eng{c, fn, M, k, precond, cg_tol, tol, rtol, std::vector<double>((size_t)B * k), std::vector<double>((size_t)B * k),
+          std::vector<double>(5 * (size_t)B), {0, 0, 0, 0}};
+    bool moved = false;
+    const int rc = vch_newton_rounds(eng, call, moved);
     if (moved) c->pgd_r_valid = false;      // r_hist is the adjoint of an iterate that has been replaced
     if (rc < 0) (void)reset_counters(c);
     HIPCHK(hipMemcpyAsync(c->J_dev, c->J_host.data(), sizeof(double) * 5 * B, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (rc < 0) return rc;
-    if (seconds_out) memcpy(seconds_out, sec, sizeof(sec));
-    return done_rounds;
+    if (rc >= 0 && seconds_out) memcpy(seconds_out, eng.sec, sizeof(eng.sec));
+    return rc;
 }
 
 extern "C" int vch2d_mass_shifts(vch2d_ctx *c, double *out) {

@@ -1,10 +1,12 @@
-// vch_newton.h — the verdicts of the device-resident damped Newton rounds of both engines (vch2d_pgd_newton, DESIGN.md 10i;
-// vch1d_pgd_newton): who ends after the solve, the Armijo test and the halving of the trials, who sits a trial
-// or a round out.  Host arithmetic only (no HIP, no I/O): the engines act on its verdicts, tests/newton_replay_main.cpp
-// replays it on the CPU.
+// vch_newton.h — the device-resident damped Newton rounds of both engines (vch2d_pgd_newton; vch1d_pgd_newton,
+// DESIGN.md 10j).  vch_newton_state holds the verdicts: who ends after the solve, the Armijo test and the halving of the
+// trials, who sits a trial or a round out.  vch_newton_check and vch_newton_rounds are the shared argument checks and the round
+// loop that applies the verdicts and keeps the call's record, over an adapter for what an engine does.  Host arithmetic only
+// (no HIP, no I/O): the engines and tests/newton_replay_main.cpp (scripted solves and costs, on the CPU) are its adapters.
 #pragma once
 #include "../../include/vch.h"
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 constexpr double VCH_NEWTON_ARMIJO = 1e-4;      // a trial is accepted when J(trial) <= cost - 1e-4 s pred
@@ -59,3 +61,94 @@ struct vch_newton_state {
         return VCH_NT_PENDING;
     }
 };
+
+// What a call of vch?d_pgd_newton shares between the engines: the arguments the rounds are run with and the record they
+// write, [B][n_rounds] per array (counts: [B][n_rounds][3] = {n_free, pinned, clipped}).
+struct vch_newton_call {
+    int B, n_rounds, k;
+    double cg_tol;
+    int precond, max_halvings;
+    double *cost, *cost_new, *s, *pred, *rnorm0;
+    int32_t *halvings, *cg_steps, *cg_status, *status;
+    int64_t *counts;
+};
+// The first of these arguments the call must refuse with VCH_ERR_ARG, as the text that follows the entry point's name in
+// the message, or NULL.  An entry point checks this before anything is enqueued, copied or allocated.
+inline const char *vch_newton_check(const vch_newton_call &a) {
+    if (a.n_rounds < 1) return "n_rounds must be >= 1";
+    if (a.k < 1) return "k must be >= 1";
+    if (a.max_halvings < 0) return "max_halvings must be >= 0";
+    if (a.precond != 0 && a.precond != 1) return "precond must be 0 or 1";
+    if (!std::isfinite(a.cg_tol)) return "cg_tol must be finite";
+    if (!(a.cost && a.cost_new && a.s && a.pred && a.rnorm0 && a.halvings && a.cg_steps && a.cg_status && a.status && a.counts))
+        return "NULL cost_out, cost_new_out, s_out, pred_out, rnorm0_out, halvings_out, cg_steps_out, cg_status_out, status_out or "
+               "counts_out";
+    return nullptr;
+}
+
+// The rounds of a call that passed vch_newton_check: the record is initialised, then written round by round.  Returns the
+// rounds run (fewer than n_rounds once every trajectory has ended) or the first negative code a hook returned; `moved`: a
+// step was accepted, on either way out.  The hooks of E, every int one returning < 0 to fail the call:
+//   int solve(pred, rnorm0, steps, status, n_free)   the Newton-CG solve of every trajectory about its iterate into these [B]
+//                                        arrays (an idle trajectory's solve is not gated)
+//   double cost(b)                       the cost of b's iterate
+//   int trial(decided, s, sums, c_new)   the trial control of the steps s, its march and its cost for who is not decided: sums
+//                                        [B][4] = {.., .., pinned, clipped}, c_new [B] (NaN: a march that must not be accepted)
+//   int accept(b, c_new)                 b's trial becomes its iterate
+//   int after_trial(), int after_round()
+template <class E>
+int vch_newton_rounds(E &eng, const vch_newton_call &a, bool &moved) {
+    const int B = a.B;
+    moved = false;
+    for (size_t i = 0; i < (size_t)B * a.n_rounds; ++i) {
+        a.cost[i] = a.cost_new[i] = a.s[i] = a.pred[i] = a.rnorm0[i] = std::nan("");
+        a.halvings[i] = a.cg_steps[i] = a.cg_status[i] = 0;
+        a.status[i] = VCH_NEWTON_IDLE;
+        a.counts[3 * i] = a.counts[3 * i + 1] = a.counts[3 * i + 2] = 0;
+    }
+    vch_newton_state nt;
+    nt.reset(B);
+    std::vector<double> pred(B), rn0(B), sums(4 * (size_t)B), c_new(B);
+    std::vector<int32_t> steps(B), cgst(B);
+    std::vector<int64_t> nfree(B);
+    int rc, done_rounds = 0;
+    for (int r = 0; r < a.n_rounds && nt.begin_round(); ++r) {
+        // --- the Newton step of every trajectory on its free set
+        if ((rc = eng.solve(pred.data(), rn0.data(), steps.data(), cgst.data(), nfree.data())) < 0) return rc;
+        for (int b = 0; b < B; ++b) {
+            if (nt.idle(b)) continue;
+            const size_t i = (size_t)b * a.n_rounds + r;
+            a.cost[i] = a.cost_new[i] = eng.cost(b);
+            a.pred[i] = pred[b];
+            a.rnorm0[i] = rn0[b];
+            a.cg_steps[i] = steps[b];
+            a.cg_status[i] = cgst[b];
+            a.counts[3 * i] = nfree[b];
+            a.status[i] = nt.after_solve(b, nfree[b], rn0[b], cgst[b], steps[b]);
+        }
+        // --- trials s = 1, 1/2, ...: a trajectory whose verdict is in sits the trial out
+        while (!nt.all_decided()) {
+            if ((rc = eng.trial(nt.decided, nt.s, sums.data(), c_new.data())) < 0) return rc;
+            for (int b = 0; b < B; ++b) {
+                if (nt.decided[b]) continue;
+                const size_t i = (size_t)b * a.n_rounds + r;
+                a.halvings[i] = nt.halvings[b];
+                a.counts[3 * i + 1] = (int64_t)sums[4 * b + 2];
+                a.counts[3 * i + 2] = (int64_t)sums[4 * b + 3];
+                const double s = nt.s[b];
+                const vch_newton_verdict v = nt.judge(b, eng.cost(b), pred[b], c_new[b], a.max_halvings);
+                if (v == VCH_NT_STALL) a.status[i] = VCH_NEWTON_STALLED;
+                if (v != VCH_NT_ACCEPT) continue;
+                // accepted: the trial becomes the iterate, as in the PGD loop
+                if ((rc = eng.accept(b, c_new[b])) < 0) return rc;
+                moved = true;
+                a.cost_new[i] = c_new[b];
+                a.s[i] = s;
+            }
+            if ((rc = eng.after_trial()) < 0) return rc;
+        }
+        if ((rc = eng.after_round()) < 0) return rc;
+        done_rounds = r + 1;
+    }
+    return done_rounds;
+}
