@@ -342,8 +342,11 @@ def time_grid(T, dt, time_tol=1e-10):
 _COUNTS = ("newton_its", "solves", "armijo_trials")
 
 
-def forward(P: Params2D, control=None, phi0=None, seed=42, amp=0.1, max_steps=None, stats=None):
+def forward(P: Params2D, control=None, phi0=None, seed=42, amp=0.1, max_steps=None, stats=None, dts=None):
     """Time march (F2:489-596).  Returns (phi_hist (M+1,Nx+1,Ny+1), (x,y), t_hist).
+
+    `dts` (optional sequence): the march takes exactly these steps, whatever P.T and P.dt_initial say, and t_hist
+    accumulates them; None is the reference's rule dt = min(dt_initial, T - t) while t < T - 1e-10 (time_grid).
 
     `phi0`/`seed`/`amp` generalise the hard-coded init_phi_random(amp=0.1, seed=42)
     of F2:517 (the reference's tests monkey-patch it instead).  `control` rows are
@@ -370,10 +373,11 @@ def forward(P: Params2D, control=None, phi0=None, seed=42, amp=0.1, max_steps=No
     hist, ts = [phi.copy()], [0.0]
     t, step = 0.0, 0
     lo, hi = -1.0 + DELTA_SEP, 1.0 - DELTA_SEP
-    while t < P.T - 1e-10:
+    given = None if dts is None else [float(d) for d in dts]
+    while (t < P.T - 1e-10) if given is None else (step < len(given)):
         if max_steps is not None and step >= max_steps:
             break
-        dts = min(P.dt_initial, P.T - t)
+        dts = min(P.dt_initial, P.T - t) if given is None else given[step]
         if control is not None and step < control.shape[0] - 1:
             u_n, u_np1 = control[step], control[step + 1]
         else:
@@ -410,7 +414,7 @@ def forward(P: Params2D, control=None, phi0=None, seed=42, amp=0.1, max_steps=No
         t += dts
         step += 1
         hist.append(phi.copy())
-        ts.append(min(t, P.T))
+        ts.append(min(t, P.T) if given is None else t)
         if stats is not None:           # per-step wall time, operator assembly (once per march) excluded
             stats.setdefault("step_seconds", []).append(_time.perf_counter() - _t_step)
     return np.array(hist), (x, y), np.array(ts)

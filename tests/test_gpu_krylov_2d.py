@@ -59,9 +59,10 @@ def _tile(a, nb):
 class Problem:
     """One base point (grid, march, control, targets) from which contexts of any batch are made."""
 
-    def __init__(self, V, P, t, dts, x, y, phi0, u, opt, env=None):
+    def __init__(self, V, P, t, dts, x, y, phi0, u, opt, env=None, max_steps=None):
         self.V, self.P, self.t, self.dts, self.x, self.y, self.phi0, self.u, self.opt = V, P, t, dts, x, y, phi0, u, opt
         self.M, self.env = len(dts), env or {}
+        self.max_steps = self.M if max_steps is None else max_steps      # of the contexts made here: the march may be shorter
         e = _engine(V, P, 1, max_steps=self.M)
         hist, _ = e.forward(phi0, dts, u=u)
         e.close()
@@ -70,7 +71,7 @@ class Problem:
 
     def context(self, nb):
         with _env(**self.env):
-            eng = _engine(self.V, self.P, nb, max_steps=self.M)
+            eng = _engine(self.V, self.P, nb, max_steps=self.max_steps)
         eng.forward(_tile(self.phi0, nb), self.dts, u=_tile(self.u, nb), store=False)
         return eng
 

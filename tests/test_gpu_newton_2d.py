@@ -21,6 +21,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from test_gpu_forms import _env
 from test_gpu_hessvec_2d import EPS, _engine
 from test_gpu_krylov_2d import Problem, V, _mask_of, _q0, _tile, chunks, dense, tiles      # noqa: F401 (fixtures)
 
@@ -39,7 +40,8 @@ PGD_KEYS = ("cost", "alpha", "attempts", "change", "tracking_error", "terminal_e
 def _pgd(pr, opts, u0, alpha0=None):
     """A context of batch len(opts) with the problem of `pr` resident as a PGD problem from the controls u0."""
     nb = len(opts)
-    eng = _engine(pr.V, pr.P, nb, max_steps=pr.M)
+    with _env(**pr.env):
+        eng = _engine(pr.V, pr.P, nb, max_steps=pr.max_steps)
     eng.pgd_init(_tile(pr.phi0, nb), _tile(pr.phi_T, nb), pr.t, list(opts), phi_Q=_tile(pr.phi_Q, nb), ramp=False, x=pr.x, y=pr.y,
                  u0=np.ascontiguousarray(u0), alpha0=alpha0)
     return eng

@@ -80,6 +80,28 @@ def _tol(name):
     return OWN.get(name, (TOL_D1, TOL_D2, TOL_S))
 
 
+def cos_controls(xx, yy, M, a, B):
+    """The "cos<a>" controls: M + 1 rows per trajectory, amplitude a (1 - 0.02 b) (-1)^b, the modes shifted by b."""
+    cos = lambda amp, s: amp * np.stack([np.cos(np.pi * xx * (1 + (k + s) % 3)) * np.cos(np.pi * yy) * np.sin(1 + k + s)
+                                         for k in range(M + 1)])
+    return np.stack([cos(a * (1.0 - 0.02 * b) * (-1.0) ** b, b) for b in range(B)])
+
+
+def directions(xx, yy, M, B):
+    """(B, M + 1, ..) directions.  Even trajectories: white noise (it must cross tile edges), odd: smooth, with phases and
+    a ramp that keep it from being orthogonal to the controls (a scalar that vanishes by symmetry has no relative deviation)."""
+    rng = np.random.default_rng(11)
+    H = []
+    for b in range(B):
+        if b % 2 == 0:
+            n = rng.standard_normal((M + 1,) + xx.shape)
+            H.append(n / np.abs(n).max())
+        else:
+            H.append(np.stack([np.exp(xx + 0.5 * yy - 1.5) * np.cos(2 * np.pi * xx * (1 + b % 3) + 0.3) * np.cos(np.pi * yy + 0.2)
+                               * np.cos(0.3 * k + b) for k in range(M + 1)]))
+    return np.stack(H)
+
+
 def _problem(name):
     (Nx, Ny, Lx, Ly), par, M, dt, B, ctrl, fft = CASES[name]
     P = o.Params2D(Nx=Nx, Ny=Ny, Lx=Lx, Ly=Ly, T=M * dt, dt_initial=dt, **par)
@@ -87,34 +109,20 @@ def _problem(name):
     assert len(dts) == M <= 4
     x, y = np.linspace(0.0, Lx, Nx + 1), np.linspace(0.0, Ly, Ny + 1)
     xx, yy = np.meshgrid(x / Lx, y / Ly, indexing="ij")
-    cos = lambda amp, s: amp * np.stack([np.cos(np.pi * xx * (1 + (k + s) % 3)) * np.cos(np.pi * yy) * np.sin(1 + k + s)
-                                         for k in range(M + 1)])
     if ctrl == "forms":
         U = _controls(x, y, Lx, Ly, B, M + 1)
     elif ctrl == "wide":            # both trajectories march the one qualified input; their directions differ
         U = np.repeat(_controls(x, y, Lx, Ly, 1, M + 1), B, axis=0)
     else:
-        a = float(ctrl[3:])
-        U = np.stack([cos(a * (1.0 - 0.02 * b) * (-1.0) ** b, b) for b in range(B)])
+        U = cos_controls(xx, yy, M, float(ctrl[3:]), B)
     if ctrl == "wide":
         front = 0.95 * np.tanh((x[:, None] - 0.5 + 0.1 * np.cos(2 * np.pi * y[None, :] / Ly)) / 0.04)
         p0 = np.clip(front + 0.15 * o.init_phi_random(Nx, Ny, o.DELTA_SEP, amp=0.1, seed=42), -0.98, 0.98)
         phi0 = np.stack([p0] * B)
     else:
         phi0 = np.stack([o.init_phi_random(Nx, Ny, o.DELTA_SEP, amp=0.1, seed=42 + b % 7) for b in range(B)])
-    rng = np.random.default_rng(11)
-    H = []
-    # even: white noise (it must cross tile edges), odd: smooth, with phases and a ramp that keep it from being orthogonal to
-    # the controls (a scalar that vanishes by symmetry has no relative deviation)
-    for b in range(B):
-        if b % 2 == 0:
-            n = rng.standard_normal((M + 1, Nx + 1, Ny + 1))
-            H.append(n / np.abs(n).max())
-        else:
-            H.append(np.stack([np.exp(xx + 0.5 * yy - 1.5) * np.cos(2 * np.pi * xx * (1 + b % 3) + 0.3) * np.cos(np.pi * yy + 0.2)
-                               * np.cos(0.3 * k + b) for k in range(M + 1)]))
     W = [(5.0, 10.0, 1e-4)] * B if B <= 2 else [(1.0 + 0.3 * b, 10.0 - 0.2 * b, 1e-4 * (1 + b)) for b in range(B)]
-    return dict(name=name, P=P, t=t, dts=dts, M=M, B=B, x=x, y=y, U=U, H=np.stack(H), phi0=phi0, W=W, fft=fft)
+    return dict(name=name, P=P, t=t, dts=dts, M=M, B=B, x=x, y=y, U=U, H=directions(xx, yy, M, B), phi0=phi0, W=W, fft=fft)
 
 
 _PROBLEMS = {}

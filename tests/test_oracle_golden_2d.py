@@ -132,6 +132,32 @@ def test_forward_backward_cost(tag):
         assert relerr(r0, g["r_none"]) < SOLVE
 
 
+def test_forward_over_given_steps_is_the_default_march():
+    """forward(dts=time_grid(T, dt)[1]) takes the default march's steps: the same bits in the history and the time levels and
+    the same statistics (step_seconds is wall time), with and without a control; other steps are taken as given."""
+    g = golden("g2d_forward_14x11.npz")
+    P = O2.Params2D(Nx=int(g["Nx"]), Ny=int(g["Ny"]), Lx=float(g["Lx"]), Ly=float(g["Ly"]),
+                    T=float(g["T"]), dt_initial=float(g["dt"]))
+    t, dts = O2.time_grid(P.T, P.dt_initial)
+    for u in (None, g["u"]):
+        s0, s1 = {}, {}
+        want, _, t0 = O2.forward(P, control=u, stats=s0)
+        got, _, t1 = O2.forward(P, control=u, stats=s1, dts=dts)
+        assert np.array_equal(got, want) and np.array_equal(t1, t0) and np.array_equal(t0, t)
+        assert set(s0) == set(s1) and "mass_shifts" in s0
+        for k in s0:
+            if k != "step_seconds":
+                assert np.array_equal(np.asarray(s0[k]), np.asarray(s1[k])), k
+        assert np.abs(np.array(s0["mass_shifts"])).min() > 0
+    # given steps rule, not P.T and P.dt_initial; t_hist accumulates them
+    own = np.array([0.004, 0.013, 0.007])
+    phi, _, th = O2.forward(P, control=g["u"], dts=own)
+    assert phi.shape[0] == 4 and np.array_equal(th, np.concatenate([[0.0], np.cumsum(own)]))
+    assert relerr(phi[1], want[1]) > 1e-3
+    cut, _, tc = O2.forward(P, control=g["u"], dts=own, max_steps=2)
+    assert np.array_equal(cut, phi[:3]) and np.array_equal(tc, th[:3])
+
+
 def test_forward_stress():
     g = golden("g2d_forward_32_stress.npz")
     P = O2.Params2D(Nx=32, Ny=32, T=float(g["T"]), dt_initial=float(g["dt"]))
