@@ -282,11 +282,15 @@ def newton_step(phi_old, mu_old, w_old, w_new, dt, P, h, solver="dense", return_
 
 
 def forward(P: Params1D, control=None, initial_phi=None, seed=42, amp=0.01, solver="dense",
-            max_steps=None, stats=None):
+            max_steps=None, stats=None, dts=None):
     """F1:286-386.  History has M+2 rows: t=0 appears twice (F1:329-336).  Control rows
     (u[step], u[step+1]) while step < len(u)-1, else hold u[step] (F1:347-353; an array
     shorter than that raises IndexError as in the reference).  Post-step: clip, then a
-    uniform shift by mass_error/Lx, always (F1:361-366)."""
+    uniform shift by mass_error/Lx, always (F1:361-366).
+
+    `dts` (optional sequence): the march takes exactly these steps, whatever P.T and P.dt_initial say, and t_hist
+    accumulates them after the duplicated t = 0 row; None is the reference's rule dt = min(dt_initial, T - t) while
+    t < T - 1e-10."""
     N, h = int(P.N), P.Lx / int(P.N)
     x = np.linspace(0, P.Lx, N + 1)
     if initial_phi is not None and initial_phi.shape == (N + 1,):
@@ -301,10 +305,11 @@ def forward(P: Params1D, control=None, initial_phi=None, seed=42, amp=0.01, solv
     ts = [0.0, 0.0]
     hist = [phi.copy(), phi.copy()]
     zero = np.zeros(N + 1)
-    while t < P.T - 1e-10:
+    given = None if dts is None else [float(d) for d in dts]
+    while (t < P.T - 1e-10) if given is None else (step < len(given)):
         if max_steps is not None and step >= max_steps:
             break
-        dts = min(P.dt_initial, P.T - t)
+        dt = min(P.dt_initial, P.T - t) if given is None else given[step]
         if control is not None:
             if step < control.shape[0] - 1:
                 u_n, u_np1 = control[step, :], control[step + 1, :]
@@ -312,15 +317,15 @@ def forward(P: Params1D, control=None, initial_phi=None, seed=42, amp=0.01, solv
                 u_n = u_np1 = control[step, :]
         else:
             u_n = u_np1 = zero
-        w_new = w_filter(w, dts, P.gamma, u_n, u_np1)
-        pn, mn = newton_step(phi, mu, w, w_new, dts, P, h, solver=solver, stats=stats)
+        w_new = w_filter(w, dt, P.gamma, u_n, u_np1)
+        pn, mn = newton_step(phi, mu, w, w_new, dt, P, h, solver=solver, stats=stats)
         phi = np.clip(pn, -1 + DELTA_SEP, 1 - DELTA_SEP)
         mu, w = mn, w_new
         phi -= (np.dot(wts_h, phi) - mass0) / P.Lx
-        t += dts
+        t += dt
         step += 1
         hist.append(phi.copy())
-        ts.append(min(t, P.T))
+        ts.append(min(t, P.T) if given is None else t)
     return np.array(hist), x, np.array(ts)
 
 

@@ -60,13 +60,14 @@ def _tile(a, nb):
 class Problem:
     """One base point (grid, state history, control, targets) from which contexts of any batch are made."""
 
-    def __init__(self, V, P, t, dts, x, phi, u, opt):
+    def __init__(self, V, P, t, dts, x, phi, u, opt, max_steps=8):
         self.V, self.P, self.t, self.dts, self.x, self.phi, self.u, self.opt = V, P, t, np.asarray(dts), x, phi, u, opt
         self.M, self.shape = len(dts), u.shape
+        self.max_steps = max_steps                   # of the contexts made here: the march may be shorter
         self.phi_T, self.phi_Q = o.build_targets(x, t, phi[0], P.Lx, P.T)
 
     def context(self, nb):
-        return _engine(self.V, self.P, nb)
+        return _engine(self.V, self.P, nb, max_steps=self.max_steps)
 
     def kw(self, nb=0):
         """Keyword arguments of hessvec / hess_lanczos: a shared base (nb = 0) or the base tiled nb times."""

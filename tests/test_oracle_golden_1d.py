@@ -91,6 +91,33 @@ def test_forward_backward_cost(tag, solver):
     assert relerr(r0, g["r_none"]) < SOLVE
 
 
+@pytest.mark.parametrize("tag", ["64", "64_ragged"])
+def test_forward_over_given_steps_is_the_default_march(tag):
+    """forward(dts=time_grid(T, dt)[1]) takes the default march's steps: the same bits in the history and the time levels and
+    the same statistics (the 1D march records no wall time), with and without a control; other steps are taken as given,
+    under max_steps too."""
+    from oracle.vch2d_oracle import time_grid
+    g = golden(f"g1d_forward_{tag}.npz")
+    P = O1.Params1D(N=int(g["N"]), T=float(g["T"]), dt_initial=float(g["dt"]))
+    t, dts = time_grid(P.T, P.dt_initial)
+    for u in (None, g["u"]):
+        s0, s1 = {}, {}
+        want, _, t0 = O1.forward(P, control=u, solver="banded", stats=s0)
+        got, _, t1 = O1.forward(P, control=u, solver="banded", stats=s1, dts=dts)
+        assert np.array_equal(got, want) and np.array_equal(t1, t0) and np.array_equal(t0[1:], t) and t0[0] == 0.0
+        assert set(s0) == set(s1) and "exits" in s0
+        for k in s0:
+            assert np.array_equal(np.asarray(s0[k]), np.asarray(s1[k])), k
+    if tag == "64_ragged":
+        assert dts[-1] < dts[0]                                            # the last step of the default march is ragged
+    own = np.array([0.004, 0.013, 0.007])
+    phi, _, th = O1.forward(P, control=g["u"], solver="banded", dts=own)
+    assert phi.shape[0] == 5 and np.array_equal(th, np.concatenate([[0.0, 0.0], np.cumsum(own)]))
+    assert relerr(phi[2], want[2]) > 1e-3
+    cut, _, tc = O1.forward(P, control=g["u"], solver="banded", dts=own, max_steps=2)
+    assert np.array_equal(cut, phi[:4]) and np.array_equal(tc, th[:4])
+
+
 @pytest.mark.parametrize("tag", ["32", "32_bt"])
 def test_pgd(tag):
     g = golden(f"g1d_pgd_{tag}.npz")
