@@ -468,6 +468,7 @@ int vch2d_cg_vector(vch2d_ctx *ctx, int which /* 0: x, 1: r, 2: p */, double *ou
 #define VCH_NEWTON_BREAKDOWN 3
 #define VCH_NEWTON_STALLED 4
 #define VCH_NEWTON_IDLE 5
+#define VCH_NEWTON_REJECTED 6       /* vch1d_pgd_trust: the round's trial was rejected, the trajectory goes on */
 int vch2d_pgd_newton(vch2d_ctx *ctx, int n_rounds, int k, double cg_tol, int precond /* 0 | 1 */, double tol, double rtol,
                      int max_halvings, double *cost_out, double *cost_new_out, double *s_out, double *pred_out,
                      double *rnorm0_out /* [B][n_rounds] */, int32_t *halvings_out, int32_t *cg_steps_out,
@@ -858,6 +859,34 @@ int vch1d_hess_cg(vch1d_ctx *ctx, const double *phi_hist, const double *u, int n
                   double *resid_out /* [B][k] */, double *curv_out /* [B][k] */, double *pred_out /* [B] */,
                   double *rnorm0_out /* [B] */, int32_t *steps_out /* [B] */, int32_t *status_out /* [B] */,
                   int64_t *n_free_out /* [B] */, vch_stats *stats);
+/* Truncated (Steihaug-Toint) Newton-CG in a trust region on the free set of the 1D engine (ABI version stays 3:
+ * detect this entry point and vch1d_pgd_trust by symbol).  The arguments, base point, resident mode, mask, precond, outputs,
+ * looks, storage, invalidation rules and errors are those of vch1d_hess_cg, plus radius [B] and xnorm_out [B].  The region is
+ * ||x||_D <= radius_b in the preconditioner's norm, ||x||_D^2 = sum D x^2 with D = diag(wt'_k wx_i) for precond 1 and the
+ * identity for precond 0.  The iteration is vch1d_hess_cg's with xx = ||x||_D^2 and xp = x.D p kept by their recurrences
+ * (x_0 = 0: both start at 0), tau the positive root of xx + 2 tau xp + tau^2 pp = radius^2 (pp = p.D p).  At step j, after
+ * c = p.P H p:
+ *   c not finite: VCH_CG_BREAKDOWN, as vch1d_hess_cg;
+ *   !(c > 0): the step tau along p to the boundary, then VCH_CG_NEGCURV ("stepped to the boundary along a direction of
+ *     non-positive curvature"; at step 0, x = tau D^-1 P b).  With radius +inf there is no boundary: the call stops as
+ *     vch1d_hess_cg does, x the iterate before that direction;
+ *   the step rho / c would leave the region: the step tau to the boundary, then VCH_CG_BOUNDARY;
+ *   otherwise the step of vch1d_hess_cg, with its stop rules.
+ * A step to the boundary updates x and r as any step does (r = P b - P H P x stays true for vch1d_cg_vector), adds
+ * tau rho - tau^2 c / 2 to pred, writes resid[j] and counts in steps_out.  xnorm_out [B]: ||x||_D by the recurrence (0 for
+ * P b == 0).  With radius = +inf every output, x, r and p are bitwise those of vch1d_hess_cg on a trajectory that ends
+ * VCH_CG_CONVERGED or VCH_CG_LIMIT.  VCH_ERR_ARG, before anything is enqueued, for NULL radius or xnorm_out and a radius_b
+ * that is not > 0 (NaN included). */
+int vch1d_hess_cg_tr(vch1d_ctx *ctx, const double *phi_hist, const double *u, int n_base, int rows,
+                     const double *dt, const double *t_hist, const double *x,
+                     const double *phi_Q, const double *phi_T, const vch_opt_params *opts, int n_opts,
+                     const uint8_t *mask /* [n_base][rows][N+1] or NULL */, double tol,
+                     const double *rhs  /* [B][rows][N+1] or NULL */, int k, double cg_tol, int precond /* 0 | 1 */,
+                     double *resid_out /* [B][k] */, double *curv_out /* [B][k] */, double *pred_out /* [B] */,
+                     double *rnorm0_out /* [B] */, int32_t *steps_out /* [B] */, int32_t *status_out /* [B] */,
+                     int64_t *n_free_out /* [B] */, vch_stats *stats, const double *radius /* [B] */,
+                     double *xnorm_out /* [B] */);
+#define VCH_CG_BOUNDARY 4
 /* out = x (which 0), r (1) or p (2) of the last vch1d_hess_cg of this context; masked-off nodes are exact zeros.
  * VCH_ERR_STATE without resident vectors (no call yet, a failed call, or a vch1d_hess_lanczos since). */
 int vch1d_cg_vector(vch1d_ctx *ctx, int which /* 0: x, 1: r, 2: p */, double *out /* [B][rows][N+1] */);
@@ -908,6 +937,38 @@ int vch1d_pgd_newton(vch1d_ctx *ctx, int n_rounds, int k, double cg_tol, int pre
                      int32_t *cg_status_out, int32_t *status_out /* [B][n_rounds] */,
                      int64_t *counts_out /* [B][n_rounds][3]: n_free, pinned, clipped */,
                      double *seconds_out /* [4] or NULL: solves, trial kernel, marches, costs */);
+/* Trust-region (Steihaug) Newton-CG rounds on the free set about the resident PGD iterate of the 1D engine, batched, with
+ * every trajectory's own parameters, radius and decisions (ABI version stays 3: detect by symbol).  The
+ * checks, the stop quirk before round 0, the resident state afterwards and the untouched PGD counters are those of
+ * vch1d_pgd_newton; pgd_r_valid is cleared once anything moved.  Per round and live trajectory b, with radius Delta_b
+ * (radius0_b in round 0):
+ *   1. the solve of vch1d_hess_cg_tr in its resident mode (as step 1 of vch1d_pgd_newton) inside Delta_b.
+ *   2. VCH_NEWTON_STATIONARY (empty free set or ||P b|| == 0) and VCH_NEWTON_BREAKDOWN end the trajectory without a trial.
+ *      Every other CG exit, VCH_CG_NEGCURV included, gives a step x.
+ *   3. one trial at s = 1 (the trial of vch1d_pgd_newton: clip to the box, a free node with t u < 0 becomes 0), its march
+ *      and its cost J(t); rho = (J(u) - J(t)) / pred.
+ *   4. accepted iff J(t) is finite and J(t) <= J(u) - 1e-4 pred (the damped rounds' Armijo test at s = 1), copied as
+ *      vch1d_pgd_newton copies a trial: VCH_NEWTON_ACCEPTED.  Otherwise the trajectory stays unmoved: VCH_NEWTON_REJECTED,
+ *      and it goes on to the next round.
+ *   5. the radius: rho < 1/4 or not finite: Delta = min(Delta, ||x||_D) / 4; else rho > 3/4 after VCH_CG_BOUNDARY or
+ *      VCH_CG_NEGCURV: Delta = min(2 Delta, radius_max).  A Delta below radius_min ends the trajectory: a rejected one
+ *      with VCH_NEWTON_STALLED, an accepted one keeps VCH_NEWTON_ACCEPTED.
+ * An ended trajectory is VCH_NEWTON_IDLE in all later rounds, its doubles NaN, its integers 0; its solves are not gated (they
+ * run with its radius0).  The call returns the rounds run and stops early once every trajectory has ended.  Outputs, all
+ * required and [B][n_rounds]: cost (J(u) before the trial), cost_new (after the round), pred, rnorm0, radius (the round's
+ * Delta), ratio (rho; NaN without a trial), xnorm (||x||_D), cg_steps, cg_status (VCH_CG_*), status (VCH_NEWTON_*);
+ * counts_out [B][n_rounds][3] = {n_free, pinned, clipped of the trial}; seconds_out [4] or NULL = {solves, trial kernel,
+ * marches, costs}.  No atomics: a trajectory's outputs and its iterate are bitwise those of a single-trajectory context.
+ * Storage: that of vch1d_pgd_newton.  Errors, all before anything is enqueued, copied or allocated: VCH_ERR_STATE before
+ * vch1d_pgd_init / _init_v; VCH_ERR_ARG for n_rounds < 1, k < 1, precond outside 0 / 1, a cg_tol that is not finite, NULL
+ * radius0, a radius0_b, radius_max or radius_min that is not finite or not > 0, NULL outputs, and with precond 1 the
+ * time-weight check of vch1d_hess_cg. */
+int vch1d_pgd_trust(vch1d_ctx *ctx, int n_rounds, int k, double cg_tol, int precond /* 0 | 1 */, double tol,
+                    const double *radius0 /* [B] */, double radius_max, double radius_min,
+                    double *cost_out, double *cost_new_out, double *pred_out, double *rnorm0_out, double *radius_out,
+                    double *ratio_out, double *xnorm_out /* [B][n_rounds] */, int32_t *cg_steps_out, int32_t *cg_status_out,
+                    int32_t *status_out /* [B][n_rounds] */, int64_t *counts_out /* [B][n_rounds][3]: n_free, pinned, clipped */,
+                    double *seconds_out /* [4] or NULL: solves, trial kernel, marches, costs */);
 /* The trial kernel's seam, after any successful vch1d_hess_cg, stateless or resident: t = min(max(u + s_b x, u_min_b),
  * u_max_b) with u that call's base control (a shared base: one for the batch; NULL: zeros), x, the free set and the box the
  * ones it left resident; a free node with t u < 0 becomes 0.  Writes only the trial-control scratch (allocated on first use

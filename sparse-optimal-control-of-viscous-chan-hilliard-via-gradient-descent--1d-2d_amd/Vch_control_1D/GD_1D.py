@@ -183,7 +183,7 @@ def run_optimization_resident(fwd_config: ForwardSolverConfig, opt_config: Optim
 
 
 def run_sweep(fwd_config: ForwardSolverConfig, opt_configs, n_iter=None, seed=42, amp=0.01, initial_phi=None, choice_t=1,
-              choice_q=1, u0=None, return_controls=False, n_newton=0):
+              choice_q=1, u0=None, return_controls=False, n_newton=0, n_trust=0, radius0=1.0):
     """A parameter sweep as ONE batch: member b runs the PGD loop with opt_configs[b] (weights, sparsity parameter, box,
     alpha_max), all members from the same initial state (`initial_phi` (N+1,), else `seed`, `amp`) and targets, so that
     they differ by their parameters only.  `u0`: start control, one (rows, N+1) array for every member or one per member
@@ -194,7 +194,10 @@ def run_sweep(fwd_config: ForwardSolverConfig, opt_configs, n_iter=None, seed=42
     return_controls); the state history never leaves the device.  `n_newton` > 0 polishes every member after its PGD
     iterations by that many damped Newton rounds on its free set (Engine1D.pgd_newton, on the device) and adds `newton`
     (its records) and `costs_newton` [B][n_newton+1] (the cost before the first round, then after every round); kkt and u
-    are then those of the polished iterate.  0 leaves the result as it is without the polish."""
+    are then those of the polished iterate.  0 leaves the result as it is without the polish.  `n_trust` > 0 does the same
+    (after the Newton rounds, if both are asked for) with that many trust-region rounds from the radius `radius0`
+    (Engine1D.pgd_trust), which follow a direction of non-positive curvature instead of ending on it, and adds `trust` and
+    `costs_trust` [B][n_trust+1]."""
     from ..engine import Engine1D, time_grid
     from .Forward_solver import init_phi_random, delta_sep
     opt_configs = list(opt_configs)
@@ -224,16 +227,19 @@ def run_sweep(fwd_config: ForwardSolverConfig, opt_configs, n_iter=None, seed=42
         n = int(max(int(o.max_iter) for o in opt_configs) if n_iter is None else n_iter)
         res = eng.pgd_iterate(n)
         newton = eng.pgd_newton(int(n_newton)) if int(n_newton) > 0 else None
+        trust = eng.pgd_trust(int(n_trust), radius0) if int(n_trust) > 0 else None
         out = dict(costs=np.concatenate([J0[:, 4:5], res["cost"]], axis=1), alphas=res["alpha"], trials=res["trials"],
                    changes=res["change"], tracking_error=res["tracking_error"], terminal_error=res["terminal_error"],
                    iters=res["iters"], seconds=res["seconds"], kkt=eng.pgd_kkt(refresh=True), phi_T=phi_T, t_hist=t_hist,
                    x=x)
-        if newton is not None:
+        for name, rec in (("newton", newton), ("trust", trust)):
+            if rec is None:
+                continue
             # an idle round carries the cost the member ended with
-            cn = np.concatenate([newton["cost"][:, :1], newton["cost_new"]], axis=1)
+            cn = np.concatenate([rec["cost"][:, :1], rec["cost_new"]], axis=1)
             for r in range(1, cn.shape[1]):
                 cn[:, r] = np.where(np.isnan(cn[:, r]), cn[:, r - 1], cn[:, r])
-            out["newton"], out["costs_newton"] = newton, cn
+            out[name], out["costs_" + name] = rec, cn
         if return_controls:
             out["u"] = eng.pgd_get("u").reshape(B, len(t_hist), N + 1)
     finally:
@@ -333,6 +339,94 @@ def _newton_refine_device(fwd_config, opt_config, u, phi_Q_target, phi_T_target,
                             steps=int(R["cg_steps"][0, r]), status=Engine1D.CG_STATUS[int(R["cg_status"][0, r])],
                             s=None if np.isnan(s) else s, cost_new=float(R["cost_new"][0, r])))
     return eng.pgd_get("u"), records
+
+
+def trust_refine(fwd_config: ForwardSolverConfig, opt_config: OptimizationConfig, u, phi_Q_target, phi_T_target,
+                 n_rounds=3, radius0=1.0, k=50, cg_tol=1e-8, radius_max=None, radius_min=None, on_device=False):
+    """Rounds of a trust-region Newton method on the free set, from the control `u`: newton_refine with the damping
+    replaced by a radius.  Per round: the Steihaug step x of the full cost on the free set of the iterate inside
+    ||x||_D <= radius (Engine1D.hess_cg_trust: a direction of non-positive curvature is followed to the boundary instead
+    of ending the loop), one trial clip(u + x, box) with a flipped sign set to 0 (Engine1D.newton_trial(1)), its march
+    from the default start of `run_main_simulation` and its cost J(t); rho = (J(u) - J(t)) / pred.  The trial is accepted
+    iff J(t) is finite and J(t) <= J(u) - 1e-4 pred, else the iterate stays ("rejected") and the loop goes on.  The radius:
+    rho < 1/4 or not finite: min(radius, ||x||_D) / 4; else rho > 3/4 after a "boundary" or "negcurv" exit:
+    min(2 radius, radius_max).  The loop ends after `n_rounds` rounds, on a vanishing right-hand side ("stationary"), a
+    CG breakdown, or once the radius is below radius_min ("stalled" when that round was rejected).  radius_max /
+    radius_min default to 1024 radius0 and 1e-10 radius0.
+
+    Returns (u, records): one dict per round with cost, cost_new, pred, rnorm0, radius (the round's), ratio, xnorm,
+    steps, cg_status (a name of Engine1D.TRUST_CG_STATUS), status (a name of Engine1D.TRUST_STATUS), n_free.
+
+    on_device=True runs the rounds on the device (Engine1D.pgd_trust): one context, one pgd_init(u0=u) with this loop's
+    own start state and targets; the records have the same keys."""
+    from ..engine import Engine1D, time_grid
+    from ._ctx import engine_for_config
+    from .Forward_solver import init_phi_random, delta_sep
+    N = int(fwd_config.N)
+    tg, dts = time_grid(float(fwd_config.T), float(fwd_config.dt_initial))
+    t_hist = np.concatenate([[0.0], tg])
+    M = len(dts)
+    u = np.asarray(u, dtype=np.float64)[:M + 2]
+    radius = float(radius0)
+    radius_max = 1024.0 * radius if radius_max is None else float(radius_max)
+    radius_min = 1e-10 * radius if radius_min is None else float(radius_min)
+    phi0 = init_phi_random(N, delta_sep, amp=0.01, seed=42, enforce_zero_mean=True)
+    x = np.linspace(0.0, float(fwd_config.Lx), N + 1)
+    pq, pt = np.asarray(phi_Q_target, dtype=np.float64)[None, :M + 2], np.asarray(phi_T_target, dtype=np.float64)[None]
+    opt = make_opt(opt_config)
+    eng = engine_for_config(fwd_config, batch=1, max_steps=max(M, 1))
+    CGS, NTS = Engine1D.TRUST_CG_STATUS, Engine1D.TRUST_STATUS
+    if on_device:
+        eng.pgd_init(phi0[None], pt, t_hist, dts, [opt], phi_Q=pq, x=x, u0=u[None])
+        R = eng.pgd_trust(int(n_rounds), radius, k=k, cg_tol=cg_tol, radius_max=radius_max, radius_min=radius_min)
+        records = []
+        for r in range(int(R["rounds"])):
+            if NTS[int(R["status"][0, r])] == "idle":
+                break
+            records.append(dict(cost=float(R["cost"][0, r]), cost_new=float(R["cost_new"][0, r]), pred=float(R["pred"][0, r]),
+                                rnorm0=float(R["rnorm0"][0, r]), radius=float(R["radius"][0, r]), ratio=float(R["ratio"][0, r]),
+                                xnorm=float(R["xnorm"][0, r]), steps=int(R["cg_steps"][0, r]),
+                                cg_status=CGS[int(R["cg_status"][0, r])], status=NTS[int(R["status"][0, r])],
+                                n_free=int(R["n_free"][0, r])))
+        return eng.pgd_get("u").reshape(M + 2, N + 1), records
+
+    def full_cost(v):
+        phi, _ = eng.forward(phi0[None], dts, u=v[None], store=True)
+        J = eng.cost(phi.reshape((1, M + 2, N + 1)), v[None], pq, pt, x, t_hist, opt)
+        return float(np.atleast_2d(J)[0, 4])
+
+    cost = full_cost(u)
+    records = []
+    for _ in range(int(n_rounds)):
+        eng.forward(phi0[None], dts, u=np.ascontiguousarray(u[None]), store=False)
+        S = eng.hess_cg_trust(int(k), radius, t_hist, opt, cg_tol=cg_tol, u=np.ascontiguousarray(u[None]), phi_Q=pq, phi_T=pt,
+                              dt=dts, x=x)
+        st = int(S["status"][0])
+        rec = dict(cost=cost, cost_new=cost, pred=float(S["pred"][0]), rnorm0=float(S["rnorm0"][0]), radius=radius,
+                   ratio=float("nan"), xnorm=float(S["xnorm"][0]), steps=int(S["steps"][0]), cg_status=CGS[st], status="stationary",
+                   n_free=int(S["n_free"][0]))
+        records.append(rec)
+        if rec["n_free"] < 1 or rec["rnorm0"] == 0.0:
+            break
+        if CGS[st] == "breakdown":
+            rec["status"] = "breakdown"
+            break
+        trial = eng.newton_trial(1.0)["u"][0]
+        J = full_cost(trial)
+        with np.errstate(all="ignore"):
+            rho = rec["ratio"] = float((np.float64(cost) - np.float64(J)) / np.float64(rec["pred"]))
+        accept = bool(np.isfinite(J)) and J <= cost - 1e-4 * rec["pred"]
+        if not np.isfinite(rho) or rho < 0.25:
+            radius = 0.25 * min(radius, rec["xnorm"])
+        elif rho > 0.75 and CGS[st] in ("boundary", "negcurv"):
+            radius = min(2.0 * radius, radius_max)
+        small = radius < radius_min
+        rec["status"] = "accepted" if accept else ("stalled" if small else "rejected")
+        if accept:
+            u, cost, rec["cost_new"] = trial, J, J
+        if small:
+            break
+    return u, records
 
 
 def main(n_iter=None, params_file="last_run_config.json", control_file="optimal_control.npy", num_directions=3,

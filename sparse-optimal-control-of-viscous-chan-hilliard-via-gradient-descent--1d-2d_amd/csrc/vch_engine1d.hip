@@ -960,6 +960,7 @@ extern "C" int vch1d_hessvec(vch1d_ctx *c, const double *phi_hist, const double 
 struct Kr1Layout {
     size_t part, coef1, coef2, ucoef, alpha, beta, look, scal, amax, lim, stop, steps, box, wt, mean, wtp, ks, total;
     size_t ntpart, nts, ntsum;      // vch1d_newton_trial: its partials [B][chunks][4], the step table [B], the sums [B][4]
+    size_t tr;                      // vch1d_hess_cg_tr: [6][B] = radius, xx, xp, pp, c, the pending exit
 };
 static int kr1_chunks(const vch1d_ctx *c, int rows) { return (int)(((long)rows * c->n + KR1_CHUNK - 1) / KR1_CHUNK); }
 static Kr1Layout kr1_layout(const vch1d_ctx *c, int S, int K) {
@@ -987,6 +988,7 @@ static Kr1Layout kr1_layout(const vch1d_ctx *c, int S, int K) {
     L.ntpart = take(B * kr1_chunks(c, (int)R) * 4);
     L.nts = take(B);
     L.ntsum = take(4 * B);
+    L.tr = take(6 * B);
     L.total = at;
     return L;
 }
@@ -1230,11 +1232,14 @@ static Ncg1Args ncg1_args(const vch1d_ctx *c, const Kr1Layout &L, int rows, long
 // empty_ok (the Newton rounds): a trajectory with an empty free set is no error.  The set-up returns for it before it
 // writes x, r, p and its cells, so the host takes n_free = 0 from the look alone: zero steps, VCH_CG_CONVERGED,
 // pred = rnorm0 = 0, none of the stale cells read, and its three slots zeroed for vch1d_cg_vector.
+// radius (or NULL): the trust region of vch1d_hess_cg_tr, k1d_ncg_fin_tr in place of k1d_ncg_fin and xnorm_out [B] = ||x||_D
+// by the recurrence (0 for an empty free set); NULL runs the launches of vch1d_hess_cg exactly.
 static int hess_cg1_core(vch1d_ctx *c, const char *fn, bool empty_ok, const double *phi_hist, const double *u, int n_base, int rows,
                          const double *dt, const double *t_hist, const double *x, const double *phi_Q, const double *phi_T,
                          const vch_opt_params *opts, int n_opts, const uint8_t *mask, double tol, const double *rhs, int k,
                          double cg_tol, int precond, double *resid_out, double *curv_out, double *pred_out, double *rnorm0_out,
-                         int32_t *steps_out, int32_t *status_out, int64_t *n_free_out, vch_stats *stats) {
+                         int32_t *steps_out, int32_t *status_out, int64_t *n_free_out, vch_stats *stats,
+                         const double *radius = nullptr, double *xnorm_out = nullptr) {
     const int B = c->B, n = c->n;
     VCHCHK(so1_check_shape(c, fn, n_base, rows, n_opts, 2));
     if (!resid_out || !curv_out || !pred_out || !rnorm0_out || !steps_out || !status_out || !n_free_out)
@@ -1242,6 +1247,10 @@ static int hess_cg1_core(vch1d_ctx *c, const char *fn, bool empty_ok, const doub
     if (k < 1) return vch_fail(VCH_ERR_ARG, "%s: k = %d must be >= 1", fn, k);
     if (precond != 0 && precond != 1) return vch_fail(VCH_ERR_ARG, "%s: precond = %d is neither 0 nor 1", fn, precond);
     if (!std::isfinite(cg_tol)) return vch_fail(VCH_ERR_ARG, "%s: cg_tol must be finite", fn);
+    if (radius)
+        for (int b = 0; b < B; ++b)
+            if (!(radius[b] > 0.0))
+                return vch_fail(VCH_ERR_ARG, "%s: trajectory %d: radius %g must be > 0 (+inf allowed, NaN not)", fn, b, radius[b]);
     const int M = rows - 2;
     const long hs = hs1(c);
     Kr1Call C;
@@ -1254,6 +1263,12 @@ static int hess_cg1_core(vch1d_ctx *c, const char *fn, bool empty_ok, const doub
     const dim3 kgrid(nch, B);
     const double stop_at = cg_tol > 0 ? cg_tol : 1e-8;
     C.G.hd = c->kr_Q + (long)NCG1_P * B * hs;
+    double *tr = sc + L.tr;
+    const Ntr1Cells tcells{tr, tr + B, tr + 2 * B, tr + 3 * B, tr + 4 * B, (long long *)(tr + 5 * B)};
+    if (radius) {
+        VCHCHK(up(c, tr, radius, B));
+        HIPCHK(hipMemsetAsync(tr + B, 0, sizeof(double) * 5 * B, c->stream));     // xx = xp = 0 (x_0 = 0), nothing pending
+    }
     // the set-up: the free set, the gradient sweep once per base point (yp of every step stays in kr_X), r = P b, x, p
     double *keepX = c->kr_nocache ? nullptr : c->kr_X;
     if (rhs)
@@ -1281,13 +1296,17 @@ static int hess_cg1_core(vch1d_ctx *c, const char *fn, bool empty_ok, const doub
         VCHCHK(kr1_step(c, rows, C.G, cells.stop));
         // w = H p in kr_W
         LAUNCH(k1d_ncg_curv, kgrid, dim3(KR1_T), K, (const double *)c->kr_W, part);
-        LAUNCH(k1d_ncg_fin, dim3(B), dim3(KR1_T), cells, (const double *)part, nch, S, 2, j, k, stop_at);
+        if (radius) LAUNCH(k1d_ncg_fin_tr, dim3(B), dim3(KR1_T), cells, tcells, (const double *)part, nch, S, 2, j, k, stop_at);
+        else LAUNCH(k1d_ncg_fin, dim3(B), dim3(KR1_T), cells, (const double *)part, nch, S, 2, j, k, stop_at);
         LAUNCH(k1d_ncg_update, kgrid, dim3(KR1_T), K, (const double *)c->kr_W, part);
-        LAUNCH(k1d_ncg_fin, dim3(B), dim3(KR1_T), cells, (const double *)part, nch, S, 3, j, k, stop_at);
+        if (radius) LAUNCH(k1d_ncg_fin_tr, dim3(B), dim3(KR1_T), cells, tcells, (const double *)part, nch, S, 3, j, k, stop_at);
+        else LAUNCH(k1d_ncg_fin, dim3(B), dim3(KR1_T), cells, (const double *)part, nch, S, 3, j, k, stop_at);
         if (j + 1 < k) LAUNCH(k1d_ncg_dir, kgrid, dim3(KR1_T), K);
     }
     HIPCHK(hipEventRecord(c->ev1, c->stream));
     std::vector<long long> steps(B), prods(B), stop(B);
+    std::vector<double> xx(radius ? B : 0);
+    if (radius) HIPCHK(hipMemcpyAsync(xx.data(), tcells.xx, sizeof(double) * B, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(resid_out, cells.resid, sizeof(double) * B * k, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(curv_out, cells.curv, sizeof(double) * B * k, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(pred_out, cells.pred, sizeof(double) * B, hipMemcpyDeviceToHost, c->stream));
@@ -1303,8 +1322,10 @@ static int hess_cg1_core(vch1d_ctx *c, const char *fn, bool empty_ok, const doub
             status_out[b] = VCH_CG_CONVERGED;
             n_free_out[b] = 0;
             pred_out[b] = rnorm0_out[b] = 0.0;
+            if (radius) xnorm_out[b] = 0.0;
             continue;
         }
+        if (radius) xnorm_out[b] = std::sqrt(xx[b]);
         steps_out[b] = (int32_t)steps[b];
         status_out[b] = (int32_t)stop[b];           // 0: still running after k steps, VCH_CG_LIMIT
         n_free_out[b] = (int64_t)look[2 * b];
@@ -1329,6 +1350,20 @@ extern "C" int vch1d_hess_cg(vch1d_ctx *c, const double *phi_hist, const double 
     CTXCHK(c);
     return hess_cg1_core(c, "vch1d_hess_cg", false, phi_hist, u, n_base, rows, dt, t_hist, x, phi_Q, phi_T, opts, n_opts, mask, tol, rhs,
                          k, cg_tol, precond, resid_out, curv_out, pred_out, rnorm0_out, steps_out, status_out, n_free_out, stats);
+}
+
+extern "C" int vch1d_hess_cg_tr(vch1d_ctx *c, const double *phi_hist, const double *u, int n_base, int rows, const double *dt,
+                                const double *t_hist, const double *x, const double *phi_Q, const double *phi_T,
+                                const vch_opt_params *opts, int n_opts, const uint8_t *mask, double tol, const double *rhs, int k,
+                                double cg_tol, int precond, double *resid_out, double *curv_out, double *pred_out,
+                                double *rnorm0_out, int32_t *steps_out, int32_t *status_out, int64_t *n_free_out, vch_stats *stats,
+                                const double *radius, double *xnorm_out) {
+    CTXCHK(c);
+    const char *fn = "vch1d_hess_cg_tr";
+    if (!radius || !xnorm_out) return vch_fail(VCH_ERR_ARG, "%s: NULL radius or xnorm_out", fn);
+    return hess_cg1_core(c, fn, false, phi_hist, u, n_base, rows, dt, t_hist, x, phi_Q, phi_T, opts, n_opts, mask, tol, rhs, k, cg_tol,
+                         precond, resid_out, curv_out, pred_out, rnorm0_out, steps_out, status_out, n_free_out, stats, radius,
+                         xnorm_out);
 }
 
 extern "C" int vch1d_cg_vector(vch1d_ctx *c, int which, double *out) {
@@ -1380,6 +1415,103 @@ extern "C" int vch1d_newton_trial(vch1d_ctx *c, const double *s, double *u_out, 
     return u_out ? down_hist(c, u_out, c->u_trial, c->ncg_rows) : 0;
 }
 
+// The engine's side of the Newton and trust-region rounds (vch_newton.h) about the resident PGD iterate; sec = {solves, trial
+// controls, marches, costs}.
+struct Pgd1Rounds {
+    vch1d_ctx *c;
+    const char *fn;
+    int rows, k, precond;
+    double cg_tol, tol;
+    std::vector<double> resid, curv, Jt;
+    std::vector<int> bad;
+    double sec[4];
+    double lap() {
+        float ms = 0;
+        hipEventSynchronize(c->ev1);
+        hipEventElapsedTime(&ms, c->ev0, c->ev1);
+        return (double)ms * 1e-3;
+    }
+    // The stop quirk: a trajectory the PGD stop rule ended holds the new control beside the previous iterate's state and
+    // cost (G1:462-465).  One march of the resident control, the others sitting it out, brings both up to the control.
+    int stop_quirk() {
+        const int B = c->B;
+        std::vector<int> sit(B);
+        bool stale = false;
+        for (int b = 0; b < B; ++b) {
+            sit[b] = !(c->pgd.done[b] && !c->pgd_synced[b]);
+            stale = stale || !sit[b];
+        }
+        if (!stale) return 0;
+        HIPCHK(hipEventRecord(c->ev0, c->stream));
+        HIPCHK(hipMemcpyAsync(c->skip_dev, sit.data(), sizeof(int) * B, hipMemcpyHostToDevice, c->stream));
+        VCHCHK(fwd1_core(c, c->u_hist, rows, c->phi_trial, c->skip_dev));
+        HIPCHK(hipEventRecord(c->ev1, c->stream));
+        sec[2] += lap();
+        HIPCHK(hipEventRecord(c->ev0, c->stream));
+        VCHCHK(cost1_core(c, c->phi_trial, c->u_hist, rows, Jt.data()));
+        HIPCHK(hipEventRecord(c->ev1, c->stream));
+        sec[3] += lap();
+        for (int b = 0; b < B; ++b) {
+            if (sit[b]) continue;
+            VCHCHK(copy_traj1(c, c->phi_hist, c->phi_trial, b, rows));
+            c->pgd.cost[b] = Jt[5 * b + 4];
+            c->pgd_synced[b] = 1;
+        }
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return 0;
+    }
+    int solve(double *pred, double *rnorm0, int32_t *steps, int32_t *status, int64_t *n_free) {
+        vch_stats st;
+        VCHCHK(hess_cg1_core(c, fn, true, nullptr, VCH_RESIDENT, c->B, rows, c->dt_host.data(), c->t_host.data(), c->x_host.data(),
+                             VCH_RESIDENT, VCH_RESIDENT, c->opts.data(), c->B, nullptr, tol, nullptr, k, cg_tol, precond, resid.data(),
+                             curv.data(), pred, rnorm0, steps, status, n_free, &st));
+        sec[0] += st.seconds;
+        return 0;
+    }
+    // the trust-region rounds: the Steihaug solve inside radius [B]
+    int solve(const double *radius, double *pred, double *rnorm0, int32_t *steps, int32_t *status, int64_t *n_free, double *xnorm) {
+        vch_stats st;
+        VCHCHK(hess_cg1_core(c, fn, true, nullptr, VCH_RESIDENT, c->B, rows, c->dt_host.data(), c->t_host.data(), c->x_host.data(),
+                             VCH_RESIDENT, VCH_RESIDENT, c->opts.data(), c->B, nullptr, tol, nullptr, k, cg_tol, precond, resid.data(),
+                             curv.data(), pred, rnorm0, steps, status, n_free, &st, radius, xnorm));
+        sec[0] += st.seconds;
+        return 0;
+    }
+    // the trust-region rounds' one trial at s = 1
+    int trial(const std::vector<int> &decided, double *sums, double *c_new) {
+        return trial(decided, std::vector<double>(c->B, 1.0), sums, c_new);
+    }
+    double cost(int b) const { return c->pgd.cost[b]; }
+    int trial(const std::vector<int> &decided, const std::vector<double> &s, double *sums, double *c_new) {
+        HIPCHK(hipEventRecord(c->ev0, c->stream));
+        HIPCHK(hipMemcpyAsync(c->skip_dev, decided.data(), sizeof(int) * c->B, hipMemcpyHostToDevice, c->stream));
+        VCHCHK(newton_trial1_core(c, s.data(), c->skip_dev, sums));
+        HIPCHK(hipEventRecord(c->ev1, c->stream));
+        sec[1] += lap();
+        HIPCHK(hipEventRecord(c->ev0, c->stream));
+        VCHCHK(fwd1_core(c, c->u_trial, rows, c->phi_trial, c->skip_dev, bad.data()));
+        HIPCHK(hipEventRecord(c->ev1, c->stream));
+        sec[2] += lap();
+        HIPCHK(hipEventRecord(c->ev0, c->stream));
+        VCHCHK(cost1_core(c, c->phi_trial, c->u_trial, rows, Jt.data()));
+        HIPCHK(hipEventRecord(c->ev1, c->stream));
+        sec[3] += lap();
+        // a march that reported a non-finite mass defect: the trial counts as not accepted
+        for (int b = 0; b < c->B; ++b) c_new[b] = bad[b] ? std::nan("") : Jt[5 * b + 4];
+        return 0;
+    }
+    int accept(int b, double c_new) {
+        c->pgd.cost[b] = c_new;
+        VCHCHK(copy_traj1(c, c->u_hist, c->u_trial, b, rows));
+        return copy_traj1(c, c->phi_hist, c->phi_trial, b, rows);
+    }
+    int after_trial() {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return 0;
+    }
+    int after_round() { return 0; }
+};
+
 extern "C" int vch1d_pgd_newton(vch1d_ctx *c, int n_rounds, int k, double cg_tol, int precond, double tol, int max_halvings,
                                 double *cost_out, double *cost_new_out, double *s_out, double *pred_out, double *rnorm0_out,
                                 int32_t *halvings_out, int32_t *cg_steps_out, int32_t *cg_status_out, int32_t *status_out,
@@ -1399,92 +1531,45 @@ extern "C" int vch1d_pgd_newton(vch1d_ctx *c, int n_rounds, int k, double cg_tol
                               VCH_RESIDENT, c->opts.data(), B, dts, wts));
         VCHCHK(ncg1_weights(fn, c->t_host.data(), rows, precond, wt, wtp));
     }
-    // the engine's side of the rounds (vch_newton.h); sec = {solves, trial controls, marches, costs}
-    struct Rounds {
-        vch1d_ctx *c;
-        const char *fn;
-        int rows, k, precond;
-        double cg_tol, tol;
-        std::vector<double> resid, curv, Jt;
-        std::vector<int> bad;
-        double sec[4];
-        double lap() {
-            float ms = 0;
-            hipEventSynchronize(c->ev1);
-            hipEventElapsedTime(&ms, c->ev0, c->ev1);
-            return (double)ms * 1e-3;
-        }
-        // The stop quirk: a trajectory the PGD stop rule ended holds the new control beside the previous iterate's state and
-        // cost (G1:462-465).  One march of the resident control, the others sitting it out, brings both up to the control.
-        int stop_quirk() {
-            const int B = c->B;
-            std::vector<int> sit(B);
-            bool stale = false;
-            for (int b = 0; b < B; ++b) {
-                sit[b] = !(c->pgd.done[b] && !c->pgd_synced[b]);
-                stale = stale || !sit[b];
-            }
-            if (!stale) return 0;
-            HIPCHK(hipEventRecord(c->ev0, c->stream));
-            HIPCHK(hipMemcpyAsync(c->skip_dev, sit.data(), sizeof(int) * B, hipMemcpyHostToDevice, c->stream));
-            VCHCHK(fwd1_core(c, c->u_hist, rows, c->phi_trial, c->skip_dev));
-            HIPCHK(hipEventRecord(c->ev1, c->stream));
-            sec[2] += lap();
-            HIPCHK(hipEventRecord(c->ev0, c->stream));
-            VCHCHK(cost1_core(c, c->phi_trial, c->u_hist, rows, Jt.data()));
-            HIPCHK(hipEventRecord(c->ev1, c->stream));
-            sec[3] += lap();
-            for (int b = 0; b < B; ++b) {
-                if (sit[b]) continue;
-                VCHCHK(copy_traj1(c, c->phi_hist, c->phi_trial, b, rows));
-                c->pgd.cost[b] = Jt[5 * b + 4];
-                c->pgd_synced[b] = 1;
-            }
-            HIPCHK(hipStreamSynchronize(c->stream));
-            return 0;
-        }
-        int solve(double *pred, double *rnorm0, int32_t *steps, int32_t *status, int64_t *n_free) {
-            vch_stats st;
-            VCHCHK(hess_cg1_core(c, fn, true, nullptr, VCH_RESIDENT, c->B, rows, c->dt_host.data(), c->t_host.data(), c->x_host.data(),
-                                 VCH_RESIDENT, VCH_RESIDENT, c->opts.data(), c->B, nullptr, tol, nullptr, k, cg_tol, precond, resid.data(),
-                                 curv.data(), pred, rnorm0, steps, status, n_free, &st));
-            sec[0] += st.seconds;
-            return 0;
-        }
-        double cost(int b) const { return c->pgd.cost[b]; }
-        int trial(const std::vector<int> &decided, const std::vector<double> &s, double *sums, double *c_new) {
-            HIPCHK(hipEventRecord(c->ev0, c->stream));
-            HIPCHK(hipMemcpyAsync(c->skip_dev, decided.data(), sizeof(int) * c->B, hipMemcpyHostToDevice, c->stream));
-            VCHCHK(newton_trial1_core(c, s.data(), c->skip_dev, sums));
-            HIPCHK(hipEventRecord(c->ev1, c->stream));
-            sec[1] += lap();
-            HIPCHK(hipEventRecord(c->ev0, c->stream));
-            VCHCHK(fwd1_core(c, c->u_trial, rows, c->phi_trial, c->skip_dev, bad.data()));
-            HIPCHK(hipEventRecord(c->ev1, c->stream));
-            sec[2] += lap();
-            HIPCHK(hipEventRecord(c->ev0, c->stream));
-            VCHCHK(cost1_core(c, c->phi_trial, c->u_trial, rows, Jt.data()));
-            HIPCHK(hipEventRecord(c->ev1, c->stream));
-            sec[3] += lap();
-            // a march that reported a non-finite mass defect: the trial counts as not accepted
-            for (int b = 0; b < c->B; ++b) c_new[b] = bad[b] ? std::nan("") : Jt[5 * b + 4];
-            return 0;
-        }
-        int accept(int b, double c_new) {
-            c->pgd.cost[b] = c_new;
-            VCHCHK(copy_traj1(c, c->u_hist, c->u_trial, b, rows));
-            return copy_traj1(c, c->phi_hist, c->phi_trial, b, rows);
-        }
-        int after_trial() {
-            HIPCHK(hipStreamSynchronize(c->stream));
-            return 0;
-        }
-        int after_round() { return 0; }
-    } eng{c, fn, rows, k, precond, cg_tol, tol, std::vector<double>((size_t)B * k), std::vector<double>((size_t)B * k),
-          std::vector<double>(5 * (size_t)B), std::vector<int>(B), {0, 0, 0, 0}};
+    // the engine's side of the rounds (vch_newton.h)
+    Pgd1Rounds eng{c, fn, rows, k, precond, cg_tol, tol, std::vector<double>((size_t)B * k), std::vector<double>((size_t)B * k),
+                   std::vector<double>(5 * (size_t)B), std::vector<int>(B), {0, 0, 0, 0}};
     VCHCHK(eng.stop_quirk());
     bool moved = false;
     const int rc = vch_newton_rounds(eng, call, moved);
+    if (moved) c->pgd_r_valid = false;      // r_hist is the adjoint of an iterate that has been replaced
+    if (rc >= 0 && seconds_out) memcpy(seconds_out, eng.sec, sizeof(eng.sec));
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------
+// Trust-region (Steihaug) Newton-CG rounds on the free set about the resident PGD iterate (kernels: k1d_ncg_fin_tr in
+// vch_kernels1d.h, verdicts: vch_trust_state in vch_newton.h)
+// ------------------------------------------------------------------------------------
+extern "C" int vch1d_pgd_trust(vch1d_ctx *c, int n_rounds, int k, double cg_tol, int precond, double tol, const double *radius0,
+                               double radius_max, double radius_min, double *cost_out, double *cost_new_out, double *pred_out,
+                               double *rnorm0_out, double *radius_out, double *ratio_out, double *xnorm_out, int32_t *cg_steps_out,
+                               int32_t *cg_status_out, int32_t *status_out, int64_t *counts_out, double *seconds_out) {
+    CTXCHK(c);
+    const char *fn = "vch1d_pgd_trust";
+    // everything below is checked before anything is enqueued, copied or allocated
+    if (!c->pgd_ready) return vch_fail(VCH_ERR_STATE, "%s: call vch1d_pgd_init first", fn);
+    const int B = c->B, rows = c->pgd_rows;
+    const vch_trust_call call{B, n_rounds, k, cg_tol, precond, radius0, radius_max, radius_min, cost_out, cost_new_out, pred_out,
+                              rnorm0_out, radius_out, ratio_out, xnorm_out, cg_steps_out, cg_status_out, status_out, counts_out};
+    if (const char *bad = vch_trust_check(call)) return vch_fail(VCH_ERR_ARG, "%s: %s", fn, bad);
+    {   // what the solve of a round checks, here as well: the stop quirk below marches before the first solve
+        std::vector<double> dts, wts, wt, wtp;
+        VCHCHK(so1_check_shape(c, fn, B, rows, B, 2));
+        VCHCHK(so1_check_rest(c, fn, nullptr, VCH_RESIDENT, rows, c->dt_host.data(), c->t_host.data(), c->x_host.data(), VCH_RESIDENT,
+                              VCH_RESIDENT, c->opts.data(), B, dts, wts));
+        VCHCHK(ncg1_weights(fn, c->t_host.data(), rows, precond, wt, wtp));
+    }
+    Pgd1Rounds eng{c, fn, rows, k, precond, cg_tol, tol, std::vector<double>((size_t)B * k), std::vector<double>((size_t)B * k),
+                   std::vector<double>(5 * (size_t)B), std::vector<int>(B), {0, 0, 0, 0}};
+    VCHCHK(eng.stop_quirk());
+    bool moved = false;
+    const int rc = vch_trust_rounds(eng, call, moved);
     if (moved) c->pgd_r_valid = false;      // r_hist is the adjoint of an iterate that has been replaced
     if (rc >= 0 && seconds_out) memcpy(seconds_out, eng.sec, sizeof(eng.sec));
     return rc;

@@ -1736,6 +1736,91 @@ __global__ __launch_bounds__(KR1_T) void k1d_ncg_fin(Ncg1Cells x, const double *
 }
 
 // ---------------------------------------------------------------------------------
+// Truncated (Steihaug-Toint) conjugate gradients in a trust region (vch1d_hess_cg_tr): the iteration above
+// with k1d_ncg_fin_tr in place of k1d_ncg_fin, every other kernel unchanged.  The region is ||x||_D <= radius with the
+// preconditioner's D (the identity without it).  Since x_0 = 0, the recurrences xx = ||x||_D^2 and xp = x.D p start at 0:
+//   x' = x + alpha p:   xx' = xx + 2 alpha xp + alpha^2 pp
+//   p' = D^-1 r' + beta p, x'.r' = 0:   xp' = beta (xp + alpha pp)
+// tau = the positive root of xx + 2 tau xp + tau^2 pp = radius^2.  An exit on the boundary is pending between mode 2 and
+// mode 3, so that k1d_ncg_update runs once more with alpha = tau and r stays P b - P H P x.
+// ---------------------------------------------------------------------------------
+enum { NCG1_BOUNDARY = 4 };                     // VCH_CG_BOUNDARY of vch.h
+struct Ntr1Cells {
+    const double *radius;             // [B]
+    double *xx, *xp, *pp, *c;         // [B] ||x||_D^2, x.D p, p.D p and p.P H p of the step
+    long long *pend;                  // [B] the exit mode 3 takes: 0, NCG1_NEGCURV or NCG1_BOUNDARY
+};
+// tau >= 0 with xx + 2 tau xp + tau^2 pp = d2 (xx <= d2, pp > 0), in the form without cancellation for either sign of xp
+__device__ __forceinline__ double ntr1_tau(double xx, double xp, double pp, double d2) {
+    const double gap = fmax(d2 - xx, 0.0), disc = sqrt(xp * xp + pp * gap);
+    return xp > 0.0 ? gap / (xp + disc) : (disc - xp) / pp;
+}
+// mode 2   as k1d_ncg_fin, then: c not finite: BREAKDOWN; !(c > 0): alpha = tau, pending NEGCURV; the step rho / c would
+//          leave the region (xx + 2 alpha xp + alpha^2 pp >= radius^2): alpha = tau, pending BOUNDARY; otherwise alpha = rho / c.
+//          A tau that is not finite (radius = +inf on a direction of non-positive curvature) stops at once with NEGCURV as
+//          k1d_ncg_fin does: x stays as it is.
+// mode 3   pending: pred += tau rho - tau^2 c / 2, resid[j], steps = j + 1, xx by its recurrence, stop = the pending exit;
+//          otherwise k1d_ncg_fin's arithmetic, then xx and (still running) xp by their recurrences.
+__global__ __launch_bounds__(KR1_T) void k1d_ncg_fin_tr(Ncg1Cells x, Ntr1Cells t, const double *__restrict__ part, int nch, int S,
+                                                        int mode, int j, int k, double cg_tol) {
+    __shared__ double sh[KR1_T];
+    const int b = blockIdx.x;
+    const double *p = part + (long)b * nch * S;
+    if (x.stop[b]) return;                  // uniform: stopped at an earlier step
+    const double s0 = ncg1_sum(p, nch, S, 0, sh), s1 = ncg1_sum(p, nch, S, 1, sh);
+    if (threadIdx.x != 0) return;
+    long long st = NCG1_RUNNING;
+    const double xx = t.xx[b], xp = t.xp[b];
+    if (mode == 2) {
+        x.curv[(long)b * k + j] = s0 / s1;
+        x.prods[b] = j + 1;
+        long long pend = NCG1_RUNNING;
+        if (!isfinite(s0)) {
+            st = NCG1_BREAKDOWN;
+        } else {
+            const double rad = t.radius[b], d2 = rad * rad;
+            double al = 0.0;
+            if (!(s0 > 0.0)) {
+                pend = NCG1_NEGCURV;
+            } else {
+                al = x.rho[b] / s0;
+                if (xx + 2.0 * al * xp + al * al * s1 >= d2) pend = NCG1_BOUNDARY;
+            }
+            if (pend) al = ntr1_tau(xx, xp, s1, d2);
+            if (pend && !isfinite(al)) {
+                st = NCG1_NEGCURV;
+                pend = NCG1_RUNNING;
+            } else {
+                x.alpha[b] = al;
+            }
+        }
+        t.pp[b] = s1;
+        t.c[b] = s0;
+        t.pend[b] = pend;
+    } else {
+        const long long pend = t.pend[b];
+        const double rho = x.rho[b], res = sqrt(s0) / x.rnorm0[b], al = x.alpha[b], pp = t.pp[b];
+        x.resid[(long)b * k + j] = res;
+        x.steps[b] = j + 1;
+        if (pend) {
+            x.pred[b] += al * rho - 0.5 * (al * al) * t.c[b];
+            st = pend;
+        } else {
+            x.pred[b] += 0.5 * x.alpha[b] * rho;
+            if (!isfinite(res) || !isfinite(s1)) st = NCG1_BREAKDOWN;
+            else if (res <= cg_tol) st = NCG1_CONVERGED;
+            else {
+                x.beta[b] = s1 / rho;
+                x.rho[b] = s1;
+            }
+        }
+        t.xx[b] = xx + 2.0 * al * xp + al * al * pp;
+        if (st == NCG1_RUNNING) t.xp[b] = x.beta[b] * (xp + al * pp);
+    }
+    x.stop[b] = st;
+}
+
+// ---------------------------------------------------------------------------------
 // Damped Newton rounds on the free set (vch1d_pgd_newton, vch1d_newton_trial): the trial control of a step
 // length, on the streaming grid of the Newton-CG kernels above (chunks of KR1_CHUNK nodes, B) with their indexing: node i of
 // trajectory b sits at b hs + i, hs the stride of a history of max_steps + 2 rows, not rows n.  x is slot NCG1_X, the mask

@@ -152,3 +152,154 @@ int vch_newton_rounds(E &eng, const vch_newton_call &a, bool &moved) {
     }
     return done_rounds;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Trust-region rounds (vch1d_pgd_trust): one trial per round at s = 1 of the Steihaug step inside the radius,
+// the damped rounds' Armijo test at s = 1 for acceptance, the ratio rho = (J(u) - J(t)) / pred for the radius.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr double VCH_TRUST_SHRINK_BELOW = 0.25;     // rho below (or not finite): radius = 1/4 min(radius, ||x||_D)
+constexpr double VCH_TRUST_GROW_ABOVE = 0.75;       // rho above and the step ended on the boundary: radius = min(2 radius, max)
+
+struct vch_trust_state {
+    std::vector<int> ended;         // per trajectory: ended in an earlier round or in this one, sits out all later rounds
+    std::vector<double> radius;     // the radius of the next solve
+    std::vector<double> radius0;
+
+    void reset(const double *r0, int B) {
+        ended.assign(B, 0);
+        radius0.assign(r0, r0 + B);
+        radius = radius0;
+    }
+    bool any_live() const { return std::find(ended.begin(), ended.end(), 0) != ended.end(); }
+    bool idle(int b) const { return ended[b] != 0; }
+    // the radius b's solve runs with: an ended trajectory's solve is not gated and gets its first radius, which passes the
+    // solve's check whatever the rounds did to its own
+    double solve_radius(int b) const { return ended[b] ? radius0[b] : radius[b]; }
+    // Trajectory b after the round's solve: VCH_NEWTON_STATIONARY (empty free set or ||P b|| == 0) or VCH_NEWTON_BREAKDOWN
+    // end it without a trial; otherwise VCH_NEWTON_ACCEPTED, pending: x is the step to try, whatever the CG exit.
+    int after_solve(int b, long long n_free, double rnorm0, int cg_status) {
+        int st = VCH_NEWTON_ACCEPTED;
+        if (n_free < 1 || rnorm0 == 0.0) st = VCH_NEWTON_STATIONARY;
+        else if (cg_status == VCH_CG_BREAKDOWN) st = VCH_NEWTON_BREAKDOWN;
+        if (st != VCH_NEWTON_ACCEPTED) ended[b] = 1;
+        return st;
+    }
+    // b's trial: `cost` the iterate's, `pred` the model's decrease, `c_new` the trial's, `xnorm` ||x||_D, `cg_status` the CG
+    // exit.  Accepted iff c_new is finite and c_new <= cost - 1e-4 pred.  The radius: rho < 1/4 or not finite: 1/4 min(radius,
+    // xnorm); else rho > 3/4 after VCH_CG_BOUNDARY or VCH_CG_NEGCURV: min(2 radius, radius_max).  A radius below radius_min
+    // ends the trajectory: VCH_NEWTON_STALLED after a rejection (unmoved), VCH_NEWTON_ACCEPTED after an acceptance.
+    // Otherwise a rejected trajectory is VCH_NEWTON_REJECTED, unmoved, and goes on.  ratio: rho.
+    int judge(int b, double cost, double pred, double c_new, double xnorm, int cg_status, double radius_max, double radius_min,
+              double &ratio) {
+        ratio = (cost - c_new) / pred;
+        const bool accept = std::isfinite(c_new) && c_new <= cost - VCH_NEWTON_ARMIJO * pred;
+        double &rad = radius[b];
+        if (!std::isfinite(ratio) || ratio < VCH_TRUST_SHRINK_BELOW)
+            rad = 0.25 * std::min(rad, xnorm);
+        else if (ratio > VCH_TRUST_GROW_ABOVE && (cg_status == VCH_CG_BOUNDARY || cg_status == VCH_CG_NEGCURV))
+            rad = std::min(2.0 * rad, radius_max);
+        const bool small = rad < radius_min;
+        if (small) ended[b] = 1;
+        if (accept) return VCH_NEWTON_ACCEPTED;
+        return small ? VCH_NEWTON_STALLED : VCH_NEWTON_REJECTED;
+    }
+};
+
+// What a call of vch1d_pgd_trust passes the rounds: the arguments and the record, [B][n_rounds] per array (counts:
+// [B][n_rounds][3] = {n_free, pinned, clipped}).
+struct vch_trust_call {
+    int B, n_rounds, k;
+    double cg_tol;
+    int precond;
+    const double *radius0;
+    double radius_max, radius_min;
+    double *cost, *cost_new, *pred, *rnorm0, *radius, *ratio, *xnorm;
+    int32_t *cg_steps, *cg_status, *status;
+    int64_t *counts;
+};
+// The first of these arguments the call must refuse with VCH_ERR_ARG (the text that follows the entry point's name in the
+// message), or NULL.  An entry point checks this before anything is enqueued, copied or allocated.
+inline const char *vch_trust_check(const vch_trust_call &a) {
+    if (a.n_rounds < 1) return "n_rounds must be >= 1";
+    if (a.k < 1) return "k must be >= 1";
+    if (a.precond != 0 && a.precond != 1) return "precond must be 0 or 1";
+    if (!std::isfinite(a.cg_tol)) return "cg_tol must be finite";
+    if (!a.radius0) return "NULL radius0";
+    for (int b = 0; b < a.B; ++b)
+        if (!(std::isfinite(a.radius0[b]) && a.radius0[b] > 0.0)) return "every radius0 must be finite and > 0";
+    if (!(std::isfinite(a.radius_max) && a.radius_max > 0.0)) return "radius_max must be finite and > 0";
+    if (!(std::isfinite(a.radius_min) && a.radius_min > 0.0)) return "radius_min must be finite and > 0";
+    if (!(a.cost && a.cost_new && a.pred && a.rnorm0 && a.radius && a.ratio && a.xnorm && a.cg_steps && a.cg_status && a.status &&
+          a.counts))
+        return "NULL cost_out, cost_new_out, pred_out, rnorm0_out, radius_out, ratio_out, xnorm_out, cg_steps_out, cg_status_out, "
+               "status_out or counts_out";
+    return nullptr;
+}
+
+// The rounds of a call that passed vch_trust_check, as vch_newton_rounds: the record is initialised (NaN, 0, IDLE), then
+// written round by round.  Returns the rounds run (fewer than n_rounds once every trajectory has ended) or the first negative
+// code a hook returned; `moved`: a trial was accepted.  The hooks of E, every int one returning < 0 to fail the call:
+//   int solve(radius, pred, rnorm0, steps, status, n_free, xnorm)   the Steihaug solve of every trajectory about its iterate
+//                                        inside radius [B] into these [B] arrays (an idle trajectory's solve is not gated)
+//   double cost(b)                       the cost of b's iterate
+//   int trial(decided, sums, c_new)      the trial control at s = 1, its march and its cost for who is not decided: sums [B][4]
+//                                        = {.., .., pinned, clipped}, c_new [B] (NaN: a march that must not be accepted)
+//   int accept(b, c_new)                 b's trial becomes its iterate
+//   int after_trial(), int after_round()
+template <class E>
+int vch_trust_rounds(E &eng, const vch_trust_call &a, bool &moved) {
+    const int B = a.B;
+    moved = false;
+    for (size_t i = 0; i < (size_t)B * a.n_rounds; ++i) {
+        a.cost[i] = a.cost_new[i] = a.pred[i] = a.rnorm0[i] = a.radius[i] = a.ratio[i] = a.xnorm[i] = std::nan("");
+        a.cg_steps[i] = a.cg_status[i] = 0;
+        a.status[i] = VCH_NEWTON_IDLE;
+        a.counts[3 * i] = a.counts[3 * i + 1] = a.counts[3 * i + 2] = 0;
+    }
+    vch_trust_state tr;
+    tr.reset(a.radius0, B);
+    std::vector<double> rad(B), pred(B), rn0(B), xn(B), sums(4 * (size_t)B), c_new(B);
+    std::vector<int32_t> steps(B), cgst(B);
+    std::vector<int64_t> nfree(B);
+    std::vector<int> decided(B);
+    int rc, done_rounds = 0;
+    for (int r = 0; r < a.n_rounds && tr.any_live(); ++r) {
+        for (int b = 0; b < B; ++b) rad[b] = tr.solve_radius(b);
+        if ((rc = eng.solve(rad.data(), pred.data(), rn0.data(), steps.data(), cgst.data(), nfree.data(), xn.data())) < 0) return rc;
+        for (int b = 0; b < B; ++b) {
+            decided[b] = tr.idle(b);
+            if (decided[b]) continue;
+            const size_t i = (size_t)b * a.n_rounds + r;
+            a.cost[i] = a.cost_new[i] = eng.cost(b);
+            a.pred[i] = pred[b];
+            a.rnorm0[i] = rn0[b];
+            a.radius[i] = rad[b];
+            a.xnorm[i] = xn[b];
+            a.cg_steps[i] = steps[b];
+            a.cg_status[i] = cgst[b];
+            a.counts[3 * i] = nfree[b];
+            a.status[i] = tr.after_solve(b, nfree[b], rn0[b], cgst[b]);
+            decided[b] = a.status[i] != VCH_NEWTON_ACCEPTED;
+        }
+        // one trial at s = 1 for whoever has a step; a trajectory whose verdict is in sits it out
+        if (std::find(decided.begin(), decided.end(), 0) != decided.end()) {
+            if ((rc = eng.trial(decided, sums.data(), c_new.data())) < 0) return rc;
+            for (int b = 0; b < B; ++b) {
+                if (decided[b]) continue;
+                const size_t i = (size_t)b * a.n_rounds + r;
+                a.counts[3 * i + 1] = (int64_t)sums[4 * b + 2];
+                a.counts[3 * i + 2] = (int64_t)sums[4 * b + 3];
+                const int st = tr.judge(b, eng.cost(b), pred[b], c_new[b], xn[b], cgst[b], a.radius_max, a.radius_min, a.ratio[i]);
+                a.status[i] = st;
+                if (st != VCH_NEWTON_ACCEPTED) continue;
+                if ((rc = eng.accept(b, c_new[b])) < 0) return rc;
+                moved = true;
+                a.cost_new[i] = c_new[b];
+            }
+            if ((rc = eng.after_trial()) < 0) return rc;
+        }
+        if ((rc = eng.after_round()) < 0) return rc;
+        done_rounds = r + 1;
+    }
+    return done_rounds;
+}

@@ -1122,3 +1122,67 @@ class Engine1D:
         cnt = np.zeros((self.B, 2), dtype=np.int64)
         check(self.lib.vch1d_newton_trial(self.ctx, _dp(s), _dp(out), _dp(chg), cnt.ctypes.data_as(C.POINTER(C.c_int64))))
         return dict(u=out, change=chg, pinned=cnt[:, 0].copy(), clipped=cnt[:, 1].copy())
+
+    TRUST_CG_STATUS = CG_STATUS + ("boundary",)                     # VCH_CG_LIMIT .. VCH_CG_BOUNDARY
+    TRUST_STATUS = NEWTON_STATUS + ("rejected",)                    # VCH_NEWTON_ACCEPTED .. _REJECTED
+
+    def hess_cg_trust(self, k, radius, t_hist, opt, rhs=None, cg_tol=0.0, precond=True, mask=None, tol=0.0, phi_hist=None,
+                      u=None, phi_Q=None, phi_T=None, dt=None, x=None, shared_base=False):
+        """Truncated (Steihaug-Toint) conjugate gradients on P H P x = P b inside ||x||_D <= radius_b (vch1d_hess_cg_tr):
+        hess_cg with a trust region in the preconditioner's norm, ||x||_D^2 = sum D x^2, D = diag(wt' wx) with precond and
+        the identity without.  radius: [B] or a scalar, > 0, +inf allowed.  A step that would leave the region, or a
+        direction of non-positive curvature, is followed to the boundary: "boundary" and "negcurv" of TRUST_CG_STATUS.
+        Returns hess_cg's dict (status: indices of TRUST_CG_STATUS) plus xnorm: [B] ||x||_D by the recurrence.  With
+        radius = inf everything equals hess_cg's bit for bit on a trajectory that ends "converged" or "limit"."""
+        t_hist, rows, nb, keep, dt, x, arr = self._base_point(t_hist, phi_hist, u, phi_Q, phi_T, dt, x, opt, shared_base)
+        k = int(k)
+        rhs = None if rhs is None else self._hist(rhs, rows, "rhs")
+        mask = self._free_mask(mask, rows, nb)
+        radius = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float64), (self.B,)))
+        kk = max(k, 1)
+        resid, curv = np.full((self.B, kk), np.nan), np.full((self.B, kk), np.nan)
+        pred, rnorm0, xnorm = np.full(self.B, np.nan), np.full(self.B, np.nan), np.full(self.B, np.nan)
+        steps, status, n_free = np.zeros(self.B, dtype=np.int32), np.zeros(self.B, dtype=np.int32), np.zeros(self.B, dtype=np.int64)
+        st = Stats()
+        precond = int(precond) if isinstance(precond, (bool, int, np.integer)) else -1
+        check(self.lib.vch1d_hess_cg_tr(self.ctx, keep[0][1], keep[1][1], nb, rows, _dp(dt), _dp(t_hist), _dp(x), keep[2][1],
+                                        keep[3][1], arr, len(arr),
+                                        None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint8)), float(tol),
+                                        _dp(rhs), k, float(cg_tol), precond, _dp(resid), _dp(curv), _dp(pred), _dp(rnorm0),
+                                        steps.ctypes.data_as(_lib._I32), status.ctypes.data_as(_lib._I32),
+                                        n_free.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(st), _dp(radius), _dp(xnorm)))
+        self._cg_rows = rows
+        return dict(steps=steps, status=status, n_free=n_free, resid=resid, curv=curv, pred=pred, rnorm0=rnorm0, xnorm=xnorm,
+                    stats=st.as_dict())
+
+    def pgd_trust(self, n_rounds, radius0, k=50, cg_tol=1e-8, precond=True, tol=0.0, radius_max=None, radius_min=None):
+        """Trust-region (Steihaug) Newton-CG rounds on the free set about the resident PGD iterate (vch1d_pgd_trust), every
+        trajectory with its own parameters, radius and decisions.  Per round: the step of hess_cg_trust in its resident mode
+        inside the trajectory's radius (a direction of non-positive curvature is followed to the boundary and does not end
+        the trajectory), one trial clip(u + x, box) as newton_trial(1) builds it, rho = (J(u) - J(trial)) / pred.  The trial
+        is accepted iff J(trial) is finite and <= J(u) - 1e-4 pred; otherwise the trajectory stays unmoved, "rejected", and
+        goes on.  The radius: rho < 1/4 or not finite: min(radius, ||x||_D) / 4; else rho > 3/4 after a "boundary" or
+        "negcurv" exit: min(2 radius, radius_max).  A trajectory ends "stationary", "breakdown", or "stalled" (rejected with
+        the radius below radius_min) and is "idle" afterwards.  radius0: [B] or a scalar, finite and > 0; radius_max /
+        radius_min default to 1024 max(radius0) and 1e-10 min(radius0).  Returns dict(rounds; cost, cost_new, pred, rnorm0,
+        radius (the round's), ratio, xnorm: (B, n_rounds), NaN where idle; cg_steps, cg_status (indices of TRUST_CG_STATUS),
+        status (indices of TRUST_STATUS): int32 (B, n_rounds); n_free, pinned, clipped: int64 (B, n_rounds); seconds)."""
+        n = max(int(n_rounds), 1)
+        radius0 = np.ascontiguousarray(np.broadcast_to(np.asarray(radius0, dtype=np.float64), (self.B,)))
+        radius_max = 1024.0 * float(np.max(radius0)) if radius_max is None else float(radius_max)
+        radius_min = 1e-10 * float(np.min(radius0)) if radius_min is None else float(radius_min)
+        dbl = [np.full((self.B, n), np.nan) for _ in range(7)]
+        i32 = [np.zeros((self.B, n), dtype=np.int32) for _ in range(3)]
+        cnt = np.zeros((self.B, n, 3), dtype=np.int64)
+        sec = np.zeros(4)
+        precond = int(precond) if isinstance(precond, (bool, int, np.integer)) else -1
+        done = check(self.lib.vch1d_pgd_trust(self.ctx, int(n_rounds), int(k), float(cg_tol), precond, float(tol), _dp(radius0),
+                                              radius_max, radius_min, *[_dp(a) for a in dbl],
+                                              *[a.ctypes.data_as(_lib._I32) for a in i32],
+                                              cnt.ctypes.data_as(C.POINTER(C.c_int64)), _dp(sec)))
+        self._cg_rows = self._pgd_rows
+        out = dict(zip(("cost", "cost_new", "pred", "rnorm0", "radius", "ratio", "xnorm"), dbl), rounds=done)
+        out.update(zip(("cg_steps", "cg_status", "status"), i32))
+        out.update(n_free=cnt[:, :, 0].copy(), pinned=cnt[:, :, 1].copy(), clipped=cnt[:, :, 2].copy(),
+                   seconds=dict(zip(("solve", "trial", "forward", "cost"), sec)))
+        return out
