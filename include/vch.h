@@ -431,6 +431,27 @@ int vch2d_hess_cg(vch2d_ctx *ctx, const double *dt, int M, const double *t_hist,
 /* out = x (which 0), r (1) or p (2) of the last vch2d_hess_cg of this context; masked-off nodes are exact zeros.
  * VCH_ERR_STATE without resident vectors (no call yet, a failed call, or a vch2d_hess_lanczos since). */
 int vch2d_cg_vector(vch2d_ctx *ctx, int which /* 0: x, 1: r, 2: p */, double *out /* [B][M+1][Nx+1][Ny+1] */);
+/* Truncated (Steihaug-Toint) Newton-CG in a trust region on the free set of the 2D engine (ABI version stays 3:
+ * detect this entry point and vch2d_pgd_trust by symbol).  The arguments, modes, mask, precond, outputs, looks, storage,
+ * invalidation rules and errors are those of vch2d_hess_cg, plus radius [B] and xnorm_out [B].  The region is
+ * ||x||_D <= radius_b in the preconditioner's norm, ||x||_D^2 = sum D x^2 with D = diag(wt_n W_ij) for precond 1 and the
+ * identity for precond 0.  The iteration, its exits (VCH_CG_BOUNDARY = 4 among them, a VCH_CG_NEGCURV that has stepped to the
+ * boundary), pred, resid, steps_out and the bitwise equality with vch2d_hess_cg at radius = +inf on a trajectory that ends
+ * VCH_CG_CONVERGED or VCH_CG_LIMIT are those of vch1d_hess_cg_tr, word for word.  One kernel differs from vch2d_hess_cg's:
+ * k_ncg_fin_tr in place of k_ncg_fin, with six more scalars per trajectory in cells of the Lanczos block that CG leaves
+ * unused, so the storage and every request are those of vch2d_hess_cg.  The host uploads the B radii before the start and
+ * looks as vch2d_hess_cg does; a boundary exit takes the launches of one ordinary step.  x, r = P b - P H P x and p stay
+ * resident for vch2d_cg_vector and vch2d_newton_trial.  xnorm_out [B]: ||x||_D by the recurrence (0 for P b == 0).
+ * VCH_ERR_ARG, before anything is enqueued, copied or allocated, for NULL radius or xnorm_out and a radius_b that is not > 0
+ * (NaN included; +inf is allowed). */
+int vch2d_hess_cg_tr(vch2d_ctx *ctx, const double *dt, int M, const double *t_hist, const double *x, const double *y,
+                     const double *phi_Q, const double *phi_T, const vch_opt_params *opts, int n_opts, double rtol,
+                     const uint8_t *mask /* [B][M+1][Nx+1][Ny+1] or NULL */, double tol,
+                     const double *rhs /* [B][M+1][Nx+1][Ny+1] or NULL */, int k, double cg_tol, int precond /* 0 | 1 */,
+                     double *resid_out /* [B][k] */, double *curv_out /* [B][k] */, double *pred_out /* [B] */,
+                     double *rnorm0_out /* [B] */, int32_t *steps_out /* [B] */, int32_t *status_out /* [B] */,
+                     int64_t *n_free_out /* [B] */, vch_stats *stats, const double *radius /* [B] */,
+                     double *xnorm_out /* [B] */);
 /* Damped Newton rounds on the free set about the resident PGD iterate, batched, with every trajectory's own parameters and
  * decisions (ABI version stays 3: detect both entry points by symbol).  No history crosses the bus.
  * Per round:
@@ -468,12 +489,31 @@ int vch2d_cg_vector(vch2d_ctx *ctx, int which /* 0: x, 1: r, 2: p */, double *ou
 #define VCH_NEWTON_BREAKDOWN 3
 #define VCH_NEWTON_STALLED 4
 #define VCH_NEWTON_IDLE 5
-#define VCH_NEWTON_REJECTED 6       /* vch1d_pgd_trust: the round's trial was rejected, the trajectory goes on */
+#define VCH_NEWTON_REJECTED 6       /* vch1d_pgd_trust, vch2d_pgd_trust: the round's trial was rejected, the trajectory goes on */
 int vch2d_pgd_newton(vch2d_ctx *ctx, int n_rounds, int k, double cg_tol, int precond /* 0 | 1 */, double tol, double rtol,
                      int max_halvings, double *cost_out, double *cost_new_out, double *s_out, double *pred_out,
                      double *rnorm0_out /* [B][n_rounds] */, int32_t *halvings_out, int32_t *cg_steps_out,
                      int32_t *cg_status_out, int32_t *status_out /* [B][n_rounds] */,
                      int64_t *counts_out /* [B][n_rounds][3]: n_free, pinned, clipped */, double *seconds_out /* [4] */);
+/* Trust-region (Steihaug) Newton-CG rounds on the free set about the resident PGD iterate of the 2D engine, batched, with
+ * every trajectory's own parameters, radius and decisions (ABI version stays 3: detect by symbol).  The state
+ * checks, the solve's mode (tol, rtol as passed), the trial, its march and cost, the copies of an accepted trial, the
+ * resident state afterwards, the refreshed device cost scalars and the untouched PGD counters are those of vch2d_pgd_newton;
+ * the adjoint r of vch2d_pgd_kkt(refresh = 0) is invalid once anything moved.  The rounds -- the solve of vch2d_hess_cg_tr
+ * inside Delta_b (radius0_b in round 0), no trial after VCH_NEWTON_STATIONARY or VCH_NEWTON_BREAKDOWN, one trial at s = 1
+ * after every other CG exit (VCH_CG_NEGCURV included), rho = (J(u) - J(t)) / pred, acceptance, VCH_NEWTON_REJECTED, the radius
+ * rule, VCH_NEWTON_STALLED below radius_min, VCH_NEWTON_IDLE afterwards -- and the outputs are those of vch1d_pgd_trust, word
+ * for word: one march per round.  Up to 32 trajectories, no atomics: a trajectory's outputs and its iterate are bitwise
+ * those of a single-trajectory context.  Storage: that of vch2d_pgd_newton.  Errors, all before anything is enqueued, copied
+ * or allocated: VCH_ERR_STATE before vch2d_pgd_init / _init_v (or when the resident state is no longer the PGD iterate);
+ * VCH_ERR_ARG for n_rounds < 1, k < 1, precond outside 0 / 1, a cg_tol that is not finite, NULL radius0, a radius0_b,
+ * radius_max or radius_min that is not finite or not > 0, and NULL outputs (seconds_out may be NULL). */
+int vch2d_pgd_trust(vch2d_ctx *ctx, int n_rounds, int k, double cg_tol, int precond /* 0 | 1 */, double tol, double rtol,
+                    const double *radius0 /* [B] */, double radius_max, double radius_min,
+                    double *cost_out, double *cost_new_out, double *pred_out, double *rnorm0_out, double *radius_out,
+                    double *ratio_out, double *xnorm_out /* [B][n_rounds] */, int32_t *cg_steps_out, int32_t *cg_status_out,
+                    int32_t *status_out /* [B][n_rounds] */, int64_t *counts_out /* [B][n_rounds][3]: n_free, pinned, clipped */,
+                    double *seconds_out /* [4] or NULL: solves, trial kernel, marches, costs */);
 /* The trial kernel's seam: t = min(max(u + s_b x, u_min_b), u_max_b) with u the resident control (rows beyond the march's
  * control are zeros), x and the free set those the last successful vch2d_hess_cg (forward or PGD mode) left resident and the
  * box that call's opts; a free node with t u < 0 becomes 0.  Writes only the trial-control scratch and leaves x, r, p resident.

@@ -82,7 +82,7 @@ def run_optimization(fwd_config: ForwardSolverConfig, opt_config: OptimizationCo
 
 
 def run_sweep(fwd_config: ForwardSolverConfig, opt_configs, n_iter=None, seed=42, amp=0.1, choice_t=DEFAULT_TARGET_CHOICE,
-              choice_q=DEFAULT_TRACKING_CHOICE, u0=None, return_controls=False, device=0, n_newton=0):
+              choice_q=DEFAULT_TRACKING_CHOICE, u0=None, return_controls=False, device=0, n_newton=0, n_trust=0, radius0=1.0):
     """A parameter sweep as ONE batch: member b runs the PGD loop with opt_configs[b] (weights, sparsity parameter, box,
     alpha_max), all members from the same initial state (`seed`, `amp`) and targets, so that they differ by their
     parameters only.  `u0`: start control, one (M+1, Nx+1, Ny+1) array for every member or one per member (continuation
@@ -93,7 +93,9 @@ def run_sweep(fwd_config: ForwardSolverConfig, opt_configs, n_iter=None, seed=42
     the state history never leaves the device.  `n_newton` > 0 polishes every member after its PGD iterations by that many
     damped Newton rounds on its free set (Engine2D.pgd_newton, on the device) and adds `newton` (its records) and
     `costs_newton` [B][n_newton+1] (the cost before the first round, then after every round); kkt and u are then those of
-    the polished iterate.  0 leaves the result as it is without the polish."""
+    the polished iterate.  0 leaves the result as it is without the polish.  `n_trust` > 0 does the same (after the Newton
+    rounds, if both are asked for) with that many trust-region rounds from the radius `radius0` (Engine2D.pgd_trust), which
+    follow a direction of non-positive curvature instead of ending on it, and adds `trust` and `costs_trust` [B][n_trust+1]."""
     opt_configs = list(opt_configs)
     B = len(opt_configs)
     if B < 1:
@@ -113,16 +115,19 @@ def run_sweep(fwd_config: ForwardSolverConfig, opt_configs, n_iter=None, seed=42
     n = int(max(int(o.max_iter) for o in opt_configs) if n_iter is None else n_iter)
     res = eng.pgd_iterate(n)
     newton = eng.pgd_newton(int(n_newton)) if int(n_newton) > 0 else None
+    trust = eng.pgd_trust(int(n_trust), radius0) if int(n_trust) > 0 else None
     out = dict(costs=np.concatenate([J0[:, 4:5], res["cost"]], axis=1), alphas=res["alpha"], attempts=res["attempts"],
                changes=res["change"], tracking_error=res["tracking_error"], terminal_error=res["terminal_error"],
                iters=res["iters"], seconds=res["seconds"], kkt=eng.pgd_kkt(refresh=True), phi_T=phi_T, t_hist=t_hist,
                x=eng.x.copy(), y=eng.y.copy())
-    if newton is not None:
+    for name, rec in (("newton", newton), ("trust", trust)):
+        if rec is None:
+            continue
         # an idle round carries the cost the member ended with
-        cn = np.concatenate([newton["cost"][:, :1], newton["cost_new"]], axis=1)
+        cn = np.concatenate([rec["cost"][:, :1], rec["cost_new"]], axis=1)
         for r in range(1, cn.shape[1]):
             cn[:, r] = np.where(np.isnan(cn[:, r]), cn[:, r - 1], cn[:, r])
-        out["newton"], out["costs_newton"] = newton, cn
+        out[name], out["costs_" + name] = rec, cn
     if return_controls:
         out["u"] = eng.pgd_get("u").reshape((B, len(t_hist)) + eng.shape)
     return out
@@ -210,6 +215,90 @@ def _newton_refine_device(fwd_config, opt_config, u, phi_Q_target, phi_T_target,
                             steps=int(R["cg_steps"][0, r]), status=Engine2D.CG_STATUS[int(R["cg_status"][0, r])],
                             s=None if np.isnan(s) else s, cost_new=float(R["cost_new"][0, r])))
     return eng.pgd_get("u"), records
+
+
+def trust_refine(fwd_config: ForwardSolverConfig, opt_config: OptimizationConfig, u, phi_Q_target, phi_T_target,
+                 n_trust=3, radius0=1.0, k=50, cg_tol=1e-8, radius_max=None, radius_min=None, on_device=False):
+    """Rounds of a trust-region Newton method on the free set, from the control `u`: newton_refine with the damping
+    replaced by a radius.  Per round: the Steihaug step x of the full cost on the free set of the iterate inside
+    ||x||_D <= radius (Engine2D.hess_cg_trust: a direction of non-positive curvature is followed to the boundary instead
+    of ending the loop), one trial clip(u + x, box) with a flipped sign set to 0 (Engine2D.newton_trial(1)), its march
+    from the start state of newton_refine and its cost J(t); rho = (J(u) - J(t)) / pred.  The trial is accepted iff J(t) is
+    finite and J(t) <= J(u) - 1e-4 pred, else the iterate stays ("rejected") and the loop goes on.  The radius: rho < 1/4
+    or not finite: min(radius, ||x||_D) / 4; else rho > 3/4 after a "boundary" or "negcurv" exit: min(2 radius,
+    radius_max).  The loop ends after `n_trust` rounds, on a vanishing right-hand side ("stationary"), a CG breakdown, or
+    once the radius is below radius_min ("stalled" when that round was rejected).  radius_max / radius_min default to
+    1024 radius0 and 1e-10 radius0.
+
+    Returns (u, records): one dict per round with cost, cost_new, pred, rnorm0, radius (the round's), ratio, xnorm,
+    steps, cg_status (a name of Engine2D.TRUST_CG_STATUS), status (a name of Engine2D.TRUST_STATUS), n_free.
+
+    on_device=True runs the rounds on the device (Engine2D.pgd_trust): one context, one pgd_init(u0=u) with this loop's
+    own start state and targets; the records have the same keys."""
+    from ..engine import Engine2D
+    Nx, Ny = int(fwd_config.Nx), int(fwd_config.Ny)
+    t_hist, dts = time_grid(float(fwd_config.T), float(fwd_config.dt_initial))
+    M = len(dts)
+    u = np.asarray(u, dtype=np.float64)[:M + 1]
+    radius = float(radius0)
+    radius_max = 1024.0 * radius if radius_max is None else float(radius_max)
+    radius_min = 1e-10 * radius if radius_min is None else float(radius_min)
+    phi0 = init_phi_random(Nx, Ny, DELTA_SEP, amp=0.1, seed=42)
+    x, y = np.linspace(0.0, fwd_config.Lx, Nx + 1), np.linspace(0.0, fwd_config.Ly, Ny + 1)
+    pq, pt = np.asarray(phi_Q_target, dtype=np.float64)[None, :M + 1], np.asarray(phi_T_target, dtype=np.float64)[None]
+    opt = make_opt(opt_config)
+    eng = engine_for_config(fwd_config, batch=1, max_steps=max(M, 1))
+    CGS, NTS = Engine2D.TRUST_CG_STATUS, Engine2D.TRUST_STATUS
+    if on_device:
+        eng.pgd_init(phi0[None], pt, t_hist, [opt], phi_Q=pq, ramp=False, x=x, y=y, u0=u[None])
+        R = eng.pgd_trust(int(n_trust), radius, k=k, cg_tol=cg_tol, radius_max=radius_max, radius_min=radius_min)
+        records = []
+        for r in range(int(R["rounds"])):
+            if NTS[int(R["status"][0, r])] == "idle":
+                break
+            records.append(dict(cost=float(R["cost"][0, r]), cost_new=float(R["cost_new"][0, r]), pred=float(R["pred"][0, r]),
+                                rnorm0=float(R["rnorm0"][0, r]), radius=float(R["radius"][0, r]), ratio=float(R["ratio"][0, r]),
+                                xnorm=float(R["xnorm"][0, r]), steps=int(R["cg_steps"][0, r]),
+                                cg_status=CGS[int(R["cg_status"][0, r])], status=NTS[int(R["status"][0, r])],
+                                n_free=int(R["n_free"][0, r])))
+        return eng.pgd_get("u").reshape((M + 1, Nx + 1, Ny + 1)), records
+
+    def full_cost(v):
+        phi, _ = eng.forward(phi0[None], dts, u=np.ascontiguousarray(v[None]), store=True)
+        J = eng.cost(phi.reshape((1, M + 1, Nx + 1, Ny + 1)), v[None], pq, pt, t_hist, opt_config, x, y)
+        return float(np.atleast_2d(J)[0, 4])
+
+    cost = full_cost(u)
+    records = []
+    for _ in range(int(n_trust)):
+        eng.forward(phi0[None], dts, u=np.ascontiguousarray(u[None]), store=False)
+        S = eng.hess_cg_trust(int(k), radius, cg_tol=cg_tol, tol=1e-8, dt=dts, t_hist=t_hist, opt=opt, phi_Q=pq, phi_T=pt, x=x, y=y)
+        st = int(S["status"][0])
+        rec = dict(cost=cost, cost_new=cost, pred=float(S["pred"][0]), rnorm0=float(S["rnorm0"][0]), radius=radius,
+                   ratio=float("nan"), xnorm=float(S["xnorm"][0]), steps=int(S["steps"][0]), cg_status=CGS[st], status="stationary",
+                   n_free=int(S["n_free"][0]))
+        records.append(rec)
+        if rec["n_free"] < 1 or rec["rnorm0"] == 0.0:
+            break
+        if CGS[st] == "breakdown":
+            rec["status"] = "breakdown"
+            break
+        trial = eng.newton_trial(1.0)["u"][0]
+        J = full_cost(trial)
+        with np.errstate(all="ignore"):
+            rho = rec["ratio"] = float((np.float64(cost) - np.float64(J)) / np.float64(rec["pred"]))
+        accept = bool(np.isfinite(J)) and J <= cost - 1e-4 * rec["pred"]
+        if not np.isfinite(rho) or rho < 0.25:
+            radius = 0.25 * min(radius, rec["xnorm"])
+        elif rho > 0.75 and CGS[st] in ("boundary", "negcurv"):
+            radius = min(2.0 * radius, radius_max)
+        small = radius < radius_min
+        rec["status"] = "accepted" if accept else ("stalled" if small else "rejected")
+        if accept:
+            u, cost, rec["cost_new"] = trial, J, J
+        if small:
+            break
+    return u, records
 
 
 def main(n_iter=None, params_file="last_run_config_2d.json", num_directions=5, verbose=True):

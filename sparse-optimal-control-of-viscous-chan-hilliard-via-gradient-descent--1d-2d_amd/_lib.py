@@ -196,6 +196,11 @@ SIGNATURES = {
                                    C.POINTER(C.c_int64), C.POINTER(Stats), _D, _D]),
     "vch1d_pgd_trust": (C.c_int, [_P, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, _D, C.c_double, C.c_double,
                                   _D, _D, _D, _D, _D, _D, _D, _I32, _I32, _I32, C.POINTER(C.c_int64), _D]),
+    "vch2d_hess_cg_tr": (C.c_int, [_P, _D, C.c_int, _D, _D, _D, _D, _D, C.POINTER(OptParams), C.c_int, C.c_double,
+                                   C.POINTER(C.c_uint8), C.c_double, _D, C.c_int, C.c_double, C.c_int, _D, _D, _D, _D, _I32, _I32,
+                                   C.POINTER(C.c_int64), C.POINTER(Stats), _D, _D]),
+    "vch2d_pgd_trust": (C.c_int, [_P, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_double, _D, C.c_double, C.c_double,
+                                  _D, _D, _D, _D, _D, _D, _D, _I32, _I32, _I32, C.POINTER(C.c_int64), _D]),
     "vch2d_counters": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "vch_comm_unique_id": (C.c_int, [C.POINTER(C.c_ubyte)]),
     "vch_comm_create": (_P, [C.POINTER(C.c_ubyte), C.c_int, C.c_int, C.c_int]),

@@ -3124,11 +3124,14 @@ extern "C" int vch2d_krylov_vector(vch2d_ctx *c, const double *coef, int m, doub
 // The body of vch2d_hess_cg, shared with the rounds of vch2d_pgd_newton.  fn: the entry point the messages name.
 // empty_ok (the Newton rounds): a trajectory with an empty free set is no error; with P b = 0 the start gives it zero steps,
 // VCH_CG_CONVERGED and x = 0.
+// radius (host [B], or NULL): the trust region of vch2d_hess_cg_tr, k_ncg_fin_tr in place of k_ncg_fin and xnorm_out [B] =
+// ||x||_D by the recurrence (0 for P b = 0); NULL enqueues the launches, looks and copies of vch2d_hess_cg exactly.
 static int hess_cg_core(vch2d_ctx *c, const char *fn, bool empty_ok, const double *dt, int M, const double *t_hist, const double *x,
                         const double *y, const double *phi_Q, const double *phi_T, const vch_opt_params *opts, int n_opts,
                         double rtol, const uint8_t *mask, double tol, const double *rhs, int k, double cg_tol, int precond,
                         double *resid_out, double *curv_out, double *pred_out, double *rnorm0_out, int32_t *steps_out,
-                        int32_t *status_out, int64_t *n_free_out, vch_stats *stats) {
+                        int32_t *status_out, int64_t *n_free_out, vch_stats *stats, const double *radius = nullptr,
+                        double *xnorm_out = nullptr) {
     // everything below is checked before anything is enqueued, copied or allocated
     VCHCHK(tan_check_state(c, fn));
     TANCHK(opts, "NULL opts");
@@ -3137,6 +3140,10 @@ static int hess_cg_core(vch2d_ctx *c, const char *fn, bool empty_ok, const doubl
     TANCHK(k >= 1, "k must be >= 1");
     TANCHK(precond == 0 || precond == 1, "precond must be 0 or 1");
     TANCHK(std::isfinite(cg_tol), "cg_tol must be finite");
+    if (radius)
+        for (int b = 0; b < c->B; ++b)
+            if (!(radius[b] > 0.0))
+                return vch_fail(VCH_ERR_ARG, "%s: trajectory %d: radius %g must be > 0 (+inf allowed, NaN not)", fn, b, radius[b]);
     KrCall K;
     VCHCHK(kr_open(c, fn, K, 3, k, empty_ok, &dt, M, &t_hist, x, y, phi_Q, phi_T, opts, n_opts, rtol, mask, tol));
     const Geom &G = c->G;
@@ -3145,12 +3152,19 @@ static int hess_cg_core(vch2d_ctx *c, const char *fn, bool empty_ok, const doubl
     // the cells of the iteration in the block of the Lanczos scalars: resid, curv where alpha, beta live
     const NcgCells nc{cells.alpha, cells.beta, cells.look, cells.scal, cells.amax, cells.coef1, cells.coef1 + B, cells.coef1 + 2 * B,
                       cells.lim, cells.stop};
+    // the six cells of the trust region where CG leaves the Lanczos block unused: three in coef2, three in ucoef, each
+    // B * S doubles with S >= 3 (kr_open asked for three slots, and kr_storage keeps resident storage only if it holds at
+    // least what is asked).  ucoef is otherwise written by vch2d_krylov_vector alone, whose basis this call invalidates.
+    double *const ucoef = c->kr_sc + kr_layout(c, c->kr_slots, c->kr_kcap).ucoef;
+    const NtrCells tc{cells.coef2, cells.coef2 + B, cells.coef2 + 2 * B, ucoef, ucoef + B, (long long *)(ucoef + 2 * B)};
+    std::vector<double> xx(radius ? B : 0);
     const KrArgs a = kr_args(c, levels, 0, 0, 3, S);
     const double stop_at = cg_tol > 0 ? cg_tol : 1e-8;
     std::vector<double> look(2 * (size_t)B);
     std::vector<long long> steps(B), stop(B);
     auto run = [&]() -> int {
         HvRun r{dt, M, K.pq, K.pt, levels, levels, {}};
+        if (radius) HIPCHK(hipMemcpyAsync(cells.coef2, radius, sizeof(double) * B, hipMemcpyHostToDevice, c->stream));
         if (rhs) VCHCHK(h2d_hist(c, c->u_trial, rhs, levels));   // through the trial-control scratch, which then holds p
         VCHCHK(hv_begin(c, r, t_hist, opts, n_opts));
         // the gradient sweep once per base point: its xp of every step stays in kr_X, its field is the Newton right-hand
@@ -3168,7 +3182,8 @@ static int hess_cg_core(vch2d_ctx *c, const char *fn, bool empty_ok, const doubl
             LAUNCHC(PC_KRYLOV, (k_ncg_start<0>), K.kgrid, dim3(NTH), G, a, (const double *)c->u_trial, K.u_dev, K.u_rows,
                     (const double *)c->hv_wt, (const double *)c->W_cost, (const double *)c->seam_tab, precond, c->u_trial, K.part);
         }
-        LAUNCHC(PC_KRYLOV, k_ncg_fin, dim3(B), dim3(NTH), nc, (const double *)K.part, K.nsum, S, 1, 0, k, stop_at);
+        if (radius) LAUNCHC(PC_KRYLOV, k_ncg_fin_tr, dim3(B), dim3(NTH), nc, tc, (const double *)K.part, K.nsum, S, 1, 0, k, stop_at);
+        else LAUNCHC(PC_KRYLOV, k_ncg_fin, dim3(B), dim3(NTH), nc, (const double *)K.part, K.nsum, S, 1, 0, k, stop_at);
         HIPCHK(hipMemsetAsync(nc.resid, 0xff, sizeof(double) * 2 * B * c->kr_kcap, c->stream));         // NaN: resid, then curv
         VCHCHK(kr_look(c, look.data(), nc.look, sizeof(double) * 2 * B));
         bool any = false;
@@ -3183,10 +3198,12 @@ static int hess_cg_core(vch2d_ctx *c, const char *fn, bool empty_ok, const doubl
             // H p in hv_H
             LAUNCHC(PC_KRYLOV, k_ncg_curv, K.kgrid, dim3(NTH), G, a, (const double *)c->hv_H, (const double *)c->hv_wt,
                     (const double *)c->W_cost, precond, K.part);
-            LAUNCHC(PC_KRYLOV, k_ncg_fin, dim3(B), dim3(NTH), nc, (const double *)K.part, K.nsum, S, 2, j, k, stop_at);
+            if (radius) LAUNCHC(PC_KRYLOV, k_ncg_fin_tr, dim3(B), dim3(NTH), nc, tc, (const double *)K.part, K.nsum, S, 2, j, k, stop_at);
+            else LAUNCHC(PC_KRYLOV, k_ncg_fin, dim3(B), dim3(NTH), nc, (const double *)K.part, K.nsum, S, 2, j, k, stop_at);
             LAUNCHC(PC_KRYLOV, k_ncg_update, K.kgrid, dim3(NTH), G, a, (const double *)c->hv_H, (const double *)nc.alpha,
                     (const double *)c->hv_wt, (const double *)c->W_cost, precond, K.part);
-            LAUNCHC(PC_KRYLOV, k_ncg_fin, dim3(B), dim3(NTH), nc, (const double *)K.part, K.nsum, S, 3, j, k, stop_at);
+            if (radius) LAUNCHC(PC_KRYLOV, k_ncg_fin_tr, dim3(B), dim3(NTH), nc, tc, (const double *)K.part, K.nsum, S, 3, j, k, stop_at);
+            else LAUNCHC(PC_KRYLOV, k_ncg_fin, dim3(B), dim3(NTH), nc, (const double *)K.part, K.nsum, S, 3, j, k, stop_at);
             if (j + 1 < k)
                 LAUNCHC(PC_KRYLOV, k_ncg_dir, K.kgrid, dim3(NTH), G, a, (const double *)nc.beta, (const double *)c->hv_wt,
                         (const double *)c->W_cost, precond, c->u_trial);
@@ -3196,6 +3213,7 @@ static int hess_cg_core(vch2d_ctx *c, const char *fn, bool empty_ok, const doubl
             for (int b = 0; b < B; ++b) any = any || look[2 * b + 1] == 0.0;
         }
         HIPCHK(hipEventRecord(c->ev1, c->stream));
+        if (radius) HIPCHK(hipMemcpyAsync(xx.data(), tc.xx, sizeof(double) * B, hipMemcpyDeviceToHost, c->stream));
         for (int b = 0; b < B; ++b) {
             HIPCHK(hipMemcpyAsync(resid_out + (size_t)b * k, nc.resid + (size_t)b * k, sizeof(double) * k, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(hipMemcpyAsync(curv_out + (size_t)b * k, nc.curv + (size_t)b * k, sizeof(double) * k, hipMemcpyDeviceToHost, c->stream));
@@ -3213,6 +3231,7 @@ static int hess_cg_core(vch2d_ctx *c, const char *fn, bool empty_ok, const doubl
         n_free_out[b] = K.nfree[b];
         steps_out[b] = (int32_t)steps[b];
         status_out[b] = (int32_t)stop[b];           // 0: still running after k steps, VCH_CG_LIMIT
+        if (radius) xnorm_out[b] = std::sqrt(xx[b]);
     }
     c->ncg_valid = true;
     c->ncg_levels = levels;
@@ -3227,6 +3246,18 @@ extern "C" int vch2d_hess_cg(vch2d_ctx *c, const double *dt, int M, const double
     CTXCHK(c);
     return hess_cg_core(c, __func__, false, dt, M, t_hist, x, y, phi_Q, phi_T, opts, n_opts, rtol, mask, tol, rhs, k, cg_tol, precond,
                         resid_out, curv_out, pred_out, rnorm0_out, steps_out, status_out, n_free_out, stats);
+}
+
+extern "C" int vch2d_hess_cg_tr(vch2d_ctx *c, const double *dt, int M, const double *t_hist, const double *x, const double *y,
+                                const double *phi_Q, const double *phi_T, const vch_opt_params *opts, int n_opts, double rtol,
+                                const uint8_t *mask, double tol, const double *rhs, int k, double cg_tol, int precond,
+                                double *resid_out, double *curv_out, double *pred_out, double *rnorm0_out, int32_t *steps_out,
+                                int32_t *status_out, int64_t *n_free_out, vch_stats *stats, const double *radius,
+                                double *xnorm_out) {
+    CTXCHK(c);
+    if (!radius || !xnorm_out) return vch_fail(VCH_ERR_ARG, "%s: NULL radius or xnorm_out", __func__);
+    return hess_cg_core(c, __func__, false, dt, M, t_hist, x, y, phi_Q, phi_T, opts, n_opts, rtol, mask, tol, rhs, k, cg_tol, precond,
+                        resid_out, curv_out, pred_out, rnorm0_out, steps_out, status_out, n_free_out, stats, radius, xnorm_out);
 }
 
 extern "C" int vch2d_cg_vector(vch2d_ctx *c, int which, double *out) {
@@ -3278,6 +3309,66 @@ extern "C" int vch2d_newton_trial(vch2d_ctx *c, const double *s, double *u_out, 
     return u_out ? d2h_hist(c, u_out, c->u_trial, c->ncg_levels) : 0;
 }
 
+// The engine's side of the Newton and trust-region rounds (vch_newton.h) about the resident PGD iterate; sec = {solves, trial
+// controls, marches, costs}.
+struct PgdRounds {
+    vch2d_ctx *c;
+    const char *fn;
+    int M, k, precond;
+    double cg_tol, tol, rtol;
+    std::vector<double> resid, curv, Jt;
+    double sec[4];
+    int solve(double *pred, double *rnorm0, int32_t *steps, int32_t *status, int64_t *n_free) {
+        vch_stats st;
+        VCHCHK(hess_cg_core(c, fn, true, nullptr, M, nullptr, nullptr, nullptr, nullptr, nullptr, c->opts.data(), c->B, rtol, nullptr,
+                            tol, nullptr, k, cg_tol, precond, resid.data(), curv.data(), pred, rnorm0, steps, status, n_free, &st));
+        sec[0] += st.seconds;
+        return 0;
+    }
+    // the trust-region rounds: the Steihaug solve inside radius [B]
+    int solve(const double *radius, double *pred, double *rnorm0, int32_t *steps, int32_t *status, int64_t *n_free, double *xnorm) {
+        vch_stats st;
+        VCHCHK(hess_cg_core(c, fn, true, nullptr, M, nullptr, nullptr, nullptr, nullptr, nullptr, c->opts.data(), c->B, rtol, nullptr,
+                            tol, nullptr, k, cg_tol, precond, resid.data(), curv.data(), pred, rnorm0, steps, status, n_free, &st,
+                            radius, xnorm));
+        sec[0] += st.seconds;
+        return 0;
+    }
+    // the trust-region rounds' one trial at s = 1
+    int trial(const std::vector<int> &decided, double *sums, double *c_new) {
+        return trial(decided, std::vector<double>(c->B, 1.0), sums, c_new);
+    }
+    double cost(int b) const { return c->J_host[5 * b + 4]; }
+    int trial(const std::vector<int> &decided, const std::vector<double> &s, double *sums, double *c_new) {
+        VCHCHK(reset_counters(c));
+        VCHCHK(freeze(c, decided));
+        HIPCHK(hipEventRecord(c->ev0, c->stream));
+        VCHCHK(newton_trial_core(c, s.data(), (const int *)c->frozen_dev, sums));
+        HIPCHK(hipEventRecord(c->ev1, c->stream));
+        sec[1] += elapsed_s(c, c->ev0, c->ev1);
+        HIPCHK(hipEventRecord(c->ev0, c->stream));
+        HIPCHK(hipMemcpyAsync(c->phi_s, c->phi0, sizeof(double) * c->B * c->G.plane, hipMemcpyDeviceToDevice, c->stream));
+        VCHCHK(forward_core(c, c->u_trial, M + 1, c->dt.data(), M, c->phi_trial));
+        HIPCHK(hipEventRecord(c->ev1, c->stream));
+        sec[2] += elapsed_s(c, c->ev0, c->ev1);
+        HIPCHK(hipEventRecord(c->ev0, c->stream));
+        VCHCHK(cost_core(c, c->phi_trial, c->u_trial, c->phiQ, c->phiT, false, M, c->t_hist.data(), c->opts.data(), Jt.data(), nullptr, c->B));
+        HIPCHK(hipEventRecord(c->ev1, c->stream));
+        sec[3] += elapsed_s(c, c->ev0, c->ev1);
+        for (int b = 0; b < c->B; ++b) c_new[b] = Jt[5 * b + 4];
+        return 0;
+    }
+    int accept(int b, double c_new) {
+        std::copy_n(&Jt[5 * b], 5, &c->J_host[5 * b]);
+        c->pgd.cost[b] = c_new;
+        VCHCHK(copy_traj(c, c->u_hist, c->u_trial, b, M + 1));
+        VCHCHK(copy_traj(c, c->phi_hist, c->phi_trial, b, M + 1));
+        return copy_traj_shifts(c, b);
+    }
+    int after_trial() { return 0; }
+    int after_round() { return reset_counters(c); }
+};
+
 extern "C" int vch2d_pgd_newton(vch2d_ctx *c, int n_rounds, int k, double cg_tol, int precond, double tol, double rtol,
                                 int max_halvings, double *cost_out, double *cost_new_out, double *s_out, double *pred_out,
                                 double *rnorm0_out, int32_t *halvings_out, int32_t *cg_steps_out, int32_t *cg_status_out,
@@ -3292,54 +3383,42 @@ extern "C" int vch2d_pgd_newton(vch2d_ctx *c, int n_rounds, int k, double cg_tol
     const vch_newton_call call{B, n_rounds, k, cg_tol, precond, max_halvings, cost_out, cost_new_out, s_out, pred_out, rnorm0_out,
                                halvings_out, cg_steps_out, cg_status_out, status_out, counts_out};
     if (const char *bad = vch_newton_check(call)) return vch_fail(VCH_ERR_ARG, "%s: %s", fn, bad);
-    // the engine's side of the rounds (vch_newton.h); sec = {solves, trial controls, marches, costs}
-    struct Rounds {
-        vch2d_ctx *c;
-        const char *fn;
-        int M, k, precond;
-        double cg_tol, tol, rtol;
-        std::vector<double> resid, curv, Jt;
-        double sec[4];
-        int solve(double *pred, double *rnorm0, int32_t *steps, int32_t *status, int64_t *n_free) {
-            vch_stats st;
-            VCHCHK(hess_cg_core(c, fn, true, nullptr, M, nullptr, nullptr, nullptr, nullptr, nullptr, c->opts.data(), c->B, rtol, nullptr,
-                                tol, nullptr, k, cg_tol, precond, resid.data(), curv.data(), pred, rnorm0, steps, status, n_free, &st));
-            sec[0] += st.seconds;
-            return 0;
-        }
-        double cost(int b) const { return c->J_host[5 * b + 4]; }
-        int trial(const std::vector<int> &decided, const std::vector<double> &s, double *sums, double *c_new) {
-            VCHCHK(reset_counters(c));
-            VCHCHK(freeze(c, decided));
-            HIPCHK(hipEventRecord(c->ev0, c->stream));
-            VCHCHK(newton_trial_core(c, s.data(), (const int *)c->frozen_dev, sums));
-            HIPCHK(hipEventRecord(c->ev1, c->stream));
-            sec[1] += elapsed_s(c, c->ev0, c->ev1);
-            HIPCHK(hipEventRecord(c->ev0, c->stream));
-            HIPCHK(hipMemcpyAsync(c->phi_s, c->phi0, sizeof(double) * c->B * c->G.plane, hipMemcpyDeviceToDevice, c->stream));
-            VCHCHK(forward_core(c, c->u_trial, M + 1, c->dt.data(), M, c->phi_trial));
-            HIPCHK(hipEventRecord(c->ev1, c->stream));
-            sec[2] += elapsed_s(c, c->ev0, c->ev1);
-            HIPCHK(hipEventRecord(c->ev0, c->stream));
-            VCHCHK(cost_core(c, c->phi_trial, c->u_trial, c->phiQ, c->phiT, false, M, c->t_hist.data(), c->opts.data(), Jt.data(), nullptr, c->B));
-            HIPCHK(hipEventRecord(c->ev1, c->stream));
-            sec[3] += elapsed_s(c, c->ev0, c->ev1);
-            for (int b = 0; b < c->B; ++b) c_new[b] = Jt[5 * b + 4];
-            return 0;
-        }
-        int accept(int b, double c_new) {
-            std::copy_n(&Jt[5 * b], 5, &c->J_host[5 * b]);
-            c->pgd.cost[b] = c_new;
-            VCHCHK(copy_traj(c, c->u_hist, c->u_trial, b, M + 1));
-            VCHCHK(copy_traj(c, c->phi_hist, c->phi_trial, b, M + 1));
-            return copy_traj_shifts(c, b);
-        }
-        int after_trial() { return 0; }
-        int after_round() { return reset_counters(c); }
-    } eng{c, fn, M, k, precond, cg_tol, tol, rtol, std::vector<double>((size_t)B * k), std::vector<double>((size_t)B * k),
-          std::vector<double>(5 * (size_t)B), {0, 0, 0, 0}};
+    // the engine's side of the rounds (vch_newton.h)
+    PgdRounds eng{c, fn, M, k, precond, cg_tol, tol, rtol, std::vector<double>((size_t)B * k), std::vector<double>((size_t)B * k),
+                  std::vector<double>(5 * (size_t)B), {0, 0, 0, 0}};
     bool moved = false;
     const int rc = vch_newton_rounds(eng, call, moved);
+    if (moved) c->pgd_r_valid = false;      // r_hist is the adjoint of an iterate that has been replaced
+    if (rc < 0) (void)reset_counters(c);
+    HIPCHK(hipMemcpyAsync(c->J_dev, c->J_host.data(), sizeof(double) * 5 * B, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (rc >= 0 && seconds_out) memcpy(seconds_out, eng.sec, sizeof(eng.sec));
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------
+// Trust-region (Steihaug) Newton-CG rounds on the free set about the resident PGD iterate (kernels: k_ncg_fin_tr in
+// vch_kernels2d.h, verdicts: vch_trust_state in vch_newton.h)
+// ------------------------------------------------------------------------------------
+extern "C" int vch2d_pgd_trust(vch2d_ctx *c, int n_rounds, int k, double cg_tol, int precond, double tol, double rtol,
+                               const double *radius0, double radius_max, double radius_min, double *cost_out, double *cost_new_out,
+                               double *pred_out, double *rnorm0_out, double *radius_out, double *ratio_out, double *xnorm_out,
+                               int32_t *cg_steps_out, int32_t *cg_status_out, int32_t *status_out, int64_t *counts_out,
+                               double *seconds_out) {
+    CTXCHK(c);
+    // everything below is checked before anything is enqueued, copied or allocated
+    if (!c->pgd_ready) return vch_fail(VCH_ERR_STATE, "vch2d_pgd_trust: call vch2d_pgd_init first");
+    if (!c->res_pgd || !c->shift_res || c->M_res < 1)
+        return vch_fail(VCH_ERR_STATE, "vch2d_pgd_trust: the resident state history is no longer the PGD iterate's (call vch2d_pgd_init again)");
+    const char *fn = "vch2d_pgd_trust";
+    const int B = c->B, M = c->M_res;
+    const vch_trust_call call{B, n_rounds, k, cg_tol, precond, radius0, radius_max, radius_min, cost_out, cost_new_out, pred_out,
+                              rnorm0_out, radius_out, ratio_out, xnorm_out, cg_steps_out, cg_status_out, status_out, counts_out};
+    if (const char *bad = vch_trust_check(call)) return vch_fail(VCH_ERR_ARG, "%s: %s", fn, bad);
+    PgdRounds eng{c, fn, M, k, precond, cg_tol, tol, rtol, std::vector<double>((size_t)B * k), std::vector<double>((size_t)B * k),
+                  std::vector<double>(5 * (size_t)B), {0, 0, 0, 0}};
+    bool moved = false;
+    const int rc = vch_trust_rounds(eng, call, moved);
     if (moved) c->pgd_r_valid = false;      // r_hist is the adjoint of an iterate that has been replaced
     if (rc < 0) (void)reset_counters(c);
     HIPCHK(hipMemcpyAsync(c->J_dev, c->J_host.data(), sizeof(double) * 5 * B, hipMemcpyHostToDevice, c->stream));

@@ -4010,6 +4010,119 @@ __global__ __launch_bounds__(NTH) void k_ncg_fin(NcgCells x, const double *__res
 }
 
 // ---------------------------------------------------------------------------------
+// Truncated (Steihaug-Toint) conjugate gradients in a trust region (vch2d_hess_cg_tr): the iteration above
+// with k_ncg_fin_tr in place of k_ncg_fin, every other kernel unchanged.  The region is ||x||_D <= radius with the
+// preconditioner's D (the identity without it).  Since x_0 = 0, the recurrences xx = ||x||_D^2 and xp = x.D p start at 0:
+//   x' = x + alpha p:   xx' = xx + 2 alpha xp + alpha^2 pp
+//   p' = D^-1 r' + beta p, x'.r' = 0:   xp' = beta (xp + alpha pp)
+// tau = the positive root of xx + 2 tau xp + tau^2 pp = radius^2.  An exit on the boundary is pending between mode 2 and
+// mode 3: the stop cell and look[1] stay 0, so that k_ncg_update runs once more with alpha = tau and r stays P b - P H P x.
+// ---------------------------------------------------------------------------------
+enum { NCG_BOUNDARY = 4 };                      // VCH_CG_BOUNDARY of vch.h
+struct NtrCells {
+    const double *radius;             // [B]
+    double *xx, *xp, *pp, *c;         // [B] ||x||_D^2, x.D p, p.D p and p.P H p of the step
+    long long *pend;                  // [B] the exit mode 3 takes: 0, NCG_NEGCURV or NCG_BOUNDARY
+};
+// tau >= 0 with xx + 2 tau xp + tau^2 pp = d2 (xx <= d2, pp > 0), in the form without cancellation for either sign of xp
+__device__ __forceinline__ double ntr_tau(double xx, double xp, double pp, double d2) {
+    const double gap = fmax(d2 - xx, 0.0), disc = sqrt(xp * xp + pp * gap);
+    return xp > 0.0 ? gap / (xp + disc) : (disc - xp) / pp;
+}
+// ncg_sum, word for word: a copy for the reason given there, so that k_ncg_fin keeps its registers too.
+__device__ __forceinline__ double ntr_sum(const double *__restrict__ part, long n, int pstride, int slot, double *sh) {
+    double s = 0.0;
+    for (long e = threadIdx.x; e < n; e += NTH) s += part[e * pstride + slot];
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    for (int h = NTH / 2; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) sh[threadIdx.x] += sh[threadIdx.x + h];
+        __syncthreads();
+    }
+    const double r = sh[0];
+    __syncthreads();
+    return r;
+}
+// mode 1   as k_ncg_fin, then xx = xp = 0 and nothing pending.
+// mode 2   as k_ncg_fin, then: c not finite: BREAKDOWN; !(c > 0): alpha = tau, pending NEGCURV; the step rho / c would
+//          leave the region (xx + 2 alpha xp + alpha^2 pp >= radius^2): alpha = tau, pending BOUNDARY; otherwise alpha = rho / c.
+//          A tau that is not finite (radius = +inf on a direction of non-positive curvature) stops at once with NEGCURV as
+//          k_ncg_fin does: x stays as it is.
+// mode 3   pending: pred += tau rho - tau^2 c / 2, resid[j], steps = j + 1, xx by its recurrence, stop = the pending exit;
+//          otherwise k_ncg_fin's arithmetic, then xx and (still running) xp by their recurrences.
+__global__ __launch_bounds__(NTH) void k_ncg_fin_tr(NcgCells x, NtrCells t, const double *__restrict__ part, long n, int pstride,
+                                                    int mode, int j, int k, double cg_tol) {
+    __shared__ double sh[NTH];
+    const int b = blockIdx.x;
+    const double *p = part + (long)b * n * pstride;
+    if (mode != 1 && x.stop[b]) return;     // uniform: stopped at an earlier step
+    const double s0 = ntr_sum(p, n, pstride, 0, sh), s1 = ntr_sum(p, n, pstride, 1, sh);
+    if (threadIdx.x != 0) return;
+    long long st = NCG_RUNNING;
+    if (mode == 1) {
+        const double nb = sqrt(s0);
+        x.rnorm0[b] = nb;
+        x.rho[b] = s1;
+        x.pred[b] = 0.0;
+        x.steps[b] = 0;
+        x.look[2 * b] = nb;
+        st = nb == 0.0 ? NCG_CONVERGED : NCG_RUNNING;
+        t.xx[b] = 0.0;
+        t.xp[b] = 0.0;
+        t.pend[b] = NCG_RUNNING;
+    } else if (mode == 2) {
+        const double xx = t.xx[b], xp = t.xp[b];
+        x.curv[(long)b * k + j] = s0 / s1;
+        long long pend = NCG_RUNNING;
+        if (!isfinite(s0)) {
+            st = NCG_BREAKDOWN;
+        } else {
+            const double rad = t.radius[b], d2 = rad * rad;
+            double al = 0.0;
+            if (!(s0 > 0.0)) {
+                pend = NCG_NEGCURV;
+            } else {
+                al = x.rho[b] / s0;
+                if (xx + 2.0 * al * xp + al * al * s1 >= d2) pend = NCG_BOUNDARY;
+            }
+            if (pend) al = ntr_tau(xx, xp, s1, d2);
+            if (pend && !isfinite(al)) {
+                st = NCG_NEGCURV;
+                pend = NCG_RUNNING;
+            } else {
+                x.alpha[b] = al;
+            }
+        }
+        t.pp[b] = s1;
+        t.c[b] = s0;
+        t.pend[b] = pend;
+    } else {
+        const long long pend = t.pend[b];
+        const double xx = t.xx[b], xp = t.xp[b];
+        const double rho = x.rho[b], res = sqrt(s0) / x.rnorm0[b], al = x.alpha[b], pp = t.pp[b];
+        x.resid[(long)b * k + j] = res;
+        x.steps[b] = j + 1;
+        x.look[2 * b] = res;
+        if (pend) {
+            x.pred[b] += al * rho - 0.5 * (al * al) * t.c[b];
+            st = pend;
+        } else {
+            x.pred[b] += 0.5 * x.alpha[b] * rho;
+            if (!isfinite(res) || !isfinite(s1)) st = NCG_BREAKDOWN;
+            else if (res <= cg_tol) st = NCG_CONVERGED;
+            else {
+                x.beta[b] = s1 / rho;
+                x.rho[b] = s1;
+            }
+        }
+        t.xx[b] = xx + 2.0 * al * xp + al * al * pp;
+        if (st == NCG_RUNNING) t.xp[b] = x.beta[b] * (xp + al * pp);
+    }
+    x.stop[b] = st;
+    x.look[2 * b + 1] = (double)st;
+}
+
+// ---------------------------------------------------------------------------------
 // Damped Newton rounds on the free set (vch2d_pgd_newton, vch2d_newton_trial): the trial control of a step
 // length.  Tiling and partials are those of the Newton-CG passes above (KrArgs, KR_COORDS / KR_NODES; x is slot NCG_X), the
 // partials here have 4 slots per workgroup: {sum (t - u)^2, sum u^2, nodes pinned to 0, nodes the clip moved}, the counts

@@ -612,6 +612,75 @@ class Engine2D:
         check(self.lib.vch2d_newton_trial(self.ctx, _dp(s), _dp(out), _dp(chg), cnt.ctypes.data_as(C.POINTER(C.c_int64))))
         return dict(u=out, change=chg, pinned=cnt[:, 0].copy(), clipped=cnt[:, 1].copy())
 
+    TRUST_CG_STATUS = CG_STATUS + ("boundary",)                     # VCH_CG_LIMIT .. VCH_CG_BOUNDARY
+    TRUST_STATUS = NEWTON_STATUS + ("rejected",)                    # VCH_NEWTON_ACCEPTED .. _REJECTED
+
+    def hess_cg_trust(self, k, radius, rhs=None, cg_tol=0.0, precond=True, mask=None, tol=0.0, dt=None, t_hist=None, opt=None,
+                      phi_Q=None, phi_T=None, x=None, y=None, rtol=0.0):
+        """Truncated (Steihaug-Toint) conjugate gradients on P H P x = P b inside ||x||_D <= radius_b (vch2d_hess_cg_tr):
+        hess_cg with a trust region in the preconditioner's norm, ||x||_D^2 = sum D x^2, D = diag(wt W_cost) with precond and
+        the identity without.  radius: [B] or a scalar, > 0, +inf allowed.  A step that would leave the region, or a
+        direction of non-positive curvature, is followed to the boundary: "boundary" and "negcurv" of TRUST_CG_STATUS.
+        Returns hess_cg's dict (status: indices of TRUST_CG_STATUS) plus xnorm: [B] ||x||_D by the recurrence.  With
+        radius = inf everything equals hess_cg's bit for bit on a trajectory that ends "converged" or "limit"."""
+        k = int(k)
+        dt, t_hist, x, y, M = self._base_point(dt, t_hist, x, y)
+        rhs = None if rhs is None else self._hist(rhs, M + 1, "rhs")
+        mask = self._free_mask(mask, M)
+        pq = None if phi_Q is None else self._hist(phi_Q, M + 1, "phi_Q_target")
+        pt = None if phi_T is None else self._fld(phi_T, "phi_T_target")
+        seq = list(opt) if isinstance(opt, (list, tuple)) else [opt]
+        arr = (OptParams * len(seq))(*[o if isinstance(o, OptParams) else make_opt(o) for o in seq])
+        radius = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float64), (self.B,)))
+        kk = max(k, 1)
+        resid, curv = np.full((self.B, kk), np.nan), np.full((self.B, kk), np.nan)
+        pred, rnorm0, xnorm = np.full(self.B, np.nan), np.full(self.B, np.nan), np.full(self.B, np.nan)
+        steps, status, n_free = np.zeros(self.B, dtype=np.int32), np.zeros(self.B, dtype=np.int32), np.zeros(self.B, dtype=np.int64)
+        st = Stats()
+        precond = int(precond) if isinstance(precond, (bool, int, np.integer)) else -1
+        check(self.lib.vch2d_hess_cg_tr(self.ctx, _dp(dt), M, _dp(t_hist), _dp(x), _dp(y), _dp(pq), _dp(pt), arr, len(seq),
+                                        float(rtol), None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                        float(tol), _dp(rhs), k, float(cg_tol), precond, _dp(resid), _dp(curv), _dp(pred),
+                                        _dp(rnorm0), steps.ctypes.data_as(_lib._I32), status.ctypes.data_as(_lib._I32),
+                                        n_free.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(st), _dp(radius), _dp(xnorm)))
+        self._cg_rows = M + 1
+        return dict(steps=steps, status=status, n_free=n_free, resid=resid, curv=curv, pred=pred, rnorm0=rnorm0, xnorm=xnorm,
+                    stats=st.as_dict())
+
+    def pgd_trust(self, n_rounds, radius0, k=50, cg_tol=1e-8, precond=True, tol=0.0, rtol=0.0, radius_max=None, radius_min=None):
+        """Trust-region (Steihaug) Newton-CG rounds on the free set about the resident PGD iterate (vch2d_pgd_trust), every
+        trajectory with its own parameters, radius and decisions; no history crosses the bus.  Per round: the step of
+        hess_cg_trust(rhs=None) inside the trajectory's radius (a direction of non-positive curvature is followed to the
+        boundary and does not end the trajectory), one trial clip(u + x, box) as newton_trial(1) builds it,
+        rho = (J(u) - J(trial)) / pred.  The trial is accepted iff J(trial) is finite and <= J(u) - 1e-4 pred; otherwise the
+        trajectory stays unmoved, "rejected", and goes on.  The radius: rho < 1/4 or not finite: min(radius, ||x||_D) / 4;
+        else rho > 3/4 after a "boundary" or "negcurv" exit: min(2 radius, radius_max).  A trajectory ends "stationary",
+        "breakdown", or "stalled" (rejected with the radius below radius_min) and is "idle" afterwards.  radius0: [B] or a
+        scalar, finite and > 0; radius_max / radius_min default to 1024 max(radius0) and 1e-10 min(radius0).  Returns the
+        keys of Engine1D.pgd_trust: dict(rounds; cost, cost_new, pred, rnorm0, radius (the round's), ratio, xnorm:
+        (B, n_rounds), NaN where idle; cg_steps, cg_status (indices of TRUST_CG_STATUS), status (indices of TRUST_STATUS):
+        int32 (B, n_rounds); n_free, pinned, clipped: int64 (B, n_rounds); seconds)."""
+        n = max(int(n_rounds), 1)
+        radius0 = np.ascontiguousarray(np.broadcast_to(np.asarray(radius0, dtype=np.float64), (self.B,)))
+        radius_max = 1024.0 * float(np.max(radius0)) if radius_max is None else float(radius_max)
+        radius_min = 1e-10 * float(np.min(radius0)) if radius_min is None else float(radius_min)
+        dbl = [np.full((self.B, n), np.nan) for _ in range(7)]
+        i32 = [np.zeros((self.B, n), dtype=np.int32) for _ in range(3)]
+        cnt = np.zeros((self.B, n, 3), dtype=np.int64)
+        sec = np.zeros(4)
+        precond = int(precond) if isinstance(precond, (bool, int, np.integer)) else -1
+        done = check(self.lib.vch2d_pgd_trust(self.ctx, int(n_rounds), int(k), float(cg_tol), precond, float(tol), float(rtol),
+                                              _dp(radius0), radius_max, radius_min, *[_dp(a) for a in dbl],
+                                              *[a.ctypes.data_as(_lib._I32) for a in i32],
+                                              cnt.ctypes.data_as(C.POINTER(C.c_int64)), _dp(sec)))
+        self._base = ("pgd", self._pgd_M, self._pgd_M + 1)
+        self._cg_rows = self._pgd_M + 1
+        out = dict(zip(("cost", "cost_new", "pred", "rnorm0", "radius", "ratio", "xnorm"), dbl), rounds=done)
+        out.update(zip(("cg_steps", "cg_status", "status"), i32))
+        out.update(n_free=cnt[:, :, 0].copy(), pinned=cnt[:, :, 1].copy(), clipped=cnt[:, :, 2].copy(),
+                   seconds=dict(zip(("solve", "trial", "forward", "cost"), sec)))
+        return out
+
     def mass_shifts(self):
         """(B, M): what the march's interior mass fix subtracted at the end of every step of the resident state history
         (vch2d_mass_shifts; zeros where the fix was not applied); M = the steps of that history."""
