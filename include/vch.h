@@ -710,6 +710,56 @@ int vch1d_pgd_kkt(vch1d_ctx *ctx, int refresh, double tol, int64_t *counts_out /
  * same conventions as vch2d_pgd_errors. */
 int vch1d_pgd_errors(vch1d_ctx *ctx, int n_iters, double *tracking_out, double *terminal_out);
 
+/* Directional sparsity in the 1D engine (ABI version stays 3: detect the three entry points below by symbol).
+ * Beside the full-sparsity term g(u) = kappa_s int int |u| (VCH_SPARSITY_FULL: a node-wise soft threshold, everything
+ * above) the sparsity term and its prox can be taken by groups:
+ *   VCH_SPARSITY_TIME   g(u) = kappa_s int_0^T ||u(., t)||_{L2(Omega)} dt: group k is row k of the control,
+ *                       ||z||^2 = sum_i wx_i z_i^2; the control vanishes on whole time intervals.
+ *   VCH_SPARSITY_SPACE  g(u) = kappa_s int_Omega ||u(x, .)||_{L2(0,T)} dx: group i is column i, ||z||^2 = sum_k wt_k z_k^2;
+ *                       the control vanishes on whole regions for all times.
+ * wx = the trapezoid weights of x, wt those of t_hist (0 for the duplicated t = 0 row).  The prox is taken in the L2(Q)
+ * metric like the node-wise threshold, so the threshold is lam = alpha kappa_s for every group.  With v = u - alpha (r + b3 u)
+ * and the box u_min <= 0 <= u_max, per group:
+ *   c = ||cone(v)|| <= lam (cone drops the positive entries when u_max == 0, the negative ones when u_min == 0): u+ = 0, s = 0;
+ *   otherwise u+ = clip(s v), s in (0, 1] the root of h(s) = ||clip(s v)|| (1 - s) - lam s; where clip(s0 v) = s0 v for
+ *   s0 = 1 - lam / ||v|| (always with an infinite box) s = s0, else a safeguarded Newton iteration on the device finds it.
+ * The cost's J4 becomes kappa_s * trapezoid in t of sqrt(sum_i wx_i u^2) (TIME) or kappa_s sum_i wx_i sqrt(sum_k wt_k u^2)
+ * (SPACE); J1..J3 are unchanged.  No atomics: a member of a mixed batch computes the bits of a single run with its mode and
+ * parameters.
+ *
+ * vch1d_pgd_init_g: vch1d_pgd_init_v with a mode per trajectory: sparsity[n_sparsity], n_sparsity = 1 or B.  All
+ * VCH_SPARSITY_FULL is vch1d_pgd_init_v bit for bit; vch1d_pgd_init and vch1d_pgd_init_v reset every mode to FULL.
+ * VCH_ERR_ARG, before anything is copied or enqueued and with the resident problem left as it was: NULL sparsity, n_sparsity
+ * neither 1 nor B, a mode outside 0..2, a group-mode trajectory whose box does not contain 0.
+ * vch1d_pgd_iterate, vch1d_pgd_kkt, vch1d_pgd_get and vch1d_pgd_errors then act per trajectory on its mode.  For a
+ * group-mode trajectory vch1d_pgd_kkt counts groups: counts_out[b] = { #groups ||u_g|| < tol, #groups ||r_g|| <=
+ * kappa_sparsity, #groups where the two agree, #groups } in the group's norm (a group of the optimal control is zero exactly
+ * when ||r_g|| <= kappa_s, for u_min < 0 < u_max), and the stationarity takes the mode's prox at alpha = 1.
+ * Refused with VCH_ERR_STATE before anything is enqueued while any trajectory of the resident problem is in a group mode:
+ * vch1d_pgd_newton, vch1d_pgd_trust, and vch1d_hess_cg / vch1d_hess_cg_tr with u == VCH_RESIDENT and rhs == NULL: they build
+ * the sign term and the free set of the L1 functional.  vch1d_second_order, vch1d_hessvec, vch1d_hess_lanczos and
+ * vch1d_hess_cg with an explicit rhs concern the smooth part only and keep working. */
+#define VCH_SPARSITY_FULL 0
+#define VCH_SPARSITY_TIME 1
+#define VCH_SPARSITY_SPACE 2
+int vch1d_pgd_init_g(vch1d_ctx *ctx, const double *phi0, const double *phi_T, const double *phi_Q,
+                     const double *x, const double *t_hist, int rows, const double *dt,
+                     const vch_opt_params *opts, int n_opts,
+                     const double *u0 /* [B][rows][N+1] or NULL */, const double *alpha0 /* [B] or NULL */,
+                     const int32_t *sparsity /* [n_sparsity] */, int n_sparsity /* 1 or B */,
+                     double *J0_out /* [B][5] */);
+/* The stateless seam of the prox: vch1d_grad_prox with the mode `sparsity` for the whole batch.  x [N+1] (TIME) and t_hist
+ * [rows] (SPACE) give the group's weights and may be NULL where the mode does not read them.  scale_out (or NULL) receives
+ * s per group, [B][rows] for TIME or [B][N+1] for SPACE.  VCH_SPARSITY_FULL is vch1d_grad_prox (scale_out is not written).
+ * VCH_ERR_ARG for a mode outside 0..2 and, in a group mode, for a box that does not contain 0. */
+int vch1d_grad_prox_g(vch1d_ctx *ctx, const double *u, const double *r, int rows, const double *x,
+                      const double *t_hist, const double *alpha, const vch_opt_params *opt, int sparsity,
+                      double *u_out, double *scale_out);
+/* vch1d_cost with J4 of the mode `sparsity`; VCH_SPARSITY_FULL is vch1d_cost. */
+int vch1d_cost_g(vch1d_ctx *ctx, const double *phi_hist, const double *u, const double *phi_Q,
+                 const double *phi_T, int rows, const double *x, const double *t_hist,
+                 const vch_opt_params *opt, int sparsity, double *J_out);
+
 /* Exact first and second directional derivatives of the smooth part J1 + J2 + J3 of the 1D cost along h, by a tangent
  * (linearised) march on the device: the 1D counterpart of vch2d_second_order (ABI version stays 3: detect this entry point
  * by symbol).  One persistent workgroup per direction runs the whole march and the quadrature; no adjoint, no nonlinear

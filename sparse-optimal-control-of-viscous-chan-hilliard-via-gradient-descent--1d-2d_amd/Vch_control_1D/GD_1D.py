@@ -33,18 +33,46 @@ def perform_proximal_and_projection(u_temp, alpha, kappa, u_min, u_max):
     return np.asarray(out).reshape(shp)
 
 
+def perform_group_proximal_and_projection(u_temp, alpha, kappa, u_min, u_max, sparsity, x, t_hist):
+    """perform_proximal_and_projection for the directional sparsity functionals: the prox of
+    alpha * kappa * sum of the group norms under the box, the groups being the rows ("time") or the columns ("space") of the
+    (rows, N+1) control; the engine's group kernel with r = 0, b3 = 0 on the already stepped control."""
+    u2 = np.asarray(u_temp, dtype=np.float64)
+    eng = engine_for(u2.shape[1] - 1, float(x[-1] - x[0]), max_steps=max(u2.shape[0], 1))
+    o = make_opt(b3=0.0, kappa_sparsity=float(kappa), u_min=float(u_min), u_max=float(u_max))
+    return np.asarray(eng.grad_prox(u2, np.zeros_like(u2), float(alpha), o, sparsity=sparsity, x=x, t_hist=t_hist))
+
+
+def _prox(u_temp, alpha, kappa, u_min, u_max, sparsity, x, t_hist):
+    if sparsity == "full":
+        return perform_proximal_and_projection(u_temp, alpha, kappa, u_min, u_max)
+    return perform_group_proximal_and_projection(u_temp, alpha, kappa, u_min, u_max, sparsity, x, t_hist)
+
+
+def _cost(phi, u, phi_Q, phi_T, x, t_hist, b1, b2, b3, kappa, sparsity):
+    """calculate_cost, silent, with J4 of the sparsity mode."""
+    if sparsity == "full":
+        with contextlib.redirect_stdout(io.StringIO()):
+            return calculate_cost(phi, u, phi_Q, phi_T, x, t_hist, b1, b2, b3, kappa, verbose=False)
+    rows, n = phi.shape
+    eng = engine_for(n - 1, float(x[-1] - x[0]), max_steps=max(rows - 2, 1))
+    J = eng.cost(phi, u, phi_Q, phi_T, x, t_hist, make_opt(b1=b1, b2=b2, b3=b3, kappa_sparsity=kappa), sparsity=sparsity)
+    return float(J[4])
+
+
 def perform_backtracking_line_search(u_k, cost_k, grad_smooth, phi_Q_target, phi_T_target, x, t_hist, b1, b2, b3,
-                                     kappa, u_min, u_max, fwd_config, alpha_init=10.0, beta=0.8, max_ls_iter=5):
+                                     kappa, u_min, u_max, fwd_config, alpha_init=10.0, beta=0.8, max_ls_iter=5,
+                                     sparsity="full", initial_phi=None):
     """G1:73-113."""
     alpha, n_trials = alpha_init, 0
     u_next = phi_next = None
     cost_next = cost_k
     for _ in range(max_ls_iter):
         n_trials += 1
-        u_next = perform_proximal_and_projection(perform_gradient_step(u_k, grad_smooth, alpha), alpha, kappa, u_min, u_max)
-        phi_next, _, _ = run_main_simulation(fwd_config, store_history=True, control_input=u_next, verbose=False)
-        with contextlib.redirect_stdout(io.StringIO()):
-            cost_next = calculate_cost(phi_next, u_next, phi_Q_target, phi_T_target, x, t_hist, b1, b2, b3, kappa, verbose=False)
+        u_next = _prox(perform_gradient_step(u_k, grad_smooth, alpha), alpha, kappa, u_min, u_max, sparsity, x, t_hist)
+        phi_next, _, _ = run_main_simulation(fwd_config, store_history=True, control_input=u_next, verbose=False,
+                                             initial_phi=initial_phi)
+        cost_next = _cost(phi_next, u_next, phi_Q_target, phi_T_target, x, t_hist, b1, b2, b3, kappa, sparsity)
         if cost_next < cost_k:
             return alpha, u_next, cost_next, phi_next, 0.0, 0.0, n_trials
         alpha *= beta
@@ -99,33 +127,41 @@ def relative_errors(phi, phi_Q, phi_T, x, t_hist):
 
 
 def run_optimization(fwd_config: ForwardSolverConfig, opt_config: OptimizationConfig, n_iter=None, choice_t=1,
-                     choice_q=1):
-    """The loop of G1:333-477 -> dict(costs, alphas, trials, tracking_error, terminal_error, u, phi, r, converged)."""
+                     choice_q=1, sparsity="full", initial_phi=None):
+    """The loop of G1:333-477 -> dict(costs, alphas, trials, tracking_error, terminal_error, u, phi, r, converged).
+    `sparsity` "time" / "space": the same loop with the prox and J4 of the directional sparsity functional (a name of
+    Engine1D.SPARSITY; "full" is the reference's loop).  `initial_phi` (N+1,): the start state of every march (default:
+    the reference's seed 42)."""
+    from ..engine import Engine1D
+    Engine1D._mode(sparsity)
     O = opt_config
     quiet = contextlib.redirect_stdout(io.StringIO())
-    phi_k, x, t_hist = run_main_simulation(fwd_config, store_history=True, verbose=False)
+    phi_k, x, t_hist = run_main_simulation(fwd_config, store_history=True, verbose=False, initial_phi=initial_phi)
     u_k = np.zeros_like(phi_k)
     phi_T, phi_Q = build_targets_1d(x, t_hist, phi_k[0].copy(), float(fwd_config.Lx), float(fwd_config.T),
                                     choice_t=choice_t, choice_q=choice_q)
-    with quiet:
-        cost_k = calculate_cost(phi_k, u_k, phi_Q, phi_T, x, t_hist, O.b1, O.b2, O.b3, O.kappa_sparsity)
+    if sparsity == "full":
+        with quiet:
+            cost_k = calculate_cost(phi_k, u_k, phi_Q, phi_T, x, t_hist, O.b1, O.b2, O.b3, O.kappa_sparsity)
+    else:
+        cost_k = _cost(phi_k, u_k, phi_Q, phi_T, x, t_hist, O.b1, O.b2, O.b3, O.kappa_sparsity, sparsity)
     costs, alphas, trials, track, term = [cost_k], [], [], [], []
     alpha_prev, plateau, converged = O.alpha_max, 0, False
     r_k = None
     for k in range(O.max_iter if n_iter is None else n_iter):
         _, _, r_k = run_backward(phi_k, x, t_hist, O.b1, O.b2, phi_Q, phi_T)
         g = calculate_gradient(r_k, u_k, O.b3)
-        u_o = perform_proximal_and_projection(perform_gradient_step(u_k, g, alpha_prev), alpha_prev,
-                                              O.kappa_sparsity, O.u_min, O.u_max)
-        phi_o, _, _ = run_main_simulation(fwd_config, store_history=True, control_input=u_o, verbose=False)
-        with contextlib.redirect_stdout(io.StringIO()):
-            c_o = calculate_cost(phi_o, u_o, phi_Q, phi_T, x, t_hist, O.b1, O.b2, O.b3, O.kappa_sparsity, verbose=False)
+        u_o = _prox(perform_gradient_step(u_k, g, alpha_prev), alpha_prev, O.kappa_sparsity, O.u_min, O.u_max, sparsity, x,
+                    t_hist)
+        phi_o, _, _ = run_main_simulation(fwd_config, store_history=True, control_input=u_o, verbose=False,
+                                          initial_phi=initial_phi)
+        c_o = _cost(phi_o, u_o, phi_Q, phi_T, x, t_hist, O.b1, O.b2, O.b3, O.kappa_sparsity, sparsity)
         if c_o < cost_k:
             a_k, u_n, c_n, phi_n, nt = alpha_prev, u_o, c_o, phi_o, 1
         else:
             a_k, u_n, c_n, phi_n, _, _, nt = perform_backtracking_line_search(
                 u_k, cost_k, g, phi_Q, phi_T, x, t_hist, O.b1, O.b2, O.b3, O.kappa_sparsity, O.u_min, O.u_max,
-                fwd_config, alpha_init=alpha_prev)
+                fwd_config, alpha_init=alpha_prev, sparsity=sparsity, initial_phi=initial_phi)
         costs.append(c_n); alphas.append(a_k); trials.append(nt)
         e_q, e_t = relative_errors(phi_n, phi_Q, phi_T, x, t_hist)
         track.append(e_q); term.append(e_t)
@@ -144,11 +180,12 @@ def run_optimization(fwd_config: ForwardSolverConfig, opt_config: OptimizationCo
 
 
 def run_optimization_resident(fwd_config: ForwardSolverConfig, opt_config: OptimizationConfig, n_iter=None, choice_t=1,
-                              choice_q=1, initial_phi=None, seeds=None):
+                              choice_q=1, initial_phi=None, seeds=None, sparsity="full"):
     """The same loop (G1:333-477) run device-resident through `vch1d_pgd_*`: control, state history,
     adjoint and targets never leave HBM between iterations.  `seeds` (a list) or `initial_phi`
     ((B, N+1)) gives a batch of trajectories; default = the reference's seed 42.  Returns the same
-    dict as run_optimization, with a leading trajectory axis when batched."""
+    dict as run_optimization, with a leading trajectory axis when batched.  `sparsity`: a name of Engine1D.SPARSITY for
+    every trajectory, or a list with one name per trajectory; "full" takes the calls of the reference's loop exactly."""
     from ..engine import Engine1D, time_grid
     from .Forward_solver import init_phi_random, delta_sep
     O = opt_config
@@ -169,7 +206,8 @@ def run_optimization_resident(fwd_config: ForwardSolverConfig, opt_config: Optim
         phi_T = np.stack([build_targets_1d(x, t_hist, phi0[b], float(fwd_config.Lx), float(fwd_config.T),
                                            choice_t=choice_t, choice_q=2)[0] for b in range(B)])
         phi_Q = None if choice_q == 1 else np.zeros((B, len(t_hist), N + 1))
-        J0 = eng.pgd_init(phi0, phi_T, t_hist, dts, make_opt(O), phi_Q=phi_Q, x=x)
+        J0 = eng.pgd_init(phi0, phi_T, t_hist, dts, make_opt(O), phi_Q=phi_Q, x=x,
+                          sparsity=None if isinstance(sparsity, str) and sparsity == "full" else sparsity)
         n = O.max_iter if n_iter is None else n_iter
         res = eng.pgd_iterate(n)
         sq = (lambda a: a[0]) if B == 1 else (lambda a: a)
@@ -183,7 +221,7 @@ def run_optimization_resident(fwd_config: ForwardSolverConfig, opt_config: Optim
 
 
 def run_sweep(fwd_config: ForwardSolverConfig, opt_configs, n_iter=None, seed=42, amp=0.01, initial_phi=None, choice_t=1,
-              choice_q=1, u0=None, return_controls=False, n_newton=0, n_trust=0, radius0=1.0):
+              choice_q=1, u0=None, return_controls=False, n_newton=0, n_trust=0, radius0=1.0, sparsity=None):
     """A parameter sweep as ONE batch: member b runs the PGD loop with opt_configs[b] (weights, sparsity parameter, box,
     alpha_max), all members from the same initial state (`initial_phi` (N+1,), else `seed`, `amp`) and targets, so that
     they differ by their parameters only.  `u0`: start control, one (rows, N+1) array for every member or one per member
@@ -197,7 +235,8 @@ def run_sweep(fwd_config: ForwardSolverConfig, opt_configs, n_iter=None, seed=42
     are then those of the polished iterate.  0 leaves the result as it is without the polish.  `n_trust` > 0 does the same
     (after the Newton rounds, if both are asked for) with that many trust-region rounds from the radius `radius0`
     (Engine1D.pgd_trust), which follow a direction of non-positive curvature instead of ending on it, and adds `trust` and
-    `costs_trust` [B][n_trust+1]."""
+    `costs_trust` [B][n_trust+1].  `sparsity`: None (every member "full", today's calls), one name of Engine1D.SPARSITY or one
+    per member; the Newton and trust-region polish is refused by the engine while a member is in a group mode."""
     from ..engine import Engine1D, time_grid
     from .Forward_solver import init_phi_random, delta_sep
     opt_configs = list(opt_configs)
@@ -223,7 +262,7 @@ def run_sweep(fwd_config: ForwardSolverConfig, opt_configs, n_iter=None, seed=42
                                  choice_q=2)[0]
         phi_Q = None if choice_q == 1 else np.zeros((B, len(t_hist), N + 1))
         J0 = eng.pgd_init(phi0, np.repeat(phi_T[None], B, axis=0), t_hist, dts, [make_opt(o) for o in opt_configs],
-                          phi_Q=phi_Q, x=x, u0=u0)
+                          phi_Q=phi_Q, x=x, u0=u0, sparsity=sparsity)
         n = int(max(int(o.max_iter) for o in opt_configs) if n_iter is None else n_iter)
         res = eng.pgd_iterate(n)
         newton = eng.pgd_newton(int(n_newton)) if int(n_newton) > 0 else None

@@ -173,6 +173,9 @@ SIGNATURES = {
     "vch1d_free_energy": (C.c_int, [_P, _D, C.c_int, _D, C.c_double, C.c_double, _D]),
     "vch1d_pgd_init": (C.c_int, [_P, _D, _D, _D, _D, _D, C.c_int, _D, C.POINTER(OptParams), _D]),
     "vch1d_pgd_init_v": (C.c_int, [_P, _D, _D, _D, _D, _D, C.c_int, _D, C.POINTER(OptParams), C.c_int, _D, _D, _D]),
+    "vch1d_pgd_init_g": (C.c_int, [_P, _D, _D, _D, _D, _D, C.c_int, _D, C.POINTER(OptParams), C.c_int, _D, _D, _I32, C.c_int, _D]),
+    "vch1d_grad_prox_g": (C.c_int, [_P, _D, _D, C.c_int, _D, _D, _D, C.POINTER(OptParams), C.c_int, _D, _D]),
+    "vch1d_cost_g": (C.c_int, [_P, _D, _D, _D, _D, C.c_int, _D, _D, C.POINTER(OptParams), C.c_int, _D]),
     "vch1d_pgd_kkt": (C.c_int, [_P, C.c_int, C.c_double, C.POINTER(C.c_int64), _D]),
     "vch1d_pgd_iterate": (C.c_int, [_P, C.c_int, _D, _D, _I32, _D, _D]),
     "vch1d_pgd_get": (C.c_int, [_P, C.c_int, _D]),

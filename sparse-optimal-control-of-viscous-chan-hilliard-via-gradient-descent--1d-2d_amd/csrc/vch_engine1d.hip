@@ -69,7 +69,20 @@ struct vch1d_ctx {
     // its state history and stored cost brought up to its control (the stop quirk)
     std::vector<double> dt_host, x_host;
     std::vector<int> pgd_synced;
+    // directional sparsity: the resident problem's mode per trajectory (empty or all VCH_SPARSITY_FULL: none
+    // of what follows is allocated or launched), its device copy, the time weights [Mmax+2], s per group [B][max(Mmax+2, n)],
+    // the column kernel's change partials [B][gp_nblk][2], the squared column norms [B][n] with their host copy, alpha = 1
+    std::vector<int> modes;
+    int *mode_dev = nullptr;
+    double *gp_wt = nullptr, *gp_s = nullptr, *gp_chg = nullptr, *gp_col = nullptr, *gp_one = nullptr;
+    std::vector<double> gp_chg_host, gp_col_host, wx_host;
 };
+
+static inline int gp_nblk(const vch1d_ctx *c) { return (c->n + 63) / 64; }
+static inline long gp_ss(const vch1d_ctx *c) { return std::max(c->Mmax + 2, c->n); }
+static bool gp_any(const vch1d_ctx *c, int mode) { return std::find(c->modes.begin(), c->modes.end(), mode) != c->modes.end(); }
+static bool gp_group(const vch1d_ctx *c) { return gp_any(c, VCH_SPARSITY_TIME) || gp_any(c, VCH_SPARSITY_SPACE); }
+static int gp_mode(const vch1d_ctx *c, int b) { return c->modes.empty() ? VCH_SPARSITY_FULL : c->modes[b]; }
 
 // no launch bookkeeping (LAUNCH_LDS, vch_common.h)
 static bool launch_begin(vch1d_ctx *, int) { return false; }
@@ -359,10 +372,32 @@ static std::vector<double> trapz_w1(const double *t, int n) {
     return w;
 }
 
-extern "C" int vch1d_cost(vch1d_ctx *c, const double *phi_hist, const double *u, const double *phi_Q, const double *phi_T,
-                          int rows, const double *x, const double *t_hist, const vch_opt_params *o, double *J_out) {
-    CTXCHK(c);
-    ARGCHK(phi_hist && x && t_hist && o && J_out && rows >= 2 && rows <= c->Mmax + 2, "NULL argument or rows out of range");
+// what a group-mode function seam needs beyond its histories: the column norms, s per group and the time weights of t_hist
+// (NULL: not needed) on the device
+static int gp_tables(vch1d_ctx *c, const double *t_hist, int rows) {
+    VCHCHK(dalloc1(c, &c->gp_wt, c->Mmax + 2));
+    VCHCHK(dalloc1(c, &c->gp_col, (size_t)c->B * c->n));
+    VCHCHK(dalloc1(c, &c->gp_s, (size_t)c->B * gp_ss(c)));
+    if (!t_hist) return 0;
+    const std::vector<double> wt = trapz_w1(t_hist, rows);
+    VCHCHK(up(c, c->gp_wt, wt.data(), rows));
+    HIPCHK(hipStreamSynchronize(c->stream));          // wt is a local
+    return 0;
+}
+
+// J4 of a group mode for one trajectory: s [rows][4] the level sums of k1d_cost (TIME: column 2 = sum_i wx_i u^2), t [rows];
+// colsq [n] the squared column norms of k1d_colnorm and wx [n] (SPACE).  Host sums in index order.
+static double gp_j4(int mode, const double *s, const double *t, int rows, const double *colsq, const double *wx, int n) {
+    double acc = 0;
+    if (mode == VCH_SPARSITY_TIME)
+        for (int k = 0; k + 1 < rows; ++k) acc += (t[k + 1] - t[k]) * (std::sqrt(s[(k + 1) * 4 + 2]) + std::sqrt(s[k * 4 + 2])) / 2.0;
+    else
+        for (int i = 0; i < n; ++i) acc += wx[i] * std::sqrt(colsq[i]);
+    return acc;
+}
+
+static int cost1_seam(vch1d_ctx *c, const double *phi_hist, const double *u, const double *phi_Q, const double *phi_T, int rows,
+                      const double *x, const double *t_hist, const vch_opt_params *o, int mode, double *J_out) {
     VCHCHK(ensure1(c, &c->phi_hist));
     VCHCHK(up_hist(c, c->phi_hist, phi_hist, rows));
     c->rows_res = rows;
@@ -375,6 +410,15 @@ extern "C" int vch1d_cost(vch1d_ctx *c, const double *phi_hist, const double *u,
             (const double *)(u ? c->u_hist : nullptr), (const double *)(phi_Q ? c->phiQ : nullptr),
             (const double *)(phi_T ? c->phiT : nullptr), hs1(c), c->cost_lvl);
     VCHCHK(down(c, c->cost_host, c->cost_lvl, (size_t)c->B * rows * 4));
+    if (mode == VCH_SPARSITY_SPACE) {
+        c->gp_col_host.assign((size_t)c->B * c->n, 0.0);
+        if (u) {
+            VCHCHK(gp_tables(c, t_hist, rows));
+            LAUNCH(k1d_colnorm, dim3(gp_nblk(c), c->B), dim3(GC_T), c->n, rows, (const double *)c->u_hist, hs1(c), (const int *)nullptr,
+                   (const double *)c->gp_wt, c->gp_col);
+            VCHCHK(down(c, c->gp_col_host.data(), c->gp_col, c->gp_col_host.size()));
+        }
+    }
     for (int b = 0; b < c->B; ++b) {
         const double *s = c->cost_host + (size_t)b * rows * 4;
         double i1 = 0, i3 = 0, i4 = 0;
@@ -384,6 +428,7 @@ extern "C" int vch1d_cost(vch1d_ctx *c, const double *phi_hist, const double *u,
             i3 += d * (s[(k + 1) * 4 + 2] + s[k * 4 + 2]) / 2.0;
             i4 += d * (s[(k + 1) * 4 + 3] + s[k * 4 + 3]) / 2.0;
         }
+        if (mode != VCH_SPARSITY_FULL) i4 = gp_j4(mode, s, t_hist, rows, c->gp_col_host.data() + (size_t)b * c->n, wx.data(), c->n);
         double *J = J_out + 5 * b;
         J[0] = (o->b1 / 2.0) * i1;
         J[1] = (o->b2 / 2.0) * s[(rows - 1) * 4 + 1];
@@ -392,6 +437,21 @@ extern "C" int vch1d_cost(vch1d_ctx *c, const double *phi_hist, const double *u,
         J[4] = J[0] + J[1] + J[2] + J[3];
     }
     return 0;
+}
+
+extern "C" int vch1d_cost(vch1d_ctx *c, const double *phi_hist, const double *u, const double *phi_Q, const double *phi_T,
+                          int rows, const double *x, const double *t_hist, const vch_opt_params *o, double *J_out) {
+    CTXCHK(c);
+    ARGCHK(phi_hist && x && t_hist && o && J_out && rows >= 2 && rows <= c->Mmax + 2, "NULL argument or rows out of range");
+    return cost1_seam(c, phi_hist, u, phi_Q, phi_T, rows, x, t_hist, o, VCH_SPARSITY_FULL, J_out);
+}
+
+extern "C" int vch1d_cost_g(vch1d_ctx *c, const double *phi_hist, const double *u, const double *phi_Q, const double *phi_T,
+                            int rows, const double *x, const double *t_hist, const vch_opt_params *o, int sparsity, double *J_out) {
+    CTXCHK(c);
+    ARGCHK(phi_hist && x && t_hist && o && J_out && rows >= 2 && rows <= c->Mmax + 2, "NULL argument or rows out of range");
+    ARGCHK(sparsity >= VCH_SPARSITY_FULL && sparsity <= VCH_SPARSITY_SPACE, "sparsity is none of VCH_SPARSITY_FULL, _TIME, _SPACE");
+    return cost1_seam(c, phi_hist, u, phi_Q, phi_T, rows, x, t_hist, o, sparsity, J_out);
 }
 
 extern "C" int vch1d_grad_prox(vch1d_ctx *c, const double *u, const double *r, int rows, const double *alpha,
@@ -408,6 +468,64 @@ extern "C" int vch1d_grad_prox(vch1d_ctx *c, const double *u, const double *r, i
     VCHCHK(seam_row(c, 0.0, 0.0, o->b3, o->kappa_sparsity, o->u_min, o->u_max));
     LAUNCH(k1d_grad_prox, dim3(rows, c->B), dim3(T1), c->n, (const double *)c->u_hist, (const double *)c->r_hist, hs1(c),
             (const double *)c->alpha_dev, (const double *)c->seam_tab, 0, c->u_trial, (double *)nullptr);
+    return down_hist(c, u_out, c->u_trial, rows);
+}
+
+// The group prox kernels for the trajectories of `mode` (mode_dev NULL: all of them): u, r -> uout (or NULL), s in gp_s, the
+// change partials in chg_t (rows kernel, [B][rows][2]) or gp_chg (column kernel); tab / stride as for k1d_grad_prox.
+static int gp_launch(vch1d_ctx *c, int mode, const int *mode_dev, int rows, const double *alpha_dev, const double *tab, int stride,
+                     double *uout, double *chg_t) {
+#define GP_ROWS(NV)                                                                                                        \
+    LAUNCH((k1d_group_prox_rows<NV>), dim3(rows, c->B), dim3(T1), c->n, (const double *)c->u_hist, (const double *)c->r_hist, \
+           hs1(c), alpha_dev, tab, stride, mode_dev, (const double *)c->wx, uout, c->gp_s, gp_ss(c), chg_t)
+    if (mode == VCH_SPARSITY_TIME) {
+        switch (gp_rows_nv(c->n)) {       // the values per thread that hold a row
+        case 1: GP_ROWS(1); break;
+        case 2: GP_ROWS(2); break;
+        case 4: GP_ROWS(4); break;
+        default: GP_ROWS(GP_NV);
+        }
+    } else
+        LAUNCH(k1d_group_prox_cols, dim3(gp_nblk(c), c->B), dim3(GC_T), c->n, rows, (const double *)c->u_hist,
+               (const double *)c->r_hist, hs1(c), alpha_dev, tab, stride, mode_dev, (const double *)c->gp_wt, uout, c->gp_s, gp_ss(c),
+               c->gp_chg);
+#undef GP_ROWS
+    return 0;
+}
+
+extern "C" int vch1d_grad_prox_g(vch1d_ctx *c, const double *u, const double *r, int rows, const double *x, const double *t_hist,
+                                 const double *alpha, const vch_opt_params *o, int sparsity, double *u_out, double *scale_out) {
+    CTXCHK(c);
+    ARGCHK(sparsity >= VCH_SPARSITY_FULL && sparsity <= VCH_SPARSITY_SPACE, "sparsity is none of VCH_SPARSITY_FULL, _TIME, _SPACE");
+    if (sparsity == VCH_SPARSITY_FULL) return vch1d_grad_prox(c, u, r, rows, alpha, o, u_out);
+    ARGCHK(u && r && alpha && o && u_out && rows >= 1 && rows <= c->Mmax + 2, "NULL argument or rows out of range");
+    ARGCHK(sparsity == VCH_SPARSITY_TIME ? x != nullptr : (t_hist != nullptr), "NULL x (TIME) or t_hist (SPACE): the group's weights");
+    ARGCHK(o->u_min <= 0.0 && o->u_max >= 0.0, "a group mode needs a box with u_min <= 0 <= u_max");
+    ARGCHK(std::isfinite(o->kappa_sparsity) && o->kappa_sparsity >= 0, "kappa_sparsity must be finite and >= 0");
+    VCHCHK(ensure1(c, &c->u_hist));
+    VCHCHK(ensure1(c, &c->r_hist));
+    VCHCHK(ensure1(c, &c->u_trial));
+    VCHCHK(dalloc1(c, &c->gp_chg, (size_t)c->B * gp_nblk(c) * 2));
+    c->pgd_r_valid = false;               // as in vch1d_backward
+    VCHCHK(up_hist(c, c->u_hist, u, rows));
+    VCHCHK(up_hist(c, c->r_hist, r, rows));
+    VCHCHK(up(c, c->alpha_dev, alpha, c->B));
+    VCHCHK(seam_row(c, 0.0, 0.0, o->b3, o->kappa_sparsity, o->u_min, o->u_max));
+    if (sparsity == VCH_SPARSITY_TIME) {
+        VCHCHK(gp_tables(c, nullptr, 0));
+        const std::vector<double> wx = trapz_w1(x, c->n);
+        VCHCHK(up(c, c->wx, wx.data(), c->n));
+        HIPCHK(hipStreamSynchronize(c->stream));      // wx is a local
+    } else {
+        VCHCHK(gp_tables(c, t_hist, rows));
+    }
+    VCHCHK(gp_launch(c, sparsity, nullptr, rows, c->alpha_dev, c->seam_tab, 0, c->u_trial, nullptr));
+    if (scale_out) {
+        const int ng = sparsity == VCH_SPARSITY_TIME ? rows : c->n;
+        for (int b = 0; b < c->B; ++b)
+            HIPCHK(hipMemcpyAsync(scale_out + (size_t)b * ng, c->gp_s + b * gp_ss(c), sizeof(double) * ng, hipMemcpyDeviceToHost,
+                                  c->stream));
+    }
     return down_hist(c, u_out, c->u_trial, rows);
 }
 
@@ -443,6 +561,11 @@ static int cost1_core(vch1d_ctx *c, const double *phi_dev, const double *u_dev, 
     LAUNCH(k1d_cost, dim3(rows, c->B), dim3(T1), c->n, rows, (const double *)c->wx, phi_dev, u_dev,
             (const double *)c->phiQ, (const double *)c->phiT, hs1(c), c->cost_lvl);
     VCHCHK(down(c, c->cost_host, c->cost_lvl, (size_t)c->B * rows * 4));
+    if (gp_any(c, VCH_SPARSITY_SPACE)) {      // the squared column norms of the SPACE trajectories
+        LAUNCH(k1d_colnorm, dim3(gp_nblk(c), c->B), dim3(GC_T), c->n, rows, u_dev, hs1(c), (const int *)c->mode_dev,
+               (const double *)c->gp_wt, c->gp_col);
+        VCHCHK(down(c, c->gp_col_host.data(), c->gp_col, c->gp_col_host.size()));
+    }
     const double *t = c->t_host.data();
     for (int b = 0; b < c->B; ++b) {
         const double *s = c->cost_host + (size_t)b * rows * 4;
@@ -453,6 +576,8 @@ static int cost1_core(vch1d_ctx *c, const double *phi_dev, const double *u_dev, 
             i3 += d * (s[(k + 1) * 4 + 2] + s[k * 4 + 2]) / 2.0;
             i4 += d * (s[(k + 1) * 4 + 3] + s[k * 4 + 3]) / 2.0;
         }
+        if (gp_mode(c, b) != VCH_SPARSITY_FULL)
+            i4 = gp_j4(gp_mode(c, b), s, t, rows, c->gp_col_host.data() + (size_t)b * c->n, c->wx_host.data(), c->n);
         const vch_opt_params *o = &c->opts[b];
         double *J = J_out + 5 * b;
         J[0] = (o->b1 / 2.0) * i1;
@@ -514,19 +639,36 @@ static int backward1_core(vch1d_ctx *c, int rows) {
     return 0;
 }
 
-extern "C" int vch1d_pgd_init_v(vch1d_ctx *c, const double *phi0, const double *phi_T, const double *phi_Q, const double *x,
-                                const double *t_hist, int rows, const double *dt, const vch_opt_params *opts, int n_opts,
-                                const double *u0, const double *alpha0, double *J0_out) {
-    CTXCHK(c);
-    ARGCHK(phi0 && phi_T && x && t_hist && dt && opts, "NULL argument");
-    ARGCHK(rows >= 3 && rows <= c->Mmax + 2, "rows out of range (3..max_steps+2)");
-    ARGCHK(n_opts == 1 || n_opts == c->B, "n_opts must be 1 or the context's batch");
+// vch1d_pgd_init_v and vch1d_pgd_init_g (fn: who the messages name).  sparsity NULL: every trajectory VCH_SPARSITY_FULL.
+static int pgd_init1(vch1d_ctx *c, const char *fn, const double *phi0, const double *phi_T, const double *phi_Q, const double *x,
+                     const double *t_hist, int rows, const double *dt, const vch_opt_params *opts, int n_opts, const double *u0,
+                     const double *alpha0, const int32_t *sparsity, int n_sparsity, double *J0_out) {
+    if (!(phi0 && phi_T && x && t_hist && dt && opts)) return vch_fail(VCH_ERR_ARG, "%s: NULL argument", fn);
+    if (!(rows >= 3 && rows <= c->Mmax + 2)) return vch_fail(VCH_ERR_ARG, "%s: rows out of range (3..max_steps+2)", fn);
+    if (!(n_opts == 1 || n_opts == c->B)) return vch_fail(VCH_ERR_ARG, "%s: n_opts must be 1 or the context's batch", fn);
     const int B = c->B, M = rows - 2;
-    for (int k = 0; k < M; ++k) ARGCHK(dt[k] > 0, "dt must be positive");
+    for (int k = 0; k < M; ++k)
+        if (!(dt[k] > 0)) return vch_fail(VCH_ERR_ARG, "%s: dt must be positive", fn);
     // all of this before anything is copied or launched, or any resident state changes
     for (int b = 0; b < B; ++b)
         if (const char *bad = vch_pgd_check(opts, n_opts, alpha0, b))
-            return vch_fail(VCH_ERR_ARG, "vch1d_pgd_init_v: trajectory %d: %s", b, bad);
+            return vch_fail(VCH_ERR_ARG, "%s: trajectory %d: %s", fn, b, bad);
+    bool grouped = false;
+    if (sparsity) {
+        if (!(n_sparsity == 1 || n_sparsity == B)) return vch_fail(VCH_ERR_ARG, "%s: n_sparsity must be 1 or the context's batch", fn);
+        for (int b = 0; b < B; ++b) {
+            const int m = sparsity[n_sparsity == 1 ? 0 : b];
+            const vch_opt_params &o = vch_pgd_opt(opts, n_opts, b);
+            if (m < VCH_SPARSITY_FULL || m > VCH_SPARSITY_SPACE)
+                return vch_fail(VCH_ERR_ARG, "%s: trajectory %d: sparsity %d is none of VCH_SPARSITY_FULL, _TIME, _SPACE", fn, b, m);
+            if (m != VCH_SPARSITY_FULL && !(o.u_min <= 0.0 && o.u_max >= 0.0))
+                return vch_fail(VCH_ERR_ARG, "%s: trajectory %d: a group mode needs a box with u_min <= 0 <= u_max", fn, b);
+            grouped = grouped || m != VCH_SPARSITY_FULL;
+        }
+    }
+    c->modes.assign(B, VCH_SPARSITY_FULL);
+    if (sparsity)
+        for (int b = 0; b < B; ++b) c->modes[b] = sparsity[n_sparsity == 1 ? 0 : b];
     c->opts.resize(B);
     std::vector<double> &tab = c->opt_tab_host;
     tab.assign((size_t)B * OPT1_STRIDE, 0.0);
@@ -554,7 +696,24 @@ extern "C" int vch1d_pgd_init_v(vch1d_ctx *c, const double *phi0, const double *
         VCHCHK(dalloc1(c, &c->opt_tab, tab.size()));
         if (!c->kkt_cnt) MEMCHK(c->pool.dev(&c->kkt_cnt, sizeof(long long) * 4 * B));
         VCHCHK(dalloc1(c, &c->kkt_nrm, 2 * (size_t)B));
+        if (grouped) {      // the mode table and what the group kernels write
+            if (!c->mode_dev) MEMCHK(c->pool.dev(&c->mode_dev, sizeof(int) * B));
+            VCHCHK(dalloc1(c, &c->gp_wt, c->Mmax + 2));
+            VCHCHK(dalloc1(c, &c->gp_s, (size_t)B * gp_ss(c)));
+            VCHCHK(dalloc1(c, &c->gp_chg, (size_t)B * gp_nblk(c) * 2));
+            VCHCHK(dalloc1(c, &c->gp_col, (size_t)B * c->n));
+            VCHCHK(dalloc1(c, &c->gp_one, B));
+        }
         g.keep();
+    }
+    if (grouped) {
+        c->gp_chg_host.assign((size_t)B * gp_nblk(c) * 2, 0.0);
+        c->gp_col_host.assign((size_t)B * c->n, 0.0);
+        const std::vector<double> wt = trapz_w1(t_hist, rows), one(B, 1.0);
+        HIPCHK(hipMemcpyAsync(c->mode_dev, c->modes.data(), sizeof(int) * B, hipMemcpyHostToDevice, c->stream));
+        VCHCHK(up(c, c->gp_wt, wt.data(), rows));
+        VCHCHK(up(c, c->gp_one, one.data(), B));
+        HIPCHK(hipStreamSynchronize(c->stream));      // wt, one are locals
     }
     VCHCHK(up(c, c->opt_tab, tab.data(), tab.size()));
     c->chg_host.assign((size_t)B * rows * 2, 0.0);
@@ -565,6 +724,7 @@ extern "C" int vch1d_pgd_init_v(vch1d_ctx *c, const double *phi0, const double *
     const std::vector<double> wx = trapz_w1(x, c->n);
     VCHCHK(up(c, c->wx, wx.data(), c->n));
     HIPCHK(hipStreamSynchronize(c->stream));          // wx is a local
+    c->wx_host = wx;
     // u = 0 and the uncontrolled march (G1:341), or the caller's u0 as given (not clipped) and the march under it
     HIPCHK(hipMemsetAsync(c->u_hist, 0, sizeof(double) * B * hs1(c), c->stream));
     if (u0) VCHCHK(up_hist(c, c->u_hist, u0, rows));
@@ -592,6 +752,22 @@ extern "C" int vch1d_pgd_init_v(vch1d_ctx *c, const double *phi0, const double *
     if (J0_out) memcpy(J0_out, J.data(), sizeof(double) * 5 * B);
     c->pgd_ready = true;
     return 0;
+}
+
+extern "C" int vch1d_pgd_init_v(vch1d_ctx *c, const double *phi0, const double *phi_T, const double *phi_Q, const double *x,
+                                const double *t_hist, int rows, const double *dt, const vch_opt_params *opts, int n_opts,
+                                const double *u0, const double *alpha0, double *J0_out) {
+    CTXCHK(c);
+    return pgd_init1(c, "vch1d_pgd_init_v", phi0, phi_T, phi_Q, x, t_hist, rows, dt, opts, n_opts, u0, alpha0, nullptr, 0, J0_out);
+}
+
+extern "C" int vch1d_pgd_init_g(vch1d_ctx *c, const double *phi0, const double *phi_T, const double *phi_Q, const double *x,
+                                const double *t_hist, int rows, const double *dt, const vch_opt_params *opts, int n_opts,
+                                const double *u0, const double *alpha0, const int32_t *sparsity, int n_sparsity, double *J0_out) {
+    CTXCHK(c);
+    if (!sparsity) return vch_fail(VCH_ERR_ARG, "vch1d_pgd_init_g: NULL sparsity");
+    return pgd_init1(c, "vch1d_pgd_init_g", phi0, phi_T, phi_Q, x, t_hist, rows, dt, opts, n_opts, u0, alpha0, sparsity, n_sparsity,
+                     J0_out);
 }
 
 extern "C" int vch1d_pgd_init(vch1d_ctx *c, const double *phi0, const double *phi_T, const double *phi_Q, const double *x,
@@ -637,20 +813,38 @@ extern "C" int vch1d_pgd_iterate(vch1d_ctx *c, int n_iters, double *cost_out, do
             HIPCHK(tick(c->ev0));
             VCHCHK(up(c, c->alpha_dev, st.alpha.data(), B));
             HIPCHK(hipMemcpyAsync(c->skip_dev, st.accepted.data(), sizeof(int) * B, hipMemcpyHostToDevice, c->stream));
-            LAUNCH(k1d_grad_prox, dim3(rows, B), dim3(T1), c->n, (const double *)c->u_hist, (const double *)c->r_hist, hs1(c),
-                    (const double *)c->alpha_dev, (const double *)c->opt_tab, OPT1_STRIDE, c->u_trial, c->chg_dev);
+            // k1d_grad_prox for every run of FULL trajectories (without a group mode: one launch over the batch, as ever), the
+            // group kernels for the others: the mode table makes them leave a trajectory that is not theirs alone
+            for (int b0 = 0; b0 < B;) {
+                if (gp_mode(c, b0) != VCH_SPARSITY_FULL) { ++b0; continue; }
+                int b1 = b0;
+                while (b1 < B && gp_mode(c, b1) == VCH_SPARSITY_FULL) ++b1;
+                LAUNCH(k1d_grad_prox, dim3(rows, b1 - b0), dim3(T1), c->n, (const double *)(c->u_hist + b0 * hs1(c)),
+                        (const double *)(c->r_hist + b0 * hs1(c)), hs1(c), (const double *)(c->alpha_dev + b0),
+                        (const double *)(c->opt_tab + (size_t)b0 * OPT1_STRIDE), OPT1_STRIDE, c->u_trial + b0 * hs1(c),
+                        c->chg_dev + (size_t)b0 * rows * 2);
+                b0 = b1;
+            }
+            for (int mode : {VCH_SPARSITY_TIME, VCH_SPARSITY_SPACE})
+                if (gp_any(c, mode))
+                    VCHCHK(gp_launch(c, mode, c->mode_dev, rows, c->alpha_dev, c->opt_tab, OPT1_STRIDE, c->u_trial, c->chg_dev));
             VCHCHK(fwd1_core(c, c->u_trial, rows, c->phi_trial, c->skip_dev));
             VCHCHK(cost1_core(c, c->phi_trial, c->u_trial, rows, Jt.data(), raw.data()));
             VCHCHK(down(c, c->chg_host.data(), c->chg_dev, (size_t)B * rows * 2));
+            if (gp_any(c, VCH_SPARSITY_SPACE)) VCHCHK(down(c, c->gp_chg_host.data(), c->gp_chg, c->gp_chg_host.size()));
             HIPCHK(tick(c->ev1));
             sec[round == 0 ? 1 : 2] += lap();
             bool pending = false;
             for (int b = 0; b < B; ++b) {
                 if (st.accepted[b]) continue;
                 double d2 = 0, n2 = 0;
-                for (int r = 0; r < rows; ++r) {
-                    d2 += c->chg_host[((size_t)b * rows + r) * 2];
-                    n2 += c->chg_host[((size_t)b * rows + r) * 2 + 1];
+                // the partials of the change sums: one per row, or one per workgroup of the column kernel
+                const bool cols = gp_mode(c, b) == VCH_SPARSITY_SPACE;
+                const int np = cols ? gp_nblk(c) : rows;
+                const double *part = cols ? c->gp_chg_host.data() : c->chg_host.data();
+                for (int r = 0; r < np; ++r) {
+                    d2 += part[((size_t)b * np + r) * 2];
+                    n2 += part[((size_t)b * np + r) * 2 + 1];
                 }
                 vch_pgd_step s;
                 const vch_pgd_verdict v =
@@ -705,6 +899,14 @@ extern "C" int vch1d_pgd_kkt(vch1d_ctx *c, int refresh, double tol, int64_t *cou
     }
     LAUNCH(k1d_kkt, dim3(B), dim3(T1), c->n, rows, (const double *)c->u_hist, (const double *)c->r_hist, hs1(c),
             (const double *)c->opt_tab, tol, c->kkt_cnt, c->kkt_nrm);
+    if (gp_group(c)) {      // the group modes: their prox at alpha = 1 for the change sums alone, then the counts by groups
+        for (int mode : {VCH_SPARSITY_TIME, VCH_SPARSITY_SPACE})
+            if (gp_any(c, mode))
+                VCHCHK(gp_launch(c, mode, c->mode_dev, rows, c->gp_one, c->opt_tab, OPT1_STRIDE, nullptr, c->chg_dev));
+        LAUNCH(k1d_kkt_g, dim3(B), dim3(T1), c->n, rows, (const double *)c->u_hist, (const double *)c->r_hist, hs1(c),
+               (const double *)c->opt_tab, (const int *)c->mode_dev, (const double *)c->wx, (const double *)c->gp_wt, tol,
+               (const double *)c->chg_dev, (const double *)c->gp_chg, gp_nblk(c), c->kkt_cnt, c->kkt_nrm);
+    }
     std::vector<long long> cnt(4 * (size_t)B);
     std::vector<double> nh(2 * (size_t)B);
     HIPCHK(hipMemcpyAsync(cnt.data(), c->kkt_cnt, sizeof(long long) * 4 * B, hipMemcpyDeviceToHost, c->stream));
@@ -1234,6 +1436,15 @@ static Ncg1Args ncg1_args(const vch1d_ctx *c, const Kr1Layout &L, int rows, long
 // pred = rnorm0 = 0, none of the stale cells read, and its three slots zeroed for vch1d_cg_vector.
 // radius (or NULL): the trust region of vch1d_hess_cg_tr, k1d_ncg_fin_tr in place of k1d_ncg_fin and xnorm_out [B] = ||x||_D
 // by the recurrence (0 for an empty free set); NULL runs the launches of vch1d_hess_cg exactly.
+// The right-hand side that vch1d_hess_cg builds itself (rhs == NULL) and the free set are those of the L1 functional: with
+// the resident control (`resident`) of a problem that has a trajectory in a group mode they would belong to another cost.
+static int gp_refuse(const vch1d_ctx *c, const char *fn, bool resident) {
+    if (resident && c->pgd_ready && gp_group(c))
+        return vch_fail(VCH_ERR_STATE, "%s: the resident problem has a trajectory in a directional-sparsity mode; the sign term and "
+                        "the free set of this call are those of the L1 functional", fn);
+    return 0;
+}
+
 static int hess_cg1_core(vch1d_ctx *c, const char *fn, bool empty_ok, const double *phi_hist, const double *u, int n_base, int rows,
                          const double *dt, const double *t_hist, const double *x, const double *phi_Q, const double *phi_T,
                          const vch_opt_params *opts, int n_opts, const uint8_t *mask, double tol, const double *rhs, int k,
@@ -1241,6 +1452,7 @@ static int hess_cg1_core(vch1d_ctx *c, const char *fn, bool empty_ok, const doub
                          int32_t *steps_out, int32_t *status_out, int64_t *n_free_out, vch_stats *stats,
                          const double *radius = nullptr, double *xnorm_out = nullptr) {
     const int B = c->B, n = c->n;
+    VCHCHK(gp_refuse(c, fn, !rhs && u == VCH_RESIDENT));
     VCHCHK(so1_check_shape(c, fn, n_base, rows, n_opts, 2));
     if (!resid_out || !curv_out || !pred_out || !rnorm0_out || !steps_out || !status_out || !n_free_out)
         return vch_fail(VCH_ERR_ARG, "%s: NULL resid_out, curv_out, pred_out, rnorm0_out, steps_out, status_out or n_free_out", fn);
@@ -1520,6 +1732,7 @@ extern "C" int vch1d_pgd_newton(vch1d_ctx *c, int n_rounds, int k, double cg_tol
     const char *fn = "vch1d_pgd_newton";
     // everything below is checked before anything is enqueued, copied or allocated
     if (!c->pgd_ready) return vch_fail(VCH_ERR_STATE, "%s: call vch1d_pgd_init first", fn);
+    VCHCHK(gp_refuse(c, fn, true));
     const int B = c->B, rows = c->pgd_rows;
     const vch_newton_call call{B, n_rounds, k, cg_tol, precond, max_halvings, cost_out, cost_new_out, s_out, pred_out, rnorm0_out,
                                halvings_out, cg_steps_out, cg_status_out, status_out, counts_out};
@@ -1554,6 +1767,7 @@ extern "C" int vch1d_pgd_trust(vch1d_ctx *c, int n_rounds, int k, double cg_tol,
     const char *fn = "vch1d_pgd_trust";
     // everything below is checked before anything is enqueued, copied or allocated
     if (!c->pgd_ready) return vch_fail(VCH_ERR_STATE, "%s: call vch1d_pgd_init first", fn);
+    VCHCHK(gp_refuse(c, fn, true));
     const int B = c->B, rows = c->pgd_rows;
     const vch_trust_call call{B, n_rounds, k, cg_tol, precond, radius0, radius_max, radius_min, cost_out, cost_new_out, pred_out,
                               rnorm0_out, radius_out, ratio_out, xnorm_out, cg_steps_out, cg_status_out, status_out, counts_out};

@@ -971,6 +971,294 @@ __global__ __launch_bounds__(T1) void k1d_kkt(int n, int rows, const double *__r
     }
 }
 
+// ---------------------------------------------------------------------------------
+// Directional sparsity: the prox of kappa_s * sum over groups of ||u_g|| under the box, a group being a row
+// of the control (VCH_SPARSITY_TIME, ||z||^2 = sum_i wx_i z_i^2) or a column (VCH_SPARSITY_SPACE, ||z||^2 = sum_k wt_k z_k^2).
+// With v = u - alpha (r + b3 u) and lam = alpha kappa_s:  c = ||cone(v)|| <= lam gives u+ = 0, s = 0; otherwise
+// u+ = clip(s v) with s the root of h(s) = ||clip(s v)|| (1 - s) - lam s, which is s0 = 1 - lam / ||v|| where clip(s0 v) = s0 v.
+// No atomics; every sum has one fixed order, so a trajectory's bits do not depend on the batch it runs in.
+// ---------------------------------------------------------------------------------
+constexpr int GP_FULL = 0, GP_TIME = 1, GP_SPACE = 2;      // VCH_SPARSITY_* of vch.h
+constexpr int GP_NV = (4096 + 1 + T1 - 1) / T1;            // values of a row per thread at the largest N
+constexpr int GP_MAXIT = 100;                              // the bracket ends the iteration long before
+constexpr int GC_W = 16, GC_T = 64 * GC_W;                 // the column kernels: 64 columns across the lanes, rows over GC_W waves
+// values per thread the rows kernel is instantiated with: the smallest of 1, 2, 4, GP_NV that holds a row of n nodes (a short
+// row in a kernel built for the longest would leave most registers, and with them most of the CU, idle)
+inline int gp_rows_nv(int n) {
+    const int nv = (n + T1 - 1) / T1;
+    return nv <= 1 ? 1 : (nv <= 2 ? 2 : (nv <= 4 && 4 < GP_NV ? 4 : GP_NV));
+}
+
+// the gradient step, with its two roundings written out: every pass of a kernel recomputes the same bits
+__device__ __forceinline__ double gp_v(double uu, double rr, double al, double b3) { return fma(-al, fma(b3, uu, rr), uu); }
+__device__ __forceinline__ double gp_cone(double v, double umin, double umax) {
+    return (umax == 0.0 && v > 0.0) || (umin == 0.0 && v < 0.0) ? 0.0 : v;
+}
+__device__ __forceinline__ double gp_out(double s, double v, double umin, double umax) {
+    return s == 0.0 ? 0.0 : fmin(fmax(s * v, umin), umax);
+}
+// One step of the safeguarded iteration at s, where Q = ||clip(s v)||^2 and A = the sum of w v^2 over the nodes the box does
+// not hold (d/ds ||clip(s v)|| = A s / ||clip(s v)||).  The bracket keeps h(lo) > 0 >= h(hi).  The candidate is Newton's,
+// doubled while Newton closes in from one side (so that the other end of the bracket follows), else the midpoint.
+// true: h vanishes or lo, hi are adjacent doubles; s is the answer.
+__device__ __forceinline__ bool gp_step(double Q, double A, double lam, double &s, double &lo, double &hi) {
+    const double rho = sqrt(Q);
+    const double h = rho * (1.0 - s) - lam * s;
+    if (h == 0.0) return true;
+    if (h > 0.0) lo = s; else hi = s;
+    const double dh = (rho > 0.0 ? A * s / rho : 0.0) * (1.0 - s) - rho - lam;
+    const double step = -h / dh;
+    double sn = fabs(step) < 0.25 * (hi - lo) ? s + 2.0 * step : s + step;
+    if (!(sn > lo && sn < hi)) sn = s + step;
+    if (!(sn > lo && sn < hi)) sn = lo + 0.5 * (hi - lo);
+    if (!(sn > lo && sn < hi)) return true;
+    s = sn;
+    return false;
+}
+
+// TIME: one workgroup per (row, trajectory), the row's v, weights and u in registers (NV each, fully unrolled; NV * T1 >= n,
+// gp_rows_nv): one read of u and r, one write of u+.  The sums add the nodes in index order whatever NV is.  mode (or NULL: every trajectory): [B], a trajectory of another mode is left alone.
+// sout (or NULL): s of the group at [b * ss + row]; uout (or NULL: the sums alone); chg (or NULL): the sums of k1d_grad_prox.
+template <int NV>
+__global__ __launch_bounds__(T1) void k1d_group_prox_rows(int n, const double *__restrict__ u, const double *__restrict__ r, long hs,
+                                                          const double *__restrict__ alpha, const double *__restrict__ opt_tab,
+                                                          int opt_stride, const int *__restrict__ mode,
+                                                          const double *__restrict__ wx, double *__restrict__ uout,
+                                                          double *__restrict__ sout, long ss, double *__restrict__ chg) {
+    __shared__ double sk[3 * (T1 / 64)];
+    __shared__ double bc[2];
+    const int row = blockIdx.x, b = blockIdx.y, rows = gridDim.x, tid = threadIdx.x;
+    if (mode && mode[b] != GP_TIME) return;
+    const double *ot = opt_tab + b * opt_stride;
+    const double b3 = ot[OPT1_B3], ks = ot[OPT1_KS], umin = ot[OPT1_UMIN], umax = ot[OPT1_UMAX];
+    const long o = b * hs + (long)row * n;
+    const double al = alpha[b], lam = al * ks;
+    double v[NV], w[NV], uu[NV];
+    double a3[3] = {0.0, 0.0, 0.0};           // ||cone(v)||^2, ||v||^2, sum u^2
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        const int i = tid + k * T1;
+        uu[k] = 0.0; w[k] = 0.0; v[k] = 0.0;
+        if (i < n) {
+            uu[k] = u[o + i];
+            w[k] = wx[i];
+            v[k] = gp_v(uu[k], r[o + i], al, b3);
+        }
+        const double cv = gp_cone(v[k], umin, umax);
+        a3[0] += w[k] * (cv * cv);
+        a3[1] += w[k] * (v[k] * v[k]);
+        a3[2] += uu[k] * uu[k];
+    }
+    block_sums<3>(a3, sk);
+    double s = 0.0;
+    if (sqrt(a3[0]) > lam) {                  // the same in every thread: the sums are broadcast
+        s = 1.0 - lam / sqrt(a3[1]);
+        double out = 0.0;                     // the vote: does s0 leave the box inactive?
+#pragma unroll
+        for (int k = 0; k < NV; ++k) out = (s * v[k] < umin || s * v[k] > umax) ? 1.0 : out;
+        if (block_red<2>(out, sk) != 0.0) {
+            double lo = 0.0, hi = 1.0;        // thread 0's
+            for (int it = 0; it < GP_MAXIT; ++it) {
+                double qa[2] = {0.0, 0.0};
+#pragma unroll
+                for (int k = 0; k < NV; ++k) {
+                    const double sv = s * v[k], cl = fmin(fmax(sv, umin), umax);
+                    qa[0] += w[k] * (cl * cl);
+                    qa[1] += cl == sv ? w[k] * (v[k] * v[k]) : 0.0;
+                }
+                block_sums<2>(qa, sk);
+                if (tid == 0) {
+                    const bool done = gp_step(qa[0], qa[1], lam, s, lo, hi);
+                    bc[0] = s; bc[1] = done ? 1.0 : 0.0;
+                }
+                __syncthreads();              // the next write of bc comes after the two barriers of block_sums
+                s = bc[0];
+                if (bc[1] != 0.0) break;
+            }
+        }
+    }
+    double d2 = 0.0;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        const int i = tid + k * T1;
+        const double un = gp_out(s, v[k], umin, umax);
+        if (i < n) {
+            if (uout) uout[o + i] = un;
+            d2 += (un - uu[k]) * (un - uu[k]);
+        }
+    }
+    d2 = block_red<0>(d2, sk);
+    if (tid == 0) {
+        if (sout) sout[b * ss + row] = s;
+        if (chg) { chg[((long)b * rows + row) * 2] = d2; chg[((long)b * rows + row) * 2 + 1] = a3[2]; }
+    }
+}
+
+// SPACE: one workgroup of GC_W waves per (64 columns, trajectory); lane = column, so every row read is coalesced; wave w
+// takes rows w, w + GC_W, ... and the waves' partial sums are added in wave order.  Pass one: ||cone(v)||^2, ||v||^2 and the extremes of
+// v, which say whether s0 leaves the box inactive (s0 v is monotone in v).  Columns the box holds iterate together, each
+// step re-reading the column; the last pass writes u+.  chg (or NULL): [B][gridDim.x][2], this workgroup's share of
+// sum (u+ - u)^2 and sum u^2; sout (or NULL): s at [b * ss + column].
+__global__ __launch_bounds__(GC_T) void k1d_group_prox_cols(int n, int rows, const double *__restrict__ u, const double *__restrict__ r,
+                                                            long hs, const double *__restrict__ alpha,
+                                                            const double *__restrict__ opt_tab, int opt_stride,
+                                                            const int *__restrict__ mode, const double *__restrict__ wt,
+                                                            double *__restrict__ uout, double *__restrict__ sout, long ss,
+                                                            double *__restrict__ chg) {
+    __shared__ double part[4][GC_W][64];
+    const int b = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (mode && mode[b] != GP_SPACE) return;
+    const int i = blockIdx.x * 64 + lane;
+    const bool ok = i < n;
+    const double *ot = opt_tab + b * opt_stride;
+    const double b3 = ot[OPT1_B3], ks = ot[OPT1_KS], umin = ot[OPT1_UMIN], umax = ot[OPT1_UMAX];
+    const long o = b * hs + i;
+    const double al = alpha[b], lam = al * ks;
+    double cc = 0.0, vv = 0.0, mx = 0.0, mn = 0.0;
+    if (ok) {
+#pragma unroll 4
+        for (int k = wv; k < rows; k += GC_W) {
+            const double uu = u[o + (long)k * n], v = gp_v(uu, r[o + (long)k * n], al, b3), w = wt[k];
+            const double cv = gp_cone(v, umin, umax);
+            cc += w * (cv * cv);
+            vv += w * (v * v);
+            mx = fmax(mx, v);
+            mn = fmin(mn, v);
+        }
+    }
+    part[0][wv][lane] = cc; part[1][wv][lane] = vv; part[2][wv][lane] = mx; part[3][wv][lane] = mn;
+    __syncthreads();
+    cc = part[0][0][lane]; vv = part[1][0][lane]; mx = part[2][0][lane]; mn = part[3][0][lane];
+    for (int w = 1; w < GC_W; ++w) {
+        cc += part[0][w][lane]; vv += part[1][w][lane];
+        mx = fmax(mx, part[2][w][lane]); mn = fmin(mn, part[3][w][lane]);
+    }
+    // from here on the waves hold the same numbers for a column and take the same steps
+    double s = 0.0, lo = 0.0, hi = 1.0;
+    bool active = false;
+    if (ok && sqrt(cc) > lam) {
+        s = 1.0 - lam / sqrt(vv);
+        active = s * mx > umax || s * mn < umin;
+    }
+    for (int it = 0; it < GP_MAXIT; ++it) {
+        if (!__syncthreads_or(active)) break;         // also the barrier between two uses of part
+        double q = 0.0, a = 0.0;
+        if (active) {
+#pragma unroll 4
+            for (int k = wv; k < rows; k += GC_W) {
+                const double uu = u[o + (long)k * n], v = gp_v(uu, r[o + (long)k * n], al, b3), w = wt[k];
+                const double sv = s * v, cl = fmin(fmax(sv, umin), umax);
+                q += w * (cl * cl);
+                a += cl == sv ? w * (v * v) : 0.0;
+            }
+        }
+        part[0][wv][lane] = q; part[1][wv][lane] = a;
+        __syncthreads();
+        if (active) {
+            q = part[0][0][lane]; a = part[1][0][lane];
+            for (int w = 1; w < GC_W; ++w) { q += part[0][w][lane]; a += part[1][w][lane]; }
+            active = !gp_step(q, a, lam, s, lo, hi);
+        }
+    }
+    double d2 = 0.0, n2 = 0.0;
+    if (ok) {
+#pragma unroll 4
+        for (int k = wv; k < rows; k += GC_W) {
+            const double uu = u[o + (long)k * n], v = gp_v(uu, r[o + (long)k * n], al, b3);
+            const double un = gp_out(s, v, umin, umax);
+            if (uout) uout[o + (long)k * n] = un;
+            d2 += (un - uu) * (un - uu);
+            n2 += uu * uu;
+        }
+    }
+    if (ok && wv == 0 && sout) sout[b * ss + i] = s;
+    if (!chg) return;
+    d2 = wsum1(d2); n2 = wsum1(n2);
+    __syncthreads();
+    if (lane == 0) { part[0][wv][0] = d2; part[1][wv][0] = n2; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        d2 = part[0][0][0]; n2 = part[1][0][0];
+        for (int w = 1; w < GC_W; ++w) { d2 += part[0][w][0]; n2 += part[1][w][0]; }
+        double *q = chg + ((long)b * gridDim.x + blockIdx.x) * 2;
+        q[0] = d2; q[1] = n2;
+    }
+}
+
+// out [B][n] = sum_k wt_k u_{k,i}^2, the squared column norms of the SPACE cost, in the order of the kernel above
+__global__ __launch_bounds__(GC_T) void k1d_colnorm(int n, int rows, const double *__restrict__ u, long hs, const int *__restrict__ mode,
+                                                    const double *__restrict__ wt, double *__restrict__ out) {
+    __shared__ double part[GC_W][64];
+    const int b = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (mode && mode[b] != GP_SPACE) return;
+    const int i = blockIdx.x * 64 + lane;
+    double a = 0.0;
+    if (i < n) {
+#pragma unroll 4
+        for (int k = wv; k < rows; k += GC_W) {
+            const double uu = u[b * hs + (long)k * n + i];
+            a += wt[k] * (uu * uu);
+        }
+    }
+    part[wv][lane] = a;
+    __syncthreads();
+    if (wv == 0 && i < n) {
+        a = part[0][lane];
+        for (int w = 1; w < GC_W; ++w) a += part[w][lane];
+        out[(long)b * n + i] = a;
+    }
+}
+
+// The KKT statistic by groups, one workgroup per trajectory of a group mode (the others are left to k1d_kkt): cnt [B][4] =
+// {#groups ||u_g|| < tol, #groups ||r_g|| <= kappa_s, #agree, #groups} in the group's norm, and nrm [B][2] = the change sums
+// of the mode's prox at alpha = 1, which the prox kernel left as partials (chg_t [B][rows][2] of the rows kernel, chg_s
+// [B][nblk][2] of the column kernel), added here in index order.
+__global__ __launch_bounds__(T1) void k1d_kkt_g(int n, int rows, const double *__restrict__ u, const double *__restrict__ r, long hs,
+                                                const double *__restrict__ opt_tab, const int *__restrict__ mode,
+                                                const double *__restrict__ wx, const double *__restrict__ wt, double tol,
+                                                const double *__restrict__ chg_t, const double *__restrict__ chg_s, int nblk,
+                                                long long *__restrict__ cnt, double *__restrict__ nrm) {
+    __shared__ double sk[3 * (T1 / 64)];
+    const int b = blockIdx.x, tid = threadIdx.x, m = mode[b];
+    if (m != GP_TIME && m != GP_SPACE) return;
+    const double ks = opt_tab[b * OPT1_STRIDE + OPT1_KS];
+    const long o = b * hs;
+    double c3[3] = {0.0, 0.0, 0.0};
+    if (m == GP_TIME) {
+        for (int k = 0; k < rows; ++k) {
+            double a2[2] = {0.0, 0.0};
+            for (int i = tid; i < n; i += T1) {
+                const double uu = u[o + (long)k * n + i], rr = r[o + (long)k * n + i], w = wx[i];
+                a2[0] += w * (uu * uu);
+                a2[1] += w * (rr * rr);
+            }
+            block_sums<2>(a2, sk);
+            const bool zero = sqrt(a2[0]) < tol, small = sqrt(a2[1]) <= ks;
+            c3[0] += zero; c3[1] += small; c3[2] += (zero == small);
+        }
+    } else {
+        for (int i = tid; i < n; i += T1) {
+            double a0 = 0.0, a1 = 0.0;
+            for (int k = 0; k < rows; ++k) {
+                const double uu = u[o + (long)k * n + i], rr = r[o + (long)k * n + i], w = wt[k];
+                a0 += w * (uu * uu);
+                a1 += w * (rr * rr);
+            }
+            const bool zero = sqrt(a0) < tol, small = sqrt(a1) <= ks;
+            c3[0] += zero; c3[1] += small; c3[2] += (zero == small);
+        }
+        block_sums<3>(c3, sk);                // counts: integers add exactly in any order
+    }
+    if (tid == 0) {
+        const int ng = m == GP_TIME ? rows : n, np = m == GP_TIME ? rows : nblk;
+        const double *q = (m == GP_TIME ? chg_t : chg_s) + (long)b * np * 2;
+        double d2 = 0.0, n2 = 0.0;
+        for (int j = 0; j < np; ++j) { d2 += q[2 * j]; n2 += q[2 * j + 1]; }
+        cnt[4 * b] = (long long)c3[0]; cnt[4 * b + 1] = (long long)c3[1]; cnt[4 * b + 2] = (long long)c3[2]; cnt[4 * b + 3] = ng;
+        nrm[2 * b] = d2; nrm[2 * b + 1] = n2;
+    }
+}
+
 // phi_Q = (1 - t/T) phi_initial + (t/T) phi_T, phi_initial = history row 0 (build_targets_1d, G1:238-241)
 __global__ __launch_bounds__(T1) void k1d_ramp(int n, const double *__restrict__ tp, const double *__restrict__ phi_hist,
                                                const double *__restrict__ phiT, long hs, double *__restrict__ phiQ) {
