@@ -980,7 +980,11 @@ __global__ __launch_bounds__(T1) void k1d_kkt(int n, int rows, const double *__r
 // ---------------------------------------------------------------------------------
 constexpr int GP_FULL = 0, GP_TIME = 1, GP_SPACE = 2;      // VCH_SPARSITY_* of vch.h
 constexpr int GP_NV = (4096 + 1 + T1 - 1) / T1;            // values of a row per thread at the largest N
-constexpr int GP_MAXIT = 100;                              // the bracket ends the iteration long before
+// A cap, not the usual end: the bracket ends the iteration after at most 54 steps on 32 000 groups of the regimes of
+// tests/test_gpu_dirsparse_edges_1d.py (a CPU port of gp_step; |c / lam - 1| >= 1e-9).  A group at the threshold itself
+// (lam = c (1 - 2^-52) under a one-sided box, root at s ~ 1e-16) can run into the cap, about one group in 300 of that kind;
+// the s it then holds is within 6e-16 of the bisection's.
+constexpr int GP_MAXIT = 100;
 constexpr int GC_W = 16, GC_T = 64 * GC_W;                 // the column kernels: 64 columns across the lanes, rows over GC_W waves
 // values per thread the rows kernel is instantiated with: the smallest of 1, 2, 4, GP_NV that holds a row of n nodes (a short
 // row in a kernel built for the longest would leave most registers, and with them most of the CU, idle)

@@ -55,36 +55,41 @@ def group_prox(v, w, lam, lo, hi):
     return np.clip(b * v, lo, hi), b, "box"
 
 
-def group_prox_many(V, w, lam, lo, hi):
+def group_prox_many(V, w, lam, lo, hi, dtype=np.float64):
     """group_prox of every row of V (G, m), the same formulas with the bisection of all box-active rows run side by side
-    -> (U (G, m), s (G,), kinds: list of G names)."""
-    V = np.asarray(V, dtype=np.float64)
+    -> (U (G, m), s (G,), kinds: list of G names).  `dtype` np.longdouble: the same V, w and lam (doubles) with every
+    product, sum, square root and the bisection (to adjacent long doubles) in extended precision; U and s come back in it.
+    That variant is the yardstick of this restatement's own rounding: its sums carry 11 more bits than any order of a
+    double sum loses on a row of a few thousand nodes."""
+    V, w, lam = np.asarray(V, dtype=np.float64).astype(dtype), np.asarray(w, dtype=np.float64).astype(dtype), dtype(lam)
+    one = dtype(1.0)
     nrm = lambda Z: np.sqrt(np.sum(w * Z * Z, axis=1))
     live = nrm(cone(V, lo, hi)) > lam
     with np.errstate(divide="ignore", invalid="ignore"):
-        s = np.where(live, 1.0 - lam / nrm(V), 0.0)
+        s = np.where(live, one - lam / nrm(V), dtype(0.0))
     S0 = s[:, None] * V
     box = live & np.any(np.clip(S0, lo, hi) != S0, axis=1)
-    Vb, a, b = V[box], np.zeros(int(box.sum())), np.ones(int(box.sum()))
+    Vb, a, b = V[box], np.zeros(int(box.sum()), dtype=dtype), np.ones(int(box.sum()), dtype=dtype)
     while Vb.size:
-        m = a + 0.5 * (b - a)
+        m = a + dtype(0.5) * (b - a)
         go = (a < m) & (m < b)
         if not go.any():
             break
-        pos = nrm(np.clip(m[:, None] * Vb, lo, hi)) * (1.0 - m) - lam * m > 0.0
+        pos = nrm(np.clip(m[:, None] * Vb, lo, hi)) * (one - m) - lam * m > 0.0
         a, b = np.where(go & pos, m, a), np.where(go & ~pos, m, b)
     s[box] = b
-    U = np.where(live[:, None], np.clip(s[:, None] * V, lo, hi), 0.0)
+    U = np.where(live[:, None], np.clip(s[:, None] * V, lo, hi), dtype(0.0))
     return U, s, ["box" if x else ("closed" if y else "zero") for x, y in zip(box, live)]
 
 
-def prox(u, r, alpha, b3, ks, lo, hi, mode, x=None, t_hist=None):
-    """(u+, s, kinds) of one (rows, n) control: the gradient step v = u - alpha (r + b3 u), then the prox of the mode."""
+def prox(u, r, alpha, b3, ks, lo, hi, mode, x=None, t_hist=None, dtype=np.float64):
+    """(u+, s, kinds) of one (rows, n) control: the gradient step v = u - alpha (r + b3 u) in doubles, then the prox of the
+    mode (in `dtype`, see group_prox_many)."""
     u = np.asarray(u, dtype=np.float64)
     v = u - alpha * (r + b3 * u)
     if mode == "time":
-        return group_prox_many(v, trapz_w(x), alpha * ks, lo, hi)
-    out, s, kinds = group_prox_many(np.ascontiguousarray(v.T), trapz_w(t_hist), alpha * ks, lo, hi)
+        return group_prox_many(v, trapz_w(x), alpha * ks, lo, hi, dtype)
+    out, s, kinds = group_prox_many(np.ascontiguousarray(v.T), trapz_w(t_hist), alpha * ks, lo, hi, dtype)
     return np.ascontiguousarray(out.T), s, kinds
 
 
@@ -117,18 +122,21 @@ def kkt(u, r, x, t_hist, b3, ks, lo, hi, mode, tol=1e-6):
     return np.array([zero.sum(), small.sum(), (zero == small).sum(), zero.size], dtype=np.int64), stat
 
 
-def pgd(O1, P, O, mode, n_iter, initial_phi=None):
+def pgd(O1, P, O, mode, n_iter, initial_phi=None, u0=None, alpha0=None):
     """The loop of vch_pgd.h's 1D rule (optimistic step with alpha_prev, else backtracking with beta 0.8 and at most 5
-    trials, growth 1.2) over the oracle's forward / backward, with the prox and J4 of the mode.  Short runs only: the
-    plateau and stop rules need k > 10 and are left out.  -> dict(costs, trials, u, phi, r of the last sweep, x, t_hist)."""
+    trials, growth 1.2) over the oracle's forward / backward, with the prox and J4 of the mode.  `u0` (rows, n): the start
+    control, taken as given (not clipped; default zeros); `alpha0`: the first step, capped at alpha_max (default alpha_max).
+    Short runs only: the plateau and stop rules need k > 10 and are left out.  -> dict(costs, trials, change, u, phi, x,
+    t_hist, phi_Q, phi_T), change[k] = ||u_{k+1} - u_k||_F / (||u_k||_F + 1e-9), the stop rule's quantity."""
     fwd = lambda u: O1.forward(P, control=u, initial_phi=initial_phi)
-    phi_k, x, t_hist = fwd(None)
-    u_k = np.zeros_like(phi_k)
+    phi_k, x, t_hist = fwd(None if u0 is None else np.asarray(u0, dtype=np.float64))
+    u_k = np.zeros_like(phi_k) if u0 is None else np.array(u0, dtype=np.float64)
     phi_T, phi_Q = O1.build_targets(x, t_hist, phi_k[0].copy(), P.Lx, P.T, 1, 1)
     J = lambda phi, u: cost(O1, phi, u, phi_Q, phi_T, x, t_hist, O.b1, O.b2, O.b3, O.kappa_sparsity, mode)
     step = lambda u, r, a: prox(u, r, a, O.b3, O.kappa_sparsity, O.u_min, O.u_max, mode, x, t_hist)[0]
     cost_k = J(phi_k, u_k)
-    costs, trials, alpha_prev = [cost_k], [], O.alpha_max
+    costs, trials, change = [cost_k], [], []
+    alpha_prev = O.alpha_max if alpha0 is None else min(float(alpha0), O.alpha_max)
     for _ in range(n_iter):
         r_k = O1.backward(phi_k, x, t_hist, O.b1, O.b2, phi_Q, phi_T)[2]
         alpha, nt = alpha_prev, 0
@@ -142,9 +150,10 @@ def pgd(O1, P, O, mode, n_iter, initial_phi=None):
             alpha *= 0.8
         costs.append(c_n)
         trials.append(nt)
+        change.append(float(np.linalg.norm(u_n - u_k) / (np.linalg.norm(u_k) + 1e-9)))
         alpha_prev = min(O.alpha_max, alpha * 1.2)
         u_k, cost_k, phi_k = u_n, c_n, phi_n
-    return dict(costs=costs, trials=trials, u=u_k, phi=phi_k, x=x, t_hist=t_hist, phi_Q=phi_Q, phi_T=phi_T)
+    return dict(costs=costs, trials=trials, change=change, u=u_k, phi=phi_k, x=x, t_hist=t_hist, phi_Q=phi_Q, phi_T=phi_T)
 
 
 def brute_force_improvement(v, w, lam, lo, hi, u, rng, tries=400):

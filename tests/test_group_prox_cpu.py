@@ -119,6 +119,65 @@ def test_modes_costs_and_kkt_of_the_restatement():
     assert [k == "zero" for k in kinds] == list(vn <= 0.6)
 
 
+def test_long_double_variant_of_the_side_by_side_bisection():
+    """dtype=np.longdouble runs the same formulas on the same doubles in extended precision: it returns long doubles, agrees
+    with the double variant on the kind and to a few ulps of a double on s, and is exact to its own precision where the
+    answer is known in closed form."""
+    LD = np.longdouble
+    assert np.finfo(LD).eps < 1e-18
+    rng = np.random.default_rng(10)
+    for lo, hi in BOXES:
+        w = rng.uniform(0.2, 1.5, 9)
+        w[2] = 0.0
+        V = rng.standard_normal((40, 9)) * 10.0 ** rng.uniform(-1.5, 0.7, (40, 1))
+        U, s, kinds = G.group_prox_many(V, w, 0.4, lo, hi)
+        Ul, sl, kl = G.group_prox_many(V, w, 0.4, lo, hi, dtype=LD)
+        assert Ul.dtype == LD and sl.dtype == LD and s.dtype == np.float64 and U.dtype == np.float64
+        assert kinds == kl and np.max(np.abs(s - sl)) <= 1e-15 and np.max(np.abs(U - Ul)) <= 1e-15 * np.max(np.abs(V))
+    # ||(3, 4)|| = 5, lam = 1: s = 4/5, which no double holds
+    s = G.group_prox_many(np.array([[3.0, 4.0]]), np.ones(2), 1.0, -np.inf, np.inf, dtype=LD)[1]
+    assert abs(s[0] - LD(4) / LD(5)) <= 2 * np.finfo(LD).eps
+    # v = (3, 8) under u_max = 2: at s = 1/2 the second entry is cut, rho = ||(3/2, 2)|| = 5/2 and rho (1 - s) = lam s for lam = 5/2
+    U, s, kinds = G.group_prox_many(np.array([[3.0, 8.0]]), np.ones(2), 2.5, -1.0, 2.0, dtype=LD)
+    assert kinds == ["box"] and abs(s[0] - LD(0.5)) <= 2 * np.finfo(LD).eps and np.max(np.abs(U[0] - [1.5, 2.0])) <= 4 * np.finfo(LD).eps
+    for mode in ("time", "space"):
+        u, r = rng.standard_normal((2, 6, 7))
+        x, t = np.linspace(0, 1, 7), np.r_[0.0, np.linspace(0, 1, 5)]
+        a, b = G.prox(u, r, 0.5, 0.1, 1.2, -1.0, 1.0, mode, x, t), G.prox(u, r, 0.5, 0.1, 1.2, -1.0, 1.0, mode, x, t, dtype=LD)
+        assert a[2] == b[2] and b[0].shape == u.shape and np.max(np.abs(a[1] - b[1])) <= 1e-15
+
+
+def test_loop_of_the_restatement_from_a_warm_start():
+    """pgd's u0, alpha0 and change: the defaults are the run from u = 0 with alpha_max; alpha0 is capped at alpha_max; a
+    warm start is where the first step starts from; change[k] is ||u_{k+1} - u_k||_F / (||u_k||_F + 1e-9)."""
+    from oracle import vch1d_oracle as O1
+    P = O1.Params1D(N=16, T=0.03, dt_initial=1e-2)
+    same = lambda a, b: a["costs"] == b["costs"] and a["trials"] == b["trials"] and a["change"] == b["change"] and np.array_equal(a["u"], b["u"])
+    for mode, ks in (("time", 0.03), ("space", 0.005)):             # some groups of the first step vanish, some do not
+        O = O1.OptParams1D(kappa_sparsity=ks, alpha_max=40.0, u_min=-0.3, u_max=0.5)
+        base = G.pgd(O1, P, O, mode, 2)
+        gn = G.group_norms(G.pgd(O1, P, O, mode, 1)["u"], base["x"], base["t_hist"], mode)[1:]
+        assert 0 < np.count_nonzero(gn) < gn.size
+        assert len(base["change"]) == 2 and base["u"].shape == (5, 17)
+        assert same(base, G.pgd(O1, P, O, mode, 2, u0=np.zeros((5, 17)), alpha0=40.0))
+        assert same(base, G.pgd(O1, P, O, mode, 2, alpha0=1e9))
+        assert not same(base, G.pgd(O1, P, O, mode, 2, alpha0=5.0))
+        one = G.pgd(O1, P, O, mode, 1)
+        assert base["change"][0] == np.linalg.norm(one["u"]) / 1e-9                  # from u = 0: the quotient means nothing
+        assert base["change"][1] == np.linalg.norm(base["u"] - one["u"]) / (np.linalg.norm(one["u"]) + 1e-9)
+        # a warm start outside the box is taken as given: the loop continued from `one` is the loop of two iterations,
+        # given the step size it would have had
+        rng = np.random.default_rng(4)
+        u0 = 0.6 * rng.standard_normal((5, 17))
+        w1, w2 = G.pgd(O1, P, O, mode, 1, u0=u0, alpha0=3.0), G.pgd(O1, P, O, mode, 2, u0=u0, alpha0=3.0)
+        assert w1["costs"][0] == w2["costs"][0] and w1["costs"][0] != base["costs"][0]
+        assert w2["change"][0] == np.linalg.norm(w1["u"] - u0) / (np.linalg.norm(u0) + 1e-9) < 10.0
+        a1 = min(O.alpha_max, 3.0 * 0.8 ** (w1["trials"][0] - 1 + (w1["costs"][1] >= w1["costs"][0])) * 1.2)
+        cont = G.pgd(O1, P, O, mode, 1, u0=w1["u"], alpha0=a1)
+        assert cont["trials"][0] == w2["trials"][1] and np.allclose(cont["u"], w2["u"], rtol=0, atol=1e-12)
+        assert np.isclose(cont["change"][0], w2["change"][1], rtol=1e-10)
+
+
 # ---- the public surface (fails without the feature) ---------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def V():
