@@ -590,6 +590,7 @@ class PGDResult:
     alphas: list = field(default_factory=list)
     alphas_used: list = field(default_factory=list)   # the step the accepted control was made with, see pgd
     trials: list = field(default_factory=list)
+    changes: list = field(default_factory=list)       # relative control change of every iteration (the stop rule's input)
     tracking: list = field(default_factory=list)
     terminal: list = field(default_factory=list)
     u: np.ndarray = None
@@ -659,6 +660,7 @@ def pgd(P: Params1D, O: OptParams1D, n_iter=None, choice_t=1, choice_q=1, solver
         else:
             alpha_prev = min(O.alpha_max, a_k * 1.2)
         change = np.linalg.norm(u_n - u_k) / (np.linalg.norm(u_k) + 1e-9)
+        res.changes.append(change)
         if change < 1e-5 and k > 10:
             u_k = u_n.copy()
             res.converged = True

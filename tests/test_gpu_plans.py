@@ -251,10 +251,27 @@ def test_engine_variants_agree(V, O2, g):
         assert np.max(np.abs(ph - phs)) < 1e-10, (sw, float(np.max(np.abs(ph - phs))))
 
 
+# The loop's by-products against the oracle's loop.  The oracle solves to other tolerances than the engine, so these are
+# measured, not derived: 10x the worst gap seen on the MI355X over the cases of the two tests below (change 3.06e-8 at
+# 512 x 16, errors 7.33e-15 in the batch of 33 at 16 x 16; profiles/pgd_byproducts.txt), which is far inside what the same
+# tests give the quantities they derive from (the errors from the cost, 1e-7; the change from u, 1e-6).  The errors are
+# ratios near 1 that two short iterations barely move, hence the small figure; it is below what a reordered sum may cost
+# (nodes x 2^-52), so a change of the reduction order means measuring again.  The derived comparison is
+# tests/test_gpu_pgd_byproducts.py.
+ERR_TOL, CHANGE_TOL = 7.4e-14, 3.1e-7
+
+
+def _byproduct_gaps(out, b, r):
+    """The largest relative gaps of trajectory b's change / tracking_error / terminal_error to those of the oracle's loop r."""
+    return tuple(float(np.max(np.abs(out[k][b] / np.asarray(ref) - 1.0)))
+                 for k, ref in (("change", r.changes), ("tracking_error", r.tracking), ("terminal_error", r.terminal)))
+
+
 @pytest.mark.parametrize("g", [(512, 16, 2.0, 0.25), (16, 512, 0.25, 2.0), (100, 70, 1.3, 0.9)], ids=gid)
 def test_pgd_two_iterations_vs_oracle(V, O2, g):
     """Two device-resident PGD iterations (adjoint sweep, prox, optimistic march, line search) per orientation of the
-    1024-point plan and on the GEMM path, B = 2, against O2.pgd: equal attempts and step lengths, costs to 1e-7."""
+    1024-point plan and on the GEMM path, B = 2, against O2.pgd: equal attempts and step lengths, costs to 1e-7, the
+    relative control change to CHANGE_TOL and the tracking / terminal errors to ERR_TOL."""
     Nx, Ny, Lx, Ly = g
     P = O2.Params2D(Nx=Nx, Ny=Ny, Lx=Lx, Ly=Ly, T=M * DT, dt_initial=DT)
     Op = O2.OptParams()
@@ -273,6 +290,9 @@ def test_pgd_two_iterations_vs_oracle(V, O2, g):
         assert np.allclose(out["alpha"][b], r.alphas, rtol=1e-12, atol=0), (out["alpha"][b], r.alphas)
         assert np.allclose(out["cost"][b], r.costs[1:], rtol=1e-7, atol=0), (out["cost"][b], r.costs)
         assert relerr(u[b], r.u) < 1e-6
+        gc, gq, gt = _byproduct_gaps(out, b, r)
+        print(f"MEASURE oracle two_iterations {gid(g)} b {b}: change {gc:.2e} tracking {gq:.2e} terminal {gt:.2e}")
+        assert gc < CHANGE_TOL and gq < ERR_TOL and gt < ERR_TOL, (b, gc, gq, gt)
 
 
 def test_column_pass_width_variants(V, O2):
@@ -418,7 +438,8 @@ def test_batch_beyond_guess_bmax_vs_oracle(V, O2, g, B):
 
 @pytest.mark.parametrize("g", SMALL, ids=gid)
 def test_pgd_batch_33_vs_oracle(V, O2, g):
-    """Two PGD iterations of a 33-trajectory batch (distinct seeds) against O2.pgd per trajectory."""
+    """Two PGD iterations of a 33-trajectory batch (distinct seeds) against O2.pgd per trajectory, the relative control
+    change and the tracking / terminal errors included (CHANGE_TOL, ERR_TOL)."""
     Nx, Ny, Lx, Ly = g
     B = 33
     P = O2.Params2D(Nx=Nx, Ny=Ny, Lx=Lx, Ly=Ly, T=M * DT, dt_initial=DT)
@@ -436,3 +457,6 @@ def test_pgd_batch_33_vs_oracle(V, O2, g):
         assert list(out["attempts"][b]) == list(r.attempts), (b, out["attempts"][b], r.attempts)
         assert np.allclose(out["alpha"][b], r.alphas, rtol=1e-12, atol=0), (b, out["alpha"][b], r.alphas)
         assert np.allclose(out["cost"][b], r.costs[1:], rtol=1e-7, atol=0), (b, out["cost"][b], r.costs)
+        gc, gq, gt = _byproduct_gaps(out, b, r)
+        print(f"MEASURE oracle batch_33 {gid(g)} b {b}: change {gc:.2e} tracking {gq:.2e} terminal {gt:.2e}")
+        assert gc < CHANGE_TOL and gq < ERR_TOL and gt < ERR_TOL, (b, gc, gq, gt)
