@@ -442,6 +442,8 @@ int vch2d_cg_vector(vch2d_ctx *ctx, int which /* 0: x, 1: r, 2: p */, double *ou
  * unused, so the storage and every request are those of vch2d_hess_cg.  The host uploads the B radii before the start and
  * looks as vch2d_hess_cg does; a boundary exit takes the launches of one ordinary step.  x, r = P b - P H P x and p stay
  * resident for vch2d_cg_vector and vch2d_newton_trial.  xnorm_out [B]: ||x||_D by the recurrence (0 for P b == 0).
+ * As in vch1d_hess_cg_tr, a radius whose square is not finite (>= 2^512) has no boundary and acts as +inf, and a radius
+ * whose square underflows gives a zero step.
  * VCH_ERR_ARG, before anything is enqueued, copied or allocated, for NULL radius or xnorm_out and a radius_b that is not > 0
  * (NaN included; +inf is allowed). */
 int vch2d_hess_cg_tr(vch2d_ctx *ctx, const double *dt, int M, const double *t_hist, const double *x, const double *y,
@@ -965,8 +967,10 @@ int vch1d_hess_cg(vch1d_ctx *ctx, const double *phi_hist, const double *u, int n
  * A step to the boundary updates x and r as any step does (r = P b - P H P x stays true for vch1d_cg_vector), adds
  * tau rho - tau^2 c / 2 to pred, writes resid[j] and counts in steps_out.  xnorm_out [B]: ||x||_D by the recurrence (0 for
  * P b == 0).  With radius = +inf every output, x, r and p are bitwise those of vch1d_hess_cg on a trajectory that ends
- * VCH_CG_CONVERGED or VCH_CG_LIMIT.  VCH_ERR_ARG, before anything is enqueued, for NULL radius or xnorm_out and a radius_b
- * that is not > 0 (NaN included). */
+ * VCH_CG_CONVERGED or VCH_CG_LIMIT.  The kernel forms radius^2 in a double: a radius whose square is not finite (>= 2^512)
+ * has no boundary and acts as +inf; a radius whose square underflows gives a zero step (tau = 0: x = 0, r = P b, pred = 0
+ * after one counted step, VCH_CG_BOUNDARY, or VCH_CG_NEGCURV where the first direction has non-positive curvature).
+ * VCH_ERR_ARG, before anything is enqueued, for NULL radius or xnorm_out and a radius_b that is not > 0 (NaN included). */
 int vch1d_hess_cg_tr(vch1d_ctx *ctx, const double *phi_hist, const double *u, int n_base, int rows,
                      const double *dt, const double *t_hist, const double *x,
                      const double *phi_Q, const double *phi_T, const vch_opt_params *opts, int n_opts,

@@ -622,7 +622,9 @@ class Engine2D:
         the identity without.  radius: [B] or a scalar, > 0, +inf allowed.  A step that would leave the region, or a
         direction of non-positive curvature, is followed to the boundary: "boundary" and "negcurv" of TRUST_CG_STATUS.
         Returns hess_cg's dict (status: indices of TRUST_CG_STATUS) plus xnorm: [B] ||x||_D by the recurrence.  With
-        radius = inf everything equals hess_cg's bit for bit on a trajectory that ends "converged" or "limit"."""
+        radius = inf everything equals hess_cg's bit for bit on a trajectory that ends "converged" or "limit".  A radius
+        whose square is not finite (>= 2^512) has no boundary and acts as +inf; a radius whose square underflows gives a zero
+        step (x = 0 after one counted step)."""
         k = int(k)
         dt, t_hist, x, y, M = self._base_point(dt, t_hist, x, y)
         rhs = None if rhs is None else self._hist(rhs, M + 1, "rhs")
@@ -1252,7 +1254,9 @@ class Engine1D:
         the identity without.  radius: [B] or a scalar, > 0, +inf allowed.  A step that would leave the region, or a
         direction of non-positive curvature, is followed to the boundary: "boundary" and "negcurv" of TRUST_CG_STATUS.
         Returns hess_cg's dict (status: indices of TRUST_CG_STATUS) plus xnorm: [B] ||x||_D by the recurrence.  With
-        radius = inf everything equals hess_cg's bit for bit on a trajectory that ends "converged" or "limit"."""
+        radius = inf everything equals hess_cg's bit for bit on a trajectory that ends "converged" or "limit".  A radius
+        whose square is not finite (>= 2^512) has no boundary and acts as +inf; a radius whose square underflows gives a zero
+        step (x = 0 after one counted step)."""
         t_hist, rows, nb, keep, dt, x, arr = self._base_point(t_hist, phi_hist, u, phi_Q, phi_T, dt, x, opt, shared_base)
         k = int(k)
         rhs = None if rhs is None else self._hist(rhs, rows, "rhs")

@@ -9,7 +9,10 @@ test_gpu_trust_1d.py compares the engine with it.
                        (a tau that is not finite, radius = inf: NEGCURV at once, x as it is, as _cg_ref.cg)
             alpha = rho / c;  xx + 2 alpha xp + alpha^2 pp >= radius^2: the same tau, exit BOUNDARY after the step tau
             a step to the boundary: x += tau p, r -= tau P A p, pred += tau rho - tau^2 c / 2, resid[j], steps = j + 1
-            otherwise the step of _cg_ref.cg, then xx += 2 alpha xp + alpha^2 pp, xp = beta (xp + alpha pp)"""
+            otherwise the step of _cg_ref.cg, then xx += 2 alpha xp + alpha^2 pp, xp = beta (xp + alpha pp)
+
+radius^2 is formed in a double, as on the device: a radius whose square is not finite (>= 2^512) has no boundary and acts as
+inf; a radius whose square underflows gives tau = 0, one counted step that moves nothing."""
 import math
 
 import numpy as np
@@ -145,3 +148,68 @@ def trust_rounds(A, c, kappa, w, u, lo, hi, n_rounds, radius0, radius_max=None, 
         if rec["status"] == ACCEPTED:
             u, rec["cost_new"] = t, Jt
     return u, recs
+
+
+def replay(R, i, radius_max, radius_min):
+    """Member i of the record against `judge`, exactly: the status of every judged round and the radius (or
+    IDLE) of the round after it."""
+    n = R["status"].shape[1]
+    for r in range(n):
+        st = int(R["status"][i, r])
+        if st in (IDLE, STATIONARY, NT_BREAKDOWN):
+            assert all(R["status"][i, r + 1:] == IDLE)
+            return
+        cost, pred, ratio, xnorm, cgs, radius = (R[key][i, r] for key in ("cost", "pred", "ratio", "xnorm", "cg_status", "radius"))
+        c_new = R["cost_new"][i, r] if st == ACCEPTED else cost - ratio * pred
+        assert judge(cost, pred, c_new, xnorm, cgs, radius, radius_max, radius_min)[0] == st, (i, r)
+        _, same, new_radius, ended = judge(ratio, 1.0, 0.0, xnorm, cgs, radius, radius_max, radius_min)       # (ratio - 0) / 1: the ratio itself
+        assert same == ratio or (np.isnan(same) and np.isnan(ratio))
+        assert (st == STALLED) == (ended and st != ACCEPTED), (i, r)
+        if st != ACCEPTED:
+            assert R["cost_new"][i, r] == cost, (i, r)
+        if r + 1 < n:
+            if ended:
+                assert R["status"][i, r + 1] == IDLE, (i, r)
+            else:
+                assert R["radius"][i, r + 1] == new_radius and R["cost"][i, r + 1] == R["cost_new"][i, r], (i, r)
+
+
+def host_rounds(march, solve, trial, full_cost, u0, n_rounds, radius0, radius_max, radius_min):
+    """The host loop of GD_1D.trust_refine / GD2_configured.trust_refine over three engine calls, with the verdicts of
+    `judge`: march(u) makes u the base point, solve(u, radius) -> the dict of hess_cg_trust (batch 1), trial() -> the control
+    of newton_trial(1), full_cost(u) -> J of a march of u.  -> (u, records); the loop ends with the trajectory."""
+    u, radius = np.array(u0), float(radius0)
+    cost = full_cost(u)
+    recs = []
+    for _ in range(n_rounds):
+        march(u)
+        S = solve(u, radius)
+        rec = dict(cost=cost, cost_new=cost, radius=radius, steps=int(S["steps"][0]), cg_status=int(S["status"][0]),
+                   n_free=int(S["n_free"][0]), status=None)
+        recs.append(rec)
+        assert rec["n_free"] >= 1 and S["rnorm0"][0] > 0.0 and rec["cg_status"] in (LIMIT, CONVERGED, NEGCURV, BOUNDARY)
+        t = trial()
+        J = full_cost(t)
+        rec["status"], _, radius, ended = judge(cost, float(S["pred"][0]), J, float(S["xnorm"][0]), rec["cg_status"], radius, radius_max,
+                                                radius_min)
+        if rec["status"] == ACCEPTED:
+            u, cost, rec["cost_new"] = t, J, J
+        if ended:
+            break
+    return u, recs
+
+
+def off_block_members(q, box_cut, dnorm):
+    """The batch of three of the rounds off one block, for either engine (box_cut and dnorm are the engine's helpers).
+    Member 0: b3 = 1 from the control cut to 0.7 of its amplitude inside the box at 0.75 of it, in a twentieth of its norm:
+    the Newton step is about -u, so the solve leaves the region (BOUNDARY).  Member 1: the same start with b3 = -100, far
+    below the reduced Hessian of the tracking terms in the mass norm (b1 T^2 + b2 T, 0.3 at T = 0.03 and 2.2 at T = 0.2,
+    bounds it for a march that does not amplify): the first CG direction has negative curvature (NEGCURV).  Member 2: the
+    box-cut start of the damped rounds' tests inside ten times its norm: the trial is clipped to the bound 2^-20 below, gains
+    less than a quarter of pred, and the radius is quartered.  -> (opts, u0, radius0)."""
+    mk = q.V.make_opt
+    top = float(np.abs(q.u).max())
+    u = np.clip(q.u, -0.7 * top, 0.7 * top)
+    cut, half = box_cut(q)
+    opts = [mk(b3=1.0, u_min=-0.75 * top, u_max=0.75 * top), mk(b3=-100.0, u_min=-0.75 * top, u_max=0.75 * top), cut]
+    return opts, np.stack([u, u, half]), np.array([0.05 * dnorm(q, u, True), 0.02 * dnorm(q, u, True), 10.0 * dnorm(q, half, True)])

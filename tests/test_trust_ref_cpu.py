@@ -111,6 +111,40 @@ def test_negative_definite_block_steps_along_the_preconditioned_gradient(precond
     assert S["pred"] > 0                                  # tau rho - tau^2 c / 2 with c < 0
 
 
+@pytest.mark.parametrize("precond", [False, True])
+def test_a_radius_whose_square_is_not_finite_has_no_boundary(precond):
+    """d2 = radius * radius: 2^600 squares to +inf, tau is not finite and the call is the radius = inf call (NEGCURV at once,
+    x = 0); 2^500 squares to 2^1000 and the direction of negative curvature is followed to the boundary."""
+    A = -_spd(16, 4)
+    mask, b, D = _case(16, 4)
+    D = D if precond else None
+    inf = steihaug(lambda v: A @ v, mask, b, 10, math.inf, 0.0, D)
+    big = steihaug(lambda v: A @ v, mask, b, 10, 2.0 ** 600, 0.0, D)
+    assert inf["status"] == NEGCURV and inf["steps"] == 0 and not inf["x"].any() and inf["pred"] == 0.0 and inf["xnorm"] == 0.0
+    assert set(big) == set(inf)
+    for key in inf:
+        assert np.array_equal(big[key], inf[key], equal_nan=True), key
+    mid = steihaug(lambda v: A @ v, mask, b, 10, 2.0 ** 500, 0.0, D)
+    Dv = np.ones(16) if D is None else D
+    direct = math.sqrt(float(np.sum(Dv * mid["x"] ** 2)))
+    assert mid["status"] == NEGCURV and mid["steps"] == 1 and np.isfinite(mid["x"]).all() and np.isfinite(mid["pred"]) and mid["pred"] > 0
+    assert abs(mid["xnorm"] - 2.0 ** 500) <= 4 * EPS * 2.0 ** 500 and abs(direct - 2.0 ** 500) <= 4 * EPS * 2.0 ** 500
+
+
+@pytest.mark.parametrize("precond", [False, True])
+def test_a_radius_whose_square_underflows_gives_a_zero_step(precond):
+    """d2 = 0 for radius 2^-600: the first step already leaves the region, tau = 0, and the exit is BOUNDARY after one step
+    that moves nothing."""
+    A = _spd(24, 3)
+    mask, b, D = _case(24, 3)
+    S = steihaug(lambda v: A @ v, mask, b, 10, 2.0 ** -600, 0.0, D if precond else None)
+    assert S["status"] == BOUNDARY and S["steps"] == 1
+    assert not S["x"].any() and S["pred"] == 0.0 and S["xnorm"] == 0.0 and S["resid"][0] == 1.0
+    assert np.array_equal(S["r"], np.where(mask, b, 0.0))
+    assert all(np.isfinite(S[key]).all() for key in ("x", "r", "p", "pred", "rnorm0", "xnorm")) and np.isfinite(S["curv"][0])
+    assert np.isnan(S["resid"][1:]).all()
+
+
 @pytest.mark.parametrize("matrix", ["spd", "indefinite"])
 @pytest.mark.parametrize("radius", [0.01, 0.5, 3.0, 1e3])
 def test_the_decrease_is_at_least_the_cauchy_point_s(matrix, radius):
