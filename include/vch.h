@@ -762,6 +762,46 @@ int vch1d_cost_g(vch1d_ctx *ctx, const double *phi_hist, const double *u, const 
                  const double *phi_T, int rows, const double *x, const double *t_hist,
                  const vch_opt_params *opt, int sparsity, double *J_out);
 
+/* Directional sparsity in the 2D engine (ABI version stays 3: detect the three entry points below by symbol).
+ * The same two functionals, the same modes and the same prox per group as in 1D (above), with the groups of a control
+ * [rows][Nx+1][Ny+1]:
+ *   VCH_SPARSITY_TIME   group k is level k, ||z||^2 = sum_ij W_ij z_ij^2, W_ij = wx_i wy_j the product trapezoid weights of
+ *                       x and y (the cost's own);
+ *   VCH_SPARSITY_SPACE  group (i, j) is the pencil u[:, i, j], ||z||^2 = sum_k wt_k z_k^2, wt the trapezoid weights of t_hist
+ *                       (strictly increasing: no level of weight zero but through a grid the caller repeats a node of).
+ * J4 becomes kappa_s * trapezoid in t of sqrt(sum_ij W_ij u^2) (TIME) or kappa_s sum_ij W_ij sqrt(sum_k wt_k u^2) (SPACE);
+ * J1..J3 are unchanged.  No floating-point atomics and one summation order fixed by the grid: a member of a mixed batch
+ * computes the bits of a single run with its mode and parameters.
+ *
+ * vch2d_pgd_init_g: vch2d_pgd_init_v with a mode per trajectory: sparsity[n_sparsity], n_sparsity = 1 or B.  All
+ * VCH_SPARSITY_FULL is vch2d_pgd_init_v bit for bit; vch2d_pgd_init and vch2d_pgd_init_v reset every mode to FULL.
+ * VCH_ERR_ARG, before anything is copied or enqueued and with the resident problem left as it was: NULL sparsity, n_sparsity
+ * neither 1 nor B, a mode outside 0..2, a group-mode trajectory whose box does not contain 0.
+ * vch2d_pgd_iterate, vch2d_pgd_kkt, vch2d_pgd_get and vch2d_pgd_errors then act per trajectory on its mode.  For a
+ * group-mode trajectory vch2d_pgd_kkt counts groups: counts_out[b] = { #groups ||u_g|| < tol, #groups ||r_g|| <=
+ * kappa_sparsity, #groups where the two agree, #groups = M+1 or (Nx+1)(Ny+1) } in the group's norm, and the stationarity
+ * takes the mode's prox at alpha = 1.
+ * Refused with VCH_ERR_STATE before anything is enqueued while any trajectory of the resident problem is in a group mode:
+ * vch2d_pgd_newton, vch2d_pgd_trust, vch2d_newton_trial, and vch2d_hess_cg / vch2d_hess_cg_tr about the resident iterate
+ * with rhs == NULL: they build the sign term and the free set of the L1 functional.  vch2d_second_order, vch2d_hessvec,
+ * vch2d_hess_lanczos and vch2d_hess_cg with an explicit rhs concern the smooth part only and keep working. */
+int vch2d_pgd_init_g(vch2d_ctx *ctx, const double *phi0, const double *phi_T, const double *phi_Q,
+                     int ramp, double T, const double *t_hist, int M, const double *x, const double *y,
+                     const vch_opt_params *opts, int n_opts, const double *u0 /* or NULL */,
+                     const double *alpha0 /* [B] or NULL */, const int32_t *sparsity /* [n_sparsity] */,
+                     int n_sparsity /* 1 or B */, double *J0_out /* [B][5] */);
+/* The stateless seam of the prox: vch2d_grad_prox with the mode `sparsity` for the whole batch.  x [Nx+1], y [Ny+1] (TIME)
+ * and t_hist [rows] (SPACE) give the group's weights and may be NULL where the mode does not read them.  scale_out (or NULL)
+ * receives s per group, [B][rows] for TIME or [B][Nx+1][Ny+1] for SPACE.  VCH_SPARSITY_FULL is vch2d_grad_prox (scale_out
+ * is not written).  VCH_ERR_ARG for a mode outside 0..2 and, in a group mode, for a box that does not contain 0. */
+int vch2d_grad_prox_g(vch2d_ctx *ctx, const double *u, const double *r, int rows, const double *x,
+                      const double *y, const double *t_hist, const double *alpha,
+                      const vch_opt_params *opt, int sparsity, double *u_out, double *scale_out);
+/* vch2d_cost with J4 of the mode `sparsity`; VCH_SPARSITY_FULL is vch2d_cost. */
+int vch2d_cost_g(vch2d_ctx *ctx, const double *phi_hist, const double *u, const double *phi_Q,
+                 const double *phi_T, int M, const double *x, const double *y, const double *t_hist,
+                 const vch_opt_params *opt, int sparsity, double *J_out);
+
 /* Exact first and second directional derivatives of the smooth part J1 + J2 + J3 of the 1D cost along h, by a tangent
  * (linearised) march on the device: the 1D counterpart of vch2d_second_order (ABI version stays 3: detect this entry point
  * by symbol).  One persistent workgroup per direction runs the whole march and the quadrature; no adjoint, no nonlinear

@@ -60,8 +60,10 @@ def perform_backtracking_line_search_2D(u_k, cost_k, grad_smooth, phi_Q_target, 
 
 
 def run_optimization(fwd_config: ForwardSolverConfig, opt_config: OptimizationConfig, n_iter=None, seeds=(42,),
-                     choice_t=DEFAULT_TARGET_CHOICE, choice_q=DEFAULT_TRACKING_CHOICE, amp=0.1, device=0):
+                     choice_t=DEFAULT_TARGET_CHOICE, choice_q=DEFAULT_TRACKING_CHOICE, amp=0.1, device=0, sparsity=None):
     """The PGD loop of G2:291-382 for a batch of initial conditions (`seeds`), device-resident.
+    `sparsity`: a name of Engine2D.SPARSITY for the batch or one per seed (directional sparsity); None is the
+    reference's functional through the calls of before.
     Returns dict(costs [B][it+1], alphas, attempts, changes, tracking_error, terminal_error (the two relative
     error histories the driver appends per iteration, G2:336-363, from the cost kernel's sums), u, phi, r, seconds)."""
     Nx, Ny = int(fwd_config.Nx), int(fwd_config.Ny)
@@ -72,7 +74,7 @@ def run_optimization(fwd_config: ForwardSolverConfig, opt_config: OptimizationCo
     phi_T, _ = build_targets(eng.x, eng.y, t_hist, phi0[0], fwd_config.Lx, fwd_config.Ly, fwd_config.T,
                              choice_t=choice_t, choice_q=2)
     phi_Tb = np.broadcast_to(phi_T, phi0.shape).copy()
-    J0 = eng.pgd_init(phi0, phi_Tb, t_hist, make_opt(opt_config), ramp=(choice_q == 1), T=float(fwd_config.T))
+    J0 = eng.pgd_init(phi0, phi_Tb, t_hist, make_opt(opt_config), ramp=(choice_q == 1), T=float(fwd_config.T), sparsity=sparsity)
     n = int(opt_config.max_iter if n_iter is None else n_iter)
     res = eng.pgd_iterate(n)
     costs = np.concatenate([J0[:, 4:5], res["cost"]], axis=1)
@@ -82,7 +84,8 @@ def run_optimization(fwd_config: ForwardSolverConfig, opt_config: OptimizationCo
 
 
 def run_sweep(fwd_config: ForwardSolverConfig, opt_configs, n_iter=None, seed=42, amp=0.1, choice_t=DEFAULT_TARGET_CHOICE,
-              choice_q=DEFAULT_TRACKING_CHOICE, u0=None, return_controls=False, device=0, n_newton=0, n_trust=0, radius0=1.0):
+              choice_q=DEFAULT_TRACKING_CHOICE, u0=None, return_controls=False, device=0, n_newton=0, n_trust=0, radius0=1.0,
+              sparsity=None):
     """A parameter sweep as ONE batch: member b runs the PGD loop with opt_configs[b] (weights, sparsity parameter, box,
     alpha_max), all members from the same initial state (`seed`, `amp`) and targets, so that they differ by their
     parameters only.  `u0`: start control, one (M+1, Nx+1, Ny+1) array for every member or one per member (continuation
@@ -95,7 +98,10 @@ def run_sweep(fwd_config: ForwardSolverConfig, opt_configs, n_iter=None, seed=42
     `costs_newton` [B][n_newton+1] (the cost before the first round, then after every round); kkt and u are then those of
     the polished iterate.  0 leaves the result as it is without the polish.  `n_trust` > 0 does the same (after the Newton
     rounds, if both are asked for) with that many trust-region rounds from the radius `radius0` (Engine2D.pgd_trust), which
-    follow a direction of non-positive curvature instead of ending on it, and adds `trust` and `costs_trust` [B][n_trust+1]."""
+    follow a direction of non-positive curvature instead of ending on it, and adds `trust` and `costs_trust` [B][n_trust+1].
+    `sparsity`: a name of Engine2D.SPARSITY for the batch or one per member (None: every member "full", the calls of before);
+    kkt then counts a group-mode member's groups.  The Newton and trust-region rounds are those of the L1 functional: with a
+    member in a group mode n_newton > 0 or n_trust > 0 raises the engine's error."""
     opt_configs = list(opt_configs)
     B = len(opt_configs)
     if B < 1:
@@ -111,7 +117,7 @@ def run_sweep(fwd_config: ForwardSolverConfig, opt_configs, n_iter=None, seed=42
         if u0.ndim == 3:
             u0 = np.repeat(u0[None], B, axis=0)
     J0 = eng.pgd_init(phi0, np.repeat(phi_T[None], B, axis=0), t_hist, [make_opt(o) for o in opt_configs],
-                      ramp=(choice_q == 1), T=float(fwd_config.T), u0=u0)
+                      ramp=(choice_q == 1), T=float(fwd_config.T), u0=u0, sparsity=sparsity)
     n = int(max(int(o.max_iter) for o in opt_configs) if n_iter is None else n_iter)
     res = eng.pgd_iterate(n)
     newton = eng.pgd_newton(int(n_newton)) if int(n_newton) > 0 else None

@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("VCH_LIB") or os.path.join(HERE, "libvch_hip.so")     # VCH_LIB: A/B builds
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 SOURCES = ["vch_hip.hip"]
-DEPS = ["vch_hip.hip", "vch_comm.hip", "vch_engine2d.hip", "vch_kernels2d.h", "vch_gemm.h", "vch_fft.h", "vch_common.h", "vch_mem.h", "vch_engine1d.hip", "vch_kernels1d.h", "vch_pgd.h", "vch_newton.h",
+DEPS = ["vch_hip.hip", "vch_comm.hip", "vch_engine2d.hip", "vch_kernels2d.h", "vch_gemm.h", "vch_fft.h", "vch_common.h", "vch_mem.h", "vch_engine1d.hip", "vch_kernels1d.h", "vch_gp.h", "vch_pgd.h", "vch_newton.h",
         os.path.join(ROOT, "include", "vch.h")]
 
 
@@ -137,6 +137,10 @@ SIGNATURES = {
     "vch2d_pgd_init_v": (C.c_int, [_P, _D, _D, _D, C.c_int, C.c_double, _D, C.c_int, _D, _D,
                                    C.POINTER(OptParams), C.c_int, _D, _D, _D]),
     "vch2d_pgd_kkt": (C.c_int, [_P, C.c_int, C.c_double, C.POINTER(C.c_int64), _D]),
+    "vch2d_pgd_init_g": (C.c_int, [_P, _D, _D, _D, C.c_int, C.c_double, _D, C.c_int, _D, _D,
+                                   C.POINTER(OptParams), C.c_int, _D, _D, _I32, C.c_int, _D]),
+    "vch2d_grad_prox_g": (C.c_int, [_P, _D, _D, C.c_int, _D, _D, _D, _D, C.POINTER(OptParams), C.c_int, _D, _D]),
+    "vch2d_cost_g": (C.c_int, [_P, _D, _D, _D, _D, C.c_int, _D, _D, _D, C.POINTER(OptParams), C.c_int, _D]),
     "vch2d_second_order": (C.c_int, [_P, _D, C.c_int, _D, C.c_int, _D, _D, _D, _D, _D, C.POINTER(OptParams), C.c_int,
                                      C.c_int, C.c_double, _D, _D, _D, C.POINTER(Stats)]),
     "vch2d_mass_shifts": (C.c_int, [_P, _D]),

@@ -227,6 +227,14 @@ struct vch2d_ctx {
     std::vector<double> tab_host;
     bool pgd_r_valid;                     // r_hist holds an adjoint of the resident problem (a sweep has run since the init)
     unsigned long long *kkt_dev;          // vch2d_pgd_kkt: [B][3] counts, then [B][Mmax+1][3] per-level partials
+    // directional sparsity: the mode of every trajectory (empty = all VCH_SPARSITY_FULL) with its device
+    // copy; and, allocated as one group only when a trajectory is in a group mode (or a group seam is called): the time
+    // weights [Mmax+1], s per group [B][gp2_ss], the tile partials of the TIME prox [B][Mmax+1][nblk][4], the change
+    // partials [B][gp2_nsb][2] and the cost partials [B][gp2_nsb] of the pencil kernels with their host copies, alpha = 1
+    std::vector<int> modes;
+    int *mode_dev = nullptr;
+    double *gp_wt = nullptr, *gp_s = nullptr, *gp_tpart = nullptr, *gp_chg = nullptr, *gp_j4 = nullptr, *gp_one = nullptr;
+    std::vector<double> gp_chg_host, gp_j4_host;
     // vch2d_second_order (lazy): workgroup partials [B][Mmax+1][nblk][TAN_NSUM], level sums [B][Mmax+1][TAN_NSUM], the time
     // levels [Mmax+1] and the six scalars [B][6] on the device; rows of the control the resident state history was marched
     // under (0: none)
@@ -1984,11 +1992,94 @@ static int ensure_cost_bufs(vch2d_ctx *c) {
     return g.keep();
 }
 
+// ------------------------------------------------------------------------------------
+// directional sparsity: the mode table and what the group kernels need
+// ------------------------------------------------------------------------------------
+static inline int gp2_nsb(const vch2d_ctx *c) { return (int)((c->G.plane + 63) / 64); }      // workgroups of a pencil kernel
+static inline long gp2_ss(const vch2d_ctx *c) { return std::max<long>(c->Mmax + 1, (long)c->G.ns * c->G.nf); }
+static bool gp2_any(const vch2d_ctx *c, int mode) { return std::find(c->modes.begin(), c->modes.end(), mode) != c->modes.end(); }
+static bool gp2_group(const vch2d_ctx *c) { return gp2_any(c, VCH_SPARSITY_TIME) || gp2_any(c, VCH_SPARSITY_SPACE); }
+static int gp2_mode(const vch2d_ctx *c, int b) { return c->modes.empty() ? VCH_SPARSITY_FULL : c->modes[b]; }
+constexpr int GP2_RESIDENT = -1;          // cost_core: every trajectory by the resident problem's mode table
+
+// the buffers of the group kernels, all or none, beside the cost buffers whose layout the TIME prox shares
+static int gp2_ensure(vch2d_ctx *c) {
+    VCHCHK(ensure_cost_bufs(c));
+    if (!c->gp_s) {
+        const size_t B = c->B, nsb = gp2_nsb(c);
+        vch_group g(c->pool);
+        MEMCHK(c->pool.dev(&c->mode_dev, sizeof(int) * B));
+        MEMCHK(c->pool.dev(&c->gp_wt, sizeof(double) * (c->Mmax + 1)));
+        MEMCHK(c->pool.dev(&c->gp_s, sizeof(double) * B * gp2_ss(c)));
+        MEMCHK(c->pool.dev(&c->gp_tpart, sizeof(double) * B * (c->Mmax + 1) * c->nblk * 4));
+        MEMCHK(c->pool.dev(&c->gp_chg, sizeof(double) * B * nsb * 2));
+        MEMCHK(c->pool.dev(&c->gp_j4, sizeof(double) * B * nsb));
+        MEMCHK(c->pool.dev(&c->gp_one, sizeof(double) * B));
+        g.keep();
+        const std::vector<double> one(B, 1.0);
+        HIPCHK(hipMemcpyAsync(c->gp_one, one.data(), sizeof(double) * B, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));          // one is a local
+    }
+    c->gp_chg_host.resize((size_t)c->B * gp2_nsb(c) * 2);
+    c->gp_j4_host.resize((size_t)c->B * gp2_nsb(c));
+    return 0;
+}
+
+// the trapezoid weights of t_hist [rows] for the pencil norms
+static int gp2_time_weights(vch2d_ctx *c, const double *t_hist, int rows) {
+    const std::vector<double> wt = trapz_w(t_hist, rows);
+    HIPCHK(hipMemcpyAsync(c->gp_wt, wt.data(), sizeof(double) * rows, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));              // wt is a local
+    return 0;
+}
+
+// The group prox of the trajectories of `mode` (mode_dev NULL: all of them): u, r -> uout (or NULL: the sums alone), s in
+// gp_s.  TIME: three launches, the change partials in cost_part (the layout of k_grad_prox).  SPACE: one launch, the change
+// partials in gp_chg.  W_cost (TIME) and gp_wt (SPACE) hold the group's weights.
+static int gp2_launch(vch2d_ctx *c, int mode, const int *mode_dev, const double *u_dev, const double *r_dev, int rows,
+                      const double *alpha_dev, const double *opt_tab, double *uout) {
+    const Geom &G = c->G;
+    if (mode == VCH_SPARSITY_TIME) {
+        const dim3 g(c->nblk, rows, c->B);
+        LAUNCHC(PC_PROX, k_gp_time_part, g, dim3(NTH), G, G.tiles_f, u_dev, r_dev, hist_stride(c), alpha_dev, opt_tab, mode_dev,
+                (const double *)c->W_cost, c->gp_tpart);
+        LAUNCHC(PC_PROX, k_gp_time_solve, dim3(rows, c->B), dim3(GT_T), G, c->nblk, u_dev, r_dev, hist_stride(c), alpha_dev, opt_tab,
+                mode_dev, (const double *)c->W_cost, (const double *)c->gp_tpart, c->gp_s, gp2_ss(c));
+        LAUNCHC(PC_PROX, k_gp_time_apply, g, dim3(NTH), G, G.tiles_f, u_dev, r_dev, hist_stride(c), alpha_dev, opt_tab, mode_dev,
+                (const double *)c->gp_s, gp2_ss(c), uout, c->cost_part);
+    } else {
+        LAUNCHC(PC_PROX, k_gp_space, dim3(gp2_nsb(c), c->B), dim3(GT_T), G, rows, u_dev, r_dev, hist_stride(c), alpha_dev, opt_tab,
+                mode_dev, (const double *)c->gp_wt, uout, c->gp_s, gp2_ss(c), c->gp_chg);
+    }
+    return 0;
+}
+
+// sum_ij W_ij ||u[:, i, j]||_wt of the SPACE trajectories (mode_dev NULL: all) into gp_j4_host [B][gp2_nsb], one look
+static int gp2_pencil_cost(vch2d_ctx *c, const int *mode_dev, const double *u_dev, int rows) {
+    LAUNCHC(PC_COST, k_gp_pencil, dim3(gp2_nsb(c), c->B), dim3(GT_T), c->G, rows, u_dev, hist_stride(c), mode_dev,
+            (const double *)c->gp_wt, (const double *)c->W_cost, c->gp_j4);
+    HIPCHK(hipMemcpyAsync(c->gp_j4_host.data(), c->gp_j4, sizeof(double) * c->gp_j4_host.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// J4 / kappa_s of a group mode for one trajectory: s [levels][4] the level sums of k_cost (TIME: column 2 = sum W u^2), or
+// the pencil kernel's partials pen [gp2_nsb] (SPACE).  Host sums in index order.
+static double gp2_j4(int mode, const double *s, const double *t, int M, const double *pen, int nsb) {
+    double acc = 0;
+    if (mode == VCH_SPARSITY_TIME)
+        for (int n = 0; n < M; ++n) acc += (t[n + 1] - t[n]) * (std::sqrt(s[(n + 1) * 4 + 2]) + std::sqrt(s[n * 4 + 2])) / 2.0;
+    else
+        for (int j = 0; j < nsb; ++j) acc += pen[j];
+    return acc;
+}
+
 // J_out [B][5]; arrays on the device in history layout; phiQ_dev NULL + ramp => on-the-fly ramp target
 static int cost_core(vch2d_ctx *c, const double *phi_dev, const double *u_dev, const double *pq_dev, const double *pt_dev,
                      bool ramp, int M, const double *t_hist, const vch_opt_params *opts, double *J_out,
                      double *raw_out = nullptr /* [B][2] = {int int (phi - phi_Q)^2, int (phi_M - phi_T)^2} */,
-                     int n_opts = 1 /* 1: opts[0] weighs every trajectory; B: trajectory b takes opts[b] */) {
+                     int n_opts = 1 /* 1: opts[0] weighs every trajectory; B: trajectory b takes opts[b] */,
+                     int mode_sel = VCH_SPARSITY_FULL /* J4 of this mode for the whole batch; GP2_RESIDENT: by the mode table */) {
     const Geom &G = c->G;
     const int levels = M + 1, ntiles = c->nblk;
     VCHCHK(ensure_cost_bufs(c));
@@ -1999,6 +2090,10 @@ static int cost_core(vch2d_ctx *c, const double *phi_dev, const double *u_dev, c
     LAUNCH(k_cost_fin, dim3(c->B * levels), dim3(64), ntiles, (const double *)c->cost_part, c->cost_lvl);
     HIPCHK(hipMemcpyAsync(c->cost_lvl_host, c->cost_lvl, (size_t)c->B * levels * 4 * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    // the pencil norms of the SPACE trajectories (none: the launches and looks above are the call's)
+    const bool resident = mode_sel == GP2_RESIDENT;
+    if (u_dev && (resident ? gp2_any(c, VCH_SPARSITY_SPACE) : mode_sel == VCH_SPARSITY_SPACE))
+        VCHCHK(gp2_pencil_cost(c, resident ? (const int *)c->mode_dev : nullptr, u_dev, levels));
     for (int b = 0; b < c->B; ++b) {
         const double *s = c->cost_lvl_host + (size_t)b * levels * 4;
         double i1 = 0.0, i3 = 0.0, i4 = 0.0;
@@ -2008,6 +2103,9 @@ static int cost_core(vch2d_ctx *c, const double *phi_dev, const double *u_dev, c
             i3 += d * (s[(n + 1) * 4 + 2] + s[n * 4 + 2]) / 2.0;
             i4 += d * (s[(n + 1) * 4 + 3] + s[n * 4 + 3]) / 2.0;
         }
+        const int mode = resident ? gp2_mode(c, b) : mode_sel;
+        if (mode != VCH_SPARSITY_FULL)
+            i4 = u_dev ? gp2_j4(mode, s, t_hist, M, c->gp_j4_host.data() + (size_t)b * gp2_nsb(c), gp2_nsb(c)) : 0.0;
         double *J = J_out + 5 * b;
         const vch_opt_params *o = opts + (n_opts == 1 ? 0 : b);
         J[0] = (o->b1 / 2.0) * i1;
@@ -2044,11 +2142,13 @@ static int l2sq_core(vch2d_ctx *c, const double *arr, long stride, int levels, c
     return 0;
 }
 
-extern "C" int vch2d_cost(vch2d_ctx *c, const double *phi_hist, const double *u, const double *phi_Q, const double *phi_T,
-                          int M, const double *x, const double *y, const double *t_hist, const vch_opt_params *opt,
-                          double *J_out) {
-    CTXCHK(c);
-    ARGCHK(x && y && t_hist && opt && J_out && M >= 1 && M <= c->Mmax, "NULL argument or M out of range");
+// vch2d_cost and vch2d_cost_g: J4 of `mode` for the whole batch
+static int cost_seam(vch2d_ctx *c, const double *phi_hist, const double *u, const double *phi_Q, const double *phi_T, int M,
+                     const double *x, const double *y, const double *t_hist, const vch_opt_params *opt, int mode, double *J_out) {
+    if (mode == VCH_SPARSITY_SPACE) {
+        VCHCHK(gp2_ensure(c));
+        VCHCHK(gp2_time_weights(c, t_hist, M + 1));
+    }
     VCHCHK(set_cost_weights(c, x, y));
     if (phi_hist) {
         VCHCHK(ensure_hist(c, &c->phi_hist));
@@ -2081,7 +2181,24 @@ extern "C" int vch2d_cost(vch2d_ctx *c, const double *phi_hist, const double *u,
         VCHCHK(h2d(c, c->phiT, phi_T, c->B));
         pt = c->phiT;
     }
-    return cost_core(c, c->phi_hist, ud, pq, pt, false, M, t_hist, opt, J_out);
+    return cost_core(c, c->phi_hist, ud, pq, pt, false, M, t_hist, opt, J_out, nullptr, 1, mode);
+}
+
+extern "C" int vch2d_cost(vch2d_ctx *c, const double *phi_hist, const double *u, const double *phi_Q, const double *phi_T,
+                          int M, const double *x, const double *y, const double *t_hist, const vch_opt_params *opt,
+                          double *J_out) {
+    CTXCHK(c);
+    ARGCHK(x && y && t_hist && opt && J_out && M >= 1 && M <= c->Mmax, "NULL argument or M out of range");
+    return cost_seam(c, phi_hist, u, phi_Q, phi_T, M, x, y, t_hist, opt, VCH_SPARSITY_FULL, J_out);
+}
+
+extern "C" int vch2d_cost_g(vch2d_ctx *c, const double *phi_hist, const double *u, const double *phi_Q, const double *phi_T,
+                            int M, const double *x, const double *y, const double *t_hist, const vch_opt_params *opt,
+                            int sparsity, double *J_out) {
+    CTXCHK(c);
+    ARGCHK(x && y && t_hist && opt && J_out && M >= 1 && M <= c->Mmax, "NULL argument or M out of range");
+    ARGCHK(sparsity >= VCH_SPARSITY_FULL && sparsity <= VCH_SPARSITY_SPACE, "sparsity is none of VCH_SPARSITY_FULL, _TIME, _SPACE");
+    return cost_seam(c, phi_hist, u, phi_Q, phi_T, M, x, y, t_hist, opt, sparsity, J_out);
 }
 
 extern "C" int vch2d_free_energy(vch2d_ctx *c, const double *phi_hist, int rows, const double *w_hist, double hx, double hy,
@@ -2124,24 +2241,57 @@ extern "C" int vch2d_free_energy(vch2d_ctx *c, const double *phi_hist, int rows,
 }
 
 // u_out = prox(u - alpha (r + b3 u)), trajectory b with row b of the device table opt_tab; change_out [B][2] =
-// {sum (u+ - u)^2, sum u^2} or NULL
+// {sum (u+ - u)^2, sum u^2} or NULL.  mode_sel: the prox of this mode for the whole batch, or GP2_RESIDENT: every trajectory
+// by the resident problem's mode table, k_grad_prox once per run of consecutive FULL trajectories (pointer offsets) and each
+// group kernel once over the batch.  Without a group mode the launches, looks and bits are those of the one k_grad_prox
+// launch over the batch.  uout_dev NULL (group modes only): the change sums alone.
 static int grad_prox_core(vch2d_ctx *c, const double *u_dev, const double *r_dev, int rows, const double *alpha_host,
-                          const double *opt_tab, double *uout_dev, double *change_out) {
+                          const double *opt_tab, double *uout_dev, double *change_out, int mode_sel = VCH_SPARSITY_FULL) {
     HIPCHK(hipMemcpyAsync(c->alpha_dev, alpha_host, sizeof(double) * c->B, hipMemcpyHostToDevice, c->stream));
     VCHCHK(ensure_cost_bufs(c));
-    dim3 g(c->nblk, rows, c->B);
-    HIPCHK(hipMemsetAsync(c->cost_part, 0, (size_t)c->B * rows * c->nblk * 4 * 8, c->stream));
-    LAUNCHC(PC_PROX, k_grad_prox, g, dim3(NTH), c->G, c->G.tiles_f, u_dev, r_dev, hist_stride(c), (const double *)c->alpha_dev, opt_tab,
-           uout_dev, c->cost_part);
+    const int B = c->B;
+    const bool resident = mode_sel == GP2_RESIDENT && gp2_group(c);
+    const bool grouped = resident || (mode_sel != GP2_RESIDENT && mode_sel != VCH_SPARSITY_FULL);
+    HIPCHK(hipMemsetAsync(c->cost_part, 0, (size_t)B * rows * c->nblk * 4 * 8, c->stream));
+    if (!grouped) {
+        dim3 g(c->nblk, rows, B);
+        LAUNCHC(PC_PROX, k_grad_prox, g, dim3(NTH), c->G, c->G.tiles_f, u_dev, r_dev, hist_stride(c), (const double *)c->alpha_dev, opt_tab,
+               uout_dev, c->cost_part);
+    } else if (resident) {
+        const long hs = hist_stride(c);
+        for (int b0 = 0; b0 < B;) {
+            if (gp2_mode(c, b0) != VCH_SPARSITY_FULL) { ++b0; continue; }
+            int b1 = b0 + 1;
+            while (b1 < B && gp2_mode(c, b1) == VCH_SPARSITY_FULL) ++b1;
+            LAUNCHC(PC_PROX, k_grad_prox, dim3(c->nblk, rows, b1 - b0), dim3(NTH), c->G, c->G.tiles_f, u_dev + b0 * hs, r_dev + b0 * hs, hs,
+                    (const double *)c->alpha_dev + b0, opt_tab + (size_t)b0 * OPT_STRIDE, uout_dev + b0 * hs,
+                    c->cost_part + (size_t)b0 * rows * c->nblk * 4);
+            b0 = b1;
+        }
+        for (int mode : {VCH_SPARSITY_TIME, VCH_SPARSITY_SPACE})
+            if (gp2_any(c, mode))
+                VCHCHK(gp2_launch(c, mode, c->mode_dev, u_dev, r_dev, rows, c->alpha_dev, opt_tab, uout_dev));
+    } else {
+        VCHCHK(gp2_launch(c, mode_sel, nullptr, u_dev, r_dev, rows, c->alpha_dev, opt_tab, uout_dev));
+    }
     if (change_out) {
-        LAUNCH(k_cost_fin, dim3(c->B * rows), dim3(64), c->nblk, (const double *)c->cost_part, c->cost_lvl);
-        HIPCHK(hipMemcpyAsync(c->cost_lvl_host, c->cost_lvl, (size_t)c->B * rows * 4 * 8, hipMemcpyDeviceToHost, c->stream));
+        LAUNCH(k_cost_fin, dim3(B * rows), dim3(64), c->nblk, (const double *)c->cost_part, c->cost_lvl);
+        HIPCHK(hipMemcpyAsync(c->cost_lvl_host, c->cost_lvl, (size_t)B * rows * 4 * 8, hipMemcpyDeviceToHost, c->stream));
+        const bool space = resident ? gp2_any(c, VCH_SPARSITY_SPACE) : (grouped && mode_sel == VCH_SPARSITY_SPACE);
+        if (space)
+            HIPCHK(hipMemcpyAsync(c->gp_chg_host.data(), c->gp_chg, sizeof(double) * c->gp_chg_host.size(), hipMemcpyDeviceToHost,
+                                  c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
-        for (int b = 0; b < c->B; ++b) {
+        for (int b = 0; b < B; ++b) {
             double d = 0.0, n = 0.0;
-            for (int l = 0; l < rows; ++l) {
-                d += c->cost_lvl_host[((size_t)b * rows + l) * 4 + 0];
-                n += c->cost_lvl_host[((size_t)b * rows + l) * 4 + 1];
+            if (space && (resident ? gp2_mode(c, b) : mode_sel) == VCH_SPARSITY_SPACE) {
+                const double *q = c->gp_chg_host.data() + (size_t)b * gp2_nsb(c) * 2;      // the pencil kernel's workgroups, in index order
+                for (int j = 0; j < gp2_nsb(c); ++j) { d += q[2 * j]; n += q[2 * j + 1]; }
+            } else {
+                for (int l = 0; l < rows; ++l) {
+                    d += c->cost_lvl_host[((size_t)b * rows + l) * 4 + 0];
+                    n += c->cost_lvl_host[((size_t)b * rows + l) * 4 + 1];
+                }
             }
             change_out[2 * b] = d;
             change_out[2 * b + 1] = n;
@@ -2164,6 +2314,34 @@ extern "C" int vch2d_grad_prox(vch2d_ctx *c, const double *u, const double *r, i
     return d2h_hist(c, u_out, c->u_trial, rows);
 }
 
+extern "C" int vch2d_grad_prox_g(vch2d_ctx *c, const double *u, const double *r, int rows, const double *x, const double *y,
+                                 const double *t_hist, const double *alpha, const vch_opt_params *opt, int sparsity,
+                                 double *u_out, double *scale_out) {
+    CTXCHK(c);
+    ARGCHK(sparsity >= VCH_SPARSITY_FULL && sparsity <= VCH_SPARSITY_SPACE, "sparsity is none of VCH_SPARSITY_FULL, _TIME, _SPACE");
+    if (sparsity == VCH_SPARSITY_FULL) return vch2d_grad_prox(c, u, r, rows, alpha, opt, u_out);
+    ARGCHK(u && r && alpha && opt && u_out && rows >= 1 && rows <= c->Mmax + 1, "NULL argument or rows out of range");
+    ARGCHK(sparsity == VCH_SPARSITY_TIME ? (x && y) : (t_hist != nullptr), "NULL x, y (TIME) or t_hist (SPACE): the group's weights");
+    ARGCHK(opt->u_min <= 0.0 && opt->u_max >= 0.0, "a group mode needs a box with u_min <= 0 <= u_max");
+    ARGCHK(std::isfinite(opt->kappa_sparsity) && opt->kappa_sparsity >= 0, "kappa_sparsity must be finite and >= 0");
+    VCHCHK(ensure_hist(c, &c->u_hist));
+    VCHCHK(ensure_hist(c, &c->r_hist));
+    VCHCHK(ensure_hist(c, &c->u_trial));
+    VCHCHK(gp2_ensure(c));
+    VCHCHK(h2d_hist(c, c->u_hist, u, rows));
+    VCHCHK(h2d_hist(c, c->r_hist, r, rows));
+    VCHCHK(write_opt_tab(c, c->seam_tab, opt, 1));
+    if (sparsity == VCH_SPARSITY_TIME) VCHCHK(set_cost_weights(c, x, y));
+    else VCHCHK(gp2_time_weights(c, t_hist, rows));
+    VCHCHK(grad_prox_core(c, c->u_hist, c->r_hist, rows, alpha, c->seam_tab, c->u_trial, nullptr, sparsity));
+    if (scale_out) {
+        const size_t ng = sparsity == VCH_SPARSITY_TIME ? (size_t)rows : (size_t)c->G.ns * c->G.nf;
+        for (int b = 0; b < c->B; ++b)
+            HIPCHK(hipMemcpyAsync(scale_out + b * ng, c->gp_s + b * gp2_ss(c), sizeof(double) * ng, hipMemcpyDeviceToHost, c->stream));
+    }
+    return d2h_hist(c, u_out, c->u_trial, rows);
+}
+
 // ------------------------------------------------------------------------------------
 // device-resident PGD loop (G2:291-382)
 // ------------------------------------------------------------------------------------
@@ -2179,16 +2357,40 @@ static int copy_traj(vch2d_ctx *c, double *dst, const double *src, int b, int ro
     return 0;
 }
 
-extern "C" int vch2d_pgd_init_v(vch2d_ctx *c, const double *phi0, const double *phi_T, const double *phi_Q, int ramp, double T,
-                                const double *t_hist, int M, const double *x, const double *y, const vch_opt_params *opts,
-                                int n_opts, const double *u0, const double *alpha0, double *J0_out) {
-    CTXCHK(c);
-    ARGCHK(phi0 && phi_T && t_hist && x && y && opts && M >= 1 && M <= c->Mmax, "NULL argument or M out of range");
-    ARGCHK(n_opts == 1 || n_opts == c->B, "n_opts must be 1 or the context's batch");
+// vch2d_pgd_init_v and vch2d_pgd_init_g (fn: who the messages name).  sparsity NULL: every trajectory VCH_SPARSITY_FULL.
+static int pgd_init2(vch2d_ctx *c, const char *fn, const double *phi0, const double *phi_T, const double *phi_Q, int ramp, double T,
+                     const double *t_hist, int M, const double *x, const double *y, const vch_opt_params *opts, int n_opts,
+                     const double *u0, const double *alpha0, const int32_t *sparsity, int n_sparsity, double *J0_out) {
+    if (!(phi0 && phi_T && t_hist && x && y && opts && M >= 1 && M <= c->Mmax))
+        return vch_fail(VCH_ERR_ARG, "%s: NULL argument or M out of range", fn);
+    if (!(n_opts == 1 || n_opts == c->B)) return vch_fail(VCH_ERR_ARG, "%s: n_opts must be 1 or the context's batch", fn);
     // all of this before anything is enqueued or any resident state changes
     for (int b = 0; b < c->B; ++b)
         if (const char *bad = vch_pgd_check(opts, n_opts, alpha0, b))
-            return vch_fail(VCH_ERR_ARG, "vch2d_pgd_init_v: trajectory %d: %s", b, bad);
+            return vch_fail(VCH_ERR_ARG, "%s: trajectory %d: %s", fn, b, bad);
+    bool grouped = false;
+    if (sparsity) {
+        if (!(n_sparsity == 1 || n_sparsity == c->B)) return vch_fail(VCH_ERR_ARG, "%s: n_sparsity must be 1 or the context's batch", fn);
+        for (int b = 0; b < c->B; ++b) {
+            const int m = sparsity[n_sparsity == 1 ? 0 : b];
+            const vch_opt_params &o = vch_pgd_opt(opts, n_opts, b);
+            if (m < VCH_SPARSITY_FULL || m > VCH_SPARSITY_SPACE)
+                return vch_fail(VCH_ERR_ARG, "%s: trajectory %d: sparsity %d is none of VCH_SPARSITY_FULL, _TIME, _SPACE", fn, b, m);
+            if (m != VCH_SPARSITY_FULL && !(o.u_min <= 0.0 && o.u_max >= 0.0))
+                return vch_fail(VCH_ERR_ARG, "%s: trajectory %d: a group mode needs a box with u_min <= 0 <= u_max", fn, b);
+            grouped = grouped || m != VCH_SPARSITY_FULL;
+        }
+        for (int n = 0; n < M; ++n)
+            if (!(t_hist[n + 1] - t_hist[n] > 0)) return vch_fail(VCH_ERR_ARG, "%s: t_hist must be strictly increasing", fn);
+    }
+    if (grouped) VCHCHK(gp2_ensure(c));      // before any resident state changes: a refused allocation leaves the problem as it was
+    c->modes.assign(c->B, VCH_SPARSITY_FULL);
+    if (sparsity)
+        for (int b = 0; b < c->B; ++b) c->modes[b] = sparsity[n_sparsity == 1 ? 0 : b];
+    if (grouped) {
+        HIPCHK(hipMemcpyAsync(c->mode_dev, c->modes.data(), sizeof(int) * c->B, hipMemcpyHostToDevice, c->stream));
+        VCHCHK(gp2_time_weights(c, t_hist, M + 1));
+    }
     c->opts.resize(c->B);
     for (int b = 0; b < c->B; ++b) c->opts[b] = vch_pgd_opt(opts, n_opts, b);
     VCHCHK(write_opt_tab(c, c->opt_tab, c->opts.data(), c->B));
@@ -2197,7 +2399,7 @@ extern "C" int vch2d_pgd_init_v(vch2d_ctx *c, const double *phi0, const double *
     c->dt.resize(M);
     for (int n = 0; n < M; ++n) {
         c->dt[n] = t_hist[n + 1] - t_hist[n];
-        ARGCHK(c->dt[n] > 0, "t_hist must be strictly increasing");
+        if (!(c->dt[n] > 0)) return vch_fail(VCH_ERR_ARG, "%s: t_hist must be strictly increasing", fn);
     }
     c->xg.assign(x, x + c->prm.Nx + 1);
     c->yg.assign(y, y + c->prm.Ny + 1);
@@ -2241,7 +2443,7 @@ extern "C" int vch2d_pgd_init_v(vch2d_ctx *c, const double *phi0, const double *
     c->shift_res = true;
     c->J_host.assign(5 * c->B, 0.0);
     VCHCHK(cost_core(c, c->phi_hist, c->u_hist, (phi_Q || ramp) ? c->phiQ : nullptr, c->phiT, false, M, c->t_hist.data(),
-                     c->opts.data(), c->J_host.data(), nullptr, c->B));
+                     c->opts.data(), c->J_host.data(), nullptr, c->B, GP2_RESIDENT));
     // target norms of the error metrics (G2:348-361)
     c->pgd.denQ2.assign(c->B, 0.0);
     c->pgd.denT2.assign(c->B, 0.0);
@@ -2259,6 +2461,23 @@ extern "C" int vch2d_pgd_init_v(vch2d_ctx *c, const double *phi0, const double *
     c->pgd_ready = true;
     c->res_pgd = true;
     return 0;
+}
+
+extern "C" int vch2d_pgd_init_v(vch2d_ctx *c, const double *phi0, const double *phi_T, const double *phi_Q, int ramp, double T,
+                                const double *t_hist, int M, const double *x, const double *y, const vch_opt_params *opts,
+                                int n_opts, const double *u0, const double *alpha0, double *J0_out) {
+    CTXCHK(c);
+    return pgd_init2(c, "vch2d_pgd_init_v", phi0, phi_T, phi_Q, ramp, T, t_hist, M, x, y, opts, n_opts, u0, alpha0, nullptr, 0, J0_out);
+}
+
+extern "C" int vch2d_pgd_init_g(vch2d_ctx *c, const double *phi0, const double *phi_T, const double *phi_Q, int ramp, double T,
+                                const double *t_hist, int M, const double *x, const double *y, const vch_opt_params *opts,
+                                int n_opts, const double *u0, const double *alpha0, const int32_t *sparsity, int n_sparsity,
+                                double *J0_out) {
+    CTXCHK(c);
+    if (!sparsity) return vch_fail(VCH_ERR_ARG, "vch2d_pgd_init_g: NULL sparsity");
+    return pgd_init2(c, "vch2d_pgd_init_g", phi0, phi_T, phi_Q, ramp, T, t_hist, M, x, y, opts, n_opts, u0, alpha0, sparsity, n_sparsity,
+                     J0_out);
 }
 
 extern "C" int vch2d_pgd_init(vch2d_ctx *c, const double *phi0, const double *phi_T, const double *phi_Q, int ramp, double T,
@@ -2310,7 +2529,7 @@ extern "C" int vch2d_pgd_iterate(vch2d_ctx *c, int n_iters, double *cost_out, do
         for (int round = 0; round < R.rounds; ++round) {
             // round 0 = optimistic step with alpha_prev (G2:304-313); later rounds = backtracking trials (G2:128-146)
             HIPCHK(hipEventRecord(e0, c->stream));
-            VCHCHK(grad_prox_core(c, c->u_hist, c->r_hist, rows, st.alpha.data(), c->opt_tab, c->u_trial, chg.data()));
+            VCHCHK(grad_prox_core(c, c->u_hist, c->r_hist, rows, st.alpha.data(), c->opt_tab, c->u_trial, chg.data(), GP2_RESIDENT));
             HIPCHK(hipEventRecord(e1, c->stream));
             sec[1] += elapsed_s(c, e0, e1);
             HIPCHK(hipEventRecord(e0, c->stream));
@@ -2322,7 +2541,8 @@ extern "C" int vch2d_pgd_iterate(vch2d_ctx *c, int n_iters, double *cost_out, do
             HIPCHK(hipEventRecord(e1, c->stream));
             sec[round == 0 ? 2 : 4] += elapsed_s(c, e0, e1);
             HIPCHK(hipEventRecord(e0, c->stream));
-            VCHCHK(cost_core(c, c->phi_trial, c->u_trial, pq, c->phiT, false, M, c->t_hist.data(), c->opts.data(), Jt.data(), raw.data(), B));
+            VCHCHK(cost_core(c, c->phi_trial, c->u_trial, pq, c->phiT, false, M, c->t_hist.data(), c->opts.data(), Jt.data(), raw.data(), B,
+                             GP2_RESIDENT));
             HIPCHK(hipEventRecord(e1, c->stream));
             sec[round == 0 ? 3 : 4] += elapsed_s(c, e0, e1);
             bool pending = false;
@@ -2405,10 +2625,40 @@ extern "C" int vch2d_pgd_kkt(vch2d_ctx *c, int refresh, double tol, int64_t *cou
         for (int k = 0; k < 3; ++k) counts_out[4 * b + k] = (int64_t)cnt[3 * b + k];
         counts_out[4 * b + 3] = total;
     }
+    if (gp2_group(c)) {     // the group modes count groups in the group's norm (the node counts above stand for the FULL members)
+        std::vector<double> nu((size_t)B * rows), scratch(B);
+        if (gp2_any(c, VCH_SPARSITY_TIME)) {      // sum W u^2 and sum W r^2 of every level by the cost kernel, counted on the host
+            VCHCHK(l2sq_core(c, c->u_hist, hist_stride(c), rows, c->t_hist.data(), scratch.data()));
+            for (size_t k = 0; k < nu.size(); ++k) nu[k] = c->cost_lvl_host[4 * k];
+            VCHCHK(l2sq_core(c, c->r_hist, hist_stride(c), rows, c->t_hist.data(), scratch.data()));
+        }
+        if (gp2_any(c, VCH_SPARSITY_SPACE)) {
+            HIPCHK(hipMemsetAsync(c->kkt_dev, 0, sizeof(unsigned long long) * 3 * B, c->stream));
+            LAUNCH(k_gp_kkt_space, dim3(gp2_nsb(c), B), dim3(GT_T), c->G, rows, (const double *)c->u_hist, (const double *)c->r_hist,
+                   hist_stride(c), (const double *)c->opt_tab, (const int *)c->mode_dev, (const double *)c->gp_wt, tol, c->kkt_dev);
+            HIPCHK(hipMemcpyAsync(cnt.data(), c->kkt_dev, sizeof(unsigned long long) * 3 * B, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+        }
+        for (int b = 0; b < B; ++b) {
+            int64_t *q = counts_out + 4 * b;
+            if (gp2_mode(c, b) == VCH_SPARSITY_TIME) {
+                q[0] = q[1] = q[2] = 0;
+                for (int l = 0; l < rows; ++l) {
+                    const bool zero = std::sqrt(nu[(size_t)b * rows + l]) < tol;
+                    const bool small = std::sqrt(c->cost_lvl_host[((size_t)b * rows + l) * 4]) <= c->opts[b].kappa_sparsity;
+                    q[0] += zero; q[1] += small; q[2] += (zero == small);
+                }
+                q[3] = rows;
+            } else if (gp2_mode(c, b) == VCH_SPARSITY_SPACE) {
+                for (int k = 0; k < 3; ++k) q[k] = (int64_t)cnt[3 * b + k];
+                q[3] = (int64_t)c->G.ns * c->G.nf;
+            }
+        }
+    }
     if (stationarity_out) {
         // prox_1(u): the grad-prox step with alpha = 1 into the trial-control scratch, and that kernel's change sums
         std::vector<double> one(B, 1.0), chg(2 * (size_t)B);
-        VCHCHK(grad_prox_core(c, c->u_hist, c->r_hist, rows, one.data(), c->opt_tab, c->u_trial, chg.data()));
+        VCHCHK(grad_prox_core(c, c->u_hist, c->r_hist, rows, one.data(), c->opt_tab, c->u_trial, chg.data(), GP2_RESIDENT));
         for (int b = 0; b < B; ++b) stationarity_out[b] = std::sqrt(chg[2 * b]) / (std::sqrt(chg[2 * b + 1]) + 1e-9);
     }
     return 0;
@@ -3126,6 +3376,15 @@ extern "C" int vch2d_krylov_vector(vch2d_ctx *c, const double *coef, int m, doub
 // VCH_CG_CONVERGED and x = 0.
 // radius (host [B], or NULL): the trust region of vch2d_hess_cg_tr, k_ncg_fin_tr in place of k_ncg_fin and xnorm_out [B] =
 // ||x||_D by the recurrence (0 for P b = 0); NULL enqueues the launches, looks and copies of vch2d_hess_cg exactly.
+// The right-hand side a Newton-CG call builds itself and its free set are those of the L1 functional: about the resident
+// iterate of a problem that has a trajectory in a group mode they would belong to another cost.
+static int gp2_refuse(const vch2d_ctx *c, const char *fn, bool resident) {
+    if (resident && c->pgd_ready && gp2_group(c))
+        return vch_fail(VCH_ERR_STATE, "%s: the resident problem has a trajectory in a directional-sparsity mode; the sign term and "
+                        "the free set of this call are those of the L1 functional", fn);
+    return 0;
+}
+
 static int hess_cg_core(vch2d_ctx *c, const char *fn, bool empty_ok, const double *dt, int M, const double *t_hist, const double *x,
                         const double *y, const double *phi_Q, const double *phi_T, const vch_opt_params *opts, int n_opts,
                         double rtol, const uint8_t *mask, double tol, const double *rhs, int k, double cg_tol, int precond,
@@ -3133,6 +3392,7 @@ static int hess_cg_core(vch2d_ctx *c, const char *fn, bool empty_ok, const doubl
                         int32_t *status_out, int64_t *n_free_out, vch_stats *stats, const double *radius = nullptr,
                         double *xnorm_out = nullptr) {
     // everything below is checked before anything is enqueued, copied or allocated
+    VCHCHK(gp2_refuse(c, fn, !rhs && c->res_pgd));
     VCHCHK(tan_check_state(c, fn));
     TANCHK(opts, "NULL opts");
     TANCHK(resid_out && curv_out && pred_out && rnorm0_out && steps_out && status_out && n_free_out,
@@ -3296,6 +3556,7 @@ extern "C" int vch2d_newton_trial(vch2d_ctx *c, const double *s, double *u_out, 
     CTXCHK(c);
     ARGCHK(s && chg_out && counts_out, "NULL s, chg_out or counts_out");
     for (int b = 0; b < c->B; ++b) ARGCHK(std::isfinite(s[b]) && s[b] > 0, "s must be finite and > 0");
+    VCHCHK(gp2_refuse(c, "vch2d_newton_trial", true));
     if (!c->ncg_valid || !c->kr_Q || !c->u_trial)
         return vch_fail(VCH_ERR_STATE, "vch2d_newton_trial: no resident vectors (call vch2d_hess_cg first)");
     std::vector<double> sums(4 * (size_t)c->B);
@@ -3376,6 +3637,7 @@ extern "C" int vch2d_pgd_newton(vch2d_ctx *c, int n_rounds, int k, double cg_tol
     CTXCHK(c);
     // everything below is checked before anything is enqueued, copied or allocated
     if (!c->pgd_ready) return vch_fail(VCH_ERR_STATE, "vch2d_pgd_newton: call vch2d_pgd_init first");
+    VCHCHK(gp2_refuse(c, "vch2d_pgd_newton", true));
     if (!c->res_pgd || !c->shift_res || c->M_res < 1)
         return vch_fail(VCH_ERR_STATE, "vch2d_pgd_newton: the resident state history is no longer the PGD iterate's (call vch2d_pgd_init again)");
     const char *fn = "vch2d_pgd_newton";
@@ -3408,6 +3670,7 @@ extern "C" int vch2d_pgd_trust(vch2d_ctx *c, int n_rounds, int k, double cg_tol,
     CTXCHK(c);
     // everything below is checked before anything is enqueued, copied or allocated
     if (!c->pgd_ready) return vch_fail(VCH_ERR_STATE, "vch2d_pgd_trust: call vch2d_pgd_init first");
+    VCHCHK(gp2_refuse(c, "vch2d_pgd_trust", true));
     if (!c->res_pgd || !c->shift_res || c->M_res < 1)
         return vch_fail(VCH_ERR_STATE, "vch2d_pgd_trust: the resident state history is no longer the PGD iterate's (call vch2d_pgd_init again)");
     const char *fn = "vch2d_pgd_trust";

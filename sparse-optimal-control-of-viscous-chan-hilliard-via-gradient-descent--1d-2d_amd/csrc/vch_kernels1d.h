@@ -19,6 +19,7 @@
 // the implicit levels are back-substituted.  Any N+1 works (missing neighbours = zero blocks).
 #pragma once
 #include "vch_common.h"
+#include "vch_gp.h"
 
 #ifndef VCH_T1
 #define VCH_T1 512
@@ -978,13 +979,7 @@ __global__ __launch_bounds__(T1) void k1d_kkt(int n, int rows, const double *__r
 // u+ = clip(s v) with s the root of h(s) = ||clip(s v)|| (1 - s) - lam s, which is s0 = 1 - lam / ||v|| where clip(s0 v) = s0 v.
 // No atomics; every sum has one fixed order, so a trajectory's bits do not depend on the batch it runs in.
 // ---------------------------------------------------------------------------------
-constexpr int GP_FULL = 0, GP_TIME = 1, GP_SPACE = 2;      // VCH_SPARSITY_* of vch.h
 constexpr int GP_NV = (4096 + 1 + T1 - 1) / T1;            // values of a row per thread at the largest N
-// A cap, not the usual end: the bracket ends the iteration after at most 54 steps on 32 000 groups of the regimes of
-// tests/test_gpu_dirsparse_edges_1d.py (a CPU port of gp_step; |c / lam - 1| >= 1e-9).  A group at the threshold itself
-// (lam = c (1 - 2^-52) under a one-sided box, root at s ~ 1e-16) can run into the cap, about one group in 300 of that kind;
-// the s it then holds is within 6e-16 of the bisection's.
-constexpr int GP_MAXIT = 100;
 constexpr int GC_W = 16, GC_T = 64 * GC_W;                 // the column kernels: 64 columns across the lanes, rows over GC_W waves
 // values per thread the rows kernel is instantiated with: the smallest of 1, 2, 4, GP_NV that holds a row of n nodes (a short
 // row in a kernel built for the longest would leave most registers, and with them most of the CU, idle)
@@ -993,32 +988,7 @@ inline int gp_rows_nv(int n) {
     return nv <= 1 ? 1 : (nv <= 2 ? 2 : (nv <= 4 && 4 < GP_NV ? 4 : GP_NV));
 }
 
-// the gradient step, with its two roundings written out: every pass of a kernel recomputes the same bits
-__device__ __forceinline__ double gp_v(double uu, double rr, double al, double b3) { return fma(-al, fma(b3, uu, rr), uu); }
-__device__ __forceinline__ double gp_cone(double v, double umin, double umax) {
-    return (umax == 0.0 && v > 0.0) || (umin == 0.0 && v < 0.0) ? 0.0 : v;
-}
-__device__ __forceinline__ double gp_out(double s, double v, double umin, double umax) {
-    return s == 0.0 ? 0.0 : fmin(fmax(s * v, umin), umax);
-}
-// One step of the safeguarded iteration at s, where Q = ||clip(s v)||^2 and A = the sum of w v^2 over the nodes the box does
-// not hold (d/ds ||clip(s v)|| = A s / ||clip(s v)||).  The bracket keeps h(lo) > 0 >= h(hi).  The candidate is Newton's,
-// doubled while Newton closes in from one side (so that the other end of the bracket follows), else the midpoint.
-// true: h vanishes or lo, hi are adjacent doubles; s is the answer.
-__device__ __forceinline__ bool gp_step(double Q, double A, double lam, double &s, double &lo, double &hi) {
-    const double rho = sqrt(Q);
-    const double h = rho * (1.0 - s) - lam * s;
-    if (h == 0.0) return true;
-    if (h > 0.0) lo = s; else hi = s;
-    const double dh = (rho > 0.0 ? A * s / rho : 0.0) * (1.0 - s) - rho - lam;
-    const double step = -h / dh;
-    double sn = fabs(step) < 0.25 * (hi - lo) ? s + 2.0 * step : s + step;
-    if (!(sn > lo && sn < hi)) sn = s + step;
-    if (!(sn > lo && sn < hi)) sn = lo + 0.5 * (hi - lo);
-    if (!(sn > lo && sn < hi)) return true;
-    s = sn;
-    return false;
-}
+// gp_v, gp_cone, gp_out and gp_step, the prox of one group whatever its norm, are in vch_gp.h (shared with the 2D kernels)
 
 // TIME: one workgroup per (row, trajectory), the row's v, weights and u in registers (NV each, fully unrolled; NV * T1 >= n,
 // gp_rows_nv): one read of u and r, one write of u+.  The sums add the nodes in index order whatever NV is.  mode (or NULL: every trajectory): [B], a trajectory of another mode is left alone.

@@ -13,6 +13,7 @@
 // fixed order, so results are deterministic run to run.
 #pragma once
 #include "vch_common.h"
+#include "vch_gp.h"
 
 struct TrajState {
     // Newton iteration (F2:323-427)
@@ -1262,6 +1263,314 @@ __global__ void k_kkt_fin(int levels, const unsigned long long *__restrict__ par
         if (a[k]) atomicAdd(&tot[k], a[k]);
     __syncthreads();
     if (threadIdx.x < 3) counts[3 * b + threadIdx.x] = tot[threadIdx.x];
+}
+
+// ---------------------------------------------------------------------------------
+// Directional sparsity: the prox of kappa_s * sum over groups of ||u_g|| under the box, a group being a level
+// of the control (VCH_SPARSITY_TIME, ||z||^2 = sum_ij W_ij z_ij^2 with the plane W of the cost) or the pencil of one node
+// through the levels (VCH_SPARSITY_SPACE, ||z||^2 = sum_k wt_k z_k^2).  gp_v, gp_cone, gp_out and gp_step (vch_gp.h) are the
+// 1D kernels' own.  No floating-point atomics; every sum is taken in one order fixed by the geometry alone, so a member of a
+// mixed batch has the bits of its single run; every loop has a cap; no workgroup waits on another.  `mode` [B] (or NULL:
+// every trajectory): a workgroup of a trajectory in another mode returns at once.  Pad columns of the pitched rows and rows
+// beyond ns take no part.
+// ---------------------------------------------------------------------------------
+constexpr int GT_W = 16, GT_T = 64 * GT_W;       // the plane solver and the pencil kernels: 16 wavefronts
+
+// TIME, stage 1.  Per (tile, level, trajectory) the partials {sum W cone(v)^2, sum W v^2, max(v, 0), min(v, 0)} at
+// part[b][level][tile][4]; s0 v is monotone in v, so the extremes decide whether the box is inactive at s0.
+// grid = (tiles, levels, B)
+__global__ __launch_bounds__(NTH) void k_gp_time_part(Geom G, int tiles_f, const double *__restrict__ u,
+                                                      const double *__restrict__ r, long hist_stride,
+                                                      const double *__restrict__ alpha, const double *__restrict__ opt_tab,
+                                                      const int *__restrict__ mode, const double *__restrict__ W,
+                                                      double *__restrict__ part) {
+    const int b = blockIdx.z, lvl = blockIdx.y;
+    if (mode && mode[b] != GP_TIME) return;
+    const double *ot = opt_tab + b * OPT_STRIDE;
+    const double b3 = ot[OPT_B3], umin = ot[OPT_UMIN], umax = ot[OPT_UMAX];
+    const int tf = blockIdx.x % tiles_f, ts = blockIdx.x / tiles_f;
+    const int c0 = tf * TX, r0 = ts * TY;
+    const int lx = threadIdx.x & 63, ly0 = threadIdx.x >> 6;
+    __shared__ double sred[NPART * 4];
+    const double al = alpha[b];
+    const long lb = b * hist_stride + (long)lvl * G.plane;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int k = 0; k < TY / 4; ++k) {
+        const int rr = r0 + ly0 + 4 * k, c = c0 + lx;
+        if (rr < G.ns && c < G.nf) {
+            const long o = (long)rr * G.pitch + c;
+            const double v = gp_v(u[lb + o], r[lb + o], al, b3), w = W[o];
+            const double cv = gp_cone(v, umin, umax);
+            acc[0] += w * (cv * cv);
+            acc[1] += w * (v * v);
+            acc[2] = fmax(acc[2], v);
+            acc[3] = fmin(acc[3], v);
+        }
+    }
+    const int op[4] = {0, 0, 2, 1};
+    block_reduce_store<4>(acc, op, sred, part + (((long)b * gridDim.y + lvl) * gridDim.x + blockIdx.x) * 4);
+}
+
+// TIME, stage 2.  One workgroup per (level, trajectory): thread 0 adds the tile partials in index order and decides: zero
+// (s = 0), the closed form s0 = 1 - lam / ||v|| where the box is inactive at s0, or box-active.  A box-active plane alone
+// iterates gp_step, each step one pass over the plane (row = wavefront + 16 j, node = lane + 64 i: the same order whatever
+// the batch) and one reduction in wavefront order; thread 0 updates s and broadcasts it through LDS, so that the control
+// flow is uniform.  s at sout[b * ss + level].
+// grid = (levels, B)
+__global__ __launch_bounds__(GT_T) void k_gp_time_solve(Geom G, int ntiles, const double *__restrict__ u,
+                                                        const double *__restrict__ r, long hist_stride,
+                                                        const double *__restrict__ alpha, const double *__restrict__ opt_tab,
+                                                        const int *__restrict__ mode, const double *__restrict__ W,
+                                                        const double *__restrict__ part, double *__restrict__ sout, long ss) {
+    __shared__ double sk[2][GT_W];
+    __shared__ double bc[2];
+    const int lvl = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (mode && mode[b] != GP_TIME) return;
+    const double *ot = opt_tab + b * OPT_STRIDE;
+    const double b3 = ot[OPT_B3], ks = ot[OPT_KS], umin = ot[OPT_UMIN], umax = ot[OPT_UMAX];
+    const double al = alpha[b], lam = al * ks;
+    if (tid == 0) {
+        const double *p = part + ((long)b * gridDim.x + lvl) * ntiles * 4;
+        double cc = 0.0, vv = 0.0, mx = 0.0, mn = 0.0;
+        for (int t = 0; t < ntiles; ++t) {
+            cc += p[4 * t]; vv += p[4 * t + 1];
+            mx = fmax(mx, p[4 * t + 2]); mn = fmin(mn, p[4 * t + 3]);
+        }
+        double s = 0.0, act = 0.0;
+        if (sqrt(cc) > lam) {
+            s = 1.0 - lam / sqrt(vv);
+            act = (s * mx > umax || s * mn < umin) ? 1.0 : 0.0;
+        }
+        bc[0] = s; bc[1] = act;
+        if (act == 0.0) sout[b * ss + lvl] = s;
+    }
+    __syncthreads();
+    double s = bc[0];
+    if (bc[1] == 0.0) return;                 // the same in every thread
+    const long lb = b * hist_stride + (long)lvl * G.plane;
+    double lo = 0.0, hi = 1.0;                // thread 0's
+    for (int it = 0; it < GP_MAXIT; ++it) {
+        double q = 0.0, a = 0.0;
+        for (int rr = wv; rr < G.ns; rr += GT_W)
+            for (int c = lane; c < G.nf; c += 64) {
+                const long o = (long)rr * G.pitch + c;
+                const double v = gp_v(u[lb + o], r[lb + o], al, b3), w = W[o];
+                const double sv = s * v, cl = fmin(fmax(sv, umin), umax);
+                q += w * (cl * cl);
+                a += cl == sv ? w * (v * v) : 0.0;
+            }
+        q = wave_sum(q); a = wave_sum(a);
+        if (lane == 0) { sk[0][wv] = q; sk[1][wv] = a; }
+        __syncthreads();
+        if (tid == 0) {
+            q = sk[0][0]; a = sk[1][0];
+            for (int w = 1; w < GT_W; ++w) { q += sk[0][w]; a += sk[1][w]; }
+            const bool done = gp_step(q, a, lam, s, lo, hi);
+            bc[0] = s; bc[1] = done ? 1.0 : 0.0;
+        }
+        __syncthreads();                      // the next write of bc comes after the next step's barrier, which follows these reads
+        s = bc[0];
+        if (bc[1] != 0.0) break;
+    }
+    if (tid == 0) sout[b * ss + lvl] = s;
+}
+
+// TIME, stage 3.  u+ = clip(s v) of every node with its level's s into uout (or NULL: the sums alone), and the change
+// partials {sum (u+ - u)^2, sum u^2} in the layout of k_grad_prox, which k_cost_fin folds.
+// grid = (tiles, levels, B)
+__global__ __launch_bounds__(NTH) void k_gp_time_apply(Geom G, int tiles_f, const double *__restrict__ u,
+                                                       const double *__restrict__ r, long hist_stride,
+                                                       const double *__restrict__ alpha, const double *__restrict__ opt_tab,
+                                                       const int *__restrict__ mode, const double *__restrict__ sv, long ss,
+                                                       double *__restrict__ uout, double *__restrict__ part) {
+    const int b = blockIdx.z, lvl = blockIdx.y;
+    if (mode && mode[b] != GP_TIME) return;
+    const double *ot = opt_tab + b * OPT_STRIDE;
+    const double b3 = ot[OPT_B3], umin = ot[OPT_UMIN], umax = ot[OPT_UMAX];
+    const int tf = blockIdx.x % tiles_f, ts = blockIdx.x / tiles_f;
+    const int c0 = tf * TX, r0 = ts * TY;
+    const int lx = threadIdx.x & 63, ly0 = threadIdx.x >> 6;
+    __shared__ double sred[NPART * 4];
+    const double al = alpha[b], s = sv[b * ss + lvl];
+    const long lb = b * hist_stride + (long)lvl * G.plane;
+    double acc[2] = {0.0, 0.0};
+    for (int k = 0; k < TY / 4; ++k) {
+        const int rr = r0 + ly0 + 4 * k, c = c0 + lx;
+        if (rr < G.ns && c < G.nf) {
+            const long o = lb + (long)rr * G.pitch + c;
+            const double uu = u[o];
+            const double un = gp_out(s, gp_v(uu, r[o], al, b3), umin, umax);
+            if (uout) uout[o] = un;
+            acc[0] += (un - uu) * (un - uu);
+            acc[1] += uu * uu;
+        }
+    }
+    if (part) {
+        const int op[2] = {0, 0};
+        block_reduce_store<2>(acc, op, sred, part + (((long)b * gridDim.y + lvl) * gridDim.x + blockIdx.x) * 4);
+    }
+}
+
+// SPACE: one workgroup of GT_W wavefronts per (64 consecutive doubles of the pitched plane, trajectory); lane = node, so
+// every level read is one coalesced 512-byte segment; wavefront w takes levels w, w + GT_W, ... and the wavefronts' partial
+// sums are added in wavefront order through LDS.  Pass one: ||cone(v)||^2, ||v||^2 and the extremes of v.  Pencils the box
+// holds iterate together (__syncthreads_or ends the loop), each step re-reading the pencil; the last pass writes u+ (uout
+// or NULL: the sums alone).  chg (or NULL): [B][gridDim.x][2], this workgroup's share of sum (u+ - u)^2 and sum u^2; sout
+// (or NULL): s at [b * ss + node], node = row * nf + column.
+// grid = (ceil(plane / 64), B)
+__global__ __launch_bounds__(GT_T) void k_gp_space(Geom G, int levels, const double *__restrict__ u, const double *__restrict__ r,
+                                                   long hist_stride, const double *__restrict__ alpha,
+                                                   const double *__restrict__ opt_tab, const int *__restrict__ mode,
+                                                   const double *__restrict__ wt, double *__restrict__ uout,
+                                                   double *__restrict__ sout, long ss, double *__restrict__ chg) {
+    __shared__ double part[4][GT_W][64];
+    const int b = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (mode && mode[b] != GP_SPACE) return;
+    const long e = (long)blockIdx.x * 64 + lane;
+    const int row = (int)(e / G.pitch), col = (int)(e - (long)row * G.pitch);
+    const bool ok = e < G.plane && col < G.nf;
+    const double *ot = opt_tab + b * OPT_STRIDE;
+    const double b3 = ot[OPT_B3], ks = ot[OPT_KS], umin = ot[OPT_UMIN], umax = ot[OPT_UMAX];
+    const long o = b * hist_stride + e;
+    const double al = alpha[b], lam = al * ks;
+    double cc = 0.0, vv = 0.0, mx = 0.0, mn = 0.0;
+    if (ok) {
+#pragma unroll 4
+        for (int k = wv; k < levels; k += GT_W) {
+            const double v = gp_v(u[o + k * G.plane], r[o + k * G.plane], al, b3), w = wt[k];
+            const double cv = gp_cone(v, umin, umax);
+            cc += w * (cv * cv);
+            vv += w * (v * v);
+            mx = fmax(mx, v);
+            mn = fmin(mn, v);
+        }
+    }
+    part[0][wv][lane] = cc; part[1][wv][lane] = vv; part[2][wv][lane] = mx; part[3][wv][lane] = mn;
+    __syncthreads();
+    cc = part[0][0][lane]; vv = part[1][0][lane]; mx = part[2][0][lane]; mn = part[3][0][lane];
+    for (int w = 1; w < GT_W; ++w) {
+        cc += part[0][w][lane]; vv += part[1][w][lane];
+        mx = fmax(mx, part[2][w][lane]); mn = fmin(mn, part[3][w][lane]);
+    }
+    // from here on the wavefronts hold the same numbers for a pencil and take the same steps
+    double s = 0.0, lo = 0.0, hi = 1.0;
+    bool active = false;
+    if (ok && sqrt(cc) > lam) {
+        s = 1.0 - lam / sqrt(vv);
+        active = s * mx > umax || s * mn < umin;
+    }
+    for (int it = 0; it < GP_MAXIT; ++it) {
+        if (!__syncthreads_or(active)) break;         // also the barrier between two uses of part
+        double q = 0.0, a = 0.0;
+        if (active) {
+#pragma unroll 4
+            for (int k = wv; k < levels; k += GT_W) {
+                const double v = gp_v(u[o + k * G.plane], r[o + k * G.plane], al, b3), w = wt[k];
+                const double sv = s * v, cl = fmin(fmax(sv, umin), umax);
+                q += w * (cl * cl);
+                a += cl == sv ? w * (v * v) : 0.0;
+            }
+        }
+        part[0][wv][lane] = q; part[1][wv][lane] = a;
+        __syncthreads();
+        if (active) {
+            q = part[0][0][lane]; a = part[1][0][lane];
+            for (int w = 1; w < GT_W; ++w) { q += part[0][w][lane]; a += part[1][w][lane]; }
+            active = !gp_step(q, a, lam, s, lo, hi);
+        }
+    }
+    double d2 = 0.0, n2 = 0.0;
+    if (ok) {
+#pragma unroll 4
+        for (int k = wv; k < levels; k += GT_W) {
+            const double uu = u[o + k * G.plane];
+            const double un = gp_out(s, gp_v(uu, r[o + k * G.plane], al, b3), umin, umax);
+            if (uout) uout[o + k * G.plane] = un;
+            d2 += (un - uu) * (un - uu);
+            n2 += uu * uu;
+        }
+    }
+    if (ok && wv == 0 && sout) sout[b * ss + (long)row * G.nf + col] = s;
+    if (!chg) return;
+    d2 = wave_sum(d2); n2 = wave_sum(n2);
+    __syncthreads();
+    if (lane == 0) { part[0][wv][0] = d2; part[1][wv][0] = n2; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        d2 = part[0][0][0]; n2 = part[1][0][0];
+        for (int w = 1; w < GT_W; ++w) { d2 += part[0][w][0]; n2 += part[1][w][0]; }
+        double *q = chg + ((long)b * gridDim.x + blockIdx.x) * 2;
+        q[0] = d2; q[1] = n2;
+    }
+}
+
+// The pencil norms of the SPACE cost, in the order of the kernel above: out [B][gridDim.x] = this workgroup's share of
+// sum_ij W_ij sqrt(sum_k wt_k u_kij^2), its 64 nodes added by the wavefront's fixed tree; the host adds the workgroups in
+// index order.
+// grid = (ceil(plane / 64), B)
+__global__ __launch_bounds__(GT_T) void k_gp_pencil(Geom G, int levels, const double *__restrict__ u, long hist_stride,
+                                                    const int *__restrict__ mode, const double *__restrict__ wt,
+                                                    const double *__restrict__ W, double *__restrict__ out) {
+    __shared__ double part[GT_W][64];
+    const int b = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (mode && mode[b] != GP_SPACE) return;
+    const long e = (long)blockIdx.x * 64 + lane;
+    const bool ok = e < G.plane && (int)(e % G.pitch) < G.nf;
+    double a = 0.0;
+    if (ok) {
+#pragma unroll 4
+        for (int k = wv; k < levels; k += GT_W) {
+            const double uu = u[b * hist_stride + k * G.plane + e];
+            a += wt[k] * (uu * uu);
+        }
+    }
+    part[wv][lane] = a;
+    __syncthreads();
+    if (wv == 0) {
+        a = part[0][lane];
+        for (int w = 1; w < GT_W; ++w) a += part[w][lane];
+        a = wave_sum(ok ? W[e] * sqrt(a) : 0.0);
+        if (lane == 0) out[(long)b * gridDim.x + blockIdx.x] = a;
+    }
+}
+
+// The KKT statistic by pencils for the SPACE trajectories (the others are left to k_kkt_count and to the level sums):
+// cnt [B][3] += {#pencils ||u_g|| < tol, #pencils ||r_g|| <= kappa_s, #agree} in the pencil's norm, by ballot + popcount and
+// three vector integer atomics per workgroup (integer sums do not depend on the order).  The caller zeroes cnt.
+// grid = (ceil(plane / 64), B)
+__global__ __launch_bounds__(GT_T) void k_gp_kkt_space(Geom G, int levels, const double *__restrict__ u,
+                                                       const double *__restrict__ r, long hist_stride,
+                                                       const double *__restrict__ opt_tab, const int *__restrict__ mode,
+                                                       const double *__restrict__ wt, double tol,
+                                                       unsigned long long *__restrict__ cnt) {
+    __shared__ double part[2][GT_W][64];
+    const int b = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (mode[b] != GP_SPACE) return;
+    const long e = (long)blockIdx.x * 64 + lane;
+    const bool ok = e < G.plane && (int)(e % G.pitch) < G.nf;
+    const double ks = opt_tab[b * OPT_STRIDE + OPT_KS];
+    double a0 = 0.0, a1 = 0.0;
+    if (ok) {
+#pragma unroll 4
+        for (int k = wv; k < levels; k += GT_W) {
+            const long o = b * hist_stride + k * G.plane + e;
+            const double uu = u[o], rr = r[o], w = wt[k];
+            a0 += w * (uu * uu);
+            a1 += w * (rr * rr);
+        }
+    }
+    part[0][wv][lane] = a0; part[1][wv][lane] = a1;
+    __syncthreads();
+    if (wv == 0) {
+        a0 = part[0][0][lane]; a1 = part[1][0][lane];
+        for (int w = 1; w < GT_W; ++w) { a0 += part[0][w][lane]; a1 += part[1][w][lane]; }
+        const bool zero = ok && sqrt(a0) < tol, small = ok && sqrt(a1) <= ks;
+        const unsigned nz = __popcll(__ballot(zero)), nsm = __popcll(__ballot(small)), nm = __popcll(__ballot(ok && zero == small));
+        if (lane < 3) {
+            const unsigned v = lane == 0 ? nz : (lane == 1 ? nsm : nm);
+            if (v) atomicAdd(cnt + 3 * b + lane, (unsigned long long)v);
+        }
+    }
 }
 
 // =================================================================================

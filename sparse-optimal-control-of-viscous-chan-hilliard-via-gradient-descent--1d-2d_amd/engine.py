@@ -231,7 +231,19 @@ class Engine2D:
                                       _dp(pt), _dp(outs["p"]), _dp(outs["q"]), _dp(outs["r"]), C.byref(st)))
         return tuple(None if outs[k] is None else self._sq(outs[k]) for k in ("p", "q", "r")) + (st.as_dict(),)
 
-    def cost(self, phi_hist, u, phi_Q, phi_T, t_hist, opt, x=None, y=None):
+    # the sparsity functional: index = VCH_SPARSITY_* of include/vch.h
+    SPARSITY = ("full", "time", "space")
+
+    @classmethod
+    def _mode(cls, sparsity):
+        if sparsity not in cls.SPARSITY:
+            raise ValueError(f"sparsity must be one of {cls.SPARSITY}, got {sparsity!r}")
+        return cls.SPARSITY.index(sparsity)
+
+    def cost(self, phi_hist, u, phi_Q, phi_T, t_hist, opt, x=None, y=None, sparsity="full"):
+        """J (B, 5) = {J1, J2, J3, J4, J}.  `sparsity`: J4 = kappa_s int int |u| ("full"), kappa_s int ||u(., t)||_L2(Omega) dt
+        ("time") or kappa_s int_Omega ||u(x, .)||_L2(0,T) dx ("space")."""
+        mode = self._mode(sparsity)
         t_hist = np.ascontiguousarray(t_hist, dtype=np.float64)
         M = int(t_hist.size) - 1
         ph = None if phi_hist is None else self._hist(phi_hist, M + 1, "phi_hist")
@@ -244,25 +256,53 @@ class Engine2D:
             raise ValueError("x, y must have Nx+1, Ny+1 entries")
         J = np.empty((self.B, 5))
         o = opt if isinstance(opt, OptParams) else make_opt(opt)
-        check(self.lib.vch2d_cost(self.ctx, _dp(ph), _dp(uu), _dp(pq), _dp(pt), M, _dp(x), _dp(y), _dp(t_hist),
-                                  C.byref(o), _dp(J)))
+        if mode == 0:
+            check(self.lib.vch2d_cost(self.ctx, _dp(ph), _dp(uu), _dp(pq), _dp(pt), M, _dp(x), _dp(y), _dp(t_hist),
+                                      C.byref(o), _dp(J)))
+        else:
+            check(self.lib.vch2d_cost_g(self.ctx, _dp(ph), _dp(uu), _dp(pq), _dp(pt), M, _dp(x), _dp(y), _dp(t_hist),
+                                        C.byref(o), mode, _dp(J)))
         return J[0] if self.B == 1 else J
 
-    def grad_prox(self, u, r, alpha, opt):
+    def grad_prox(self, u, r, alpha, opt, sparsity="full", x=None, y=None, t_hist=None, return_scale=False):
+        """prox of the sparsity term at u - alpha (r + b3 u) under the box of `opt`.  `sparsity` "time" / "space": the prox
+        of the group norm over the levels (weights: product trapezoid in `x`, `y`, default the engine's grid) or the pencils
+        u[:, i, j] (weights: trapezoid in `t_hist`, required) of the control; the box must contain 0.  return_scale=True:
+        (u+, s) with s the factor of every group, (B, rows) or (B, Nx+1, Ny+1): u+ = clip(s v), 0 for a group that vanishes."""
+        mode = self._mode(sparsity)
         u = self._hist(u, 0, "u")
         r = self._hist(r, u.shape[1], "r")
+        rows = int(u.shape[1])
         al = np.ascontiguousarray(np.broadcast_to(np.asarray(alpha, dtype=np.float64), (self.B,)))
         out = np.empty_like(u)
         o = opt if isinstance(opt, OptParams) else make_opt(opt)
-        check(self.lib.vch2d_grad_prox(self.ctx, _dp(u), _dp(r), int(u.shape[1]), _dp(al), C.byref(o), _dp(out)))
-        return self._sq(out)
+        if mode == 0:
+            if return_scale:
+                raise ValueError('return_scale needs sparsity "time" or "space": the node-wise prox has no group factor')
+            check(self.lib.vch2d_grad_prox(self.ctx, _dp(u), _dp(r), rows, _dp(al), C.byref(o), _dp(out)))
+            return self._sq(out)
+        xx = np.ascontiguousarray(self.x if x is None else x, dtype=np.float64)
+        yy = np.ascontiguousarray(self.y if y is None else y, dtype=np.float64)
+        if mode == 2 and t_hist is None:
+            raise ValueError('sparsity "space" needs t_hist: the weights of the pencil norm')
+        tt = None if t_hist is None else np.ascontiguousarray(t_hist, dtype=np.float64)
+        if xx.shape != (self.Nx + 1,) or yy.shape != (self.Ny + 1,) or (tt is not None and tt.shape != (rows,)):
+            raise ValueError(f"x, y must have Nx+1, Ny+1 entries and t_hist {rows}")
+        s = np.empty((self.B, rows) if mode == 1 else (self.B,) + self.shape)
+        check(self.lib.vch2d_grad_prox_g(self.ctx, _dp(u), _dp(r), rows, _dp(xx), _dp(yy), _dp(tt), _dp(al), C.byref(o), mode,
+                                         _dp(out), _dp(s)))
+        return (self._sq(out), self._sq(s)) if return_scale else self._sq(out)
 
     # -- device-resident PGD -------------------------------------------------------------
-    def pgd_init(self, phi0, phi_T, t_hist, opt, phi_Q=None, ramp=True, T=None, x=None, y=None, u0=None, alpha0=None):
+    def pgd_init(self, phi0, phi_T, t_hist, opt, phi_Q=None, ramp=True, T=None, x=None, y=None, u0=None, alpha0=None,
+                 sparsity=None):
         """Load the problem and evaluate J(u^0); returns J0 [B][5].  `opt`: one parameter object for the whole batch or
         a sequence of B (trajectory b runs with opt[b]: weights, sparsity parameter, box and alpha_max).  `u0` [B][M+1][..]:
         start control (taken as given, not clipped; default zeros).  `alpha0` [B] or a scalar: first step size, capped at
-        each trajectory's alpha_max (default: alpha_max).  A single `opt` without u0 / alpha0 goes through vch2d_pgd_init."""
+        each trajectory's alpha_max (default: alpha_max).  A single `opt` without u0 / alpha0 goes through vch2d_pgd_init.
+        `sparsity`: a name of Engine2D.SPARSITY for the whole batch or a list of B names (vch2d_pgd_init_g: the prox, J4 and
+        the KKT statistic of a "time" / "space" trajectory go by levels / pencils of the control; its box must contain 0);
+        None takes the calls above exactly, every trajectory "full"."""
         phi0, phi_T = self._fld(phi0, "phi0"), self._fld(phi_T, "phi_T_target")
         t_hist = np.ascontiguousarray(t_hist, dtype=np.float64)
         M = int(t_hist.size) - 1
@@ -272,7 +312,7 @@ class Engine2D:
         J0 = np.empty((self.B, 5))
         Tq = float(t_hist[-1] if T is None else T)
         many = isinstance(opt, (list, tuple))
-        if not many and u0 is None and alpha0 is None:
+        if sparsity is None and not many and u0 is None and alpha0 is None:
             o = opt if isinstance(opt, OptParams) else make_opt(opt)
             check(self.lib.vch2d_pgd_init(self.ctx, _dp(phi0), _dp(phi_T), _dp(pq), int(bool(ramp)), Tq, _dp(t_hist), M,
                                           _dp(x), _dp(y), C.byref(o), _dp(J0)))
@@ -282,8 +322,17 @@ class Engine2D:
             uu = None if u0 is None else self._hist(u0, M + 1, "u0")
             al = None if alpha0 is None else np.ascontiguousarray(
                 np.broadcast_to(np.asarray(alpha0, dtype=np.float64), (self.B,)))
-            check(self.lib.vch2d_pgd_init_v(self.ctx, _dp(phi0), _dp(phi_T), _dp(pq), int(bool(ramp)), Tq, _dp(t_hist), M,
-                                            _dp(x), _dp(y), arr, len(seq), _dp(uu), _dp(al), _dp(J0)))
+            if sparsity is None:
+                check(self.lib.vch2d_pgd_init_v(self.ctx, _dp(phi0), _dp(phi_T), _dp(pq), int(bool(ramp)), Tq, _dp(t_hist), M,
+                                                _dp(x), _dp(y), arr, len(seq), _dp(uu), _dp(al), _dp(J0)))
+            else:
+                names = [sparsity] if isinstance(sparsity, str) else list(sparsity)
+                if len(names) not in (1, self.B):
+                    raise ValueError(f"sparsity must be one name or {self.B}, got {len(names)}")
+                modes = np.array([self._mode(s) for s in names], dtype=np.int32)
+                check(self.lib.vch2d_pgd_init_g(self.ctx, _dp(phi0), _dp(phi_T), _dp(pq), int(bool(ramp)), Tq, _dp(t_hist), M,
+                                                _dp(x), _dp(y), arr, len(seq), _dp(uu), _dp(al),
+                                                modes.ctypes.data_as(_lib._I32), len(names), _dp(J0)))
         self._pgd_M = M
         self._base = ("pgd", M, M + 1)
         return J0
@@ -292,7 +341,10 @@ class Engine2D:
         """KKT sparsity statistic `u* = 0 <=> |r*| <= kappa_sparsity` of the resident iterate, counted on the device.
         refresh=True recomputes the adjoint of the resident state first; refresh=False takes the resident r (the adjoint of
         the iterate before the last accepted step).  Returns dict(n_zero, n_small, n_match, total: int64 [B]; pct [B][3],
-        the three percentages of verify_sparsity_condition; stationarity [B] = ||prox_1(u) - u|| / (||u|| + 1e-9))."""
+        the three percentages of verify_sparsity_condition; stationarity [B] = ||prox_1(u) - u|| / (||u|| + 1e-9)).
+        What is counted depends on the trajectory's sparsity mode (pgd_init): "full" counts nodes; "time" counts the levels
+        of the control and "space" its pencils, ||u_g|| < tol and ||r_g|| <= kappa_sparsity in the group's weighted norm,
+        total = M+1 or (Nx+1)(Ny+1); prox_1 is the mode's prox at alpha = 1."""
         cnt = np.zeros((self.B, 4), dtype=np.int64)
         stat = np.empty(self.B)
         check(self.lib.vch2d_pgd_kkt(self.ctx, int(bool(refresh)), float(tol), cnt.ctypes.data_as(C.POINTER(C.c_int64)),
