@@ -793,7 +793,12 @@ int vch2d_pgd_init_g(vch2d_ctx *ctx, const double *phi0, const double *phi_T, co
 /* The stateless seam of the prox: vch2d_grad_prox with the mode `sparsity` for the whole batch.  x [Nx+1], y [Ny+1] (TIME)
  * and t_hist [rows] (SPACE) give the group's weights and may be NULL where the mode does not read them.  scale_out (or NULL)
  * receives s per group, [B][rows] for TIME or [B][Nx+1][Ny+1] for SPACE.  VCH_SPARSITY_FULL is vch2d_grad_prox (scale_out
- * is not written).  VCH_ERR_ARG for a mode outside 0..2 and, in a group mode, for a box that does not contain 0. */
+ * is not written).  VCH_ERR_ARG for a mode outside 0..2 and, in a group mode, for a box that does not contain 0.
+ * x, y and t_hist need only be non-decreasing here (vch2d_pgd_init_g wants t_hist strictly increasing): a repeated node
+ * gives a line of nodes (TIME) or a level (SPACE) of weight zero, which takes the same formulas; what stands there does not
+ * enter its group's norm and is scaled and clipped with the rest of the group.
+ * A group-mode call overwrites the resident u_hist, r_hist, u_trial and the weights W_cost (TIME) or gp_wt (SPACE): do not
+ * interleave it with the iterations of a resident problem on the same context; the next vch2d_pgd_init* restores all five. */
 int vch2d_grad_prox_g(vch2d_ctx *ctx, const double *u, const double *r, int rows, const double *x,
                       const double *y, const double *t_hist, const double *alpha,
                       const vch_opt_params *opt, int sparsity, double *u_out, double *scale_out);

@@ -111,7 +111,10 @@ def test_group_prox_seam_at_rho_over_lambda_1e6(V, engines, mode):
 
 @pytest.mark.parametrize("mode", ["time", "space"])
 def test_group_prox_seam_with_a_weightless_line_of_nodes(V, engines, mode):
-    """An x grid with one node three times: the nodes of that line have W = 0 and carry entries of 50."""
+    """An x grid with one node three times: the nodes of that line have W = 0 and carry entries of 50.  In time mode they
+    drop out of their level's norm.  In space mode the repeated x node weighs nothing in the prox: the pencil kernels read
+    wt only, never W, so this case is an ordinary one there; a level of weight zero (a repeated t) is
+    tests/test_gpu_dirsparse_edges_2d.py::test_seam_on_nodes_and_levels_of_zero_weight[zero_t-...]."""
     Nx, Ny = 70, 20
     case = K.seam_case(mode, Nx, Ny, 17, -1.0, 1.0, triple_x=True)
     assert np.count_nonzero(G.plane_w(case["x"], case["y"]) == 0.0) == Ny + 1
